@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- V-cycle hot path of AgglomerationMultigrid1D on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2-elems E]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2-elems E] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step is one multigrid_v_cycle (V(3,3), alpha = 2/3, src/solvers.jl:19-50) over the
@@ -9,10 +9,19 @@ BASELINE.json config-3/4 hierarchy: DG p=3 fine level (2^E elements) -> AggDG pA
 AggDG (2:1) -> AggDG (2:1), all operators and vectors resident in HBM before the timed region.
 Default E = 24: the size BASELINE.json's north_star / BASELINE.md section 2 quote the 1-vs-8-GPU
 target on ("2^24-element p=3 DG hierarchy"), so that `--gpus 1,2,4,8` is one strong-scaling
-series; at N = 1 the same line also carries the literal config-3 size (2^22) as `config3_2p22` and
-BASELINE config 5's realisable shape (CG p=4 -> 2 -> 1 -> DG p=0) at its stated size,
-2^24 elements, as `config5_2p24_1gpu`.  For N > 1 the hierarchy is partitioned by contiguous element
-range (config 4).  Rank 0 prints ONE JSON line.
+series.  For N > 1 the hierarchy is partitioned by contiguous element range (config 4).  Rank 0
+prints ONE JSON line.
+
+At N = 1 a plain run sets up, warms up, times the K steps and prints the headline figures.
+--full adds everything else, each leg outside the K-step bracket: the roofline and per-kernel
+tables (HIP events), K more steps timed one by one, the multi-cycle entry point, the outer
+solvers, the literal config-3 size (2^22) as `config3_2p22`, BASELINE config 5's realisable shape
+(CG p=4 -> 2 -> 1 -> DG p=0) at its stated size, 2^24 elements, as `config5_2p24_1gpu`,
+the ragged hierarchy, the smoother-only legs and the CPU baseline.
+--dump-outputs DIR (N = 1): after the timed steps, the iterate the last step returned is written
+as DIR/x.npy (float64), all of it up to 2^22 entries, else the entries at a fixed seeded sample
+of 2^22 sorted indices (32 MB).  The inputs depend on the arguments only (zero initial guess,
+synthetic right-hand side), so two builds can be compared output for output.
 
 metric  fine-level DoF-updates/s per V-cycle = N_fine * (nPre + nPost) / t_vcycle, the whole
         cycle timed (the coarsest direct solve included; its share is reported beside it).  `value`
@@ -77,7 +86,24 @@ def parse():
                          "one JSON line with n_gpus N and a `rehearsal` note; not a measurement")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-smoother-bench", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also the roofline / per-kernel tables, the outer solvers and the other sizes, shapes, "
+                         "smoother-only legs and CPU baseline (the --also / --cg / --ragged / --cpu options apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="N = 1: write the iterate of the last timed step to DIR/x.npy (float64, sampled above 2^22 entries)")
     return ap.parse_args()
+
+
+DUMP_MAX_ENTRIES = 2 ** 22      # 32 MB of float64
+
+
+def dump_outputs(directory, x):
+    """DIR/x.npy: x whole, or its entries at a fixed seeded sample of DUMP_MAX_ENTRIES sorted indices"""
+    if x.size > DUMP_MAX_ENTRIES:
+        idx = np.sort(np.random.default_rng(0).choice(x.size, DUMP_MAX_ENTRIES, replace=False))
+        x = x[idx]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "x.npy"), np.ascontiguousarray(x, dtype=np.float64))
 
 
 def cpu_baseline(args, nPre, nPost, alpha):
@@ -574,6 +600,8 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     nPre = nPost = 3
     alpha = 2.0 / 3.0
+    if args.dump_outputs and (args.gpus > 1 or os.environ.get("AGGMG_FORCE_DIST") == "1"):
+        raise SystemExit("--dump-outputs: single-GPU runs only")
     if args.gpus > 1 and args.rehearse_threads:
         import threading
         from agglomerationmultigrid1d_amd import distributed as dist_mg
@@ -612,10 +640,11 @@ def main():
 
     ctx = mg.Context(local_rank)
 
-    def run_size(E, steps, warmup, profile, host_entry=False):
-        """build the hierarchy at 2^E fine elements, run `steps` timed V-cycles and the same count
-        through the multi-cycle entry point; host_entry: also time the host-pointer entry point
-        (aggmg_vcycle: x0, b in and x out over PCIe on every call) -- the PCIe-inclusive rate"""
+    def run_size(E, steps, warmup, profile, host_entry=False, full=True, dump=None):
+        """build the hierarchy at 2^E fine elements, run `steps` timed V-cycles and, full, the same count
+        one by one and through the multi-cycle entry point, and the outer solvers; host_entry: also time
+        the host-pointer entry point (aggmg_vcycle: x0, b in and x out over PCIe on every call) -- the
+        PCIe-inclusive rate; dump: write the last timed step's iterate there (dump_outputs)"""
         n = 2 ** E
         t0 = time.perf_counter()
         U = UniformDgAggHierarchy(n, p=args.p, pAgg=1, ratios=(4, 2, 2))
@@ -652,6 +681,11 @@ def main():
         if profile:
             ctx.profile_enable(False)
             prof_dom = ctx.profile_collect()
+        if dump:
+            dump_outputs(dump, state[0].download())
+        if not full:
+            H.free()
+            return dict(N=N, dt=dt, bytes_model=bytes_model, level_sizes=level_sizes, t_gen=t_gen, t_lib=t_lib)
         # median of >= 20 repetitions, each timed on its own
         per = [_time_loop(ctx, run, 1) for _ in range(steps)]
         if profile:
@@ -744,13 +778,39 @@ def main():
                     bytes_model=bytes_model, level_sizes=level_sizes, t_gen=t_gen, t_lib=t_lib,
                     coarse_info=info, outer=outer, pcie=pcie, comp_rw=comp_rw, comp_all=comp_all, paired=paired)
 
-    R = run_size(args.log2_elems, args.steps, args.warmup, True)
-    N, dt, dt_loop, prof, bytes_model = R["N"], R["dt"], R["dt_loop"], R["prof"], R["bytes_model"]
+    R = run_size(args.log2_elems, args.steps, args.warmup, args.full, full=args.full, dump=args.dump_outputs)
+    N, dt, bytes_model = R["N"], R["dt"], R["bytes_model"]
     level_sizes = R["level_sizes"]
 
     ms_per_step = 1e3 * dt / args.steps
     value = N * (nPre + nPost) * args.steps / dt
     vcycle_bytes = sum(l['vcycle'] for l in bytes_model)
+    out = {
+        "metric": "fine_level_dof_updates_per_s_per_vcycle",
+        "value": value,
+        "unit": "DoF-updates/s",
+        "n_gpus": 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": f"config 3/4 hierarchy: V(3,3) cycle, alpha=2/3, DG p={args.p} n=2^{args.log2_elems} -> AggDG "
+                               f"pAgg=1 4:1 -> 2:1 -> 2:1 (4 levels), uniform mesh, Neumann/Dirichlet, CDir=1000n"
+                               + (" (north-star 1-vs-8-GPU size; config 3's own 2^22 in config3_2p22)"
+                                  if args.log2_elems == 24 else ""),
+                   "fine_dofs": N, "level_dofs": level_sizes, "nPre": nPre, "nPost": nPost,
+                   "parallelism": "single GPU"},
+        "achieved_algorithmic_GBs_vcycle": vcycle_bytes * args.steps / dt / 1e9,
+        "setup_s": R["t_gen"] + R["t_lib"], "setup_generator_s": R["t_gen"], "setup_library_s": R["t_lib"],
+    }
+    if not args.full:
+        print(json.dumps(out))
+        return
+    dt_loop, prof = R["dt_loop"], R["prof"]
     dom = list(R["prof_dom"].items())[0]   # the fine-level fused-down launch, timed inside the region
     (dkind, dlevel), (dms, dcnt) = dom
     lm = bytes_model[dlevel]
@@ -772,32 +832,14 @@ def main():
                 v_["physical_frac"] = t_ / (v_["ms_per_launch"] * 1e-3) / 1e9 / HBM_PEAK_GBS
     coarse_dev = [v["ms_per_launch"] for k, v in kern_ms.items() if k.startswith("coarse_")]
     coarse_step_ms = coarse_dev[0] if coarse_dev else 0.0
-    out = {
-        "metric": "fine_level_dof_updates_per_s_per_vcycle",
-        "value": value,
-        "unit": "DoF-updates/s",
-        "n_gpus": 1,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "median_ms_per_step": 1e3 * statistics.median(R["per"]),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": f"config 3/4 hierarchy: V(3,3) cycle, alpha=2/3, DG p={args.p} n=2^{args.log2_elems} -> AggDG "
-                               f"pAgg=1 4:1 -> 2:1 -> 2:1 (4 levels), uniform mesh, Neumann/Dirichlet, CDir=1000n"
-                               + (" (north-star 1-vs-8-GPU size; config 3's own 2^22 in config3_2p22)"
-                                  if args.log2_elems == 24 else ""),
-                   "fine_dofs": N, "level_dofs": level_sizes, "nPre": nPre, "nPost": nPost,
-                   "parallelism": "single GPU",
-                   "sizes_by_leg": {"value / roofline": f"2^{args.log2_elems} fine elements",
-                                    "config3_2p22": f"2^{args.also_log2_elems}" if args.also_log2_elems else None,
-                                    "cpu_baseline": None if args.no_cpu_baseline else f"2^{args.cpu_log2_elems or args.log2_elems} fine elements",
-                                    "config5": f"2^{args.cg_log2_elems}" if args.cg_log2_elems else None,
-                                    "smoother_only (config 2)": "2^20", "ragged": f"2^{args.ragged_log2_elems}" if args.ragged_log2_elems else None}},
-        "achieved_algorithmic_GBs_vcycle": vcycle_bytes * args.steps / dt / 1e9,
+    out["median_ms_per_step"] = 1e3 * statistics.median(R["per"])
+    out["config"]["sizes_by_leg"] = {
+        "value / roofline": f"2^{args.log2_elems} fine elements",
+        "config3_2p22": f"2^{args.also_log2_elems}" if args.also_log2_elems else None,
+        "cpu_baseline": None if args.no_cpu_baseline else f"2^{args.cpu_log2_elems or args.log2_elems} fine elements",
+        "config5": f"2^{args.cg_log2_elems}" if args.cg_log2_elems else None,
+        "smoother_only (config 2)": "2^20", "ragged": f"2^{args.ragged_log2_elems}" if args.ragged_log2_elems else None}
+    out.update({
         "vcycles_loop": {"value": N * (nPre + nPost) * args.steps / dt_loop, "unit": "DoF-updates/s",
                          "ms_per_cycle": 1e3 * dt_loop / args.steps,
                          "note": f"aggmg_vcycles_dev({args.steps} cycles): same arithmetic as {args.steps} separate "
@@ -819,8 +861,7 @@ def main():
                               "+ restriction; kept for continuity with r01-r03, not a bound"),
         "kernels": kern_ms,
         "two_level_launches": {kd: [f"levels {k + 1}+{k + 2}" for k in v] for kd, v in R["paired"].items()},
-        "setup_s": R["t_gen"] + R["t_lib"], "setup_generator_s": R["t_gen"], "setup_library_s": R["t_lib"],
-    }
+    })
     if args.also_log2_elems and args.also_log2_elems != args.log2_elems:
         R2 = run_size(args.also_log2_elems, args.steps, args.warmup, False, host_entry=True)
         out[f"config3_2p{args.also_log2_elems}"] = {

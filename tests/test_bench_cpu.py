@@ -52,3 +52,29 @@ def test_argument_surface_of_the_driver_contract(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "5", "--warmup", "2"])
     a = b.parse()
     assert (a.gpus, a.steps, a.warmup) == (8, 5, 2) and a.cpu_log2_elems == 0    # cpu_baseline at the size of `value`
+
+
+def test_plain_run_is_lean_by_default_and_full_is_an_option(monkeypatch):
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 7
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out_dir"])
+    a = b.parse()
+    assert a.full and a.dump_outputs == "out_dir"
+
+
+def test_dump_outputs_writes_a_fixed_float64_sample_within_64_mb(tmp_path):
+    import numpy as np
+    b = _bench()
+    small = np.arange(1000, dtype=np.float64)
+    b.dump_outputs(str(tmp_path / "s"), small)
+    got = np.load(tmp_path / "s" / "x.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small)          # small outputs: whole
+    big = np.arange(2 * b.DUMP_MAX_ENTRIES, dtype=np.float64)
+    b.dump_outputs(str(tmp_path / "a"), big)
+    b.dump_outputs(str(tmp_path / "b"), big)
+    xa, xb = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert xa.dtype == np.float64 and xa.size == b.DUMP_MAX_ENTRIES and xa.nbytes <= 64 * 2**20
+    assert np.array_equal(xa, xb)                                            # the same entries every run
+    assert np.all(np.diff(xa) > 0) and np.array_equal(big[xa.astype(np.int64)], xa)

@@ -54,3 +54,43 @@ def test_compulsory_bytes_of_standalone_launches(mg):
     assert mg.smoother_launch_bytes(op2, J, "sweeps") == (12 * nnz + 4 * (N + 1) + 24 * N, 8 * N)
     assert mg.smoother_launch_bytes(op2, None, "residual") == (12 * nnz + 4 * (N + 1) + 16 * N, 8 * N)
     assert np.isfinite(nnz)
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_the_last_iterate(mg, tmp_path):
+    """`bench.py --gpus 1` without --full: the headline line only, and --dump-outputs writes the iterate the last timed
+    step returned -- here (2^12 fine elements, under the sampling threshold) all of it, equal to warmup + steps V-cycles
+    of the same hierarchy from a zero guess"""
+    import json
+    import os
+    import subprocess
+    import sys
+    from agglomerationmultigrid1d_amd.uniform import UniformDgAggHierarchy, build_device_hierarchy
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    E, steps, warmup = 12, 3, 2
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--log2-elems", str(E), "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "fine_level_dof_updates_per_s_per_vcycle" and d["unit"] == "DoF-updates/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f64" and d["steps"] == steps and d["warmup"] == warmup
+    assert d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["fine_dofs"] * 6 / (d["ms_per_step"] * 1e-3)) <= 1e-9 * d["value"]
+    for k in ("roofline", "kernels", "median_ms_per_step", "outer_solvers_to_1e-8", "cpu_baseline", "smoother_only"):
+        assert k not in d, k
+    x = np.load(tmp_path / "x.npy")
+    U = UniformDgAggHierarchy(2 ** E, p=3, pAgg=1, ratios=(4, 2, 2))
+    ctx = mg.Context(0)
+    H = build_device_hierarchy(U, ctx)
+    b = U.rhs()
+    assert x.dtype == np.float64 and x.shape == b.shape == (d["config"]["fine_dofs"],)
+    bd = ctx.to_device(b)
+    xa, xb = ctx.to_device(np.zeros(len(b))), ctx.alloc(len(b))
+    for _ in range(warmup + steps):
+        H.vcycle_dev(xa, bd, xb, 3, 3, 2.0 / 3.0)
+        xa, xb = xb, xa
+    ref = xa.download()
+    H.free()
+    assert np.max(np.abs(x - ref)) <= 1e-12 * np.max(np.abs(ref)), float(np.max(np.abs(x - ref)))

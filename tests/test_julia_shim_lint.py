@@ -7,13 +7,15 @@ checked here, on the CPU:
     (Handle / Ptr{..} / Ref{..} <-> pointer of the matching pointee, Int64 <-> int64_t, Cint <-> int, Float64 <-> double);
   * every reference function the shim gives a device method is imported from the parent module (a `function f` on a
     name that is not imported would define a new, unrelated AggMGHip.f) and keeps the reference's positional arity,
-    keyword names and keyword defaults (src/solvers.jl:19-20,63,84,116-117,189-191; src/smoother.jl:6,88,142); when
-    /root/reference is present the table of those signatures is itself checked against the reference's text;
+    keyword names and keyword defaults (src/solvers.jl:19-20,63,84,116-117,189-191; src/smoother.jl:6,88,142); the
+    table of those signatures is itself checked against what this file's parser read from the reference's text
+    (tests/golden/reference_signatures.json);
   * the Julia and the Python mirror agree on the defaults of the keywords they add (`exact`, `check_every`);
   * every ccall that passes a DeviceVector's address (`v.p`) stands under `GC.@preserve v` (the r03 use-after-free
     rule of api.DeviceVector.ptr, mirrored).
 """
 import inspect
+import json
 import os
 import re
 
@@ -192,7 +194,7 @@ def norm_default(s):
 
 
 # The reference's signatures on this path: name -> list of (positional count, {keyword: default}) with the
-# file:line each one stands at.  Checked against the reference's text below when it is present.
+# file:line each one stands at.  Checked below against the signatures read from the reference's text.
 REFERENCE_SIGNATURES = {
     "multigrid_v_cycle": [("src/solvers.jl", 19, 3, {"nPre": "3", "nPost": "3", "alpha": "2.0/3.0"})],
     "multigrid": [("src/solvers.jl", 116, 5, {})],
@@ -282,16 +284,16 @@ def test_extended_functions_are_imported_and_keep_the_reference_signature(shim):
 
 
 def test_reference_signature_table_matches_the_reference_text():
-    ref = "/root/reference"
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present (GPU box)")
+    # the signatures as this file's parser read them from the reference's text (tests/golden/make_reference_signatures.py)
+    with open(os.path.join(ROOT, "tests", "golden", "reference_signatures.json")) as f:
+        read = json.load(f)
+    assert sorted(read) == sorted(REFERENCE_SIGNATURES)
     for name, sigs in REFERENCE_SIGNATURES.items():
         for path, line, npos, kws in sigs:
-            txt = open(os.path.join(ref, path)).read()
-            defs = [d for d in jl_functions(txt) if d[0] == name and d[3] == line]
+            defs = [d for d in read[name] if d["path"] == path and d["line"] == line]
             assert defs, f"{path}:{line}: no `function {name}` there"
-            _, pos, got, _ = defs[0]
-            assert len(pos) == npos, (name, pos)
+            got = defs[0]["keywords"]
+            assert defs[0]["npos"] == npos, (name, defs[0]["npos"])
             assert {k: norm_default(v) for k, v in got.items()} == {k: norm_default(v) for k, v in kws.items()}, (name, got)
 
 
