@@ -19,6 +19,7 @@ OPT_COARSE_CHUNK_LOG2 = 2
 OPT_DETECT_CHAIN = 3
 OPT_PAIR_LEVELS = 4
 OPT_MG_CHECKPOINT = 5
+OPT_SYMMETRIC_RESIDUAL = 6
 PROFILE_NTAGS = 256
 KIND_FUSED_DOWN, KIND_FUSED_UP, KIND_SMOOTH, KIND_RESIDUAL, KIND_RESTRICT, KIND_PROLONG, \
     KIND_JACOBI, KIND_BLOCK_APPLY, KIND_COARSE, KIND_FUSED_MID = range(10)
@@ -139,6 +140,7 @@ SYMBOLS = {
     "aggmg_host_alloc": (c_int, [_P, c_int64, POINTER(_P)]),
     "aggmg_host_free": (c_int, [_P, _P]),
     "aggmg_hier_level_paired": (c_int, [_P, _P, c_int, c_int, POINTER(c_int)]),
+    "aggmg_hier_level_sym_residual": (c_int, [_P, _P, c_int, POINTER(c_int)]),
     "aggmg_hier_launch_bytes": (c_int, [_P, _P, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "aggmg_smoother_launch_bytes": (c_int, [_P, _P, _P, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "aggmg_hier_coarse_info": (c_int, [_P, _P, POINTER(c_int), POINTER(c_int), POINTER(c_double)]),

@@ -806,6 +806,17 @@ class MeshHierarchy:
             out.append(_lib.LEVEL_KIND_NAMES[v.value])
         return out
 
+    def sym_residual_levels(self):
+        """levels whose explicit residual reads the lossless symmetric form of the operator's entries (C ABI
+        aggmg_hier_level_sym_residual, AGGMG_OPT_SYMMETRIC_RESIDUAL)"""
+        out = []
+        for k in range(self.nlevels):
+            v = ctypes.c_int(0)
+            self.ctx.check(self.ctx.lib.aggmg_hier_level_sym_residual(self.ctx.handle, self.handle, k, ctypes.byref(v)))
+            if v.value:
+                out.append(k)
+        return out
+
     def paired_levels(self, nsweeps=3, direction="down"):
         """levels k whose launch also carries level k + 1 (C ABI aggmg_hier_level_paired), as the descent walks the
         hierarchy (pairs taken from the fine side) or, direction='up', as the ascent does (from the coarse side)"""

@@ -158,6 +158,9 @@ extern "C" int aggmg_set_option(aggmg_ctx* ctx, int option, int value) {
     case AGGMG_OPT_MG_CHECKPOINT:
       ctx->mg_checkpoint = value != 0;
       return AGGMG_OK;
+    case AGGMG_OPT_SYMMETRIC_RESIDUAL:
+      ctx->sym_residual = value != 0;
+      return AGGMG_OK;
   }
   return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_set_option: unknown option");
 }
@@ -591,6 +594,9 @@ static int launch_btd_t(aggmg_ctx* ctx, FusedArgs a, int halo, const TileSel& se
                      (chk ? ((size_t)2 * (T::NT / 64) + (CMP ? (size_t)T::NT * T::NS * (M + 1) : 0)) * sizeof(double) : 0);
   constexpr bool kGrp = (CMP && (M == 2 || M == 4 || M == 8)) || (!CMP && (M == 2 || M == 4));
   const bool sym = kGrp && a.lv.bsym;
+  // the lossless symmetric form of the residual's entries: block-Jacobi launches that form the explicit residual
+  constexpr bool kSres = kGrp && CMP && M <= 4;
+  const bool sres = kSres && a.lv.dup && !a.gs && !chk && a.do_residual && (a.r_out || a.lf_out);
   // instantiations per (M, CMP): symmetric packing x (block-Jacobi / red-black GS / block-Jacobi with checkpoint)
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a);
@@ -601,6 +607,8 @@ static int launch_btd_t(aggmg_ctx* ctx, FusedArgs a, int halo, const TileSel& se
         go(btd_fused_kernel<M, CMP, T::NS, true, T::NT, true>);
       else if (chk)
         go(btd_fused_kernel<M, CMP, T::NS, true, T::NT, false, true>);
+      else if (sres)
+        go(btd_fused_kernel<M, CMP, T::NS, true, T::NT, false, false, kSres>);
       else
         go(btd_fused_kernel<M, CMP, T::NS, true, T::NT, false>);
       HIPCHK(hipGetLastError());
@@ -660,7 +668,7 @@ static int btd_tile_elems(const BtdDev& b) {
 static FusedArgs btd_args(const BtdDev& b) {
   FusedArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.lv = BtdLevel{b.binv, b.dblk, b.bsym, b.scol, b.pcol, b.qrow, b.sub, b.sup, b.P, b.Q, b.ne, b.c_sub, b.r_sup};
+  a.lv = BtdLevel{b.binv, b.dblk, b.bsym, b.dup, b.corr, b.scol, b.pcol, b.qrow, b.sub, b.sup, b.P, b.Q, b.ne, b.c_sub, b.r_sup};
   return a;
 }
 
@@ -1641,6 +1649,14 @@ static int launch_pair_up(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPost, doubl
 extern "C" int aggmg_hier_level_paired(aggmg_ctx* ctx, const aggmg_hier* h, int level, int nsweeps, int* paired) {
   if (!ctx || !h || !paired) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_paired: NULL argument");
   *paired = pair_ok(ctx, h, level, nsweeps) ? 1 : 0;
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_hier_level_sym_residual(aggmg_ctx* ctx, const aggmg_hier* h, int level, int* on) {
+  if (!ctx || !h || !on) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_sym_residual: NULL argument");
+  if (level < 0 || level >= (int)h->lv.size()) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_sym_residual: level out of range");
+  const Level& l = h->lv[level];
+  *on = (l.S && l.S->btd && l.S->btd->dup) ? 1 : 0;
   return AGGMG_OK;
 }
 

@@ -43,6 +43,7 @@ struct aggmg_ctx {
   bool detect_chain = true; // AGGMG_OPT_DETECT_CHAIN
   bool mg_checkpoint = [] { const char* e = std::getenv("AGGMG_MG_CHECKPOINT"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_MG_CHECKPOINT
   bool pair_levels = [] { const char* e = std::getenv("AGGMG_PAIR"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_PAIR_LEVELS
+  bool sym_residual = [] { const char* e = std::getenv("AGGMG_SYM_RESIDUAL"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_SYMMETRIC_RESIDUAL
   int profiling = 0;  // 0 off, 1 every launch, 2 only the fine-level fused-down launch (dominant kernel)
   std::vector<ProfEvent> prof;
   std::vector<hipEvent_t> ev_pool;
@@ -105,10 +106,15 @@ struct BtdDev {
   int c_sub = 0, r_sup = 0;
   double *binv = nullptr, *dblk = nullptr, *scol = nullptr, *pcol = nullptr, *qrow = nullptr;
   double* bsym = nullptr;  // packed symmetric inverses (replaces binv + pcol in the kernels) or null
+  // lossless symmetric form of the explicit residual's entries (compressed couplings, m <= 4, with bsym): the upper
+  // triangle of D_e row-owned, one word of int8 corrections per row (setup_kernels.hpp, btd_sym_residual_kernel); or null
+  double* dup = nullptr;
+  uint32_t* corr = nullptr;
   double *sub = nullptr, *sup = nullptr, *P = nullptr, *Q = nullptr;
   ~BtdDev() {
-    for (double* p : {binv, dblk, scol, pcol, qrow, bsym, sub, sup, P, Q})
+    for (double* p : {binv, dblk, scol, pcol, qrow, bsym, dup, sub, sup, P, Q})
       if (p) (void)hipFree(p);
+    if (corr) (void)hipFree(corr);
   }
 };
 

@@ -658,6 +658,12 @@ struct BtdLevel {
   // sub-diagonal column of element e is the super-diagonal row of element e-1
   // (scol_e = qrow_{e-1}), so pcol_e = B_e^{-1} qrow_{e-1} is formed in the kernel
   const double* bsym;
+  // (with bsym, compressed couplings, M <= 4; else null) the explicit residual's entries in lossless symmetric form:
+  // dup [ne][M(M+1)/2] the upper triangle of D_e, row-owned; corr [N] int8 corrections of row i's lower entries
+  // D[i][j < i] (byte j) and of its coupling entry scol_e[i] (byte 3) against their mirrors D[j][i] and qrow_{e-1}[i]
+  // (setup_kernels.hpp, btd_sym_residual_kernel)
+  const double* dup;
+  const uint32_t* corr;
   const double *scol, *pcol, *qrow;
   const double *sub, *sup, *P, *Q;
   int64_t ne;
@@ -751,6 +757,14 @@ __device__ __forceinline__ int64_t fused_tile(const FusedArgs& a) {
 #define AGGMG_ST(p, v) ((p) = (v))
 #endif
 
+// lossless symmetric form of the residual's entries (BtdLevel::dup / corr): an entry is its mirror's fp64 bit pattern
+// plus a signed difference in units of the last place -- exact, modulo 2^64, for any pair whose difference fits the
+// int8; kSymResidualEscape marks the entries read from the full arrays instead (the difference does not fit, or the
+// level's first element, whose coupling has no mirror in the level's arrays)
+constexpr int kSymResidualEscape = -128;
+__device__ __forceinline__ double sym_residual_decode(double mirror, int delta) {
+  return __longlong_as_double((long long)((unsigned long long)__double_as_longlong(mirror) + (unsigned long long)(long long)delta));
+}
 // sum / broadcast inside the group of W consecutive lanes holding one element's rows (W = 2^k), no LDS traffic, no
 // barrier.  W = 2, 4: the group lies inside a quad of lanes, so the exchange is a DPP quad permutation -- a VALU move
 // modifier -- instead of ds_bpermute, which goes through the LDS pipe and costs its latency twice per sweep in the
@@ -792,6 +806,33 @@ __device__ __forceinline__ double group_bcast(double v, int j) {
   }
 }
 
+// row i of element e (the element's M rows in the M lanes of one lane group, all of them active): D_e[i][:] into dk,
+// the coupling entry scol_e[i] into sc.  Lane i reads only its own run D[i][i..M-1] of the packed triangle; a lower
+// entry D[i][j] is rebuilt from lane j's D[j][i], moved across the group by DPP (no LDS, no memory traffic).  The
+// coupling entry's mirror q_{e-1}[i] lies in lines the tile has loaded already; the escape is always taken at e = 0.
+template <int M>
+__device__ __forceinline__ void sym_residual_row(const BtdLevel& lv, int64_t e, int i, double (&dk)[M], double& sc) {
+  constexpr int T = M * (M + 1) / 2;
+  const int64_t row = e * M + i;
+  const uint32_t w = lv.corr[row];
+  const double* du = lv.dup + e * T + i * M - (i * (i - 1)) / 2 - i;   // du[j] = D[i][j], j >= i
+#pragma unroll
+  for (int j = 0; j < M; ++j) dk[j] = j >= i ? du[j] : 0.0;
+#pragma unroll
+  for (int j = 0; j < M - 1; ++j) {
+    double mir = 0.0;   // D[j][i], from lane j
+#pragma unroll
+    for (int c = j + 1; c < M; ++c) {
+      const double v = group_bcast<M>(dk[c], j);
+      if (i == c) mir = v;
+    }
+    const int d = (int)(int8_t)(w >> (8 * j));
+    if (j < i) dk[j] = d == kSymResidualEscape ? lv.dblk[row * M + j] : sym_residual_decode(mir, d);
+  }
+  const int dc = (int)(int8_t)(w >> 24);
+  sc = dc == kSymResidualEscape ? lv.scol[row] : sym_residual_decode(lv.qrow[row - M], dc);
+}
+
 // GS: red-black block Gauss-Seidel sweeps (FusedArgs::gs gives the colour order) instead of
 // block-Jacobi ones -- a compile-time variant, so the block-Jacobi kernel carries none of it
 // (AGGMG_CHK_WAVES: minimum waves per SIMD asked of the checkpoint variant; measured 7 and 6 -- spills into the sweep
@@ -799,7 +840,10 @@ __device__ __forceinline__ double group_bcast(double v, int j) {
 #ifndef AGGMG_CHK_WAVES
 #define AGGMG_CHK_WAVES 1
 #endif
-template <int M, bool CMP, int NS, bool SYM = false, int NT = kThreads, bool GS = false, bool CHK = false>
+// SR: the explicit residual reads the lossless symmetric form (BtdLevel::dup / corr; the launcher picks this variant only
+// for block-Jacobi launches with an explicit residual on a level that has the form) -- a variant of its own, so the
+// launches without that residual (the ascent) keep the smaller kernel
+template <int M, bool CMP, int NS, bool SYM = false, int NT = kThreads, bool GS = false, bool CHK = false, bool SR = false>
 __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kernel(FusedArgs a) {
   static_assert(!SYM || M == 2 || M == 4 || M == 8, "symmetric packing needs the lane-group path");
   static_assert(!(CHK && GS), "the checkpoint is for block-Jacobi launches");
@@ -809,6 +853,12 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
   // dense off-diagonal blocks of a symmetric operator: only the super-diagonal blocks are read
   // (Sub_e = Sup_{e-1}'), P = B^{-1}Sub and Q = B^{-1}Sup are formed in registers at load time
   constexpr bool DSYM = !CMP && SYM;
+  // symmetric-packed compressed levels with M <= 4: the explicit residual reads the lossless symmetric form of its
+  // entries (BtdLevel::dup / corr) -- the coupling entry's mirror is q_{e-1}[i], which the tile has loaded already.
+  // Not the checkpoint variant: it reads the entries once per launch anyway (then from its LDS stash), and the decode
+  // would cost it a wave per SIMD (89 -> 111 VGPRs); nor the Gauss-Seidel one
+  constexpr bool SRES = SR && SYM && GRP && M <= 4 && !CHK && !GS;
+  const bool sres = SRES && a.lv.dup != nullptr;
   constexpr int EPS = NT / M;  // elements per slab
   constexpr int TE = EPS * NS;       // elements per tile (owned + halos)
   extern __shared__ double lds[];
@@ -1035,15 +1085,25 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
   // over the diagonal blocks (2.1 GB at 2^24 elements p = 3)
   [[maybe_unused]] double* const stash = lds + 2 * (TE + 2) * M + 2 * (NT / 64);
   [[maybe_unused]] bool stashed = false;
+  // (CMP) the row's entries from memory: the full arrays, or (sres) the lossless symmetric form -- the same bits
+  [[maybe_unused]] auto load_row = [&](int s, int64_t row, double (&dk)[M], double& sc) {
+    if constexpr (SRES) {
+      if (sres) {
+        sym_residual_row<M>(a.lv, row / M, i, dk, sc);
+        return;
+      }
+    }
+    sc = a.lv.scol[row];
+#pragma unroll
+    for (int j = 0; j < M; ++j) dk[j] = a.lv.dblk[row * M + j];
+  };
   [[maybe_unused]] auto row_entries = [&](int s, int64_t row, double (&dk)[M], double& sc) {
     if (CHK && CMP && stashed) {
 #pragma unroll
       for (int j = 0; j < M; ++j) dk[j] = stash[(s * (M + 1) + j) * NT + tid];
       sc = stash[(s * (M + 1) + M) * NT + tid];
     } else {
-      sc = a.lv.scol[row];
-#pragma unroll
-      for (int j = 0; j < M; ++j) dk[j] = a.lv.dblk[row * M + j];
+      load_row(s, row, dk, sc);
       if constexpr (CHK && CMP) {
 #pragma unroll
         for (int j = 0; j < M; ++j) stash[(s * (M + 1) + j) * NT + tid] = dk[j];
@@ -1211,9 +1271,7 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
           if constexpr (CHK) {
             row_entries(s, row, dk, sc);
           } else {
-            sc = a.lv.scol[row];
-#pragma unroll
-            for (int j = 0; j < M; ++j) dk[j] = a.lv.dblk[row * M + j];
+            load_row(s, row, dk, sc);
           }
           t += sc * um[a.lv.c_sub];
 #pragma unroll

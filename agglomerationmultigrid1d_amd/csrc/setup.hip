@@ -436,6 +436,26 @@ int setup_block_smoother(aggmg_ctx* ctx, aggmg_smoother* sm, const int64_t* bloc
           if (!a1) {
             CHECK(dalloc(ctx, &b->bsym, nb * (int64_t)(m * (m + 1) / 2), false));
             LAUNCH(btd_sym_pack_kernel, nb, nb, m, (const double*)b->binv, b->bsym);
+            if (cmp && m <= 4 && ctx->sym_residual) {
+              // the explicit residual's entries as half + exact int8 corrections (AGGMG_OPT_SYMMETRIC_RESIDUAL); a level
+              // where more than 1 / 1024 of the corrections overflow keeps the full arrays only
+              const int T = m * (m + 1) / 2;
+              Flags over;
+              CHECK(over.init(ctx, 1));
+              CHECK(dalloc(ctx, &b->dup, nb * (int64_t)T, false));
+              CHECK(dalloc(ctx, &b->corr, N, false));
+              LAUNCH(btd_sym_residual_kernel, N, nb, m, (const double*)b->dblk, (const double*)b->scol,
+                     (const double*)b->qrow, b->dup, b->corr, over.d);
+              int nover = 0;
+              CHECK(over.read(ctx, &nover));
+              const int64_t entries = nb * (int64_t)(m * (m - 1) / 2 + m);   // lower entries of D + couplings
+              if ((int64_t)nover * 1024 > entries) {
+                (void)hipFree(b->dup);
+                (void)hipFree(b->corr);
+                b->dup = nullptr;
+                b->corr = nullptr;
+              }
+            }
           }
         }
         if (cmp) {  // the dense off-diagonal blocks are not read by the compressed kernels

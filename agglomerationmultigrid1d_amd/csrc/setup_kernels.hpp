@@ -476,6 +476,51 @@ __global__ __launch_bounds__(kSetupThreads) void btd_sym_pack_kernel(int64_t ne,
     for (int j = i; j < m; ++j) bsym[e * T + q++] = 0.5 * (binv[(e * m + i) * m + j] + binv[(e * m + j) * m + i]);
 }
 
+// lossless symmetric form of the explicit residual's row entries (compressed couplings, m <= 4; BtdDev::dup / corr):
+//   dup[e][T]  the upper triangle of D_e, row-owned (row i's entries D[i][i..m-1] contiguous at i*m - i(i-1)/2)
+//   corr[row]  byte j < i: D[i][j] - D[j][i] as the int64 difference of their bit patterns (units in the last place);
+//              byte 3: scol_e[i] - qrow_{e-1}[i] likewise.  kSymResidualEscape (kernels.hpp): "read the full array" --
+//              the pair does not fit an int8, or (coupling of a level's first element) there is no mirror in the level's
+//              arrays.
+// The decode mirror + delta of the bit patterns (modulo 2^64, sym_residual_decode) gives every entry's fp64 bits back
+// exactly.  over[0]
+// counts the entries that needed the escape although they have a mirror.  One thread per row.
+__device__ __forceinline__ int sym_residual_delta(double v, double mirror) {
+  const int64_t d = (int64_t)((uint64_t)__double_as_longlong(v) - (uint64_t)__double_as_longlong(mirror));
+  return (d > kSymResidualEscape && d <= 127) ? (int)d : kSymResidualEscape;
+}
+__global__ __launch_bounds__(kSetupThreads) void btd_sym_residual_kernel(int64_t ne, int m, const double* __restrict__ dblk,
+                                                                         const double* __restrict__ scol,
+                                                                         const double* __restrict__ qrow,
+                                                                         double* __restrict__ dup, uint32_t* __restrict__ corr,
+                                                                         int* __restrict__ over) {
+  const int64_t row = (int64_t)blockIdx.x * kSetupThreads + threadIdx.x;
+  if (row >= ne * m) return;
+  const int64_t e = row / m;
+  const int i = (int)(row - e * m);
+  const int T = m * (m + 1) / 2;
+  double* du = dup + e * T + i * m - (i * (i - 1)) / 2 - i;   // du[j] = D[i][j], j >= i
+  uint32_t w = 0;
+  int nover = 0;
+  for (int j = 0; j < m; ++j) {
+    if (j >= i) {
+      du[j] = dblk[row * m + j];
+    } else {
+      const int d = sym_residual_delta(dblk[row * m + j], dblk[(e * m + j) * m + i]);
+      nover += d == kSymResidualEscape;
+      w |= (uint32_t)(uint8_t)(int8_t)d << (8 * j);
+    }
+  }
+  int dc = kSymResidualEscape;
+  if (e > 0) {
+    dc = sym_residual_delta(scol[row], qrow[(e - 1) * m + i]);
+    nover += dc == kSymResidualEscape;
+  }
+  w |= (uint32_t)(uint8_t)(int8_t)dc << 24;
+  corr[row] = w;
+  if (nover) atomicAdd(over, nover);
+}
+
 // ------------------------------------------------------------------------------------------
 // structured transfers of block-tridiagonal levels
 // ------------------------------------------------------------------------------------------

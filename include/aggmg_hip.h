@@ -84,6 +84,16 @@ int aggmg_synchronize(aggmg_ctx* ctx);
  * again up to that sweep).  Fused block-tridiagonal and point-Jacobi CG-chain fine levels / smoothers; others take the
  * separate launches. */
 #define AGGMG_OPT_MG_CHECKPOINT 5
+/* AGGMG_OPT_SYMMETRIC_RESIDUAL (default 1; environment AGGMG_SYM_RESIDUAL=0 makes the default 0): on a symmetric-packed
+ * level with compressed couplings and blocks of 2 or 4 rows, the explicit residual of the fused kernel reads the upper
+ * triangle of each diagonal block plus one 32-bit word of int8 corrections per row instead of the full block and the
+ * sub-diagonal column: every lower entry, and every coupling entry, is its mirror's bit pattern plus the exact
+ * difference in units of the last place, so the entries and all results are bit for bit those of the full arrays
+ * (an entry whose difference does not fit is read from the full array; a level where more than 1 / 1024 of them do not
+ * fit keeps the full arrays).  Smoothers set up afterwards; aggmg_hier_level_sym_residual reports the levels.  At 2^24
+ * p = 3: 64 of the fine descent's 404 bytes per element; the descent 9 % faster, the V-cycle 2 - 4 % (DESIGN.md
+ * section 5). */
+#define AGGMG_OPT_SYMMETRIC_RESIDUAL 6
 int aggmg_set_option(aggmg_ctx* ctx, int option, int value);
 /* Raw device memory owned by the context's device (plumbing for harnesses without torch, and the storage of the
  * Julia shim's DeviceVector).  aggmg_dev_alloc returns ZEROED memory: a fresh vector is the zero initial guess of
@@ -340,6 +350,9 @@ int aggmg_hier_level_kind(aggmg_ctx* ctx, const aggmg_hier* h, int level, int* k
  * the separate launches.  The launch is then attributed to `level` (profile tags, aggmg_hier_launch_bytes of both
  * levels apply).  AGGMG_OPT_PAIR_LEVELS switches the pairing off. */
 int aggmg_hier_level_paired(aggmg_ctx* ctx, const aggmg_hier* h, int level, int nsweeps, int* paired);
+/* Whether level `level`'s fused kernel forms its explicit residual from the lossless symmetric form of the operator's
+ * entries (AGGMG_OPT_SYMMETRIC_RESIDUAL): 1 when it was built at set-up, 0 otherwise. */
+int aggmg_hier_level_sym_residual(aggmg_ctx* ctx, const aggmg_hier* h, int level, int* on);
 /* Which coarsest solver a hierarchy uses: on_device (1 = cyclic reduction), its block size and the
  * largest pivot-block condition estimate met while factoring (0 for the host solver). */
 int aggmg_hier_coarse_info(aggmg_ctx* ctx, const aggmg_hier* h, int* on_device, int* block_size,
