@@ -122,6 +122,8 @@ SYMBOLS = {
     "aggmg_hier_free": (c_int, [_P, _P]),
     "aggmg_vcycle": (c_int, [_P, _P, _PD, _PD, c_int, c_int, c_double, _PD]),
     "aggmg_vcycle_dev": (c_int, [_P, _P, _P, _P, c_int, c_int, c_double, _P]),
+    "aggmg_vcycle_multi_dev": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int, c_int, c_double, _P]),
+    "aggmg_hier_multi_info": (c_int, [_P, _P, c_int64, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
     "aggmg_vcycles_dev": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_double, _P]),
     "aggmg_hier_set_restriction": (c_int, [_P, _P, c_int]),
     "aggmg_hier_get_restriction": (c_int, [_P, _P, POINTER(c_int)]),
@@ -142,6 +144,7 @@ SYMBOLS = {
     "aggmg_hier_level_paired": (c_int, [_P, _P, c_int, c_int, POINTER(c_int)]),
     "aggmg_hier_level_sym_residual": (c_int, [_P, _P, c_int, POINTER(c_int)]),
     "aggmg_hier_launch_bytes": (c_int, [_P, _P, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "aggmg_hier_multi_launch_bytes": (c_int, [_P, _P, c_int, c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_int64)]),
     "aggmg_smoother_launch_bytes": (c_int, [_P, _P, _P, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "aggmg_hier_coarse_info": (c_int, [_P, _P, POINTER(c_int), POINTER(c_int), POINTER(c_double)]),
     "aggmg_hier_coarse_probe": (c_int, [_P, _P, POINTER(c_double)]),

@@ -204,11 +204,64 @@ class DeviceVector:
             pass
 
 
+class DeviceMatrix:
+    """fp64 N x K matrix in HBM owned by a Context, column-major (column j at `.ptr + 8 j N`), for the K-column cycle
+    (MeshHierarchy.vcycle_multi_dev; EXTENSION).  Same lifetime rules as DeviceVector: `.ptr` keeps the matrix alive,
+    after free() it raises."""
+
+    def __init__(self, ctx, n, k):
+        self.ctx = ctx
+        self.n = int(n)
+        self.k = int(k)
+        if self.n < 0 or self.k < 1:
+            raise ArgumentError("DeviceMatrix: needs n >= 0 rows and k >= 1 columns")
+        self._p = None
+        p = ctypes.c_void_p()
+        ctx.check(ctx.lib.aggmg_dev_alloc(ctx.handle, self.n * self.k * 8, ctypes.byref(p)))
+        self._p = p
+
+    @property
+    def shape(self):
+        return (self.n, self.k)
+
+    @property
+    def ptr(self):
+        if self._p is None:
+            raise ArgumentError("DeviceMatrix: used after free() -- its device memory has been released")
+        q = _DevPtr(self._p.value)
+        q._owner = self
+        return q
+
+    def upload(self, X):
+        X = np.asarray(X, dtype=np.float64)
+        if X.shape != (self.n, self.k):
+            raise DimensionMismatch(f"DeviceMatrix.upload: shape {X.shape}, expected {(self.n, self.k)}")
+        F = np.asfortranarray(X)
+        self.ctx.check(self.ctx.lib.aggmg_memcpy_h2d(self.ctx.handle, self.ptr, F.ctypes.data, F.size * 8))
+
+    def download(self):
+        out = np.empty((self.n, self.k), order="F")
+        self.ctx.check(self.ctx.lib.aggmg_memcpy_d2h(self.ctx.handle, out.ctypes.data, self.ptr, out.size * 8))
+        return out
+
+    def free(self):
+        """release the device memory (waits for the launches already enqueued on the context's stream)"""
+        p, self._p = self._p, None
+        if p is not None and self.ctx.handle:
+            self.ctx.lib.aggmg_dev_free(self.ctx.handle, p)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def _ptr(v):
-    """device pointer of a DeviceVector / torch tensor / int"""
+    """device pointer of a DeviceVector / DeviceMatrix / torch tensor / int"""
     if v is None:
         return ctypes.c_void_p(None)
-    if isinstance(v, DeviceVector):
+    if isinstance(v, (DeviceVector, DeviceMatrix)):
         return v.ptr
     if hasattr(v, "data_ptr"):
         return ctypes.c_void_p(v.data_ptr())
@@ -858,6 +911,42 @@ class MeshHierarchy:
         c.check(c.lib.aggmg_vcycle_dev(c.handle, self.handle, _ptr(x0), _ptr(b), int(nPre), int(nPost),
                                        float(alpha), _ptr(x_out)))
 
+    def vcycle_multi_dev(self, X0, B, X, ncols=None, ld=None, nPre=3, nPost=3, alpha=2.0 / 3.0):
+        """Device-resident V-cycle on K right-hand sides (C ABI aggmg_vcycle_multi_dev; EXTENSION): X0 (None: zero
+        guesses), B, X are DeviceMatrix / column-major device buffers with leading dimension ld (default N); column j of
+        X is bit for bit vcycle_dev of column j.  Asynchronous on the context stream."""
+        N = self._ops[0].shape[0]
+        if ncols is None:
+            ncols = B.k if isinstance(B, DeviceMatrix) else None
+        if ncols is None:
+            raise ArgumentError("vcycle_multi_dev: ncols is needed for raw device pointers")
+        if ld is None:
+            ld = N
+        for M_ in (X0, B, X):   # (ncols < 1, ld < N: the C ABI's ArgumentError)
+            if isinstance(M_, DeviceMatrix) and int(ncols) >= 1 and (M_.n != N or M_.k < int(ncols)):
+                raise DimensionMismatch("vcycle_multi_dev: matrix shape does not match (N, ncols)")
+        c = self.ctx
+        c.check(c.lib.aggmg_vcycle_multi_dev(c.handle, self.handle, _ptr(X0), _ptr(B), int(ncols), int(ld), int(nPre),
+                                             int(nPost), float(alpha), _ptr(X)))
+
+    def multi_info(self, K, nPre=3, nPost=3):
+        """-> (fused, group): whether a K-column cycle runs K-column launches (True) or the single-column cycle column by
+        column (False), and the columns per launch (C ABI aggmg_hier_multi_info)"""
+        f, g = ctypes.c_int(0), ctypes.c_int(0)
+        self.ctx.check(self.ctx.lib.aggmg_hier_multi_info(self.ctx.handle, self.handle, int(K), int(nPre), int(nPost),
+                                                          ctypes.byref(f), ctypes.byref(g)))
+        return bool(f.value), g.value
+
+    def multi_launch_bytes(self, level, kind, K, has_x0=None):
+        """(read, write) compulsory HBM bytes of a K-column fused launch of `level`, kind 'down' / 'up' (C ABI
+        aggmg_hier_multi_launch_bytes): the operator's arrays once, the vectors once per column"""
+        kk = {"down": _lib.KIND_FUSED_DOWN, "up": _lib.KIND_FUSED_UP}[kind]
+        r, w = ctypes.c_int64(0), ctypes.c_int64(0)
+        x0 = (level == 0) if has_x0 is None else bool(has_x0)
+        self.ctx.check(self.ctx.lib.aggmg_hier_multi_launch_bytes(self.ctx.handle, self.handle, int(level), kk, int(x0),
+                                                                  int(K), ctypes.byref(r), ctypes.byref(w)))
+        return r.value, w.value
+
     def vcycles_dev(self, x0, b, x_out, ncycles, nPre=3, nPost=3, alpha=2.0 / 3.0):
         """ncycles device-resident V-cycles back to back (x <- V(x, b)), the loop body of
         multigrid (src/solvers.jl:124-126); between cycles the fine level's post- and pre-smoothing
@@ -942,6 +1031,8 @@ def multigrid_v_cycle(H, x0, b, nPre=3, nPost=3, alpha=2.0 / 3.0, out=None):
     by DMA instead of staging them."""
     if not isinstance(nPre, (int, np.integer)) or not isinstance(nPost, (int, np.integer)):
         raise TypeError("nPre / nPost must be integers (nPre::Integer, src/solvers.jl:20)")
+    if isinstance(b, DeviceMatrix) or (not isinstance(b, DeviceVector) and np.ndim(b) == 2):
+        return _multigrid_v_cycle_multi(H, x0, b, int(nPre), int(nPost), float(alpha))
     if x0 is None and isinstance(b, DeviceVector):      # zero initial guess (ldiv!): nothing is read for it
         out = H.ctx.alloc(b.n)
         H.vcycle_dev(None, b, out, int(nPre), int(nPost), float(alpha))
@@ -972,6 +1063,44 @@ def multigrid_v_cycle(H, x0, b, nPre=3, nPost=3, alpha=2.0 / 3.0, out=None):
     return out
 
 
+def _multigrid_v_cycle_multi(H, X0, B, nPre, nPost, alpha):
+    """K right-hand sides (EXTENSION; the reference's methods take vectors, src/solvers.jl:19,63,84): B an (N, K) host
+    array in either memory order (-> (N, K) array) or a DeviceMatrix (-> DeviceMatrix); X0 likewise, or None for zero
+    guesses.  Column j is bit for bit the single-vector cycle of column j (aggmg_vcycle_multi_dev)."""
+    N = H._ops[0].shape[0]
+    c = H.ctx
+    if isinstance(B, DeviceMatrix):
+        if X0 is not None and not isinstance(X0, DeviceMatrix):
+            raise ArgumentError("multigrid_v_cycle: X0 must be a DeviceMatrix (or None) when B is one")
+        K = B.k
+        if B.n != N or (X0 is not None and X0.shape != B.shape):
+            raise DimensionMismatch("multigrid_v_cycle: X0 / B do not match (N, K) of the fine operator")
+        X = DeviceMatrix(c, N, K)
+        H.vcycle_multi_dev(X0, B, X, K, N, nPre, nPost, alpha)
+        return X
+    if isinstance(X0, (DeviceVector, DeviceMatrix)):
+        raise ArgumentError("multigrid_v_cycle: X0 is on the device but B is a host array")
+    B = np.asarray(B, dtype=np.float64)
+    if B.ndim != 2 or B.shape[0] != N:
+        raise DimensionMismatch(f"multigrid_v_cycle: B has shape {B.shape}, expected ({N}, K)")
+    K = B.shape[1]
+    if K < 1:
+        raise ArgumentError("multigrid_v_cycle: B has no columns")
+    if X0 is not None:
+        X0 = np.asarray(X0, dtype=np.float64)
+        if X0.shape != B.shape:
+            raise DimensionMismatch(f"multigrid_v_cycle: X0 has shape {X0.shape}, B {B.shape}")
+    dB = DeviceMatrix(c, N, K)
+    dB.upload(B)
+    dX0 = None
+    if X0 is not None:
+        dX0 = DeviceMatrix(c, N, K)
+        dX0.upload(X0)
+    dX = DeviceMatrix(c, N, K)
+    H.vcycle_multi_dev(dX0, dB, dX, K, N, nPre, nPost, alpha)
+    return dX.download()
+
+
 def ldiv(*args):
     """ldiv!(H, b) -- overwrites b (src/solvers.jl:63-71);  ldiv!(y, H, b) (src/solvers.jl:84-92).
     One V-cycle from a zero initial guess."""
@@ -984,6 +1113,21 @@ def ldiv(*args):
         raise TypeError("ldiv(H, b) or ldiv(y, H, b)")
     N = H._ops[0].shape[0]
     u0 = None        # zero initial guess: aggmg_vcycle(x0 = NULL), no vector of zeros crosses PCIe
+    if isinstance(b, DeviceMatrix) or (not isinstance(b, DeviceVector) and np.ndim(b) == 2):
+        # K right-hand sides (EXTENSION): ldiv!(Y, H, B) with matrices, one K-column cycle from zero guesses.  The
+        # DeviceMatrix form writes Y on the device and needs a Y apart from B (ArgumentError otherwise)
+        if isinstance(b, DeviceMatrix):
+            if not isinstance(y, DeviceMatrix):
+                raise ArgumentError("ldiv: Y must be a DeviceMatrix when B is one")
+            if y.shape != b.shape or b.n != N:
+                raise DimensionMismatch(f"ldiv: Y has shape {y.shape}, B {b.shape}, the fine operator {N} rows")
+            H.vcycle_multi_dev(None, b, y, b.k, N)
+            return None
+        Y = _multigrid_v_cycle_multi(H, None, b, 3, 3, 2.0 / 3.0)
+        if np.shape(y) != Y.shape:
+            raise DimensionMismatch(f"ldiv: Y has shape {np.shape(y)}, B {Y.shape}")
+        y[...] = Y
+        return None
     direct = (y is not b and isinstance(y, np.ndarray) and y.dtype == np.float64 and y.shape == (N,) and y.flags["C_CONTIGUOUS"]
               and not np.shares_memory(y, np.asarray(b)))
     if direct:      # straight into y: with y and b page-locked (Context.pin) nothing is staged

@@ -6,6 +6,7 @@
 // the CG chain path: cgt.hip; element-partitioned runs: dist.hip; sparse set-up products: spops.hip.
 // No CPU compute fallback exists: every hot-path entry point launches HIP kernels or fails.
 #include "internal.hpp"
+#include "multi_kernels.hpp"
 #include "pair_kernels.hpp"
 
 // ---------------------------------------------------------------------------------------------
@@ -1854,6 +1855,205 @@ extern "C" int aggmg_vcycle_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0,
   return vcycle_up(ctx, h, b, nPost, alpha, x_out);
 }
 
+// ---- K right-hand sides in one pass over the operators (EXTENSION: the reference's multigrid_v_cycle / ldiv! take
+// vectors, src/solvers.jl:19,63,84) ------------------------------------------------------------------------------
+// The columns go in groups of at most kMultiKB; every non-coarsest level runs ONE btd_multi_kernel launch per group
+// on the way down and one on the way up (no two-level launches here), the coarsest solve runs column by column.
+// A hierarchy with a level outside the kernel's coverage runs the single-column cycle on every column instead: the
+// same bits either way (multi_kernels.hpp), aggmg_hier_multi_info says which.
+#ifndef AGGMG_MULTI_KB
+#define AGGMG_MULTI_KB 8
+#endif
+#ifndef AGGMG_MULTI_NT
+#define AGGMG_MULTI_NT 256
+#endif
+constexpr int kMultiKB = AGGMG_MULTI_KB, kMultiNT = AGGMG_MULTI_NT;
+static_assert(kMultiKB == 1 || kMultiKB == 2 || kMultiKB == 4 || kMultiKB == 8, "column groups of 1, 2, 4 or 8");
+
+static bool multi_level_ok(const aggmg_hier* h, int k, int nPre, int nPost) {
+  const Level& l = h->lv[k];
+  if (!(l.S && l.S->btd && l.S->A == l.A && l.tb) || l.cgt_fused || l.S->gs) return false;
+  const BtdDev& b = *l.S->btd;
+  const TransferBtd& t = *l.tb;
+  if (b.cmp ? !(b.m == 2 || b.m == 4) : b.m != 2) return false;
+  if (t.mc != 2 || t.rho <= 0 || b.ne != (int64_t)t.rho * t.nec) return false;
+  if (t.ld && h->restriction == AGGMG_RESTRICT_PRECONDITIONED) return false;
+  // the single-column cycle's launches at this level are single fused launches (no chunked sweeps) ...
+  if (!btd_fits(*l.S, nPre, 1) || !btd_fits(*l.S, nPost, 0)) return false;
+  // ... and the K-column tile holds the same halos
+  const int te = kMultiNT / b.m;
+  return ((te - 2 * (nPre + 1)) / t.rho) * t.rho > 0 && te - 2 * nPost > 0;
+}
+
+static bool multi_ok(const aggmg_hier* h, int nPre, int nPost) {
+  const int n = (int)h->lv.size();
+  if (n < 2 || h->coarse_mode == AGGMG_COARSE_EXTERNAL) return false;
+  for (int k = 0; k < n - 1; ++k)
+    if (!multi_level_ok(h, k, nPre, nPost)) return false;
+  return true;
+}
+
+template <int M, bool CMP, bool SYM>
+static int launch_multi_t(aggmg_ctx* ctx, MultiArgs m, int halo) {
+  constexpr int TE = kMultiNT / M;
+  const int align = m.a.lf_out ? m.a.rho_out : 1;
+  const int owned = ((TE - 2 * halo) / align) * align;
+  if (owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column tile too small for the requested halo");
+  m.a.owned = owned;
+  m.a.halo_left = halo;
+  const int64_t ntiles = (m.a.lv.ne + owned - 1) / owned;
+  if (ntiles == 0) return AGGMG_OK;
+  auto go = [&](auto kern, int kb) {
+    const size_t lds = (size_t)2 * kb * (TE + 2) * M * sizeof(double);
+    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(kMultiNT), lds, ctx->stream, m);
+  };
+  // the smallest instantiated group that holds the columns
+  if (m.kc <= 1)
+    go(btd_multi_kernel<M, CMP, SYM, 1, kMultiNT>, 1);
+  else if (m.kc <= 2 || kMultiKB == 2)
+    go(btd_multi_kernel<M, CMP, SYM, 2, kMultiNT>, 2);
+  else if (m.kc <= 4 || kMultiKB == 4)
+    go(btd_multi_kernel<M, CMP, SYM, 4, kMultiNT>, 4);
+  else
+    go(btd_multi_kernel<M, CMP, SYM, 8, kMultiNT>, 8);
+  HIPCHK(hipGetLastError());
+  return AGGMG_OK;
+}
+
+static int launch_multi(aggmg_ctx* ctx, const BtdDev& b, const MultiArgs& m, int halo) {
+  const bool sym = b.bsym != nullptr;
+  if (b.cmp && b.m == 4) return sym ? launch_multi_t<4, true, true>(ctx, m, halo) : launch_multi_t<4, true, false>(ctx, m, halo);
+  if (b.cmp && b.m == 2) return sym ? launch_multi_t<2, true, true>(ctx, m, halo) : launch_multi_t<2, true, false>(ctx, m, halo);
+  if (!b.cmp && b.m == 2) return sym ? launch_multi_t<2, false, true>(ctx, m, halo) : launch_multi_t<2, false, false>(ctx, m, halo);
+  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: block size not instantiated for the K-column kernel");
+}
+
+// per-level K-column vectors for groups of `cols` columns; a call with no more columns than before allocates nothing
+static int multi_workspace(aggmg_ctx* ctx, aggmg_hier* h, int64_t cols) {
+  if (h->multi_cols >= cols && !h->mu.empty()) return AGGMG_OK;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (auto& m : h->mu)
+    for (double*& p : m) {
+      if (p) HIPCHK(hipFree(p));
+      p = nullptr;
+    }
+  h->multi_cols = 0;
+  const int n = (int)h->lv.size();
+  h->mu.assign(n, {nullptr, nullptr, nullptr});
+  for (int k = 0; k < n; ++k) {
+    const size_t bytes = (size_t)std::max<int64_t>(h->lv[k].N * cols, 1) * sizeof(double);
+    const bool coarsest = k == n - 1;
+    for (int s = 0; s < 3; ++s) {
+      if (s == 1 && (k == 0 || coarsest)) continue;   // the ascent's output: the caller's X at level 0, none at the coarsest
+      if (s == 2 && k == 0) continue;                 // level 0's right-hand side is the caller's B
+      HIPCHK(hipMalloc((void**)&h->mu[k][s], bytes));
+    }
+  }
+  h->multi_cols = cols;
+  return AGGMG_OK;
+}
+
+// columns [c0, c0 + kc) of a K-column cycle whose every non-coarsest level multi_level_ok accepts
+static int vcycle_multi_group(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, const double* B, int64_t ld, int nPre,
+                              int nPost, double alpha, double* X, int kc) {
+  const int n = (int)h->lv.size();
+  for (int k = 0; k < n - 1; ++k) {   // descent (src/solvers.jl:28-37)
+    Level& l = h->lv[k];
+    Level& c = h->lv[k + 1];
+    MultiArgs m;
+    std::memset(&m, 0, sizeof(m));
+    m.a = btd_args(*l.S->btd);
+    m.kc = kc;
+    m.a.u_in = k == 0 ? X0 : nullptr;   // u[k] = zeros for k > 1 (:29-31)
+    m.ld_uin = ld;
+    m.a.b = k == 0 ? B : h->mu[k][2];
+    m.ld_b = k == 0 ? ld : l.N;
+    m.a.u_out = h->mu[k][0];
+    m.ld_uout = l.N;
+    m.a.alpha = alpha;
+    m.a.nsweeps = nPre;
+    m.a.do_residual = 1;
+    m.a.lf_out = l.tb->lf;
+    xfer_out(m.a, *l.tb);
+    m.a.rc_out = h->mu[k + 1][2];
+    m.ld_rc = c.N;
+    ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
+    CHECK(launch_multi(ctx, *l.S->btd, m, nPre + 1));
+  }
+  {  // coarsest solve (:39), column by column
+    const int64_t Nc = h->lv[n - 1].N;
+    for (int j = 0; j < kc; ++j) CHECK(coarse_solve(ctx, h, h->mu[n - 1][2] + j * Nc, h->mu[n - 1][0] + j * Nc));
+  }
+  for (int k = n - 2; k >= 0; --k) {   // ascent (:41-47)
+    Level& l = h->lv[k];
+    Level& c = h->lv[k + 1];
+    MultiArgs m;
+    std::memset(&m, 0, sizeof(m));
+    m.a = btd_args(*l.S->btd);
+    m.kc = kc;
+    m.a.u_in = h->mu[k][0];
+    m.ld_uin = l.N;
+    m.a.b = k == 0 ? B : h->mu[k][2];
+    m.ld_b = k == 0 ? ld : l.N;
+    m.a.u_out = k == 0 ? X : h->mu[k][1];
+    m.ld_uout = k == 0 ? ld : l.N;
+    m.a.alpha = alpha;
+    m.a.nsweeps = nPost;
+    m.a.lf_in = l.tb->lf;
+    m.a.uc = (k + 1 == n - 1) ? h->mu[k + 1][0] : h->mu[k + 1][1];
+    m.ld_uc = c.N;
+    xfer_in(m.a, *l.tb);
+    ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
+    CHECK(launch_multi(ctx, *l.S->btd, m, nPost));
+  }
+  return AGGMG_OK;
+}
+
+static bool ranges_overlap(const double* a, int64_t na, const double* b, int64_t nb) {
+  if (!a || !b) return false;
+  return a < b + nb && b < a + na;
+}
+
+extern "C" int aggmg_vcycle_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, const double* B, int64_t ncols,
+                                      int64_t ld, int nPre, int nPost, double alpha, double* X) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!h || !B || !X) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: NULL argument");
+  if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: ncols must be >= 1");
+  if (nPre < 0 || nPost < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: negative sweep count");
+  const int64_t N = h->lv[0].N;
+  if (ld < N) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: ld must be >= N (" + std::to_string(N) + ")");
+  const int64_t span = (ncols - 1) * ld + N;   // doubles from the first column's start to the last one's end
+  if (ranges_overlap(X, span, X0, span) || ranges_overlap(X, span, B, span))
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: X must not overlap X0 or B");
+  if (h->coarse_mode == AGGMG_COARSE_EXTERNAL)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: hierarchy was created with AGGMG_COARSE_EXTERNAL");
+  if (!multi_ok(h, nPre, nPost)) {   // column by column: the single-column cycle on every column slice
+    for (int64_t j = 0; j < ncols; ++j)
+      CHECK(aggmg_vcycle_dev(ctx, h, X0 ? X0 + j * ld : nullptr, B + j * ld, nPre, nPost, alpha, X + j * ld));
+    return AGGMG_OK;
+  }
+  const int64_t group = std::min<int64_t>(ncols, kMultiKB);
+  CHECK(multi_workspace(ctx, h, group));
+  h->last_coarse_ms = 0.0;
+  for (int64_t c0 = 0; c0 < ncols; c0 += group) {
+    const int kc = (int)std::min<int64_t>(group, ncols - c0);
+    CHECK(vcycle_multi_group(ctx, h, X0 ? X0 + c0 * ld : nullptr, B + c0 * ld, ld, nPre, nPost, alpha, X + c0 * ld, kc));
+  }
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_hier_multi_info(aggmg_ctx* ctx, const aggmg_hier* h, int64_t ncols, int nPre, int nPost, int* fused,
+                                     int* group) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!h || !fused || !group) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_info: NULL argument");
+  if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_info: ncols must be >= 1");
+  if (nPre < 0 || nPost < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_info: negative sweep count");
+  const bool f = multi_ok(h, nPre, nPost);
+  *fused = f ? 1 : 0;
+  *group = f ? (int)std::min<int64_t>(ncols, kMultiKB) : 1;
+  return AGGMG_OK;
+}
+
 // ncycles V-cycles back to back, x <- V(x, b): the hot loop of multigrid() (src/solvers.jl:124-126).
 // Between two cycles the fine level runs post-smoothing of cycle i and pre-smoothing of cycle i+1
 // on the same iterate with the same right-hand side, so both go into ONE fused launch
@@ -2242,14 +2442,15 @@ extern "C" int aggmg_hier_level_kind(aggmg_ctx* ctx, const aggmg_hier* h, int le
 // ---- compulsory bytes of a launch: what its arrays hold, each read or written once -------------
 // (the denominator-free side of the roofline fraction: no halo re-reads, no cache effects, no CSR
 // model -- the arrays in the format the level stores them)
+// ncols: columns of a K-column launch (btd_multi_kernel) -- the vectors' bytes once per column, the operator's once
 static void btd_launch_bytes(const BtdDev& b, bool sweeps, bool u_in, bool residual, bool r_out, const TransferBtd* tin,
-                             const TransferBtd* tout, bool preconditioned, int64_t* rd, int64_t* wr) {
-  const int64_t m = b.m, ne = b.ne, N = ne * m, D = sizeof(double);
+                             const TransferBtd* tout, bool preconditioned, int64_t* rd, int64_t* wr, int64_t ncols = 1) {
+  const int64_t m = b.m, ne = b.ne, N = ne * m, D = sizeof(double), K = ncols;
   const bool need_g = sweeps || (tout && preconditioned);
   const bool grp = (b.cmp && (m == 2 || m == 4 || m == 8)) || (!b.cmp && (m == 2 || m == 4));
   const bool sym = grp && b.bsym;
-  int64_t r = N * D, w = 0;                                                 // b
-  if (u_in) r += N * D;
+  int64_t r = K * N * D, w = 0;                                             // b
+  if (u_in) r += K * N * D;
   if (need_g) {
     r += sym ? ne * (m * (m + 1) / 2) * D : N * m * D;                       // B^{-1}: packed or full rows
     if (b.cmp) r += sym ? 0 : N * D;                                         // pcol (rebuilt from qrow when packed)
@@ -2264,18 +2465,18 @@ static void btd_launch_bytes(const BtdDev& b, bool sweeps, bool u_in, bool resid
   }
   if (tin) {
     r += tin->lf1 ? N * D : N * tin->mc * D;                                 // rows of L
-    r += tin->nec * tin->mc * D;                                             // coarse iterate
+    r += K * tin->nec * tin->mc * D;                                         // coarse iterate
     if (!tin->rho) r += ne * 4;                                              // parent map
   }
-  if (sweeps || tin) w += N * D;                                             // iterate
-  if (r_out) w += N * D;
+  if (sweeps || tin) w += K * N * D;                                         // iterate
+  if (r_out) w += K * N * D;
   if (residual && tout) {
     if (preconditioned)
       r += N * tout->mc * D;                                                 // rows of (L'D)'
     else if (tout != tin)
       r += tout->lf1 ? N * D : N * tout->mc * D;                             // rows of L (once when the launch prolongs with them too)
     if (!tout->rho) r += ne * 4 + (tout->nec + 1) * 4;
-    w += tout->nec * tout->mc * D;
+    w += K * tout->nec * tout->mc * D;
   }
   *rd = r;
   *wr = w;
@@ -2296,6 +2497,25 @@ extern "C" int aggmg_hier_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int 
   const bool pre = l.tb->ld && h->restriction == AGGMG_RESTRICT_PRECONDITIONED;
   btd_launch_bytes(*l.S->btd, true, up || has_x0, down, false, up ? l.tb.get() : nullptr, down ? l.tb.get() : nullptr, pre,
                    read_bytes, write_bytes);
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_hier_multi_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int level, int kind, int has_x0,
+                                             int64_t ncols, int64_t* read_bytes, int64_t* write_bytes) {
+  if (!ctx || !h || !read_bytes || !write_bytes)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_launch_bytes: NULL argument");
+  if (level < 0 || level + 1 >= (int)h->lv.size())
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_launch_bytes: level out of range (the coarsest level has no fused launch)");
+  if (kind != AGGMG_KIND_FUSED_DOWN && kind != AGGMG_KIND_FUSED_UP)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_launch_bytes: kind must be AGGMG_KIND_FUSED_DOWN / _UP");
+  if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_launch_bytes: ncols must be >= 1");
+  const Level& l = h->lv[level];
+  if (l.cgt_fused || !(l.S && l.S->btd && l.S->A == l.A && l.tb))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_hier_multi_launch_bytes: the level has no fused block-tridiagonal launch");
+  const bool down = kind == AGGMG_KIND_FUSED_DOWN;
+  const bool pre = l.tb->ld && h->restriction == AGGMG_RESTRICT_PRECONDITIONED;
+  btd_launch_bytes(*l.S->btd, true, !down || has_x0, down, false, down ? nullptr : l.tb.get(), down ? l.tb.get() : nullptr, pre,
+                   read_bytes, write_bytes, ncols);
   return AGGMG_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -277,6 +278,11 @@ struct aggmg_hier {
   CrDev cr;
   double* cyc[2] = {nullptr, nullptr};  // iterate ping-pong for multi-cycle calls (lazy)
   double* io[3] = {nullptr, nullptr, nullptr};  // x0, b, x_out of the host-pointer entry aggmg_vcycle (lazy)
+  // K-column cycles (aggmg_vcycle_multi_dev, lazy, grown to the largest column group asked for): per level, multi_cols
+  // columns of the pre-smoothed iterate (mu[k][0]), the post-smoothed one (mu[k][1], levels 1 .. n-2) and the right-hand
+  // side (mu[k][2], levels >= 1); the coarsest level's solution goes to mu[n-1][0]
+  std::vector<std::array<double*, 3>> mu;
+  int64_t multi_cols = 0;
   int restriction = 0;  // AGGMG_RESTRICT_EXPLICIT (default) / AGGMG_RESTRICT_PRECONDITIONED
   std::vector<double> h_coarse;
   double last_coarse_ms = 0.0;
@@ -292,6 +298,9 @@ struct aggmg_hier {
       if (p) (void)hipFree(p);
     for (double* p : io)
       if (p) (void)hipFree(p);
+    for (auto& m : mu)
+      for (double* p : m)
+        if (p) (void)hipFree(p);
   }
 };
 

@@ -833,6 +833,128 @@ __device__ __forceinline__ void sym_residual_row(const BtdLevel& lv, int64_t e, 
   sc = dc == kSymResidualEscape ? lv.scol[row] : sym_residual_decode(lv.qrow[row - M], dc);
 }
 
+// sum of a * b over the group, W = 2, 4: the first step's addition fused to the lane's own product, fma(a, b, partner's
+// rounded a * b), later steps plain additions -- what the compiler makes of group_sum<W>(a * b) in btd_fused_kernel,
+// written out: whether the contraction is formed depends on the code around it (measured: the K-column kernel's
+// residual kept a separate multiply and add -- a few ulps apart), so the kernels that must agree bit for bit say it.
+// (The red-black Gauss-Seidel variants are compiled to a separate multiply and add in one of their group sums at
+// M = 2: they keep group_sum's unpinned form -- DOT = false in the helpers below -- and with it their bits.)
+template <int W>
+__device__ __forceinline__ double group_dot(double a, double b) {
+  if constexpr (AGGMG_DPP && (W == 2 || W == 4)) {
+    const double p = a * b;
+    if constexpr (W == 4) {
+      double v = __fma_rn(a, b, quad_perm<0x4E>(p));
+      v += quad_perm<0xB1>(v);
+      return v;
+    } else {
+      return __fma_rn(a, b, quad_perm<0xB1>(p));
+    }
+  } else {
+    return group_sum<W>(a * b);
+  }
+}
+
+// ---- per-element arithmetic of the fused schedule, shared by btd_fused_kernel and btd_multi_kernel (multi_kernels.hpp):
+// one set of expressions in one order, so a column of a K-column launch is bit for bit the single-column launch's ----
+// B^{-1}_row v_e with the element's v_e broadcast across its lane group (g = B^{-1} b, the symmetric pcol = B^{-1} q_{e-1})
+template <int M>
+__device__ __forceinline__ double btd_group_apply(const double (&bi)[M], double v) {
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < M; ++j) acc += bi[j] * group_bcast<M>(v, j);
+  return acc;
+}
+// DSYM: the rows of Sup_{e-1} (parked in Pr) and Sup_e (parked in Qr) turned into rows of P = B^{-1} Sub, Q = B^{-1} Sup
+//   P_i[j] = sum_k B^{-1}_ik Sup_{e-1}[j][k]   (lane j holds row j of Sup_{e-1})
+//   Q_i[j] = sum_k B^{-1}_ik Sup_e[k][j]       (lane k holds row k of Sup_e)
+template <int M>
+__device__ __forceinline__ void btd_dsym_pq(const double (&bi)[M], double (&Pr)[M], double (&Qr)[M]) {
+  double pn[M], qn[M];
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    double pa = 0.0, qa = 0.0;
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      pa += bi[k] * group_bcast<M>(Pr[k], j);
+      qa += bi[k] * group_bcast<M>(Qr[j], k);
+    }
+    pn[j] = pa;
+    qn[j] = qa;
+  }
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    Pr[j] = pn[j];
+    Qr[j] = qn[j];
+  }
+}
+// g - P u_{e-1} - Q u_{e+1} of one row (= u_e + (B^{-1}(b - A u))_row) from the iterate rows um / up in LDS.  Compressed
+// couplings: P u- = pcol * u-[c_sub], Q u+ = B^{-1}[:, r_sup] (q . u+); GRP: the dot product summed across the lane group
+template <int M, bool GRP, bool DOT = true>
+__device__ __forceinline__ double btd_stencil_cmp(double g, double pc, const double* qv, double binv_r, const double* um,
+                                                  const double* up, int c_sub, int i) {
+  double acc = g;
+  acc -= pc * um[c_sub];
+  double dot = 0.0;
+  if (GRP) {
+    dot = DOT ? group_dot<M>(qv[0], up[i]) : group_sum<M>(qv[0] * up[i]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < (GRP ? 1 : M); ++j) dot += qv[j] * up[j];
+  }
+  acc -= binv_r * dot;
+  return acc;
+}
+template <int M>
+__device__ __forceinline__ double btd_stencil_dense(double g, const double (&Pr)[M], const double (&Qr)[M], const double* um,
+                                                    const double* up) {
+  double acc = g;
+#pragma unroll
+  for (int j = 0; j < M; ++j) acc -= Pr[j] * um[j];
+#pragma unroll
+  for (int j = 0; j < M; ++j) acc -= Qr[j] * up[j];
+  return acc;
+}
+// one damped sweep of a row: u + alpha (g - P u- - Q u+ - u)
+__device__ __forceinline__ double btd_damped(double u, double alpha, double acc) { return u + alpha * (acc - u); }
+// (A u)_row in ascending column order with the operator's own entries: compressed couplings (dk: row of D_e, sc: the
+// sub-diagonal column entry; GRP: q . u+ summed across the lane group, kept by row r_sup) ...
+template <int M, bool GRP, bool DOT = true>
+__device__ __forceinline__ double btd_apply_cmp(double sc, const double (&dk)[M], const double* qv, const double* um,
+                                                const double* ux, const double* up, int c_sub, int r_sup, int i) {
+  double t = 0.0;
+  t += sc * um[c_sub];
+#pragma unroll
+  for (int j = 0; j < M; ++j) t += dk[j] * ux[j];
+  if (GRP) {
+    const double d = DOT ? group_dot<M>(qv[0], up[i]) : group_sum<M>(qv[0] * up[i]);
+    if (i == r_sup) t += d;
+  } else if (i == r_sup) {
+#pragma unroll
+    for (int j = 0; j < (GRP ? 1 : M); ++j) t += qv[j] * up[j];
+  }
+  return t;
+}
+// ... and dense ones (the row's entries of Sub_e, D_e, Sup_e)
+template <int M>
+__device__ __forceinline__ double btd_apply_dense(const double* sb, const double* dk, const double* sp, const double* um,
+                                                  const double* ux, const double* up) {
+  double t = 0.0;
+#pragma unroll
+  for (int j = 0; j < M; ++j) t += sb[j] * um[j];
+#pragma unroll
+  for (int j = 0; j < M; ++j) t += dk[j] * ux[j];
+#pragma unroll
+  for (int j = 0; j < M; ++j) t += sp[j] * up[j];
+  return t;
+}
+// prolongation of two coarse modes: (L uc)_row = l.x uc[2J] + l.y uc[2J + 1]
+__device__ __forceinline__ double btd_prolong2(double2 l2, double2 u2) {
+  double add = l2.x * u2.x;
+  add += l2.y * u2.y;
+  return add;
+}
+
 // GS: red-black block Gauss-Seidel sweeps (FusedArgs::gs gives the colour order) instead of
 // block-Jacobi ones -- a compile-time variant, so the block-Jacobi kernel carries none of it
 // (AGGMG_CHK_WAVES: minimum waves per SIMD asked of the checkpoint variant; measured 7 and 6 -- spills into the sweep
@@ -982,8 +1104,7 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
             l2.y = lv2.y;
           }
           const double2 u2 = *reinterpret_cast<const double2*>(a.uc + J * 2);
-          add = l2.x * u2.x;
-          add += l2.y * u2.y;
+          add = btd_prolong2(l2, u2);
         } else {
           for (int c = 0; c < a.mc_in; ++c) add += a.lf_in[row * a.mc_in + c] * a.uc[J * a.mc_in + c];
         }
@@ -1015,13 +1136,10 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
     // g = B^{-1} b with the element's b_e broadcast across its lane group
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-      double acc = 0.0;
-#pragma unroll
-      for (int j = 0; j < M; ++j) acc += bi[s][j] * group_bcast<M>(bb[s], j);
-      g[s] = acc;
+      g[s] = btd_group_apply<M>(bi[s], bb[s]);
       if (DSYM) {
-        // P_i[j] = sum_k B^{-1}_ik Sup_{e-1}[j][k]   (lane j holds row j of Sup_{e-1})
-        // Q_i[j] = sum_k B^{-1}_ik Sup_e[k][j]       (lane k holds row k of Sup_e)
+        // btd_dsym_pq's expressions, written out: the helper call costs the M = 4 variants 38 VGPRs (96 -> 134, 5 -> 3
+        // waves per SIMD), with the same arithmetic instructions
         double pn[M], qn[M];
 #pragma unroll
         for (int j = 0; j < M; ++j) {
@@ -1040,13 +1158,7 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
           Qr[s][j] = qn[j];
         }
       }
-      if (SYM && CMP) {  // pcol = B^{-1} q_{e-1}
-        const double qp = pc[s];
-        double pacc = 0.0;
-#pragma unroll
-        for (int j = 0; j < M; ++j) pacc += bi[s][j] * group_bcast<M>(qp, j);
-        pc[s] = pacc;
-      }
+      if (SYM && CMP) pc[s] = btd_group_apply<M>(bi[s], pc[s]);  // pcol = B^{-1} q_{e-1}
     }
     __syncthreads();
   } else {
@@ -1122,27 +1234,13 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
         const double* um = it + (x - 1) * M;
         const double* ux = it + x * M;
         const double* up = it + (x + 1) * M;
-        double t = 0.0;
+        double t;
         if (CMP) {
           double dk[M], sc;
           row_entries(s, row, dk, sc);
-          t += sc * um[a.lv.c_sub];
-#pragma unroll
-          for (int j = 0; j < M; ++j) t += dk[j] * ux[j];
-          if (GRP) {
-            const double d = group_sum<M>(qv[s][0] * up[i]);
-            if (i == a.lv.r_sup) t += d;
-          } else if (i == a.lv.r_sup) {
-#pragma unroll
-            for (int j = 0; j < (GRP ? 1 : M); ++j) t += qv[s][j] * up[j];
-          }
+          t = btd_apply_cmp<M, GRP, !GS>(sc, dk, qv[s], um, ux, up, a.lv.c_sub, a.lv.r_sup, i);
         } else {
-#pragma unroll
-          for (int j = 0; j < M; ++j) t += a.lv.sub[row * M + j] * um[j];
-#pragma unroll
-          for (int j = 0; j < M; ++j) t += a.lv.dblk[row * M + j] * ux[j];
-#pragma unroll
-          for (int j = 0; j < M; ++j) t += a.lv.sup[row * M + j] * up[j];
+          t = btd_apply_dense<M>(a.lv.sub + row * M, a.lv.dblk + row * M, a.lv.sup + row * M, um, ux, up);
         }
         const double r = bb[s] - t;
         sr += r * r;
@@ -1196,24 +1294,12 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
       if (active) {
         const double* um = cur + (x - 1) * M;
         const double* up = cur + (x + 1) * M;
-        double acc = g[s];
-        if (CMP) {
-          acc -= pc[s] * um[a.lv.c_sub];
-          double dot = 0.0;
-          if (GRP) {
-            dot = group_sum<M>(qv[s][0] * up[i]);
-          } else {
-#pragma unroll
-            for (int j = 0; j < (GRP ? 1 : M); ++j) dot += qv[s][j] * up[j];
-          }
-          acc -= binv_r[s] * dot;
-        } else {
-#pragma unroll
-          for (int j = 0; j < M; ++j) acc -= Pr[s][j] * um[j];
-#pragma unroll
-          for (int j = 0; j < M; ++j) acc -= Qr[s][j] * up[j];
-        }
-        double un = uu[s] + a.alpha * (acc - uu[s]);
+        double acc;
+        if (CMP)
+          acc = btd_stencil_cmp<M, GRP, !GS>(g[s], pc[s], qv[s], binv_r[s], um, up, a.lv.c_sub, i);
+        else
+          acc = btd_stencil_dense<M>(g[s], Pr[s], Qr[s], um, up);
+        double un = btd_damped(uu[s], a.alpha, acc);
         if (!valid[s]) un = 0.0;
         if constexpr (!GS) {
           uu[s] = un;
@@ -1265,7 +1351,7 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
         const double* um = cur + (x - 1) * M;
         const double* ux = cur + x * M;
         const double* up = cur + (x + 1) * M;
-        double t = 0.0;
+        double t;
         if (CMP) {
           double dk[M], sc;
           if constexpr (CHK) {
@@ -1273,23 +1359,9 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
           } else {
             load_row(s, row, dk, sc);
           }
-          t += sc * um[a.lv.c_sub];
-#pragma unroll
-          for (int j = 0; j < M; ++j) t += dk[j] * ux[j];
-          if (GRP) {
-            const double d = group_sum<M>(qv[s][0] * up[i]);
-            if (i == a.lv.r_sup) t += d;
-          } else if (i == a.lv.r_sup) {
-#pragma unroll
-            for (int j = 0; j < (GRP ? 1 : M); ++j) t += qv[s][j] * up[j];
-          }
+          t = btd_apply_cmp<M, GRP, !GS>(sc, dk, qv[s], um, ux, up, a.lv.c_sub, a.lv.r_sup, i);
         } else {
-#pragma unroll
-          for (int j = 0; j < M; ++j) t += a.lv.sub[row * M + j] * um[j];
-#pragma unroll
-          for (int j = 0; j < M; ++j) t += a.lv.dblk[row * M + j] * ux[j];
-#pragma unroll
-          for (int j = 0; j < M; ++j) t += a.lv.sup[row * M + j] * up[j];
+          t = btd_apply_dense<M>(a.lv.sub + row * M, a.lv.dblk + row * M, a.lv.sup + row * M, um, ux, up);
         }
         rr[s] = bb[s] - t;
         if (a.r_out) a.r_out[row] = rr[s];
@@ -1307,23 +1379,11 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
       if (valid[s] && x >= xo0 && x < xo1) {
         const double* um = cur + (x - 1) * M;
         const double* up = cur + (x + 1) * M;
-        double acc = g[s];
-        if (CMP) {
-          acc -= pc[s] * um[a.lv.c_sub];
-          double dot = 0.0;
-          if (GRP) {
-            dot = group_sum<M>(qv[s][0] * up[i]);
-          } else {
-#pragma unroll
-            for (int j = 0; j < (GRP ? 1 : M); ++j) dot += qv[s][j] * up[j];
-          }
-          acc -= binv_r[s] * dot;
-        } else {
-#pragma unroll
-          for (int j = 0; j < M; ++j) acc -= Pr[s][j] * um[j];
-#pragma unroll
-          for (int j = 0; j < M; ++j) acc -= Qr[s][j] * up[j];
-        }
+        double acc;
+        if (CMP)
+          acc = btd_stencil_cmp<M, GRP, !GS>(g[s], pc[s], qv[s], binv_r[s], um, up, a.lv.c_sub, i);
+        else
+          acc = btd_stencil_dense<M>(g[s], Pr[s], Qr[s], um, up);
         rr[s] = acc - uu[s];
       }
     }

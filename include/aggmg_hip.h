@@ -270,6 +270,21 @@ int aggmg_vcycle(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const double* 
                  int nPost, double alpha, double* x_out);
 int aggmg_vcycle_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const double* b, int nPre,
                      int nPost, double alpha, double* x_out);
+/* multigrid_v_cycle on K right-hand sides (EXTENSION: the reference's methods take vectors, src/solvers.jl:19,63,84).
+ * X0, B, X: device, column-major N x ncols, leading dimension ld >= N; X0 == NULL: zero initial guesses (ldiv!).
+ * Column j of X is bit for bit what aggmg_vcycle_dev gives for column j of X0 and B.  X must not overlap X0 or B.
+ * The columns go in groups (aggmg_hier_multi_info); each non-coarsest level runs one launch per group each way and
+ * reads its operator once for the whole group, the coarsest solve runs column by column.  A hierarchy with a level
+ * the K-column kernel does not cover (CG chain or generic levels, Gauss-Seidel sweeps, agglomerates of different sizes,
+ * the preconditioned restriction, block sizes other than 2 / 4 (compressed) and 2 (dense), transfers with other than
+ * two coarse modes, sweep counts beyond the tiles' halo) runs aggmg_vcycle_dev column by column instead.  Per-level
+ * work space for one group is allocated on the hierarchy on first use (grown for a larger group, freed with it).
+ * Asynchronous on the context stream.  AGGMG_ERR_ARGUMENT: NULL, ncols < 1, ld < N, X overlapping X0 or B, negative
+ * sweep counts, a hierarchy created with AGGMG_COARSE_EXTERNAL. */
+int aggmg_vcycle_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, const double* B, int64_t ncols, int64_t ld,
+                           int nPre, int nPost, double alpha, double* X);
+/* fused = 1 when the cycle runs K-column launches, 0 when it runs column by column; group = columns per launch */
+int aggmg_hier_multi_info(aggmg_ctx* ctx, const aggmg_hier* h, int64_t ncols, int nPre, int nPost, int* fused, int* group);
 /* ncycles V-cycles back to back, x <- multigrid_v_cycle(H, x, b): the hot loop of multigrid()
  * (src/solvers.jl:124-126), same arithmetic as ncycles aggmg_vcycle_dev calls.  On block-
  * tridiagonal fine levels the post-smoothing of one cycle and the pre-smoothing of the next run in
@@ -555,6 +570,10 @@ int aggmg_profile_collect(aggmg_ctx* ctx, double* total_ms, int64_t* counts);
  * what = 1 aggmg_residual_dev (sm may be NULL). */
 int aggmg_hier_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int level, int kind, int has_x0, int64_t* read_bytes,
                             int64_t* write_bytes);
+/* compulsory bytes of one K-column fused launch (aggmg_vcycle_multi_dev, kind = AGGMG_KIND_FUSED_DOWN / _UP): the
+ * operator's arrays once, the vectors' once per column -- ncols = 1 gives aggmg_hier_launch_bytes' figures */
+int aggmg_hier_multi_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int level, int kind, int has_x0, int64_t ncols,
+                                  int64_t* read_bytes, int64_t* write_bytes);
 int aggmg_smoother_launch_bytes(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, int what, int64_t* read_bytes,
                                 int64_t* write_bytes);
 

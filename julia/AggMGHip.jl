@@ -377,6 +377,82 @@ function la.ldiv!(Hd::DeviceHierarchy, b::DeviceVector)
     return
 end
 
+# ---- K right-hand sides (EXTENSION: the reference's multigrid_v_cycle / ldiv! take vectors, src/solvers.jl:19,63,84) ----
+# An N x K Float64 matrix in HBM, column-major like a Julia Matrix; same lifetime rule as DeviceVector.  The cycle reads
+# each level's operator once per group of columns (aggmg_vcycle_multi_dev); column j is bit for bit the single-vector
+# cycle of column j.
+mutable struct DeviceMatrix
+    ctx::Context
+    p::Ptr{Cvoid}
+    n::Int
+    k::Int
+    function DeviceMatrix(ctx::Context, n::Integer, k::Integer)
+        (k >= 1) || throw(ArgumentError("DeviceMatrix: needs k >= 1 columns"))
+        r = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ctx.h, ccall((:aggmg_dev_alloc, LIB), Cint, (Handle, Int64, Ref{Ptr{Cvoid}}), ctx.h, 8n * k, r))
+        M = new(ctx, r[], n, k)
+        finalizer(free!, M)
+        return M
+    end
+end
+function free!(M::DeviceMatrix)
+    if M.p != C_NULL && M.ctx.h != C_NULL
+        ccall((:aggmg_dev_free, LIB), Cint, (Handle, Ptr{Cvoid}), M.ctx.h, M.p)
+    end
+    M.p = C_NULL
+    return nothing
+end
+function DeviceMatrix(ctx::Context, X::AbstractMatrix)
+    Xm = Matrix{Float64}(X)
+    M = DeviceMatrix(ctx, size(Xm, 1), size(Xm, 2))
+    GC.@preserve M Xm check(ctx.h, ccall((:aggmg_memcpy_h2d, LIB), Cint, (Handle, Ptr{Cvoid}, Ptr{Float64}, Int64),
+        ctx.h, M.p, Xm, 8length(Xm)))
+    return M
+end
+Base.size(M::DeviceMatrix) = (M.n, M.k)
+function download(M::DeviceMatrix)
+    out = Matrix{Float64}(undef, M.n, M.k)
+    GC.@preserve M out check(M.ctx.h, ccall((:aggmg_memcpy_d2h, LIB), Cint, (Handle, Ptr{Float64}, Ptr{Cvoid}, Int64),
+        M.ctx.h, out, M.p, 8length(out)))
+    return out
+end
+Base.Matrix(M::DeviceMatrix) = download(M)
+Base.Array(M::DeviceMatrix) = download(M)
+
+# the cycle on device matrices: a new DeviceMatrix comes back, X0 / B are left as they are
+function multigrid_v_cycle(Hd::DeviceHierarchy, X0::DeviceMatrix, B::DeviceMatrix;
+        nPre::Integer = 3, nPost::Integer = 3, alpha::AbstractFloat = 2.0 / 3.0)
+    (size(X0) == size(B)) || throw(DimensionMismatch("multigrid_v_cycle: X0 and B differ in size"))
+    X = DeviceMatrix(Hd.ctx, B.n, B.k)
+    GC.@preserve X0 B X check(Hd.ctx.h, ccall((:aggmg_vcycle_multi_dev, LIB), Cint,
+        (Handle, Handle, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Cint, Float64, Ptr{Cvoid}),
+        Hd.ctx.h, Hd.h, X0.p, B.p, B.k, B.n, nPre, nPost, Float64(alpha), X.p))
+    return X
+end
+# host matrices: through device copies, a new Matrix comes back
+function multigrid_v_cycle(Hd::DeviceHierarchy, X0::AbstractMatrix, B::AbstractMatrix;
+        nPre::Integer = 3, nPost::Integer = 3, alpha::AbstractFloat = 2.0 / 3.0)
+    (size(X0) == size(B)) || throw(DimensionMismatch("multigrid_v_cycle: X0 and B differ in size"))
+    X = multigrid_v_cycle(Hd, DeviceMatrix(Hd.ctx, X0), DeviceMatrix(Hd.ctx, B); nPre = nPre, nPost = nPost, alpha = alpha)
+    return download(X)
+end
+# ldiv!(Y, H, B) with matrices: one K-column cycle from zero guesses (Y must not be B on the device)
+function la.ldiv!(Y::DeviceMatrix, Hd::DeviceHierarchy, B::DeviceMatrix)
+    (size(Y) == size(B)) || throw(DimensionMismatch("ldiv!: Y and B differ in size"))
+    GC.@preserve B Y check(Hd.ctx.h, ccall((:aggmg_vcycle_multi_dev, LIB), Cint,      # X0 = C_NULL: zero guesses
+        (Handle, Handle, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Cint, Float64, Ptr{Cvoid}),
+        Hd.ctx.h, Hd.h, C_NULL, B.p, B.k, B.n, 3, 3, 2.0 / 3.0, Y.p))
+    return
+end
+function la.ldiv!(Y::AbstractMatrix, Hd::DeviceHierarchy, B::AbstractMatrix)
+    (size(Y) == size(B)) || throw(DimensionMismatch("ldiv!: Y and B differ in size"))
+    Bd = DeviceMatrix(Hd.ctx, B)
+    Yd = DeviceMatrix(Hd.ctx, size(B, 1), size(B, 2))
+    la.ldiv!(Yd, Hd, Bd)
+    Y[:, :] = download(Yd)
+    return
+end
+
 # ldiv!(H, b) (overwrites b) / ldiv!(y, H, b): src/solvers.jl:63-92 -- one V-cycle from a zero guess
 function la.ldiv!(Hd::DeviceHierarchy, b::AbstractVector)
     b[:] = multigrid_v_cycle(Hd, zeros(size(Hd.H.mStiffness[1], 1)), b); return
