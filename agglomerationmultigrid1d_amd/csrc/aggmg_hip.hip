@@ -522,6 +522,8 @@ struct BtdTile {
   static constexpr int NS = (M == 1) ? 2 : (M == 2) ? AGGMG_NS2 : (M == 3) ? 3 : (M == 4) ? AGGMG_NS4 : (M <= 7) ? 3 : 2;
   static constexpr int EPS = NT / M;
   static constexpr int TE = EPS * NS;
+  static constexpr int kM = M;
+  static constexpr bool kCmp = CMP;
 };
 
 // Which tiles of a level a launch covers: all of them, only those holding elements [0, head) and
@@ -556,22 +558,16 @@ static int launch_btd_t(aggmg_ctx* ctx, FusedArgs a, int halo, const TileSel& se
   const bool vr = (a.lf_out || a.ld_out) && a.par_out;
   const int align = ((a.lf_out || a.ld_out) && !vr) ? a.rho_out : 1;
   if (a.gs) halo += a.nsweeps;  // two half-sweeps per sweep, one element of halo each
-  int shift = 0;
-  if (vr) {
-    if (sel.mode == 1 || sel.mode == 2) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "tile selection on a level with agglomerates of different sizes");
-    if (a.agg_shift >= 0 && T::TE - 2 * halo - a.agg_shift >= T::TE / 2) {
-      shift = a.agg_shift;  // owned ranges on agglomerate boundaries: plain stores
-    } else {
-      a.agg_shift = -1;     // agglomerates cut by a tile boundary are summed from two tiles
-      HIPCHK(hipMemsetAsync(a.rc_out, 0, (size_t)a.nec_out * a.mc_out * sizeof(double), ctx->stream));
-    }
-  } else {
-    a.agg_shift = -1;
-  }
-  int owned = ((T::TE - 2 * halo - shift) / align) * align;
+  if (vr && (sel.mode == 1 || sel.mode == 2))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "tile selection on a level with agglomerates of different sizes");
+  const FusedTilePlan plan = fused_tile_plan(T::TE, halo, align, vr, a.agg_shift);   // host_plan.hpp
+  a.agg_shift = plan.agg_shift;
+  if (vr && plan.agg_shift < 0)   // agglomerates cut by a tile boundary are summed from two tiles
+    HIPCHK(hipMemsetAsync(a.rc_out, 0, (size_t)a.nec_out * a.mc_out * sizeof(double), ctx->stream));
+  const int owned = plan.owned;
   if (owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "fused tile too small for the requested halo");
   a.owned = owned;
-  a.halo_left = halo + shift;
+  a.halo_left = plan.halo_left;
   const TileSubset sub = fused_tile_subset(a.lv.ne, owned, sel.mode == 3 ? 0 : sel.mode, sel.head, sel.tail);   // host_plan.hpp (3: every tile)
   const int64_t ntiles = sub.ntiles;
   a.tile_split = sub.split;
@@ -631,39 +627,42 @@ static int btd_max_halo() {
   return (BtdTile<M, CMP>::TE - 8) / 2;
 }
 
-static int launch_btd(aggmg_ctx* ctx, const BtdDev& b, const FusedArgs& a, int halo, const TileSel& sel = TileSel(),
-                      int64_t* ntiles_out = nullptr) {
-#define CASE(MM)                                             \
-  case MM:                                                   \
-    return b.cmp ? launch_btd_t<MM, true>(ctx, a, halo, sel, ntiles_out) \
-                 : launch_btd_t<MM, false>(ctx, a, halo, sel, ntiles_out);
-#define CASE_C(MM) \
-  case MM:         \
-    return launch_btd_t<MM, true>(ctx, a, halo, sel, ntiles_out);
+// The (M, CMP) the fused kernel is instantiated for, the one list of them: f(BtdTile<M, CMP>()) for the form that
+// serves b; false when there is none.
+template <class F>
+static bool btd_with_tile(const BtdDev& b, F&& f) {
+#define CASE(MM)                        \
+  case MM:                              \
+    if (b.cmp) f(BtdTile<MM, true>());  \
+    else f(BtdTile<MM, false>());       \
+    return true;
+#define CASE_C(MM)           \
+  case MM:                   \
+    f(BtdTile<MM, true>());  \
+    return true;
   switch (b.m) {
     case 1:
-      return launch_btd_t<1, false>(ctx, a, halo, sel, ntiles_out);
+      f(BtdTile<1, false>());
+      return true;
       CASE(2) CASE(3) CASE(4) CASE(5) CASE_C(6) CASE_C(7) CASE_C(8) CASE_C(9)
-    default:
-      return fail(ctx, AGGMG_ERR_UNSUPPORTED, "block size not instantiated for the fused kernel");
   }
 #undef CASE
 #undef CASE_C
+  return false;
+}
+
+static int launch_btd(aggmg_ctx* ctx, const BtdDev& b, const FusedArgs& a, int halo, const TileSel& sel = TileSel(),
+                      int64_t* ntiles_out = nullptr) {
+  int rc = AGGMG_OK;
+  if (!btd_with_tile(b, [&](auto t) { rc = launch_btd_t<decltype(t)::kM, decltype(t)::kCmp>(ctx, a, halo, sel, ntiles_out); }))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "block size not instantiated for the fused kernel");
+  return rc;
 }
 
 static int btd_tile_elems(const BtdDev& b) {
-  switch (b.m) {
-    case 1: return BtdTile<1, false>::TE;
-    case 2: return BtdTile<2, false>::TE;
-    case 3: return BtdTile<3, false>::TE;
-    case 4: return BtdTile<4, false>::TE;
-    case 5: return BtdTile<5, false>::TE;
-    case 6: return BtdTile<6, true>::TE;
-    case 7: return BtdTile<7, true>::TE;
-    case 8: return BtdTile<8, true>::TE;
-    case 9: return BtdTile<9, true>::TE;
-  }
-  return 0;
+  int te = 0;
+  btd_with_tile(b, [&](auto t) { te = decltype(t)::TE; });
+  return te;
 }
 
 static FusedArgs btd_args(const BtdDev& b) {
@@ -671,6 +670,58 @@ static FusedArgs btd_args(const BtdDev& b) {
   std::memset(&a, 0, sizeof(a));
   a.lv = BtdLevel{b.binv, b.dblk, b.bsym, b.dup, b.corr, b.scol, b.pcol, b.qrow, b.sub, b.sup, b.P, b.Q, b.ne, b.c_sub, b.r_sup};
   return a;
+}
+
+// ---- the arguments of a fused launch, part by part: every launch has the sweeps; an ascent adds the prolongation in
+// front of them, a descent the residual and its restriction behind them, a launch between two cycles both -----------
+// gs: 0 block Jacobi, 1 red-black Gauss-Seidel even elements first, 2 odd ones first
+static FusedArgs fused_sweeps(const BtdDev& b, const double* u_in, const double* rhs, double* u_out, double alpha, int nsweeps,
+                              int gs = 0) {
+  FusedArgs a = btd_args(b);
+  a.u_in = u_in;
+  a.b = rhs;
+  a.u_out = u_out;
+  a.alpha = alpha;
+  a.nsweeps = nsweeps;
+  a.gs = gs;
+  return a;
+}
+// u_in + L uc before the sweeps
+static void fused_ascent(FusedArgs& a, const Level& l, const double* uc) {
+  a.lf_in = l.tb->lf;
+  a.uc = uc;
+  xfer_in(a, *l.tb);
+}
+// lf applied to r, or (L'D) applied to B^{-1} r (the kernel then reads neither D nor L): the one place that chooses
+static bool restrict_with_ld(const aggmg_hier* h, const Level& l) {
+  return l.tb->ld && h->restriction == AGGMG_RESTRICT_PRECONDITIONED;
+}
+// rc = L' (b - A u) after the sweeps
+static void fused_descent(FusedArgs& a, const aggmg_hier* h, const Level& l, double* rc) {
+  a.do_residual = 1;
+  if (restrict_with_ld(h, l))
+    a.ld_out = l.tb->ld;
+  else
+    a.lf_out = l.tb->lf;
+  a.rc_out = rc;
+  xfer_out(a, *l.tb);
+}
+// Which restriction modes a fused descent serves, caller by caller.  vcycle_down takes any: without (L'D) it restricts
+// with lf whatever the mode.  The launch between two cycles (aggmg_vcycles_dev) wants the mode's own form to exist;
+// the checkpointed one (aggmg_multigrid_dev) forms residual rows for its norms and takes the explicit form alone.
+static bool vcycles_restriction_ok(const aggmg_hier* h, const Level& l) {
+  return l.tb->ld || h->restriction == AGGMG_RESTRICT_EXPLICIT;
+}
+static bool multigrid_restriction_ok(const aggmg_hier* h) { return h->restriction == AGGMG_RESTRICT_EXPLICIT; }
+
+// Checkpoints of a launch (the checkpoint variants of the fused kernel and of the chain kernel): after `sweep`,
+// sweep + stride, ... sweeps, and (final) after the last one; ntiles comes back from the launch.
+static void fused_chk(FusedArgs& a, const CgtChk& c) {
+  a.chk_sweep = c.sweep;
+  a.chk_stride = c.stride;
+  a.chk_final = c.final;
+  a.chk_exact = c.exact;
+  a.chk_part = c.part;
 }
 
 // Max sweeps fused into one launch: the halo costs 2*S/TE redundant work.
@@ -708,13 +759,7 @@ static int btd_smooth(aggmg_ctx* ctx, const BtdDev& b, const double* u_in, const
   for (int c = 0; c < nchunks; ++c) {
     const int s = std::min(left, smax);
     double* dst = (c == nchunks - 1) ? u_out : (((nchunks - 1 - c) % 2 == 1) ? t0 : t1);
-    FusedArgs a = btd_args(b);
-    a.u_in = src;
-    a.b = rhs;
-    a.u_out = dst;
-    a.alpha = alpha;
-    a.nsweeps = s;
-    a.gs = gs;
+    const FusedArgs a = fused_sweeps(b, src, rhs, dst, alpha, s, gs);
     {
       ProfScope ps(ctx, AGGMG_KIND_SMOOTH, level);
       CHECK(launch_btd(ctx, b, a, s));
@@ -884,9 +929,7 @@ extern "C" int aggmg_residual_dev(aggmg_ctx* ctx, aggmg_op* A, const double* u, 
   ProfScope ps(ctx, AGGMG_KIND_RESIDUAL, 0);
   if (A->cgt && r_out != u && r_out != b) return cgt_residual_ext(ctx, *A->cgt, u, b, r_out);
   if (A->btd && r_out != u && r_out != b) {  // index-free block-tridiagonal form, one fused pass
-    FusedArgs a = btd_args(*A->btd);
-    a.u_in = u;
-    a.b = b;
+    FusedArgs a = fused_sweeps(*A->btd, u, b, nullptr, 0.0, 0);
     a.do_residual = 1;
     a.r_out = r_out;
     return launch_btd(ctx, *A->btd, a, 1);
@@ -1570,20 +1613,17 @@ static int launch_pair_down(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPre, doub
   Level& b = h->lv[k + 1];
   Level& c = h->lv[k + 2];
   PairArgs p = pair_args(h, k, alpha, nPre);
-  const int hh = nPre + 1;
-  int te_b = std::min(kPairTEB, (kPairTEA - 2 * hh) / p.ab.rho);
-  const int own = ((te_b - 2 * hh) / p.bc.rho) * p.bc.rho;
-  if (own <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: paired tile too small");
-  te_b = own + 2 * hh;
-  p.own = own;
-  p.te_b = te_b;
-  p.te_a = te_b * p.ab.rho + 2 * hh;
+  const PairTilePlan plan = pair_down_plan(nPre, p.ab.rho, p.bc.rho, kPairTEA, kPairTEB);   // host_plan.hpp
+  if (plan.own <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: paired tile too small");
+  p.own = plan.own;
+  p.te_b = plan.te_b;
+  p.te_a = plan.te_a;
   p.rhs_a = a.rhs;
   p.u_a = a.u[0];
   p.rhs_b = b.rhs;
   p.u_b = b.u[0];
   p.rhs_c = c.rhs;
-  const int64_t ntiles = (p.B.ne + own - 1) / own;
+  const int64_t ntiles = (p.B.ne + plan.own - 1) / plan.own;
   if (ntiles == 0) return AGGMG_OK;
   const size_t lds = ((size_t)2 * (kPairTEA + 2) * kPairM + (size_t)kPairTEB * 2) * sizeof(double);
   ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
@@ -1604,14 +1644,12 @@ static int launch_pair_up(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPost, doubl
   Level& b = h->lv[k + 1];
   Level& c = h->lv[k + 2];
   PairArgs p = pair_args(h, k, alpha, nPost);
-  const int rhoA = p.ab.rho, rhoB = p.bc.rho;
-  p.hb = (nPost + rhoA - 1) / rhoA;
-  int own = std::min(kPairTEA - 2 * nPost, (kPairTEB - 2 * p.hb - 2 * nPost) * rhoA);
-  own = (own / rhoA) * rhoA;
-  if (own <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: paired tile too small");
-  p.own = own;
-  p.te_a = own + 2 * nPost;
-  p.te_b = own / rhoA + 2 * p.hb + 2 * nPost;
+  PairTilePlan plan = pair_up_plan(nPost, p.ab.rho, kPairTEA, kPairTEB);   // host_plan.hpp
+  if (plan.own <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: paired tile too small");
+  p.hb = plan.hb;
+  p.own = plan.own;
+  p.te_a = plan.te_a;
+  p.te_b = plan.te_b;
   p.rhs_a = a.rhs;
   p.rhs_b_in = b.rhs;
   p.ua_in = a.u[0];
@@ -1619,23 +1657,16 @@ static int launch_pair_up(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPost, doubl
   p.uc = (k + 2 == n - 1) ? c.u[0] : c.u[1];
   p.u_a = dst;
   p.ub_out = nullptr;   // nothing reads the post-smoothed iterate of level k + 1 but level k's prolongation
-  const int64_t all = (p.A.ne + own - 1) / own;
-  int64_t ntiles = all;
-  if (part != 0) {
-    // tile t prolongs from the elements floor(Eb0 / rho_b) .. floor((Eb0 + te_b - 1) / rho_b) of level k + 2 (clipped to
-    // the level): tiles are ordered, so the ones touching the ghosts are a prefix and a suffix
-    auto jmin = [&](int64_t t) { return std::max<int64_t>((t * own) / rhoA - p.hb - nPost, 0) / rhoB; };
-    auto jmax = [&](int64_t t) { return std::min<int64_t>((t * own) / rhoA - p.hb - nPost + p.te_b - 1, p.B.ne - 1) / rhoB; };
-    int64_t tA = 0, tB = 0;
-    while (tA < all && jmin(tA) < gh_lo) ++tA;
-    while (tB < all - tA && jmax(all - 1 - tB) >= p.bc.nec - gh_hi) ++tB;
+  int64_t ntiles = (p.A.ne + plan.own - 1) / plan.own;
+  if (part != 0) {   // the tiles touching the ghosts: a prefix tA and a suffix tB
+    pair_up_split(&plan, nPost, p.ab.rho, p.bc.rho, p.A.ne, p.bc.nec, gh_lo, gh_hi);
     if (part == 1) {
-      p.tile_split = (int)tA;
-      p.tile_skip = all - tA - tB;
-      ntiles = tA + tB;
+      p.tile_split = (int)plan.tA;
+      p.tile_skip = plan.all - plan.tA - plan.tB;
+      ntiles = plan.tA + plan.tB;
     } else {
-      p.tile_skip = tA;
-      ntiles = all - tA - tB;
+      p.tile_skip = plan.tA;
+      ntiles = plan.all - plan.tA - plan.tB;
     }
   }
   if (ntiles == 0) return AGGMG_OK;
@@ -1681,20 +1712,9 @@ static int vcycle_down(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const do
     }
     const bool structured = l.S->btd && l.S->A == l.A;
     if (structured && l.tb && btd_fits(*l.S, nPre, 1)) {
-      FusedArgs a = btd_args(*l.S->btd);
-      a.u_in = uin;
-      a.b = rhs;
-      a.u_out = l.u[0];
-      a.alpha = alpha;
-      a.nsweeps = nPre;
-      a.gs = l.S->gs ? 1 : 0;  // pre-smoothing: even elements, then odd ones
-      a.do_residual = 1;
-      if (l.tb->ld && h->restriction == AGGMG_RESTRICT_PRECONDITIONED)
-        a.ld_out = l.tb->ld;  // restrict B^{-1} r with (L'D): the kernel then reads neither D nor L
-      else
-        a.lf_out = l.tb->lf;
-      a.rc_out = c.rhs;
-      xfer_out(a, *l.tb);
+      // (Gauss-Seidel pre-smoothing: even elements, then odd ones)
+      FusedArgs a = fused_sweeps(*l.S->btd, uin, rhs, l.u[0], alpha, nPre, l.S->gs ? 1 : 0);
+      fused_descent(a, h, l, c.rhs);
       ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
       CHECK(launch_btd(ctx, *l.S->btd, a, nPre + 1));
     } else {
@@ -1783,16 +1803,9 @@ static int vcycle_up(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, 
     }
     const bool structured = l.S->btd && l.S->A == l.A;
     if (structured && l.tb && btd_fits(*l.S, nPost, 0)) {
-      FusedArgs a = btd_args(*l.S->btd);
-      a.u_in = l.u[0];
-      a.b = rhs;
-      a.u_out = dst;
-      a.alpha = alpha;
-      a.nsweeps = nPost;
-      a.gs = l.S->gs ? 2 : 0;  // post-smoothing in the reverse colour order: the cycle stays symmetric
-      a.lf_in = l.tb->lf;
-      a.uc = uc;
-      xfer_in(a, *l.tb);
+      // (Gauss-Seidel post-smoothing in the reverse colour order: the cycle stays symmetric)
+      FusedArgs a = fused_sweeps(*l.S->btd, l.u[0], rhs, dst, alpha, nPost, l.S->gs ? 2 : 0);
+      fused_ascent(a, l, uc);
       ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
       CHECK(launch_btd(ctx, *l.S->btd, a, std::max(nPost, 0), k == 0 ? sel : TileSel()));
     } else {
@@ -1882,7 +1895,7 @@ static bool multi_level_ok(const aggmg_hier* h, int k, int nPre, int nPost) {
   if (!btd_fits(*l.S, nPre, 1) || !btd_fits(*l.S, nPost, 0)) return false;
   // ... and the K-column tile holds the same halos
   const int te = kMultiNT / b.m;
-  return ((te - 2 * (nPre + 1)) / t.rho) * t.rho > 0 && te - 2 * nPost > 0;
+  return multi_tile_owned(te, nPre + 1, t.rho) > 0 && multi_tile_owned(te, nPost, 1) > 0;
 }
 
 static bool multi_ok(const aggmg_hier* h, int nPre, int nPost) {
@@ -1897,7 +1910,7 @@ template <int M, bool CMP, bool SYM>
 static int launch_multi_t(aggmg_ctx* ctx, MultiArgs m, int halo) {
   constexpr int TE = kMultiNT / M;
   const int align = m.a.lf_out ? m.a.rho_out : 1;
-  const int owned = ((TE - 2 * halo) / align) * align;
+  const int owned = multi_tile_owned(TE, halo, align);   // host_plan.hpp, as multi_level_ok
   if (owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column tile too small for the requested halo");
   m.a.owned = owned;
   m.a.halo_left = halo;
@@ -1962,20 +1975,13 @@ static int vcycle_multi_group(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, c
     Level& c = h->lv[k + 1];
     MultiArgs m;
     std::memset(&m, 0, sizeof(m));
-    m.a = btd_args(*l.S->btd);
+    // u[k] = zeros for k > 1 (:29-31)
+    m.a = fused_sweeps(*l.S->btd, k == 0 ? X0 : nullptr, k == 0 ? B : h->mu[k][2], h->mu[k][0], alpha, nPre);
+    fused_descent(m.a, h, l, h->mu[k + 1][2]);   // (lf: multi_level_ok refuses the levels that would take (L'D))
     m.kc = kc;
-    m.a.u_in = k == 0 ? X0 : nullptr;   // u[k] = zeros for k > 1 (:29-31)
     m.ld_uin = ld;
-    m.a.b = k == 0 ? B : h->mu[k][2];
     m.ld_b = k == 0 ? ld : l.N;
-    m.a.u_out = h->mu[k][0];
     m.ld_uout = l.N;
-    m.a.alpha = alpha;
-    m.a.nsweeps = nPre;
-    m.a.do_residual = 1;
-    m.a.lf_out = l.tb->lf;
-    xfer_out(m.a, *l.tb);
-    m.a.rc_out = h->mu[k + 1][2];
     m.ld_rc = c.N;
     ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
     CHECK(launch_multi(ctx, *l.S->btd, m, nPre + 1));
@@ -1989,20 +1995,13 @@ static int vcycle_multi_group(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, c
     Level& c = h->lv[k + 1];
     MultiArgs m;
     std::memset(&m, 0, sizeof(m));
-    m.a = btd_args(*l.S->btd);
+    m.a = fused_sweeps(*l.S->btd, h->mu[k][0], k == 0 ? B : h->mu[k][2], k == 0 ? X : h->mu[k][1], alpha, nPost);
+    fused_ascent(m.a, l, (k + 1 == n - 1) ? h->mu[k + 1][0] : h->mu[k + 1][1]);
     m.kc = kc;
-    m.a.u_in = h->mu[k][0];
     m.ld_uin = l.N;
-    m.a.b = k == 0 ? B : h->mu[k][2];
     m.ld_b = k == 0 ? ld : l.N;
-    m.a.u_out = k == 0 ? X : h->mu[k][1];
     m.ld_uout = k == 0 ? ld : l.N;
-    m.a.alpha = alpha;
-    m.a.nsweeps = nPost;
-    m.a.lf_in = l.tb->lf;
-    m.a.uc = (k + 1 == n - 1) ? h->mu[k + 1][0] : h->mu[k + 1][1];
     m.ld_uc = c.N;
-    xfer_in(m.a, *l.tb);
     ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
     CHECK(launch_multi(ctx, *l.S->btd, m, nPost));
   }
@@ -2054,12 +2053,118 @@ extern "C" int aggmg_hier_multi_info(aggmg_ctx* ctx, const aggmg_hier* h, int64_
   return AGGMG_OK;
 }
 
-// ncycles V-cycles back to back, x <- V(x, b): the hot loop of multigrid() (src/solvers.jl:124-126).
+// ---- the cycle sequence of aggmg_vcycles_dev and aggmg_multigrid_dev ------------------------------------------------
 // Between two cycles the fine level runs post-smoothing of cycle i and pre-smoothing of cycle i+1
 // on the same iterate with the same right-hand side, so both go into ONE fused launch
 // (prolongation-add -> nPost + nPre sweeps -> restriction): the fine operator is read once per
 // cycle instead of twice and the intermediate iterates never travel to HBM.  The arithmetic is
 // that of ncycles separate aggmg_vcycle_dev calls.
+
+// levels 1.. of one cycle: rhs_1 is in lv[1].rhs (descend) or every right-hand side is in place already; result u_1
+static int coarse_levels(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPre, int nPost, double alpha, bool descend) {
+  const int n = (int)h->lv.size();
+  if (descend) CHECK(vcycle_down(ctx, h, nullptr, b, nPre, alpha, 1));
+  Level& c = h->lv[n - 1];
+  CHECK(coarse_solve(ctx, h, c.rhs, c.u[0]));
+  if (n > 2) CHECK(vcycle_up(ctx, h, b, nPost, alpha, nullptr, 1));
+  return AGGMG_OK;
+}
+
+// upper bounds of the tiles of a checkpoint launch (its partial sums: two doubles per tile and checkpoint)
+static int64_t btd_chk_tiles(const BtdDev& b) { return 2 * b.ne / std::max(btd_tile_elems(b), 1) + 2; }
+static int64_t cgt_chk_tiles(const CgtDev& g) { return 4 * g.ne / std::max(cgt_tile_blocks(g.m), 1) + 2; }
+
+// The fine level of the sequence: the fused block-tridiagonal kernel, or the chain kernel of a CG mesh (cgt.hip).
+// chk: the launch forms a checkpoint's sums and reports its tile count there.
+struct FineLevel {
+  aggmg_ctx* ctx;
+  aggmg_hier* h;
+  const double* b;
+  int nPre, nPost;
+  double alpha;
+  bool chain;
+  Level& l0() const { return h->lv[0]; }
+  const double* uc() const { return h->lv.size() == 2 ? h->lv[1].u[0] : h->lv[1].u[1]; }
+  // post-smoothing of one cycle, pre-smoothing and restriction of the next: cur -> alt
+  int mid(const double* cur, double* alt, CgtChk* chk) const {
+    if (chain) return cgt_mid(ctx, h, cur, alt, b, nPost + nPre, alpha, chk);
+    const BtdDev& B0 = *l0().S->btd;
+    FusedArgs a = fused_sweeps(B0, cur, b, alt, alpha, nPost + nPre);
+    fused_ascent(a, l0(), uc());
+    fused_descent(a, h, l0(), h->lv[1].rhs);
+    if (chk) fused_chk(a, *chk);
+    ProfScope ps(ctx, AGGMG_KIND_FUSED_MID, 0);
+    return launch_btd(ctx, B0, a, nPost + nPre + 1, TileSel(), chk ? &chk->ntiles : nullptr);
+  }
+  // the ascent alone: src -> dst
+  int up(const double* src, double* dst, CgtChk* chk) const {
+    if (chain) return cgt_up(ctx, h, 0, b, nPost, alpha, dst, src, chk);
+    const BtdDev& B0 = *l0().S->btd;
+    FusedArgs a = fused_sweeps(B0, src, b, dst, alpha, nPost);
+    fused_ascent(a, l0(), uc());
+    if (chk) fused_chk(a, *chk);
+    ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, 0);
+    // (a checkpoint here forms residual rows of the FINAL iterate: one more element of halo, as a residual)
+    return launch_btd(ctx, B0, a, nPost + (chk ? 1 : 0), TileSel(), chk ? &chk->ntiles : nullptr);
+  }
+  int64_t chk_tiles() const { return chain ? cgt_chk_tiles(*l0().S->cgt) : btd_chk_tiles(*l0().S->btd); }
+};
+
+// Histories and stopping test of launches with checkpoints (with the outer solver loops below)
+struct ChkHist {
+  double *part = nullptr, *mid = nullptr, *sc = nullptr;   // on the device: tile sums, their partial reduction, the norms
+  const double* u_exact = nullptr;
+  double tol_nb = 0.0;
+  double *res = nullptr, *err = nullptr;
+  int checks = 0;
+};
+static int chk_collect(aggmg_ctx* ctx, ChkHist& H, int nchk, int64_t ntiles, int* met);
+
+// ncycles cycles from x0 into x_out.  H (or null: no checks): the residual test (and the error norm) of every
+// check_every-th cycle and of the last one are formed INSIDE the fine-level launch that post-smooths it; the loop stops
+// at the first one that meets the tolerance.  *done: the cycles run.
+static int cycle_loop(const FineLevel& f, const double* x0, int ncycles, double* x_out, int check_every, ChkHist* H, int* done) {
+  aggmg_ctx* ctx = f.ctx;
+  aggmg_hier* h = f.h;
+  h->last_coarse_ms = 0.0;
+  CHECK(vcycle_down(ctx, h, x0, f.b, f.nPre, f.alpha, 0));                    // cycle 1: every level down ...
+  CHECK(coarse_levels(ctx, h, f.b, f.nPre, f.nPost, f.alpha, false));         // ... the coarsest solve and the coarser levels up
+  double* cur = f.l0().u[0];   // pre-smoothed fine iterate of the current cycle
+  double* alt = f.l0().u[1];
+  for (int it = 1; it <= ncycles; ++it) {
+    const bool last = it == ncycles;
+    const bool check = H && ((it % check_every == 0) || last);
+    CgtChk chk;   // one checkpoint per launch: x_it, after the post-smoothing
+    if (check) {
+      chk.sweep = f.nPost;
+      chk.exact = H->u_exact;
+      chk.part = H->part;
+    }
+    if (!last) {
+      CHECK(f.mid(cur, alt, check ? &chk : nullptr));
+      std::swap(cur, alt);
+    } else {       // the last ascent: its result is x_ncycles
+      CHECK(f.up(cur, x_out, check ? &chk : nullptr));
+    }
+    if (done) *done = it;
+    if (check) {
+      int met = -1;
+      CHECK(chk_collect(ctx, *H, 1, chk.ntiles, &met));
+      if (met >= 0) {   // src/solvers.jl:131
+        // x_it passed through LDS only (no store per checked cycle: 8 B/DoF saved every time).  The launch's input --
+        // the pre-smoothed iterate of cycle `it`, now in alt -- and the coarse correction are untouched: the
+        // ascent once more, alone, gives x_it with the same arithmetic
+        if (!last) CHECK(f.up(alt, x_out, nullptr));
+        break;
+      }
+    }
+    if (!last) CHECK(coarse_levels(ctx, h, f.b, f.nPre, f.nPost, f.alpha, true));
+  }
+  return AGGMG_OK;
+}
+
+// ncycles V-cycles back to back, x <- V(x, b): the hot loop of multigrid() (src/solvers.jl:124-126) -- cycle_loop
+// without checks where the fine level has a fused launch between two cycles.
 extern "C" int aggmg_vcycles_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const double* b, int ncycles,
                                  int nPre, int nPost, double alpha, double* x_out) {
   CHECK(vcycle_args(ctx, h, x0, b, nPre, nPost));
@@ -2069,97 +2174,21 @@ extern "C" int aggmg_vcycles_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycles: hierarchy was created with AGGMG_COARSE_EXTERNAL");
   const int n = (int)h->lv.size();
   Level& l0 = h->lv[0];
-  const bool fusable = n >= 2 && l0.S && l0.S->btd && l0.S->A == l0.A && l0.tb && (l0.tb->ld || h->restriction == AGGMG_RESTRICT_EXPLICIT) &&
+  const bool fusable = n >= 2 && l0.S && l0.S->btd && l0.S->A == l0.A && l0.tb && vcycles_restriction_ok(h, l0) &&
                        btd_fits(*l0.S, nPre + nPost, 1) && !l0.S->gs;
-  if (n >= 2 && l0.cgt_fused && ncycles > 1 && l0.S->cgt->sw != 3) {
-    // CG chain fine level: the same cross-cycle fusion with the chain kernel
-    h->last_coarse_ms = 0.0;
-    auto rest = [&]() -> int {  // levels 1.. of one cycle (their right-hand side is in place)
-      Level& c = h->lv[n - 1];
-      CHECK(coarse_solve(ctx, h, c.rhs, c.u[0]));
-      if (n > 2) CHECK(vcycle_up(ctx, h, b, nPost, alpha, nullptr, 1));
-      return AGGMG_OK;
-    };
-    CHECK(vcycle_down(ctx, h, x0, b, nPre, alpha, 0));
-    CHECK(rest());
-    double* cur = l0.u[0];
-    double* alt = l0.u[1];
-    for (int cyc = 1; cyc < ncycles; ++cyc) {
-      CHECK(cgt_mid(ctx, h, cur, alt, b, nPost + nPre, alpha));
-      std::swap(cur, alt);
-      CHECK(vcycle_down(ctx, h, nullptr, b, nPre, alpha, 1));
-      CHECK(rest());
-    }
-    return cgt_up(ctx, h, 0, b, nPost, alpha, x_out, cur);
-  }
-  if (!fusable || ncycles == 1) {
-    // plain sequence; intermediate iterates ping-pong between two vectors owned by the hierarchy
-    if (ncycles > 1)
-      for (double*& p : h->cyc)
-        if (!p) HIPCHK(hipMalloc((void**)&p, (size_t)std::max<int64_t>(l0.N, 1) * sizeof(double)));
-    const double* src = x0;
-    for (int c = 0; c < ncycles; ++c) {
-      double* dst = (c == ncycles - 1) ? x_out : h->cyc[c & 1];
-      CHECK(aggmg_vcycle_dev(ctx, h, src, b, nPre, nPost, alpha, dst));
-      src = dst;
-    }
-    return AGGMG_OK;
-  }
-  h->last_coarse_ms = 0.0;
-  Level& c1 = h->lv[1];
-  auto coarse_part = [&]() -> int {  // levels 1.. of one cycle: rhs_1 is in c1.rhs, result u_1
-    CHECK(vcycle_down(ctx, h, nullptr, b, nPre, alpha, 1));
-    Level& c = h->lv[n - 1];
-    CHECK(coarse_solve(ctx, h, c.rhs, c.u[0]));
-    if (n > 2) CHECK(vcycle_up(ctx, h, b, nPost, alpha, nullptr, 1));
-    return AGGMG_OK;
-  };
-  const double* uc = (1 == n - 1) ? c1.u[0] : c1.u[1];
-  CHECK(vcycle_down(ctx, h, x0, b, nPre, alpha, 0));  // cycle 1, level 0 .. then levels >= 1 below
-  // (vcycle_down with k_first = 0 already descended all levels)
-  {
-    Level& c = h->lv[n - 1];
-    CHECK(coarse_solve(ctx, h, c.rhs, c.u[0]));
-    if (n > 2) CHECK(vcycle_up(ctx, h, b, nPost, alpha, nullptr, 1));
-  }
-  double* cur = l0.u[0];  // pre-smoothed fine iterate of the current cycle
-  double* alt = l0.u[1];
-  for (int cyc = 1; cyc < ncycles; ++cyc) {
-    FusedArgs a = btd_args(*l0.S->btd);
-    a.u_in = cur;
-    a.b = b;
-    a.u_out = alt;
-    a.alpha = alpha;
-    a.nsweeps = nPost + nPre;
-    a.lf_in = l0.tb->lf;
-    a.uc = uc;
-    xfer_in(a, *l0.tb);
-    a.do_residual = 1;
-    if (h->restriction == AGGMG_RESTRICT_PRECONDITIONED)
-      a.ld_out = l0.tb->ld;
-    else
-      a.lf_out = l0.tb->lf;
-    a.rc_out = c1.rhs;
-    xfer_out(a, *l0.tb);
-    {
-      ProfScope ps(ctx, AGGMG_KIND_FUSED_MID, 0);
-      CHECK(launch_btd(ctx, *l0.S->btd, a, nPost + nPre + 1));
-    }
-    std::swap(cur, alt);
-    CHECK(coarse_part());
-  }
-  {  // last ascent on the fine level
-    FusedArgs a = btd_args(*l0.S->btd);
-    a.u_in = cur;
-    a.b = b;
-    a.u_out = x_out;
-    a.alpha = alpha;
-    a.nsweeps = nPost;
-    a.lf_in = l0.tb->lf;
-    a.uc = uc;
-    xfer_in(a, *l0.tb);
-    ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, 0);
-    CHECK(launch_btd(ctx, *l0.S->btd, a, nPost));
+  // CG chain fine level: the same cross-cycle fusion with the chain kernel
+  const bool chain = n >= 2 && l0.cgt_fused && ncycles > 1 && l0.S->cgt->sw != 3;
+  if (chain || (fusable && ncycles > 1))
+    return cycle_loop(FineLevel{ctx, h, b, nPre, nPost, alpha, chain}, x0, ncycles, x_out, 0, nullptr, nullptr);
+  // plain sequence; intermediate iterates ping-pong between two vectors owned by the hierarchy
+  if (ncycles > 1)
+    for (double*& p : h->cyc)
+      if (!p) HIPCHK(hipMalloc((void**)&p, (size_t)std::max<int64_t>(l0.N, 1) * sizeof(double)));
+  const double* src = x0;
+  for (int c = 0; c < ncycles; ++c) {
+    double* dst = (c == ncycles - 1) ? x_out : h->cyc[c & 1];
+    CHECK(aggmg_vcycle_dev(ctx, h, src, b, nPre, nPost, alpha, dst));
+    src = dst;
   }
   return AGGMG_OK;
 }
@@ -2738,6 +2767,31 @@ static int chk_reduce(aggmg_ctx* ctx, int nchk, int64_t ntiles, const double* pa
   return AGGMG_OK;
 }
 
+// room for launches of up to nchk_max checkpoints over at most `tiles` tiles; sc: where their norms go
+static int chk_buffers(aggmg_ctx* ctx, int nchk_max, int64_t tiles, double* sc, ChkHist* H) {
+  const int64_t npart = (int64_t)nchk_max * 2 * tiles;
+  CHECK(solv_vec(ctx, 2, npart + (int64_t)nchk_max * 2 * kChkReduceGroups, &H->part));
+  H->mid = H->part + npart;
+  H->sc = sc;
+  return AGGMG_OK;
+}
+
+// The nchk (<= 16) checkpoints of a launch, in order, into the histories up to the first one that meets the tolerance:
+// *met is its index, or -1.
+static int chk_collect(aggmg_ctx* ctx, ChkHist& H, int nchk, int64_t ntiles, int* met) {
+  CHECK(chk_reduce(ctx, nchk, ntiles, H.part, H.mid, H.sc));
+  double host[32];   // per checkpoint: ||A x - b||, ||x - u_exact||
+  HIPCHK(hipMemcpyAsync(host, H.sc, (size_t)2 * nchk * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *met = -1;
+  for (int k = 0; k < nchk && *met < 0; ++k) {
+    if (H.u_exact) H.err[H.checks] = host[2 * k + 1];   // err[i] = ||x - u_exact||, src/solvers.jl:128, :202
+    H.res[H.checks++] = host[2 * k];                    // res[i] = ||A x - b||,      :127, :201
+    if (host[2 * k] < H.tol_nb) *met = k;               // :131, :206
+  }
+  return AGGMG_OK;
+}
+
 extern "C" int aggmg_multigrid_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const double* b, int maxiter,
                                    double tol, int check_every, int nPre, int nPost, double alpha, double* x_out,
                                    double* res_hist, int* n_cycles, int* n_checks, const double* u_exact,
@@ -2772,161 +2826,26 @@ extern "C" int aggmg_multigrid_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* 
   // cross-cycle fusion) -- so a check after every cycle, the reference's semantics (src/solvers.jl:124-131), costs a
   // store of the iterate and a few reductions instead of a residual launch over the fine operator and a cycle without
   // the cross-cycle fusion (AGGMG_OPT_MG_CHECKPOINT = 0: the form below, for A/B runs and tests).
-  const bool use_chk = ctx->mg_checkpoint;
-  {
-    const int n = (int)h->lv.size();
-    Level& l0 = h->lv[0];
-    const bool fusable = n >= 2 && l0.S && l0.S->btd && l0.S->A == l0.A && l0.tb && h->restriction == AGGMG_RESTRICT_EXPLICIT &&
-                         btd_fits(*l0.S, nPre + nPost, 1) && !l0.S->gs && h->coarse_mode != AGGMG_COARSE_EXTERNAL;
-    if (use_chk && fusable) {
-      const BtdDev& B0 = *l0.S->btd;
-      double* part = nullptr;
-      const int64_t npart = 2 * (2 * B0.ne / std::max(btd_tile_elems(B0), 1) + 2);
-      CHECK(solv_vec(ctx, 2, npart + 2 * kChkReduceGroups, &part));
-      double* mid = part + npart;
-      double* sc = ctx->solv_sc + 8;   // [8] ||A x - b||  [9] ||x - u_exact||
-      Level& c1 = h->lv[1];
-      const double* uc = (1 == n - 1) ? c1.u[0] : c1.u[1];
-      auto coarse_part = [&](bool descend) -> int {  // levels 1.. of one cycle: rhs_1 is in c1.rhs, result u_1
-        if (descend) CHECK(vcycle_down(ctx, h, nullptr, b, nPre, alpha, 1));
-        Level& c = h->lv[n - 1];
-        CHECK(coarse_solve(ctx, h, c.rhs, c.u[0]));
-        if (n > 2) CHECK(vcycle_up(ctx, h, b, nPost, alpha, nullptr, 1));
-        return AGGMG_OK;
-      };
-      h->last_coarse_ms = 0.0;
-      CHECK(vcycle_down(ctx, h, x0, b, nPre, alpha, 0));   // cycle 1: every level down ...
-      CHECK(coarse_part(false));                            // ... the coarsest solve and the coarser levels up
-      double* it_cur = l0.u[0];   // pre-smoothed fine iterate of the current cycle
-      double* it_alt = l0.u[1];
-      for (int it = 1; it <= maxiter; ++it) {
-        const bool check = (it % check_every == 0) || it == maxiter;
-        FusedArgs a = btd_args(B0);
-        a.u_in = it_cur;
-        a.b = b;
-        a.alpha = alpha;
-        a.lf_in = l0.tb->lf;
-        a.uc = uc;
-        xfer_in(a, *l0.tb);
-        int64_t ntiles = 0;
-        if (it < maxiter) {   // post-smoothing of cycle `it`, [checkpoint: x_it], pre-smoothing + restriction of cycle it + 1
-          a.u_out = it_alt;
-          a.nsweeps = nPost + nPre;
-          a.do_residual = 1;
-          a.lf_out = l0.tb->lf;
-          a.rc_out = c1.rhs;
-          xfer_out(a, *l0.tb);
-        } else {              // the last ascent: its result is x_maxiter
-          a.u_out = x_out;
-          a.nsweeps = nPost;
-        }
-        if (check) {
-          a.chk_sweep = nPost;
-          a.chk_stride = 1 << 30;   // one checkpoint per launch
-          a.chk_exact = u_exact;
-          a.chk_part = part;
-        }
-        {
-          ProfScope ps(ctx, it < maxiter ? AGGMG_KIND_FUSED_MID : AGGMG_KIND_FUSED_UP, 0);
-          // (the last ascent's checkpoint forms residual rows of the FINAL iterate: one more element of halo, as a residual)
-          CHECK(launch_btd(ctx, B0, a, it < maxiter ? nPost + nPre + 1 : nPost + 1, TileSel(), &ntiles));
-        }
-        if (it < maxiter) std::swap(it_cur, it_alt);
-        done = it;
-        if (check) {
-          CHECK(chk_reduce(ctx, 1, ntiles, part, mid, sc));
-          double host[2] = {0.0, 0.0};
-          HIPCHK(hipMemcpyAsync(host, sc, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-          HIPCHK(hipStreamSynchronize(ctx->stream));
-          if (u_exact) err_hist[checks] = host[1];   // err[i] = ||x - u_exact||, src/solvers.jl:128
-          res_hist[checks++] = host[0];              // res[i] = ||A x - b||,      :127
-          if (host[0] < tol * nb) {                  // :131
-            if (it < maxiter) {
-              // x_it passed through LDS only (no store per checked cycle: 8 B/DoF saved every time).  The launch's input --
-              // the pre-smoothed iterate of cycle `it`, now in it_alt -- and the coarse correction are untouched: the
-              // ascent once more, alone, gives x_it with the same arithmetic
-              FusedArgs f = btd_args(B0);
-              f.u_in = it_alt;
-              f.b = b;
-              f.alpha = alpha;
-              f.lf_in = l0.tb->lf;
-              f.uc = uc;
-              xfer_in(f, *l0.tb);
-              f.u_out = x_out;
-              f.nsweeps = nPost;
-              ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, 0);
-              CHECK(launch_btd(ctx, B0, f, nPost));
-            }
-            break;
-          }
-        }
-        if (it < maxiter) CHECK(coarse_part(true));
-      }
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      *n_cycles = done;
-      *n_checks = checks;
-      return AGGMG_OK;
-    }
-  }
-  {
-    // CG chain fine level (point-Jacobi): the same loop with the chain kernel's checkpoint variant
-    const int n = (int)h->lv.size();
-    Level& l0 = h->lv[0];
-    if (use_chk && n >= 2 && l0.cgt_fused && l0.S->cgt->sw == 0 && h->coarse_mode != AGGMG_COARSE_EXTERNAL &&
-        nPost + nPre <= cgt_max_fused_sweeps(*l0.S->cgt)) {
-      const CgtDev& g = *l0.S->cgt;
-      double* part = nullptr;
-      const int64_t npart = 2 * (4 * g.ne / std::max(cgt_tile_blocks(g.m), 1) + 2);
-      CHECK(solv_vec(ctx, 2, npart + 2 * kChkReduceGroups, &part));
-      double* mid = part + npart;
-      double* sc = ctx->solv_sc + 8;
-      auto rest = [&]() -> int {  // levels 1.. of one cycle (their right-hand side is in place)
-        Level& c = h->lv[n - 1];
-        CHECK(coarse_solve(ctx, h, c.rhs, c.u[0]));
-        if (n > 2) CHECK(vcycle_up(ctx, h, b, nPost, alpha, nullptr, 1));
-        return AGGMG_OK;
-      };
-      h->last_coarse_ms = 0.0;
-      CHECK(vcycle_down(ctx, h, x0, b, nPre, alpha, 0));
-      CHECK(rest());
-      double* it_cur = l0.u[0];
-      double* it_alt = l0.u[1];
-      for (int it = 1; it <= maxiter; ++it) {
-        const bool check = (it % check_every == 0) || it == maxiter;
-        CgtChk chk;
-        chk.sweep = nPost;
-        chk.exact = u_exact;
-        chk.part = part;
-        if (it < maxiter) {
-          CHECK(cgt_mid(ctx, h, it_cur, it_alt, b, nPost + nPre, alpha, check ? &chk : nullptr));
-          std::swap(it_cur, it_alt);
-        } else {
-          CHECK(cgt_up(ctx, h, 0, b, nPost, alpha, x_out, it_cur, &chk));
-        }
-        done = it;
-        if (check) {
-          CHECK(chk_reduce(ctx, 1, chk.ntiles, part, mid, sc));
-          double host[2] = {0.0, 0.0};
-          HIPCHK(hipMemcpyAsync(host, sc, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-          HIPCHK(hipStreamSynchronize(ctx->stream));
-          if (u_exact) err_hist[checks] = host[1];
-          res_hist[checks++] = host[0];
-          if (host[0] < tol * nb) {
-            // (no store of x at the checkpoints: the ascent once more from the launch's untouched input, now in it_alt)
-            if (it < maxiter) CHECK(cgt_up(ctx, h, 0, b, nPost, alpha, x_out, it_alt));
-            break;
-          }
-        }
-        if (it < maxiter) {
-          CHECK(vcycle_down(ctx, h, nullptr, b, nPre, alpha, 1));
-          CHECK(rest());
-        }
-      }
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      *n_cycles = done;
-      *n_checks = checks;
-      return AGGMG_OK;
-    }
+  // The CG chain fine level (point-Jacobi): the same loop with the chain kernel's checkpoint variant.
+  const int n = (int)h->lv.size();
+  Level& l0 = h->lv[0];
+  const bool fusable = n >= 2 && l0.S && l0.S->btd && l0.S->A == l0.A && l0.tb && multigrid_restriction_ok(h) &&
+                       btd_fits(*l0.S, nPre + nPost, 1) && !l0.S->gs && h->coarse_mode != AGGMG_COARSE_EXTERNAL;
+  const bool chain = !fusable && n >= 2 && l0.cgt_fused && l0.S->cgt->sw == 0 && h->coarse_mode != AGGMG_COARSE_EXTERNAL &&
+                     nPost + nPre <= cgt_max_fused_sweeps(*l0.S->cgt);
+  if (ctx->mg_checkpoint && (fusable || chain)) {
+    const FineLevel f{ctx, h, b, nPre, nPost, alpha, chain};
+    ChkHist H;
+    CHECK(chk_buffers(ctx, 1, f.chk_tiles(), ctx->solv_sc + 8, &H));   // [8] ||A x - b||  [9] ||x - u_exact||
+    H.u_exact = u_exact;
+    H.tol_nb = tol * nb;
+    H.res = res_hist;
+    H.err = err_hist;
+    CHECK(cycle_loop(f, x0, maxiter, x_out, check_every, &H, &done));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *n_cycles = done;
+    *n_checks = H.checks;
+    return AGGMG_OK;
   }
   while (done < maxiter) {
     const int k = std::min(check_every, maxiter - done);
@@ -2980,101 +2899,45 @@ extern "C" int aggmg_smoother_solve_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoot
   // traffic instead of a sweep launch, a residual launch and a reduction per iteration.  A launch whose histories show
   // the tolerance met after j < S sweeps is run again for j sweeps from the same iterate (the same arithmetic: the
   // iterate the reference stops with, bit for bit).  AGGMG_OPT_MG_CHECKPOINT = 0: the form below.
-  if (ctx->mg_checkpoint && sm->btd && sm->A == A && !sm->gs && btd_max_sweeps(*sm->btd, 1) >= 1 && maxiter > 0) {
-    const BtdDev& B0 = *sm->btd;
-    const int smax = std::min(btd_max_sweeps(B0, 1), 16);   // (+ 1: the residual rows of the last sweep's iterate)
-    double* part = nullptr;
-    const int64_t npart = (int64_t)smax * 2 * (2 * B0.ne / std::max(btd_tile_elems(B0), 1) + 2);
-    CHECK(solv_vec(ctx, 2, npart + (int64_t)smax * 2 * kChkReduceGroups, &part));
-    double* mid = part + npart;
-    double* sc = ctx->solv_sc + 16;
+  // Point-Jacobi on a CG chain: the same with the chain kernel.
+  const bool fused = ctx->mg_checkpoint && sm->btd && sm->A == A && !sm->gs && btd_max_sweeps(*sm->btd, 1) >= 1 && maxiter > 0;
+  const bool chain = !fused && ctx->mg_checkpoint && sm->cgt && sm->A == A && sm->cgt->sw == 0 && cgt_max_fused_sweeps(*sm->cgt) >= 2;
+  if (fused || chain) {
+    // (one less than a launch takes: the residual rows of the last sweep's iterate)
+    const int smax = std::min(fused ? btd_max_sweeps(*sm->btd, 1) : cgt_max_fused_sweeps(*sm->cgt) - 1, 16);
+    ChkHist H;
+    CHECK(chk_buffers(ctx, smax, fused ? btd_chk_tiles(*sm->btd) : cgt_chk_tiles(*sm->cgt), ctx->solv_sc + 16, &H));
+    H.u_exact = u_exact;
+    H.tol_nb = tol * nb;
+    H.res = res_hist;
+    H.err = err_hist;
+    // S sweeps src -> dst in one launch; chk: with its checkpoints (one more element of halo for their residual rows)
+    auto sweeps = [&](const double* src, double* dst, int S, CgtChk* chk) -> int {
+      if (chain) return cgt_smooth_ext(ctx, *sm->cgt, src, b, alpha, S, dst, 0, chk);
+      if (!chk) return btd_smooth(ctx, *sm->btd, src, b, alpha, S, dst, 0, N, 0);
+      FusedArgs a = fused_sweeps(*sm->btd, src, b, dst, alpha, S);
+      fused_chk(a, *chk);
+      ProfScope ps(ctx, AGGMG_KIND_SMOOTH, 0);
+      return launch_btd(ctx, *sm->btd, a, S + 1, TileSel(), &chk->ntiles);
+    };
     while (done < maxiter) {
       const int S = std::min(smax, maxiter - done);
       double* dst = (cur == x_out) ? alt : x_out;
       // checked iteration counts in (done, done + S]: multiples of check_every, and maxiter
-      const int first = check_every - done % check_every;   // sweeps of this launch before its first check
-      FusedArgs a = btd_args(B0);
-      a.u_in = cur;
-      a.b = b;
-      a.alpha = alpha;
-      a.u_out = dst;
-      a.nsweeps = S;
-      a.chk_sweep = first;
-      a.chk_stride = check_every;
-      a.chk_final = (done + S == maxiter && (done + S) % check_every != 0) ? 1 : 0;
-      a.chk_exact = u_exact;
-      a.chk_part = part;
-      int nchk = (first <= S ? 1 + (S - first) / check_every : 0) + a.chk_final;
-      int64_t ntiles = 0;
-      {
-        ProfScope ps(ctx, AGGMG_KIND_SMOOTH, 0);
-        if (nchk == 0) a.chk_part = nullptr;
-        CHECK(launch_btd(ctx, B0, a, S + (nchk ? 1 : 0), TileSel(), &ntiles));
-      }
-      int stop = -1;   // sweeps of this launch after which the tolerance was met
-      if (nchk) {
-        CHECK(chk_reduce(ctx, nchk, ntiles, part, mid, sc));
-        double host[32];
-        HIPCHK(hipMemcpyAsync(host, sc, (size_t)2 * nchk * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        for (int k = 0; k < nchk && stop < 0; ++k) {
-          const int at = (a.chk_final && k == nchk - 1) ? S : first + k * check_every;
-          if (u_exact) err_hist[checks] = host[2 * k + 1];   // err[i] = ||x - uExact||, src/solvers.jl:202
-          res_hist[checks++] = host[2 * k];                  // res[i] = ||A x - b||,    :201
-          if (host[2 * k] < tol * nb) stop = at;             // :206
-        }
-      }
-      if (stop >= 0 && stop < S) {   // met before the launch's last sweep: that iterate again, without the rest
-        CHECK(btd_smooth(ctx, B0, cur, b, alpha, stop, dst, 0, N, 0));
-        done += stop;
-      } else {
-        done += S;
-      }
-      cur = dst;
-      if (stop >= 0) break;
-    }
-    if (cur != x_out) HIPCHK(hipMemcpyAsync(x_out, cur, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    *n_iters = done;
-    *n_checks = checks;
-    return AGGMG_OK;
-  }
-  // point-Jacobi on a CG chain: the same with the chain kernel
-  if (ctx->mg_checkpoint && sm->cgt && sm->A == A && sm->cgt->sw == 0 && cgt_max_fused_sweeps(*sm->cgt) >= 2) {
-    const CgtDev& g = *sm->cgt;
-    const int smax = std::min(cgt_max_fused_sweeps(g) - 1, 16);
-    double* part = nullptr;
-    const int64_t npart = (int64_t)smax * 2 * (4 * g.ne / std::max(cgt_tile_blocks(g.m), 1) + 2);
-    CHECK(solv_vec(ctx, 2, npart + (int64_t)smax * 2 * kChkReduceGroups, &part));
-    double* mid = part + npart;
-    double* sc = ctx->solv_sc + 16;
-    while (done < maxiter) {
-      const int S = std::min(smax, maxiter - done);
-      double* dst = (cur == x_out) ? alt : x_out;
-      const int first = check_every - done % check_every;
       CgtChk chk;
-      chk.sweep = first;
+      chk.sweep = check_every - done % check_every;   // sweeps of this launch before its first check
       chk.stride = check_every;
       chk.final = (done + S == maxiter && (done + S) % check_every != 0) ? 1 : 0;
       chk.exact = u_exact;
-      chk.part = part;
-      const int nchk = (first <= S ? 1 + (S - first) / check_every : 0) + chk.final;
-      CHECK(cgt_smooth_ext(ctx, g, cur, b, alpha, S, dst, 0, nchk ? &chk : nullptr));
-      int stop = -1;
-      if (nchk) {
-        CHECK(chk_reduce(ctx, nchk, chk.ntiles, part, mid, sc));
-        double host[32];
-        HIPCHK(hipMemcpyAsync(host, sc, (size_t)2 * nchk * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        for (int k = 0; k < nchk && stop < 0; ++k) {
-          const int at = (chk.final && k == nchk - 1) ? S : first + k * check_every;
-          if (u_exact) err_hist[checks] = host[2 * k + 1];
-          res_hist[checks++] = host[2 * k];
-          if (host[2 * k] < tol * nb) stop = at;
-        }
-      }
-      if (stop >= 0 && stop < S) {
-        CHECK(cgt_smooth_ext(ctx, g, cur, b, alpha, stop, dst, 0));
+      chk.part = H.part;
+      const int nchk = (chk.sweep <= S ? 1 + (S - chk.sweep) / check_every : 0) + chk.final;
+      CHECK(sweeps(cur, dst, S, nchk ? &chk : nullptr));
+      int met = -1;
+      if (nchk) CHECK(chk_collect(ctx, H, nchk, chk.ntiles, &met));
+      // sweeps of this launch after which the tolerance was met
+      const int stop = met < 0 ? -1 : ((chk.final && met == nchk - 1) ? S : chk.sweep + met * check_every);
+      if (stop >= 0 && stop < S) {   // met before the launch's last sweep: that iterate again, without the rest
+        CHECK(sweeps(cur, dst, stop, nullptr));
         done += stop;
       } else {
         done += S;
@@ -3085,7 +2948,7 @@ extern "C" int aggmg_smoother_solve_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoot
     if (cur != x_out) HIPCHK(hipMemcpyAsync(x_out, cur, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     *n_iters = done;
-    *n_checks = checks;
+    *n_checks = H.checks;
     return AGGMG_OK;
   }
   while (done < maxiter) {

@@ -193,6 +193,76 @@ inline TileSubset fused_tile_subset(int64_t ne, int owned, int mode, int64_t hea
   return t;
 }
 
+// ---- fused level launches: the tile itself ------------------------------------------------------------------------
+// The tile constants (elements a workgroup holds) come in as arguments; every plan reports "no tile" as a zero size.
+
+// Single-level launch: a tile of te elements keeps `halo` elements each side and owns the rest, rounded down to a
+// multiple of `align` (the agglomeration ratio when the launch restricts to uniform agglomerates, 1 otherwise).
+// var_agg: the launch restricts to agglomerates of different sizes (at most agg_shift + 1 elements; < 0: not known).
+// Where the tile can afford it the owned ranges are moved onto agglomerate boundaries (agg_shift taken: plain
+// stores); otherwise agglomerates cut by a tile boundary are summed from two tiles into a zeroed vector (-1).
+struct FusedTilePlan {
+  int owned = 0, halo_left = 0;
+  int agg_shift = -1;
+};
+inline FusedTilePlan fused_tile_plan(int te, int halo, int align, bool var_agg, int agg_shift) {
+  FusedTilePlan p;
+  const bool aligned = var_agg && agg_shift >= 0 && te - 2 * halo - agg_shift >= te / 2;
+  const int shift = aligned ? agg_shift : 0;
+  if (aligned) p.agg_shift = agg_shift;
+  p.owned = std::max(0, ((te - 2 * halo - shift) / align) * align);
+  p.halo_left = halo + shift;
+  return p;
+}
+
+// K-column launch (multi_kernels.hpp): the same without agglomerates of different sizes
+inline int multi_tile_owned(int te, int halo, int align) { return std::max(0, ((te - 2 * halo) / align) * align); }
+
+// Two levels A (fine, ratio rho_ab to B) and B (ratio rho_bc to C) in one launch (pair_kernels.hpp); tea / teb: the
+// elements of A / B a workgroup can hold.  own == 0: no tile for these ratios and sweeps.
+struct PairTilePlan {
+  int own = 0;           // descent: owned elements of B, a multiple of rho_bc; ascent: of A, a multiple of rho_ab
+  int te_a = 0, te_b = 0;
+  int hb = 0;            // ascent: halo of B behind A's nPost elements
+  int64_t all = 0, tA = 0, tB = 0;   // split ascent: tiles of the level, of them the prefix / suffix touching ghosts
+};
+inline PairTilePlan pair_down_plan(int nPre, int rho_ab, int rho_bc, int tea, int teb) {
+  PairTilePlan p;
+  const int hh = nPre + 1;
+  const int te_b = std::min(teb, (tea - 2 * hh) / rho_ab);
+  const int own = ((te_b - 2 * hh) / rho_bc) * rho_bc;
+  if (own <= 0) return p;
+  p.own = own;
+  p.te_b = own + 2 * hh;
+  p.te_a = p.te_b * rho_ab + 2 * hh;
+  return p;
+}
+inline PairTilePlan pair_up_plan(int nPost, int rho_ab, int tea, int teb) {
+  PairTilePlan p;
+  const int hb = (nPost + rho_ab - 1) / rho_ab;
+  const int own = (std::min(tea - 2 * nPost, (teb - 2 * hb - 2 * nPost) * rho_ab) / rho_ab) * rho_ab;
+  if (own <= 0) return p;
+  p.hb = hb;
+  p.own = own;
+  p.te_a = own + 2 * nPost;
+  p.te_b = own / rho_ab + 2 * hb + 2 * nPost;
+  return p;
+}
+// The ascent in two parts (element-partitioned runs, C = the coarsest level of nec elements, A has ne): tile t
+// prolongs from the elements floor(Eb0 / rho_bc) .. floor((Eb0 + te_b - 1) / rho_bc) of C (clipped to the level).
+// Tiles are ordered, so the ones reading the first gh_lo / last gh_hi elements of C are a prefix and a suffix.
+inline void pair_up_split(PairTilePlan* p, int nPost, int rho_ab, int rho_bc, int64_t ne, int64_t nec, int64_t gh_lo,
+                          int64_t gh_hi) {
+  const int64_t ne_b = ne / rho_ab;
+  auto eb0 = [&](int64_t t) { return (t * p->own) / rho_ab - p->hb - nPost; };
+  auto jmin = [&](int64_t t) { return std::max<int64_t>(eb0(t), 0) / rho_bc; };
+  auto jmax = [&](int64_t t) { return std::min<int64_t>(eb0(t) + p->te_b - 1, ne_b - 1) / rho_bc; };
+  p->all = (ne + p->own - 1) / p->own;
+  p->tA = p->tB = 0;
+  while (p->tA < p->all && jmin(p->tA) < gh_lo) ++p->tA;
+  while (p->tB < p->all - p->tA && jmax(p->all - 1 - p->tB) >= nec - gh_hi) ++p->tB;
+}
+
 // ---- host-pointer entry (aggmg_vcycle): lane t's byte range of a copy split over `lanes` worker threads ----------
 inline void stage_lane_range(size_t bytes, int lanes, int t, size_t* lo, size_t* hi) {
   const size_t per = ((bytes / (size_t)lanes) + 4095) & ~(size_t)4095;

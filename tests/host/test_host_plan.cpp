@@ -186,6 +186,109 @@ static void test_tile_subsets() {
         }
 }
 
+// the tile constants the library uses (BtdTile<M>::TE for M = 1 .. 9, the K-column tiles, the two-level tiles) and a few others
+static const int kSingleTE[] = {512, 128, 255, 153, 126, 108, 64, 56, 32, 17, 1000};
+static const int kRatios[] = {2, 3, 4, 5, 7, 8, 12, 13, 16, 31, 32, 60, 64};
+
+// ceil(ne / own) tiles of `own` elements cover [0, ne): back to back, the last one clipped
+static void check_cover(int64_t ne, int own) {
+  const int64_t ntiles = (ne + own - 1) / own;
+  int64_t at = 0;
+  for (int64_t t = 0; t < ntiles; ++t) {
+    EXPECT(t * own == at && at < ne);
+    at = std::min<int64_t>((t + 1) * own, ne);
+  }
+  EXPECT(at == ne);
+}
+
+static void test_fused_tile_plan() {
+  for (int te : kSingleTE)
+    for (int ns = 0; ns <= 8; ++ns)
+      for (int halo : {ns, ns + 1, 2 * ns, 2 * ns + 1}) {   // sweeps (+ a residual), Gauss-Seidel: two half-sweeps each
+        for (int rho : kRatios) {   // restriction to uniform agglomerates
+          const FusedTilePlan p = fused_tile_plan(te, halo, rho, false, -1);
+          EXPECT(p.owned >= 0 && p.agg_shift == -1);
+          if (p.owned > 0) {
+            EXPECT(p.owned % rho == 0 && p.halo_left == halo && p.halo_left + p.owned + halo <= te);
+            for (int64_t ne : {(int64_t)rho, (int64_t)rho * 37, (int64_t)rho * 4096}) check_cover(ne, p.owned);
+          }
+          EXPECT(multi_tile_owned(te, halo, rho) == p.owned);   // the K-column tile: the same arithmetic
+        }
+        for (int shift = -1; shift <= 9; ++shift) {   // agglomerates of different sizes, the largest of shift + 1 elements
+          const FusedTilePlan p = fused_tile_plan(te, halo, 1, true, shift);
+          EXPECT(p.owned >= 0 && (p.agg_shift == -1 || p.agg_shift == shift));
+          if (p.owned == 0) continue;
+          EXPECT(p.halo_left >= halo && p.halo_left + p.owned + halo <= te);
+          // moved onto agglomerate boundaries: a tile may start up to `shift` elements early and still owns half of itself
+          if (p.agg_shift >= 0) EXPECT(p.halo_left == halo + shift && p.owned >= te / 2 - 1);
+          else EXPECT(p.halo_left == halo);
+          for (int64_t ne : {(int64_t)1, (int64_t)777, (int64_t)100000}) check_cover(ne, p.owned);
+        }
+        EXPECT(fused_tile_plan(te, halo, 1, false, 3).agg_shift == -1);   // no shift without such agglomerates
+      }
+  EXPECT(fused_tile_plan(16, 8, 1, false, -1).owned == 0 && fused_tile_plan(16, 9, 2, false, -1).owned == 0);   // no room: no tile
+}
+
+static void test_pair_plans() {
+  const std::pair<int, int> tiles[] = {{256, 128}, {384, 256}, {512, 256}, {128, 128}, {100, 40}};   // (TEA, TEB); the first: the library's
+  for (auto [tea, teb] : tiles)
+    for (int ns = 0; ns <= 8; ++ns)
+      for (int ra : kRatios)
+        for (int rb : kRatios) {
+          const PairTilePlan d = pair_down_plan(ns, ra, rb, tea, teb);
+          const int hh = ns + 1;   // the sweeps and the residual
+          EXPECT(d.own >= 0);
+          if (d.own == 0) {
+            EXPECT(d.te_a == 0 && d.te_b == 0);   // "no tile" never looks like a size
+          } else {
+            EXPECT(d.own % rb == 0 && d.te_a <= tea && d.te_b <= teb);
+            EXPECT(d.te_b >= d.own + 2 * hh && d.te_a >= d.te_b * ra + 2 * hh);   // B's tile with its halo, A's around B's
+            check_cover((int64_t)rb * 1000, d.own);
+          }
+          const PairTilePlan u = pair_up_plan(ns, ra, tea, teb);
+          EXPECT(u.own >= 0);
+          if (u.own == 0) {
+            EXPECT(u.te_a == 0 && u.te_b == 0);
+            continue;
+          }
+          EXPECT(u.own % ra == 0 && u.te_a <= tea && u.te_b <= teb && u.hb * ra >= ns);
+          EXPECT(u.te_a >= u.own + 2 * ns && u.te_b >= u.own / ra + 2 * u.hb + 2 * ns);
+          check_cover((int64_t)ra * rb * 300, u.own);
+          // the ascent in two parts around the ghosts of the coarsest level
+          if (tea > 384) continue;   // (the library's tiles and one other pair: the check below walks every tile)
+          for (int64_t nec : {(int64_t)1, (int64_t)2, (int64_t)9, (int64_t)40}) {
+            const int64_t ne_b = nec * rb, ne = ne_b * ra;
+            for (int64_t gh_lo : {(int64_t)0, (int64_t)1, (int64_t)3, nec})
+              for (int64_t gh_hi : {(int64_t)0, (int64_t)1, (int64_t)4, nec}) {
+                PairTilePlan s = u;
+                pair_up_split(&s, ns, ra, rb, ne, nec, gh_lo, gh_hi);
+                EXPECT(s.all == (ne + s.own - 1) / s.own && s.tA >= 0 && s.tB >= 0 && s.tA + s.tB <= s.all);
+                // parts 1 and 2 as the launch numbers them: workgroup b runs tile b + (b >= split ? skip : 0)
+                std::multiset<int64_t> seen;
+                for (int64_t b = 0; b < s.tA + s.tB; ++b) seen.insert(b + (b >= s.tA ? s.all - s.tA - s.tB : 0));
+                for (int64_t b = 0; b < s.all - s.tA - s.tB; ++b) seen.insert(b + s.tA);
+                EXPECT((int64_t)seen.size() == s.all);
+                int64_t want = 0;
+                for (int64_t tile : seen) EXPECT(tile == want++);
+                // no part-2 tile reads a ghost: from the definition, element by element of the tile's window of B
+                for (int64_t t = s.tA; t < s.all - s.tB; ++t) {
+                  const int64_t e0 = t * s.own / ra - s.hb - ns;
+                  for (int64_t e = e0; e < e0 + s.te_b; ++e) {
+                    const int64_t j = std::min(std::max<int64_t>(e, 0), ne_b - 1) / rb;
+                    EXPECT(j >= gh_lo && j < nec - gh_hi);
+                  }
+                }
+              }
+          }
+        }
+  // the library's tiles (256, 128): ratios (4, 16, 16) at V(3,3) -- levels 1 and 2 both agglomerate by 16 -- and equal
+  // ratios of 13 and above at 3 sweeps, of 9 and above at 8, have no descent tile
+  EXPECT(pair_down_plan(3, 16, 16, 256, 128).own == 0);
+  for (int r = 13; r <= 64; ++r) EXPECT(pair_down_plan(3, r, r, 256, 128).own == 0);
+  for (int r = 9; r <= 64; ++r) EXPECT(pair_down_plan(8, r, r, 256, 128).own == 0);
+  EXPECT(pair_down_plan(3, 4, 4, 256, 128).own > 0 && pair_down_plan(3, 2, 2, 256, 128).own > 0);   // the benchmarked ratios have one
+}
+
 static void test_lane_ranges() {
   for (size_t bytes : {(size_t)0, (size_t)1, (size_t)4095, (size_t)4096, (size_t)(16u << 20), (size_t)134217728, (size_t)134217729})
     for (int lanes = 1; lanes <= 8; ++lanes) {
@@ -230,6 +333,8 @@ int main() {
   test_lds_cap();
   test_row_blocks();
   test_tile_subsets();
+  test_fused_tile_plan();
+  test_pair_plans();
   test_lane_ranges();
   test_chunk_route();
   if (failures) {
