@@ -142,6 +142,7 @@ SYMBOLS = {
     "aggmg_host_alloc": (c_int, [_P, c_int64, POINTER(_P)]),
     "aggmg_host_free": (c_int, [_P, _P]),
     "aggmg_hier_level_paired": (c_int, [_P, _P, c_int, c_int, POINTER(c_int)]),
+    "aggmg_hier_level_paired_up": (c_int, [_P, _P, c_int, c_int, POINTER(c_int)]),
     "aggmg_hier_level_sym_residual": (c_int, [_P, _P, c_int, POINTER(c_int)]),
     "aggmg_hier_launch_bytes": (c_int, [_P, _P, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "aggmg_hier_multi_launch_bytes": (c_int, [_P, _P, c_int, c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_int64)]),

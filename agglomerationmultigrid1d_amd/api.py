@@ -871,11 +871,14 @@ class MeshHierarchy:
         return out
 
     def paired_levels(self, nsweeps=3, direction="down"):
-        """levels k whose launch also carries level k + 1 (C ABI aggmg_hier_level_paired), as the descent walks the
-        hierarchy (pairs taken from the fine side) or, direction='up', as the ascent does (from the coarse side)"""
+        """levels k whose launch also carries level k + 1 (C ABI aggmg_hier_level_paired / _paired_up), as the descent
+        walks the hierarchy (pairs taken from the fine side) or, direction='up', as the ascent does (from the coarse
+        side); the two directions have tiles of their own and may differ"""
+        fn = self.ctx.lib.aggmg_hier_level_paired if direction == "down" else self.ctx.lib.aggmg_hier_level_paired_up
+
         def ok(k):
             v = ctypes.c_int(0)
-            self.ctx.check(self.ctx.lib.aggmg_hier_level_paired(self.ctx.handle, self.handle, k, int(nsweeps), ctypes.byref(v)))
+            self.ctx.check(fn(self.ctx.handle, self.handle, k, int(nsweeps), ctypes.byref(v)))
             return bool(v.value)
         out = []
         if direction == "down":

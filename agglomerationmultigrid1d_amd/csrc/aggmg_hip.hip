@@ -540,6 +540,12 @@ static void xfer_in(FusedArgs& a, const TransferBtd& t) {
   a.rho_in = t.rho;
   a.par_in = t.rho ? nullptr : t.parent;
 }
+// agglomerates of different sizes: the elements a tile may move to stand on an agglomerate boundary (-1: none)
+static int xfer_agg_shift(const TransferBtd& t) {
+  // (AGGMG_AGG_ALIGN=0: the two-part atomic restriction for every size, as before r03)
+  static const int max_shift = cr_env_int_early("AGGMG_AGG_ALIGN", 1) ? 8 : -1;
+  return (!t.rho && t.maxagg >= 1 && t.maxagg - 1 <= max_shift) ? t.maxagg - 1 : -1;
+}
 static void xfer_out(FusedArgs& a, const TransferBtd& t) {
   a.lf1_out = t.lf1;
   a.mc_out = t.mc;
@@ -547,13 +553,11 @@ static void xfer_out(FusedArgs& a, const TransferBtd& t) {
   a.par_out = t.rho ? nullptr : t.parent;
   a.first_out = t.rho ? nullptr : t.first;
   a.nec_out = t.nec;
-  // (AGGMG_AGG_ALIGN=0: the two-part atomic restriction for every size, as before r03)
-  static const int max_shift = cr_env_int_early("AGGMG_AGG_ALIGN", 1) ? 8 : -1;
-  a.agg_shift = (!t.rho && t.maxagg >= 1 && t.maxagg - 1 <= max_shift) ? t.maxagg - 1 : -1;
+  a.agg_shift = xfer_agg_shift(t);
 }
 
 template <int M, bool CMP>
-static int launch_btd_t(aggmg_ctx* ctx, FusedArgs a, int halo, const TileSel& sel, int64_t* ntiles_out) {
+static int launch_btd_t(aggmg_ctx* ctx, FusedArgs a, int halo, const TileSel& sel, CgtChk* chk_io) {
   using T = BtdTile<M, CMP>;
   const bool vr = (a.lf_out || a.ld_out) && a.par_out;
   const int align = ((a.lf_out || a.ld_out) && !vr) ? a.rho_out : 1;
@@ -572,10 +576,13 @@ static int launch_btd_t(aggmg_ctx* ctx, FusedArgs a, int halo, const TileSel& se
   const int64_t ntiles = sub.ntiles;
   a.tile_split = sub.split;
   a.tile_skip = sub.skip;
-  if (ntiles_out) *ntiles_out = ntiles;
+  if (chk_io) chk_io->ntiles = ntiles;
   if (ntiles == 0) return AGGMG_OK;
   const bool chk = a.chk_part != nullptr;   // checkpoint variant (multigrid's per-cycle residual test inside the launch)
   if (chk && a.gs) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: checkpoint launch with Gauss-Seidel sweeps");
+  // every tile stores its sums at chk_part[(checkpoint * ntiles + tile) * 2]: never past what was reserved
+  if (chk && (!chk_io || ntiles > chk_io->cap))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: checkpoint launch of more tiles than its partial sums have room for");
   a.chk_tiles = ntiles;
   if (chk) {   // measurement aid (tools/exp_outer_loop.py): the checkpoint variant's code with no checkpoint ever due
     static const int never = cr_env_int_early("AGGMG_CHK_NEVER", 0);
@@ -652,9 +659,9 @@ static bool btd_with_tile(const BtdDev& b, F&& f) {
 }
 
 static int launch_btd(aggmg_ctx* ctx, const BtdDev& b, const FusedArgs& a, int halo, const TileSel& sel = TileSel(),
-                      int64_t* ntiles_out = nullptr) {
+                      CgtChk* chk = nullptr) {
   int rc = AGGMG_OK;
-  if (!btd_with_tile(b, [&](auto t) { rc = launch_btd_t<decltype(t)::kM, decltype(t)::kCmp>(ctx, a, halo, sel, ntiles_out); }))
+  if (!btd_with_tile(b, [&](auto t) { rc = launch_btd_t<decltype(t)::kM, decltype(t)::kCmp>(ctx, a, halo, sel, chk); }))
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, "block size not instantiated for the fused kernel");
   return rc;
 }
@@ -734,6 +741,22 @@ static int btd_max_sweeps(const BtdDev& b, int extra) {
 // does a launch of nsweeps sweeps (+ a residual) fit the halo budget of smoother sm's tiles?
 static bool btd_fits(const aggmg_smoother& sm, int nsweeps, int residual) {
   return (sm.gs ? 2 : 1) * nsweeps + residual <= btd_max_sweeps(*sm.btd, 0);
+}
+
+// ... and does that launch have a tile (host_plan.hpp, the planner launch_btd_t runs)?  tout: the transfer it restricts
+// through, or null.  Where it has none the callers take their unfused sequence.
+static bool btd_launch_ok(const aggmg_smoother& sm, int nsweeps, int residual, const TransferBtd* tout) {
+  if (!btd_fits(sm, nsweeps, residual)) return false;
+  TileQuery q;
+  q.launch = kTileFused;
+  q.te = btd_tile_elems(*sm.btd);
+  q.halo = (sm.gs ? 2 : 1) * nsweeps + residual;
+  if (tout) {
+    q.var_agg = tout->rho == 0;
+    q.align = tout->rho ? tout->rho : 1;
+    q.agg_shift = xfer_agg_shift(*tout);
+  }
+  return launch_has_tile(q);
 }
 
 // structured: nsweeps sweeps from u_in (may be nullptr = zero) into u_out (!= u_in)
@@ -1581,15 +1604,24 @@ static bool pair_level_ok(const Level& l) {
          l.tb->mc == 2 && l.tb->rho > 0 && l.S->btd->ne == (int64_t)l.tb->rho * l.tb->nec;
 }
 
-// levels k and k + 1 (both smoothed, both below the finest: their iterates start at zero on the way down)
-static bool pair_ok(const aggmg_ctx* ctx, const aggmg_hier* h, int k, int nsweeps) {
+// levels k and k + 1 (both smoothed, both below the finest: their iterates start at zero on the way down) in one launch
+// of the descent (up = false) or of the ascent: the level kinds allow it and the launch has a tile for these ratios
+// and sweeps (host_plan.hpp, the planners launch_pair_down / launch_pair_up run); otherwise one launch per level
+static bool pair_ok(const aggmg_ctx* ctx, const aggmg_hier* h, int k, int nsweeps, bool up) {
   const int n = (int)h->lv.size();
   if (!ctx->pair_levels || k < 1 || k + 2 > n - 1 || nsweeps < 1 || nsweeps > 8) return false;
   const Level& a = h->lv[k];
   const Level& b = h->lv[k + 1];
   if (!pair_level_ok(a) || !pair_level_ok(b) || b.S->btd->ne != a.tb->nec) return false;
   if (h->restriction == AGGMG_RESTRICT_PRECONDITIONED && (a.tb->ld || b.tb->ld)) return false;
-  return true;
+  TileQuery q;
+  q.launch = up ? kTilePairUp : kTilePairDown;
+  q.te = kPairTEA;
+  q.te_b = kPairTEB;
+  q.halo = nsweeps;
+  q.align = a.tb->rho;
+  q.rho_bc = b.tb->rho;
+  return launch_has_tile(q);
 }
 
 static PairArgs pair_args(const aggmg_hier* h, int k, double alpha, int nsweeps) {
@@ -1680,7 +1712,13 @@ static int launch_pair_up(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPost, doubl
 
 extern "C" int aggmg_hier_level_paired(aggmg_ctx* ctx, const aggmg_hier* h, int level, int nsweeps, int* paired) {
   if (!ctx || !h || !paired) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_paired: NULL argument");
-  *paired = pair_ok(ctx, h, level, nsweeps) ? 1 : 0;
+  *paired = pair_ok(ctx, h, level, nsweeps, false) ? 1 : 0;
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_hier_level_paired_up(aggmg_ctx* ctx, const aggmg_hier* h, int level, int nsweeps, int* paired) {
+  if (!ctx || !h || !paired) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_paired_up: NULL argument");
+  *paired = pair_ok(ctx, h, level, nsweeps, true) ? 1 : 0;
   return AGGMG_OK;
 }
 
@@ -1705,13 +1743,13 @@ static int vcycle_down(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const do
       CHECK(cgt_down(ctx, h, k, uin, rhs, nPre, alpha));
       continue;
     }
-    if (pair_ok(ctx, h, k, nPre)) {   // this level and the next in one launch
+    if (pair_ok(ctx, h, k, nPre, false)) {   // this level and the next in one launch
       CHECK(launch_pair_down(ctx, h, k, nPre, alpha));
       ++k;
       continue;
     }
     const bool structured = l.S->btd && l.S->A == l.A;
-    if (structured && l.tb && btd_fits(*l.S, nPre, 1)) {
+    if (structured && l.tb && btd_launch_ok(*l.S, nPre, 1, l.tb.get())) {
       // (Gauss-Seidel pre-smoothing: even elements, then odd ones)
       FusedArgs a = fused_sweeps(*l.S->btd, uin, rhs, l.u[0], alpha, nPre, l.S->gs ? 1 : 0);
       fused_descent(a, h, l, c.rhs);
@@ -1770,12 +1808,12 @@ static int vcycle_up(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, 
   const int n = (int)h->lv.size();
   if (cs.mode != 0) {
     const int k = n - 2;
-    if (!(sel.mode == 0 && k - 1 >= std::max(k_last, 1) && pair_ok(ctx, h, k - 1, nPost)))
+    if (!(sel.mode == 0 && k - 1 >= std::max(k_last, 1) && pair_ok(ctx, h, k - 1, nPost, true)))
       return fail(ctx, AGGMG_ERR_UNSUPPORTED, "split coarse ascent needs a two-level launch next to the coarsest level");
     CHECK(launch_pair_up(ctx, h, k - 1, nPost, alpha, h->lv[k - 1].u[1], cs.mode, cs.gh_lo, cs.gh_hi));
     if (cs.mode == 2) return AGGMG_OK;
     for (int kk = k - 2; kk >= k_last; --kk) {   // the levels above the pair, as below (no further pairs are split)
-      if (kk - 1 >= std::max(k_last, 1) && pair_ok(ctx, h, kk - 1, nPost)) {
+      if (kk - 1 >= std::max(k_last, 1) && pair_ok(ctx, h, kk - 1, nPost, true)) {
         CHECK(launch_pair_up(ctx, h, kk - 1, nPost, alpha, h->lv[kk - 1].u[1]));
         --kk;
         continue;
@@ -1790,7 +1828,7 @@ static int vcycle_up(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, 
     const double* rhs = k == 0 ? b : l.rhs;
     double* dst = k == 0 ? x_out : l.u[1];
     const double* uc = (k + 1 == n - 1) ? c.u[0] : c.u[1];
-    if (sel.mode == 0 && k - 1 >= std::max(k_last, 1) && pair_ok(ctx, h, k - 1, nPost)) {   // this level and the finer one in one launch
+    if (sel.mode == 0 && k - 1 >= std::max(k_last, 1) && pair_ok(ctx, h, k - 1, nPost, true)) {   // this level and the finer one in one launch
       CHECK(launch_pair_up(ctx, h, k - 1, nPost, alpha, h->lv[k - 1].u[1]));
       --k;
       continue;
@@ -1802,7 +1840,7 @@ static int vcycle_up(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, 
       continue;
     }
     const bool structured = l.S->btd && l.S->A == l.A;
-    if (structured && l.tb && btd_fits(*l.S, nPost, 0)) {
+    if (structured && l.tb && btd_launch_ok(*l.S, nPost, 0, nullptr)) {
       // (Gauss-Seidel post-smoothing in the reverse colour order: the cycle stays symmetric)
       FusedArgs a = fused_sweeps(*l.S->btd, l.u[0], rhs, dst, alpha, nPost, l.S->gs ? 2 : 0);
       fused_ascent(a, l, uc);
@@ -1892,10 +1930,15 @@ static bool multi_level_ok(const aggmg_hier* h, int k, int nPre, int nPost) {
   if (t.mc != 2 || t.rho <= 0 || b.ne != (int64_t)t.rho * t.nec) return false;
   if (t.ld && h->restriction == AGGMG_RESTRICT_PRECONDITIONED) return false;
   // the single-column cycle's launches at this level are single fused launches (no chunked sweeps) ...
-  if (!btd_fits(*l.S, nPre, 1) || !btd_fits(*l.S, nPost, 0)) return false;
+  if (!btd_launch_ok(*l.S, nPre, 1, &t) || !btd_launch_ok(*l.S, nPost, 0, nullptr)) return false;
   // ... and the K-column tile holds the same halos
-  const int te = kMultiNT / b.m;
-  return multi_tile_owned(te, nPre + 1, t.rho) > 0 && multi_tile_owned(te, nPost, 1) > 0;
+  TileQuery down, up;
+  down.launch = up.launch = kTileMulti;
+  down.te = up.te = kMultiNT / b.m;
+  down.halo = nPre + 1;
+  down.align = t.rho;
+  up.halo = nPost;
+  return launch_has_tile(down) && launch_has_tile(up);
 }
 
 static bool multi_ok(const aggmg_hier* h, int nPre, int nPost) {
@@ -2070,9 +2113,17 @@ static int coarse_levels(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPr
   return AGGMG_OK;
 }
 
-// upper bounds of the tiles of a checkpoint launch (its partial sums: two doubles per tile and checkpoint)
-static int64_t btd_chk_tiles(const BtdDev& b) { return 2 * b.ne / std::max(btd_tile_elems(b), 1) + 2; }
-static int64_t cgt_chk_tiles(const CgtDev& g) { return 4 * g.ne / std::max(cgt_tile_blocks(g.m), 1) + 2; }
+// upper bounds of the tiles of a checkpoint launch (its partial sums: two doubles per tile and checkpoint), from the
+// planner the launches run (host_plan.hpp): sweeps = the most any of them takes (+ the residual rows), tout = the
+// transfer the one between two cycles restricts through (null: none restricts)
+static int64_t btd_chk_tiles(const BtdDev& b, int sweeps, const TransferBtd* tout) {
+  return fused_chk_reserve(b.ne, btd_tile_elems(b), sweeps + 1, tout && tout->rho ? tout->rho : 1, tout && !tout->rho,
+                           tout ? xfer_agg_shift(*tout) : -1);
+}
+// (chain kernel: a block of halo per sweep and side, two for the residual, one for the restriction)
+static int64_t cgt_chk_tiles(const CgtDev& g, int sweeps, int rho) {
+  return chain_chk_reserve(g.ne, cgt_tile_blocks(g.m), 2 * sweeps + 3, std::max(rho, 1));
+}
 
 // The fine level of the sequence: the fused block-tridiagonal kernel, or the chain kernel of a CG mesh (cgt.hip).
 // chk: the launch forms a checkpoint's sums and reports its tile count there.
@@ -2094,7 +2145,7 @@ struct FineLevel {
     fused_descent(a, h, l0(), h->lv[1].rhs);
     if (chk) fused_chk(a, *chk);
     ProfScope ps(ctx, AGGMG_KIND_FUSED_MID, 0);
-    return launch_btd(ctx, B0, a, nPost + nPre + 1, TileSel(), chk ? &chk->ntiles : nullptr);
+    return launch_btd(ctx, B0, a, nPost + nPre + 1, TileSel(), chk);
   }
   // the ascent alone: src -> dst
   int up(const double* src, double* dst, CgtChk* chk) const {
@@ -2105,14 +2156,18 @@ struct FineLevel {
     if (chk) fused_chk(a, *chk);
     ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, 0);
     // (a checkpoint here forms residual rows of the FINAL iterate: one more element of halo, as a residual)
-    return launch_btd(ctx, B0, a, nPost + (chk ? 1 : 0), TileSel(), chk ? &chk->ntiles : nullptr);
+    return launch_btd(ctx, B0, a, nPost + (chk ? 1 : 0), TileSel(), chk);
   }
-  int64_t chk_tiles() const { return chain ? cgt_chk_tiles(*l0().S->cgt) : btd_chk_tiles(*l0().S->btd); }
+  int64_t chk_tiles() const {
+    return chain ? cgt_chk_tiles(*l0().S->cgt, nPost + nPre, l0().tc ? l0().tc->rho : 1)
+                 : btd_chk_tiles(*l0().S->btd, nPost + nPre, l0().tb.get());
+  }
 };
 
 // Histories and stopping test of launches with checkpoints (with the outer solver loops below)
 struct ChkHist {
   double *part = nullptr, *mid = nullptr, *sc = nullptr;   // on the device: tile sums, their partial reduction, the norms
+  int64_t cap = 0;                                         // tiles `part` has room for (per checkpoint)
   const double* u_exact = nullptr;
   double tol_nb = 0.0;
   double *res = nullptr, *err = nullptr;
@@ -2139,6 +2194,7 @@ static int cycle_loop(const FineLevel& f, const double* x0, int ncycles, double*
       chk.sweep = f.nPost;
       chk.exact = H->u_exact;
       chk.part = H->part;
+      chk.cap = H->cap;
     }
     if (!last) {
       CHECK(f.mid(cur, alt, check ? &chk : nullptr));
@@ -2174,8 +2230,9 @@ extern "C" int aggmg_vcycles_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycles: hierarchy was created with AGGMG_COARSE_EXTERNAL");
   const int n = (int)h->lv.size();
   Level& l0 = h->lv[0];
+  // (no tile for the launch between two cycles -- a fine-level ratio its halo leaves no room for: the plain sequence)
   const bool fusable = n >= 2 && l0.S && l0.S->btd && l0.S->A == l0.A && l0.tb && vcycles_restriction_ok(h, l0) &&
-                       btd_fits(*l0.S, nPre + nPost, 1) && !l0.S->gs;
+                       btd_launch_ok(*l0.S, nPre + nPost, 1, l0.tb.get()) && !l0.S->gs;
   // CG chain fine level: the same cross-cycle fusion with the chain kernel
   const bool chain = n >= 2 && l0.cgt_fused && ncycles > 1 && l0.S->cgt->sw != 3;
   if (chain || (fusable && ncycles > 1))
@@ -2224,7 +2281,7 @@ extern "C" int aggmg_vcycle_up_split_dev(aggmg_ctx* ctx, aggmg_hier* h, const do
     return vcycle_up(ctx, h, b, nPost, alpha, x_out, 0, all);
   }
   Level& l = h->lv[0];
-  if (!(l.S && l.S->btd && l.S->A == l.A && l.tb && btd_fits(*l.S, nPost, 0)))
+  if (!(l.S && l.S->btd && l.S->A == l.A && l.tb && btd_launch_ok(*l.S, nPost, 0, nullptr)))
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, "split ascent needs the fused block-tridiagonal fine level");
   if (part == 0) return h->lv.size() > 2 ? vcycle_up(ctx, h, b, nPost, alpha, x_out, 1) : AGGMG_OK;
   TileSel sel;
@@ -2772,6 +2829,7 @@ static int chk_buffers(aggmg_ctx* ctx, int nchk_max, int64_t tiles, double* sc, 
   const int64_t npart = (int64_t)nchk_max * 2 * tiles;
   CHECK(solv_vec(ctx, 2, npart + (int64_t)nchk_max * 2 * kChkReduceGroups, &H->part));
   H->mid = H->part + npart;
+  H->cap = tiles;
   H->sc = sc;
   return AGGMG_OK;
 }
@@ -2830,7 +2888,7 @@ extern "C" int aggmg_multigrid_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* 
   const int n = (int)h->lv.size();
   Level& l0 = h->lv[0];
   const bool fusable = n >= 2 && l0.S && l0.S->btd && l0.S->A == l0.A && l0.tb && multigrid_restriction_ok(h) &&
-                       btd_fits(*l0.S, nPre + nPost, 1) && !l0.S->gs && h->coarse_mode != AGGMG_COARSE_EXTERNAL;
+                       btd_launch_ok(*l0.S, nPre + nPost, 1, l0.tb.get()) && !l0.S->gs && h->coarse_mode != AGGMG_COARSE_EXTERNAL;
   const bool chain = !fusable && n >= 2 && l0.cgt_fused && l0.S->cgt->sw == 0 && h->coarse_mode != AGGMG_COARSE_EXTERNAL &&
                      nPost + nPre <= cgt_max_fused_sweeps(*l0.S->cgt);
   if (ctx->mg_checkpoint && (fusable || chain)) {
@@ -2906,7 +2964,8 @@ extern "C" int aggmg_smoother_solve_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoot
     // (one less than a launch takes: the residual rows of the last sweep's iterate)
     const int smax = std::min(fused ? btd_max_sweeps(*sm->btd, 1) : cgt_max_fused_sweeps(*sm->cgt) - 1, 16);
     ChkHist H;
-    CHECK(chk_buffers(ctx, smax, fused ? btd_chk_tiles(*sm->btd) : cgt_chk_tiles(*sm->cgt), ctx->solv_sc + 16, &H));
+    CHECK(chk_buffers(ctx, smax, fused ? btd_chk_tiles(*sm->btd, smax, nullptr) : cgt_chk_tiles(*sm->cgt, smax, 1), ctx->solv_sc + 16,
+                      &H));
     H.u_exact = u_exact;
     H.tol_nb = tol * nb;
     H.res = res_hist;
@@ -2918,7 +2977,7 @@ extern "C" int aggmg_smoother_solve_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoot
       FusedArgs a = fused_sweeps(*sm->btd, src, b, dst, alpha, S);
       fused_chk(a, *chk);
       ProfScope ps(ctx, AGGMG_KIND_SMOOTH, 0);
-      return launch_btd(ctx, *sm->btd, a, S + 1, TileSel(), &chk->ntiles);
+      return launch_btd(ctx, *sm->btd, a, S + 1, TileSel(), chk);
     };
     while (done < maxiter) {
       const int S = std::min(smax, maxiter - done);
@@ -2930,6 +2989,7 @@ extern "C" int aggmg_smoother_solve_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoot
       chk.final = (done + S == maxiter && (done + S) % check_every != 0) ? 1 : 0;
       chk.exact = u_exact;
       chk.part = H.part;
+      chk.cap = H.cap;
       const int nchk = (chk.sweep <= S ? 1 + (S - chk.sweep) / check_every : 0) + chk.final;
       CHECK(sweeps(cur, dst, S, nchk ? &chk : nullptr));
       int met = -1;

@@ -70,17 +70,17 @@ static int cgt_max_sweeps(int m, int sw = 0) {
 int cgt_max_fused_sweeps(const CgtDev& g) { return cgt_max_sweeps(g.m, g.sw); }
 
 template <int M, int K>
-static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, int sw, int64_t* ntiles_out);
+static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, int sw, CgtChk* chk_io);
 
 template <int M>
-static int cgt_launch_t(aggmg_ctx* ctx, CgtArgs a, int sw, int64_t* ntiles_out) {
+static int cgt_launch_t(aggmg_ctx* ctx, CgtArgs a, int sw, CgtChk* chk_io) {
   if (a.nsweeps == 0) sw = 0;
-  if (sw == 3) return cgt_launch_tt<M, 2>(ctx, a, sw, ntiles_out);
-  return sw ? cgt_launch_tt<M, 1>(ctx, a, sw, ntiles_out) : cgt_launch_tt<M, 0>(ctx, a, sw, ntiles_out);
+  if (sw == 3) return cgt_launch_tt<M, 2>(ctx, a, sw, chk_io);
+  return sw ? cgt_launch_tt<M, 1>(ctx, a, sw, chk_io) : cgt_launch_tt<M, 0>(ctx, a, sw, chk_io);
 }
 
 template <int M, int K>
-static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, int sw, int64_t* ntiles_out) {
+static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, int sw, CgtChk* chk_io) {
   using T = CgtTile<M, K>;
   // halo: one block per sweep and side (element Schwarz: the update of a block reads the residual of its two
   // neighbours, i.e. the iterate two blocks away); the residual needs one more valid neighbour on both sides,
@@ -97,15 +97,18 @@ static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, int sw, int64_t* ntiles_out)
   }
   if (a.chk_part && K != 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: checkpoint launch with element-block sweeps");
   const int align = a.tout.type == kTrAgg ? a.tout.rho : 1;
-  const int owned = ((T::TE - hl - hr) / align) * align;
+  const int owned = chain_tile_owned(T::TE, hl, hr, align);   // host_plan.hpp
   if (owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "chain tile too small for the requested halo");
   a.owned = owned;
   a.halo_left = hl;
   a.tile_split = 0;
   a.tile_skip = 0;
   const int64_t ntiles = (a.lv.ne + owned - 1) / owned;
-  if (ntiles_out) *ntiles_out = ntiles;
+  if (chk_io) chk_io->ntiles = ntiles;
   if (ntiles == 0) return AGGMG_OK;
+  // every tile stores its sums at chk_part[(checkpoint * ntiles + tile) * 2]: never past what was reserved
+  if (a.chk_part && (!chk_io || ntiles > chk_io->cap))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: checkpoint launch of more tiles than its partial sums have room for");
   if (ntiles >= ((int64_t)1 << 31)) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "grid too large");
   a.chk_tiles = ntiles;
   if (a.chk_stride < 1) a.chk_stride = 1 << 30;
@@ -131,11 +134,11 @@ static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, int sw, int64_t* ntiles_out)
   return AGGMG_OK;
 }
 
-static int cgt_launch(aggmg_ctx* ctx, const CgtDev& g, const CgtArgs& a, int64_t* ntiles_out = nullptr) {
+static int cgt_launch(aggmg_ctx* ctx, const CgtDev& g, const CgtArgs& a, CgtChk* chk_io = nullptr) {
   switch (g.m) {
 #define CASE(MM) \
   case MM:       \
-    return cgt_launch_t<MM>(ctx, a, g.sw, ntiles_out);
+    return cgt_launch_t<MM>(ctx, a, g.sw, chk_io);
     CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
 #undef CASE
   }
@@ -228,7 +231,7 @@ static int cgt_run(aggmg_ctx* ctx, const CgtDev& g, const CgtChain& c, double al
     }
     {
       ProfScope ps(ctx, q == nl - 1 ? kind : AGGMG_KIND_SMOOTH, level);
-      CHECK(cgt_launch(ctx, g, a, chk ? &chk->ntiles : nullptr));
+      CHECK(cgt_launch(ctx, g, a, chk));
     }
     src = dst;
     src_ext = false;

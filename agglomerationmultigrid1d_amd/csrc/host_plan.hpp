@@ -263,6 +263,62 @@ inline void pair_up_split(PairTilePlan* p, int nPost, int rho_ab, int rho_bc, in
   while (p->tB < p->all - p->tA && jmax(p->all - 1 - p->tB) >= nec - gh_hi) ++p->tB;
 }
 
+// The chain kernel (cgt.hip): a tile of te blocks keeps hl / hr blocks of halo and owns the rest, rounded down to a
+// multiple of `align` (the ratio of an agglomerating restriction, 1 otherwise)
+inline int chain_tile_owned(int te, int hl, int hr, int align) { return std::max(0, ((te - hl - hr) / align) * align); }
+
+// ---- does a launch have a tile? ----------------------------------------------------------------------------------
+// One question for every tiled launch, answered by the planner its launcher runs: the callers that choose between a
+// launch and its fallback (two levels or one per launch, fused or unfused sequence, K columns or column by column) ask
+// here, so a launch that was chosen never finds "no tile".
+enum TileLaunch { kTileFused = 0, kTileMulti = 1, kTilePairDown = 2, kTilePairUp = 3 };
+struct TileQuery {
+  int launch = kTileFused;
+  int te = 0, te_b = 0;   // elements a workgroup holds (pairs: of level A and of level B)
+  int halo = 0;           // fused / K-column: elements kept each side; pairs: the sweeps
+  int align = 1;          // fused / K-column: see fused_tile_plan; pairs: rho_ab
+  int rho_bc = 1;         // descent of a pair
+  bool var_agg = false;   // fused: see fused_tile_plan
+  int agg_shift = -1;
+};
+inline bool launch_has_tile(const TileQuery& q) {
+  if (q.te <= 0 || q.align < 1 || q.rho_bc < 1 || q.halo < 0) return false;
+  switch (q.launch) {
+    case kTileFused: return fused_tile_plan(q.te, q.halo, q.align, q.var_agg, q.agg_shift).owned > 0;
+    case kTileMulti: return multi_tile_owned(q.te, q.halo, q.align) > 0;
+    case kTilePairDown: return pair_down_plan(q.halo, q.align, q.rho_bc, q.te, q.te_b).own > 0;
+    case kTilePairUp: return pair_up_plan(q.halo, q.align, q.te, q.te_b).own > 0;
+  }
+  return false;
+}
+
+// ---- checkpoint launches: room for their partial sums ---------------------------------------------------------------
+// A checkpoint launch stores two doubles per tile and checkpoint; the buffer is sized before the launches are known one
+// by one.  What is known: the level (ne elements in tiles of te), the largest halo any of them takes, and the restriction
+// of the one between two cycles (align / var_agg / agg_shift as fused_tile_plan; the others restrict nothing: align 1).
+// -> the largest tile count of any such launch with a halo of 1 .. halo_max (the owned size is not monotone in the halo
+// where agglomerates of different sizes move the tiles), at least 1.  The launchers refuse a launch with more tiles.
+inline int64_t fused_chk_reserve(int64_t ne, int te, int halo_max, int align, bool var_agg, int agg_shift) {
+  int64_t most = 1;
+  for (int halo = 1; halo <= halo_max; ++halo)
+    for (int restricting = 0; restricting < 2; ++restricting) {
+      const int owned = restricting ? fused_tile_plan(te, halo, align, var_agg, agg_shift).owned
+                                    : fused_tile_plan(te, halo, 1, false, -1).owned;
+      if (owned > 0) most = std::max(most, fused_tile_subset(ne, owned, 0, 0, 0).ntiles);
+    }
+  return most;
+}
+// the chain kernel's: hsum_max = the largest hl + hr of its checkpoint launches
+inline int64_t chain_chk_reserve(int64_t ne, int te, int hsum_max, int align) {
+  int64_t most = 1;
+  for (int hs = 2; hs <= hsum_max; ++hs)
+    for (int a : {align, 1}) {
+      const int owned = chain_tile_owned(te, hs - hs / 2, hs / 2, a);
+      if (owned > 0) most = std::max(most, (ne + owned - 1) / owned);
+    }
+  return most;
+}
+
 // ---- host-pointer entry (aggmg_vcycle): lane t's byte range of a copy split over `lanes` worker threads ----------
 inline void stage_lane_range(size_t bytes, int lanes, int t, size_t* lo, size_t* hi) {
   const size_t per = ((bytes / (size_t)lanes) + 4095) & ~(size_t)4095;

@@ -407,7 +407,8 @@ struct CgtChk {
   int sweep = 0, stride = 1 << 30, final = 0;
   const double* exact = nullptr;
   double* part = nullptr;
-  int64_t ntiles = 0;
+  int64_t cap = 0;      // tiles `part` has room for (per checkpoint): a launch of more is refused
+  int64_t ntiles = 0;   // out: the tiles of the launch
 };
 int cgt_max_fused_sweeps(const CgtDev& g);   // sweeps one launch takes (point-Jacobi: + a residual or a closing checkpoint)
 int cgt_build(aggmg_ctx* ctx, aggmg_smoother* sm, const int64_t* elems, int64_t m1, int64_t nel, int one_based);

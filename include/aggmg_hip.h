@@ -363,8 +363,13 @@ int aggmg_hier_level_kind(aggmg_ctx* ctx, const aggmg_hier* h, int level, int* k
  * small agglomerated levels -- block size 2, dense off-diagonal blocks, one agglomeration ratio per level -- below
  * the finest one, both halves of src/solvers.jl:28-37 / :41-47 for two levels with the hand-over in LDS; bit for bit
  * the separate launches.  The launch is then attributed to `level` (profile tags, aggmg_hier_launch_bytes of both
- * levels apply).  AGGMG_OPT_PAIR_LEVELS switches the pairing off. */
+ * levels apply).  AGGMG_OPT_PAIR_LEVELS switches the pairing off.
+ * aggmg_hier_level_paired answers for the descent, aggmg_hier_level_paired_up for the ascent: besides the level
+ * kinds the launch needs a tile that holds both levels with their halos, which depends on the two agglomeration
+ * ratios, the sweeps and the direction (ratios (16, 16) at three sweeps: no descent tile, an ascent tile); levels
+ * without one take one launch each. */
 int aggmg_hier_level_paired(aggmg_ctx* ctx, const aggmg_hier* h, int level, int nsweeps, int* paired);
+int aggmg_hier_level_paired_up(aggmg_ctx* ctx, const aggmg_hier* h, int level, int nsweeps, int* paired);
 /* Whether level `level`'s fused kernel forms its explicit residual from the lossless symmetric form of the operator's
  * entries (AGGMG_OPT_SYMMETRIC_RESIDUAL): 1 when it was built at set-up, 0 otherwise. */
 int aggmg_hier_level_sym_residual(aggmg_ctx* ctx, const aggmg_hier* h, int level, int* on);

@@ -289,6 +289,164 @@ static void test_pair_plans() {
   EXPECT(pair_down_plan(3, 4, 4, 256, 128).own > 0 && pair_down_plan(3, 2, 2, 256, 128).own > 0);   // the benchmarked ratios have one
 }
 
+// "does this launch have a tile" (launch_has_tile, what the callers that choose a launch ask) against the planner the
+// launcher runs, over every launch kind; and the ratios the library's tiles have none for, pinned
+static void test_launch_has_tile() {
+  for (int te : kSingleTE)
+    for (int halo = 0; halo <= 17; ++halo)
+      for (int align = 1; align <= te + 1; ++align) {
+        TileQuery q;
+        q.te = te;
+        q.halo = halo;
+        q.align = align;
+        EXPECT(launch_has_tile(q) == (fused_tile_plan(te, halo, align, false, -1).owned > 0));
+        EXPECT(launch_has_tile(q) == (te - 2 * halo >= align));   // room for one agglomerate between the halos
+        q.launch = kTileMulti;
+        EXPECT(launch_has_tile(q) == (multi_tile_owned(te, halo, align) > 0));
+        if (align > 10) continue;
+        q.launch = kTileFused;
+        q.align = 1;
+        q.var_agg = true;
+        q.agg_shift = align - 2;   // -1 .. 8
+        EXPECT(launch_has_tile(q) == (fused_tile_plan(te, halo, 1, true, align - 2).owned > 0));
+      }
+  const std::pair<int, int> tiles[] = {{256, 128}, {384, 256}, {128, 128}, {100, 40}};
+  for (auto [tea, teb] : tiles)
+    for (int ns = 0; ns <= 9; ++ns)
+      for (int ra = 1; ra <= 66; ++ra)
+        for (int rb = 1; rb <= 66; ++rb) {
+          TileQuery q;
+          q.launch = kTilePairDown;
+          q.te = tea;
+          q.te_b = teb;
+          q.halo = ns;
+          q.align = ra;
+          q.rho_bc = rb;
+          EXPECT(launch_has_tile(q) == (pair_down_plan(ns, ra, rb, tea, teb).own > 0));
+          q.launch = kTilePairUp;
+          EXPECT(launch_has_tile(q) == (pair_up_plan(ns, ra, tea, teb).own > 0));
+        }
+  // the library's two-level tiles (256, 128): descents without a tile at V(3,3) -- te_b < 2 (nPre + 1) makes the plan's
+  // numerator negative for (32, 2) -- and the ones that lose theirs at 8 sweeps
+  auto down = [](int ns, int ra, int rb) {
+    TileQuery q;
+    q.launch = kTilePairDown;
+    q.te = 256;
+    q.te_b = 128;
+    q.halo = ns;
+    q.align = ra;
+    q.rho_bc = rb;
+    return launch_has_tile(q);
+  };
+  const std::pair<int, int> none3[] = {{16, 8}, {16, 16}, {13, 13}, {12, 16}, {8, 32}, {4, 64}, {31, 2}, {32, 2}};
+  for (auto [ra, rb] : none3) EXPECT(!down(3, ra, rb));
+  const std::pair<int, int> none8[] = {{12, 2}, {5, 32}, {3, 64}};
+  for (auto [ra, rb] : none8) EXPECT(down(3, ra, rb) && !down(8, ra, rb));
+  EXPECT(down(3, 12, 12) && down(3, 8, 8) && down(3, 4, 4) && down(3, 2, 2));
+  {  // ... while the ascent of (16, 16) has one: the two directions are decided apart
+    TileQuery q;
+    q.launch = kTilePairUp;
+    q.te = 256;
+    q.te_b = 128;
+    q.halo = 3;
+    q.align = 16;
+    EXPECT(launch_has_tile(q));
+  }
+  // single-level launches: ratio 128 never fits the 128-element tile; ratio 52 fits the 64-element tile of block size 8
+  // in a V(3,3) descent (halo 4) and not in the launch between two cycles (halo 7)
+  auto fused = [](int te, int halo, int rho) {
+    TileQuery q;
+    q.te = te;
+    q.halo = halo;
+    q.align = rho;
+    return launch_has_tile(q);
+  };
+  EXPECT(!fused(128, 4, 128) && !fused(128, 0, 129) && fused(128, 4, 120));
+  EXPECT(fused(64, 4, 52) && !fused(64, 7, 52));
+}
+
+// Room for the partial sums of checkpoint launches (fused_chk_reserve / chain_chk_reserve): no launch the reservation
+// was made for runs more tiles.  The formulas they replace -- 2 ne / TE + 2 and 4 ne / TE + 2, i.e. "a tile owns at
+// least half (a quarter) of itself" -- are swept alongside: the first must be seen to fall short (a ratio just under
+// TE / 2 - halo leaves a tile ONE agglomerate), or this test would not have caught the defect it was written for.
+static void test_chk_reserve() {
+  struct Shipped { int m, te; };
+  const Shipped btd[] = {{1, 512}, {2, 128}, {3, 255}, {4, 128}, {5, 153}, {6, 126}, {7, 108}, {8, 64}, {9, 56}};   // BtdTile<M>::TE
+  int64_t old_short = 0;
+  bool shown = false;
+  for (const Shipped& t : btd) {
+    const int smax = std::min(8, t.te / 8);   // sweeps of one launch (btd_max_sweeps)
+    for (int sweeps = 1; sweeps <= smax; ++sweeps)
+      for (int align = 1; align <= t.te; ++align) {
+        const int own_min = fused_tile_plan(t.te, sweeps + 1, align, false, -1).owned;
+        for (int64_t ne : {(int64_t)1, (int64_t)own_min - 1, (int64_t)own_min, (int64_t)own_min + 1, (int64_t)align * 37,
+                           (int64_t)1920, (int64_t)7680, (int64_t)align * 4099, (int64_t)1 << 24}) {
+          if (ne < 1) continue;
+          const int64_t reserved = fused_chk_reserve(ne, t.te, sweeps + 1, align, false, -1);
+          const int64_t old_reserved = 2 * ne / t.te + 2;
+          EXPECT(reserved >= 1);
+          for (int halo = 1; halo <= sweeps + 1; ++halo)     // any launch with at most these sweeps (+ 1: residual rows)
+            for (int a : {align, 1}) {                       // the one between two cycles restricts, the others do not
+              const int owned = fused_tile_plan(t.te, halo, a, false, -1).owned;
+              if (owned <= 0) continue;                      // no tile: the callers take the unfused sequence
+              const int64_t ntiles = fused_tile_subset(ne, owned, 0, 0, 0).ntiles;
+              EXPECT(ntiles <= reserved);
+              if (ntiles > old_reserved) {
+                ++old_short;
+                if (!shown && t.te == 128 && halo == 7 && a == 60 && ne == 7680) {
+                  std::printf("chk reserve, former formula 2 ne / TE + 2: TE %d halo %d ratio %d ne %lld -> %lld tiles > %lld reserved\n",
+                              t.te, halo, a, (long long)ne, (long long)ntiles, (long long)old_reserved);
+                  shown = true;
+                }
+              }
+            }
+        }
+      }
+    // agglomerates of different sizes: the owned size is not monotone in the halo (a tile that can no longer afford the
+    // shift drops it)
+    for (int sweeps = 1; sweeps <= smax; ++sweeps)
+      for (int shift = -1; shift <= 8; ++shift)
+        for (int64_t ne : {(int64_t)1, (int64_t)777, (int64_t)100000}) {
+          const int64_t reserved = fused_chk_reserve(ne, t.te, sweeps + 1, 1, true, shift);
+          for (int halo = 1; halo <= sweeps + 1; ++halo) {
+            const int owned = fused_tile_plan(t.te, halo, 1, true, shift).owned;
+            if (owned > 0) EXPECT(fused_tile_subset(ne, owned, 0, 0, 0).ntiles <= reserved);
+          }
+        }
+  }
+  EXPECT(old_short > 0 && shown);   // p = 3, ratios (60, 2), n = 7680: 128 tiles against 122
+  EXPECT(fused_tile_subset(7680, fused_tile_plan(128, 7, 60, false, -1).owned, 0, 0, 0).ntiles == 128);
+  EXPECT(fused_chk_reserve(7680, 128, 7, 60, false, -1) >= 128);
+  // the default ratios reserve no more than before
+  EXPECT(fused_chk_reserve((int64_t)1 << 24, 128, 7, 4, false, -1) <= 2 * ((int64_t)1 << 24) / 128 + 2);
+
+  // the chain kernel (CgtTile<M>::TE, point-Jacobi): hl + hr = 2 sweeps + 2 (checkpoint after the last sweep) or + 3
+  // (residual and restriction); owned = chain_tile_owned, the launcher's own arithmetic
+  const Shipped cgt[] = {{1, 256}, {2, 128}, {3, 85}, {4, 64}, {5, 153}, {6, 126}, {7, 108}, {8, 64}};
+  int64_t old_chain_short = 0;
+  for (const Shipped& t : cgt) {
+    const int smax = std::max(1, std::min(8, t.te / 8));
+    for (int sweeps = 1; sweeps <= smax; ++sweeps)
+      for (int align = 1; align <= t.te; ++align)
+        for (int64_t ne : {(int64_t)1, (int64_t)align, (int64_t)align * 37, (int64_t)7680, (int64_t)align * 4099, (int64_t)1 << 24}) {
+          const int64_t reserved = chain_chk_reserve(ne, t.te, 2 * sweeps + 3, align);
+          for (int s = 1; s <= sweeps; ++s)
+            for (int extra : {2, 3})
+              for (int a : {align, 1}) {
+                const int hs = 2 * s + extra;
+                for (int hl : {hs / 2, hs - hs / 2}) {   // the odd block goes left (chain) or right (agglomerating)
+                  const int owned = chain_tile_owned(t.te, hl, hs - hl, a);
+                  if (owned <= 0) continue;
+                  const int64_t ntiles = (ne + owned - 1) / owned;
+                  EXPECT(ntiles <= reserved);
+                  if (ntiles > 4 * ne / t.te + 2) ++old_chain_short;
+                }
+              }
+        }
+  }
+  std::printf("chk reserve, former chain formula 4 ne / TE + 2: short in %lld swept launches\n", (long long)old_chain_short);
+}
+
 static void test_lane_ranges() {
   for (size_t bytes : {(size_t)0, (size_t)1, (size_t)4095, (size_t)4096, (size_t)(16u << 20), (size_t)134217728, (size_t)134217729})
     for (int lanes = 1; lanes <= 8; ++lanes) {
@@ -335,6 +493,8 @@ int main() {
   test_tile_subsets();
   test_fused_tile_plan();
   test_pair_plans();
+  test_launch_has_tile();
+  test_chk_reserve();
   test_lane_ranges();
   test_chunk_route();
   if (failures) {

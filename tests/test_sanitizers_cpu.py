@@ -100,3 +100,5 @@ def test_host_planners_under_asan_ubsan():
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert not any(s in r.stderr for s in BAD), r.stderr[-3000:]
     assert "host_plan OK" in r.stdout
+    # the sweep of the checkpoint reservation saw the formula it replaces fall short (the defect it was written for)
+    assert "former formula 2 ne / TE + 2: TE 128 halo 7 ratio 60 ne 7680 -> 128 tiles > 122 reserved" in r.stdout

@@ -41,7 +41,12 @@ def test_reference_element_matches_oracle(oracle):
 
 @pytest.mark.parametrize("n,p,pAgg,ratios", [(16, 3, 1, (4, 2, 2)), (64, 3, 1, (4, 2, 2)), (32, 2, 1, (2, 2)),
                                              (32, 1, 0, (2, 2, 2)), (48, 4, 1, (4,)), (16, 0, 0, ()),
-                                             (8, 3, 1, ())])
+                                             (8, 3, 1, ()),
+                                             # ratios other than 2 and 4 (tests/test_gpu_ratio_regimes.py builds its
+                                             # reference operators with this class): odd ones, one coarse row per
+                                             # agglomerate, a ratio above the block count of a tile
+                                             (42, 3, 1, (7, 3)), (90, 2, 0, (3, 3, 5)), (64, 1, 1, (16, 2)),
+                                             (120, 3, 1, (60,)), (52, 7, 1, (13, 2))])
 def test_hierarchy_matches_oracle(oracle, n, p, pAgg, ratios):
     o = oracle
     U = UniformDgAggHierarchy(n, p=p, pAgg=pAgg, ratios=ratios)
