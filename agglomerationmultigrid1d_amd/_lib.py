@@ -179,6 +179,14 @@ SYMBOLS = {
     "aggmg_smoother_solve_dev": (c_int, [_P, _P, _P, _P, _P, c_int, c_double, c_double, c_int, _P,
                                          _PD, POINTER(c_int), POINTER(c_int), _P, _PD]),
     "aggmg_pcg_dev": (c_int, [_P, _P, _P, _P, c_int, c_double, c_int, c_int, c_double, _PD, POINTER(c_int)]),
+    "aggmg_residual_multi_dev": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P]),
+    "aggmg_dot_cols_dev": (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, _PD]),
+    "aggmg_norm2_cols_dev": (c_int, [_P, _P, c_int64, c_int64, c_int64, _PD]),
+    "aggmg_pcg_multi_dev": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int, c_double, c_int, c_int, c_double, _PD,
+                                    POINTER(c_int), POINTER(c_int64)]),
+    "aggmg_multigrid_multi_dev": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int, c_double, c_int, c_int, c_int, c_double,
+                                          _P, _PD, POINTER(c_int), POINTER(c_int), _P, _PD, POINTER(c_int64)]),
+    "aggmg_residual_multi_launch_bytes": (c_int, [_P, _P, c_int64, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "aggmg_profile_enable": (c_int, [_P, c_int]),
     "aggmg_profile_collect": (c_int, [_P, _PD, POINTER(c_int64)]),
     "aggmg_version": (c_char_p, []),

@@ -125,6 +125,24 @@ class Context:
         buf = (ctypes.c_double * int(n)).from_address(p.value)
         return np.frombuffer(buf, dtype=np.float64, count=int(n))
 
+    def dot_cols(self, X, Y, n=None, ncols=None, ld=None):
+        """X[:, j] . Y[:, j] for every column in one pass (C ABI aggmg_dot_cols_dev; EXTENSION): X, Y DeviceMatrix (or
+        column-major device buffers with n, ncols, ld given); entry j is bit for bit dot() of column j.  -> array of K"""
+        n, ncols, ld = _cols_shape("dot_cols", X, n, ncols, ld)
+        if isinstance(Y, DeviceMatrix) and Y.shape != (n, ncols):
+            raise DimensionMismatch("dot_cols: X and Y differ in shape")
+        out = np.zeros(max(1, int(ncols)))
+        self.check(self.lib.aggmg_dot_cols_dev(self.handle, _ptr(X), _ptr(Y), int(n), int(ncols), int(ld), _pd(out)))
+        return out
+
+    def norm2_cols(self, X, n=None, ncols=None, ld=None):
+        """||X[:, j]||_2 for every column in one pass (C ABI aggmg_norm2_cols_dev; EXTENSION); entry j is bit for bit
+        norm2() of column j.  -> array of K"""
+        n, ncols, ld = _cols_shape("norm2_cols", X, n, ncols, ld)
+        out = np.zeros(max(1, int(ncols)))
+        self.check(self.lib.aggmg_norm2_cols_dev(self.handle, _ptr(X), int(n), int(ncols), int(ld), _pd(out)))
+        return out
+
     def profile_enable(self, on=True):
         """True / 1: HIP events around every launch; 2: only the fine-level fused-down launch;
         False / 0: off"""
@@ -257,6 +275,16 @@ class DeviceMatrix:
             pass
 
 
+def _cols_shape(who, X, n, ncols, ld):
+    """(n, ncols, ld) of a column-major device matrix: a DeviceMatrix's own, or what the caller gives for a raw buffer"""
+    if isinstance(X, DeviceMatrix):
+        n = X.n if n is None else n
+        ncols = X.k if ncols is None else ncols
+    if n is None or ncols is None:
+        raise ArgumentError(f"{who}: n and ncols are needed for raw device pointers")
+    return int(n), int(ncols), int(n if ld is None else ld)
+
+
 def _ptr(v):
     """device pointer of a DeviceVector / DeviceMatrix / torch tensor / int"""
     if v is None:
@@ -364,6 +392,30 @@ class DeviceOperator:
 
     def release_host(self):
         self.ctx.check(self.ctx.lib.aggmg_op_release_host(self.ctx.handle, self.handle))
+
+    def residual_multi_dev(self, X, B, R, ncols=None, ld=None):
+        """R = B - A X on K columns (C ABI aggmg_residual_multi_dev; EXTENSION): X, B (None: R = -A X), R DeviceMatrix /
+        column-major device buffers with leading dimension ld (default N); column j of R is bit for bit the single-vector
+        residual of column j.  Asynchronous on the context stream."""
+        N = self.shape[0]
+        if ncols is None:
+            ncols = X.k if isinstance(X, DeviceMatrix) else None
+        if ncols is None:
+            raise ArgumentError("residual_multi_dev: ncols is needed for raw device pointers")
+        for M_ in (X, B, R):   # (ncols < 1, ld < N: the C ABI's ArgumentError)
+            if isinstance(M_, DeviceMatrix) and int(ncols) >= 1 and (M_.n != N or M_.k < int(ncols)):
+                raise DimensionMismatch("residual_multi_dev: matrix shape does not match (N, ncols)")
+        c = self.ctx
+        c.check(c.lib.aggmg_residual_multi_dev(c.handle, self.handle, _ptr(X), _ptr(B), int(ncols), int(N if ld is None else ld),
+                                               _ptr(R)))
+
+    def residual_multi_launch_bytes(self, K, has_b=True):
+        """(read, write) compulsory HBM bytes of one K-column residual launch (C ABI aggmg_residual_multi_launch_bytes):
+        the operator's entry arrays once, the vectors once per column"""
+        r, w = ctypes.c_int64(0), ctypes.c_int64(0)
+        self.ctx.check(self.ctx.lib.aggmg_residual_multi_launch_bytes(self.ctx.handle, self.handle, int(K), int(bool(has_b)),
+                                                                      ctypes.byref(r), ctypes.byref(w)))
+        return r.value, w.value
 
     def free(self):
         if getattr(self, "handle", None) and self.ctx.handle:
@@ -932,6 +984,41 @@ class MeshHierarchy:
         c.check(c.lib.aggmg_vcycle_multi_dev(c.handle, self.handle, _ptr(X0), _ptr(B), int(ncols), int(ld), int(nPre),
                                              int(nPost), float(alpha), _ptr(X)))
 
+    def pcg_multi_dev(self, B, X, ncols=None, ld=None, maxiter=50, tol=1e-10, nPre=3, nPost=3, alpha=2.0 / 3.0):
+        """pcg on K right-hand sides, resident on the device (C ABI aggmg_pcg_multi_dev; EXTENSION): B, X (initial guesses
+        in, results out) DeviceMatrix / column-major device buffers.  -> (iters[K], res: K lists, work_cols)"""
+        N = self._ops[0].shape[0]
+        _, K, ld = _cols_shape("pcg_multi_dev", B, N, ncols, ld)
+        hist = np.zeros((max(1, K), max(1, int(maxiter))))
+        its = np.zeros(max(1, K), dtype=np.int32)
+        work = ctypes.c_int64(0)
+        c = self.ctx
+        c.check(c.lib.aggmg_pcg_multi_dev(c.handle, self.handle, _ptr(B), _ptr(X), K, ld, int(maxiter), float(tol), int(nPre),
+                                          int(nPost), float(alpha), _pd(hist), its.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                          ctypes.byref(work)))
+        return its[:K].copy(), [hist[j, :its[j]].tolist() for j in range(K)], work.value
+
+    def multigrid_multi_dev(self, X0, B, X, maxiter, tol, ncols=None, ld=None, check_every=1, nPre=3, nPost=3, alpha=2.0 / 3.0,
+                            U_exact=None):
+        """multigrid on K right-hand sides, resident on the device (C ABI aggmg_multigrid_multi_dev; EXTENSION): X0, B, X
+        (and U_exact, the fine-level direct solutions, or None) DeviceMatrix / column-major device buffers.
+        -> (cycles[K], res: K lists, err: K lists ([] each without U_exact), work_cols)"""
+        N = self._ops[0].shape[0]
+        _, K, ld = _cols_shape("multigrid_multi_dev", B, N, ncols, ld)
+        nchk = max(1, -(-int(maxiter) // max(1, int(check_every))))
+        hist, ehist = np.zeros((max(1, K), nchk)), np.zeros((max(1, K), nchk))
+        ncyc, nck = np.zeros(max(1, K), dtype=np.int32), np.zeros(max(1, K), dtype=np.int32)
+        work = ctypes.c_int64(0)
+        pi = ctypes.POINTER(ctypes.c_int)
+        c = self.ctx
+        c.check(c.lib.aggmg_multigrid_multi_dev(c.handle, self.handle, _ptr(X0), _ptr(B), K, ld, int(maxiter), float(tol),
+                                                int(check_every), int(nPre), int(nPost), float(alpha), _ptr(X), _pd(hist),
+                                                ncyc.ctypes.data_as(pi), nck.ctypes.data_as(pi), _ptr(U_exact),
+                                                _pd(ehist) if U_exact is not None else None, ctypes.byref(work)))
+        res = [hist[j, :nck[j]].tolist() for j in range(K)]
+        err = [ehist[j, :nck[j]].tolist() if U_exact is not None else [] for j in range(K)]
+        return ncyc[:K].copy(), res, err, work.value
+
     def multi_info(self, K, nPre=3, nPost=3):
         """-> (fused, group): whether a K-column cycle runs K-column launches (True) or the single-column cycle column by
         column (False), and the columns per launch (C ABI aggmg_hier_multi_info)"""
@@ -1241,6 +1328,8 @@ def multigrid(H, x0, b, maxiter, tol, exact=True, check_every=1, nPre=3, nPost=3
     exact=False skips the direct solve and returns err empty.  check_every = c > 1 runs c cycles per residual check in
     one fused device call; res / err then have one entry per check and `iter` counts cycles.  x0, b may be DeviceVectors,
     x then is one too.  nPre / nPost / alpha: multigrid_v_cycle's defaults, which the reference's loop uses (:125)."""
+    if isinstance(b, DeviceMatrix) or (not isinstance(b, DeviceVector) and np.ndim(b) == 2):
+        return _multigrid_multi(H, x0, b, maxiter, tol, exact, check_every, nPre, nPost, alpha)
     c = H.ctx
     on_device = isinstance(x0, DeviceVector) and isinstance(b, DeviceVector)
     dx0 = x0 if isinstance(x0, DeviceVector) else c.to_device(_f64(x0))
@@ -1257,10 +1346,97 @@ def multigrid(H, x0, b, maxiter, tol, exact=True, check_every=1, nPre=3, nPost=3
     return (dx if on_device else dx.download()), (ncyc if check_every > 1 else len(res)), res, err
 
 
+def _copy_dev(c, dst, src, n):
+    """n doubles from device address src to device address dst, on the context stream (C ABI aggmg_copy_segments_dev)"""
+    if n <= 0:
+        return
+    one = lambda T, v: (T * 1)(v)
+    c.check(c.lib.aggmg_copy_segments_dev(c.handle, 1, one(ctypes.c_void_p, src), one(ctypes.c_void_p, dst),
+                                          one(ctypes.c_int64, 1), one(ctypes.c_int64, n), one(ctypes.c_int64, n),
+                                          one(ctypes.c_int64, n)))
+
+
+def _device_matrices(who, H, mats):
+    """the (N, K) arguments of a K-column solver as DeviceMatrix objects: all DeviceMatrix (-> on_device True) or all host
+    arrays in either memory order (uploaded); None entries stay None"""
+    N = H._ops[0].shape[0]
+    c = H.ctx
+    given = [M_ for M_ in mats if M_ is not None]
+    on_device = all(isinstance(M_, DeviceMatrix) for M_ in given)
+    if not on_device and any(isinstance(M_, (DeviceMatrix, DeviceVector)) for M_ in given):
+        raise ArgumentError(f"{who}: the matrices must be all DeviceMatrix or all host arrays")
+    out = []
+    shape = None
+    for M_ in mats:
+        if M_ is None:
+            out.append(None)
+            continue
+        if not on_device:
+            A_ = np.asarray(M_, dtype=np.float64)
+            if A_.ndim != 2 or A_.shape[0] != N:
+                raise DimensionMismatch(f"{who}: a matrix has shape {A_.shape}, expected ({N}, K)")
+            if A_.shape[1] < 1:
+                raise ArgumentError(f"{who}: a matrix has no columns")
+            M_ = DeviceMatrix(c, N, A_.shape[1])
+            M_.upload(A_)
+        if M_.n != N or (shape is not None and M_.shape != shape):
+            raise DimensionMismatch(f"{who}: the matrices do not match (N, K) of the fine operator")
+        shape = M_.shape
+        out.append(M_)
+    return out, on_device
+
+
+def _direct_solve_cols(H, dB):
+    """U[:, j] = H.mStiffness[1] \\ B[:, j], column by column through the hierarchy's DirectSolver, once"""
+    A0 = H.mStiffness[0]
+    ds = _direct_solver(H, H._ops[0], None if isinstance(A0, DeviceOperator) else A0)
+    c = H.ctx
+    N, K = dB.shape
+    U = DeviceMatrix(c, N, K)
+    bj = c.alloc(N)
+    for j in range(K):
+        _copy_dev(c, bj.ptr.value, dB.ptr.value + 8 * j * N, N)
+        uj = ds.solve_dev(bj)
+        _copy_dev(c, U.ptr.value + 8 * j * N, uj.ptr.value, N)
+        c.synchronize()      # (uj is released on the next turn of the loop)
+    return U
+
+
+def _multigrid_multi(H, X0, B, maxiter, tol, exact, check_every, nPre, nPost, alpha):
+    """multigrid on K right-hand sides (EXTENSION; the reference's takes vectors, src/solvers.jl:116-139): X0, B (N, K) host
+    arrays or DeviceMatrix.  -> (X, cycles[K], res: K lists, err: K lists); column j's X, count and histories are those
+    of multigrid on column j (C ABI aggmg_multigrid_multi_dev)."""
+    (dX0, dB), on_device = _device_matrices("multigrid", H, [X0, B])
+    if dX0 is None:
+        raise ArgumentError("multigrid: X0 is needed (the reference's multigrid takes an initial guess)")
+    U = _direct_solve_cols(H, dB) if exact else None
+    dX = DeviceMatrix(H.ctx, dB.n, dB.k)
+    ncyc, res, err, _ = H.multigrid_multi_dev(dX0, dB, dX, maxiter, tol, dB.k, dB.n, check_every, nPre, nPost, alpha, U)
+    iters = ncyc if check_every > 1 else np.array([len(r) for r in res], dtype=np.int32)
+    return (dX if on_device else dX.download()), iters, res, err
+
+
+def _pcg_multi(H, B, X0, maxiter, tol, nPre, nPost, alpha):
+    """pcg on K right-hand sides (EXTENSION): B, X0 (N, K) host arrays or DeviceMatrix, X0 None: zero guesses.
+    -> (X, iters[K], res: K lists); column j is pcg on column j (C ABI aggmg_pcg_multi_dev).  X0 is not modified."""
+    (dB, dX0), on_device = _device_matrices("pcg", H, [B, X0])
+    c = H.ctx
+    if dX0 is not None and not on_device:
+        dX = dX0                             # (the uploaded copy of the caller's array)
+    else:
+        dX = DeviceMatrix(c, dB.n, dB.k)     # (aggmg_dev_alloc zeroes: the zero guesses)
+        if dX0 is not None:
+            _copy_dev(c, dX.ptr.value, dX0.ptr.value, dB.n * dB.k)
+    its, res, _ = H.pcg_multi_dev(dB, dX, dB.k, dB.n, maxiter, tol, nPre, nPost, alpha)
+    return (dX if on_device else dX.download()), its, res
+
+
 def pcg(H, b, x0=None, maxiter=50, tol=1e-10, nPre=3, nPost=3, alpha=2.0 / 3.0):
     """Conjugate gradients with ldiv!(y, H, r) (src/solvers.jl:84-92) as the preconditioner,
     resident on the device (C ABI aggmg_pcg_dev).  EXTENSION: the reference offers ldiv! for this
     use but has no Krylov loop.  -> (x, iter, res)"""
+    if isinstance(b, DeviceMatrix) or (not isinstance(b, DeviceVector) and np.ndim(b) == 2):
+        return _pcg_multi(H, b, x0, maxiter, tol, nPre, nPost, alpha)
     b = _f64(b)
     c = H.ctx
     N = H._ops[0].shape[0]

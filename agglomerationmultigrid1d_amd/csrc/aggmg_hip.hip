@@ -7,6 +7,7 @@
 // No CPU compute fallback exists: every hot-path entry point launches HIP kernels or fails.
 #include "internal.hpp"
 #include "multi_kernels.hpp"
+#include "multi_solve_kernels.hpp"
 #include "pair_kernels.hpp"
 
 // ---------------------------------------------------------------------------------------------
@@ -53,6 +54,9 @@ extern "C" int aggmg_destroy(aggmg_ctx* ctx) {
     if (ctx->solv[s]) (void)hipFree(ctx->solv[s]);
   if (ctx->solv_part) (void)hipFree(ctx->solv_part);
   if (ctx->solv_sc) (void)hipFree(ctx->solv_sc);
+  if (ctx->cols_part) (void)hipFree(ctx->cols_part);
+  if (ctx->cols_sc) (void)hipFree(ctx->cols_sc);
+  if (ctx->cols_map) (void)hipFree(ctx->cols_map);
   for (auto& L : ctx->stage) {
     for (int k = 0; k < 2; ++k) {
       if (L.ev[k]) (void)hipEventDestroy(L.ev[k]);
@@ -3079,6 +3083,404 @@ extern "C" int aggmg_pcg_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* b, dou
     HIPCHK(hipMemcpyAsync(sc + 0, sc + 2, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  return AGGMG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// K right-hand sides through the outer loops (EXTENSION: the reference's solvers take vectors,
+// src/solvers.jl:116-139; every column keeps the single-vector entry point's arithmetic and bits)
+// ---------------------------------------------------------------------------------------------
+constexpr int kColsScalars = 8;   // per column: [0] rz  [1] p.q  [2] rz_new  [3] ||r||  [4] ||x - u_exact||  [5] ||b||
+constexpr int64_t kColsGridMax = 65535;
+
+static int cols_scalars(aggmg_ctx* ctx, int64_t K) {
+  CHECK(solv_scalars(ctx));
+  if (ctx->cols_cap >= K) return AGGMG_OK;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (ctx->cols_part) HIPCHK(hipFree(ctx->cols_part));
+  if (ctx->cols_sc) HIPCHK(hipFree(ctx->cols_sc));
+  if (ctx->cols_map) HIPCHK(hipFree(ctx->cols_map));
+  ctx->cols_part = ctx->cols_sc = nullptr;
+  ctx->cols_map = nullptr;
+  ctx->cols_cap = 0;
+  HIPCHK(hipMalloc((void**)&ctx->cols_part, (size_t)K * kDotBlocks * sizeof(double)));
+  HIPCHK(hipMalloc((void**)&ctx->cols_sc, (size_t)K * kColsScalars * sizeof(double)));
+  HIPCHK(hipMalloc((void**)&ctx->cols_map, (size_t)K * sizeof(int)));
+  ctx->cols_cap = K;
+  return AGGMG_OK;
+}
+static double* cols_sc(aggmg_ctx* ctx, int which) { return ctx->cols_sc + (int64_t)which * ctx->cols_cap; }
+
+// out[c] = X[:, c] . Y[:, c] (or its square root), c < K <= cols_cap; everything stays on the stream
+static int dev_dot_cols(aggmg_ctx* ctx, int64_t n, int64_t K, const double* x, int64_t ldx, const double* y, int64_t ldy,
+                        double* out, int take_sqrt) {
+  for (int64_t c0 = 0; c0 < K; c0 += kColsGridMax) {
+    const unsigned kc = (unsigned)std::min<int64_t>(kColsGridMax, K - c0);
+    hipLaunchKernelGGL(dot_cols_partial_kernel, dim3(kDotBlocks, kc), dim3(kThreads), 0, ctx->stream, n, x + c0 * ldx, ldx,
+                       y + c0 * ldy, ldy, ctx->cols_part + c0 * kDotBlocks);
+    hipLaunchKernelGGL(dot_cols_final_kernel, dim3(kc), dim3(kThreads), 0, ctx->stream, kDotBlocks,
+                       (const double*)(ctx->cols_part + c0 * kDotBlocks), out + c0, take_sqrt);
+  }
+  HIPCHK(hipGetLastError());
+  return AGGMG_OK;
+}
+// out[c] = ||X[:, c] - Y[:, ycol ? ycol[c] : c]||_2
+static int dev_diff_cols(aggmg_ctx* ctx, int64_t n, int64_t K, const double* x, int64_t ldx, const double* y, int64_t ldy,
+                         const int* ycol, double* out) {
+  for (int64_t c0 = 0; c0 < K; c0 += kColsGridMax) {
+    const unsigned kc = (unsigned)std::min<int64_t>(kColsGridMax, K - c0);
+    hipLaunchKernelGGL(diff2_cols_partial_kernel, dim3(kDotBlocks, kc), dim3(kThreads), 0, ctx->stream, n, x + c0 * ldx, ldx,
+                       ycol ? y : y + c0 * ldy, ldy, ycol ? ycol + c0 : nullptr, ctx->cols_part + c0 * kDotBlocks);
+    hipLaunchKernelGGL(dot_cols_final_kernel, dim3(kc), dim3(kThreads), 0, ctx->stream, kDotBlocks,
+                       (const double*)(ctx->cols_part + c0 * kDotBlocks), out + c0, 1);
+  }
+  HIPCHK(hipGetLastError());
+  return AGGMG_OK;
+}
+
+static int read_scalars(aggmg_ctx* ctx, const double* sc, int64_t K, double* out) {
+  HIPCHK(hipMemcpyAsync(out, sc, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return AGGMG_OK;
+}
+
+static int dot_cols_entry(aggmg_ctx* ctx, const char* who, const double* X, const double* Y, int64_t n, int64_t ncols, int64_t ld,
+                          double* out, int take_sqrt) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!X || !Y || !out) return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": NULL argument");
+  if (n < 0 || ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": needs n >= 0 and ncols >= 1");
+  if (ld < n) return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": ld must be >= n");
+  HIPCHK(hipSetDevice(ctx->device));
+  CHECK(cols_scalars(ctx, ncols));
+  CHECK(dev_dot_cols(ctx, n, ncols, X, ld, Y, ld, cols_sc(ctx, 3), take_sqrt));
+  return read_scalars(ctx, cols_sc(ctx, 3), ncols, out);
+}
+extern "C" int aggmg_dot_cols_dev(aggmg_ctx* ctx, const double* X, const double* Y, int64_t n, int64_t ncols, int64_t ld,
+                                  double* out_host) {
+  return dot_cols_entry(ctx, "aggmg_dot_cols_dev", X, Y, n, ncols, ld, out_host, 0);
+}
+extern "C" int aggmg_norm2_cols_dev(aggmg_ctx* ctx, const double* X, int64_t n, int64_t ncols, int64_t ld, double* out_host) {
+  return dot_cols_entry(ctx, "aggmg_norm2_cols_dev", X, X, n, ncols, ld, out_host, 1);
+}
+
+// ---- K-column residual -------------------------------------------------------------------------
+// the operators btd_residual_multi_kernel covers: what the K-column cycle covers (multi_level_ok), level by level
+static bool res_multi_ok(const aggmg_op* A) {
+  if (A->cgt || !A->btd) return false;
+  const BtdDev& b = *A->btd;
+  if (b.cmp ? !(b.m == 2 || b.m == 4) : b.m != 2) return false;
+  TileQuery q;
+  q.launch = kTileMulti;
+  q.te = kMultiNT / b.m;
+  q.halo = 1;
+  return launch_has_tile(q);
+}
+
+template <int M, bool CMP>
+static int launch_res_multi_t(aggmg_ctx* ctx, ResMultiArgs m) {
+  constexpr int TE = kMultiNT / M;
+  m.owned = multi_tile_owned(TE, 1, 1);   // host_plan.hpp, as res_multi_ok
+  if (m.owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column residual tile too small");
+  const int64_t ntiles = (m.lv.ne + m.owned - 1) / m.owned;
+  if (ntiles == 0) return AGGMG_OK;
+  auto go = [&](auto kern, int kb) {
+    const size_t lds = (size_t)kb * (TE + 2) * M * sizeof(double);
+    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(kMultiNT), lds, ctx->stream, m);
+  };
+  // the smallest instantiated group that holds the columns
+  if (m.kc <= 1)
+    go(btd_residual_multi_kernel<M, CMP, 1, kMultiNT>, 1);
+  else if (m.kc <= 2 || kMultiKB == 2)
+    go(btd_residual_multi_kernel<M, CMP, 2, kMultiNT>, 2);
+  else if (m.kc <= 4 || kMultiKB == 4)
+    go(btd_residual_multi_kernel<M, CMP, 4, kMultiNT>, 4);
+  else
+    go(btd_residual_multi_kernel<M, CMP, 8, kMultiNT>, 8);
+  HIPCHK(hipGetLastError());
+  return AGGMG_OK;
+}
+
+// R = B - A X (B null: R = -A X) on ncols columns; X, B, R column-major with their own leading dimensions
+static int residual_multi(aggmg_ctx* ctx, aggmg_op* A, const double* X, int64_t ldx, const double* B, int64_t ldb, int64_t ncols,
+                          double* R, int64_t ldr) {
+  if (!res_multi_ok(A)) {   // column by column: the single-vector residual on every column slice
+    double* zero = nullptr;
+    if (!B) {
+      CHECK(solv_vec(ctx, 4, A->m, &zero));
+      HIPCHK(hipMemsetAsync(zero, 0, A->m * sizeof(double), ctx->stream));
+    }
+    for (int64_t j = 0; j < ncols; ++j) CHECK(aggmg_residual_dev(ctx, A, X + j * ldx, B ? B + j * ldb : zero, R + j * ldr));
+    return AGGMG_OK;
+  }
+  const BtdDev& b = *A->btd;
+  const int64_t group = std::min<int64_t>(ncols, kMultiKB);
+  for (int64_t c0 = 0; c0 < ncols; c0 += group) {
+    ResMultiArgs m;
+    std::memset(&m, 0, sizeof(m));
+    m.lv = btd_args(b).lv;
+    m.x = X + c0 * ldx;
+    m.b = B ? B + c0 * ldb : nullptr;
+    m.r = R + c0 * ldr;
+    m.ld_x = ldx;
+    m.ld_b = ldb;
+    m.ld_r = ldr;
+    m.kc = (int)std::min<int64_t>(group, ncols - c0);
+    ProfScope ps(ctx, AGGMG_KIND_RESIDUAL, 0);
+    if (b.cmp && b.m == 4) CHECK((launch_res_multi_t<4, true>(ctx, m)));
+    else if (b.cmp) CHECK((launch_res_multi_t<2, true>(ctx, m)));
+    else CHECK((launch_res_multi_t<2, false>(ctx, m)));
+  }
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_residual_multi_dev(aggmg_ctx* ctx, aggmg_op* A, const double* X, const double* B, int64_t ncols, int64_t ld,
+                                        double* R) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!A || !X || !R) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_residual_multi_dev: NULL argument");
+  if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_residual_multi_dev: ncols must be >= 1");
+  if (A->m != A->n) return fail(ctx, AGGMG_ERR_DIMENSION, "aggmg_residual_multi_dev: the operator is not square");
+  const int64_t N = A->m;
+  if (ld < N) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_residual_multi_dev: ld must be >= N (" + std::to_string(N) + ")");
+  const int64_t span = (ncols - 1) * ld + N;
+  if (ranges_overlap(R, span, X, span) || ranges_overlap(R, span, B, span))
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_residual_multi_dev: R must not overlap X or B");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (N == 0) return AGGMG_OK;
+  return residual_multi(ctx, A, X, ld, B, ld, ncols, R, ld);
+}
+
+extern "C" int aggmg_residual_multi_launch_bytes(aggmg_ctx* ctx, aggmg_op* A, int64_t ncols, int has_b, int64_t* read_bytes,
+                                                 int64_t* write_bytes) {
+  if (!ctx || !A || !read_bytes || !write_bytes) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_residual_multi_launch_bytes: NULL argument");
+  if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_residual_multi_launch_bytes: ncols must be >= 1");
+  if (!res_multi_ok(A))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_residual_multi_launch_bytes: the operator runs aggmg_residual_dev column by column");
+  btd_launch_bytes(*A->btd, false, true, true, true, nullptr, nullptr, false, read_bytes, write_bytes, ncols);
+  if (!has_b) *read_bytes -= ncols * A->m * (int64_t)sizeof(double);
+  return AGGMG_OK;
+}
+
+// ---- the active set of a K-column loop: slot s of the work matrices holds column col[s]; a finished column leaves and
+// the last active slot's state moves into its place, so the active columns stay contiguous ------------------------------
+struct ActiveCols {
+  std::vector<int> col;
+  int n = 0;
+  bool dirty = true;   // the device copy of col (ctx->cols_map) is out of date
+  explicit ActiveCols(int64_t K) : col((size_t)K), n((int)K) {
+    for (int64_t j = 0; j < K; ++j) col[(size_t)j] = (int)j;
+  }
+  int upload(aggmg_ctx* ctx) {
+    if (!dirty || n == 0) return AGGMG_OK;
+    // (the stream is idle here: the callers have just read the norms back)
+    HIPCHK(hipMemcpyAsync(ctx->cols_map, col.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    dirty = false;
+    return AGGMG_OK;
+  }
+  // drops the slots flagged in `finished` (n entries); move(dst, src) carries slot src's state to slot dst
+  template <class F>
+  int drop(const std::vector<char>& finished, F&& move) {
+    for (int s = n - 1; s >= 0; --s) {
+      if (!finished[(size_t)s]) continue;
+      const int last = n - 1;
+      if (s != last) {
+        CHECK(move(s, last));
+        col[(size_t)s] = col[(size_t)last];
+      }
+      --n;
+      dirty = true;
+    }
+    return AGGMG_OK;
+  }
+};
+
+static int multi_solver_args(aggmg_ctx* ctx, const char* who, aggmg_hier* h, const double* B, const double* X, int64_t ncols,
+                             int64_t ld, int maxiter, int nPre, int nPost) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  const std::string w(who);
+  if (!h || !B || !X) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": NULL argument");
+  if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": ncols must be >= 1");
+  if (ncols > (1 << 20)) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": more than 2^20 columns");
+  if (nPre < 0 || nPost < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": negative sweep count");
+  if (maxiter < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": negative maxiter");
+  const int64_t N = h->lv[0].N;
+  if (ld < N) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": ld must be >= N (" + std::to_string(N) + ")");
+  if (h->coarse_mode == AGGMG_COARSE_EXTERNAL)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": hierarchy was created with AGGMG_COARSE_EXTERNAL");
+  return AGGMG_OK;
+}
+
+// K conjugate-gradient recurrences in lockstep (aggmg_pcg_dev per column): per-column scalars on the device, the
+// preconditioner one K-column cycle from zero guesses, q = -A p from the K-column residual
+extern "C" int aggmg_pcg_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* B, double* X, int64_t ncols, int64_t ld,
+                                   int maxiter, double tol, int nPre, int nPost, double alpha, double* res_hist, int* n_iters,
+                                   int64_t* work_cols) {
+  CHECK(multi_solver_args(ctx, "aggmg_pcg_multi_dev", h, B, X, ncols, ld, maxiter, nPre, nPost));
+  if (!res_hist || !n_iters) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_pcg_multi_dev: NULL argument");
+  if (nPre != nPost) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_pcg_multi_dev: the preconditioner must be symmetric (nPre == nPost)");
+  aggmg_op* A = h->lv[0].A;
+  const int64_t N = A->m, K = ncols;
+  const int64_t span = (K - 1) * ld + N;
+  if (ranges_overlap(X, span, B, span)) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_pcg_multi_dev: X must not overlap B");
+  HIPCHK(hipSetDevice(ctx->device));
+  CHECK(cols_scalars(ctx, K));
+  double *R = nullptr, *Z = nullptr, *P = nullptr, *Q = nullptr;
+  CHECK(solv_vec(ctx, 0, N * K, &R));
+  CHECK(solv_vec(ctx, 1, N * K, &Z));
+  CHECK(solv_vec(ctx, 2, N * K, &P));
+  CHECK(solv_vec(ctx, 3, N * K, &Q));
+  double *rz = cols_sc(ctx, 0), *pq = cols_sc(ctx, 1), *rzn = cols_sc(ctx, 2), *nr = cols_sc(ctx, 3), *nbd = cols_sc(ctx, 5);
+  const unsigned grid = (unsigned)((N + kThreads - 1) / kThreads);
+  std::vector<double> nb((size_t)K), res((size_t)K);
+  std::vector<char> fin((size_t)K);
+  int64_t work = 0;
+  for (int64_t j = 0; j < K; ++j) n_iters[j] = 0;
+  CHECK(dev_dot_cols(ctx, N, K, B, ld, B, ld, nbd, 1));
+  CHECK(read_scalars(ctx, nbd, K, nb.data()));
+  CHECK(residual_multi(ctx, A, X, ld, B, ld, K, R, N));                                    // r = b - A x
+  CHECK(aggmg_vcycle_multi_dev(ctx, h, nullptr, R, K, N, nPre, nPost, alpha, Z));           // z = M^-1 r
+  work += K;
+  HIPCHK(hipMemcpyAsync(P, Z, (size_t)N * K * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  CHECK(dev_dot_cols(ctx, N, K, R, N, Z, N, rz, 0));
+  ActiveCols act(K);
+  for (int it = 0; it < maxiter && act.n > 0; ++it) {
+    const int na = act.n;
+    CHECK(act.upload(ctx));
+    CHECK(residual_multi(ctx, A, P, N, nullptr, 0, na, Q, N));                             // q = -A p
+    CHECK(dev_dot_cols(ctx, N, na, P, N, Q, N, pq, 0));
+    for (int64_t c0 = 0; c0 < na; c0 += kColsGridMax) {
+      const unsigned kc = (unsigned)std::min<int64_t>(kColsGridMax, na - c0);
+      hipLaunchKernelGGL(pcg_xr_cols_kernel, dim3(grid, kc), dim3(kThreads), 0, ctx->stream, N, X, ld,
+                         (const int*)(ctx->cols_map + c0), R + c0 * N, (const double*)(P + c0 * N), (const double*)(Q + c0 * N), N,
+                         (const double*)(rz + c0), (const double*)(pq + c0));
+    }
+    HIPCHK(hipGetLastError());
+    CHECK(dev_dot_cols(ctx, N, na, R, N, R, N, nr, 1));
+    CHECK(read_scalars(ctx, nr, na, res.data()));
+    bool any = false;
+    for (int s = 0; s < na; ++s) {
+      const int j = act.col[(size_t)s];
+      res_hist[(int64_t)j * maxiter + it] = res[(size_t)s];
+      n_iters[j] = it + 1;
+      fin[(size_t)s] = res[(size_t)s] < tol * nb[(size_t)j];
+      any = any || fin[(size_t)s];
+    }
+    if (it + 1 == maxiter) break;   // (the single-vector loop's last cycle feeds nothing either)
+    if (any) {
+      CHECK(act.drop(fin, [&](int dst, int src) {
+        HIPCHK(hipMemcpyAsync(R + (int64_t)dst * N, R + (int64_t)src * N, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(P + (int64_t)dst * N, P + (int64_t)src * N, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(rz + dst, rz + src, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        return (int)AGGMG_OK;
+      }));
+      if (act.n == 0) break;
+    }
+    const int nn = act.n;
+    CHECK(aggmg_vcycle_multi_dev(ctx, h, nullptr, R, nn, N, nPre, nPost, alpha, Z));
+    work += nn;
+    CHECK(dev_dot_cols(ctx, N, nn, R, N, Z, N, rzn, 0));
+    for (int64_t c0 = 0; c0 < nn; c0 += kColsGridMax) {
+      const unsigned kc = (unsigned)std::min<int64_t>(kColsGridMax, nn - c0);
+      hipLaunchKernelGGL(pcg_p_cols_kernel, dim3(grid, kc), dim3(kThreads), 0, ctx->stream, N, P + c0 * N, (const double*)(Z + c0 * N), N,
+                         (const double*)(rzn + c0), (const double*)(rz + c0));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(rz, rzn, (size_t)nn * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (work_cols) *work_cols = work;
+  return AGGMG_OK;
+}
+
+// multigrid() per column: check_every K-column cycles, then the K-column residual and the column norms
+extern "C" int aggmg_multigrid_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, const double* B, int64_t ncols, int64_t ld,
+                                         int maxiter, double tol, int check_every, int nPre, int nPost, double alpha, double* X,
+                                         double* res_hist, int* n_cycles, int* n_checks, const double* U_exact, double* err_hist,
+                                         int64_t* work_cols) {
+  CHECK(multi_solver_args(ctx, "aggmg_multigrid_multi_dev", h, B, X, ncols, ld, maxiter, nPre, nPost));
+  if (!X0 || !res_hist || !n_cycles || !n_checks || check_every < 1)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_multigrid_multi_dev: bad argument");
+  if ((U_exact == nullptr) != (err_hist == nullptr))
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_multigrid_multi_dev: U_exact and err_hist come together (or both NULL)");
+  aggmg_op* A = h->lv[0].A;
+  const int64_t N = A->m, K = ncols;
+  const int64_t span = (K - 1) * ld + N;
+  if (ranges_overlap(X, span, X0, span) || ranges_overlap(X, span, B, span) || ranges_overlap(X, span, U_exact, span))
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_multigrid_multi_dev: X must not overlap X0, B or U_exact");
+  HIPCHK(hipSetDevice(ctx->device));
+  CHECK(cols_scalars(ctx, K));
+  for (int64_t j = 0; j < K; ++j) n_cycles[j] = n_checks[j] = 0;
+  if (work_cols) *work_cols = 0;
+  const size_t colb = (size_t)N * sizeof(double);
+  if (maxiter == 0) {   // the reference returns its initial `x = zeros(length(x0))` (src/solvers.jl:119)
+    if (N) HIPCHK(hipMemset2DAsync(X, (size_t)ld * sizeof(double), 0, colb, (size_t)K, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return AGGMG_OK;
+  }
+  double *Xa = nullptr, *Xb = nullptr, *Bw = nullptr, *R = nullptr;
+  CHECK(solv_vec(ctx, 0, N * K, &R));
+  CHECK(solv_vec(ctx, 1, N * K, &Xa));
+  CHECK(solv_vec(ctx, 2, N * K, &Xb));
+  CHECK(solv_vec(ctx, 3, N * K, &Bw));
+  double *nr = cols_sc(ctx, 3), *ne = cols_sc(ctx, 4), *nbd = cols_sc(ctx, 5);
+  std::vector<double> nb((size_t)K), res((size_t)K), err((size_t)K);
+  std::vector<char> fin((size_t)K);
+  CHECK(dev_dot_cols(ctx, N, K, B, ld, B, ld, nbd, 1));
+  CHECK(read_scalars(ctx, nbd, K, nb.data()));
+  const int nchk_max = (maxiter + check_every - 1) / check_every;
+  if (N) {
+    HIPCHK(hipMemcpy2DAsync(Xa, colb, X0, (size_t)ld * sizeof(double), colb, (size_t)K, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipMemcpy2DAsync(Bw, colb, B, (size_t)ld * sizeof(double), colb, (size_t)K, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  double *cur = Xa, *alt = Xb;
+  ActiveCols act(K);
+  int64_t work = 0;
+  int done = 0;
+  auto keep = [&](int s) {   // slot s's iterate is column col[s]'s result
+    if (N) HIPCHK(hipMemcpyAsync(X + (int64_t)act.col[(size_t)s] * ld, cur + (int64_t)s * N, colb, hipMemcpyDeviceToDevice, ctx->stream));
+    return (int)AGGMG_OK;
+  };
+  while (done < maxiter && act.n > 0) {
+    const int k = std::min(check_every, maxiter - done);
+    const int na = act.n;
+    for (int c = 0; c < k; ++c) {
+      CHECK(aggmg_vcycle_multi_dev(ctx, h, cur, Bw, na, N, nPre, nPost, alpha, alt));
+      std::swap(cur, alt);
+      work += na;
+    }
+    done += k;
+    if (U_exact) {   // err[i] = ||x - u_exact||, src/solvers.jl:128
+      CHECK(act.upload(ctx));
+      CHECK(dev_diff_cols(ctx, N, na, cur, N, U_exact, ld, ctx->cols_map, ne));
+    }
+    CHECK(residual_multi(ctx, A, cur, N, Bw, N, na, R, N));
+    CHECK(dev_dot_cols(ctx, N, na, R, N, R, N, nr, 1));
+    if (U_exact) CHECK(read_scalars(ctx, ne, na, err.data()));
+    CHECK(read_scalars(ctx, nr, na, res.data()));
+    bool any = false;
+    for (int s = 0; s < na; ++s) {
+      const int j = act.col[(size_t)s];
+      const int64_t at = (int64_t)j * nchk_max + n_checks[j];
+      if (U_exact) err_hist[at] = err[(size_t)s];
+      res_hist[at] = res[(size_t)s];
+      n_checks[j] += 1;
+      n_cycles[j] = done;
+      fin[(size_t)s] = res[(size_t)s] < tol * nb[(size_t)j];   // src/solvers.jl:131
+      any = any || fin[(size_t)s];
+    }
+    if (any) {
+      for (int s = 0; s < na; ++s)
+        if (fin[(size_t)s]) CHECK(keep(s));
+      CHECK(act.drop(fin, [&](int dst, int src) {
+        HIPCHK(hipMemcpyAsync(cur + (int64_t)dst * N, cur + (int64_t)src * N, colb, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(Bw + (int64_t)dst * N, Bw + (int64_t)src * N, colb, hipMemcpyDeviceToDevice, ctx->stream));
+        return (int)AGGMG_OK;
+      }));
+    }
+  }
+  for (int s = 0; s < act.n; ++s) CHECK(keep(s));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (work_cols) *work_cols = work;
   return AGGMG_OK;
 }
 

@@ -57,6 +57,13 @@ struct aggmg_ctx {
   int64_t solv_len[5] = {0, 0, 0, 0, 0};
   double* solv_part = nullptr;
   double* solv_sc = nullptr;
+  // K-column solver loops (aggmg_pcg_multi_dev, aggmg_multigrid_multi_dev, aggmg_dot_cols_dev): for cols_cap columns,
+  // kDotBlocks partials and kColsScalars scalars per column, and the slot -> column maps of the active set; lazy, grown
+  // for more columns, freed with the context
+  double* cols_part = nullptr;
+  double* cols_sc = nullptr;
+  int* cols_map = nullptr;
+  int64_t cols_cap = 0;
   // host <-> device staging of the host-pointer entry points (aggmg_vcycle): per worker thread a stream and two
   // pinned chunks (HostStager in aggmg_hip.hip); allocated on first use
   struct StageLane {

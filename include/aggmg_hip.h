@@ -285,6 +285,15 @@ int aggmg_vcycle_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, cons
                            int nPre, int nPost, double alpha, double* X);
 /* fused = 1 when the cycle runs K-column launches, 0 when it runs column by column; group = columns per launch */
 int aggmg_hier_multi_info(aggmg_ctx* ctx, const aggmg_hier* h, int64_t ncols, int nPre, int nPost, int* fused, int* group);
+/* R = B - A X on K columns (EXTENSION: the reference forms residuals of vectors, src/solvers.jl:33,127).  X, B, R:
+ * device, column-major N x ncols, leading dimension ld >= N; B == NULL: R = -A X, the bits of a zero B.  Column j of R
+ * is bit for bit what aggmg_residual_dev gives for column j.  Block-tridiagonal operators the K-column cycle covers
+ * (block sizes 2 / 4 with compressed couplings, 2 with dense ones) run one launch per group of at most 8 columns that
+ * reads the operator once for the group; every other operator (CG chain, generic CSR, other block sizes) runs
+ * aggmg_residual_dev column by column.  Asynchronous on the context stream.  AGGMG_ERR_ARGUMENT: NULL A, X or R,
+ * ncols < 1, ld < N, R overlapping X or B. */
+int aggmg_residual_multi_dev(aggmg_ctx* ctx, aggmg_op* A, const double* X, const double* B, int64_t ncols, int64_t ld,
+                             double* R);
 /* ncycles V-cycles back to back, x <- multigrid_v_cycle(H, x, b): the hot loop of multigrid()
  * (src/solvers.jl:124-126), same arithmetic as ncycles aggmg_vcycle_dev calls.  On block-
  * tridiagonal fine levels the post-smoothing of one cycle and the pre-smoothing of the next run in
@@ -542,6 +551,38 @@ int aggmg_smoother_solve_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, co
  * res_hist (host, >= maxiter entries): ||r|| of the recurrence after every iteration. */
 int aggmg_pcg_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* b, double* x_inout, int maxiter, double tol,
                   int nPre, int nPost, double alpha, double* res_hist, int* n_iters);
+/* ---- K right-hand sides through the outer loops (EXTENSION: the reference's solvers take vectors,
+ * src/solvers.jl:116-139).  All matrices: device, column-major, leading dimension ld >= N (>= n). ---- */
+/* out_host[j] = X[:, j] . Y[:, j] / ||X[:, j]||_2, j < ncols, each in one pass over the matrices: bit for bit
+ * aggmg_dot_dev / aggmg_norm2_dev on column j.  Synchronous (the scalars come back in one copy). */
+int aggmg_dot_cols_dev(aggmg_ctx* ctx, const double* X, const double* Y, int64_t n, int64_t ncols, int64_t ld,
+                       double* out_host);
+int aggmg_norm2_cols_dev(aggmg_ctx* ctx, const double* X, int64_t n, int64_t ncols, int64_t ld, double* out_host);
+/* aggmg_pcg_dev on K right-hand sides: K conjugate-gradient recurrences in lockstep, each with its own scalars (on
+ * the device), preconditioned by one K-column cycle from zero guesses (aggmg_vcycle_multi_dev), q = -A p from the
+ * K-column residual.  X holds the initial guesses and the results.  Column j's iterate, n_iters[j] and
+ * res_hist[j * maxiter + i] are bit for bit aggmg_pcg_dev's on column j (column j stops when ||r_j|| < tol ||b_j||).
+ * A column that has met its tolerance leaves the active set and costs no further work; *work_cols (may be NULL)
+ * returns the column-V-cycles actually run.  res_hist: host, ncols * maxiter entries; n_iters: host, ncols entries.
+ * Hierarchies the K-column cycle does not cover (aggmg_hier_multi_info: fused = 0) run its column-by-column form
+ * under the same contract.  Work space (4 N x ncols matrices) lives on the context; a repeated call allocates
+ * nothing.  AGGMG_ERR_ARGUMENT: NULL, ncols < 1, ld < N, X overlapping B, nPre != nPost, negative counts, a hierarchy
+ * created with AGGMG_COARSE_EXTERNAL. */
+int aggmg_pcg_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* B, double* X_inout, int64_t ncols, int64_t ld,
+                        int maxiter, double tol, int nPre, int nPost, double alpha, double* res_hist, int* n_iters,
+                        int64_t* work_cols);
+/* aggmg_multigrid_dev on K right-hand sides: check_every K-column cycles, then the K-column residual and the column
+ * norms, column j stopping when ||b_j - A x_j|| < tol ||b_j||.  Column j of X and n_cycles[j] / n_checks[j] are
+ * bit for bit aggmg_multigrid_dev's on column j; res_hist[j * n_checks_max + i] (and err_hist, ||x_j - U_exact[:, j]||,
+ * when U_exact and err_hist are given -- both or neither) are bit for bit those of its AGGMG_OPT_MG_CHECKPOINT = 0
+ * form, n_checks_max = ceil(maxiter / check_every).  maxiter == 0: X = 0, no checks.  Finished columns leave the
+ * active set; *work_cols (may be NULL): column-V-cycles actually run.  Work space (4 N x ncols matrices) on the
+ * context.  AGGMG_ERR_ARGUMENT: NULL, ncols < 1, ld < N, check_every < 1, X overlapping X0, B or U_exact, U_exact
+ * without err_hist or the reverse, negative counts, a hierarchy created with AGGMG_COARSE_EXTERNAL. */
+int aggmg_multigrid_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, const double* B, int64_t ncols, int64_t ld,
+                              int maxiter, double tol, int check_every, int nPre, int nPost, double alpha, double* X,
+                              double* res_hist, int* n_cycles, int* n_checks, const double* U_exact, double* err_hist,
+                              int64_t* work_cols);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* HIP-event timing of kernel launches on the context stream, by tag = kind * 16 + level
@@ -581,6 +622,11 @@ int aggmg_hier_multi_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int level
                                   int64_t* read_bytes, int64_t* write_bytes);
 int aggmg_smoother_launch_bytes(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, int what, int64_t* read_bytes,
                                 int64_t* write_bytes);
+/* compulsory bytes of one K-column residual launch (aggmg_residual_multi_dev, EXTENSION): the operator's entry arrays
+ * once, X (and B when has_b) once per column, R once per column.  AGGMG_ERR_UNSUPPORTED on an operator that runs
+ * column by column. */
+int aggmg_residual_multi_launch_bytes(aggmg_ctx* ctx, aggmg_op* A, int64_t ncols, int has_b, int64_t* read_bytes,
+                                      int64_t* write_bytes);
 
 /* Library / build identification ("aggmg_hip gfx950 ..."). */
 const char* aggmg_version(void);

@@ -560,6 +560,65 @@ function multigrid(Hd::DeviceHierarchy, x0::Union{AbstractVector,DeviceVector}, 
     return (on_device ? dx : download(dx)), Int(ncyc[]), res[1:nck[]], (exact ? err[1:nck[]] : Float64[])
 end
 
+# ---- the solvers on K right-hand sides (EXTENSION: the reference's take vectors, src/solvers.jl:116-139) ----
+# U[:, j] = A \\ B[:, j] on the device, column by column through the hierarchy's DirectSolver (host fallback: `\\` on
+# the downloaded matrix)
+function solve(ds::DirectSolver, A_host, B::DeviceMatrix)
+    ds.h == C_NULL && return DeviceMatrix(ds.ctx, A_host \\ download(B))
+    U = DeviceMatrix(ds.ctx, B.n, B.k); z = DeviceVector(ds.ctx, B.n)     # z: zero guess (aggmg_dev_alloc zeroes)
+    for j in 0:B.k-1
+        off = 8 * j * B.n
+        GC.@preserve z B U check(ds.ctx.h, ccall((:aggmg_vcycle_dev, LIB), Cint,
+            (Handle, Handle, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Float64, Ptr{Cvoid}),
+            ds.ctx.h, ds.h, z.p, B.p + off, 0, 0, 1.0, U.p + off))
+    end
+    return U
+end
+
+# multigrid on device matrices -> X::DeviceMatrix, cycles::Vector{Int}, res, err (one Vector per column): column j's
+# iterate, count and histories are those of multigrid on column j (aggmg_multigrid_multi_dev); columns that have met
+# their tolerance stop costing work.
+function multigrid(Hd::DeviceHierarchy, X0::DeviceMatrix, B::DeviceMatrix, maxiter::Integer, tol::AbstractFloat;
+        nPre::Integer = 3, nPost::Integer = 3, alpha::AbstractFloat = 2.0 / 3.0, exact::Bool = true,
+        check_every::Integer = 1)
+    (size(X0) == size(B)) || throw(DimensionMismatch("multigrid: X0 and B differ in size"))
+    K = B.k
+    X = DeviceMatrix(Hd.ctx, B.n, K)
+    nchk = cld(max(maxiter, 1), check_every)
+    res = zeros(nchk, K); err = zeros(nchk, K)            # column j: the history of right-hand side j
+    ncyc = zeros(Cint, K); nck = zeros(Cint, K); work = Ref{Int64}(0)
+    if exact
+        UE = solve(direct_solver(Hd, Hd.ops[1]), Hd.H.mStiffness[1], B)
+        GC.@preserve X0 B X UE res err ncyc nck check(Hd.ctx.h, ccall((:aggmg_multigrid_multi_dev, LIB), Cint,
+            (Handle, Handle, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Float64, Cint, Cint, Cint, Float64, Ptr{Cvoid},
+             Ptr{Float64}, Ptr{Cint}, Ptr{Cint}, Ptr{Cvoid}, Ptr{Float64}, Ref{Int64}),
+            Hd.ctx.h, Hd.h, X0.p, B.p, K, B.n, maxiter, Float64(tol), check_every, nPre, nPost, Float64(alpha), X.p,
+            res, ncyc, nck, UE.p, err, work))
+    else
+        GC.@preserve X0 B X res ncyc nck check(Hd.ctx.h, ccall((:aggmg_multigrid_multi_dev, LIB), Cint,
+            (Handle, Handle, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Float64, Cint, Cint, Cint, Float64, Ptr{Cvoid},
+             Ptr{Float64}, Ptr{Cint}, Ptr{Cint}, Ptr{Cvoid}, Ptr{Float64}, Ref{Int64}),
+            Hd.ctx.h, Hd.h, X0.p, B.p, K, B.n, maxiter, Float64(tol), check_every, nPre, nPost, Float64(alpha), X.p,
+            res, ncyc, nck, C_NULL, C_NULL, work))
+    end
+    return X, Int.(ncyc), [res[1:nck[j], j] for j in 1:K], [exact ? err[1:nck[j], j] : Float64[] for j in 1:K]
+end
+
+# pcg(H, B; X0, maxiter, tol) on device matrices -> X::DeviceMatrix, iters::Vector{Int}, res (one Vector per column):
+# K conjugate-gradient recurrences in lockstep, preconditioned by one K-column cycle from zero guesses
+# (aggmg_pcg_multi_dev); column j is the single-vector recurrence on column j.  X0 = nothing: zero guesses.
+function pcg(Hd::DeviceHierarchy, B::DeviceMatrix; X0::Union{Nothing,DeviceMatrix} = nothing, maxiter::Integer = 50,
+        tol::AbstractFloat = 1e-10, nPre::Integer = 3, nPost::Integer = 3, alpha::AbstractFloat = 2.0 / 3.0)
+    K = B.k
+    X = X0 === nothing ? DeviceMatrix(Hd.ctx, B.n, K) : DeviceMatrix(Hd.ctx, download(X0))   # (fresh memory is zeroed)
+    res = zeros(max(maxiter, 1), K); its = zeros(Cint, K); work = Ref{Int64}(0)
+    GC.@preserve B X res its check(Hd.ctx.h, ccall((:aggmg_pcg_multi_dev, LIB), Cint,
+        (Handle, Handle, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Float64, Cint, Cint, Float64, Ptr{Float64}, Ptr{Cint},
+         Ref{Int64}),
+        Hd.ctx.h, Hd.h, B.p, X.p, K, B.n, maxiter, Float64(tol), nPre, nPost, Float64(alpha), res, its, work))
+    return X, Int.(its), [res[1:its[j], j] for j in 1:K]
+end
+
 # iterative_smoother_solve(A, smoother, x0, b; maxiter = 1000, tol = 1e-6, alpha = 1.0) -> x, iter, res, err
 # (src/solvers.jl:189-213) for a device smoother, the reference's full 4-tuple: A is the host matrix the reference
 # passes (only the host fallback of the direct solve of :194 reads it), the sweeps run on S.A, and
