@@ -186,6 +186,10 @@ SYMBOLS = {
                                     POINTER(c_int), POINTER(c_int64)]),
     "aggmg_multigrid_multi_dev": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int, c_double, c_int, c_int, c_int, c_double,
                                           _P, _PD, POINTER(c_int), POINTER(c_int), _P, _PD, POINTER(c_int64)]),
+    "aggmg_owned_dot_dev": (c_int, [_P, _P, _P, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_double)]),
+    "aggmg_pcg_xr_owned_dev": (c_int, [_P, c_int64, _P, _P, _P, _P, c_double, c_int, POINTER(c_int64), POINTER(c_int64),
+                                       POINTER(c_double)]),
+    "aggmg_pcg_p_dev": (c_int, [_P, c_int64, _P, _P, c_double]),
     "aggmg_residual_multi_launch_bytes": (c_int, [_P, _P, c_int64, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "aggmg_profile_enable": (c_int, [_P, c_int]),
     "aggmg_profile_collect": (c_int, [_P, _PD, POINTER(c_int64)]),

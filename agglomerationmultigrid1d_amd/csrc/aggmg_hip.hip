@@ -57,6 +57,7 @@ extern "C" int aggmg_destroy(aggmg_ctx* ctx) {
   if (ctx->cols_part) (void)hipFree(ctx->cols_part);
   if (ctx->cols_sc) (void)hipFree(ctx->cols_sc);
   if (ctx->cols_map) (void)hipFree(ctx->cols_map);
+  if (ctx->own_part) (void)hipFree(ctx->own_part);
   for (auto& L : ctx->stage) {
     for (int k = 0; k < 2; ++k) {
       if (L.ev[k]) (void)hipEventDestroy(L.ev[k]);

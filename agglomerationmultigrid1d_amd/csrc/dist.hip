@@ -29,6 +29,7 @@
 #include <rccl/rccl.h>
 
 #include "internal.hpp"
+#include "dist_solve_kernels.hpp"
 
 namespace {
 
@@ -838,5 +839,99 @@ extern "C" int aggmg_dist_graph_info(aggmg_ctx* ctx, const aggmg_dist* d, int64_
     *captured = n;
   }
   if (broken) *broken = d->graph_broken ? 1 : 0;
+  return AGGMG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// conjugate gradients around the partitioned cycle (distributed.pcg): this rank's terms of the global
+// scalars and the vector updates, over the owned index ranges of a local vector (dist_solve_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+static int owned_ranges(aggmg_ctx* ctx, const char* who, int nranges, const int64_t* lo, const int64_t* hi, int64_t n,
+                        OwnedRanges* R) {
+  if (nranges < 0 || nranges > kOwnedMaxRanges || (nranges && (!lo || !hi)))
+    return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": 0..4 ranges, no NULL arrays");
+  R->n = nranges;
+  for (int g = 0; g < kOwnedMaxRanges; ++g) {
+    R->lo[g] = R->hi[g] = 0;
+    if (g >= nranges) continue;
+    if (lo[g] < 0 || hi[g] < lo[g] || (n >= 0 && hi[g] > n))
+      return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": a range must satisfy 0 <= lo <= hi <= n");
+    // (a row in two ranges would count twice in the dot product and once in the fused update: refuse it in both)
+    for (int f = 0; f < g; ++f)
+      if (lo[g] < hi[g] && lo[f] < hi[f] && lo[g] < hi[f] && lo[f] < hi[g])
+        return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": ranges must not overlap");
+    R->lo[g] = lo[g];
+    R->hi[g] = hi[g];
+  }
+  if (!ctx->own_part)
+    HIPCHK(hipMalloc((void**)&ctx->own_part, (size_t)(kOwnedBlocks * kOwnedMaxRanges + 1) * sizeof(double)));
+  return AGGMG_OK;
+}
+
+// 16-byte accesses when every vector of the call starts at the same offset from a 16-byte boundary
+template <typename... P>
+static bool owned_same_alignment(const double* first, P... rest) {
+  const uintptr_t a = (uintptr_t)first & 15;
+  bool same = true;
+  for (const double* p : {(const double*)rest...}) same = same && (((uintptr_t)p & 15) == a);
+  return same;
+}
+static int owned_parity(const double* x) { return (int)(((uintptr_t)x >> 3) & 1); }
+
+static int owned_scalar_out(aggmg_ctx* ctx, int nparts, double* out) {
+  double* sc = ctx->own_part + kOwnedBlocks * kOwnedMaxRanges;
+  hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, nparts, (const double*)ctx->own_part, sc, 0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, sc, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_owned_dot_dev(aggmg_ctx* ctx, const double* x, const double* y, int nranges, const int64_t* lo,
+                                   const int64_t* hi, double* out) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!x || !y || !out) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_owned_dot_dev: NULL argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  OwnedRanges R;
+  CHECK(owned_ranges(ctx, "aggmg_owned_dot_dev", nranges, lo, hi, -1, &R));
+  if (nranges == 0) {
+    *out = 0.0;
+    return AGGMG_OK;
+  }
+  const dim3 grid(kOwnedBlocks, (unsigned)nranges);
+  if (owned_same_alignment(x, y))
+    hipLaunchKernelGGL(owned_dot_partial_kernel<true>, grid, dim3(kThreads), 0, ctx->stream, R, owned_parity(x), x, y, ctx->own_part);
+  else
+    hipLaunchKernelGGL(owned_dot_partial_kernel<false>, grid, dim3(kThreads), 0, ctx->stream, R, owned_parity(x), x, y, ctx->own_part);
+  HIPCHK(hipGetLastError());
+  return owned_scalar_out(ctx, kOwnedBlocks * nranges, out);
+}
+
+extern "C" int aggmg_pcg_xr_owned_dev(aggmg_ctx* ctx, int64_t n, double* x, double* r, const double* p, const double* q,
+                                      double a, int nranges, const int64_t* lo, const int64_t* hi, double* rr_out) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!x || !r || !p || !q || !rr_out || n < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_pcg_xr_owned_dev: bad argument");
+  if (x == r || x == p || x == q || r == p || r == q)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_pcg_xr_owned_dev: x and r must not alias another vector");
+  HIPCHK(hipSetDevice(ctx->device));
+  OwnedRanges R;
+  CHECK(owned_ranges(ctx, "aggmg_pcg_xr_owned_dev", nranges, lo, hi, n, &R));
+  if (owned_same_alignment(x, r, p, q))
+    hipLaunchKernelGGL(owned_xr_kernel<true>, dim3(kOwnedBlocks), dim3(kThreads), 0, ctx->stream, n, owned_parity(x), x, r, p, q, a, R, ctx->own_part);
+  else
+    hipLaunchKernelGGL(owned_xr_kernel<false>, dim3(kOwnedBlocks), dim3(kThreads), 0, ctx->stream, n, owned_parity(x), x, r, p, q, a, R, ctx->own_part);
+  HIPCHK(hipGetLastError());
+  return owned_scalar_out(ctx, kOwnedBlocks, rr_out);
+}
+
+extern "C" int aggmg_pcg_p_dev(aggmg_ctx* ctx, int64_t n, double* p, const double* z, double beta) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!p || !z || n < 0 || p == z) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_pcg_p_dev: bad argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (owned_same_alignment(p, z))
+    hipLaunchKernelGGL(owned_p_kernel<true>, dim3(kOwnedBlocks), dim3(kThreads), 0, ctx->stream, n, owned_parity(p), p, z, beta);
+  else
+    hipLaunchKernelGGL(owned_p_kernel<false>, dim3(kOwnedBlocks), dim3(kThreads), 0, ctx->stream, n, owned_parity(p), p, z, beta);
+  HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }

@@ -64,6 +64,9 @@ struct aggmg_ctx {
   double* cols_sc = nullptr;
   int* cols_map = nullptr;
   int64_t cols_cap = 0;
+  // owned-range reductions of the partitioned conjugate-gradient loop (aggmg_owned_dot_dev, aggmg_pcg_xr_owned_dev):
+  // kOwnedBlocks partial sums per range, then the scalar; lazy, freed with the context
+  double* own_part = nullptr;
   // host <-> device staging of the host-pointer entry points (aggmg_vcycle): per worker thread a stream and two
   // pinned chunks (HostStager in aggmg_hip.hip); allocated on first use
   struct StageLane {

@@ -850,6 +850,55 @@ class HipEngine:
             tot += out.value
         return tot
 
+    # ---- conjugate gradients around the partitioned cycle (pcg): this rank's terms and updates, library stream ----
+    def _ranges(self, ranges, n):
+        k = len(ranges)
+        if k > 4 or any(not (0 <= lo <= hi <= n) for lo, hi in ranges):
+            raise ValueError("owned ranges: at most four [lo, hi) ranges inside the local vector")
+        arr = ctypes.c_int64 * max(k, 1)
+        return k, arr(*[int(lo) for lo, _ in ranges]), arr(*[int(hi) for _, hi in ranges])
+
+    def owned_dot(self, ranges, x, y):
+        """sum over the local rows in `ranges` of x_i y_i, one pass over all ranges (aggmg_owned_dot_dev)"""
+        c = self.ctx
+        k, lo, hi = self._ranges(ranges, min(x.numel(), y.numel()))
+        out = ctypes.c_double(0.0)
+        c.check(c.lib.aggmg_owned_dot_dev(c.handle, _p(x), _p(y), k, lo, hi, ctypes.byref(out)))
+        return out.value
+
+    def residual(self, x, b, r):
+        """r = b - A_0 x with the local fine operator (rows of owned elements exact when x's ghosts are valid)"""
+        c = self.ctx
+        c.check(c.lib.aggmg_residual_dev(c.handle, self.H._ops[0].handle, _p(x), _p(b), _p(r)))
+
+    def neg_apply(self, p, q):
+        """q = -A_0 p: the residual with a zero right-hand side, as aggmg_pcg_dev forms it"""
+        if getattr(self, "_zero_rhs", None) is None or self._zero_rhs.numel() != p.numel():
+            self._zero_rhs = self.new(p.numel())
+            self.torch.cuda.synchronize()
+        self.residual(p, self._zero_rhs, q)
+
+    def pcg_xr(self, ranges, x, r, p, q, a):
+        """x += a p, r += a q on the local vectors; -> sum over `ranges` of the new r_i^2 (aggmg_pcg_xr_owned_dev)"""
+        c = self.ctx
+        n = x.numel()
+        if not (r.numel() == p.numel() == q.numel() == n):
+            raise ValueError("pcg_xr: vectors of one length")
+        k, lo, hi = self._ranges(ranges, n)
+        out = ctypes.c_double(0.0)
+        c.check(c.lib.aggmg_pcg_xr_owned_dev(c.handle, n, _p(x), _p(r), _p(p), _p(q), float(a), k, lo, hi, ctypes.byref(out)))
+        return out.value
+
+    def pcg_p(self, p, z, beta):
+        """p = z + beta p on the local vectors (aggmg_pcg_p_dev)"""
+        c = self.ctx
+        if p.numel() != z.numel():
+            raise ValueError("pcg_p: vectors of one length")
+        c.check(c.lib.aggmg_pcg_p_dev(c.handle, p.numel(), _p(p), _p(z), float(beta)))
+
+    def assign(self, dst, src):
+        self.copy_segments([(dst, src)])
+
     def down(self, x0, b, nPre, alpha):
         self.H.vcycle_down_dev(x0, b, nPre, alpha)
 
@@ -1005,6 +1054,70 @@ def multigrid(dv, x0, b, maxiter, tol, nPre=3, nPost=3, alpha=2.0 / 3.0, check_e
             if r < tol * nb:
                 break
     return src, done, res
+
+
+def pcg(dv, b, x0=None, maxiter=50, tol=1e-10, nPre=3, nPost=3, alpha=2.0 / 3.0):
+    """Conjugate gradients on an element-partitioned hierarchy, preconditioned by one partitioned V-cycle from a zero guess
+    (ldiv!, src/solvers.jl:84-92).  EXTENSION: the recurrence of the single-GPU pcg (C ABI aggmg_pcg_dev), operation for
+    operation -- r = b - A x, z = M^-1 r, p = z, rz = r.z, then per iteration q = -A p, a = rz / (-(p.q)), x += a p, r += a q,
+    res = ||r||, stop when res < tol ||b||, z = M^-1 r, beta = rz_new / rz, p = z + beta p -- with every global scalar the
+    rank-ordered sum (comm.sum) of the ranks' owned terms: all ranks hold the same bits and take the same branch.
+
+    dv: DistributedVCycle or NativeDistributedVCycle.  b, x0: local vectors (owned + ghosts); b valid on the whole local
+    domain, as for multigrid().  Ghosts are exchanged where a vector is read beyond the owned rows: x0 once, r before each
+    cycle (the cycle reads its right-hand side on the whole local domain), p before A p -- two interface exchanges per
+    iteration beside the cycle's own, and three scalar sums (p.q, ||r||^2, r.z).  x keeps valid ghosts throughout (it is
+    updated with p's).  -> (x local vector whose owned part is the iterate, iterations, res list); maxiter <= 0 returns a
+    copy of the start vector, 0 and [].  nPre != nPost raises ValueError (the preconditioner must be symmetric), so do
+    sweep counts above the layout's halo widths; p.q >= 0 (A or M not positive definite) raises ArithmeticError on every
+    rank alike."""
+    e, L, c = dv.e, dv.L, dv.c
+    if nPre != nPost:
+        raise ValueError("pcg: nPre must equal nPost (the V-cycle preconditioner has to be symmetric)")
+    if nPre > L.nPre or nPost > L.nPost:
+        raise ValueError("halo widths were sized for fewer sweeps")
+    own = L.owned_ranges(0)
+    n = L.local_dofs(0)
+    on_gpu = hasattr(e, "torch") and e.torch.cuda.is_available()
+    sync = e.torch.cuda.synchronize if on_gpu else (lambda: None)
+    sync()                         # (x0 / b may have been filled on torch's stream just now)
+    x, r, z, p, q, zero = (e.new(n) for _ in range(6))
+    sync()                         # torch zero-filled the new vectors on ITS stream; the library may run on its own
+    if x0 is not None:
+        e.assign(x, x0)
+    if maxiter <= 0:
+        sync()
+        return x, 0, []
+    nb = np.sqrt(c.sum(e.owned_dot(own, b, b)))
+    if x0 is not None:
+        dv.exchange_ghosts(x)
+
+    def precondition():            # z = M^-1 r: one cycle from the zero vector, whose ghosts are valid as they are
+        dv.exchange_ghosts(r)
+        dv.vcycle(zero, r, z, nPre, nPost, alpha, x0_ghosts_valid=True)
+
+    e.residual(x, b, r)
+    precondition()
+    e.assign(p, z)
+    rz = c.sum(e.owned_dot(own, r, z))
+    res = []
+    for _ in range(int(maxiter)):
+        dv.exchange_ghosts(p)
+        e.neg_apply(p, q)
+        pq = c.sum(e.owned_dot(own, p, q))
+        if not pq < 0.0:
+            sync()                 # (the temporaries go back to torch's allocator: no library work may be queued on them)
+            raise ArithmeticError(f"pcg: p.Ap = {-pq!r} is not positive: the operator or the cycle is not positive definite")
+        a = rz / (-pq)
+        res.append(float(np.sqrt(c.sum(e.pcg_xr(own, x, r, p, q, a)))))
+        if res[-1] < tol * nb:
+            break
+        precondition()
+        rz_new = c.sum(e.owned_dot(own, r, z))
+        e.pcg_p(p, z, rz_new / rz)
+        rz = rz_new
+    sync()
+    return x, len(res), res
 
 
 def _replicated_coarse_hierarchy(Ac, ctx, world):

@@ -571,6 +571,26 @@ int aggmg_norm2_cols_dev(aggmg_ctx* ctx, const double* X, int64_t n, int64_t nco
 int aggmg_pcg_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* B, double* X_inout, int64_t ncols, int64_t ld,
                         int maxiter, double tol, int nPre, int nPost, double alpha, double* res_hist, int* n_iters,
                         int64_t* work_cols);
+/* ---- conjugate gradients around the element-partitioned cycle (EXTENSION: aggmg_pcg_dev's recurrence with every
+ * global scalar a rank-ordered sum of the ranks' owned terms; the reference has neither a partition nor a Krylov loop).
+ * A local vector holds a rank's owned rows and its ghost rows; the owned rows are `nranges` <= 4 index ranges
+ * [lo[g], hi[g]) of the local numbering (host arrays).  All three run on the context's stream; the two that return a
+ * scalar synchronise it, as aggmg_dot_dev does.  Fixed slices, strides and summation trees, no atomics: the same bits
+ * from run to run (for vectors at the same offsets from a 16-byte boundary).  AGGMG_ERR_ARGUMENT: NULL, more than 4
+ * ranges, a range with lo < 0 or hi < lo, two non-empty ranges that overlap, aliased vectors; hi > n where the call
+ * takes n. ---- */
+/* *out = sum over the ranges of x_i y_i: one partial-sum launch over all ranges, one final launch.  The call takes no
+ * vector length, so hi[g] is NOT checked against the end of x and y: the caller guarantees every range lies inside
+ * both. */
+int aggmg_owned_dot_dev(aggmg_ctx* ctx, const double* x, const double* y, int nranges, const int64_t* lo,
+                        const int64_t* hi, double* out);
+/* x += a p, r += a q on the n rows of the local vectors, and in the same pass *rr_out = sum over the ranges of the new
+ * r_i^2.  With q = -A p (aggmg_residual_dev with a zero right-hand side) and a = rz / (-(p.q)) this is the step of
+ * aggmg_pcg_dev; a arrives by value because the global scalars are on the host after the sum over the ranks. */
+int aggmg_pcg_xr_owned_dev(aggmg_ctx* ctx, int64_t n, double* x, double* r, const double* p, const double* q, double a,
+                           int nranges, const int64_t* lo, const int64_t* hi, double* rr_out);
+/* p = z + beta p on n rows.  Asynchronous. */
+int aggmg_pcg_p_dev(aggmg_ctx* ctx, int64_t n, double* p, const double* z, double beta);
 /* aggmg_multigrid_dev on K right-hand sides: check_every K-column cycles, then the K-column residual and the column
  * norms, column j stopping when ||b_j - A x_j|| < tol ||b_j||.  Column j of X and n_cycles[j] / n_checks[j] are
  * bit for bit aggmg_multigrid_dev's on column j; res_hist[j * n_checks_max + i] (and err_hist, ||x_j - U_exact[:, j]||,
