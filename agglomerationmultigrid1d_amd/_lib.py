@@ -123,6 +123,7 @@ SYMBOLS = {
     "aggmg_vcycle": (c_int, [_P, _P, _PD, _PD, c_int, c_int, c_double, _PD]),
     "aggmg_vcycle_dev": (c_int, [_P, _P, _P, _P, c_int, c_int, c_double, _P]),
     "aggmg_vcycle_multi_dev": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int, c_int, c_double, _P]),
+    "aggmg_hier_coarse_solve_multi_dev": (c_int, [_P, _P, _P, c_int64, c_int64, _P]),
     "aggmg_hier_multi_info": (c_int, [_P, _P, c_int64, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
     "aggmg_vcycles_dev": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_double, _P]),
     "aggmg_hier_set_restriction": (c_int, [_P, _P, c_int]),

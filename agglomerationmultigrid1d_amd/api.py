@@ -984,6 +984,28 @@ class MeshHierarchy:
         c.check(c.lib.aggmg_vcycle_multi_dev(c.handle, self.handle, _ptr(X0), _ptr(B), int(ncols), int(ld), int(nPre),
                                              int(nPost), float(alpha), _ptr(X)))
 
+    def coarse_solve_multi_dev(self, B, X, ncols=None, ld=None):
+        """X = A_n \\ B, the coarsest-level direct solve (src/solvers.jl:39) on K right-hand sides, resident on the device
+        (C ABI aggmg_hier_coarse_solve_multi_dev; EXTENSION) -- for a one-level hierarchy the `A \\ B` of :120.  B, X:
+        DeviceMatrix / column-major device buffers of N_n rows (the coarsest operator's) with leading dimension ld
+        (default N_n); on the device factorisation a group of columns shares every launch and column j of X is bit for
+        bit the single-column solve of column j.  Asynchronous on the context stream."""
+        N = self._ops[-1].shape[0]
+        for M_ in (B, X):
+            if isinstance(M_, np.ndarray) or M_ is None:
+                raise ArgumentError("coarse_solve_multi_dev: B and X must be DeviceMatrix objects or device buffers")
+        if ncols is None:
+            ncols = B.k if isinstance(B, DeviceMatrix) else None
+        if ncols is None:
+            raise ArgumentError("coarse_solve_multi_dev: ncols is needed for raw device pointers")
+        if ld is None:
+            ld = N
+        for M_ in (B, X):   # (ncols < 1, ld < N: the C ABI's ArgumentError)
+            if isinstance(M_, DeviceMatrix) and int(ncols) >= 1 and (M_.n != N or M_.k < int(ncols)):
+                raise DimensionMismatch("coarse_solve_multi_dev: matrix shape does not match (N, ncols)")
+        c = self.ctx
+        c.check(c.lib.aggmg_hier_coarse_solve_multi_dev(c.handle, self.handle, _ptr(B), int(ncols), int(ld), _ptr(X)))
+
     def pcg_multi_dev(self, B, X, ncols=None, ld=None, maxiter=50, tol=1e-10, nPre=3, nPost=3, alpha=2.0 / 3.0):
         """pcg on K right-hand sides, resident on the device (C ABI aggmg_pcg_multi_dev; EXTENSION): B, X (initial guesses
         in, results out) DeviceMatrix / column-major device buffers.  -> (iters[K], res: K lists, work_cols)"""
@@ -1277,16 +1299,34 @@ class DirectSolver:
             self.where = "host sparse LU"
 
     def solve_dev(self, b):
-        """b: DeviceVector -> DeviceVector"""
+        """b: DeviceVector -> DeviceVector, or DeviceMatrix (N, K) -> DeviceMatrix (EXTENSION; Julia's `A \\ B` takes
+        matrices): on the device the columns share every launch of the factorisation, a group at a time
+        (MeshHierarchy.coarse_solve_multi_dev), and column j is bit for bit the solve of column j; the host sparse LU
+        solves the downloaded matrix in one call"""
         N = self.op.shape[0]
+        if isinstance(b, DeviceMatrix):
+            if b.n != N:
+                raise DimensionMismatch(f"DirectSolver.solve_dev: {b.n} rows, the operator has {N}")
+            if self.H is not None:
+                X = DeviceMatrix(self.ctx, N, b.k)
+                self.H.coarse_solve_multi_dev(b, X)
+                return X
+            X = DeviceMatrix(self.ctx, N, b.k)
+            X.upload(self._host_lu().solve(b.download()))
+            return X
+        if isinstance(b, np.ndarray):
+            raise ArgumentError("DirectSolver.solve_dev: b must be a DeviceVector or a DeviceMatrix, not a host array")
         if self.H is not None:
             x, z = self.ctx.alloc(N), self.ctx.alloc(N)
             self.H.vcycle_dev(z, b, x, 0, 0, 1.0)
             return x
+        return self.ctx.to_device(self._host_lu().solve(b.download()))
+
+    def _host_lu(self):
         if self._lu is None:
             A = self._host if self._host is not None else self.op.to_scipy()
             self._lu = spla.splu(sp.csc_matrix(A))
-        return self.ctx.to_device(self._lu.solve(b.download()))
+        return self._lu
 
 
 def _direct_solver(owner, op, host_matrix=None):
@@ -1387,19 +1427,10 @@ def _device_matrices(who, H, mats):
 
 
 def _direct_solve_cols(H, dB):
-    """U[:, j] = H.mStiffness[1] \\ B[:, j], column by column through the hierarchy's DirectSolver, once"""
+    """U = H.mStiffness[1] \\ B through the hierarchy's DirectSolver, once: the columns in groups on the device"""
     A0 = H.mStiffness[0]
     ds = _direct_solver(H, H._ops[0], None if isinstance(A0, DeviceOperator) else A0)
-    c = H.ctx
-    N, K = dB.shape
-    U = DeviceMatrix(c, N, K)
-    bj = c.alloc(N)
-    for j in range(K):
-        _copy_dev(c, bj.ptr.value, dB.ptr.value + 8 * j * N, N)
-        uj = ds.solve_dev(bj)
-        _copy_dev(c, U.ptr.value + 8 * j * N, uj.ptr.value, N)
-        c.synchronize()      # (uj is released on the next turn of the loop)
-    return U
+    return ds.solve_dev(dB)
 
 
 def _multigrid_multi(H, X0, B, maxiter, tol, exact, check_every, nPre, nPost, alpha):

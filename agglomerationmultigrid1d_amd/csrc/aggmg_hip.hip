@@ -1218,6 +1218,15 @@ extern "C" int aggmg_debug_cr_trace(aggmg_ctx* ctx, unsigned long long* out, int
 }
 #endif
 
+// AGGMG_CR_FUSE_TAIL=1 (experiment): the last forward stage's last-arriving workgroup solves the tail system
+static bool cr_fuse_tail() {
+  static const bool on = [] {
+    const char* e = std::getenv("AGGMG_CR_FUSE_TAIL");
+    return e && e[0] == '1';
+  }();
+  return on;
+}
+
 static CrStageArgs cr_make_args(const CrDev& cr, const CrStage& S, bool tail) {
   CrStageArgs A;
   std::memset(&A, 0, sizeof(A));
@@ -1248,7 +1257,7 @@ static CrStageArgs cr_make_args(const CrDev& cr, const CrStage& S, bool tail) {
 // the tail system: parallel cyclic reduction when set-up prepared it, the register-blocked reduction otherwise
 template <int M>
 static void cr_launch_tail(aggmg_ctx* ctx, CrDev& cr, const CrStageArgs& T, size_t tail_lds, const double* d, const double* db,
-                           double* x) {
+                           double* x, int kc = 1) {
   if constexpr (M <= 2) {
     if (cr.pcr.valid) {
       PcrArgs P;
@@ -1259,6 +1268,8 @@ static void cr_launch_tail(aggmg_ctx* ctx, CrDev& cr, const CrStageArgs& T, size
       P.n = cr.pcr.n;
       P.L = cr.pcr.L;
       P.dstride = T.dstride;
+      P.cs_d = T.cs_d;
+      P.cs_x = T.cs_x;
 #ifdef AGGMG_CR_TRACE
       P.trace = g_cr_trace;
 #endif
@@ -1267,14 +1278,14 @@ static void cr_launch_tail(aggmg_ctx* ctx, CrDev& cr, const CrStageArgs& T, size
       if (cr.pcr.pre) {
         P.lv0 = cr.lv[cr.tail.l0];
         P.n_full = (int)cr.tail.n_in;
-        hipLaunchKernelGGL((cr_pcr_tail_kernel<M, true>), dim3(1), dim3(threads), lds, ctx->stream, P, d, db, x);
+        hipLaunchKernelGGL((cr_pcr_tail_kernel<M, true>), dim3(1, kc), dim3(threads), lds, ctx->stream, P, d, db, x);
       } else {
-        hipLaunchKernelGGL((cr_pcr_tail_kernel<M, false>), dim3(1), dim3(threads), lds, ctx->stream, P, d, db, x);
+        hipLaunchKernelGGL((cr_pcr_tail_kernel<M, false>), dim3(1, kc), dim3(threads), lds, ctx->stream, P, d, db, x);
       }
       return;
     }
   }
-  hipLaunchKernelGGL((cr_tail_kernel<M>), dim3(1), dim3(kCrThreads), tail_lds, ctx->stream, T, d, db, x);
+  hipLaunchKernelGGL((cr_tail_kernel<M>), dim3(1, kc), dim3(kCrThreads), tail_lds, ctx->stream, T, d, db, x);
 }
 
 // Stages s0.. and the tail for the right-hand side d (+ db) of stage s0's input system into x:
@@ -1288,10 +1299,7 @@ static int cr_solve_from(aggmg_ctx* ctx, CrDev& cr, int s0, const double* d, con
   CrStageArgs T = cr_make_args(cr, cr.tail, true);
   if (s0 >= ns) T.dstride = dstride;
   const size_t tail_lds = (size_t)cr.tail.lds_total * sizeof(double);
-  static const bool fuse_tail = [] {
-    const char* e = std::getenv("AGGMG_CR_FUSE_TAIL");
-    return e && e[0] == '1';
-  }();
+  const bool fuse_tail = cr_fuse_tail();
   if (s0 >= ns) {
     cr_launch_tail<M>(ctx, cr, T, tail_lds, d, db, x);
     HIPCHK(hipGetLastError());
@@ -1412,6 +1420,164 @@ static int cr_solve(aggmg_ctx* ctx, CrDev& cr, const double* rhs, double* out, i
     case 6: return cr_solve_t<6>(ctx, cr, rhs, out);
     case 7: return cr_solve_t<7>(ctx, cr, rhs, out);
     case 8: return cr_solve_t<8>(ctx, cr, rhs, out);
+  }
+  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "cyclic reduction block size not instantiated");
+}
+
+
+// ---- the same solve for a group of kc columns in ONE launch sequence (EXTENSION: the K-column cycle's coarsest level)
+// Workgroup (chunk, col) of every launch runs what workgroup `chunk` of cr_solve_from's launch runs, on column col's
+// vectors (cr_kernels.hpp): the factors are shared, every per-solve buffer has a copy per column in h->crw.
+static int64_t cr_even(int64_t v) { return (v + 1) & ~(int64_t)1; }
+
+// doubles per column and (off) start of the stage's [cols][stride] regions in h->crw; -> doubles in all
+struct CrMultiStage {
+  int64_t part = 0, stack = 0, mid = 0;              // per column: partR | partL | xq, stack, mid
+  int64_t part_off = 0, stack_off = 0, mid_off = 0;
+};
+static int64_t cr_multi_layout(const CrDev& cr, int64_t cols, std::vector<CrMultiStage>* st, CrMultiStage* tail) {
+  int64_t o = 0;
+  st->assign(cr.st.size(), CrMultiStage());
+  auto region = [&](int64_t stride, int64_t* off) {
+    *off = o;
+    o += cols * stride;
+  };
+  for (size_t s = 0; s < cr.st.size(); ++s) {
+    const CrStage& S = cr.st[s];
+    CrMultiStage& W = (*st)[s];
+    W.part = 3 * ((S.n_out * cr.m + 31) & ~(int64_t)31);   // as set-up lays out the one-column vectors (setup_cr)
+    W.stack = S.stack ? cr_even((S.n_out + 1) * (int64_t)S.stack_stride) : 0;
+    W.mid = S.mid ? cr_even(S.mid_total) : 0;
+    region(W.part, &W.part_off);
+    region(W.stack, &W.stack_off);
+    region(W.mid, &W.mid_off);
+  }
+  *tail = CrMultiStage();
+  tail->mid = cr.tail.mid ? cr_even(cr.tail.mid_total) : 0;
+  region(tail->mid, &tail->mid_off);
+  return o;
+}
+
+// grown to the largest group asked for; a call with no more columns than before allocates nothing
+static int cr_multi_workspace(aggmg_ctx* ctx, aggmg_hier* h, int64_t cols, bool staging) {
+  const CrDev& cr = h->cr;
+  if (h->crw_cols < cols) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (h->crw) HIPCHK(hipFree(h->crw));
+    h->crw = nullptr;
+    h->crw_cols = 0;
+    std::vector<CrMultiStage> st;
+    CrMultiStage tail;
+    const size_t bytes = (size_t)std::max<int64_t>(cr_multi_layout(cr, cols, &st, &tail), 1) * sizeof(double);
+    HIPCHK(hipMalloc((void**)&h->crw, bytes));
+    HIPCHK(hipMemsetAsync(h->crw, 0, bytes, ctx->stream));   // (partL[0] of every column is never written: stays zero)
+    h->crw_cols = cols;
+  }
+  if (staging && h->crw_stage_cols < cols) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (h->crw_stage) HIPCHK(hipFree(h->crw_stage));
+    h->crw_stage = nullptr;
+    h->crw_stage_cols = 0;
+    const size_t bytes = (size_t)(2 * cols * cr_even(cr.n0 * cr.m)) * sizeof(double);
+    HIPCHK(hipMalloc((void**)&h->crw_stage, bytes));
+    HIPCHK(hipMemsetAsync(h->crw_stage, 0, bytes, ctx->stream));   // (the pad rows of d0 are never written: stay zero)
+    h->crw_stage_cols = cols;
+  }
+  return AGGMG_OK;
+}
+
+// column j of X (leading dimension ldx) = cr_solve of column j of B (ldb), bit for bit, for 2 <= kc columns
+template <int M>
+static int cr_solve_multi_t(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int64_t ldb, double* X, int64_t ldx, int kc) {
+  CrDev& cr = h->cr;
+  const int64_t Npad = cr.n0 * M;
+  // without padding the caller's columns are used in place, as cr_solve_t does -- where every column starts on the 16 bytes
+  // the kernels' paired loads and stores assume of a vector
+  const bool aligned = (((uintptr_t)B | (uintptr_t)X) & 15) == 0 && ldb % 2 == 0 && ldx % 2 == 0;
+  const bool direct = Npad == cr.N && aligned && !(B < X + ((kc - 1) * ldx + cr.N) && X < B + ((kc - 1) * ldb + cr.N));
+  CHECK(cr_multi_workspace(ctx, h, kc, !direct));
+  std::vector<CrMultiStage> ws;
+  CrMultiStage wt;
+  cr_multi_layout(cr, h->crw_cols, &ws, &wt);
+  const double* d = B;
+  double* x = X;
+  int64_t cs_in = ldb, cs_out = ldx;
+  if (!direct) {
+    const int64_t sp = cr_even(Npad);
+    double* d0 = h->crw_stage;
+    x = h->crw_stage + h->crw_stage_cols * sp;
+    hipLaunchKernelGGL(cr_cols_copy_kernel<kCrThreads>, dim3((unsigned)((cr.N + kCrThreads - 1) / kCrThreads), kc), dim3(kCrThreads), 0,
+                       ctx->stream, B, ldb, d0, sp, cr.N);
+    d = d0;
+    cs_in = cs_out = sp;
+  }
+  const int ns = (int)cr.st.size();
+  CrStageArgs T = cr_make_args(cr, cr.tail, true);
+  T.mid = wt.mid ? h->crw + wt.mid_off : nullptr;
+  T.cs_mid = wt.mid;
+  const size_t tail_lds = (size_t)cr.tail.lds_total * sizeof(double);
+  auto stage_args = [&](int s) {
+    const CrStage& S = cr.st[s];
+    const CrMultiStage& W = ws[s];
+    CrStageArgs A = cr_make_args(cr, S, false);
+    A.stack = W.stack ? h->crw + W.stack_off : nullptr;
+    A.cs_stack = W.stack;
+    A.mid = W.mid ? h->crw + W.mid_off : nullptr;
+    A.cs_mid = W.mid;
+    A.cs_d = s == 0 ? cs_in : ws[s - 1].part;
+    return A;
+  };
+  auto partR = [&](int s) { return h->crw + ws[s].part_off; };
+  auto partL = [&](int s) { return h->crw + ws[s].part_off + ws[s].part / 3; };
+  auto xq = [&](int s) { return h->crw + ws[s].part_off + 2 * (ws[s].part / 3); };
+  if (ns == 0) {
+    T.cs_d = cs_in;
+    T.cs_x = cs_out;
+    cr_launch_tail<M>(ctx, cr, T, tail_lds, d, nullptr, x, kc);
+  } else {
+    const double *din = d, *dinb = nullptr;
+    for (int s = 0; s < ns; ++s) {
+      CrStageArgs A = stage_args(s);
+      A.cs_o = ws[s].part;
+      const unsigned grid = (unsigned)std::max<int64_t>(cr.st[s].n_out, 1);
+      hipLaunchKernelGGL((cr_stage_forward_kernel<M, false>), dim3(grid, kc), dim3(cr_stage_threads()),
+                         (size_t)cr.st[s].lds_total * sizeof(double), ctx->stream, A, din, dinb, partR(s), partL(s), T,
+                         (double*)nullptr, (unsigned int*)nullptr);
+      din = partR(s);
+      dinb = partL(s);
+    }
+    T.cs_d = T.cs_x = ws[ns - 1].part;
+    cr_launch_tail<M>(ctx, cr, T, tail_lds, (const double*)partR(ns - 1), (const double*)partL(ns - 1), xq(ns - 1), kc);
+    for (int s = ns - 1; s >= 0; --s) {
+      CrStageArgs A = stage_args(s);
+#ifdef AGGMG_CR_TRACE
+      A.trace_kind = 2;
+#endif
+      A.cs_xq = ws[s].part;
+      A.cs_x = s == 0 ? cs_out : ws[s - 1].part;
+      const unsigned grid = (unsigned)std::max<int64_t>(cr.st[s].n_out, 1);
+      const double* ds = s == 0 ? d : partR(s - 1);
+      const double* dsb = s == 0 ? nullptr : partL(s - 1);
+      double* xs = s == 0 ? x : xq(s - 1);
+      hipLaunchKernelGGL((cr_stage_backward_kernel<M>), dim3(grid, kc), dim3(cr_stage_threads()),
+                         (size_t)cr.st[s].lds_total * sizeof(double), ctx->stream, A, ds, dsb, (const double*)xq(s), xs);
+    }
+  }
+  if (!direct)
+    hipLaunchKernelGGL(cr_cols_copy_kernel<kCrThreads>, dim3((unsigned)((cr.N + kCrThreads - 1) / kCrThreads), kc), dim3(kCrThreads), 0,
+                       ctx->stream, (const double*)x, cs_out, X, ldx, cr.N);
+  HIPCHK(hipGetLastError());
+  return AGGMG_OK;
+}
+
+static int cr_solve_multi(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int64_t ldb, double* X, int64_t ldx, int kc, int level) {
+  ProfScope ps(ctx, AGGMG_KIND_COARSE, level);
+  switch (h->cr.m) {
+#define CASE(MM) \
+  case MM:       \
+    return cr_solve_multi_t<MM>(ctx, h, B, ldb, X, ldx, kc);
+    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+#undef CASE
   }
   return fail(ctx, AGGMG_ERR_UNSUPPORTED, "cyclic reduction block size not instantiated");
 }
@@ -1591,6 +1757,15 @@ static int coarse_solve(aggmg_ctx* ctx, aggmg_hier* h, const double* rhs_dev, do
   HIPCHK(hipMemcpyAsync(u_dev, h->h_coarse.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   h->last_coarse_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return AGGMG_OK;
+}
+
+// the coarsest solve of a column group (at most kMultiKB columns): one launch sequence on the device factorisation;
+// column by column on the host banded LU, under AGGMG_CR_FUSE_TAIL=1 (its ticket counts the chunks of one solve) and for
+// a group of one -- the same bits either way
+static int coarse_solve_multi(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int64_t ldb, double* X, int64_t ldx, int kc) {
+  if (h->cr.valid && kc > 1 && !cr_fuse_tail()) return cr_solve_multi(ctx, h, B, ldb, X, ldx, kc, (int)h->lv.size() - 1);
+  for (int j = 0; j < kc; ++j) CHECK(coarse_solve(ctx, h, B + j * ldb, X + j * ldx));
   return AGGMG_OK;
 }
 
@@ -1914,9 +2089,10 @@ extern "C" int aggmg_vcycle_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0,
 // ---- K right-hand sides in one pass over the operators (EXTENSION: the reference's multigrid_v_cycle / ldiv! take
 // vectors, src/solvers.jl:19,63,84) ------------------------------------------------------------------------------
 // The columns go in groups of at most kMultiKB; every non-coarsest level runs ONE btd_multi_kernel launch per group
-// on the way down and one on the way up (no two-level launches here), the coarsest solve runs column by column.
-// A hierarchy with a level outside the kernel's coverage runs the single-column cycle on every column instead: the
-// same bits either way (multi_kernels.hpp), aggmg_hier_multi_info says which.
+// on the way down and one on the way up (no two-level launches here), and the coarsest solve one launch sequence per
+// group (cr_solve_multi).  A hierarchy with a level outside the kernel's coverage runs the single-column cycle on every
+// column instead (a one-level hierarchy, whose cycle is the coarsest solve alone, still in groups): the same bits either
+// way (multi_kernels.hpp), aggmg_hier_multi_info says which.
 #ifndef AGGMG_MULTI_KB
 #define AGGMG_MULTI_KB 8
 #endif
@@ -2034,9 +2210,9 @@ static int vcycle_multi_group(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, c
     ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
     CHECK(launch_multi(ctx, *l.S->btd, m, nPre + 1));
   }
-  {  // coarsest solve (:39), column by column
+  {  // coarsest solve (:39): one launch sequence for the group
     const int64_t Nc = h->lv[n - 1].N;
-    for (int j = 0; j < kc; ++j) CHECK(coarse_solve(ctx, h, h->mu[n - 1][2] + j * Nc, h->mu[n - 1][0] + j * Nc));
+    CHECK(coarse_solve_multi(ctx, h, h->mu[n - 1][2], Nc, h->mu[n - 1][0], Nc, kc));
   }
   for (int k = n - 2; k >= 0; --k) {   // ascent (:41-47)
     Level& l = h->lv[k];
@@ -2061,6 +2237,32 @@ static bool ranges_overlap(const double* a, int64_t na, const double* b, int64_t
   return a < b + nb && b < a + na;
 }
 
+// the coarsest-level system for ncols column-major columns, in the cycle's groups
+static int coarse_solve_cols(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int64_t ncols, int64_t ld, double* X) {
+  const int64_t group = std::min<int64_t>(ncols, kMultiKB);
+  h->last_coarse_ms = 0.0;
+  for (int64_t c0 = 0; c0 < ncols; c0 += group)
+    CHECK(coarse_solve_multi(ctx, h, B + c0 * ld, ld, X + c0 * ld, ld, (int)std::min<int64_t>(group, ncols - c0)));
+  return AGGMG_OK;
+}
+
+// x = A_n \ b (src/solvers.jl:39; for a one-level hierarchy the reference's `A \ B`, :120) for ncols columns
+extern "C" int aggmg_hier_coarse_solve_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int64_t ncols, int64_t ld,
+                                                 double* X) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!h || !B || !X) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_coarse_solve_multi_dev: NULL argument");
+  if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_coarse_solve_multi_dev: ncols must be >= 1");
+  const int64_t N = h->lv.back().N;
+  if (ld < N)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_coarse_solve_multi_dev: ld must be >= N (" + std::to_string(N) + ")");
+  const int64_t span = (ncols - 1) * ld + N;
+  if (ranges_overlap(X, span, B, span))
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_coarse_solve_multi_dev: X must not overlap B");
+  if (h->coarse_mode == AGGMG_COARSE_EXTERNAL)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_coarse_solve_multi_dev: hierarchy was created with AGGMG_COARSE_EXTERNAL");
+  return coarse_solve_cols(ctx, h, B, ncols, ld, X);
+}
+
 extern "C" int aggmg_vcycle_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, const double* B, int64_t ncols,
                                       int64_t ld, int nPre, int nPost, double alpha, double* X) {
   if (!ctx) return AGGMG_ERR_ARGUMENT;
@@ -2074,6 +2276,7 @@ extern "C" int aggmg_vcycle_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const doubl
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: X must not overlap X0 or B");
   if (h->coarse_mode == AGGMG_COARSE_EXTERNAL)
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: hierarchy was created with AGGMG_COARSE_EXTERNAL");
+  if (h->lv.size() == 1) return coarse_solve_cols(ctx, h, B, ncols, ld, X);   // the cycle is the coarsest solve (:39)
   if (!multi_ok(h, nPre, nPost)) {   // column by column: the single-column cycle on every column slice
     for (int64_t j = 0; j < ncols; ++j)
       CHECK(aggmg_vcycle_dev(ctx, h, X0 ? X0 + j * ld : nullptr, B + j * ld, nPre, nPost, alpha, X + j * ld));

@@ -29,6 +29,11 @@
 // odd rows of its inner sub-levels (three blocks of the nine at three levels per step): the forward
 // step stores them (`mid`) instead of the backward step reading the even rows' factors of all three
 // sub-levels again to recompute them (r03: 0.22 -> 0.14 GB per backward launch at 2^20 blocks of 2).
+//
+// K right-hand sides (EXTENSION, the K-column cycle's coarsest level): every launch takes the column from blockIdx.y.
+// Workgroup (chunk, col) runs what workgroup `chunk` runs for one column, on column col's vectors -- the factors are
+// shared, the per-solve buffers are addressed with per-column strides from the launch arguments (CrStageArgs::cs_*,
+// PcrArgs::cs_*) -- so a group of columns costs the launches of one and every column keeps its bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -81,6 +86,15 @@ struct CrStageArgs {
   int ostride;    // same for the boundary rows a forward stage writes (partR / partL); 2 M = interleaved per chunk
   const double* lu_last;
   const int32_t* perm_last;
+  // K right-hand sides in one launch: workgroup (chunk, col) = (blockIdx.x, blockIdx.y) runs what workgroup `chunk` of a
+  // one-column launch runs, on column col's vectors.  Doubles between consecutive columns of every per-solve buffer (the
+  // factors are shared); a launch of one column leaves them zero
+  int64_t cs_d;      // the step-0 input d0 / d0b
+  int64_t cs_o;      // a forward stage's boundary rows partR / partL
+  int64_t cs_xq;     // a backward stage's boundary solution xq
+  int64_t cs_x;      // the output x0
+  int64_t cs_mid;    // mid
+  int64_t cs_stack;  // stack
 #ifdef AGGMG_CR_TRACE
   unsigned long long* trace;  // [3 kinds][kCrTraceWgs][16] constant-clock stamps (tools/cr_trace.py; never in the product build)
   int trace_kind;
@@ -121,6 +135,10 @@ __device__ __forceinline__ unsigned long long* cr_trace_slots() {
 #endif
 
 __device__ __forceinline__ int64_t cr_level_n(const CrStageArgs& A, int l) { return l < A.q ? A.lv[l].n : A.n_out; }
+
+// `mid` of the workgroup's column (the launch arguments are read where they are used, never copied and patched: a
+// modified copy of the argument block would live in scratch)
+__device__ __forceinline__ double* cr_col_mid(const CrStageArgs& A) { return A.mid + (int64_t)blockIdx.y * A.cs_mid; }
 
 // register-resident sub-chunk: sub-level i holds 2^(QS-i) + 1 blocks, stacked
 template <int QS, int I>
@@ -612,7 +630,7 @@ __device__ __forceinline__ void cr_step_forward(const CrStageArgs& A, int s, int
       cr_loc_load<M, QS>(A, s, g, b, d0, d0b, sh, v, thi, tshared, wg_shared && s > 0 && i == g.nb - 1);
       cr_loc_fwd<M, QS, 0>(&A.lv[g.a], b, v);
     }
-    if constexpr (QS >= 2) cr_mid_move<M, QS, 1, true>(A.mid + A.mid_off[s] + b * (cr_mid_blocks<QS>() * M), v);
+    if constexpr (QS >= 2) cr_mid_move<M, QS, 1, true>(cr_col_mid(A) + A.mid_off[s] + b * (cr_mid_blocks<QS>() * M), v);
     const double* top = v + CrOff<QS, QS>::blocks * M;
 #ifdef AGGMG_CR_TRACE
     if (s == 0 && i == (int)threadIdx.x) {
@@ -653,7 +671,7 @@ __device__ __forceinline__ void cr_step_backward(const CrStageArgs& A, int s, in
       cr_pre_load_b<M, QS, 0>(&A.lv[g.a], b, F);
       __builtin_amdgcn_sched_barrier(0);
       cr_loc_load<M, QS>(A, s, g, b, d0, d0b, sh, v, thi, tshared, wg_shared && s > 0 && i == g.nb - 1);
-      if constexpr (QS >= 2) cr_mid_move<M, QS, 1, false>(A.mid + A.mid_off[s] + b * (cr_mid_blocks<QS>() * M), v);
+      if constexpr (QS >= 2) cr_mid_move<M, QS, 1, false>(cr_col_mid(A) + A.mid_off[s] + b * (cr_mid_blocks<QS>() * M), v);
 #pragma unroll
       for (int e = 0; e < M; ++e) {
         top[e] = xtop[(b - xtop_lo) * M + e];
@@ -663,7 +681,7 @@ __device__ __forceinline__ void cr_step_backward(const CrStageArgs& A, int s, in
       cr_loc_bwd_pre<M, QS, QS - 1>(&A.lv[g.a], F, b, v);
     } else {
       cr_loc_load<M, QS>(A, s, g, b, d0, d0b, sh, v, thi, tshared, wg_shared && s > 0 && i == g.nb - 1);
-      if constexpr (QS >= 2) cr_mid_move<M, QS, 1, false>(A.mid + A.mid_off[s] + b * (cr_mid_blocks<QS>() * M), v);
+      if constexpr (QS >= 2) cr_mid_move<M, QS, 1, false>(cr_col_mid(A) + A.mid_off[s] + b * (cr_mid_blocks<QS>() * M), v);
 #pragma unroll
       for (int e = 0; e < M; ++e) {
         top[e] = xtop[(b - xtop_lo) * M + e];
@@ -783,6 +801,10 @@ __global__ __launch_bounds__(kCrThreads) CR_WAVES_ATTR void cr_tail_kernel(CrSta
                                                              const double* __restrict__ d0b,
                                                              double* __restrict__ x0) {
   extern __shared__ double sh[];
+  const int64_t col = blockIdx.y;
+  d0 += col * T.cs_d;
+  if (d0b) d0b += col * T.cs_d;
+  x0 += col * T.cs_x;
   cr_tail_body<M>(T, d0, d0b, x0, sh);
 }
 
@@ -798,6 +820,11 @@ __global__ __launch_bounds__(kCrThreads) CR_WAVES_ATTR void cr_stage_forward_ker
   extern __shared__ double sh[];
   __shared__ unsigned int s_ticket;
   const int64_t c = A.c0 + blockIdx.x;
+  const int64_t col = blockIdx.y;  // (FUSE_TAIL launches hold one column: the ticket counts the chunks of one solve)
+  d0 += col * A.cs_d;
+  if (d0b) d0b += col * A.cs_d;
+  partR += col * A.cs_o;
+  partL += col * A.cs_o;
   const bool wg_shared = ((c + 1) << A.q) <= A.lv[0].n - 1;
   CR_TRACE_BEGIN();
   CR_STAMP(A, 0);
@@ -816,7 +843,7 @@ __global__ __launch_bounds__(kCrThreads) CR_WAVES_ATTR void cr_stage_forward_ker
   // the summed inputs of the later steps are kept for the back substitution (a few hundred values
   // per chunk) instead of recomputing every step there
   if (A.stack) {
-    double* st = A.stack + c * (int64_t)A.stack_stride;
+    double* st = A.stack + col * A.cs_stack + c * (int64_t)A.stack_stride;
     int o = 0;
     for (int s = 1; s < A.nsteps; ++s) {
       const int cnt = ((1 << (A.q - A.step_a[s])) + 1) * M;
@@ -846,6 +873,11 @@ __global__ __launch_bounds__(kCrThreads) CR_WAVES_ATTR void cr_stage_backward_ke
                                                                        double* __restrict__ x0) {
   extern __shared__ double sh[];
   const int64_t c = A.c0 + blockIdx.x;
+  const int64_t col = blockIdx.y;
+  d0 += col * A.cs_d;
+  if (d0b) d0b += col * A.cs_d;
+  xq += col * A.cs_xq;
+  x0 += col * A.cs_x;
   const bool wg_shared = ((c + 1) << A.q) <= A.lv[0].n - 1;
   CR_TRACE_BEGIN();
   CR_STAMP(A, 0);
@@ -854,7 +886,7 @@ __global__ __launch_bounds__(kCrThreads) CR_WAVES_ATTR void cr_stage_backward_ke
   CR_STAMP(A, 1);
   if (A.nsteps > 1) {
     if (A.stack) {
-      const double* st = A.stack + c * (int64_t)A.stack_stride;
+      const double* st = A.stack + col * A.cs_stack + c * (int64_t)A.stack_stride;
       int o = 0;
       for (int s = 1; s < A.nsteps; ++s) {
         const int cnt = ((1 << (A.q - A.step_a[s])) + 1) * M;
@@ -889,6 +921,7 @@ struct PcrArgs {
   const int32_t* perm;  // [n][M]
   int n, L;
   int dstride;          // doubles between consecutive blocks of d0 / d0b (0: M)
+  int64_t cs_d, cs_x;   // doubles between consecutive columns (blockIdx.y) of d0 / d0b and of x0; one column: zero
   // PRE: one level of ordinary cyclic reduction around the parallel part (513 .. 1024 rows): thread t takes even row 2t through
   // the parallel levels and solves odd row 2t + 1 from its two even neighbours afterwards -- the level's own factors
   CrLevel lv0;
@@ -906,6 +939,9 @@ __global__ __launch_bounds__(512) void cr_pcr_tail_kernel(PcrArgs P, const doubl
   extern __shared__ double sh[];
   constexpr int W = 2 * M * M, D = kPcrMaxLevels;
   const int i = threadIdx.x, n = P.n;
+  d0 += (int64_t)blockIdx.y * P.cs_d;
+  if (d0b) d0b += (int64_t)blockIdx.y * P.cs_d;
+  x0 += (int64_t)blockIdx.y * P.cs_x;
   const bool act = i < n;
   const int ic = act ? i : n - 1;
 #ifdef AGGMG_CR_TRACE
@@ -1064,6 +1100,15 @@ __global__ __launch_bounds__(512) void cr_pcr_tail_kernel(PcrArgs P, const doubl
     P.trace[(1 * kCrTraceWgs + 0) * 16 + 15] = wall_clock64();
   }
 #endif
+}
+
+// columns of a column-major matrix into another leading dimension (the padded staging vectors of a column group):
+// grid (ceil(n / NT), columns)
+template <int NT>
+__global__ __launch_bounds__(NT) void cr_cols_copy_kernel(const double* __restrict__ src, int64_t ld_src,
+                                                          double* __restrict__ dst, int64_t ld_dst, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
+  if (i < n) dst[(int64_t)blockIdx.y * ld_dst + i] = src[(int64_t)blockIdx.y * ld_src + i];
 }
 
 }  // namespace aggmg

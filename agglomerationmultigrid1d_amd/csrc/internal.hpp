@@ -293,6 +293,13 @@ struct aggmg_hier {
   // side (mu[k][2], levels >= 1); the coarsest level's solution goes to mu[n-1][0]
   std::vector<std::array<double*, 3>> mu;
   int64_t multi_cols = 0;
+  // the coarsest solve of a column group in one launch sequence (cr_solve_multi; lazy, grown like mu): per column of the
+  // group what a CrStage holds for one (partR / partL / xq, stack, mid of every stage, the tail's mid) in ONE zeroed
+  // allocation, and -- only when a call needs them -- the padded staging vectors d0 / x0 of every column in another
+  double* crw = nullptr;
+  int64_t crw_cols = 0;
+  double* crw_stage = nullptr;
+  int64_t crw_stage_cols = 0;
   int restriction = 0;  // AGGMG_RESTRICT_EXPLICIT (default) / AGGMG_RESTRICT_PRECONDITIONED
   std::vector<double> h_coarse;
   double last_coarse_ms = 0.0;
@@ -311,6 +318,8 @@ struct aggmg_hier {
     for (auto& m : mu)
       for (double* p : m)
         if (p) (void)hipFree(p);
+    for (double* p : {crw, crw_stage})
+      if (p) (void)hipFree(p);
   }
 };
 

@@ -274,7 +274,8 @@ int aggmg_vcycle_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const doub
  * X0, B, X: device, column-major N x ncols, leading dimension ld >= N; X0 == NULL: zero initial guesses (ldiv!).
  * Column j of X is bit for bit what aggmg_vcycle_dev gives for column j of X0 and B.  X must not overlap X0 or B.
  * The columns go in groups (aggmg_hier_multi_info); each non-coarsest level runs one launch per group each way and
- * reads its operator once for the whole group, the coarsest solve runs column by column.  A hierarchy with a level
+ * reads its operator once for the whole group, the coarsest solve runs one launch sequence per group (column by column
+ * on the host banded LU and under AGGMG_CR_FUSE_TAIL=1).  A hierarchy with a level
  * the K-column kernel does not cover (CG chain or generic levels, Gauss-Seidel sweeps, agglomerates of different sizes,
  * the preconditioned restriction, block sizes other than 2 / 4 (compressed) and 2 (dense), transfers with other than
  * two coarse modes, sweep counts beyond the tiles' halo) runs aggmg_vcycle_dev column by column instead.  Per-level
@@ -283,6 +284,17 @@ int aggmg_vcycle_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const doub
  * sweep counts, a hierarchy created with AGGMG_COARSE_EXTERNAL. */
 int aggmg_vcycle_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, const double* B, int64_t ncols, int64_t ld,
                            int nPre, int nPost, double alpha, double* X);
+/* X = A_n \ B, the coarsest-level direct solve (src/solvers.jl:39) on ncols right-hand sides (EXTENSION: the reference
+ * solves vectors); for a one-level hierarchy that is the fine-level `A \ B` behind the err histories (src/solvers.jl:39,120).
+ * B, X: device, column-major N_n x ncols (N_n rows of the coarsest operator), leading dimension ld >= N_n.  The
+ * columns go in the cycle's groups (aggmg_hier_multi_info); on the device factorisation (block cyclic reduction) a
+ * group shares every launch -- forward stages, tail, backward stages, with a grid dimension for the column -- and
+ * column j of X is bit for bit the single-column solve of column j (aggmg_vcycle_dev on a one-level hierarchy); on the
+ * host banded LU the columns are solved one by one.  Per-column work space for one group is allocated on the hierarchy
+ * on first use (grown for a larger group, freed with it).  Asynchronous on the context stream (the host banded LU
+ * synchronises, as in aggmg_vcycle_dev).  AGGMG_ERR_ARGUMENT: NULL, ncols < 1, ld < N_n, X overlapping B, a hierarchy
+ * created with AGGMG_COARSE_EXTERNAL. */
+int aggmg_hier_coarse_solve_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int64_t ncols, int64_t ld, double* X);
 /* fused = 1 when the cycle runs K-column launches, 0 when it runs column by column; group = columns per launch */
 int aggmg_hier_multi_info(aggmg_ctx* ctx, const aggmg_hier* h, int64_t ncols, int nPre, int nPost, int* fused, int* group);
 /* R = B - A X on K columns (EXTENSION: the reference forms residuals of vectors, src/solvers.jl:33,127).  X, B, R:

@@ -561,18 +561,21 @@ function multigrid(Hd::DeviceHierarchy, x0::Union{AbstractVector,DeviceVector}, 
 end
 
 # ---- the solvers on K right-hand sides (EXTENSION: the reference's take vectors, src/solvers.jl:116-139) ----
-# U[:, j] = A \\ B[:, j] on the device, column by column through the hierarchy's DirectSolver (host fallback: `\\` on
-# the downloaded matrix)
+# U = A \\ B on the device (the reference's `\\` takes matrices too, src/solvers.jl:39,120): the columns share every launch
+# of the device factorisation, a group at a time (aggmg_hier_coarse_solve_multi_dev); column j is bit for bit `solve` on
+# column j (host fallback: `\\` on the downloaded matrix)
 function solve(ds::DirectSolver, A_host, B::DeviceMatrix)
     ds.h == C_NULL && return DeviceMatrix(ds.ctx, A_host \\ download(B))
-    U = DeviceMatrix(ds.ctx, B.n, B.k); z = DeviceVector(ds.ctx, B.n)     # z: zero guess (aggmg_dev_alloc zeroes)
-    for j in 0:B.k-1
-        off = 8 * j * B.n
-        GC.@preserve z B U check(ds.ctx.h, ccall((:aggmg_vcycle_dev, LIB), Cint,
-            (Handle, Handle, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Float64, Ptr{Cvoid}),
-            ds.ctx.h, ds.h, z.p, B.p + off, 0, 0, 1.0, U.p + off))
-    end
+    U = DeviceMatrix(ds.ctx, B.n, B.k)
+    GC.@preserve B U check(ds.ctx.h, ccall((:aggmg_hier_coarse_solve_multi_dev, LIB), Cint,
+        (Handle, Handle, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}),
+        ds.ctx.h, ds.h, B.p, B.k, B.n, U.p))
     return U
+end
+# ds \\ B: the same on a solver that runs on the device (the host fallback needs the host matrix: solve(ds, A_host, B))
+function Base.:\\(ds::DirectSolver, B::DeviceMatrix)
+    ds.h == C_NULL && throw(ArgumentError("DirectSolver: this operator is solved on the host, use solve(ds, A_host, B)"))
+    return solve(ds, nothing, B)
 end
 
 # multigrid on device matrices -> X::DeviceMatrix, cycles::Vector{Int}, res, err (one Vector per column): column j's
