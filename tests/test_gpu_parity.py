@@ -175,7 +175,9 @@ def test_banded_generic_point_jacobi_many_sweeps_per_launch(oracle, mg, n, p):
     banded, so csr_band_kernel keeps the x window of a row block in LDS and runs several sweeps per launch (the operator's own limit, 1 + 32 / bw, at most 8)
     (temporal blocking with halo rows) -- 1 .. 9 sweeps (one launch, several launches, uneven splits; several row
     blocks with halos at n = 700 .. 2000; tiny systems whose halo is the whole matrix), in place and out of place,
-    against the oracle's sweeps; the residual and y = A x take the window kernel too"""
+    against the oracle's sweeps.  Single passes stay on csr_stream_kernel (launch_csr): one sweep per call, the explicit
+    residual at the end -- only launches of two or more sweeps, and the V-cycle's sweeps-plus-residual, take the window
+    kernel"""
     o = oracle
     mesh = o.create_uniform_mesh(n, 0.0, 1.0)
     bd = o.set_boundary(mesh, 0.0, 1.0, [('neu', 0.0), ('dir', 1.0)])
