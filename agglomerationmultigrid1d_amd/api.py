@@ -327,13 +327,23 @@ class DeviceOperator:
         colptr = np.ascontiguousarray(colptr, dtype=np.int64)
         rowval = np.ascontiguousarray(rowval, dtype=np.int64)
         nzval = _f64(nzval)
+        # the C ABI takes pointers: it reads colptr[n] and then colptr[n] - base entries of rowval and nzval whatever
+        # the arrays hold, so what only the array lengths can tell is checked here
+        if int(m) < 0 or int(n) < 0:
+            raise ArgumentError("DeviceOperator: negative dimension")
+        if colptr.ndim != 1 or colptr.size != int(n) + 1:
+            raise ArgumentError(f"DeviceOperator: colptr must hold n + 1 = {int(n) + 1} entries, not {colptr.size}")
+        nnz = int(colptr[int(n)]) - (1 if one_based else 0)
+        if nnz < 0 or nnz > min(rowval.size, nzval.size):
+            raise ArgumentError(f"DeviceOperator: colptr ends at {nnz} entries, rowval and nzval hold "
+                                f"{rowval.size} and {nzval.size}")
         h = ctypes.c_void_p()
         self.ctx.check(self.ctx.lib.aggmg_csc_upload(
             self.ctx.handle, int(m), int(n), colptr.ctypes.data_as(_PI64), rowval.ctypes.data_as(_PI64),
             _pd(nzval), one_based, int(kind), ctypes.byref(h)))
         self.handle = h
         self.shape = (int(m), int(n))
-        self.nnz = int(nzval.size)
+        self.nnz = nnz        # (a SparseMatrixCSC may carry rowval / nzval longer than its colptr uses)
         self.kind = kind
 
     @classmethod

@@ -96,6 +96,7 @@ int setup_csc_upload(aggmg_ctx* ctx, int64_t m, int64_t n, const int64_t* colptr
   int h[4];
   CHECK(f.read(ctx, h));  // the row pass below walks colptr: it must be sane first
   if (h[0]) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_csc_upload: colptr not monotone");
+  if (h[3]) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_csc_upload: colptr does not start at the index base");
   LAUNCH(csc_convert_rows_kernel, n, n, m, (const int32_t*)out->rowptr, rv64.as<int64_t>(), base, out->colind, f.d);
   CHECK(f.read(ctx, h));
   if (h[1]) return fail(ctx, AGGMG_ERR_DIMENSION, "aggmg_csc_upload: row index out of range");

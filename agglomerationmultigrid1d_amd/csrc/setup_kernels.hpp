@@ -19,7 +19,9 @@ constexpr int kSetupThreads = 256;
 // ------------------------------------------------------------------------------------------
 // upload: Julia CSC (Int64, 0- or 1-based) -> int32, validated
 // ------------------------------------------------------------------------------------------
-// err[0]: colptr not monotone / out of range, err[1]: row index out of range, err[2]: rows not strictly ascending
+// err[0]: colptr not monotone / out of range, err[1]: row index out of range, err[2]: rows not strictly ascending,
+// err[3]: colptr[0] is not the index base (the entries in front of it would never be converted, yet the
+// transposition and everything else that walks all nnz entries would read them)
 __global__ __launch_bounds__(kSetupThreads) void csc_convert_colptr_kernel(int64_t n, const int64_t* __restrict__ colptr64,
                                                                            int64_t base, int64_t nnz,
                                                                            int32_t* __restrict__ colptr,
@@ -28,6 +30,7 @@ __global__ __launch_bounds__(kSetupThreads) void csc_convert_colptr_kernel(int64
   if (j > n) return;
   const int64_t v = colptr64[j] - base;
   if (v < 0 || v > nnz || (j > 0 && v < colptr64[j - 1] - base)) err[0] = 1;
+  if (j == 0 && v != 0) err[3] = 1;
   colptr[j] = (int32_t)v;
 }
 

@@ -120,7 +120,10 @@ int aggmg_host_free(aggmg_ctx* ctx, void* ptr);
 /* Upload a SparseMatrixCSC (m x n).  The device keeps a row-gather form (CSR, int32 indices)
  * and, for transfers, the transposed orientation too (the CSC arrays as given are the CSR of
  * L').  Index maps are preserved exactly: entry order inside a row/column is ascending, explicit
- * zeros stay stored.  Rejects dimensions or nnz >= 2^31 (AGGMG_ERR_ARGUMENT). */
+ * zeros stay stored.  Rejects dimensions or nnz >= 2^31 (AGGMG_ERR_ARGUMENT).  The arrays are validated on the
+ * device: a colptr that does not start at the index base, decreases or leaves 0 .. nnz, and row indices not strictly
+ * ascending inside a column are AGGMG_ERR_ARGUMENT, a row index outside 0 .. m - 1 is AGGMG_ERR_DIMENSION.  nnz is
+ * colptr[n] - base: rowval and nzval must hold that many entries (only the caller knows their lengths). */
 int aggmg_csc_upload(aggmg_ctx* ctx, int64_t m, int64_t n, const int64_t* colptr,
                      const int64_t* rowval, const double* nzval, int one_based, int kind,
                      aggmg_op** out);

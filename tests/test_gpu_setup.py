@@ -8,12 +8,15 @@ compared here with the CPU oracle at small n --
     bit-exact (all m rows of every touched block, zeros included), values to round-off;
   * sparse * sparse, sparse - sparse, transpose; the recurrences of the DG-fine constructor
     (src/mesh_heirarchy.jl:79-84,98-103,140-181) run on the device, level by level against the oracle's
-    MeshHierarchy."""
+    MeshHierarchy.
+The same kernels on unstructured patterns and pivoting blocks, bit for bit: tests/test_gpu_setup_unstructured.py."""
 import math
 
 import numpy as np
 import pytest
 import scipy.sparse as sp
+
+from lu_reference import getf2_inverse
 
 pytestmark = pytest.mark.gpu
 
@@ -43,47 +46,6 @@ def same_maps(A, B, drop_zeros=False):
             M.eliminate_zeros()
     A.sort_indices(), B.sort_indices()
     return A.shape == B.shape and np.array_equal(A.indptr, B.indptr) and np.array_equal(A.indices, B.indices)
-
-
-def getf2_inverse(a):
-    """partial-pivot LU in LAPACK getf2 order, then the inverse column by column (the operation sequence of
-    lu_invert in csrc/setup_kernels.hpp), plain Python floats"""
-    m = a.shape[0]
-    a = a.copy()
-    piv = [0] * m
-    for k in range(m):
-        p = k + int(np.argmax(np.abs(a[k:, k])))
-        piv[k] = p
-        if a[p, k] == 0.0:
-            raise ZeroDivisionError
-        if p != k:
-            a[[k, p], :] = a[[p, k], :]
-        rp = 1.0 / a[k, k]
-        for i in range(k + 1, m):
-            a[i, k] *= rp
-        for i in range(k + 1, m):
-            l = a[i, k]
-            for j in range(k + 1, m):
-                a[i, j] -= l * a[k, j]
-    inv = np.zeros((m, m))
-    for c in range(m):
-        x = np.zeros(m)
-        x[c] = 1.0
-        for k in range(m):
-            if piv[k] != k:
-                x[k], x[piv[k]] = x[piv[k]], x[k]
-        for i in range(1, m):
-            s = x[i]
-            for j in range(i):
-                s -= a[i, j] * x[j]
-            x[i] = s
-        for i in range(m - 1, -1, -1):
-            s = x[i]
-            for j in range(i + 1, m):
-                s -= a[i, j] * x[j]
-            x[i] = s / a[i, i]
-        inv[:, c] = x
-    return inv
 
 
 @pytest.mark.parametrize("p", [0, 1, 2, 3, 4, 7, 8])
