@@ -20,6 +20,7 @@ OPT_DETECT_CHAIN = 3
 OPT_PAIR_LEVELS = 4
 OPT_MG_CHECKPOINT = 5
 OPT_SYMMETRIC_RESIDUAL = 6
+OPT_OPERATOR_DICTIONARY = 7
 PROFILE_NTAGS = 256
 KIND_FUSED_DOWN, KIND_FUSED_UP, KIND_SMOOTH, KIND_RESIDUAL, KIND_RESTRICT, KIND_PROLONG, \
     KIND_JACOBI, KIND_BLOCK_APPLY, KIND_COARSE, KIND_FUSED_MID = range(10)
@@ -145,6 +146,7 @@ SYMBOLS = {
     "aggmg_hier_level_paired": (c_int, [_P, _P, c_int, c_int, POINTER(c_int)]),
     "aggmg_hier_level_paired_up": (c_int, [_P, _P, c_int, c_int, POINTER(c_int)]),
     "aggmg_hier_level_sym_residual": (c_int, [_P, _P, c_int, POINTER(c_int)]),
+    "aggmg_hier_level_dictionary": (c_int, [_P, _P, c_int, POINTER(c_int)]),
     "aggmg_hier_launch_bytes": (c_int, [_P, _P, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "aggmg_hier_multi_launch_bytes": (c_int, [_P, _P, c_int, c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_int64)]),
     "aggmg_smoother_launch_bytes": (c_int, [_P, _P, _P, c_int, POINTER(c_int64), POINTER(c_int64)]),

@@ -932,6 +932,18 @@ class MeshHierarchy:
                 out.append(k)
         return out
 
+    def dictionary_levels(self):
+        """{level: distinct operator records} of the levels whose cycle launches index the operator through a
+        dictionary of its distinct per-element records (C ABI aggmg_hier_level_dictionary,
+        AGGMG_OPT_OPERATOR_DICTIONARY)"""
+        out = {}
+        for k in range(self.nlevels):
+            v = ctypes.c_int(0)
+            self.ctx.check(self.ctx.lib.aggmg_hier_level_dictionary(self.ctx.handle, self.handle, k, ctypes.byref(v)))
+            if v.value:
+                out[k] = v.value
+        return out
+
     def paired_levels(self, nsweeps=3, direction="down"):
         """levels k whose launch also carries level k + 1 (C ABI aggmg_hier_level_paired / _paired_up), as the descent
         walks the hierarchy (pairs taken from the fine side) or, direction='up', as the ascent does (from the coarse

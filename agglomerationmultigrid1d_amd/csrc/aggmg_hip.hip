@@ -167,6 +167,9 @@ extern "C" int aggmg_set_option(aggmg_ctx* ctx, int option, int value) {
     case AGGMG_OPT_SYMMETRIC_RESIDUAL:
       ctx->sym_residual = value != 0;
       return AGGMG_OK;
+    case AGGMG_OPT_OPERATOR_DICTIONARY:
+      ctx->op_dict = value != 0;
+      return AGGMG_OK;
   }
   return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_set_option: unknown option");
 }
@@ -610,6 +613,21 @@ static int launch_btd_t(aggmg_ctx* ctx, FusedArgs a, int halo, const TileSel& se
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a);
   };
+  if constexpr (kGrp && CMP && M <= 4) {
+    // the operator dictionary (fused_dictionary put its arrays in place of the full ones): block-Jacobi launches
+    if (sym && a.lv.cls) {
+      if (a.gs || chk) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: dictionary launch of a Gauss-Seidel / checkpoint variant");
+      // the variant indexes the transfer's rows by class only on its two-mode, equal-agglomerate paths
+      if (a.par_in || a.par_out || a.ld_out || (a.lf_in && a.mc_in != 2) || (a.lf_out && a.mc_out != 2))
+        return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: dictionary launch with a transfer the variant does not index by class");
+      if (sres)
+        go(btd_fused_kernel<M, CMP, T::NS, true, T::NT, false, false, true, true>);
+      else
+        go(btd_fused_kernel<M, CMP, T::NS, true, T::NT, false, false, false, true>);
+      HIPCHK(hipGetLastError());
+      return AGGMG_OK;
+    }
+  }
   if constexpr (kGrp) {
     if (sym) {
       if (a.gs)
@@ -717,6 +735,25 @@ static void fused_descent(FusedArgs& a, const aggmg_hier* h, const Level& l, dou
     a.lf_out = l.tb->lf;
   a.rc_out = rc;
   xfer_out(a, *l.tb);
+}
+// The level's operator dictionary in place of its full arrays (after fused_ascent / fused_descent): the default-mode
+// block-Jacobi launches of a cycle -- no checkpoint, no (L'D) restriction -- on a level that has one.  The variant reads
+// the same bits from the dictionary (btd_fused_kernel<..., DICT = true>).
+static void fused_dictionary(FusedArgs& a, const Level& l) {
+  const DictDev* d = l.dict.get();
+  if (!d || a.gs || a.chk_part || a.ld_out || a.par_in || a.par_out || !a.lv.bsym) return;
+  if ((a.lf_in && a.mc_in != 2) || (a.lf_out && a.mc_out != 2)) return;
+  a.lv.bsym = d->bsym;
+  a.lv.qrow = d->qrow;
+  a.lv.qmir = d->qmir;
+  a.lv.dup = d->dup;
+  a.lv.corr = d->corr;
+  a.lv.scol = d->scol;
+  a.lv.dblk = d->dblk;
+  a.lv.cls = d->cls;
+  // (lf_in / lf_out also say that there is a prolongation / a restriction: never null then)
+  if (a.lf_in) (d->lf_unit ? a.lf1_in : a.lf_in) = d->lf;
+  if (a.lf_out) (d->lf_unit ? a.lf1_out : a.lf_out) = d->lf;
 }
 // Which restriction modes a fused descent serves, caller by caller.  vcycle_down takes any: without (L'D) it restricts
 // with lf whatever the mode.  The launch between two cycles (aggmg_vcycles_dev) wants the mode's own form to exist;
@@ -1643,6 +1680,8 @@ extern "C" int aggmg_hier_create(aggmg_ctx* ctx, int nlevels, aggmg_op* const* s
     // every fine row's stored columns must lie in the mc modes of coarse element (fine element) / rho
     CHECK(setup_transfer_btd(ctx, l.L, l.S->btd.get(), l.S->btd->m, l.S->btd->ne, hint, tb.get(), &ok));
     if (ok) l.tb = std::move(tb);
+    // the level's distinct operator records, where they are few (AGGMG_OPT_OPERATOR_DICTIONARY)
+    if (l.tb && ctx->op_dict) CHECK(setup_op_dictionary(ctx, *l.S->btd, *l.tb, &l.dict));
   }
   // CG chain levels: structured transfer to the next level; a level is fused when it has both
   for (int k = 0; k + 1 < nlevels; ++k) {
@@ -1910,6 +1949,14 @@ extern "C" int aggmg_hier_level_sym_residual(aggmg_ctx* ctx, const aggmg_hier* h
   return AGGMG_OK;
 }
 
+extern "C" int aggmg_hier_level_dictionary(aggmg_ctx* ctx, const aggmg_hier* h, int level, int* nclasses) {
+  if (!ctx || !h || !nclasses) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_dictionary: NULL argument");
+  if (level < 0 || level >= (int)h->lv.size()) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_dictionary: level out of range");
+  const Level& l = h->lv[level];
+  *nclasses = l.dict ? l.dict->nclasses : 0;
+  return AGGMG_OK;
+}
+
 // ---- descend (src/solvers.jl:28-37): leaves u[k] in lv[k].u[0] and rhs[n] in lv[n-1].rhs ----------
 static int vcycle_down(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const double* b, int nPre, double alpha,
                        int k_first = 0) {
@@ -1933,6 +1980,7 @@ static int vcycle_down(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const do
       // (Gauss-Seidel pre-smoothing: even elements, then odd ones)
       FusedArgs a = fused_sweeps(*l.S->btd, uin, rhs, l.u[0], alpha, nPre, l.S->gs ? 1 : 0);
       fused_descent(a, h, l, c.rhs);
+      fused_dictionary(a, l);
       ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
       CHECK(launch_btd(ctx, *l.S->btd, a, nPre + 1));
     } else {
@@ -2024,6 +2072,7 @@ static int vcycle_up(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, 
       // (Gauss-Seidel post-smoothing in the reverse colour order: the cycle stays symmetric)
       FusedArgs a = fused_sweeps(*l.S->btd, l.u[0], rhs, dst, alpha, nPost, l.S->gs ? 2 : 0);
       fused_ascent(a, l, uc);
+      if (sel.mode == 0) fused_dictionary(a, l);   // (the partitioned cycle's tile selections keep the full arrays)
       ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
       CHECK(launch_btd(ctx, *l.S->btd, a, std::max(nPost, 0), k == 0 ? sel : TileSel()));
     } else {
@@ -2352,6 +2401,7 @@ struct FineLevel {
     fused_ascent(a, l0(), uc());
     fused_descent(a, h, l0(), h->lv[1].rhs);
     if (chk) fused_chk(a, *chk);
+    fused_dictionary(a, l0());
     ProfScope ps(ctx, AGGMG_KIND_FUSED_MID, 0);
     return launch_btd(ctx, B0, a, nPost + nPre + 1, TileSel(), chk);
   }
@@ -2362,6 +2412,7 @@ struct FineLevel {
     FusedArgs a = fused_sweeps(B0, src, b, dst, alpha, nPost);
     fused_ascent(a, l0(), uc());
     if (chk) fused_chk(a, *chk);
+    fused_dictionary(a, l0());
     ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, 0);
     // (a checkpoint here forms residual rows of the FINAL iterate: one more element of halo, as a residual)
     return launch_btd(ctx, B0, a, nPost + (chk ? 1 : 0), TileSel(), chk);

@@ -45,6 +45,7 @@ struct aggmg_ctx {
   bool mg_checkpoint = [] { const char* e = std::getenv("AGGMG_MG_CHECKPOINT"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_MG_CHECKPOINT
   bool pair_levels = [] { const char* e = std::getenv("AGGMG_PAIR"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_PAIR_LEVELS
   bool sym_residual = [] { const char* e = std::getenv("AGGMG_SYM_RESIDUAL"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_SYMMETRIC_RESIDUAL
+  bool op_dict = [] { const char* e = std::getenv("AGGMG_OP_DICT"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_OPERATOR_DICTIONARY
   int profiling = 0;  // 0 off, 1 every launch, 2 only the fine-level fused-down launch (dominant kernel)
   std::vector<ProfEvent> prof;
   std::vector<hipEvent_t> ev_pool;
@@ -207,6 +208,24 @@ struct TransferBtd {
   }
 };
 
+// operator dictionary of a fused level (AGGMG_OPT_OPERATOR_DICTIONARY; BtdLevel::cls in kernels.hpp, the dict_* kernels of
+// setup_kernels.hpp): one copy of every distinct per-element operator record -- the level's BtdDev arrays and its
+// transfer's rows, [nclasses][...] in the layouts of the full arrays -- and the class of every element.  Belongs to the
+// hierarchy's level: the record spans the smoother's form and the transfer.  The full arrays stay; every other kernel
+// reads them.
+struct DictDev {
+  int nclasses = 0;
+  uint16_t* cls = nullptr;   // [ne]
+  double *bsym = nullptr, *qrow = nullptr, *qmir = nullptr, *dup = nullptr, *scol = nullptr, *dblk = nullptr;
+  uint32_t* corr = nullptr;
+  double* lf = nullptr;      // [nclasses][m] second entries (the transfer has lf1), else [nclasses][m][2] rows of L
+  bool lf_unit = false;      // lf holds the lf1 form
+  ~DictDev() {
+    for (void* p : {(void*)cls, (void*)bsym, (void*)qrow, (void*)qmir, (void*)dup, (void*)scol, (void*)dblk, (void*)corr, (void*)lf})
+      if (p) (void)hipFree(p);
+  }
+};
+
 // structured transfer of a CG chain level (CgtXfer in cgt_kernels.hpp)
 struct TransferCgt {
   int type = 0, mc = 0, rho = 1;
@@ -227,6 +246,7 @@ struct Level {
   double *u[2] = {nullptr, nullptr}, *rhs = nullptr, *tmp = nullptr;
   std::unique_ptr<TransferBtd> tb;  // structured transfer to level k+1, or null
   std::unique_ptr<TransferCgt> tc;  // CG chain level: structured transfer to level k+1, or null
+  std::unique_ptr<DictDev> dict;    // operator dictionary of the level's fused launches, or null
   bool cgt_fused = false;           // the level runs cgt_fused_kernel (chain form + structured transfer)
   bool native_io = false;           // rhs and u[1] are kept in block order (the finer level is a fused chain level)
   int64_t Nalloc = 0;               // length of the level's vectors (ne * m for chain levels)
@@ -463,6 +483,9 @@ int setup_invert_blocks(aggmg_ctx* ctx, int64_t nb, int m, const double* blocks_
 int setup_block_smoother(aggmg_ctx* ctx, aggmg_smoother* sm, const int64_t* blockinds, int one_based, int want_btd);
 int setup_transfer_btd(aggmg_ctx* ctx, const aggmg_op* L, const BtdDev* Abtd, int mf, int64_t nef, int hint_mc,
                        TransferBtd* out, bool* ok);
+// classes of identical per-element operator records of a fused level; *out stays null where the level does not take the
+// form: other block sizes / packings, agglomerates of different sizes, more than kDictMaxClasses distinct records
+int setup_op_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, std::unique_ptr<DictDev>* out);
 int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr);
 int cgt_detect(aggmg_ctx* ctx, aggmg_smoother* sm);   // chain form from the operator's own pattern (no element lists)
 // chunk-interleaved boundary rows of the element-partitioned coarsest solve (aggmg_hip.hip; used by dist.hip)

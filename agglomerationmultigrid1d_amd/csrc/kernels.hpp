@@ -668,6 +668,14 @@ struct BtdLevel {
   const double *sub, *sup, *P, *Q;
   int64_t ne;
   int c_sub, r_sup;
+  // operator dictionary (btd_fused_kernel<..., DICT = true> only; set-up: setup_kernels.hpp, dict_* kernels): on a
+  // uniform mesh the per-element operator records repeat, so the level keeps one copy of every DISTINCT record and
+  // cls [ne] the record of every element.  The launch then passes the dictionary's arrays ([nclasses][...], the layouts
+  // of the full ones) in the pointers above and in FusedArgs::lf_* / lf1_*, and the kernel indexes them by cls[e]
+  // instead of e; qmir [nclasses][M] is the record's copy of the left neighbour's super-diagonal row q_{e-1} (zeros at
+  // e = 0), so no load needs the neighbour's class.  The same bits from another address.
+  const uint16_t* cls;
+  const double* qmir;
 };
 
 struct FusedArgs {
@@ -810,7 +818,8 @@ __device__ __forceinline__ double group_bcast(double v, int j) {
 // the coupling entry scol_e[i] into sc.  Lane i reads only its own run D[i][i..M-1] of the packed triangle; a lower
 // entry D[i][j] is rebuilt from lane j's D[j][i], moved across the group by DPP (no LDS, no memory traffic).  The
 // coupling entry's mirror q_{e-1}[i] lies in lines the tile has loaded already; the escape is always taken at e = 0.
-template <int M>
+// DICT: e is the element's class and lv holds the dictionary's arrays; the mirror row is the record's own copy.
+template <int M, bool DICT = false>
 __device__ __forceinline__ void sym_residual_row(const BtdLevel& lv, int64_t e, int i, double (&dk)[M], double& sc) {
   constexpr int T = M * (M + 1) / 2;
   const int64_t row = e * M + i;
@@ -830,7 +839,7 @@ __device__ __forceinline__ void sym_residual_row(const BtdLevel& lv, int64_t e, 
     if (j < i) dk[j] = d == kSymResidualEscape ? lv.dblk[row * M + j] : sym_residual_decode(mir, d);
   }
   const int dc = (int)(int8_t)(w >> 24);
-  sc = dc == kSymResidualEscape ? lv.scol[row] : sym_residual_decode(lv.qrow[row - M], dc);
+  sc = dc == kSymResidualEscape ? lv.scol[row] : sym_residual_decode(DICT ? lv.qmir[row] : lv.qrow[row - M], dc);
 }
 
 // sum of a * b over the group, W = 2, 4: the first step's addition fused to the lane's own product, fma(a, b, partner's
@@ -965,10 +974,15 @@ __device__ __forceinline__ double btd_prolong2(double2 l2, double2 u2) {
 // SR: the explicit residual reads the lossless symmetric form (BtdLevel::dup / corr; the launcher picks this variant only
 // for block-Jacobi launches with an explicit residual on a level that has the form) -- a variant of its own, so the
 // launches without that residual (the ascent) keep the smaller kernel
-template <int M, bool CMP, int NS, bool SYM = false, int NT = kThreads, bool GS = false, bool CHK = false, bool SR = false>
+// DICT: the operator dictionary (BtdLevel::cls) -- every operator load takes its index from the element's class instead
+// of the element, in arrays small enough to stay in cache; the vectors and every arithmetic expression are those of the
+// plain variant.  Two-mode transfers of equal agglomerates only (the launcher's condition).
+template <int M, bool CMP, int NS, bool SYM = false, int NT = kThreads, bool GS = false, bool CHK = false, bool SR = false,
+          bool DICT = false>
 __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kernel(FusedArgs a) {
   static_assert(!SYM || M == 2 || M == 4 || M == 8, "symmetric packing needs the lane-group path");
   static_assert(!(CHK && GS), "the checkpoint is for block-Jacobi launches");
+  static_assert(!DICT || (CMP && SYM && (M == 2 || M == 4) && !GS && !CHK), "the dictionary variant's levels");
   // GRP: the rows of one element sit in M = 2^k adjacent lanes, so element-wide sums and
   // broadcasts (q.u+, B^{-1} b) go through cross-lane moves instead of LDS round trips
   constexpr bool GRP = CMP && (M == 2 || M == 4 || M == 8);
@@ -1025,6 +1039,7 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
   double binv_r[NS], pc[NS], qv[NS][GRP ? 1 : M];  // CMP (GRP: own entry of the q row only)
   double Pr[NS][M], Qr[NS][M];                   // dense
   bool valid[NS];
+  [[maybe_unused]] int ce[NS];                   // DICT: the elements' classes
 
   // ---- load phase: everything this tile needs from HBM, issued up front --------------------
 #pragma unroll
@@ -1037,6 +1052,10 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
     bb[s] = 0.0;
 #pragma unroll
     for (int j = 0; j < M; ++j) bi[s][j] = 0.0;
+    if constexpr (DICT) ce[s] = valid[s] ? (int)a.lv.cls[e] : 0;
+    // the operator's record: the element's own, or (DICT) its class's in the dictionary
+    const int64_t oe = DICT ? (int64_t)ce[s] : e;
+    const int64_t orow = oe * M + i;
     if (valid[s]) {
       if (need_g) {
         if (SYM) {  // row i of the symmetric inverse out of its packed upper triangle
@@ -1044,7 +1063,7 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
 #pragma unroll
           for (int j = 0; j < M; ++j) {
             const int lo_ = i < j ? i : j, hi_ = i < j ? j : i;
-            bi[s][j] = a.lv.bsym[e * T + lo_ * M - (lo_ * (lo_ - 1)) / 2 + (hi_ - lo_)];
+            bi[s][j] = a.lv.bsym[oe * T + lo_ * M - (lo_ * (lo_ - 1)) / 2 + (hi_ - lo_)];
           }
         } else {
 #pragma unroll
@@ -1056,21 +1075,24 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
       if (pre2) {
         if (a.lf1_out && !a.ld_out) {   // unit first column: 1.0 * r is r, bit for bit what the stored 1.0 gives
           l2x[s] = 1.0;
-          l2y[s] = AGGMG_LD(a.lf1_out[row]);
+          l2y[s] = AGGMG_LD(a.lf1_out[orow]);
         } else {
-          const double2 t2 = *reinterpret_cast<const double2*>(lfo_pre + row * 2);
+          const double2 t2 = *reinterpret_cast<const double2*>(lfo_pre + orow * 2);
           l2x[s] = t2.x;
           l2y[s] = t2.y;
         }
       }
       if (CMP) {
         if (SYM) {
-          pc[s] = (need_g && e > 0) ? a.lv.qrow[(e - 1) * M + i] : 0.0;  // q_{e-1}[i]; B^{-1} applied below
+          if constexpr (DICT)
+            pc[s] = need_g ? a.lv.qmir[orow] : 0.0;
+          else
+            pc[s] = (need_g && e > 0) ? a.lv.qrow[(e - 1) * M + i] : 0.0;  // q_{e-1}[i]; B^{-1} applied below
         } else {
           pc[s] = need_g ? AGGMG_LD(a.lv.pcol[row]) : 0.0;
         }
         if (GRP) {
-          qv[s][0] = AGGMG_LD(a.lv.qrow[e * M + i]);
+          qv[s][0] = AGGMG_LD(a.lv.qrow[oe * M + i]);
         } else {
 #pragma unroll
           for (int j = 0; j < (GRP ? 1 : M); ++j) qv[s][j] = a.lv.qrow[e * M + j];
@@ -1097,9 +1119,9 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
           double2 l2;
           if (a.lf1_in) {
             l2.x = 1.0;
-            l2.y = AGGMG_LD(a.lf1_in[row]);
+            l2.y = AGGMG_LD(a.lf1_in[orow]);
           } else {
-            const v2d lv2 = AGGMG_LD(*reinterpret_cast<const v2d*>(a.lf_in + row * 2));
+            const v2d lv2 = AGGMG_LD(*reinterpret_cast<const v2d*>(a.lf_in + orow * 2));
             l2.x = lv2.x;
             l2.y = lv2.y;
           }
@@ -1199,9 +1221,10 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
   [[maybe_unused]] bool stashed = false;
   // (CMP) the row's entries from memory: the full arrays, or (sres) the lossless symmetric form -- the same bits
   [[maybe_unused]] auto load_row = [&](int s, int64_t row, double (&dk)[M], double& sc) {
+    if constexpr (DICT) row = (int64_t)ce[s] * M + i;
     if constexpr (SRES) {
       if (sres) {
-        sym_residual_row<M>(a.lv, row / M, i, dk, sc);
+        sym_residual_row<M, DICT>(a.lv, row / M, i, dk, sc);
         return;
       }
     }
@@ -1389,7 +1412,6 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
     }
   }
   if (!lfo) return;
-
   if (a.par_out) {
     // ---- restriction onto agglomerates of different sizes: r through LDS, one thread per (J, mode) over the
     // part of the agglomerate this tile owns

@@ -586,6 +586,77 @@ int setup_transfer_btd(aggmg_ctx* ctx, const aggmg_op* L, const BtdDev* Abtd, in
 }
 
 // ---------------------------------------------------------------------------------------------
+// operator dictionary of a fused level
+// ---------------------------------------------------------------------------------------------
+int setup_op_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, std::unique_ptr<DictDev>* out) {
+  out->reset();
+  const int m = b.m;
+  // the levels of btd_fused_kernel<M, CMP, ., SYM, ...> with M = 2, 4 whose transfer has two modes on equal agglomerates
+  if (!(b.cmp && b.bsym && (m == 2 || m == 4) && b.scol && b.dblk && b.qrow)) return AGGMG_OK;
+  if (!(t.rho > 0 && t.mc == 2 && t.lf) || b.ne < 1) return AGGMG_OK;
+  const int64_t ne = b.ne;
+  const int T = m * (m + 1) / 2;
+  DictView v;
+  std::memset(&v, 0, sizeof(v));
+  v.ne = ne;
+  v.m = m;
+  v.lfw = t.lf1 ? 1 : 2;
+  v.full = DictArrays{b.bsym, b.qrow, nullptr, b.dup, b.scol, b.dblk, t.lf1 ? t.lf1 : t.lf, b.corr};
+  // the distinct record hashes; more than kDictMaxClasses: the level keeps the plain path
+  Tmp table;
+  CHECK(tmp_alloc(ctx, &table, (size_t)kDictSlots * sizeof(unsigned long long), true));
+  Flags stat;
+  CHECK(stat.init(ctx, 2));
+  LAUNCH(dict_collect_kernel, ne, v, table.as<unsigned long long>(), stat.d);
+  int st[2] = {0, 0};
+  CHECK(stat.read(ctx, st));
+  if (st[1] || st[0] > kDictMaxClasses || st[0] < 1) return AGGMG_OK;
+  std::vector<unsigned long long> slots(kDictSlots), hashes;
+  HIPCHK(hipMemcpyAsync(slots.data(), table.p, slots.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (unsigned long long s : slots)
+    if (s) hashes.push_back(s);
+  std::sort(hashes.begin(), hashes.end());
+  const int nc = (int)hashes.size();
+  if (nc != st[0]) return AGGMG_OK;
+  // classes in ascending order of the hash, each one's record from its first element: the same dictionary every time
+  auto d = std::make_unique<DictDev>();
+  d->nclasses = nc;
+  d->lf_unit = t.lf1 != nullptr;
+  Tmp sorted, rep;
+  CHECK(tmp_alloc(ctx, &sorted, (size_t)nc * sizeof(unsigned long long), false));
+  CHECK(tmp_alloc(ctx, &rep, (size_t)nc * sizeof(unsigned long long), false));
+  HIPCHK(hipMemcpyAsync(sorted.p, hashes.data(), (size_t)nc * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
+  const std::vector<unsigned long long> none((size_t)nc, (unsigned long long)ne);
+  HIPCHK(hipMemcpyAsync(rep.p, none.data(), (size_t)nc * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // (the two host vectors are done with before anything below can return)
+  CHECK(dalloc(ctx, &d->cls, ne, false));
+  CHECK(dalloc(ctx, &d->bsym, (int64_t)nc * T, false));
+  CHECK(dalloc(ctx, &d->qrow, (int64_t)nc * m, false));
+  CHECK(dalloc(ctx, &d->qmir, (int64_t)nc * m, false));
+  if (b.dup) {
+    CHECK(dalloc(ctx, &d->dup, (int64_t)nc * T, false));
+    CHECK(dalloc(ctx, &d->corr, (int64_t)nc * m, false));
+  }
+  CHECK(dalloc(ctx, &d->scol, (int64_t)nc * m, false));
+  CHECK(dalloc(ctx, &d->dblk, (int64_t)nc * m * m, false));
+  CHECK(dalloc(ctx, &d->lf, (int64_t)nc * m * v.lfw, false));
+  v.dict = DictArrays{d->bsym, d->qrow, d->qmir, d->dup, d->scol, d->dblk, d->lf, d->corr};
+  Flags bad;
+  CHECK(bad.init(ctx, 1));
+  LAUNCH(dict_assign_kernel, ne, v, nc, (const unsigned long long*)sorted.as<unsigned long long>(), d->cls,
+         rep.as<unsigned long long>(), bad.d);
+  LAUNCH(dict_gather_kernel, nc, v, nc, (const unsigned long long*)rep.as<unsigned long long>());
+  // every element's record against its class's, bit for bit: two records of one hash leave the level on the plain path
+  LAUNCH(dict_verify_kernel, ne, v, (const uint16_t*)d->cls, bad.d);
+  int b1 = 0;
+  CHECK(bad.read(ctx, &b1));
+  if (b1) return AGGMG_OK;
+  *out = std::move(d);
+  return AGGMG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // cyclic-reduction factorisation of the coarsest operator
 // ---------------------------------------------------------------------------------------------
 template <int M>

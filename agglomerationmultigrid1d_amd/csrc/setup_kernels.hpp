@@ -525,6 +525,134 @@ __global__ __launch_bounds__(kSetupThreads) void btd_sym_residual_kernel(int64_t
 }
 
 // ------------------------------------------------------------------------------------------
+// operator dictionary of a symmetric-packed compressed level (BtdLevel::cls, btd_fused_kernel<..., DICT = true>)
+// ------------------------------------------------------------------------------------------
+// The record of element e: every operator word the fused kernel reads on behalf of e, as 64-bit patterns in one fixed
+// order -- bsym[e] (T), qrow[e] (m), the mirror qrow[e-1] (m; zeros at e = 0), dup[e] (T) and corr (m words) where the
+// level has the symmetric residual form, the escape sources scol[e] (m) and dblk[e] (m*m), and the element's rows of
+// the transfer (m * lfw: lf1, or the two-entry rows of lf).  `full` holds the level's arrays, `dict` the dictionary's
+// ([nclasses][...], the same layouts; qmir is the mirror's own array there).
+constexpr int kDictMaxClasses = 1024;   // distinct records a level may have and still take the form (dictionary < 0.5 MB)
+constexpr int kDictSlots = 4096;        // open-addressed table of the records' hashes during the search (a power of two)
+struct DictArrays {
+  double *bsym, *qrow, *qmir, *dup, *scol, *dblk, *lf;
+  uint32_t* corr;
+};
+struct DictView {
+  DictArrays full, dict;   // (full.qmir unused: the mirror is qrow[e - 1])
+  int64_t ne;
+  int m, lfw;
+};
+// f(array k, word j of the element's part of it, the bits) over the record of element e, in the record's order
+template <class F>
+__device__ __forceinline__ void dict_record(const DictView& v, int64_t e, F&& f) {
+  const DictArrays& a = v.full;
+  const int m = v.m, T = m * (m + 1) / 2;
+  auto bits = [](double x) { return (unsigned long long)__double_as_longlong(x); };
+  for (int j = 0; j < T; ++j) f(0, j, bits(a.bsym[e * T + j]));
+  for (int j = 0; j < m; ++j) f(1, j, bits(a.qrow[e * m + j]));
+  for (int j = 0; j < m; ++j) f(2, j, e > 0 ? bits(a.qrow[(e - 1) * m + j]) : 0ull);
+  if (a.dup) {
+    for (int j = 0; j < T; ++j) f(3, j, bits(a.dup[e * T + j]));
+    for (int j = 0; j < m; ++j) f(4, j, (unsigned long long)a.corr[e * m + j]);
+  }
+  for (int j = 0; j < m; ++j) f(5, j, bits(a.scol[e * m + j]));
+  for (int j = 0; j < m * m; ++j) f(6, j, bits(a.dblk[e * m * m + j]));
+  for (int j = 0; j < m * v.lfw; ++j) f(7, j, bits(a.lf[e * m * v.lfw + j]));
+}
+// word (k, j) of class c's record in the dictionary: stored (store) or compared -- true when it holds w afterwards
+__device__ __forceinline__ bool dict_word(const DictView& v, int64_t c, int k, int j, unsigned long long w, bool store) {
+  const DictArrays& d = v.dict;
+  const int m = v.m, T = m * (m + 1) / 2;
+  if (k == 4) {
+    uint32_t* p = d.corr + c * m + j;
+    if (store) *p = (uint32_t)w;
+    return *p == (uint32_t)w;
+  }
+  double* p = k == 0 ? d.bsym + c * T : k == 1 ? d.qrow + c * m : k == 2 ? d.qmir + c * m : k == 3 ? d.dup + c * T
+            : k == 5 ? d.scol + c * m : k == 6 ? d.dblk + c * m * m : d.lf + c * m * v.lfw;
+  unsigned long long* q = reinterpret_cast<unsigned long long*>(p + j);
+  if (store) *q = w;
+  return *q == w;
+}
+// 64-bit hash of a record (never 0: that marks an empty slot of the table)
+__device__ __forceinline__ unsigned long long dict_hash(const DictView& v, int64_t e) {
+  unsigned long long h = 0x243F6A8885A308D3ull;
+  dict_record(v, e, [&](int, int, unsigned long long w) {
+    h = (h ^ w) * 0x9E3779B97F4A7C15ull;
+    h ^= h >> 29;
+  });
+  h *= 0xBF58476D1CE4E5B9ull;
+  h ^= h >> 32;
+  return h ? h : 1ull;
+}
+// the distinct hashes of the level, gathered in table[kDictSlots] (zeroed); stat[0] counts them, stat[1] is raised -- and
+// every later thread returns at once -- when there are more than kDictMaxClasses or the table is full.  One thread per
+// element; a slot changes once, from 0 to its hash, so a stale read only costs the compare-and-swap that settles it.
+__global__ __launch_bounds__(kSetupThreads) void dict_collect_kernel(DictView v, unsigned long long* __restrict__ table,
+                                                                     int* __restrict__ stat) {
+  const int64_t e = (int64_t)blockIdx.x * kSetupThreads + threadIdx.x;
+  if (e >= v.ne) return;
+  if (__atomic_load_n(&stat[1], __ATOMIC_RELAXED)) return;
+  const unsigned long long h = dict_hash(v, e);
+  unsigned slot = (unsigned)(h >> 20) & (kDictSlots - 1);
+  for (int probe = 0; probe < kDictSlots; ++probe, slot = (slot + 1) & (kDictSlots - 1)) {
+    unsigned long long cur = __atomic_load_n(&table[slot], __ATOMIC_RELAXED);
+    if (cur == 0) {
+      cur = atomicCAS(&table[slot], 0ull, h);
+      if (cur == 0) {
+        if (atomicAdd(&stat[0], 1) + 1 > kDictMaxClasses) atomicExch(&stat[1], 1);
+        return;
+      }
+    }
+    if (cur == h) return;
+  }
+  atomicExch(&stat[1], 1);
+}
+// cls[e]: the position of the element's hash in the ascending list sorted[nclasses]; rep[c]: the first element of class c
+// (rep initialised to ne).  bad[0] is raised for a hash that is not in the list (cannot happen after dict_collect_kernel).
+__global__ __launch_bounds__(kSetupThreads) void dict_assign_kernel(DictView v, int nclasses,
+                                                                    const unsigned long long* __restrict__ sorted,
+                                                                    uint16_t* __restrict__ cls,
+                                                                    unsigned long long* __restrict__ rep, int* __restrict__ bad) {
+  const int64_t e = (int64_t)blockIdx.x * kSetupThreads + threadIdx.x;
+  if (e >= v.ne) return;
+  const unsigned long long h = dict_hash(v, e);
+  int lo = 0, hi = nclasses - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (sorted[mid] < h) lo = mid + 1;
+    else hi = mid;
+  }
+  if (sorted[lo] != h) {
+    atomicExch(bad, 1);
+    lo = 0;
+  }
+  cls[e] = (uint16_t)lo;
+  if ((unsigned long long)e < __atomic_load_n(&rep[lo], __ATOMIC_RELAXED)) atomicMin(&rep[lo], (unsigned long long)e);
+}
+// the dictionary's records: class c's from its first element.  One thread per class.
+__global__ __launch_bounds__(kSetupThreads) void dict_gather_kernel(DictView v, int nclasses,
+                                                                    const unsigned long long* __restrict__ rep) {
+  const int64_t c = (int64_t)blockIdx.x * kSetupThreads + threadIdx.x;
+  if (c >= nclasses) return;
+  const int64_t e = (int64_t)rep[c];
+  if (e >= v.ne) return;   // (a class without an element: dict_assign_kernel raised bad)
+  dict_record(v, e, [&](int k, int j, unsigned long long w) { (void)dict_word(v, c, k, j, w, true); });
+}
+// every element's full record against its class's dictionary record, bit for bit: bad[0] raised at a difference (two
+// records of one hash).  One thread per element.
+__global__ __launch_bounds__(kSetupThreads) void dict_verify_kernel(DictView v, const uint16_t* __restrict__ cls,
+                                                                    int* __restrict__ bad) {
+  const int64_t e = (int64_t)blockIdx.x * kSetupThreads + threadIdx.x;
+  if (e >= v.ne) return;
+  const int64_t c = cls[e];
+  bool same = true;
+  dict_record(v, e, [&](int k, int j, unsigned long long w) { same = same && dict_word(v, c, k, j, w, false); });
+  if (!same) atomicExch(bad, 1);
+}
+
+// ------------------------------------------------------------------------------------------
 // structured transfers of block-tridiagonal levels
 // ------------------------------------------------------------------------------------------
 // every stored entry of L (CSC, fine x coarse) must couple fine element e to the mc modes of coarse element

@@ -94,6 +94,19 @@ int aggmg_synchronize(aggmg_ctx* ctx);
  * p = 3: 64 of the fine descent's 404 bytes per element; the descent 9 % faster, the V-cycle 2 - 4 % (DESIGN.md
  * section 5). */
 #define AGGMG_OPT_SYMMETRIC_RESIDUAL 6
+/* AGGMG_OPT_OPERATOR_DICTIONARY (default 1; environment AGGMG_OP_DICT=0 makes the default 0): on a uniform mesh the
+ * per-element operator records of a level repeat (a handful of distinct ones at 2^24 elements).  aggmg_hier_create looks
+ * for the classes of bitwise identical records on symmetric-packed levels with compressed couplings, blocks of 2 or 4
+ * rows and a two-mode transfer onto equal agglomerates -- a record is everything the fused kernel reads for one element:
+ * the packed inverse, the coupling row and its left neighbour's, the residual's entries in both forms, the transfer's
+ * rows -- and, where there are at most 1024 of them, keeps one copy of each and a 16-bit class per element.  The
+ * block-Jacobi launches of a cycle (descent, ascent, the launch between two cycles; not the checkpoint, Gauss-Seidel,
+ * K-column, two-level or partitioned ones) then index the operator by the element's class: the same bits from a table
+ * that stays in cache, so every result is bit for bit that of the full arrays, which stay allocated.  Every element's
+ * record is compared against its class's at set-up; a level with more classes, or a mismatch, keeps the plain path.
+ * Hierarchies created afterwards; aggmg_hier_level_dictionary reports the levels.  aggmg_hier_launch_bytes keeps
+ * counting the full arrays. */
+#define AGGMG_OPT_OPERATOR_DICTIONARY 7
 int aggmg_set_option(aggmg_ctx* ctx, int option, int value);
 /* Raw device memory owned by the context's device (plumbing for harnesses without torch, and the storage of the
  * Julia shim's DeviceVector).  aggmg_dev_alloc returns ZEROED memory: a fresh vector is the zero initial guess of
@@ -397,6 +410,9 @@ int aggmg_hier_level_paired_up(aggmg_ctx* ctx, const aggmg_hier* h, int level, i
 /* Whether level `level`'s fused kernel forms its explicit residual from the lossless symmetric form of the operator's
  * entries (AGGMG_OPT_SYMMETRIC_RESIDUAL): 1 when it was built at set-up, 0 otherwise. */
 int aggmg_hier_level_sym_residual(aggmg_ctx* ctx, const aggmg_hier* h, int level, int* on);
+/* Distinct operator records of the level's dictionary (AGGMG_OPT_OPERATOR_DICTIONARY); 0: the level has none and its
+ * launches read the full arrays. */
+int aggmg_hier_level_dictionary(aggmg_ctx* ctx, const aggmg_hier* h, int level, int* nclasses);
 /* Which coarsest solver a hierarchy uses: on_device (1 = cyclic reduction), its block size and the
  * largest pivot-block condition estimate met while factoring (0 for the host solver). */
 int aggmg_hier_coarse_info(aggmg_ctx* ctx, const aggmg_hier* h, int* on_device, int* block_size,

@@ -241,6 +241,27 @@ function free!(Hd::DeviceHierarchy)
     return nothing
 end
 
+# context options (aggmg_set_option; include/aggmg_hip.h).  AGGMG_OPT_OPERATOR_DICTIONARY (default 1; environment
+# AGGMG_OP_DICT=0 makes the default 0): hierarchies created afterwards keep one copy of every distinct per-element
+# operator record of a fused level and index the operator by the element's class -- the same bits, read from cache.
+const OPT_OPERATOR_DICTIONARY = 7
+function set_option!(ctx::Context, option::Integer, value::Integer)
+    check(ctx.h, ccall((:aggmg_set_option, LIB), Cint, (Handle, Cint, Cint), ctx.h, option, value))
+    return ctx
+end
+
+# level (1-based, as H.mMeshes) => distinct operator records of the levels that have a dictionary
+function dictionary_levels(Hd::DeviceHierarchy)
+    out = Dict{Int,Int}()
+    for k in 1:length(Hd.ops)
+        r = Ref{Cint}(0)
+        check(Hd.ctx.h, ccall((:aggmg_hier_level_dictionary, LIB), Cint, (Handle, Handle, Cint, Ref{Cint}),
+                              Hd.ctx.h, Hd.h, k - 1, r))
+        r[] > 0 && (out[k] = Int(r[]))
+    end
+    return out
+end
+
 # coarse_mode 2 = AGGMG_COARSE_AUTO
 function DeviceHierarchy(H::MeshHierarchy; ctx::Context = default_context(), coarse_mode::Integer = 2)
     n = length(H.mMeshes)

@@ -54,7 +54,8 @@ def main():
         H.vcycle_dev(xa, b, xb)
         ctx.synchronize()
         cr_trace.report(cr_trace.fetch(ctx, fn))
-    print(json.dumps({"kind": args.kind, "log2_elems": args.log2_elems, "steps": args.steps, "levels": H.level_kinds()}))
+    print(json.dumps({"kind": args.kind, "log2_elems": args.log2_elems, "steps": args.steps, "levels": H.level_kinds(),
+                      "dictionary": {str(k): v for k, v in H.dictionary_levels().items()}}))
 
 
 if __name__ == "__main__":
