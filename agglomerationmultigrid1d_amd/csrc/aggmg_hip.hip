@@ -1697,6 +1697,8 @@ extern "C" int aggmg_hier_create(aggmg_ctx* ctx, int nlevels, aggmg_op* const* s
     if (ok) {
       l.tc = std::move(tc);
       l.cgt_fused = true;
+      // the level's distinct operator records, where they are few (AGGMG_OPT_OPERATOR_DICTIONARY)
+      if (ctx->op_dict) CHECK(setup_cgt_dictionary(ctx, *l.S->cgt, *l.tc, &l.cdict));
     }
   }
   // a fused chain level below a fused chain level keeps its rhs / result in block order
@@ -1953,7 +1955,7 @@ extern "C" int aggmg_hier_level_dictionary(aggmg_ctx* ctx, const aggmg_hier* h, 
   if (!ctx || !h || !nclasses) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_dictionary: NULL argument");
   if (level < 0 || level >= (int)h->lv.size()) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_dictionary: level out of range");
   const Level& l = h->lv[level];
-  *nclasses = l.dict ? l.dict->nclasses : 0;
+  *nclasses = l.dict ? l.dict->nclasses : (l.cdict ? l.cdict->nclasses : 0);
   return AGGMG_OK;
 }
 

@@ -112,7 +112,19 @@ static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, int sw, CgtChk* chk_io) {
   if (ntiles >= ((int64_t)1 << 31)) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "grid too large");
   a.chk_tiles = ntiles;
   if (a.chk_stride < 1) a.chk_stride = 1 << 30;
-  const size_t lds = (size_t)(sw ? 3 : 2) * (T::TE + 2) * M * sizeof(double) + (a.chk_part ? (size_t)2 * (T::NT / 64) * sizeof(double) : 0);
+  size_t lds = (size_t)(sw ? 3 : 2) * (T::TE + 2) * M * sizeof(double) + (a.chk_part ? (size_t)2 * (T::NT / 64) * sizeof(double) : 0);
+  // the operator dictionary (cgt_dictionary put its arrays in place of the full ones): point-Jacobi launches without
+  // checkpoints on blocks of 1, 2 or 4 rows; the tile's classes go to LDS behind the iterate buffers
+  if (a.cls) {
+    if constexpr (K == 0 && (M == 1 || M == 2 || M == 4)) {
+      if (a.chk_part) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: dictionary launch of a checkpoint variant");
+      lds += (size_t)(T::TE + 2) * sizeof(uint16_t);
+      hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 0, false, true>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a);
+      HIPCHK(hipGetLastError());
+      return AGGMG_OK;
+    }
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: dictionary launch of a chain variant that does not index by class");
+  }
   if constexpr (K == 0) {
     if (a.chk_part) {
       hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 0, true>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a);
@@ -154,6 +166,22 @@ static CgtArgs cgt_args(const CgtDev& g) {
   return a;
 }
 
+// The level's operator dictionary in place of its full arrays: the point-Jacobi launches of a cycle -- no checkpoint -- on
+// a level that has one.  tin / tout are the level's own transfer (or none).  The variant reads the same bits from the
+// dictionary (cgt_fused_kernel<..., DICT = true>).
+static void cgt_dictionary(CgtArgs& a, const CgtDev& g, const CgtDictDev* d) {
+  if (!d || g.sw != 0 || a.chk_part) return;
+  a.lv.dblk = d->dblk;
+  a.lv.subrow = d->subrow;
+  a.lv.supcol = d->supcol;
+  a.cls = d->cls;
+  for (CgtXfer* x : {&a.tin, &a.tout})
+    if (x->type != kTrNone) {
+      x->l = d->l;
+      x->lp = d->lp;
+    }
+}
+
 static CgtXfer cgt_xfer(const TransferCgt& t, bool coarse_native) {
   CgtXfer x;
   x.type = t.type;
@@ -185,7 +213,7 @@ struct CgtChain {
 };
 
 static int cgt_run(aggmg_ctx* ctx, const CgtDev& g, const CgtChain& c, double alpha, int nsweeps, const CgtArgs& first,
-                   const CgtArgs& last, int kind, int level, CgtChk* chk = nullptr) {
+                   const CgtArgs& last, int kind, int level, CgtChk* chk = nullptr, const CgtDictDev* dict = nullptr) {
   // at most smax sweeps per launch (2 * smax + 3 blocks of halo always fit a tile)
   const int smax = cgt_max_sweeps(g.m, g.sw);
   const int nl = std::max(1, (nsweeps + smax - 1) / smax);
@@ -229,6 +257,7 @@ static int cgt_run(aggmg_ctx* ctx, const CgtDev& g, const CgtChain& c, double al
       a.ext |= kExtB;   // (the caller-side indices are formed: chk_exact goes through them)
       if (!c.b_ext) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: checkpoint launch on block-ordered vectors");
     }
+    cgt_dictionary(a, g, dict);   // (every chunk: the intermediate launches read the operator too)
     {
       ProfScope ps(ctx, q == nl - 1 ? kind : AGGMG_KIND_SMOOTH, level);
       CHECK(cgt_launch(ctx, g, a, chk));
@@ -294,7 +323,7 @@ int cgt_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uin, const doub
   last.do_residual = 1;
   last.tout = cgt_xfer(*l.tc, c.native_io);
   last.rc_out = c.rhs;
-  return cgt_run(ctx, g, ch, alpha, nPre, none, last, AGGMG_KIND_FUSED_DOWN, k);
+  return cgt_run(ctx, g, ch, alpha, nPre, none, last, AGGMG_KIND_FUSED_DOWN, k, nullptr, l.cdict.get());
 }
 
 // ascending half (src/solvers.jl:41-47): prolongation-add, nPost sweeps
@@ -321,7 +350,7 @@ int cgt_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* rhs, int nPost, d
   std::memset(&none, 0, sizeof(none));
   first.tin = cgt_xfer(*l.tc, c.native_io);
   first.uc = (k + 1 == n - 1) ? c.u[0] : c.u[1];
-  return cgt_run(ctx, g, ch, alpha, nPost, first, none, AGGMG_KIND_FUSED_UP, k, chk);
+  return cgt_run(ctx, g, ch, alpha, nPost, first, none, AGGMG_KIND_FUSED_UP, k, chk, l.cdict.get());
 }
 
 // Between two cycles of multigrid()'s loop (src/solvers.jl:124-126) the fine level post-smooths and then
@@ -351,7 +380,7 @@ int cgt_mid(aggmg_ctx* ctx, aggmg_hier* h, const double* cur, double* alt, const
   last.do_residual = 1;
   last.tout = cgt_xfer(*l.tc, c.native_io);
   last.rc_out = c.rhs;
-  return cgt_run(ctx, g, ch, alpha, nsweeps, first, last, AGGMG_KIND_FUSED_MID, 0, chk);
+  return cgt_run(ctx, g, ch, alpha, nsweeps, first, last, AGGMG_KIND_FUSED_MID, 0, chk, l.cdict.get());
 }
 
 // ---- compulsory bytes: what the arrays of a launch hold, each read or written once -------------

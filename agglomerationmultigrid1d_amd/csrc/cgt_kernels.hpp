@@ -84,6 +84,13 @@ struct CgtArgs {
   int64_t chk_tiles;
   const double* chk_exact;
   double* chk_part;
+  // operator dictionary (cgt_fused_kernel<..., DICT = true> only; set-up: setup_kernels.hpp, dict_* kernels): on a
+  // uniform mesh the per-block operator records -- the block's rows of dblk, subrow, supcol and of the transfer -- repeat;
+  // cls [ne] is the record of every block.  The launch then passes the dictionary's arrays ([nclasses][...], the layouts
+  // of the full ones) in lv.dblk / subrow / supcol and in the transfers' l / lp, and the kernel indexes them by class.
+  // (The level's field by meaning; it is the LAST argument so that every other one keeps its offset and the variants
+  // without a dictionary stay the code they were.)
+  const uint16_t* cls;
 };
 
 __device__ __forceinline__ int64_t cgt_tile(const CgtArgs& a) {
@@ -101,9 +108,14 @@ __device__ __forceinline__ int64_t cgt_tile(const CgtArgs& a) {
 // CG-fine hierarchy of config 5): red-black element Gauss-Seidel.  A sweep is two half-sweeps, one per element
 // colour (elements of one colour share no node): r = b - A u, then u[nodes_e] += alpha (A_e \ r[nodes_e]) for
 // every element of the colour; a.gs gives the colour order.  Four blocks of halo per sweep and side.
-template <int M, int NS, int NT, int SW = 0, bool CHK = false>
+// DICT: the operator dictionary (CgtArgs::cls) -- every operator and transfer load takes its row index from the block's
+// class instead of from the block; vectors, their indexing and the order of every sum are those of the plain variant, so
+// the results are the same bits.  The tile's classes also sit in LDS for the restriction, which walks the rows of L of
+// other threads' blocks.
+template <int M, int NS, int NT, int SW = 0, bool CHK = false, bool DICT = false>
 __global__ __launch_bounds__(NT) void cgt_fused_kernel(CgtArgs a) {
   static_assert(!CHK || SW == 0, "the checkpoint variant is for point-Jacobi launches");
+  static_assert(!DICT || (SW == 0 && !CHK && (M == 1 || M == 2 || M == 4)), "the dictionary variant's levels");
   // GRP: a block's rows sit in M = 2^k adjacent lanes; lane i keeps entry i of the block's
   // sub-diagonal row and the dot product with the left neighbour is a cross-lane sum
   constexpr bool GRP = (M == 1 || M == 2 || M == 4 || M == 8);
@@ -113,6 +125,8 @@ __global__ __launch_bounds__(NT) void cgt_fused_kernel(CgtArgs a) {
   double* buf0 = lds + M;  // index x*M + j, x in [-1, TE]
   double* buf1 = lds + (TE + 2) * M + M;
   double* rbuf = lds + 2 * (TE + 2) * M + M;  // SW: the residual of the current sweep
+  // DICT: class of block x of the tile at lcls[x], x in [-1, TE] (the launch reserves TE + 2 entries behind the iterate buffers)
+  [[maybe_unused]] uint16_t* lcls = reinterpret_cast<uint16_t*>(lds + 2 * (TE + 2) * M) + 1;
 
   const int tid = threadIdx.x;
   const bool active = tid < EPS * M;
@@ -136,14 +150,36 @@ __global__ __launch_bounds__(NT) void cgt_fused_kernel(CgtArgs a) {
   double d[NS][M], sup[NS], sr[NS][GRP ? 1 : M], dg[NS], bb[NS], uu[NS];
   int32_t pr[NS];
   bool valid[NS];
+  [[maybe_unused]] int ce[NS];   // DICT: the blocks' classes
 
   // ---- load phase ------------------------------------------------------------------------------
+  if constexpr (DICT) {
+    // the classes of every slab first: the record loads below depend on them
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const int64_t e = e0 + s * EPS + le;
+      ce[s] = (active && e >= 0 && e < ne) ? (int)a.cls[e] : 0;
+    }
+    if (tid == 0) {
+      lcls[-1] = 0;
+      lcls[TE] = 0;
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+      if (active && i == 0) lcls[s * EPS + le] = (uint16_t)ce[s];
+  }
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
     const int x = s * EPS + le;
     const int64_t e = e0 + x;
     valid[s] = active && e >= 0 && e < ne;
     const int64_t row = e * M + i;
+    // the operator's record: the block's own, or (DICT) its class's in the dictionary
+    [[maybe_unused]] int64_t oe = e, orow = row;
+    if constexpr (DICT) {
+      oe = ce[s];
+      orow = (int64_t)(ce[s] * M + i);
+    }
     uu[s] = 0.0;
     bb[s] = 0.0;
     sup[s] = 0.0;
@@ -168,13 +204,13 @@ __global__ __launch_bounds__(NT) void cgt_fused_kernel(CgtArgs a) {
         }
       }
 #pragma unroll
-      for (int j = 0; j < M; ++j) d[s][j] = AGGMG_LD(a.lv.dblk[row * M + j]);
+      for (int j = 0; j < M; ++j) d[s][j] = AGGMG_LD(a.lv.dblk[orow * M + j]);
 #pragma unroll
       for (int j = 0; j < M; ++j)
         if (j == i) dg[s] = d[s][j];
-      sup[s] = AGGMG_LD(a.lv.supcol[row]);
+      sup[s] = AGGMG_LD(a.lv.supcol[orow]);
       if (GRP) {
-        sr[s][0] = AGGMG_LD(a.lv.subrow[row]);  // entry i of the block's sub-diagonal row
+        sr[s][0] = AGGMG_LD(a.lv.subrow[orow]);  // entry i of the block's sub-diagonal row
       } else if (i == 0) {
 #pragma unroll
         for (int j = 0; j < (GRP ? 1 : M); ++j) sr[s][j] = a.lv.subrow[e * M + j];
@@ -193,7 +229,7 @@ __global__ __launch_bounds__(NT) void cgt_fused_kernel(CgtArgs a) {
       }
       if (a.tin.type == kTrChain) {
         const int mc = a.tin.mc;
-        const double* lr = a.tin.l + row * (mc + 1);
+        const double* lr = a.tin.l + orow * (mc + 1);
         double add = 0.0;
         // every load of the row's mc + 1 products issued before the first is used (a loop with a run-time trip count
         // takes them one dependent round trip at a time: the ascent was 8 % slower than the descent on the same bytes)
@@ -239,9 +275,9 @@ __global__ __launch_bounds__(NT) void cgt_fused_kernel(CgtArgs a) {
         const int64_t J = e / a.tin.rho;
         double add = 0.0;
         if (i == 0 && J >= 1 && e == J * a.tin.rho)
-          for (int c = 0; c < mc; ++c) add += a.tin.lp[e * mc + c] * a.uc[(J - 1) * mc + c];
+          for (int c = 0; c < mc; ++c) add += a.tin.lp[oe * mc + c] * a.uc[(J - 1) * mc + c];
         if (J < a.tin.nec)
-          for (int c = 0; c < mc; ++c) add += a.tin.l[row * mc + c] * a.uc[J * mc + c];
+          for (int c = 0; c < mc; ++c) add += a.tin.l[orow * mc + c] * a.uc[J * mc + c];
         uu[s] += add;
       }
     }
@@ -442,11 +478,13 @@ __global__ __launch_bounds__(NT) void cgt_fused_kernel(CgtArgs a) {
       const int x = xo0 + xl;
       const int64_t J = e0 + x;  // coarse block = fine block
       if (J >= ne || J >= a.tout.nec) continue;
-      const int64_t rowb = J * M;
+      // the rows of L of block J and of block J - 1: the blocks' own, or (DICT) their classes' in the dictionary
+      const int64_t rowb = DICT ? (int64_t)lcls[x] * M : J * M;
+      const int64_t rowl = DICT ? (int64_t)lcls[x - 1] * M : rowb - M;
       // ascending fine row of the reference numbering: own vertex, the left element's rows, own interior
       double acc = L[rowb * w + c] * nxt[x * M];
       if (c == 0 && J > 0)
-        for (int k = 0; k < M; ++k) acc += L[(rowb - M + k) * w + mc] * nxt[(x - 1) * M + k];
+        for (int k = 0; k < M; ++k) acc += L[(rowl + k) * w + mc] * nxt[(x - 1) * M + k];
       for (int k = 1; k < M; ++k) acc += L[(rowb + k) * w + c] * nxt[x * M + k];
       const int64_t cb = J * mc + c;
       const int64_t ci = a.tout.cperm ? (int64_t)a.tout.cperm[cb] : cb;
@@ -461,12 +499,19 @@ __global__ __launch_bounds__(NT) void cgt_fused_kernel(CgtArgs a) {
       const int64_t J = J0 + Jl;
       if (J >= a.tout.nec) continue;
       const int xb = xo0 + Jl * rho;
-      const int64_t rowb = (e0 + xb) * (int64_t)M;
+      [[maybe_unused]] const int64_t rowb = (e0 + xb) * (int64_t)M;
       double acc = 0.0;
-      for (int k = 0; k < rho * M; ++k) acc += a.tout.l[(rowb + k) * mc + c] * nxt[xb * M + k];
+      if constexpr (DICT) {
+        for (int q = 0; q < rho; ++q) {   // (the same rows in the same order, block by block through the classes)
+          const int64_t rq = (int64_t)lcls[xb + q] * M;
+          for (int k = 0; k < M; ++k) acc += a.tout.l[(rq + k) * mc + c] * nxt[(xb + q) * M + k];
+        }
+      } else {
+        for (int k = 0; k < rho * M; ++k) acc += a.tout.l[(rowb + k) * mc + c] * nxt[xb * M + k];
+      }
       // the vertex that closes the agglomerate on the right belongs to the next fine block
       const int64_t en = (J + 1) * rho;
-      if (en < ne) acc += a.tout.lp[en * mc + c] * nxt[(xb + rho) * M];
+      if (en < ne) acc += a.tout.lp[(DICT ? (int64_t)lcls[xb + rho] : en) * mc + c] * nxt[(xb + rho) * M];
       a.rc_out[J * mc + c] = acc;
     }
   }

@@ -238,6 +238,21 @@ struct TransferCgt {
   }
 };
 
+// operator dictionary of a fused chain level (CgtArgs::cls in cgt_kernels.hpp; the same search as DictDev's): one copy of
+// every distinct per-block record -- the block's rows of the CgtDev arrays and of the level's transfer, [nclasses][...]
+// in the layouts of the full arrays -- and the class of every block.  The full arrays stay; every other kernel reads them.
+struct CgtDictDev {
+  int nclasses = 0;
+  uint16_t* cls = nullptr;   // [ne]
+  double *dblk = nullptr, *subrow = nullptr, *supcol = nullptr;
+  double* l = nullptr;       // chain: [nclasses][m][mc + 1], agglomerating: [nclasses][m][mc]
+  double* lp = nullptr;      // agglomerating: [nclasses][mc]
+  ~CgtDictDev() {
+    for (void* p : {(void*)cls, (void*)dblk, (void*)subrow, (void*)supcol, (void*)l, (void*)lp})
+      if (p) (void)hipFree(p);
+  }
+};
+
 struct Level {
   aggmg_op* A = nullptr;
   aggmg_smoother* S = nullptr;
@@ -247,6 +262,7 @@ struct Level {
   std::unique_ptr<TransferBtd> tb;  // structured transfer to level k+1, or null
   std::unique_ptr<TransferCgt> tc;  // CG chain level: structured transfer to level k+1, or null
   std::unique_ptr<DictDev> dict;    // operator dictionary of the level's fused launches, or null
+  std::unique_ptr<CgtDictDev> cdict;  // the same of a fused chain level's point-Jacobi launches, or null
   bool cgt_fused = false;           // the level runs cgt_fused_kernel (chain form + structured transfer)
   bool native_io = false;           // rhs and u[1] are kept in block order (the finer level is a fused chain level)
   int64_t Nalloc = 0;               // length of the level's vectors (ne * m for chain levels)
@@ -486,6 +502,8 @@ int setup_transfer_btd(aggmg_ctx* ctx, const aggmg_op* L, const BtdDev* Abtd, in
 // classes of identical per-element operator records of a fused level; *out stays null where the level does not take the
 // form: other block sizes / packings, agglomerates of different sizes, more than kDictMaxClasses distinct records
 int setup_op_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, std::unique_ptr<DictDev>* out);
+// the same for a fused chain level: blocks of 1, 2 or 4 rows, point-Jacobi sweeps, chain or agglomerating transfer
+int setup_cgt_dictionary(aggmg_ctx* ctx, const CgtDev& g, const TransferCgt& t, std::unique_ptr<CgtDictDev>* out);
 int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr);
 int cgt_detect(aggmg_ctx* ctx, aggmg_smoother* sm);   // chain form from the operator's own pattern (no element lists)
 // chunk-interleaved boundary rows of the element-partitioned coarsest solve (aggmg_hip.hip; used by dist.hip)

@@ -588,20 +588,30 @@ int setup_transfer_btd(aggmg_ctx* ctx, const aggmg_op* L, const BtdDev* Abtd, in
 // ---------------------------------------------------------------------------------------------
 // operator dictionary of a fused level
 // ---------------------------------------------------------------------------------------------
-int setup_op_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, std::unique_ptr<DictDev>* out) {
-  out->reset();
-  const int m = b.m;
-  // the levels of btd_fused_kernel<M, CMP, ., SYM, ...> with M = 2, 4 whose transfer has two modes on equal agglomerates
-  if (!(b.cmp && b.bsym && (m == 2 || m == 4) && b.scol && b.dblk && b.qrow)) return AGGMG_OK;
-  if (!(t.rho > 0 && t.mc == 2 && t.lf) || b.ne < 1) return AGGMG_OK;
-  const int64_t ne = b.ne;
-  const int T = m * (m + 1) / 2;
+namespace {
+// the arrays of a level's record, in the record's order; `dict` of every field is filled in by dict_build
+struct DictFields {
   DictView v;
-  std::memset(&v, 0, sizeof(v));
-  v.ne = ne;
-  v.m = m;
-  v.lfw = t.lf1 ? 1 : 2;
-  v.full = DictArrays{b.bsym, b.qrow, nullptr, b.dup, b.scol, b.dblk, t.lf1 ? t.lf1 : t.lf, b.corr};
+  void** slot[kDictMaxFields];   // where the owner keeps the dictionary's copy of field k
+  DictFields(int64_t ne) {
+    std::memset(&v, 0, sizeof(v));
+    v.ne = ne;
+  }
+  template <typename T>
+  void add(const T* full, T** dict, int n, bool back = false) {
+    static_assert(sizeof(T) == 8 || sizeof(T) == 4, "records are made of 64- and 32-bit words");
+    slot[v.nf] = reinterpret_cast<void**>(dict);
+    v.f[v.nf++] = DictField{full, nullptr, n, (int)sizeof(T), back ? 1 : 0};
+  }
+};
+
+// The classes of identical records of a level: *nclasses > 0, cls[ne] and the dictionary's arrays (through F.slot: they
+// belong to the caller's object whatever happens) when the level takes the form; *nclasses = 0 when it has more than
+// kDictMaxClasses distinct records or two records share a hash.
+int dict_build(aggmg_ctx* ctx, DictFields& F, uint16_t** cls, int* nclasses) {
+  *nclasses = 0;
+  DictView& v = F.v;
+  const int64_t ne = v.ne;
   // the distinct record hashes; more than kDictMaxClasses: the level keeps the plain path
   Tmp table;
   CHECK(tmp_alloc(ctx, &table, (size_t)kDictSlots * sizeof(unsigned long long), true));
@@ -620,9 +630,6 @@ int setup_op_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, s
   const int nc = (int)hashes.size();
   if (nc != st[0]) return AGGMG_OK;
   // classes in ascending order of the hash, each one's record from its first element: the same dictionary every time
-  auto d = std::make_unique<DictDev>();
-  d->nclasses = nc;
-  d->lf_unit = t.lf1 != nullptr;
   Tmp sorted, rep;
   CHECK(tmp_alloc(ctx, &sorted, (size_t)nc * sizeof(unsigned long long), false));
   CHECK(tmp_alloc(ctx, &rep, (size_t)nc * sizeof(unsigned long long), false));
@@ -630,29 +637,74 @@ int setup_op_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, s
   const std::vector<unsigned long long> none((size_t)nc, (unsigned long long)ne);
   HIPCHK(hipMemcpyAsync(rep.p, none.data(), (size_t)nc * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));   // (the two host vectors are done with before anything below can return)
-  CHECK(dalloc(ctx, &d->cls, ne, false));
-  CHECK(dalloc(ctx, &d->bsym, (int64_t)nc * T, false));
-  CHECK(dalloc(ctx, &d->qrow, (int64_t)nc * m, false));
-  CHECK(dalloc(ctx, &d->qmir, (int64_t)nc * m, false));
-  if (b.dup) {
-    CHECK(dalloc(ctx, &d->dup, (int64_t)nc * T, false));
-    CHECK(dalloc(ctx, &d->corr, (int64_t)nc * m, false));
+  CHECK(dalloc(ctx, cls, ne, false));
+  for (int k = 0; k < v.nf; ++k) {
+    HIPCHK(hipMalloc(F.slot[k], (size_t)nc * v.f[k].n * v.f[k].bytes));
+    v.f[k].dict = *F.slot[k];
   }
-  CHECK(dalloc(ctx, &d->scol, (int64_t)nc * m, false));
-  CHECK(dalloc(ctx, &d->dblk, (int64_t)nc * m * m, false));
-  CHECK(dalloc(ctx, &d->lf, (int64_t)nc * m * v.lfw, false));
-  v.dict = DictArrays{d->bsym, d->qrow, d->qmir, d->dup, d->scol, d->dblk, d->lf, d->corr};
   Flags bad;
   CHECK(bad.init(ctx, 1));
-  LAUNCH(dict_assign_kernel, ne, v, nc, (const unsigned long long*)sorted.as<unsigned long long>(), d->cls,
+  LAUNCH(dict_assign_kernel, ne, v, nc, (const unsigned long long*)sorted.as<unsigned long long>(), *cls,
          rep.as<unsigned long long>(), bad.d);
   LAUNCH(dict_gather_kernel, nc, v, nc, (const unsigned long long*)rep.as<unsigned long long>());
   // every element's record against its class's, bit for bit: two records of one hash leave the level on the plain path
-  LAUNCH(dict_verify_kernel, ne, v, (const uint16_t*)d->cls, bad.d);
+  LAUNCH(dict_verify_kernel, ne, v, (const uint16_t*)*cls, bad.d);
   int b1 = 0;
   CHECK(bad.read(ctx, &b1));
-  if (b1) return AGGMG_OK;
-  *out = std::move(d);
+  if (!b1) *nclasses = nc;
+  return AGGMG_OK;
+}
+}  // namespace
+
+int setup_op_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, std::unique_ptr<DictDev>* out) {
+  out->reset();
+  const int m = b.m;
+  // the levels of btd_fused_kernel<M, CMP, ., SYM, ...> with M = 2, 4 whose transfer has two modes on equal agglomerates
+  if (!(b.cmp && b.bsym && (m == 2 || m == 4) && b.scol && b.dblk && b.qrow)) return AGGMG_OK;
+  if (!(t.rho > 0 && t.mc == 2 && t.lf) || b.ne < 1) return AGGMG_OK;
+  const int T = m * (m + 1) / 2;
+  auto d = std::make_unique<DictDev>();
+  d->lf_unit = t.lf1 != nullptr;
+  // the record: bsym[e] (T), qrow[e] (m), the mirror qrow[e-1] (m; zeros at e = 0), dup[e] (T) and corr (m words) where
+  // the level has the symmetric residual form, the escape sources scol[e] (m) and dblk[e] (m*m), and the element's rows
+  // of the transfer (lf1, or the two-entry rows of lf); the dictionary keeps the mirror in an array of its own (qmir)
+  DictFields F(b.ne);
+  F.add(b.bsym, &d->bsym, T);
+  F.add(b.qrow, &d->qrow, m);
+  F.add(b.qrow, &d->qmir, m, true);
+  if (b.dup) {
+    F.add(b.dup, &d->dup, T);
+    F.add(b.corr, &d->corr, m);
+  }
+  F.add(b.scol, &d->scol, m);
+  F.add(b.dblk, &d->dblk, m * m);
+  F.add(t.lf1 ? t.lf1 : t.lf, &d->lf, m * (t.lf1 ? 1 : 2));
+  CHECK(dict_build(ctx, F, &d->cls, &d->nclasses));
+  if (d->nclasses > 0) *out = std::move(d);
+  return AGGMG_OK;
+}
+
+int setup_cgt_dictionary(aggmg_ctx* ctx, const CgtDev& g, const TransferCgt& t, std::unique_ptr<CgtDictDev>* out) {
+  out->reset();
+  const int m = g.m;
+  // the levels of cgt_fused_kernel<M, ., ., 0, false, DICT = true>: blocks of 1, 2 or 4 rows, point-Jacobi sweeps
+  if (!((m == 1 || m == 2 || m == 4) && g.sw == 0 && g.dblk && g.subrow && g.supcol) || g.ne < 1) return AGGMG_OK;
+  if (!((t.type == kTrChain && t.l) || (t.type == kTrAgg && t.l && t.lp && t.rho >= 1)) || t.mc < 1) return AGGMG_OK;
+  auto d = std::make_unique<CgtDictDev>();
+  // the record of block e (the trailing identity-padded one is a block like any other): its rows of dblk (m*m), subrow
+  // (m) and supcol (m), and its rows of the transfer -- l[e m + i][mc + 1] (chain), or l[e m + i][mc] and lp[e][mc]
+  DictFields F(g.ne);
+  F.add(g.dblk, &d->dblk, m * m);
+  F.add(g.subrow, &d->subrow, m);
+  F.add(g.supcol, &d->supcol, m);
+  if (t.type == kTrChain) {
+    F.add(t.l, &d->l, m * (t.mc + 1));
+  } else {
+    F.add(t.l, &d->l, m * t.mc);
+    F.add(t.lp, &d->lp, t.mc);
+  }
+  CHECK(dict_build(ctx, F, &d->cls, &d->nclasses));
+  if (d->nclasses > 0) *out = std::move(d);
   return AGGMG_OK;
 }
 

@@ -525,53 +525,51 @@ __global__ __launch_bounds__(kSetupThreads) void btd_sym_residual_kernel(int64_t
 }
 
 // ------------------------------------------------------------------------------------------
-// operator dictionary of a symmetric-packed compressed level (BtdLevel::cls, btd_fused_kernel<..., DICT = true>)
+// operator dictionary of a fused level (BtdLevel::cls, btd_fused_kernel<..., DICT = true>; CgtArgs::cls,
+// cgt_fused_kernel<..., DICT = true>)
 // ------------------------------------------------------------------------------------------
 // The record of element e: every operator word the fused kernel reads on behalf of e, as 64-bit patterns in one fixed
-// order -- bsym[e] (T), qrow[e] (m), the mirror qrow[e-1] (m; zeros at e = 0), dup[e] (T) and corr (m words) where the
-// level has the symmetric residual form, the escape sources scol[e] (m) and dblk[e] (m*m), and the element's rows of
-// the transfer (m * lfw: lf1, or the two-entry rows of lf).  `full` holds the level's arrays, `dict` the dictionary's
-// ([nclasses][...], the same layouts; qmir is the mirror's own array there).
+// order.  The set-up routine lists the record's arrays (setup.hip: setup_op_dictionary, setup_cgt_dictionary), each one a
+// DictField: `n` words per element at full[e * n ...], 8 bytes (fp64 patterns) or 4 (uint32) each; `back`: the words of
+// element e - 1 instead (zeros at e = 0: the mirror of a symmetric-packed level).  `dict` is the dictionary's copy,
+// [nclasses][n].  The search below knows nothing else about a level.
 constexpr int kDictMaxClasses = 1024;   // distinct records a level may have and still take the form (dictionary < 0.5 MB)
 constexpr int kDictSlots = 4096;        // open-addressed table of the records' hashes during the search (a power of two)
-struct DictArrays {
-  double *bsym, *qrow, *qmir, *dup, *scol, *dblk, *lf;
-  uint32_t* corr;
+constexpr int kDictMaxFields = 8;
+struct DictField {
+  const void* full;
+  void* dict;
+  int n, bytes, back;
 };
 struct DictView {
-  DictArrays full, dict;   // (full.qmir unused: the mirror is qrow[e - 1])
+  DictField f[kDictMaxFields];
+  int nf;
   int64_t ne;
-  int m, lfw;
 };
 // f(array k, word j of the element's part of it, the bits) over the record of element e, in the record's order
 template <class F>
 __device__ __forceinline__ void dict_record(const DictView& v, int64_t e, F&& f) {
-  const DictArrays& a = v.full;
-  const int m = v.m, T = m * (m + 1) / 2;
-  auto bits = [](double x) { return (unsigned long long)__double_as_longlong(x); };
-  for (int j = 0; j < T; ++j) f(0, j, bits(a.bsym[e * T + j]));
-  for (int j = 0; j < m; ++j) f(1, j, bits(a.qrow[e * m + j]));
-  for (int j = 0; j < m; ++j) f(2, j, e > 0 ? bits(a.qrow[(e - 1) * m + j]) : 0ull);
-  if (a.dup) {
-    for (int j = 0; j < T; ++j) f(3, j, bits(a.dup[e * T + j]));
-    for (int j = 0; j < m; ++j) f(4, j, (unsigned long long)a.corr[e * m + j]);
+  for (int k = 0; k < v.nf; ++k) {
+    const DictField& a = v.f[k];
+    const int64_t at = (a.back ? e - 1 : e) * a.n;
+    for (int j = 0; j < a.n; ++j) {
+      unsigned long long w = 0ull;
+      if (at >= 0)
+        w = a.bytes == 4 ? (unsigned long long)static_cast<const uint32_t*>(a.full)[at + j]
+                         : static_cast<const unsigned long long*>(a.full)[at + j];
+      f(k, j, w);
+    }
   }
-  for (int j = 0; j < m; ++j) f(5, j, bits(a.scol[e * m + j]));
-  for (int j = 0; j < m * m; ++j) f(6, j, bits(a.dblk[e * m * m + j]));
-  for (int j = 0; j < m * v.lfw; ++j) f(7, j, bits(a.lf[e * m * v.lfw + j]));
 }
 // word (k, j) of class c's record in the dictionary: stored (store) or compared -- true when it holds w afterwards
 __device__ __forceinline__ bool dict_word(const DictView& v, int64_t c, int k, int j, unsigned long long w, bool store) {
-  const DictArrays& d = v.dict;
-  const int m = v.m, T = m * (m + 1) / 2;
-  if (k == 4) {
-    uint32_t* p = d.corr + c * m + j;
+  const DictField& a = v.f[k];
+  if (a.bytes == 4) {
+    uint32_t* p = static_cast<uint32_t*>(a.dict) + c * a.n + j;
     if (store) *p = (uint32_t)w;
     return *p == (uint32_t)w;
   }
-  double* p = k == 0 ? d.bsym + c * T : k == 1 ? d.qrow + c * m : k == 2 ? d.qmir + c * m : k == 3 ? d.dup + c * T
-            : k == 5 ? d.scol + c * m : k == 6 ? d.dblk + c * m * m : d.lf + c * m * v.lfw;
-  unsigned long long* q = reinterpret_cast<unsigned long long*>(p + j);
+  unsigned long long* q = static_cast<unsigned long long*>(a.dict) + c * a.n + j;
   if (store) *q = w;
   return *q == w;
 }

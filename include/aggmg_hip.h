@@ -104,8 +104,15 @@ int aggmg_synchronize(aggmg_ctx* ctx);
  * K-column, two-level or partitioned ones) then index the operator by the element's class: the same bits from a table
  * that stays in cache, so every result is bit for bit that of the full arrays, which stay allocated.  Every element's
  * record is compared against its class's at set-up; a level with more classes, or a mismatch, keeps the plain path.
+ * Fused CG chain levels take the same form: blocks of 1, 2 or 4 rows with point-Jacobi sweeps and a chain or an
+ * agglomerating transfer; the record of a block is its rows of the diagonal block, its sub-diagonal row, its
+ * super-diagonal column and its rows of the transfer (the trailing identity-padded block is a block like any other).
+ * The point-Jacobi launches of a cycle on such a level -- descent, ascent, the launch between two cycles, every chunk
+ * when the sweeps are split over several launches, the partitioned cycle's local levels included -- index operator and
+ * transfer by the block's class.  Checkpoint launches, element Schwarz and element Gauss-Seidel levels, other block
+ * sizes, the K-column launches and the operator-level entries (aggmg_smooth, aggmg_residual) keep the full arrays.
  * Hierarchies created afterwards; aggmg_hier_level_dictionary reports the levels.  aggmg_hier_launch_bytes keeps
- * counting the full arrays. */
+ * counting the full arrays (DESIGN.md sections 4 and 5). */
 #define AGGMG_OPT_OPERATOR_DICTIONARY 7
 int aggmg_set_option(aggmg_ctx* ctx, int option, int value);
 /* Raw device memory owned by the context's device (plumbing for harnesses without torch, and the storage of the
