@@ -100,6 +100,7 @@ SYMBOLS = {
     "aggmg_op_transpose": (c_int, [_P, _P, c_int, POINTER(_P)]),
     "aggmg_op_download_csc": (c_int, [_P, _P, POINTER(c_int32), POINTER(c_int32), _PD]),
     "aggmg_smoother_download_blocks": (c_int, [_P, _P, _PD]),
+    "aggmg_debug_device_memory": (c_int, [POINTER(c_int64), POINTER(c_int64)]),
     "aggmg_debug_scan_counts": (c_int, [_P, POINTER(c_int32), c_int64, POINTER(c_int64)]),
     "aggmg_debug_stream_copy": (c_int, [_P, _P, _P, c_int64, c_int, c_int, POINTER(c_double)]),
     "aggmg_blockjacobi_setup": (c_int, [_P, _P, c_int64, c_int64, POINTER(c_int64), c_int, c_int,

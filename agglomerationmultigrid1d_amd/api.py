@@ -43,6 +43,14 @@ def _pd(a):
     return a.ctypes.data_as(_PD)
 
 
+def device_memory():
+    """(live allocations, live bytes) of device memory the library holds in this process (C ABI
+    aggmg_debug_device_memory): what its handles and contexts own, not DeviceVector / DeviceMatrix storage.  Test aid."""
+    n, b = ctypes.c_int64(), ctypes.c_int64()
+    check(_lib.load().aggmg_debug_device_memory(ctypes.byref(n), ctypes.byref(b)), None)
+    return n.value, b.value
+
+
 # --------------------------------------------------------------------------------------------
 # context
 # --------------------------------------------------------------------------------------------

@@ -15,6 +15,12 @@
 // ---------------------------------------------------------------------------------------------
 extern "C" const char* aggmg_version(void) { return "aggmg_hip 0.1 gfx950 fp64"; }
 
+extern "C" int aggmg_debug_device_memory(int64_t* live_allocations, int64_t* live_bytes) {
+  if (live_allocations) *live_allocations = DevMemLive::allocations.load();
+  if (live_bytes) *live_bytes = DevMemLive::bytes.load();
+  return AGGMG_OK;
+}
+
 extern "C" int aggmg_create(int device_id, aggmg_ctx** out) {
   if (!out) return fail(nullptr, AGGMG_ERR_ARGUMENT, "aggmg_create: out is NULL");
   *out = nullptr;
@@ -48,16 +54,6 @@ extern "C" int aggmg_destroy(aggmg_ctx* ctx) {
     (void)hipEventDestroy(pe.b);
   }
   for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
-  for (int s = 0; s < 3; ++s)
-    if (ctx->scratch[s]) (void)hipFree(ctx->scratch[s]);
-  for (int s = 0; s < 5; ++s)
-    if (ctx->solv[s]) (void)hipFree(ctx->solv[s]);
-  if (ctx->solv_part) (void)hipFree(ctx->solv_part);
-  if (ctx->solv_sc) (void)hipFree(ctx->solv_sc);
-  if (ctx->cols_part) (void)hipFree(ctx->cols_part);
-  if (ctx->cols_sc) (void)hipFree(ctx->cols_sc);
-  if (ctx->cols_map) (void)hipFree(ctx->cols_map);
-  if (ctx->own_part) (void)hipFree(ctx->own_part);
   for (auto& L : ctx->stage) {
     for (int k = 0; k < 2; ++k) {
       if (L.ev[k]) (void)hipEventDestroy(L.ev[k]);
@@ -70,7 +66,7 @@ extern "C" int aggmg_destroy(aggmg_ctx* ctx) {
     else (void)hipHostUnregister(r.base);
   }
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-  delete ctx;
+  delete ctx;   // frees the context's device work space
   return AGGMG_OK;
 }
 
@@ -371,17 +367,14 @@ extern "C" int aggmg_blockdiag_setup(aggmg_ctx* ctx, int64_t m, int64_t nb, cons
   sm->contiguous = true;
   std::vector<int32_t> inds((size_t)nb * m);
   for (int64_t i = 0; i < nb * m; ++i) inds[i] = (int32_t)i;
-  CHECK(dev_upload(ctx, inds, &sm->inds));
-  const size_t bytes = (size_t)std::max<int64_t>(nb * m * m, 1) * sizeof(double);
-  HIPCHK(hipMalloc((void**)&sm->binv, bytes));
+  CHECK(sm->inds.upload(ctx, inds));
+  CHECK(sm->binv.alloc(ctx, nb * m * m));
   if (factorize) {
-    double* raw = nullptr;  // the column-major blocks as given; inverted on the device (K6)
-    HIPCHK(hipMalloc((void**)&raw, bytes));
+    DevArray<double> raw;  // the column-major blocks as given; inverted on the device (K6)
+    CHECK(raw.alloc(ctx, nb * m * m));
     if (nb) HIPCHK(hipMemcpyAsync(raw, blocks, (size_t)nb * m * m * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     int64_t sing = -1;
-    const int st = setup_invert_blocks(ctx, nb, (int)m, raw, 1, sm->binv, &sing);
-    (void)hipFree(raw);
-    CHECK(st);
+    CHECK(setup_invert_blocks(ctx, nb, (int)m, raw, 1, sm->binv, &sing));
     if (sing >= 0)
       return fail(ctx, AGGMG_ERR_SINGULAR, "aggmg_blockdiag_setup: singular block " + std::to_string(sing + 1) + " (SingularException)");
   } else {
@@ -1025,16 +1018,13 @@ extern "C" int aggmg_prolong_add_dev(aggmg_ctx* ctx, aggmg_op* L, const double* 
 // ---------------------------------------------------------------------------------------------
 struct DevVec {
   aggmg_ctx* ctx;
-  double* p = nullptr;
+  DevArray<double> p;
   explicit DevVec(aggmg_ctx* c) : ctx(c) {}
   ~DevVec() {
-    if (p) {
-      (void)hipStreamSynchronize(ctx->stream);
-      (void)hipFree(p);
-    }
+    if (p) (void)hipStreamSynchronize(ctx->stream);   // a launch may still read it
   }
   int alloc(int64_t n, const double* host) {
-    HIPCHK(hipMalloc((void**)&p, (size_t)std::max<int64_t>(n, 1) * sizeof(double)));
+    CHECK(p.alloc(ctx, n));
     if (host && n) HIPCHK(hipMemcpyAsync(p, host, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     return AGGMG_OK;
   }
@@ -1386,10 +1376,7 @@ static int cr_solve_t(aggmg_ctx* ctx, CrDev& cr, const double* rhs, double* out)
   const bool direct = (Npad == cr.N) && rhs != out;
   if (direct) return cr_solve_from<M>(ctx, cr, 0, rhs, nullptr, out);
   if (!cr.d0) {  // in-place call on an unpadded system: staging vectors on first use
-    for (double** p : {&cr.d0, &cr.x0}) {
-      HIPCHK(hipMalloc((void**)p, Npad * sizeof(double)));
-      cr.owned.push_back(*p);
-    }
+    for (DevArray<double>* p : {&cr.d0, &cr.x0}) CHECK(p->alloc(ctx, Npad));
   }
   double *d0 = cr.d0, *x0 = cr.x0;
   if (Npad > cr.N) HIPCHK(hipMemsetAsync(d0 + cr.N, 0, (Npad - cr.N) * sizeof(double), ctx->stream));
@@ -1500,24 +1487,16 @@ static int cr_multi_workspace(aggmg_ctx* ctx, aggmg_hier* h, int64_t cols, bool 
   const CrDev& cr = h->cr;
   if (h->crw_cols < cols) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (h->crw) HIPCHK(hipFree(h->crw));
-    h->crw = nullptr;
     h->crw_cols = 0;
     std::vector<CrMultiStage> st;
     CrMultiStage tail;
-    const size_t bytes = (size_t)std::max<int64_t>(cr_multi_layout(cr, cols, &st, &tail), 1) * sizeof(double);
-    HIPCHK(hipMalloc((void**)&h->crw, bytes));
-    HIPCHK(hipMemsetAsync(h->crw, 0, bytes, ctx->stream));   // (partL[0] of every column is never written: stays zero)
+    CHECK(h->crw.alloc(ctx, cr_multi_layout(cr, cols, &st, &tail), true));   // (partL[0] of every column is never written: stays zero)
     h->crw_cols = cols;
   }
   if (staging && h->crw_stage_cols < cols) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (h->crw_stage) HIPCHK(hipFree(h->crw_stage));
-    h->crw_stage = nullptr;
     h->crw_stage_cols = 0;
-    const size_t bytes = (size_t)(2 * cols * cr_even(cr.n0 * cr.m)) * sizeof(double);
-    HIPCHK(hipMalloc((void**)&h->crw_stage, bytes));
-    HIPCHK(hipMemsetAsync(h->crw_stage, 0, bytes, ctx->stream));   // (the pad rows of d0 are never written: stay zero)
+    CHECK(h->crw_stage.alloc(ctx, 2 * cols * cr_even(cr.n0 * cr.m), true));   // (the pad rows of d0 are never written: stay zero)
     h->crw_stage_cols = cols;
   }
   return AGGMG_OK;
@@ -1664,10 +1643,7 @@ extern "C" int aggmg_hier_create(aggmg_ctx* ctx, int nlevels, aggmg_op* const* s
       if (l.L->kind != AGGMG_OP_TRANSFER) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_create: interpolation must be uploaded with AGGMG_OP_TRANSFER");
       if (l.S->cgt && l.S->A == l.A) l.Nalloc = std::max(l.N, l.S->cgt->ne * l.S->cgt->m);  // block order incl. padding
     }
-    for (double** p : {&l.u[0], &l.u[1], &l.rhs, &l.tmp}) {
-      HIPCHK(hipMalloc((void**)p, (size_t)std::max<int64_t>(l.Nalloc, 1) * sizeof(double)));
-      HIPCHK(hipMemsetAsync(*p, 0, (size_t)std::max<int64_t>(l.Nalloc, 1) * sizeof(double), ctx->stream));
-    }
+    for (DevArray<double>* p : {&l.u[0], &l.u[1], &l.rhs, &l.tmp}) CHECK(p->alloc(ctx, l.Nalloc, true));
   }
   // structured transfers between consecutive levels whose fine side runs the fused kernel
   for (int k = 0; k + 1 < nlevels; ++k) {
@@ -1733,7 +1709,7 @@ extern "C" int aggmg_hier_create(aggmg_ctx* ctx, int nlevels, aggmg_op* const* s
           CHECK(aggmg_norm2_dev(ctx, lc.rhs, Nc, &nd));
           CHECK(aggmg_norm2_dev(ctx, lc.tmp, Nc, &nr));
           h->cr_probe_backward_error = nd > 0.0 ? nr / nd : 0.0;
-          for (double* p : {lc.u[0], lc.u[1], lc.rhs, lc.tmp}) HIPCHK(hipMemsetAsync(p, 0, (size_t)lc.Nalloc * sizeof(double), ctx->stream));
+          for (double* p : {lc.u[0].get(), lc.u[1].get(), lc.rhs.get(), lc.tmp.get()}) HIPCHK(hipMemsetAsync(p, 0, (size_t)lc.Nalloc * sizeof(double), ctx->stream));
           return AGGMG_OK;
         };
         CHECK(probe_once());
@@ -1769,7 +1745,7 @@ extern "C" int aggmg_hier_create(aggmg_ctx* ctx, int nlevels, aggmg_op* const* s
           h->cr.pcr.valid = false;
           CHECK(smooth_residual(&rc));
           h->cr.pcr.valid = rp <= 8.0 * rc + 1e-15;   // (NaN: false)
-          for (double* p : {lc.u[0], lc.u[1], lc.rhs, lc.tmp}) HIPCHK(hipMemsetAsync(p, 0, (size_t)lc.Nalloc * sizeof(double), ctx->stream));
+          for (double* p : {lc.u[0].get(), lc.u[1].get(), lc.rhs.get(), lc.tmp.get()}) HIPCHK(hipMemsetAsync(p, 0, (size_t)lc.Nalloc * sizeof(double), ctx->stream));
         }
       }
       if (!h->cr.valid && coarse_mode == AGGMG_COARSE_DEVICE_CR)
@@ -2221,20 +2197,16 @@ static int multi_workspace(aggmg_ctx* ctx, aggmg_hier* h, int64_t cols) {
   if (h->multi_cols >= cols && !h->mu.empty()) return AGGMG_OK;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   for (auto& m : h->mu)
-    for (double*& p : m) {
-      if (p) HIPCHK(hipFree(p));
-      p = nullptr;
-    }
+    for (auto& p : m) CHECK(p.reset(ctx));
   h->multi_cols = 0;
   const int n = (int)h->lv.size();
-  h->mu.assign(n, {nullptr, nullptr, nullptr});
+  h->mu.resize(n);
   for (int k = 0; k < n; ++k) {
-    const size_t bytes = (size_t)std::max<int64_t>(h->lv[k].N * cols, 1) * sizeof(double);
     const bool coarsest = k == n - 1;
     for (int s = 0; s < 3; ++s) {
       if (s == 1 && (k == 0 || coarsest)) continue;   // the ascent's output: the caller's X at level 0, none at the coarsest
       if (s == 2 && k == 0) continue;                 // level 0's right-hand side is the caller's B
-      HIPCHK(hipMalloc((void**)&h->mu[k][s], bytes));
+      CHECK(h->mu[k][s].alloc(ctx, h->lv[k].N * cols));
     }
   }
   h->multi_cols = cols;
@@ -2500,8 +2472,8 @@ extern "C" int aggmg_vcycles_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0
     return cycle_loop(FineLevel{ctx, h, b, nPre, nPost, alpha, chain}, x0, ncycles, x_out, 0, nullptr, nullptr);
   // plain sequence; intermediate iterates ping-pong between two vectors owned by the hierarchy
   if (ncycles > 1)
-    for (double*& p : h->cyc)
-      if (!p) HIPCHK(hipMalloc((void**)&p, (size_t)std::max<int64_t>(l0.N, 1) * sizeof(double)));
+    for (auto& p : h->cyc)
+      if (!p) CHECK(p.alloc(ctx, l0.N));
   const double* src = x0;
   for (int c = 0; c < ncycles; ++c) {
     double* dst = (c == ncycles - 1) ? x_out : h->cyc[c & 1];
@@ -2752,8 +2724,8 @@ extern "C" int aggmg_vcycle(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, con
   const int64_t N = h->lv[0].N;
   const size_t bytes = (size_t)N * sizeof(double);
   // the three device vectors of the host-pointer entry live with the hierarchy (no allocation per call)
-  for (double*& p : h->io)
-    if (!p) HIPCHK(hipMalloc((void**)&p, std::max<size_t>(bytes, 8)));
+  for (auto& p : h->io)
+    if (!p) CHECK(p.alloc(ctx, N));
   if (x0) {
     double* dv[2] = {h->io[0], h->io[1]};
     double* hv[2] = {const_cast<double*>(x0), const_cast<double*>(b)};
@@ -2993,23 +2965,14 @@ extern "C" int aggmg_hier_last_coarse_ms(aggmg_ctx* ctx, const aggmg_hier* h, do
 // the iterate, and ldiv! (src/solvers.jl:63-92) as the preconditioner of a conjugate-gradient loop
 // ---------------------------------------------------------------------------------------------
 static int solv_vec(aggmg_ctx* ctx, int slot, int64_t len, double** out) {
-  if (ctx->solv_len[slot] < len) {
-    if (ctx->solv[slot]) {
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      HIPCHK(hipFree(ctx->solv[slot]));
-    }
-    ctx->solv[slot] = nullptr;
-    ctx->solv_len[slot] = 0;
-    HIPCHK(hipMalloc((void**)&ctx->solv[slot], (size_t)std::max<int64_t>(len, 1) * sizeof(double)));
-    ctx->solv_len[slot] = len;
-  }
+  CHECK(ctx->solv[slot].reserve(ctx, len));
   *out = ctx->solv[slot];
   return AGGMG_OK;
 }
 
 static int solv_scalars(aggmg_ctx* ctx) {
-  if (!ctx->solv_part) HIPCHK(hipMalloc((void**)&ctx->solv_part, kDotBlocks * sizeof(double)));
-  if (!ctx->solv_sc) HIPCHK(hipMalloc((void**)&ctx->solv_sc, 48 * sizeof(double)));   // [16 .. 47]: checkpoint norms of a launch
+  if (!ctx->solv_part) CHECK(ctx->solv_part.alloc(ctx, kDotBlocks));
+  if (!ctx->solv_sc) CHECK(ctx->solv_sc.alloc(ctx, 48));   // [16 .. 47]: checkpoint norms of a launch
   return AGGMG_OK;
 }
 
@@ -3354,15 +3317,10 @@ static int cols_scalars(aggmg_ctx* ctx, int64_t K) {
   CHECK(solv_scalars(ctx));
   if (ctx->cols_cap >= K) return AGGMG_OK;
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (ctx->cols_part) HIPCHK(hipFree(ctx->cols_part));
-  if (ctx->cols_sc) HIPCHK(hipFree(ctx->cols_sc));
-  if (ctx->cols_map) HIPCHK(hipFree(ctx->cols_map));
-  ctx->cols_part = ctx->cols_sc = nullptr;
-  ctx->cols_map = nullptr;
   ctx->cols_cap = 0;
-  HIPCHK(hipMalloc((void**)&ctx->cols_part, (size_t)K * kDotBlocks * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&ctx->cols_sc, (size_t)K * kColsScalars * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&ctx->cols_map, (size_t)K * sizeof(int)));
+  CHECK(ctx->cols_part.alloc(ctx, K * kDotBlocks));
+  CHECK(ctx->cols_sc.alloc(ctx, K * kColsScalars));
+  CHECK(ctx->cols_map.alloc(ctx, K));
   ctx->cols_cap = K;
   return AGGMG_OK;
 }

@@ -102,20 +102,6 @@ __global__ __launch_bounds__(kThreads) void loopback_kernel(const double* __rest
 
 }  // namespace
 
-struct DevBuf {
-  double* p = nullptr;
-  int64_t n = 0;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(aggmg_ctx* ctx, int64_t len) {
-    n = len;
-    HIPCHK(hipMalloc((void**)&p, (size_t)std::max<int64_t>(len, 1) * sizeof(double)));
-    HIPCHK(hipMemsetAsync(p, 0, (size_t)std::max<int64_t>(len, 1) * sizeof(double), ctx->stream));
-    return AGGMG_OK;
-  }
-};
-
 // which entries of a local level vector travel in an interface exchange: `send` packs slices of the vector
 // into this rank's part of the all-gather (count doubles per rank), `left` / `right` unpack slices of the
 // left / right neighbour's part into the ghost entries
@@ -143,15 +129,15 @@ struct aggmg_dist {
   int world = 1, rank = 0, nl = 0;
   std::vector<int64_t> own_lo, own_hi, loc_lo, loc_hi, ne;
   std::vector<int> m, W;
-  DevBuf send[2], recv[2];  // [0]: finest level, [1]: coarsest level ghosts
+  DevArray<double> send[2], recv[2];  // [0]: finest level, [1]: coarsest level ghosts
   ExLayout ex[2];
   NbLayout nb[2];
   bool p2p = true;          // neighbour messages where the backend has them (AGGMG_DIST_P2P=0: all-gathers only)
-  DevBuf rhs_g, sol_g, zero_g;
+  DevArray<double> rhs_g, sol_g, zero_g;
   bool chunked = false;
   int q = 0;
   int64_t nq = 0, cnt = 0;
-  DevBuf zbuf, xq;          // chunk-interleaved boundary rows (one pad block in front), boundary solution
+  DevArray<double> zbuf, xq;          // chunk-interleaved boundary rows (one pad block in front), boundary solution
   // collectives
   int backend = 0;  // 0 none, 1 callback, 2 RCCL, 3 loop-back
   aggmg_allgather_fn fn = nullptr;
@@ -376,9 +362,9 @@ static int exchange_ghosts(aggmg_ctx* ctx, aggmg_dist* d, double* x, int level) 
   const int slot = level == 0 ? 0 : 1;
   if (d->world == 1 || d->ex[slot].count == 0) return AGGMG_OK;
   if (use_p2p(d, slot)) return neighbor_exchange(ctx, d, x, slot);
-  CHECK(pack_interface(ctx, d, x, level, d->send[slot].p));
-  CHECK(dist_allgather(ctx, d, d->send[slot].p, d->recv[slot].p, d->ex[slot].count));
-  return unpack_ghosts(ctx, d, x, level, d->recv[slot].p);
+  CHECK(pack_interface(ctx, d, x, level, d->send[slot]));
+  CHECK(dist_allgather(ctx, d, d->send[slot], d->recv[slot], d->ex[slot].count));
+  return unpack_ghosts(ctx, d, x, level, d->recv[slot]);
 }
 
 extern "C" int aggmg_dist_create(aggmg_ctx* ctx, aggmg_hier* local, aggmg_hier* coarse_global, int world, int rank,
@@ -423,17 +409,17 @@ extern "C" int aggmg_dist_create(aggmg_ctx* ctx, aggmg_hier* local, aggmg_hier* 
     const int lev = s == 0 ? 0 : nc;
     d->ex[s] = contiguous_layout(d.get(), lev);
     d->nb[s] = contiguous_neighbors(d.get(), lev);
-    CHECK(d->send[s].alloc(ctx, d->ex[s].count));
-    CHECK(d->recv[s].alloc(ctx, d->ex[s].count * world));
+    CHECK(d->send[s].alloc(ctx, d->ex[s].count, true));
+    CHECK(d->recv[s].alloc(ctx, d->ex[s].count * world, true));
   }
   {
     const char* e = getenv("AGGMG_DIST_P2P");
     d->p2p = !(e && e[0] == '0');
   }
   const int64_t Ng = ne[nc] * m[nc];
-  CHECK(d->rhs_g.alloc(ctx, Ng));
-  CHECK(d->sol_g.alloc(ctx, Ng));
-  CHECK(d->zero_g.alloc(ctx, Ng));
+  CHECK(d->rhs_g.alloc(ctx, Ng, true));
+  CHECK(d->sol_g.alloc(ctx, Ng, true));
+  CHECK(d->zero_g.alloc(ctx, Ng, true));
   // chunked coarsest solve when the replicated solver has a chunk plan that the partition respects
   if (world > 1) {
     int q = -1, mblk = 0;
@@ -454,8 +440,8 @@ extern "C" int aggmg_dist_create(aggmg_ctx* ctx, aggmg_hier* local, aggmg_hier* 
       d->q = q;
       d->nq = nq;
       d->cnt = (own_blk >> q) * mblk;
-      CHECK(d->zbuf.alloc(ctx, (nq + 2) * 2 * mblk));   // zeroed: the pad block in front stays zero
-      CHECK(d->xq.alloc(ctx, (nq + 1) * mblk));
+      CHECK(d->zbuf.alloc(ctx, (nq + 2) * 2 * mblk, true));   // zeroed: the pad block in front stays zero
+      CHECK(d->xq.alloc(ctx, (nq + 1) * mblk, true));
     }
   }
   HIPCHK(hipStreamCreateWithFlags(&d->side, hipStreamNonBlocking));
@@ -506,12 +492,8 @@ extern "C" int aggmg_dist_set_exchange_layout(aggmg_ctx* ctx, aggmg_dist* d, int
   HIPCHK(hipStreamSynchronize(ctx->stream));
   d->ex[slot] = L;
   d->nb[slot] = NbLayout();   // the contiguous default no longer describes this level: aggmg_dist_set_neighbor_layout
-  d->send[slot].~DevBuf();
-  new (&d->send[slot]) DevBuf();
-  d->recv[slot].~DevBuf();
-  new (&d->recv[slot]) DevBuf();
-  CHECK(d->send[slot].alloc(ctx, count));
-  CHECK(d->recv[slot].alloc(ctx, count * d->world));
+  CHECK(d->send[slot].alloc(ctx, count, true));
+  CHECK(d->recv[slot].alloc(ctx, count * d->world, true));
   for (auto& g : d->graphs)   // captured cycles refer to the old buffers
     if (g.exec) {
       (void)hipGraphExecDestroy(g.exec);
@@ -677,7 +659,7 @@ static int dist_vcycle_eager(aggmg_ctx* ctx, aggmg_dist* d, double* x0, const do
     // the exchange issued under the previous cycle's ascent (already joined to the main stream): use
     // it if it was for this x0
     if (d->pending == x0) {
-      if (!d->pending_in_place) CHECK(unpack_ghosts(ctx, d, x0, 0, d->recv[0].p));   // (neighbour messages landed in the ghosts)
+      if (!d->pending_in_place) CHECK(unpack_ghosts(ctx, d, x0, 0, d->recv[0]));   // (neighbour messages landed in the ghosts)
       ghosts_valid = true;
     }
     d->pending = nullptr;
@@ -696,11 +678,11 @@ static int dist_vcycle_eager(aggmg_ctx* ctx, aggmg_dist* d, double* x0, const do
     // the chunk kernels write their boundary rows chunk-interleaved at GLOBAL chunk positions of Z (one pad block
     // in front): this rank's chunks are the contiguous slice Z[clo .. clo + chunks), 2 cnt doubles, and the
     // all-gather runs in place -- no pack, no unpack, the boundary solve reads Z as it lies
-    double* Z = d->zbuf.p + 2 * mc;
+    double* Z = d->zbuf + 2 * mc;
     CHECK(coarse_chunk_forward_interleaved(ctx, d->Hc, own, blo, bhi, Z));
     CHECK(dist_allgather(ctx, d, Z + clo * 2 * mc, Z, 2 * cnt));
-    CHECK(coarse_boundary_solve_interleaved(ctx, d->Hc, Z, d->xq.p));
-    CHECK(aggmg_coarse_chunk_backward_dev(ctx, d->Hc, own, blo, bhi, d->xq.p, sol_c + gl * mc));
+    CHECK(coarse_boundary_solve_interleaved(ctx, d->Hc, Z, d->xq));
+    CHECK(aggmg_coarse_chunk_backward_dev(ctx, d->Hc, own, blo, bhi, d->xq, sol_c + gl * mc));
     // The neighbours' ghost blocks of the coarsest solution are read by the end tiles of the ascent only: the exchange
     // can go to the side stream and the tiles in between run under it (aggmg_dist_set_coarse_overlap; off by default:
     // with loop-back stand-ins the extra launch and the two stream joins cost 9 us against the 5 us copy they hide, a
@@ -727,10 +709,10 @@ static int dist_vcycle_eager(aggmg_ctx* ctx, aggmg_dist* d, double* x0, const do
       CHECK(exchange_ghosts(ctx, d, sol_c, nc));
     }
   } else {
-    CHECK(dist_allgather(ctx, d, own, d->rhs_g.p, own_c));
+    CHECK(dist_allgather(ctx, d, own, d->rhs_g, own_c));
     // a one-level hierarchy's V-cycle IS the coarsest direct solve (src/solvers.jl:39)
-    CHECK(aggmg_vcycle_dev(ctx, d->Hc, d->zero_g.p, d->rhs_g.p, 0, 0, 1.0, d->sol_g.p));
-    HIPCHK(hipMemcpyAsync(sol_c, d->sol_g.p + d->loc_lo[nc] * mc, (size_t)(d->loc_hi[nc] - d->loc_lo[nc]) * mc * sizeof(double),
+    CHECK(aggmg_vcycle_dev(ctx, d->Hc, d->zero_g, d->rhs_g, 0, 0, 1.0, d->sol_g));
+    HIPCHK(hipMemcpyAsync(sol_c, d->sol_g + d->loc_lo[nc] * mc, (size_t)(d->loc_hi[nc] - d->loc_lo[nc]) * mc * sizeof(double),
                           hipMemcpyDeviceToDevice, ctx->stream));
   }
   const bool overlap = (flags & AGGMG_DIST_OVERLAP_NEXT) && d->world > 1 && d->W[0] > 0;
@@ -750,9 +732,9 @@ static int dist_vcycle_eager(aggmg_ctx* ctx, aggmg_dist* d, double* x0, const do
         (void)hipEventRecord(d->ev_ends, d->side);
         // neighbour messages go from x_out's interface elements straight into the neighbours' ghost elements of
         // THEIR x_out (the middle tiles on the main stream write neither)
-        st = in_place ? neighbor_exchange(ctx, d, x_out, 0) : pack_interface(ctx, d, x_out, 0, d->send[0].p);
+        st = in_place ? neighbor_exchange(ctx, d, x_out, 0) : pack_interface(ctx, d, x_out, 0, d->send[0]);
       }
-      if (st == AGGMG_OK && !in_place) st = dist_allgather(ctx, d, d->send[0].p, d->recv[0].p, d->ex[0].count);
+      if (st == AGGMG_OK && !in_place) st = dist_allgather(ctx, d, d->send[0], d->recv[0], d->ex[0].count);
       (void)hipEventRecord(d->ev_side, d->side);
       ctx->stream = main;
       CHECK(st);
@@ -863,8 +845,7 @@ static int owned_ranges(aggmg_ctx* ctx, const char* who, int nranges, const int6
     R->lo[g] = lo[g];
     R->hi[g] = hi[g];
   }
-  if (!ctx->own_part)
-    HIPCHK(hipMalloc((void**)&ctx->own_part, (size_t)(kOwnedBlocks * kOwnedMaxRanges + 1) * sizeof(double)));
+  if (!ctx->own_part) CHECK(ctx->own_part.alloc(ctx, kOwnedBlocks * kOwnedMaxRanges + 1));
   return AGGMG_OK;
 }
 

@@ -1,6 +1,6 @@
 // Shared internals of libaggmg_hip: the objects behind the opaque handles of include/aggmg_hip.h
-// and the small host helpers every translation unit of the library uses (error reporting,
-// uploads, scratch vectors, the HIP-event profiler, the set-up thread pool).
+// and the small host helpers every translation unit of the library uses (error reporting, the
+// owner of device memory, scratch vectors, the HIP-event profiler, the set-up thread pool).
 #pragma once
 #include "../../include/aggmg_hip.h"
 
@@ -23,6 +23,29 @@
 #include "cgt_kernels.hpp"
 
 using namespace aggmg;
+
+// ---------------------------------------------------------------------------------------------
+// error helpers
+// ---------------------------------------------------------------------------------------------
+struct aggmg_ctx;
+inline int fail(aggmg_ctx* ctx, int code, const std::string& msg);   // (defined below the context)
+
+#define HIPCHK(expr)                                                                        \
+  do {                                                                                      \
+    hipError_t _e = (expr);                                                                 \
+    if (_e != hipSuccess)                                                                   \
+      return fail(ctx, AGGMG_ERR_HIP,                                                       \
+                  std::string(#expr) + ": " + hipGetErrorString(_e) + " (" + __FILE__ + ":" + \
+                      std::to_string(__LINE__) + ")");                                      \
+  } while (0)
+
+#define CHECK(expr)             \
+  do {                          \
+    int _s = (expr);            \
+    if (_s != AGGMG_OK) return _s; \
+  } while (0)
+
+#include "devmem.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // objects behind the opaque handles
@@ -50,24 +73,20 @@ struct aggmg_ctx {
   std::vector<ProfEvent> prof;
   std::vector<hipEvent_t> ev_pool;
   // scratch vectors for ping-pong / temporaries, grown on demand
-  double* scratch[3] = {nullptr, nullptr, nullptr};
-  int64_t scratch_len[3] = {0, 0, 0};
+  DevArray<double> scratch[3];
   // outer-solver work space (aggmg_multigrid_dev, aggmg_pcg_dev, ...): vectors, dot-product
   // partials and the device-resident scalars
-  double* solv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  int64_t solv_len[5] = {0, 0, 0, 0, 0};
-  double* solv_part = nullptr;
-  double* solv_sc = nullptr;
+  DevArray<double> solv[5];
+  DevArray<double> solv_part, solv_sc;
   // K-column solver loops (aggmg_pcg_multi_dev, aggmg_multigrid_multi_dev, aggmg_dot_cols_dev): for cols_cap columns,
   // kDotBlocks partials and kColsScalars scalars per column, and the slot -> column maps of the active set; lazy, grown
   // for more columns, freed with the context
-  double* cols_part = nullptr;
-  double* cols_sc = nullptr;
-  int* cols_map = nullptr;
+  DevArray<double> cols_part, cols_sc;
+  DevArray<int> cols_map;
   int64_t cols_cap = 0;
   // owned-range reductions of the partitioned conjugate-gradient loop (aggmg_owned_dot_dev, aggmg_pcg_xr_owned_dev):
   // kOwnedBlocks partial sums per range, then the scalar; lazy, freed with the context
-  double* own_part = nullptr;
+  DevArray<double> own_part;
   // host <-> device staging of the host-pointer entry points (aggmg_vcycle): per worker thread a stream and two
   // pinned chunks (HostStager in aggmg_hip.hip); allocated on first use
   struct StageLane {
@@ -87,15 +106,24 @@ struct aggmg_ctx {
   std::vector<Pinned> pinned;  // the lanes could not be allocated once: aggmg_vcycle keeps to plain hipMemcpy
 };
 
+inline int fail(aggmg_ctx* ctx, int code, const std::string& msg) {
+  if (ctx)
+    ctx->err = msg;
+  else
+    g_create_error = msg;
+  return code;
+}
+
+inline hipStream_t HipMem::stream_of(aggmg_ctx* ctx) { return ctx->stream; }
+
 struct CsrDev {
   int64_t nrows = 0, ncols = 0, nnz = 0;
-  int32_t* rowptr = nullptr;
-  int32_t* colind = nullptr;
-  double* vals = nullptr;
+  DevArray<int32_t> rowptr, colind;
+  DevArray<double> vals;
   int lpr = 1;
-  int32_t* rowblk = nullptr;  // CSR-stream row blocks (short-row matrices), nblk + 1 entries
+  DevArray<int32_t> rowblk;   // CSR-stream row blocks (short-row matrices), nblk + 1 entries
   int64_t nblk = 0;
-  int32_t* bandblk = nullptr; // CSR-band row blocks (square, entries within bw of the diagonal), nbandblk + 1 entries
+  DevArray<int32_t> bandblk;  // CSR-band row blocks (square, entries within bw of the diagonal), nbandblk + 1 entries
   int64_t nbandblk = 0;
   int band_sweeps = 1;        // most point-Jacobi sweeps a csr_band_kernel launch takes on this operator (the blocks' halo is cut for it)
   int bw = -1;                // band half-width, -1: not banded / not examined
@@ -116,18 +144,13 @@ struct BtdDev {
   int64_t ne = 0;
   bool cmp = false;
   int c_sub = 0, r_sup = 0;
-  double *binv = nullptr, *dblk = nullptr, *scol = nullptr, *pcol = nullptr, *qrow = nullptr;
-  double* bsym = nullptr;  // packed symmetric inverses (replaces binv + pcol in the kernels) or null
+  DevArray<double> binv, dblk, scol, pcol, qrow;
+  DevArray<double> bsym;   // packed symmetric inverses (replaces binv + pcol in the kernels) or null
   // lossless symmetric form of the explicit residual's entries (compressed couplings, m <= 4, with bsym): the upper
   // triangle of D_e row-owned, one word of int8 corrections per row (setup_kernels.hpp, btd_sym_residual_kernel); or null
-  double* dup = nullptr;
-  uint32_t* corr = nullptr;
-  double *sub = nullptr, *sup = nullptr, *P = nullptr, *Q = nullptr;
-  ~BtdDev() {
-    for (double* p : {binv, dblk, scol, pcol, qrow, bsym, dup, sub, sup, P, Q})
-      if (p) (void)hipFree(p);
-    if (corr) (void)hipFree(corr);
-  }
+  DevArray<double> dup;
+  DevArray<uint32_t> corr;
+  DevArray<double> sub, sup, P, Q;
 };
 
 // element-contiguous ("chain") form of a CG operator + its point-Jacobi smoother (cgt_kernels.hpp);
@@ -136,19 +159,15 @@ struct CgtDev {
   int m = 0;        // rows per block = p
   int64_t ne = 0;   // blocks = elements + 1 (the trailing one holds the last vertex, identity-padded)
   int64_t N = 0;    // DoFs of the operator; the block-ordered vectors have ne * m entries
-  double *dblk = nullptr, *subrow = nullptr, *supcol = nullptr;
-  int32_t* perm = nullptr;  // [ne*m] block order -> reference numbering, -1 = padding
-  int32_t* inv = nullptr;   // [N]    reference numbering -> block order
+  DevArray<double> dblk, subrow, supcol;
+  DevArray<int32_t> perm;   // [ne*m] block order -> reference numbering, -1 = padding
+  DevArray<int32_t> inv;    // [N]    reference numbering -> block order
   bool affine = false;      // perm is the reference's vertices-first numbering: the kernel computes it
   // element Schwarz smoothers on the chain (cg_smoother :addSchwarz / :hybridSchwarz): rows of the inverses of
   // the element blocks A[nodes_e, nodes_e] in chain-local order [block e, first row of block e + 1]
   int sw = 0;               // 0 point Jacobi, 1 additive Schwarz, 2 hybrid Schwarz
-  double* zrows = nullptr;  // [ne*m][m+1]  row i of element e's inverse at (e*m + i)
-  double* zlast = nullptr;  // [ne][m+1]    its last row (the right vertex) at e + 1: with the block that owns the vertex
-  ~CgtDev() {
-    for (void* p : {(void*)dblk, (void*)subrow, (void*)supcol, (void*)perm, (void*)inv, (void*)zrows, (void*)zlast})
-      if (p) (void)hipFree(p);
-  }
+  DevArray<double> zrows;   // [ne*m][m+1]  row i of element e's inverse at (e*m + i)
+  DevArray<double> zlast;   // [ne][m+1]    its last row (the right vertex) at e + 1: with the block that owns the vertex
 };
 
 struct aggmg_op {
@@ -158,54 +177,37 @@ struct aggmg_op {
   CsrDev csr;  // row-gather CSR of the matrix: transposed on the device on first use (generic kernels only)
   std::shared_ptr<BtdDev> btd;  // set when a block-Jacobi smoother recognised the structure
   std::shared_ptr<CgtDev> cgt;  // set when a point-Jacobi smoother was given the CG element chain
-  ~aggmg_op() {
-    for (CsrDev* d : {&csc, &csr})
-      for (void* p : {(void*)d->rowptr, (void*)d->colind, (void*)d->vals, (void*)d->rowblk, (void*)d->bandblk})
-        if (p) (void)hipFree(p);
-  }
 };
 
 struct aggmg_smoother {
   int kind = 0;  // 0 point Jacobi, 1 block (Jacobi / additive Schwarz), 2 hybrid Schwarz
   aggmg_op* A = nullptr;
   int64_t N = 0, m = 0, nb = 0;
-  double* diag = nullptr;      // point Jacobi
-  double* binv = nullptr;      // [nb][m][m] row-major
-  int32_t* inds = nullptr;     // [nb][m]
-  double* counts = nullptr;    // hybrid Schwarz
+  DevArray<double> diag;       // point Jacobi
+  DevArray<double> binv;       // [nb][m][m] row-major
+  DevArray<int32_t> inds;      // [nb][m]
+  DevArray<double> counts;     // hybrid Schwarz
   bool overlapping = false;
   bool contiguous = false;
   // which (block, local row) entries cover each row, flat index block * m + i ascending inside a row: built on first use
   // by the generic one-pass sweep (block_sweep_kernel + block_combine_kernel)
-  int32_t* cover_ptr = nullptr;   // [N + 1]
-  uint32_t* cover_idx = nullptr;  // [nb * m]
+  DevArray<int32_t> cover_ptr;    // [N + 1]
+  DevArray<uint32_t> cover_idx;   // [nb * m]
   bool ordered = false;           // the blocks have been put in ascending order of their smallest index (one-pass sweep)
   bool gs = false;  // red-black block Gauss-Seidel (extension): needs the structured form
   std::shared_ptr<BtdDev> btd;  // structured fused form, or null
   std::shared_ptr<CgtDev> cgt;  // CG chain form (point Jacobi with the element lists), or null
-  // owns its device arrays: every early return of a set-up routine releases what was uploaded
-  ~aggmg_smoother() {
-    for (void* p : {(void*)diag, (void*)binv, (void*)inds, (void*)counts, (void*)cover_ptr, (void*)cover_idx})
-      if (p) (void)hipFree(p);
-  }
 };
 
 struct TransferBtd {
   int mc = 0, rho = 0;   // rho: fine elements per coarse element; 0 = agglomerates of different sizes (parent / first)
   int64_t nec = 0;
-  double* lf = nullptr;  // [N_f][mc]  rows of L
-  double* lf1 = nullptr; // [N_f]      their second entries when mc == 2 and every first entry is exactly 1.0, else null
-  double* ld = nullptr;  // [N_f][mc]  rows of (L_e' D_e)': restriction of the preconditioned residual
-  int32_t* parent = nullptr;  // [ne_f]      coarse element of every fine element      (rho == 0)
-  int32_t* first = nullptr;   // [ne_c + 1]  first fine element of every coarse element (rho == 0)
+  DevArray<double> lf;   // [N_f][mc]  rows of L
+  DevArray<double> lf1;  // [N_f]      their second entries when mc == 2 and every first entry is exactly 1.0, else null
+  DevArray<double> ld;   // [N_f][mc]  rows of (L_e' D_e)': restriction of the preconditioned residual
+  DevArray<int32_t> parent;   // [ne_f]      coarse element of every fine element      (rho == 0)
+  DevArray<int32_t> first;    // [ne_c + 1]  first fine element of every coarse element (rho == 0)
   int maxagg = 0;             // fine elements of the largest agglomerate                 (rho == 0)
-  ~TransferBtd() {
-    if (lf) (void)hipFree(lf);
-    if (lf1) (void)hipFree(lf1);
-    if (ld) (void)hipFree(ld);
-    if (parent) (void)hipFree(parent);
-    if (first) (void)hipFree(first);
-  }
 };
 
 // operator dictionary of a fused level (AGGMG_OPT_OPERATOR_DICTIONARY; BtdLevel::cls in kernels.hpp, the dict_* kernels of
@@ -215,27 +217,19 @@ struct TransferBtd {
 // reads them.
 struct DictDev {
   int nclasses = 0;
-  uint16_t* cls = nullptr;   // [ne]
-  double *bsym = nullptr, *qrow = nullptr, *qmir = nullptr, *dup = nullptr, *scol = nullptr, *dblk = nullptr;
-  uint32_t* corr = nullptr;
-  double* lf = nullptr;      // [nclasses][m] second entries (the transfer has lf1), else [nclasses][m][2] rows of L
+  DevArray<uint16_t> cls;    // [ne]
+  DevArray<double> bsym, qrow, qmir, dup, scol, dblk;
+  DevArray<uint32_t> corr;
+  DevArray<double> lf;       // [nclasses][m] second entries (the transfer has lf1), else [nclasses][m][2] rows of L
   bool lf_unit = false;      // lf holds the lf1 form
-  ~DictDev() {
-    for (void* p : {(void*)cls, (void*)bsym, (void*)qrow, (void*)qmir, (void*)dup, (void*)scol, (void*)dblk, (void*)corr, (void*)lf})
-      if (p) (void)hipFree(p);
-  }
 };
 
 // structured transfer of a CG chain level (CgtXfer in cgt_kernels.hpp)
 struct TransferCgt {
   int type = 0, mc = 0, rho = 1;
   int64_t nec = 0;
-  double *l = nullptr, *lp = nullptr;
-  int32_t* cperm = nullptr;  // chain: coarse block order -> coarse reference numbering
-  ~TransferCgt() {
-    for (void* p : {(void*)l, (void*)lp, (void*)cperm})
-      if (p) (void)hipFree(p);
-  }
+  DevArray<double> l, lp;
+  DevArray<int32_t> cperm;   // chain: coarse block order -> coarse reference numbering
 };
 
 // operator dictionary of a fused chain level (CgtArgs::cls in cgt_kernels.hpp; the same search as DictDev's): one copy of
@@ -243,14 +237,10 @@ struct TransferCgt {
 // in the layouts of the full arrays -- and the class of every block.  The full arrays stay; every other kernel reads them.
 struct CgtDictDev {
   int nclasses = 0;
-  uint16_t* cls = nullptr;   // [ne]
-  double *dblk = nullptr, *subrow = nullptr, *supcol = nullptr;
-  double* l = nullptr;       // chain: [nclasses][m][mc + 1], agglomerating: [nclasses][m][mc]
-  double* lp = nullptr;      // agglomerating: [nclasses][mc]
-  ~CgtDictDev() {
-    for (void* p : {(void*)cls, (void*)dblk, (void*)subrow, (void*)supcol, (void*)l, (void*)lp})
-      if (p) (void)hipFree(p);
-  }
+  DevArray<uint16_t> cls;    // [ne]
+  DevArray<double> dblk, subrow, supcol;
+  DevArray<double> l;        // chain: [nclasses][m][mc + 1], agglomerating: [nclasses][m][mc]
+  DevArray<double> lp;       // agglomerating: [nclasses][mc]
 };
 
 struct Level {
@@ -258,7 +248,7 @@ struct Level {
   aggmg_smoother* S = nullptr;
   aggmg_op* L = nullptr;  // level k+1 -> k
   int64_t N = 0;
-  double *u[2] = {nullptr, nullptr}, *rhs = nullptr, *tmp = nullptr;
+  DevArray<double> u[2], rhs, tmp;
   std::unique_ptr<TransferBtd> tb;  // structured transfer to level k+1, or null
   std::unique_ptr<TransferCgt> tc;  // CG chain level: structured transfer to level k+1, or null
   std::unique_ptr<DictDev> dict;    // operator dictionary of the level's fused launches, or null
@@ -279,40 +269,45 @@ struct BandedLU {
 // one launch of the cyclic reduction: levels [l0, l0 + q) in steps of up to three thread-local levels
 // (cr_kernels.hpp); chunk stages reduce 2^q-block chunks to their end blocks, the tail takes the rest
 struct CrStage : CrStagePlan {    // the host-side plan (host_plan.hpp) + the stage's device buffers
-  double *partR = nullptr, *partL = nullptr, *xq = nullptr;  // the stage's boundary system (n_out blocks)
-  double* stack = nullptr;      // per chunk: summed inputs of the steps after the first
-  double* mid = nullptr;        // per step and sub-chunk: reduced right-hand sides of the inner sub-levels' odd rows
+  DevArray<double> partR;                     // the stage's boundary system (n_out blocks): one allocation, ...
+  double *partL = nullptr, *xq = nullptr;     // ... these two are views into it
+  DevArray<double> stack;       // per chunk: summed inputs of the steps after the first
+  DevArray<double> mid;         // per step and sub-chunk: reduced right-hand sides of the inner sub-levels' odd rows
 };
 
 struct CrDev {
   bool valid = false;
   int m = 0;
   int64_t n0 = 0, N = 0;
-  std::vector<CrLevel> lv;      // all reducing levels (device pointers)
-  std::vector<void*> owned;     // every device allocation, for free
+  std::vector<CrLevel> lv;      // all reducing levels (device pointers: views of `owned` or of `arena`)
+  struct Factors {              // what CrLevel points to, of one level / of the last block (lu, perm)
+    DevArray<double> fe, fo, lu;
+    DevArray<int32_t> perm;
+  };
+  std::vector<Factors> owned;   // per level, then the last block; empty where set-up moved the factors into `arena`
+  DevArray<char> arena;         // the small levels' factors in one allocation (setup_cr)
   const double* lu_last = nullptr;
   const int32_t* perm_last = nullptr;
   std::vector<CrStage> st;      // chunk stages ...
   CrStage tail;                 // ... then the remaining levels in one workgroup
-  double *d0 = nullptr, *x0 = nullptr;  // staging for padded systems (N not a multiple of m) / in-place calls
-  unsigned int* ticket = nullptr;       // last-arriving-workgroup counter of the fused forward + tail launch
+  DevArray<double> d0, x0;              // staging for padded systems (N not a multiple of m) / in-place calls
+  DevArray<unsigned int> ticket;        // last-arriving-workgroup counter of the fused forward + tail launch
   double cond_est = 0.0;
   // the tail's system by parallel cyclic reduction (cr_pcr_tail_kernel; block sizes 1, 2, up to 1024 blocks -- above 512
   // the parallel part takes the even rows, one ordinary reduction level around it): multipliers
-  // of every (level, row), final diagonal blocks factored; allocations in `owned`
+  // of every (level, row), final diagonal blocks factored
   struct Pcr {
     bool valid = false;
     bool pre = false;   // one ordinary cyclic-reduction level of the tail's first level around the parallel part
     int n = 0, L = 0;
-    double* mult = nullptr;
-    double* lu = nullptr;
-    int32_t* perm = nullptr;
+    DevArray<double> mult, lu;
+    DevArray<int32_t> perm;
   } pcr;
   // set-up only: copies of the (a, b, c) blocks of the small levels, until the plan says which one the tail starts at
   struct Raw {
     int level;
     int64_t n;
-    double *a, *b, *c;
+    DevArray<double> a, b, c;
   };
   std::vector<Raw> raw;
 };
@@ -322,41 +317,24 @@ struct aggmg_hier {
   int coarse_mode = 0;
   BandedLU coarse;
   CrDev cr;
-  double* cyc[2] = {nullptr, nullptr};  // iterate ping-pong for multi-cycle calls (lazy)
-  double* io[3] = {nullptr, nullptr, nullptr};  // x0, b, x_out of the host-pointer entry aggmg_vcycle (lazy)
+  DevArray<double> cyc[2];  // iterate ping-pong for multi-cycle calls (lazy)
+  DevArray<double> io[3];   // x0, b, x_out of the host-pointer entry aggmg_vcycle (lazy)
   // K-column cycles (aggmg_vcycle_multi_dev, lazy, grown to the largest column group asked for): per level, multi_cols
   // columns of the pre-smoothed iterate (mu[k][0]), the post-smoothed one (mu[k][1], levels 1 .. n-2) and the right-hand
   // side (mu[k][2], levels >= 1); the coarsest level's solution goes to mu[n-1][0]
-  std::vector<std::array<double*, 3>> mu;
+  std::vector<std::array<DevArray<double>, 3>> mu;
   int64_t multi_cols = 0;
   // the coarsest solve of a column group in one launch sequence (cr_solve_multi; lazy, grown like mu): per column of the
   // group what a CrStage holds for one (partR / partL / xq, stack, mid of every stage, the tail's mid) in ONE zeroed
   // allocation, and -- only when a call needs them -- the padded staging vectors d0 / x0 of every column in another
-  double* crw = nullptr;
+  DevArray<double> crw;
   int64_t crw_cols = 0;
-  double* crw_stage = nullptr;
+  DevArray<double> crw_stage;
   int64_t crw_stage_cols = 0;
   int restriction = 0;  // AGGMG_RESTRICT_EXPLICIT (default) / AGGMG_RESTRICT_PRECONDITIONED
   std::vector<double> h_coarse;
   double last_coarse_ms = 0.0;
   double cr_probe_backward_error = -1.0;  // ||d - A CR(d)|| / ||d|| of the set-up probe (-1: no device factorisation tried)
-  // owns every device allocation of its levels: an early return of aggmg_hier_create releases them
-  ~aggmg_hier() {
-    for (auto& l : lv)
-      for (double* p : {l.u[0], l.u[1], l.rhs, l.tmp})
-        if (p) (void)hipFree(p);
-    for (void* p : cr.owned)
-      if (p) (void)hipFree(p);
-    for (double* p : cyc)
-      if (p) (void)hipFree(p);
-    for (double* p : io)
-      if (p) (void)hipFree(p);
-    for (auto& m : mu)
-      for (double* p : m)
-        if (p) (void)hipFree(p);
-    for (double* p : {crw, crw_stage})
-      if (p) (void)hipFree(p);
-  }
 };
 
 // The restricted residual L'(b - A u) is formed from r = b - A u evaluated with the operator's own
@@ -370,54 +348,8 @@ struct aggmg_hier {
 // AGGMG_RESTRICT_PRECONDITIONED_MAX_ELEMS fine elements.
 inline int default_restriction() { return AGGMG_RESTRICT_EXPLICIT; }
 
-// ---------------------------------------------------------------------------------------------
-// error helpers
-// ---------------------------------------------------------------------------------------------
-inline int fail(aggmg_ctx* ctx, int code, const std::string& msg) {
-  if (ctx)
-    ctx->err = msg;
-  else
-    g_create_error = msg;
-  return code;
-}
-
-#define HIPCHK(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t _e = (expr);                                                                 \
-    if (_e != hipSuccess)                                                                   \
-      return fail(ctx, AGGMG_ERR_HIP,                                                       \
-                  std::string(#expr) + ": " + hipGetErrorString(_e) + " (" + __FILE__ + ":" + \
-                      std::to_string(__LINE__) + ")");                                      \
-  } while (0)
-
-#define CHECK(expr)             \
-  do {                          \
-    int _s = (expr);            \
-    if (_s != AGGMG_OK) return _s; \
-  } while (0)
-
-template <typename T>
-inline int dev_upload(aggmg_ctx* ctx, const std::vector<T>& h, T** d) {
-  *d = nullptr;
-  size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
-  HIPCHK(hipMalloc((void**)d, bytes));
-  if (!h.empty())
-    HIPCHK(hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return AGGMG_OK;
-}
-
 inline int scratch(aggmg_ctx* ctx, int slot, int64_t len, double** out) {
-  if (ctx->scratch_len[slot] < len) {
-    if (ctx->scratch[slot]) {
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      HIPCHK(hipFree(ctx->scratch[slot]));
-    }
-    ctx->scratch[slot] = nullptr;
-    ctx->scratch_len[slot] = 0;
-    HIPCHK(hipMalloc((void**)&ctx->scratch[slot], (size_t)std::max<int64_t>(len, 1) * sizeof(double)));
-    ctx->scratch_len[slot] = len;
-  }
+  CHECK(ctx->scratch[slot].reserve(ctx, len));
   *out = ctx->scratch[slot];
   return AGGMG_OK;
 }
@@ -493,7 +425,7 @@ int setup_block_order(aggmg_ctx* ctx, aggmg_smoother* sm);   // blocks in ascend
 int setup_block_cover(aggmg_ctx* ctx, aggmg_smoother* sm);   // row -> covering (block, local row) entries, on the device
 int op_ensure_csc_blocks(aggmg_ctx* ctx, aggmg_op* op);  // CSR-stream row blocks of the transposed orientation
 int op_host_csr(aggmg_ctx* ctx, aggmg_op* op, HostCsr* h);
-int setup_jacobi_diag(aggmg_ctx* ctx, const aggmg_op* A, double** diag);
+int setup_jacobi_diag(aggmg_ctx* ctx, const aggmg_op* A, DevArray<double>* diag);
 int setup_invert_blocks(aggmg_ctx* ctx, int64_t nb, int m, const double* blocks_dev, int colmajor, double* inv_dev,
                         int64_t* first_singular);
 int setup_block_smoother(aggmg_ctx* ctx, aggmg_smoother* sm, const int64_t* blockinds, int one_based, int want_btd);

@@ -1,6 +1,8 @@
 // Device-side set-up of libaggmg_hip: host code here only allocates, launches the
 // kernels of setup_kernels.hpp and reads back a handful of flags -- no O(n) host loop touches an
 // operator any more.  Compiled with -ffp-contract=off (see setup_kernels.hpp).
+#include <functional>
+
 #include <hipcub/hipcub.hpp>
 
 #include "internal.hpp"
@@ -10,45 +12,13 @@ namespace {
 
 inline unsigned grid_for(int64_t n) { return (unsigned)((n + kSetupThreads - 1) / kSetupThreads); }
 
-// device scratch that frees itself
-struct Tmp {
-  void* p = nullptr;
-  ~Tmp() {
-    if (p) (void)hipFree(p);
-  }
-  template <typename T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
-
-int tmp_alloc(aggmg_ctx* ctx, Tmp* t, size_t bytes, bool zero) {
-  HIPCHK(hipMalloc(&t->p, std::max<size_t>(bytes, 8)));
-  if (zero) HIPCHK(hipMemsetAsync(t->p, 0, std::max<size_t>(bytes, 8), ctx->stream));
-  return AGGMG_OK;
-}
-
-template <typename T>
-int dalloc(aggmg_ctx* ctx, T** out, int64_t count, bool zero) {
-  *out = nullptr;
-  const size_t bytes = (size_t)std::max<int64_t>(count, 1) * sizeof(T);
-  HIPCHK(hipMalloc((void**)out, bytes));
-  if (zero) HIPCHK(hipMemsetAsync(*out, 0, bytes, ctx->stream));
-  return AGGMG_OK;
-}
-
 // a few ints of flags on the device, read back synchronously
 struct Flags {
-  int* d = nullptr;
+  DevArray<int> d;
   int n = 0;
-  ~Flags() {
-    if (d) (void)hipFree(d);
-  }
   int init(aggmg_ctx* ctx, int count) {
     n = count;
-    HIPCHK(hipMalloc((void**)&d, count * sizeof(int)));
-    HIPCHK(hipMemsetAsync(d, 0, count * sizeof(int), ctx->stream));
-    return AGGMG_OK;
+    return d.alloc(ctx, count, true);
   }
   int read(aggmg_ctx* ctx, int* host) {
     HIPCHK(hipMemcpyAsync(host, d, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -79,25 +49,25 @@ int setup_csc_upload(aggmg_ctx* ctx, int64_t m, int64_t n, const int64_t* colptr
   out->nrows = n;  // rows of the transposed orientation = columns of the matrix
   out->ncols = m;
   out->nnz = nnz;
-  CHECK(dalloc(ctx, &out->rowptr, n + 1, false));
-  CHECK(dalloc(ctx, &out->colind, nnz, false));
-  CHECK(dalloc(ctx, &out->vals, nnz, false));
-  Tmp cp64, rv64;
-  CHECK(tmp_alloc(ctx, &cp64, (size_t)(n + 1) * 8, false));
-  CHECK(tmp_alloc(ctx, &rv64, (size_t)std::max<int64_t>(nnz, 1) * 8, false));
-  HIPCHK(hipMemcpyAsync(cp64.p, colptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  CHECK(out->rowptr.alloc(ctx, n + 1));
+  CHECK(out->colind.alloc(ctx, nnz));
+  CHECK(out->vals.alloc(ctx, nnz));
+  DevArray<int64_t> cp64, rv64;
+  CHECK(cp64.alloc(ctx, n + 1));
+  CHECK(rv64.alloc(ctx, nnz));
+  HIPCHK(hipMemcpyAsync(cp64, colptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   if (nnz) {
-    HIPCHK(hipMemcpyAsync(rv64.p, rowval, (size_t)nnz * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(rv64, rowval, (size_t)nnz * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(out->vals, nzval, (size_t)nnz * 8, hipMemcpyHostToDevice, ctx->stream));
   }
   Flags f;
   CHECK(f.init(ctx, 4));
-  LAUNCH(csc_convert_colptr_kernel, n + 1, n, cp64.as<int64_t>(), base, nnz, out->rowptr, f.d);
+  LAUNCH(csc_convert_colptr_kernel, n + 1, n, cp64.get(), base, nnz, out->rowptr, f.d);
   int h[4];
   CHECK(f.read(ctx, h));  // the row pass below walks colptr: it must be sane first
   if (h[0]) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_csc_upload: colptr not monotone");
   if (h[3]) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_csc_upload: colptr does not start at the index base");
-  LAUNCH(csc_convert_rows_kernel, n, n, m, (const int32_t*)out->rowptr, rv64.as<int64_t>(), base, out->colind, f.d);
+  LAUNCH(csc_convert_rows_kernel, n, n, m, (const int32_t*)out->rowptr, rv64.get(), base, out->colind, f.d);
   CHECK(f.read(ctx, h));
   if (h[1]) return fail(ctx, AGGMG_ERR_DIMENSION, "aggmg_csc_upload: row index out of range");
   if (h[2]) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_csc_upload: row indices not strictly ascending in a column");
@@ -125,7 +95,7 @@ int setup_stream_blocks(aggmg_ctx* ctx, CsrDev* d) {
   const int64_t nrows = d->nrows;
   const std::vector<int32_t> blk = stream_row_blocks(rowptr.data(), nrows, kStreamNnz, kStreamRows);   // host_plan.hpp
   d->nblk = (int64_t)blk.size() - 1;
-  CHECK(dev_upload(ctx, blk, &d->rowblk));
+  CHECK(d->rowblk.upload(ctx, blk));
   // square and banded: row blocks for csr_band_kernel (x window in LDS, several point-Jacobi sweeps per launch) --
   // a tile -- a block's rows plus (S - 1) * bw halo rows on either side -- has at most kThreads rows and kBandNnz entries;
   // S, the most sweeps per launch, is chosen per operator so that the halo stays near a quarter of the tile
@@ -149,7 +119,7 @@ int setup_stream_blocks(aggmg_ctx* ctx, CsrDev* d) {
         d->band_sweeps = S;
         d->bw = bw;
         d->nbandblk = (int64_t)bb.size() - 1;
-        CHECK(dev_upload(ctx, bb, &d->bandblk));
+        CHECK(d->bandblk.upload(ctx, bb));
       }
     }
   }
@@ -162,37 +132,38 @@ int setup_transpose(aggmg_ctx* ctx, const CsrDev& csc, int64_t m, CsrDev* out) {
   out->nrows = m;
   out->ncols = n;
   out->nnz = nnz;
-  CHECK(dalloc(ctx, &out->rowptr, m + 1, true));
-  CHECK(dalloc(ctx, &out->colind, nnz, false));
-  CHECK(dalloc(ctx, &out->vals, nnz, false));
+  CHECK(out->rowptr.alloc(ctx, m + 1, true));
+  CHECK(out->colind.alloc(ctx, nnz));
+  CHECK(out->vals.alloc(ctx, nnz));
   if (nnz == 0) return AGGMG_OK;
   // rowptr: histogram of the row indices, exclusive scan
-  Tmp counts;
-  CHECK(tmp_alloc(ctx, &counts, (size_t)(m + 1) * 4, true));
-  LAUNCH(row_count_kernel, nnz, nnz, (const int32_t*)csc.colind, counts.as<int32_t>());
+  DevArray<int32_t> counts;
+  CHECK(counts.alloc(ctx, m + 1, true));
+  LAUNCH(row_count_kernel, nnz, nnz, (const int32_t*)csc.colind, counts.get());
   size_t sbytes = 0;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, sbytes, counts.as<int32_t>(), out->rowptr, (int)(m + 1), ctx->stream));
-  Tmp stmp;
-  CHECK(tmp_alloc(ctx, &stmp, sbytes, false));
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(stmp.p, sbytes, counts.as<int32_t>(), out->rowptr, (int)(m + 1), ctx->stream));
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, sbytes, counts.get(), out->rowptr.get(), (int)(m + 1), ctx->stream));
+  DevArray<char> stmp;
+  CHECK(stmp.alloc(ctx, (int64_t)sbytes));
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(stmp.get(), sbytes, counts.get(), out->rowptr.get(), (int)(m + 1), ctx->stream));
   // entries sorted by row; the sort is stable, so columns stay ascending inside a row
-  Tmp ecol, iota, perm, keys;
-  CHECK(tmp_alloc(ctx, &ecol, (size_t)nnz * 4, false));
-  CHECK(tmp_alloc(ctx, &iota, (size_t)nnz * 4, false));
-  CHECK(tmp_alloc(ctx, &perm, (size_t)nnz * 4, false));
-  CHECK(tmp_alloc(ctx, &keys, (size_t)nnz * 4, false));
-  LAUNCH(csc_entry_cols_kernel, n, n, (const int32_t*)csc.rowptr, ecol.as<int32_t>());
-  LAUNCH(iota_kernel, nnz, nnz, iota.as<uint32_t>());
+  DevArray<int32_t> ecol;
+  DevArray<uint32_t> iota, perm, keys;
+  CHECK(ecol.alloc(ctx, nnz));
+  CHECK(iota.alloc(ctx, nnz));
+  CHECK(perm.alloc(ctx, nnz));
+  CHECK(keys.alloc(ctx, nnz));
+  LAUNCH(csc_entry_cols_kernel, n, n, (const int32_t*)csc.rowptr, ecol.get());
+  LAUNCH(iota_kernel, nnz, nnz, iota.get());
   int bits = 1;
   while (bits < 32 && ((int64_t)1 << bits) < m) ++bits;
   size_t rbytes = 0;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, rbytes, (const uint32_t*)csc.colind, keys.as<uint32_t>(), iota.as<uint32_t>(),
-                                            perm.as<uint32_t>(), (int)nnz, 0, bits, ctx->stream));
-  Tmp rtmp;
-  CHECK(tmp_alloc(ctx, &rtmp, rbytes, false));
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(rtmp.p, rbytes, (const uint32_t*)csc.colind, keys.as<uint32_t>(), iota.as<uint32_t>(),
-                                            perm.as<uint32_t>(), (int)nnz, 0, bits, ctx->stream));
-  LAUNCH(csr_gather_kernel, nnz, nnz, (const uint32_t*)perm.as<uint32_t>(), (const int32_t*)ecol.as<int32_t>(),
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, rbytes, (const uint32_t*)csc.colind.get(), keys.get(), iota.get(),
+                                            perm.get(), (int)nnz, 0, bits, ctx->stream));
+  DevArray<char> rtmp;
+  CHECK(rtmp.alloc(ctx, (int64_t)rbytes));
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(rtmp.get(), rbytes, (const uint32_t*)csc.colind.get(), keys.get(), iota.get(),
+                                            perm.get(), (int)nnz, 0, bits, ctx->stream));
+  LAUNCH(csr_gather_kernel, nnz, nnz, (const uint32_t*)perm, (const int32_t*)ecol,
          (const double*)csc.vals, out->colind, out->vals);
   HIPCHK(hipStreamSynchronize(ctx->stream));  // the temporaries go out of scope
   return AGGMG_OK;
@@ -223,10 +194,10 @@ int op_host_csr(aggmg_ctx* ctx, aggmg_op* op, HostCsr* h) {
 // ---------------------------------------------------------------------------------------------
 // smoothers
 // ---------------------------------------------------------------------------------------------
-int setup_jacobi_diag(aggmg_ctx* ctx, const aggmg_op* A, double** diag) {
-  CHECK(dalloc(ctx, diag, A->m, false));
+int setup_jacobi_diag(aggmg_ctx* ctx, const aggmg_op* A, DevArray<double>* diag) {
+  CHECK(diag->alloc(ctx, A->m));
   LAUNCH(diag_extract_kernel, A->m, A->m, (const int32_t*)A->csc.rowptr, (const int32_t*)A->csc.colind,
-         (const double*)A->csc.vals, *diag);
+         (const double*)A->csc.vals, diag->get());
   return AGGMG_OK;
 }
 
@@ -242,40 +213,34 @@ int setup_block_order(aggmg_ctx* ctx, aggmg_smoother* sm) {
   if (sm->nb > 1) {
     Flags uns;
     CHECK(uns.init(ctx, 1));
-    Tmp keys, keys2, iota, order;
-    CHECK(tmp_alloc(ctx, &keys, (size_t)sm->nb * 4, false));
-    LAUNCH(block_minkey_kernel, sm->nb, sm->nb, (int)sm->m, (const int32_t*)sm->inds, keys.as<uint32_t>(), uns.d);
+    DevArray<uint32_t> keys, keys2, iota, order;
+    CHECK(keys.alloc(ctx, sm->nb));
+    LAUNCH(block_minkey_kernel, sm->nb, sm->nb, (int)sm->m, (const int32_t*)sm->inds, keys.get(), uns.d);
     int u1 = 0;
     CHECK(uns.read(ctx, &u1));
     if (u1) {
-      CHECK(tmp_alloc(ctx, &keys2, (size_t)sm->nb * 4, false));
-      CHECK(tmp_alloc(ctx, &iota, (size_t)sm->nb * 4, false));
-      CHECK(tmp_alloc(ctx, &order, (size_t)sm->nb * 4, false));
-      LAUNCH(iota_kernel, sm->nb, sm->nb, iota.as<uint32_t>());
+      CHECK(keys2.alloc(ctx, sm->nb));
+      CHECK(iota.alloc(ctx, sm->nb));
+      CHECK(order.alloc(ctx, sm->nb));
+      LAUNCH(iota_kernel, sm->nb, sm->nb, iota.get());
       int kb = 1;
       while (kb < 32 && ((int64_t)1 << kb) < N) ++kb;
       size_t rb = 0;
-      HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, rb, keys.as<uint32_t>(), keys2.as<uint32_t>(), iota.as<uint32_t>(),
-                                                order.as<uint32_t>(), (int)sm->nb, 0, kb, ctx->stream));
-      Tmp rt;
-      CHECK(tmp_alloc(ctx, &rt, rb, false));
-      HIPCHK(hipcub::DeviceRadixSort::SortPairs(rt.p, rb, keys.as<uint32_t>(), keys2.as<uint32_t>(), iota.as<uint32_t>(),
-                                                order.as<uint32_t>(), (int)sm->nb, 0, kb, ctx->stream));
-      int32_t* inds2 = nullptr;
-      double* binv2 = nullptr;
-      CHECK(dalloc(ctx, &inds2, total, false));
-      Tmp o1;
-      o1.p = inds2;
-      CHECK(dalloc(ctx, &binv2, total * sm->m, false));
-      Tmp o2;
-      o2.p = binv2;
-      LAUNCH(block_permute_kernel, total, total, (int)sm->m, (const uint32_t*)order.as<uint32_t>(), (const int32_t*)sm->inds,
+      HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, rb, keys.get(), keys2.get(), iota.get(),
+                                                order.get(), (int)sm->nb, 0, kb, ctx->stream));
+      DevArray<char> rt;
+      CHECK(rt.alloc(ctx, (int64_t)rb));
+      HIPCHK(hipcub::DeviceRadixSort::SortPairs(rt.get(), rb, keys.get(), keys2.get(), iota.get(),
+                                                order.get(), (int)sm->nb, 0, kb, ctx->stream));
+      DevArray<int32_t> inds2;
+      DevArray<double> binv2;
+      CHECK(inds2.alloc(ctx, total));
+      CHECK(binv2.alloc(ctx, total * sm->m));
+      LAUNCH(block_permute_kernel, total, total, (int)sm->m, (const uint32_t*)order, (const int32_t*)sm->inds,
              (const double*)sm->binv, inds2, binv2);
       HIPCHK(hipStreamSynchronize(ctx->stream));
-      o1.p = sm->inds;   // the old arrays are released with the temporaries
-      o2.p = sm->binv;
-      sm->inds = inds2;
-      sm->binv = binv2;
+      std::swap(sm->inds, inds2);   // the old arrays are released with the temporaries
+      std::swap(sm->binv, binv2);
     }
   }
   sm->ordered = true;
@@ -286,41 +251,36 @@ int setup_block_cover(aggmg_ctx* ctx, aggmg_smoother* sm) {
   if (sm->cover_ptr) return AGGMG_OK;
   CHECK(setup_block_order(ctx, sm));
   const int64_t N = sm->N, total = sm->nb * sm->m;
-  int32_t* cptr = nullptr;
-  uint32_t* cidx = nullptr;
-  CHECK(dalloc(ctx, &cptr, N + 1, true));
-  Tmp owner_ptr;   // released on an early return
-  owner_ptr.p = cptr;
+  DevArray<int32_t> cptr;   // (the two are released on an early return)
+  DevArray<uint32_t> cidx;
+  CHECK(cptr.alloc(ctx, N + 1, true));
   if (total > 0) {
-    CHECK(dalloc(ctx, &cidx, total, false));
-    Tmp owner_idx;
-    owner_idx.p = cidx;
-    Tmp counts, iota, keys;
-    CHECK(tmp_alloc(ctx, &counts, (size_t)(N + 1) * 4, true));
-    LAUNCH(row_count_kernel, total, total, (const int32_t*)sm->inds, counts.as<int32_t>());
+    CHECK(cidx.alloc(ctx, total));
+    DevArray<int32_t> counts;
+    DevArray<uint32_t> iota, keys;
+    CHECK(counts.alloc(ctx, N + 1, true));
+    LAUNCH(row_count_kernel, total, total, (const int32_t*)sm->inds, counts.get());
     size_t sbytes = 0;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, sbytes, counts.as<int32_t>(), cptr, (int)(N + 1), ctx->stream));
-    Tmp stmp;
-    CHECK(tmp_alloc(ctx, &stmp, sbytes, false));
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(stmp.p, sbytes, counts.as<int32_t>(), cptr, (int)(N + 1), ctx->stream));
-    CHECK(tmp_alloc(ctx, &iota, (size_t)total * 4, false));
-    CHECK(tmp_alloc(ctx, &keys, (size_t)total * 4, false));
-    LAUNCH(iota_kernel, total, total, iota.as<uint32_t>());
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, sbytes, counts.get(), cptr.get(), (int)(N + 1), ctx->stream));
+    DevArray<char> stmp;
+    CHECK(stmp.alloc(ctx, (int64_t)sbytes));
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(stmp.get(), sbytes, counts.get(), cptr.get(), (int)(N + 1), ctx->stream));
+    CHECK(iota.alloc(ctx, total));
+    CHECK(keys.alloc(ctx, total));
+    LAUNCH(iota_kernel, total, total, iota.get());
     int bits = 1;
     while (bits < 32 && ((int64_t)1 << bits) < N) ++bits;
     size_t rbytes = 0;
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, rbytes, (const uint32_t*)sm->inds, keys.as<uint32_t>(), iota.as<uint32_t>(), cidx,
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, rbytes, (const uint32_t*)sm->inds.get(), keys.get(), iota.get(), cidx.get(),
                                               (int)total, 0, bits, ctx->stream));
-    Tmp rtmp;
-    CHECK(tmp_alloc(ctx, &rtmp, rbytes, false));
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(rtmp.p, rbytes, (const uint32_t*)sm->inds, keys.as<uint32_t>(), iota.as<uint32_t>(), cidx,
+    DevArray<char> rtmp;
+    CHECK(rtmp.alloc(ctx, (int64_t)rbytes));
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(rtmp.get(), rbytes, (const uint32_t*)sm->inds.get(), keys.get(), iota.get(), cidx.get(),
                                               (int)total, 0, bits, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));  // the temporaries go out of scope
-    owner_idx.p = nullptr;
   }
-  owner_ptr.p = nullptr;
-  sm->cover_ptr = cptr;
-  sm->cover_idx = cidx;
+  sm->cover_ptr = std::move(cptr);
+  sm->cover_idx = std::move(cidx);
   return AGGMG_OK;
 }
 
@@ -328,23 +288,21 @@ int setup_block_cover(aggmg_ctx* ctx, aggmg_smoother* sm) {
 // *first_singular = index of the first singular block or -1
 int setup_invert_blocks(aggmg_ctx* ctx, int64_t nb, int m, const double* blocks_dev, int colmajor, double* inv_dev,
                         int64_t* first_singular) {
-  unsigned long long* sing = nullptr;
-  HIPCHK(hipMalloc((void**)&sing, sizeof(unsigned long long)));
-  Tmp sing_owner;
-  sing_owner.p = sing;
+  DevArray<unsigned long long> sing;
+  CHECK(sing.alloc(ctx, 1));
   const unsigned long long none = (unsigned long long)nb;
   HIPCHK(hipMemcpyAsync(sing, &none, sizeof(none), hipMemcpyHostToDevice, ctx->stream));
-  Tmp work;
+  DevArray<double> work;
   switch (m) {
 #define CASE(MM)                                                                              \
   case MM:                                                                                    \
-    LAUNCH((block_invert_kernel<MM>), nb, nb, blocks_dev, colmajor, inv_dev, sing);           \
+    LAUNCH((block_invert_kernel<MM>), nb, nb, blocks_dev, colmajor, inv_dev, sing.get());     \
     break;
     CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
 #undef CASE
     default:
-      CHECK(tmp_alloc(ctx, &work, (size_t)nb * ((size_t)m * m + 2 * m) * sizeof(double), false));
-      LAUNCH(block_invert_any_kernel, nb, nb, m, blocks_dev, colmajor, work.as<double>(), inv_dev, sing);
+      CHECK(work.alloc(ctx, nb * ((int64_t)m * m + 2 * m)));
+      LAUNCH(block_invert_any_kernel, nb, nb, m, blocks_dev, colmajor, work.get(), inv_dev, sing.get());
   }
   unsigned long long got = none;
   HIPCHK(hipMemcpyAsync(&got, sing, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
@@ -367,20 +325,20 @@ int setup_block_smoother(aggmg_ctx* ctx, aggmg_smoother* sm, const int64_t* bloc
   const int m = (int)sm->m;
   const int64_t total = nb * m;
   const int64_t base = one_based ? 1 : 0;
-  Tmp inds64;
-  CHECK(tmp_alloc(ctx, &inds64, (size_t)std::max<int64_t>(total, 1) * 8, false));
-  if (total) HIPCHK(hipMemcpyAsync(inds64.p, blockinds, (size_t)total * 8, hipMemcpyHostToDevice, ctx->stream));
-  CHECK(dalloc(ctx, &sm->inds, total, false));
-  CHECK(dalloc(ctx, &sm->counts, N, true));
+  DevArray<int64_t> inds64;
+  CHECK(inds64.alloc(ctx, total));
+  if (total) HIPCHK(hipMemcpyAsync(inds64, blockinds, (size_t)total * 8, hipMemcpyHostToDevice, ctx->stream));
+  CHECK(sm->inds.alloc(ctx, total));
+  CHECK(sm->counts.alloc(ctx, N, true));
   Flags f;
   CHECK(f.init(ctx, 4));
-  LAUNCH(inds_convert_kernel, total, total, N, inds64.as<int64_t>(), base, sm->inds, sm->counts, f.d);
+  LAUNCH(inds_convert_kernel, total, total, N, inds64.get(), base, sm->inds, sm->counts, f.d);
   int h[4];
   CHECK(f.read(ctx, h));
   if (h[0]) return fail(ctx, AGGMG_ERR_DIMENSION, "aggmg_blockjacobi_setup: block index out of range");
   sm->contiguous = (total == N) && !h[1];
   sm->overlapping = h[2] != 0;
-  CHECK(dalloc(ctx, &sm->binv, total * m, false));
+  CHECK(sm->binv.alloc(ctx, total * m));
   int64_t sing = -1;
   auto b = std::make_shared<BtdDev>();
   bool btd_ok = false;
@@ -388,9 +346,9 @@ int setup_block_smoother(aggmg_ctx* ctx, aggmg_smoother* sm, const int64_t* bloc
     // scatter the entries into the three block diagonals: the diagonal blocks ARE A[inds, inds]
     b->m = m;
     b->ne = nb;
-    CHECK(dalloc(ctx, &b->dblk, N * m, true));
-    CHECK(dalloc(ctx, &b->sub, N * m, true));
-    CHECK(dalloc(ctx, &b->sup, N * m, true));
+    CHECK(b->dblk.alloc(ctx, N * m, true));
+    CHECK(b->sub.alloc(ctx, N * m, true));
+    CHECK(b->sup.alloc(ctx, N * m, true));
     Flags f2;
     CHECK(f2.init(ctx, 4));
     unsigned* masks = reinterpret_cast<unsigned*>(f2.d + 2);
@@ -411,21 +369,21 @@ int setup_block_smoother(aggmg_ctx* ctx, aggmg_smoother* sm, const int64_t* bloc
         b->c_sub = c_sub;
         b->r_sup = r_sup;
         // the fused kernel's copy of the inverses
-        CHECK(dalloc(ctx, &b->binv, N * m, false));
+        CHECK(b->binv.alloc(ctx, N * m));
         HIPCHK(hipMemcpyAsync(b->binv, sm->binv, (size_t)N * m * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
         Flags asym;
         CHECK(asym.init(ctx, 1));
         const bool grp = cmp ? (m == 2 || m == 4 || m == 8) : (m == 2 || m == 4);
         const bool try_sym = grp && ctx->sym_packing && (!cmp || c_sub == r_sup);
         if (cmp) {
-          CHECK(dalloc(ctx, &b->scol, N, false));
-          CHECK(dalloc(ctx, &b->pcol, N, false));
-          CHECK(dalloc(ctx, &b->qrow, N, false));
+          CHECK(b->scol.alloc(ctx, N));
+          CHECK(b->pcol.alloc(ctx, N));
+          CHECK(b->qrow.alloc(ctx, N));
           LAUNCH(btd_cmp_finish_kernel, nb, nb, m, c_sub, r_sup, (const double*)b->binv, (const double*)b->sub,
                  (const double*)b->sup, b->scol, b->pcol, b->qrow);
         } else {
-          CHECK(dalloc(ctx, &b->P, N * m, false));
-          CHECK(dalloc(ctx, &b->Q, N * m, false));
+          CHECK(b->P.alloc(ctx, N * m));
+          CHECK(b->Q.alloc(ctx, N * m));
           LAUNCH(btd_dense_finish_kernel, N, nb, m, (const double*)b->binv, (const double*)b->sub, (const double*)b->sup,
                  b->P, b->Q);
         }
@@ -435,7 +393,7 @@ int setup_block_smoother(aggmg_ctx* ctx, aggmg_smoother* sm, const int64_t* bloc
           int a1 = 0;
           CHECK(asym.read(ctx, &a1));
           if (!a1) {
-            CHECK(dalloc(ctx, &b->bsym, nb * (int64_t)(m * (m + 1) / 2), false));
+            CHECK(b->bsym.alloc(ctx, nb * (int64_t)(m * (m + 1) / 2)));
             LAUNCH(btd_sym_pack_kernel, nb, nb, m, (const double*)b->binv, b->bsym);
             if (cmp && m <= 4 && ctx->sym_residual) {
               // the explicit residual's entries as half + exact int8 corrections (AGGMG_OPT_SYMMETRIC_RESIDUAL); a level
@@ -443,38 +401,35 @@ int setup_block_smoother(aggmg_ctx* ctx, aggmg_smoother* sm, const int64_t* bloc
               const int T = m * (m + 1) / 2;
               Flags over;
               CHECK(over.init(ctx, 1));
-              CHECK(dalloc(ctx, &b->dup, nb * (int64_t)T, false));
-              CHECK(dalloc(ctx, &b->corr, N, false));
+              CHECK(b->dup.alloc(ctx, nb * (int64_t)T));
+              CHECK(b->corr.alloc(ctx, N));
               LAUNCH(btd_sym_residual_kernel, N, nb, m, (const double*)b->dblk, (const double*)b->scol,
                      (const double*)b->qrow, b->dup, b->corr, over.d);
               int nover = 0;
               CHECK(over.read(ctx, &nover));
               const int64_t entries = nb * (int64_t)(m * (m - 1) / 2 + m);   // lower entries of D + couplings
               if ((int64_t)nover * 1024 > entries) {
-                (void)hipFree(b->dup);
-                (void)hipFree(b->corr);
-                b->dup = nullptr;
-                b->corr = nullptr;
+                b->dup.reset();
+                b->corr.reset();
               }
             }
           }
         }
         if (cmp) {  // the dense off-diagonal blocks are not read by the compressed kernels
           (void)hipStreamSynchronize(ctx->stream);
-          (void)hipFree(b->sub);
-          (void)hipFree(b->sup);
-          b->sub = b->sup = nullptr;
+          b->sub.reset();
+          b->sup.reset();
         }
         sm->btd = b;
         A->btd = b;
       }
     }
   } else {
-    Tmp blocks;
-    CHECK(tmp_alloc(ctx, &blocks, (size_t)std::max<int64_t>(total * m, 1) * sizeof(double), false));
+    DevArray<double> blocks;
+    CHECK(blocks.alloc(ctx, total * m));
     LAUNCH(block_extract_generic_kernel, total * m, nb, m, (const int32_t*)sm->inds, (const int32_t*)A->csc.rowptr,
-           (const int32_t*)A->csc.colind, (const double*)A->csc.vals, blocks.as<double>());
-    CHECK(setup_invert_blocks(ctx, nb, m, blocks.as<double>(), 0, sm->binv, &sing));
+           (const int32_t*)A->csc.colind, (const double*)A->csc.vals, blocks.get());
+    CHECK(setup_invert_blocks(ctx, nb, m, blocks, 0, sm->binv, &sing));
   }
   if (sing >= 0)
     return fail(ctx, AGGMG_ERR_SINGULAR,
@@ -500,7 +455,7 @@ static int setup_unit_column(aggmg_ctx* ctx, TransferBtd* t, int64_t Nf) {
   int notone = 0;
   CHECK(f.read(ctx, &notone));
   if (notone) return AGGMG_OK;
-  CHECK(dalloc(ctx, &t->lf1, Nf, false));
+  CHECK(t->lf1.alloc(ctx, Nf));
   LAUNCH(transfer_second_column_kernel, Nf, Nf, (const double*)t->lf, t->lf1);
   return AGGMG_OK;
 }
@@ -519,22 +474,19 @@ int setup_transfer_btd(aggmg_ctx* ctx, const aggmg_op* L, const BtdDev* Abtd, in
     if (nec == 0 || nef % nec) continue;
     const int64_t rho = nef / nec;
     if (rho > 64) continue;
-    double* lf = nullptr;
-    CHECK(dalloc(ctx, &lf, Nf * mc, true));
+    DevArray<double> lf;
+    CHECK(lf.alloc(ctx, Nf * mc, true));
     CHECK(bad.clear(ctx));
     LAUNCH(transfer_scatter_kernel, Nc, Nc, mf, mc, rho, (const int32_t*)L->csc.rowptr, (const int32_t*)L->csc.colind,
            (const double*)L->csc.vals, lf, bad.d);
     int bf[2] = {0, 0};
     CHECK(bad.read(ctx, bf));
     const int b1 = bf[0];
-    if (b1) {
-      (void)hipFree(lf);
-      continue;
-    }
-    out->lf = lf;
+    if (b1) continue;
+    out->lf = std::move(lf);
     if (Abtd && Abtd->dblk) {
-      CHECK(dalloc(ctx, &out->ld, Nf * mc, false));
-      LAUNCH(transfer_ld_kernel, Nf, nef, mf, mc, (const double*)lf, (const double*)Abtd->dblk, out->ld);
+      CHECK(out->ld.alloc(ctx, Nf * mc));
+      LAUNCH(transfer_ld_kernel, Nf, nef, mf, mc, (const double*)out->lf, (const double*)Abtd->dblk, out->ld);
     }
     out->mc = mc;
     out->rho = (int)rho;
@@ -551,27 +503,24 @@ int setup_transfer_btd(aggmg_ctx* ctx, const aggmg_op* L, const BtdDev* Abtd, in
     if (Nc % mc) continue;
     const int64_t nec = Nc / mc;
     if (nec == 0 || nec > nef) continue;
-    double* lf = nullptr;
-    int32_t *first = nullptr, *parent = nullptr;
-    CHECK(dalloc(ctx, &lf, Nf * mc, true));
-    CHECK(dalloc(ctx, &first, nec + 1, true));
-    CHECK(dalloc(ctx, &parent, nef, true));
+    DevArray<double> lf;
+    DevArray<int32_t> first, parent;
+    CHECK(lf.alloc(ctx, Nf * mc, true));
+    CHECK(first.alloc(ctx, nec + 1, true));
+    CHECK(parent.alloc(ctx, nef, true));
     CHECK(bad.clear(ctx));
     LAUNCH(transfer_vr_kernel, nec, nec, nef, mf, mc, 64, (const int32_t*)L->csc.rowptr, (const int32_t*)L->csc.colind,
            (const double*)L->csc.vals, first, parent, lf, bad.d);
     int bf[2] = {0, 0};
     CHECK(bad.read(ctx, bf));
     const int b1 = bf[0];
-    if (b1) {
-      (void)hipFree(lf), (void)hipFree(first), (void)hipFree(parent);
-      continue;
-    }
-    out->lf = lf;
-    out->first = first;
-    out->parent = parent;
+    if (b1) continue;
+    out->lf = std::move(lf);
+    out->first = std::move(first);
+    out->parent = std::move(parent);
     if (Abtd && Abtd->dblk) {
-      CHECK(dalloc(ctx, &out->ld, Nf * mc, false));
-      LAUNCH(transfer_ld_kernel, Nf, nef, mf, mc, (const double*)lf, (const double*)Abtd->dblk, out->ld);
+      CHECK(out->ld.alloc(ctx, Nf * mc));
+      LAUNCH(transfer_ld_kernel, Nf, nef, mf, mc, (const double*)out->lf, (const double*)Abtd->dblk, out->ld);
     }
     out->mc = mc;
     out->rho = 0;
@@ -592,37 +541,42 @@ namespace {
 // the arrays of a level's record, in the record's order; `dict` of every field is filled in by dict_build
 struct DictFields {
   DictView v;
-  void** slot[kDictMaxFields];   // where the owner keeps the dictionary's copy of field k
+  std::function<int(aggmg_ctx*, int64_t)> make[kDictMaxFields];   // allocates the owner's dictionary copy of field k
   DictFields(int64_t ne) {
     std::memset(&v, 0, sizeof(v));
     v.ne = ne;
   }
   template <typename T>
-  void add(const T* full, T** dict, int n, bool back = false) {
+  void add(const DevArray<T>& full, DevArray<T>* dict, int n, bool back = false) {
     static_assert(sizeof(T) == 8 || sizeof(T) == 4, "records are made of 64- and 32-bit words");
-    slot[v.nf] = reinterpret_cast<void**>(dict);
-    v.f[v.nf++] = DictField{full, nullptr, n, (int)sizeof(T), back ? 1 : 0};
+    const int k = v.nf++;
+    make[k] = [this, k, dict](aggmg_ctx* ctx, int64_t count) {
+      CHECK(dict->alloc(ctx, count));
+      v.f[k].dict = dict->get();
+      return (int)AGGMG_OK;
+    };
+    v.f[k] = DictField{full.get(), nullptr, n, (int)sizeof(T), back ? 1 : 0};
   }
 };
 
-// The classes of identical records of a level: *nclasses > 0, cls[ne] and the dictionary's arrays (through F.slot: they
+// The classes of identical records of a level: *nclasses > 0, cls[ne] and the dictionary's arrays (through F.make: they
 // belong to the caller's object whatever happens) when the level takes the form; *nclasses = 0 when it has more than
 // kDictMaxClasses distinct records or two records share a hash.
-int dict_build(aggmg_ctx* ctx, DictFields& F, uint16_t** cls, int* nclasses) {
+int dict_build(aggmg_ctx* ctx, DictFields& F, DevArray<uint16_t>* cls, int* nclasses) {
   *nclasses = 0;
   DictView& v = F.v;
   const int64_t ne = v.ne;
   // the distinct record hashes; more than kDictMaxClasses: the level keeps the plain path
-  Tmp table;
-  CHECK(tmp_alloc(ctx, &table, (size_t)kDictSlots * sizeof(unsigned long long), true));
+  DevArray<unsigned long long> table;
+  CHECK(table.alloc(ctx, kDictSlots, true));
   Flags stat;
   CHECK(stat.init(ctx, 2));
-  LAUNCH(dict_collect_kernel, ne, v, table.as<unsigned long long>(), stat.d);
+  LAUNCH(dict_collect_kernel, ne, v, table.get(), stat.d);
   int st[2] = {0, 0};
   CHECK(stat.read(ctx, st));
   if (st[1] || st[0] > kDictMaxClasses || st[0] < 1) return AGGMG_OK;
   std::vector<unsigned long long> slots(kDictSlots), hashes;
-  HIPCHK(hipMemcpyAsync(slots.data(), table.p, slots.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(slots.data(), table, slots.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   for (unsigned long long s : slots)
     if (s) hashes.push_back(s);
@@ -630,23 +584,20 @@ int dict_build(aggmg_ctx* ctx, DictFields& F, uint16_t** cls, int* nclasses) {
   const int nc = (int)hashes.size();
   if (nc != st[0]) return AGGMG_OK;
   // classes in ascending order of the hash, each one's record from its first element: the same dictionary every time
-  Tmp sorted, rep;
-  CHECK(tmp_alloc(ctx, &sorted, (size_t)nc * sizeof(unsigned long long), false));
-  CHECK(tmp_alloc(ctx, &rep, (size_t)nc * sizeof(unsigned long long), false));
-  HIPCHK(hipMemcpyAsync(sorted.p, hashes.data(), (size_t)nc * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
+  DevArray<unsigned long long> sorted, rep;
+  CHECK(sorted.alloc(ctx, nc));
+  CHECK(rep.alloc(ctx, nc));
+  HIPCHK(hipMemcpyAsync(sorted, hashes.data(), (size_t)nc * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
   const std::vector<unsigned long long> none((size_t)nc, (unsigned long long)ne);
-  HIPCHK(hipMemcpyAsync(rep.p, none.data(), (size_t)nc * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(rep, none.data(), (size_t)nc * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));   // (the two host vectors are done with before anything below can return)
-  CHECK(dalloc(ctx, cls, ne, false));
-  for (int k = 0; k < v.nf; ++k) {
-    HIPCHK(hipMalloc(F.slot[k], (size_t)nc * v.f[k].n * v.f[k].bytes));
-    v.f[k].dict = *F.slot[k];
-  }
+  CHECK(cls->alloc(ctx, ne));
+  for (int k = 0; k < v.nf; ++k) CHECK(F.make[k](ctx, (int64_t)nc * v.f[k].n));
   Flags bad;
   CHECK(bad.init(ctx, 1));
-  LAUNCH(dict_assign_kernel, ne, v, nc, (const unsigned long long*)sorted.as<unsigned long long>(), *cls,
-         rep.as<unsigned long long>(), bad.d);
-  LAUNCH(dict_gather_kernel, nc, v, nc, (const unsigned long long*)rep.as<unsigned long long>());
+  LAUNCH(dict_assign_kernel, ne, v, nc, (const unsigned long long*)sorted, cls->get(),
+         rep.get(), bad.d);
+  LAUNCH(dict_gather_kernel, nc, v, nc, (const unsigned long long*)rep);
   // every element's record against its class's, bit for bit: two records of one hash leave the level on the plain path
   LAUNCH(dict_verify_kernel, ne, v, (const uint16_t*)*cls, bad.d);
   int b1 = 0;
@@ -712,44 +663,39 @@ int setup_cgt_dictionary(aggmg_ctx* ctx, const CgtDev& g, const TransferCgt& t, 
 // cyclic-reduction factorisation of the coarsest operator
 // ---------------------------------------------------------------------------------------------
 template <int M>
-static int cr_levels_t(aggmg_ctx* ctx, CrDev* cr, double* a, double* b, double* c, int64_t n, double* cond_dev, int* bad_dev) {
+static int cr_levels_t(aggmg_ctx* ctx, CrDev* cr, DevArray<double> a, DevArray<double> b, DevArray<double> c, int64_t n,
+                       double* cond_dev, int* bad_dev) {
   const int mm2 = M * M;
-  auto own = [&](void* p) { cr->owned.push_back(p); };
   while (n > 1) {
     if (M <= 2 && n <= 1024) {  // a candidate for the tail's first level (parallel cyclic reduction, setup_pcr)
-      CrDev::Raw R{(int)cr->lv.size(), n, nullptr, nullptr, nullptr};
-      for (double** p : {&R.a, &R.b, &R.c}) CHECK(dalloc(ctx, p, n * mm2, false));
+      CrDev::Raw R{(int)cr->lv.size(), n, {}, {}, {}};
+      for (DevArray<double>* p : {&R.a, &R.b, &R.c}) CHECK(p->alloc(ctx, n * mm2));
       HIPCHK(hipMemcpyAsync(R.a, a, n * mm2 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
       HIPCHK(hipMemcpyAsync(R.b, b, n * mm2 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
       HIPCHK(hipMemcpyAsync(R.c, c, n * mm2 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-      cr->raw.push_back(R);
+      cr->raw.push_back(std::move(R));
     }
     const int64_t ne = (n + 1) / 2, no = n / 2;
-    double *lu = nullptr, *Za = nullptr, *Zc = nullptr, *a2 = nullptr, *b2 = nullptr, *c2 = nullptr;
-    int32_t* perm = nullptr;
-    CHECK(dalloc(ctx, &lu, no * mm2, false));
-    own(lu);
-    CHECK(dalloc(ctx, &perm, no * M, false));
-    own(perm);
-    Tmp tza, tzc;
-    CHECK(tmp_alloc(ctx, &tza, (size_t)std::max<int64_t>(no, 1) * mm2 * sizeof(double), false));
-    CHECK(tmp_alloc(ctx, &tzc, (size_t)std::max<int64_t>(no, 1) * mm2 * sizeof(double), false));
-    Za = tza.as<double>();
-    Zc = tzc.as<double>();
-    CHECK(dalloc(ctx, &a2, ne * mm2, false));
-    CHECK(dalloc(ctx, &b2, ne * mm2, false));
-    CHECK(dalloc(ctx, &c2, ne * mm2, false));
-    LAUNCH((cr_factor_odd_kernel<M>), no, no, (const double*)a, (const double*)b, (const double*)c, lu, perm, Za, Zc, cond_dev,
-           bad_dev);
+    CrDev::Factors F;   // the level's: fe, fo, lu, perm below
+    DevArray<double> Za, Zc, a2, b2, c2;
+    CHECK(F.lu.alloc(ctx, no * mm2));
+    CHECK(F.perm.alloc(ctx, no * M));
+    CHECK(Za.alloc(ctx, std::max<int64_t>(no, 1) * mm2));
+    CHECK(Zc.alloc(ctx, std::max<int64_t>(no, 1) * mm2));
+    CHECK(a2.alloc(ctx, ne * mm2));
+    CHECK(b2.alloc(ctx, ne * mm2));
+    CHECK(c2.alloc(ctx, ne * mm2));
+    double *lu = F.lu, *fe = nullptr, *fo = nullptr;
+    int32_t* perm = F.perm;
+    LAUNCH((cr_factor_odd_kernel<M>), no, no, (const double*)a, (const double*)b, (const double*)c, lu, perm, Za.get(), Zc.get(),
+           cond_dev, bad_dev);
     LAUNCH((cr_schur_even_kernel<M>), ne, n, ne, (const double*)a, (const double*)b, (const double*)c, (const double*)Za,
            (const double*)Zc, a2, b2, c2);
     HIPCHK(hipStreamSynchronize(ctx->stream));  // Za / Zc leave scope
     // the solve reads the off-diagonal blocks parity-split (forward: even rows, backward: odd rows)
-    double *fe = nullptr, *fo = nullptr;
-    CHECK(dalloc(ctx, &fe, ne * 2 * mm2, false));
-    own(fe);
-    CHECK(dalloc(ctx, &fo, std::max<int64_t>(no, 1) * 2 * mm2, false));
-    own(fo);
+    CHECK(F.fe.alloc(ctx, ne * 2 * mm2));
+    CHECK(F.fo.alloc(ctx, std::max<int64_t>(no, 1) * 2 * mm2));
+    fe = F.fe, fo = F.fo;
     LAUNCH(cr_split_kernel, n * 2 * mm2, n, mm2, (const double*)a, (const double*)c, fe, fo);
     LAUNCH((cr_even_multipliers_kernel<M>), no, no, ne, (const double*)lu, (const int32_t*)perm, fe);
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -761,38 +707,25 @@ static int cr_levels_t(aggmg_ctx* ctx, CrDev* cr, double* a, double* b, double* 
     L.fo = fo;
     L.lu = lu;
     L.perm = perm;
-    (void)hipFree(a), (void)hipFree(c);
-    (void)hipFree(b);  // the diagonal blocks of this level live on in the odd factors and the next level
     cr->lv.push_back(L);
-    a = a2;
-    b = b2;
-    c = c2;
+    cr->owned.push_back(std::move(F));
+    a = std::move(a2);  // (the diagonal blocks of this level live on in the odd factors and the next level)
+    b = std::move(b2);
+    c = std::move(c2);
     n = ne;
-    if ((int)cr->lv.size() > kCrMaxLevels) {
-      (void)hipFree(a), (void)hipFree(b), (void)hipFree(c);
-      return AGGMG_ERR_UNSUPPORTED;
-    }
+    if ((int)cr->lv.size() > kCrMaxLevels) return AGGMG_ERR_UNSUPPORTED;
   }
-  double* lu = nullptr;
-  int32_t* perm = nullptr;
-  CHECK(dalloc(ctx, &lu, mm2, false));
-  own(lu);
-  CHECK(dalloc(ctx, &perm, M, false));
-  own(perm);
-  hipLaunchKernelGGL((cr_factor_last_kernel<M>), dim3(1), dim3(64), 0, ctx->stream, (const double*)b, lu, perm, cond_dev, bad_dev);
+  CrDev::Factors F;
+  CHECK(F.lu.alloc(ctx, mm2));
+  CHECK(F.perm.alloc(ctx, M));
+  hipLaunchKernelGGL((cr_factor_last_kernel<M>), dim3(1), dim3(64), 0, ctx->stream, (const double*)b, F.lu.get(), F.perm.get(),
+                     cond_dev, bad_dev);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  (void)hipFree(a), (void)hipFree(b), (void)hipFree(c);
-  cr->lu_last = lu;
-  cr->perm_last = perm;
+  cr->lu_last = F.lu;
+  cr->perm_last = F.perm;
+  cr->owned.push_back(std::move(F));
   return AGGMG_OK;
-}
-
-static void cr_raw_release(CrDev* c) {
-  for (auto& R : c->raw)
-    for (double* p : {R.a, R.b, R.c})
-      if (p) (void)hipFree(p);
-  c->raw.clear();
 }
 
 // parallel cyclic reduction of the tail's system (internal.hpp CrDev::Pcr): log2(n) levels of multipliers from the blocks
@@ -804,50 +737,38 @@ static int setup_pcr_t(aggmg_ctx* ctx, CrDev* cr, const CrDev::Raw& R) {
   int L = 0;
   while (((int64_t)1 << L) < n) ++L;
   if (L < 1 || L > kPcrMaxLevels) return AGGMG_OK;
-  double *mult = nullptr, *lu = nullptr, *a2 = nullptr, *b2 = nullptr, *c2 = nullptr;
-  int32_t* perm = nullptr;
-  CHECK(dalloc(ctx, &mult, (int64_t)L * n * 2 * MM, true));
-  CHECK(dalloc(ctx, &lu, n * MM, false));
-  CHECK(dalloc(ctx, &perm, n * M, false));
-  Tmp ta, tb, tc;
-  CHECK(tmp_alloc(ctx, &ta, (size_t)n * MM * sizeof(double), false));
-  CHECK(tmp_alloc(ctx, &tb, (size_t)n * MM * sizeof(double), false));
-  CHECK(tmp_alloc(ctx, &tc, (size_t)n * MM * sizeof(double), false));
-  a2 = ta.as<double>(), b2 = tb.as<double>(), c2 = tc.as<double>();
+  DevArray<double> mult, lu, ta, tb, tc;
+  DevArray<int32_t> perm;
+  CHECK(mult.alloc(ctx, (int64_t)L * n * 2 * MM, true));
+  CHECK(lu.alloc(ctx, n * MM));
+  CHECK(perm.alloc(ctx, n * M));
+  CHECK(ta.alloc(ctx, n * MM));
+  CHECK(tb.alloc(ctx, n * MM));
+  CHECK(tc.alloc(ctx, n * MM));
+  double *a2 = ta, *b2 = tb, *c2 = tc;
   Flags bad;
   CHECK(bad.init(ctx, 1));
   double *a = R.a, *b = R.b, *c = R.c;  // (the copies are scratch from here on: ping-pong with a2, b2, c2)
   for (int k = 0; k < L; ++k) {
-    LAUNCH((pcr_factor_kernel<M>), n, n, (const double*)b, lu, perm, bad.d);
+    LAUNCH((pcr_factor_kernel<M>), n, n, (const double*)b, lu.get(), perm.get(), bad.d);
     LAUNCH((pcr_reduce_kernel<M>), n, n, (int64_t)1 << k, (const double*)a, (const double*)b, (const double*)c,
-           (const double*)lu, (const int32_t*)perm, mult + (int64_t)k * n * 2 * MM, a2, b2, c2);
+           (const double*)lu, (const int32_t*)perm, mult.get() + (int64_t)k * n * 2 * MM, a2, b2, c2);
     std::swap(a, a2), std::swap(b, b2), std::swap(c, c2);
   }
-  LAUNCH((pcr_factor_kernel<M>), n, n, (const double*)b, lu, perm, bad.d);
+  LAUNCH((pcr_factor_kernel<M>), n, n, (const double*)b, lu.get(), perm.get(), bad.d);
   int b1 = 0;
   CHECK(bad.read(ctx, &b1));
-  if (b1) {
-    (void)hipFree(mult), (void)hipFree(lu), (void)hipFree(perm);
-    return AGGMG_OK;
-  }
-  cr->owned.push_back(mult), cr->owned.push_back(lu), cr->owned.push_back(perm);
+  if (b1) return AGGMG_OK;
   cr->pcr.n = (int)n;
   cr->pcr.L = L;
-  cr->pcr.mult = mult;
-  cr->pcr.lu = lu;
-  cr->pcr.perm = perm;
+  cr->pcr.mult = std::move(mult);
+  cr->pcr.lu = std::move(lu);
+  cr->pcr.perm = std::move(perm);
   cr->pcr.valid = true;
   return AGGMG_OK;
 }
 
-static void cr_release(CrDev* c) {
-  cr_raw_release(c);
-  for (void* p : c->owned)
-    if (p) (void)hipFree(p);
-  *c = CrDev();
-}
-
-void cr_discard(CrDev* c) { cr_release(c); }
+void cr_discard(CrDev* c) { *c = CrDev(); }
 
 // probe vector of the factorisation check: entries in [-1, 1) from a hash of the index (no structure a
 // tridiagonal stencil could annihilate)
@@ -956,50 +877,46 @@ int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr) {
   cr->m = m;
   cr->n0 = n;
   cr->N = N;
-  double *a = nullptr, *b = nullptr, *c = nullptr;
-  CHECK(dalloc(ctx, &a, n * mm2, true));
-  CHECK(dalloc(ctx, &b, n * mm2, true));
-  CHECK(dalloc(ctx, &c, n * mm2, true));
+  DevArray<double> a, b, c;
+  CHECK(a.alloc(ctx, n * mm2, true));
+  CHECK(b.alloc(ctx, n * mm2, true));
+  CHECK(c.alloc(ctx, n * mm2, true));
   LAUNCH(cr_pack_kernel, n * m, N, m, cp, rv, vv, a, b, c);
-  Tmp condt;
-  CHECK(tmp_alloc(ctx, &condt, sizeof(double), true));
+  DevArray<double> condt;
+  CHECK(condt.alloc(ctx, 1, true));
   CHECK(bad.clear(ctx));
   int st = AGGMG_OK;
   switch (m) {
 #define CASE(MM) \
   case MM:       \
-    st = cr_levels_t<MM>(ctx, cr, a, b, c, n, condt.as<double>(), bad.d); \
+    st = cr_levels_t<MM>(ctx, cr, std::move(a), std::move(b), std::move(c), n, condt, bad.d); \
     break;
     CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
 #undef CASE
   }
   if (st == AGGMG_ERR_UNSUPPORTED) {  // too many levels
-    cr_release(cr);
+    cr_discard(cr);
     return AGGMG_OK;
   }
   if (st != AGGMG_OK) {
-    cr_release(cr);
+    cr_discard(cr);
     return st;
   }
   int b1 = 0;
   CHECK(bad.read(ctx, &b1));
   double cond = 0.0;
-  HIPCHK(hipMemcpyAsync(&cond, condt.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(&cond, condt, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   cr->cond_est = cond;
   if (b1 || !(cond < 1e13)) {  // a pivot block is singular or close to it: keep the pivoted banded LU
-    cr_release(cr);
+    cr_discard(cr);
     return AGGMG_OK;
   }
   // plan: chunk stages (one workgroup per 2^q-block chunk) until what is left fits the
   // single-workgroup tail (cr_kernels.hpp)
   const int nl = (int)cr->lv.size();
   auto level_n = [&](int l) -> int64_t { return l < nl ? cr->lv[l].n : 1; };
-  auto dz = [&](int64_t len, double** out) -> int {
-    CHECK(dalloc(ctx, out, len, true));
-    cr->owned.push_back(*out);
-    return AGGMG_OK;
-  };
+  auto dz = [&](int64_t len, DevArray<double>* out) -> int { return out->alloc(ctx, len, true); };
   // (AGGMG_CR_TAIL_ROWS / AGGMG_CR_MAX_Q shrink the tail and the chunks: the tests use them to run the
   // several-stage plan of systems beyond 2^24 rows at sizes a CPU reference solves in seconds)
   auto env_int = [](const char* name, int dflt, int lo, int hi) {
@@ -1020,7 +937,7 @@ int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr) {
     // (large chunks -- every thread at least one sub-chunk of the streaming first step -- as long as a few hundred
     // workgroups remain; host_plan.hpp)
     if (!cr_plan_solve(ln, m, tail_rows, max_q, fmax, minwg, &plan)) {
-      cr_release(cr);
+      cr_discard(cr);
       return AGGMG_OK;
     }
   }
@@ -1033,7 +950,7 @@ int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr) {
     S.xq = S.partL + nb;
     if (S.stack_stride > 0) CHECK(dz((S.n_out + 1) * (int64_t)S.stack_stride, &S.stack));
     if (S.mid_total > 0) CHECK(dz(S.mid_total, &S.mid));
-    cr->st.push_back(S);
+    cr->st.push_back(std::move(S));
   }
   static_cast<CrStagePlan&>(cr->tail) = plan.tail;
   if (cr->tail.mid_total > 0) CHECK(dz(cr->tail.mid_total, &cr->tail.mid));
@@ -1053,15 +970,13 @@ int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr) {
       total += al(L.n_even * 2 * mm * sizeof(double)) + al(no * 2 * mm * sizeof(double)) + al(no * mm * sizeof(double)) +
                al(no * m * sizeof(int32_t));
     }
-    char* arena = nullptr;
-    HIPCHK(hipMalloc((void**)&arena, total));
+    DevArray<char>& arena = cr->arena;
+    CHECK(arena.alloc(ctx, (int64_t)total));
     size_t off = 0;
-    std::vector<void*> old;
     auto move = [&](const void* src, size_t bytes) -> void* {
       void* dst = arena + off;
       (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream);
       off += al(bytes);
-      old.push_back(const_cast<void*>(src));
       return dst;
     };
     for (int l = pf; l < nl; ++l) {
@@ -1076,12 +991,7 @@ int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr) {
     cr->perm_last = (const int32_t*)move(cr->perm_last, m * sizeof(int32_t));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (void* q : old) {
-      auto it = std::find(cr->owned.begin(), cr->owned.end(), q);
-      if (it != cr->owned.end()) cr->owned.erase(it);
-      (void)hipFree(q);
-    }
-    cr->owned.push_back(arena);
+    for (int l = pf; l <= nl; ++l) cr->owned[l] = CrDev::Factors();   // (entry nl: the last block's)
   }
   // the tail's system by parallel cyclic reduction where it applies (AGGMG_CR_PCR=0: off)
   if (m <= 2 && cr->tail.nsteps >= 1 && env_int("AGGMG_CR_PCR", 1, 0, 1)) {
@@ -1098,18 +1008,12 @@ int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr) {
         }
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  cr_raw_release(cr);
+  cr->raw.clear();
   if (n * m != N) {
     CHECK(dz(n * m, &cr->d0));
     CHECK(dz(n * m, &cr->x0));
   }
-  {
-    void* t = nullptr;
-    HIPCHK(hipMalloc(&t, sizeof(unsigned int)));
-    cr->owned.push_back(t);
-    cr->ticket = (unsigned int*)t;
-    HIPCHK(hipMemsetAsync(t, 0, sizeof(unsigned int), ctx->stream));
-  }
+  CHECK(cr->ticket.alloc(ctx, 1, true));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   cr->valid = true;
   return AGGMG_OK;
@@ -1158,20 +1062,20 @@ static int cgt_build_impl(aggmg_ctx* ctx, aggmg_smoother* sm, const int64_t* ele
   g->m = m;
   g->ne = ne;
   g->N = N;
-  Tmp el64;
-  CHECK(tmp_alloc(ctx, &el64, (size_t)nel * m1 * 8, false));
+  DevArray<int64_t> el64;
+  CHECK(el64.alloc(ctx, nel * m1));
   if (generate) {
-    LAUNCH(chain_generate_elements_kernel, nel, nel, m, el64.as<int64_t>());
+    LAUNCH(chain_generate_elements_kernel, nel, nel, m, el64.get());
   } else {
-    HIPCHK(hipMemcpyAsync(el64.p, elems, (size_t)nel * m1 * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(el64, elems, (size_t)nel * m1 * 8, hipMemcpyHostToDevice, ctx->stream));
   }
-  CHECK(dalloc(ctx, &g->perm, Np, false));
-  CHECK(dalloc(ctx, &g->inv, N, false));
+  CHECK(g->perm.alloc(ctx, Np));
+  CHECK(g->inv.alloc(ctx, N));
   HIPCHK(hipMemsetAsync(g->perm, 0xFF, (size_t)Np * 4, ctx->stream));
   HIPCHK(hipMemsetAsync(g->inv, 0xFF, (size_t)N * 4, ctx->stream));
   Flags f;
   CHECK(f.init(ctx, 4));
-  LAUNCH(chain_perm_kernel, nel, nel, m, N, el64.as<int64_t>(), base, g->perm, f.d);
+  LAUNCH(chain_perm_kernel, nel, nel, m, N, el64.get(), base, g->perm, f.d);
   LAUNCH(perm_invert_kernel, Np, Np, (const int32_t*)g->perm, g->inv, f.d);
   LAUNCH(perm_cover_kernel, N, N, (const int32_t*)g->inv, f.d);
   LAUNCH(chain_affine_check_kernel, Np, ne, m, (const int32_t*)g->perm, f.d);
@@ -1180,9 +1084,9 @@ static int cgt_build_impl(aggmg_ctx* ctx, aggmg_smoother* sm, const int64_t* ele
   if (h[0]) return fail(ctx, AGGMG_ERR_DIMENSION, "aggmg_jacobi_setup_elements: node index out of range");
   if (h[1]) return AGGMG_OK;  // not a chain: generic path
   g->affine = !h[3];
-  CHECK(dalloc(ctx, &g->dblk, Np * m, true));
-  CHECK(dalloc(ctx, &g->subrow, Np, true));
-  CHECK(dalloc(ctx, &g->supcol, Np, true));
+  CHECK(g->dblk.alloc(ctx, Np * m, true));
+  CHECK(g->subrow.alloc(ctx, Np, true));
+  CHECK(g->supcol.alloc(ctx, Np, true));
   LAUNCH(chain_scatter_kernel, N, N, m, (const int32_t*)g->inv, (const int32_t*)A->csc.rowptr, (const int32_t*)A->csc.colind,
          (const double*)A->csc.vals, g->dblk, g->subrow, g->supcol, f.d);
   LAUNCH(chain_pad_kernel, Np, Np, m, (const int32_t*)g->perm, g->dblk);
@@ -1202,8 +1106,8 @@ int cgt_attach_schwarz(aggmg_ctx* ctx, aggmg_smoother* sm, int sw) {
   const int M = g.m;
   const int64_t nel = g.ne - 1;
   if (sm->m != M + 1 || sm->nb != nel) return AGGMG_OK;
-  CHECK(dalloc(ctx, &g.zrows, g.ne * M * (M + 1), true));
-  CHECK(dalloc(ctx, &g.zlast, g.ne * (M + 1), true));
+  CHECK(g.zrows.alloc(ctx, g.ne * M * (M + 1), true));
+  CHECK(g.zlast.alloc(ctx, g.ne * (M + 1), true));
   LAUNCH(chain_schwarz_rows_kernel, nel * (M + 1), nel, M, (const double*)sm->binv, g.zrows, g.zlast);
   HIPCHK(hipStreamSynchronize(ctx->stream));
   g.sw = sw;
@@ -1229,7 +1133,7 @@ int cgt_build_transfer(aggmg_ctx* ctx, const aggmg_op* L, const CgtDev& f, const
   if (nel > 0 && Nc > 1 && (Nc - 1) % nel == 0 && (Nc - 1) / nel <= 8 && M >= 2) {
     const int mc = (int)((Nc - 1) / nel);
     int32_t *cperm = nullptr, *cinv = nullptr;
-    Tmp own_perm, own_inv;
+    DevArray<int32_t> own_perm, own_inv;
     bool have = false;
     if (coarse && coarse->N == Nc && coarse->m == mc && coarse->ne == f.ne) {
       cperm = coarse->perm;
@@ -1239,30 +1143,30 @@ int cgt_build_transfer(aggmg_ctx* ctx, const aggmg_op* L, const CgtDev& f, const
       // the coarse level carries no element lists (the coarsest level has no smoother): read its chain
       // off L -- a coarse column holding a fine vertex row is that block's vertex, the others are the
       // interior nodes of the one element whose fine rows they touch, in ascending order
-      CHECK(tmp_alloc(ctx, &own_perm, (size_t)f.ne * mc * 4, false));
-      CHECK(tmp_alloc(ctx, &own_inv, (size_t)Nc * 4, false));
-      cperm = own_perm.as<int32_t>();
-      cinv = own_inv.as<int32_t>();
+      CHECK(own_perm.alloc(ctx, f.ne * mc));
+      CHECK(own_inv.alloc(ctx, Nc));
+      cperm = own_perm;
+      cinv = own_inv;
       HIPCHK(hipMemsetAsync(cperm, 0xFF, (size_t)f.ne * mc * 4, ctx->stream));
       HIPCHK(hipMemsetAsync(cinv, 0xFF, (size_t)Nc * 4, ctx->stream));
-      Tmp slots;
-      CHECK(tmp_alloc(ctx, &slots, (size_t)f.ne * 4, true));
+      DevArray<int32_t> slots;
+      CHECK(slots.alloc(ctx, f.ne, true));
       LAUNCH(chain_coarse_vertices_kernel, Nc, Nc, M, mc, (const int32_t*)f.inv, cp, rv, cperm, cinv, fl.d);
-      LAUNCH(chain_coarse_interiors_kernel, Nc, Nc, M, mc, (const int32_t*)f.inv, cp, rv, cperm, cinv, slots.as<int32_t>(), fl.d);
-      LAUNCH(chain_coarse_sort_kernel, f.ne, f.ne, mc, cperm, cinv, (const int32_t*)slots.as<int32_t>(), nel, fl.d);
+      LAUNCH(chain_coarse_interiors_kernel, Nc, Nc, M, mc, (const int32_t*)f.inv, cp, rv, cperm, cinv, slots.get(), fl.d);
+      LAUNCH(chain_coarse_sort_kernel, f.ne, f.ne, mc, cperm, cinv, (const int32_t*)slots, nel, fl.d);
       CHECK(fl.read(ctx, h));
       have = !h[1];
       CHECK(fl.clear(ctx));
     }
     if (have) {
       const int w = mc + 1;
-      double* l = nullptr;
-      CHECK(dalloc(ctx, &l, Np * w, true));
+      DevArray<double> l;
+      CHECK(l.alloc(ctx, Np * w, true));
       LAUNCH(chain_transfer_scatter_kernel, Nc, Nc, M, mc, (const int32_t*)f.inv, (const int32_t*)cinv, cp, rv, vv, l, fl.d);
       CHECK(fl.read(ctx, h));
       if (!h[0]) {
-        out->l = l;
-        CHECK(dalloc(ctx, &out->cperm, f.ne * mc, false));
+        out->l = std::move(l);
+        CHECK(out->cperm.alloc(ctx, f.ne * mc));
         HIPCHK(hipMemcpyAsync(out->cperm, cperm, (size_t)f.ne * mc * 4, hipMemcpyDeviceToDevice, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         out->type = kTrChain;
@@ -1272,7 +1176,7 @@ int cgt_build_transfer(aggmg_ctx* ctx, const aggmg_op* L, const CgtDev& f, const
         *ok = true;
         return AGGMG_OK;
       }
-      (void)hipFree(l);
+      l.reset();
       CHECK(fl.clear(ctx));
     }
   }
@@ -1285,19 +1189,15 @@ int cgt_build_transfer(aggmg_ctx* ctx, const aggmg_op* L, const CgtDev& f, const
     if (nec == 0 || nel % nec) continue;
     const int64_t rho = nel / nec;
     if (rho > 64 || rho * 4 > tile_blocks) continue;
-    double *l = nullptr, *lp = nullptr;
-    CHECK(dalloc(ctx, &l, Np * mc, true));
-    CHECK(dalloc(ctx, &lp, f.ne * mc, true));
+    DevArray<double> l, lp;
+    CHECK(l.alloc(ctx, Np * mc, true));
+    CHECK(lp.alloc(ctx, f.ne * mc, true));
     CHECK(fl.clear(ctx));
     LAUNCH(agg_transfer_scatter_kernel, Nc, Nc, M, mc, rho, (const int32_t*)f.inv, cp, rv, vv, l, lp, fl.d);
     CHECK(fl.read(ctx, h));
-    if (h[0]) {
-      (void)hipFree(l);
-      (void)hipFree(lp);
-      continue;
-    }
-    out->l = l;
-    out->lp = lp;
+    if (h[0]) continue;
+    out->l = std::move(l);
+    out->lp = std::move(lp);
     out->type = kTrAgg;
     out->mc = mc;
     out->rho = (int)rho;

@@ -166,13 +166,6 @@ __global__ __launch_bounds__(kSetupThreads) void spsub_kernel(int64_t ncols, con
   if (!FILL) counts[j] = cnt;
 }
 
-struct Tmp {
-  void* p = nullptr;
-  ~Tmp() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 // int32 counts widened on the fly: the total of a product can pass 2^31 long before any single count does
 struct WidenCount {
   __host__ __device__ int64_t operator()(int32_t v) const { return (int64_t)v; }
@@ -183,37 +176,36 @@ struct WidenCount {
 // offsets.  Returns AGGMG_ERR_UNSUPPORTED (nothing scanned) when the total does not fit int32 indices.
 int scan_counts(aggmg_ctx* ctx, int32_t* counts_np1, int32_t* colptr, int64_t n, int64_t* total, const char* who) {
   hipcub::TransformInputIterator<int64_t, WidenCount, const int32_t*> wide(counts_np1, WidenCount());
-  Tmp sum;
-  HIPCHK(hipMalloc(&sum.p, sizeof(int64_t)));
+  DevArray<int64_t> sum;
+  CHECK(sum.alloc(ctx, 1));
   size_t rbytes = 0;
-  HIPCHK(hipcub::DeviceReduce::Sum(nullptr, rbytes, wide, (int64_t*)sum.p, (int)n, ctx->stream));
-  Tmp rt;
-  HIPCHK(hipMalloc(&rt.p, std::max<size_t>(rbytes, 8)));
-  HIPCHK(hipcub::DeviceReduce::Sum(rt.p, rbytes, wide, (int64_t*)sum.p, (int)n, ctx->stream));
+  HIPCHK(hipcub::DeviceReduce::Sum(nullptr, rbytes, wide, sum.get(), (int)n, ctx->stream));
+  DevArray<char> rt;
+  CHECK(rt.alloc(ctx, (int64_t)rbytes));
+  HIPCHK(hipcub::DeviceReduce::Sum(rt.get(), rbytes, wide, sum.get(), (int)n, ctx->stream));
   int64_t tot = 0;
-  HIPCHK(hipMemcpyAsync(&tot, sum.p, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(&tot, sum, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   *total = tot;
   if (tot >= ((int64_t)1 << 31))
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, std::string(who) + ": result has " + std::to_string(tot) + " >= 2^31 entries (int32 device indices)");
   size_t bytes = 0;
   HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, counts_np1, colptr, (int)(n + 1), ctx->stream));
-  Tmp t;
-  HIPCHK(hipMalloc(&t.p, std::max<size_t>(bytes, 8)));
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(t.p, bytes, counts_np1, colptr, (int)(n + 1), ctx->stream));
+  DevArray<char> t;
+  CHECK(t.alloc(ctx, (int64_t)bytes));
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(t.get(), bytes, counts_np1, colptr, (int)(n + 1), ctx->stream));
   return AGGMG_OK;
 }
 
-int new_op(aggmg_ctx* ctx, int64_t m, int64_t n, int kind, std::unique_ptr<aggmg_op>* out, int32_t** counts) {
+int new_op(aggmg_ctx* ctx, int64_t m, int64_t n, int kind, std::unique_ptr<aggmg_op>* out, DevArray<int32_t>* counts) {
   auto op = std::make_unique<aggmg_op>();
   op->m = m;
   op->n = n;
   op->kind = kind;
   op->csc.nrows = n;
   op->csc.ncols = m;
-  HIPCHK(hipMalloc((void**)&op->csc.rowptr, (size_t)(n + 1) * sizeof(int32_t)));
-  HIPCHK(hipMalloc((void**)counts, (size_t)(n + 1) * sizeof(int32_t)));
-  HIPCHK(hipMemsetAsync(*counts, 0, (size_t)(n + 1) * sizeof(int32_t), ctx->stream));
+  CHECK(op->csc.rowptr.alloc(ctx, n + 1));
+  CHECK(counts->alloc(ctx, n + 1, true));
   *out = std::move(op);
   return AGGMG_OK;
 }
@@ -221,9 +213,8 @@ int new_op(aggmg_ctx* ctx, int64_t m, int64_t n, int kind, std::unique_ptr<aggmg
 int alloc_entries(aggmg_ctx* ctx, aggmg_op* op, int64_t nnz) {
   op->nnz = nnz;
   op->csc.nnz = nnz;
-  HIPCHK(hipMalloc((void**)&op->csc.colind, (size_t)std::max<int64_t>(nnz, 1) * sizeof(int32_t)));
-  HIPCHK(hipMalloc((void**)&op->csc.vals, (size_t)std::max<int64_t>(nnz, 1) * sizeof(double)));
-  return AGGMG_OK;
+  CHECK(op->csc.colind.alloc(ctx, nnz));
+  return op->csc.vals.alloc(ctx, nnz);
 }
 
 int check_kind(aggmg_ctx* ctx, int kind, const char* who) {
@@ -243,10 +234,8 @@ extern "C" int aggmg_bd_sp_apply(aggmg_ctx* ctx, aggmg_smoother* bd, aggmg_op* S
   HIPCHK(hipSetDevice(ctx->device));
   const int m = (int)bd->m;
   std::unique_ptr<aggmg_op> op;
-  int32_t* counts = nullptr;
+  DevArray<int32_t> counts;
   CHECK(new_op(ctx, S->m, S->n, kind, &op, &counts));
-  Tmp cown;
-  cown.p = counts;
   const int64_t nc = S->n;
   if (nc) hipLaunchKernelGGL(bdsp_count_kernel, dim3(grid_for(nc)), dim3(kSetupThreads), 0, ctx->stream, nc, m,
                              (const int32_t*)S->csc.rowptr, (const int32_t*)S->csc.colind, counts);
@@ -270,15 +259,10 @@ extern "C" int aggmg_sp_matmul(aggmg_ctx* ctx, aggmg_op* A, aggmg_op* B, int kin
   if (A->n != B->m) return fail(ctx, AGGMG_ERR_DIMENSION, "aggmg_sp_matmul: DimensionMismatch");
   HIPCHK(hipSetDevice(ctx->device));
   std::unique_ptr<aggmg_op> op;
-  int32_t* counts = nullptr;
+  DevArray<int32_t> counts;
   CHECK(new_op(ctx, A->m, B->n, kind, &op, &counts));
-  Tmp cown;
-  cown.p = counts;
-  int* err = nullptr;
-  HIPCHK(hipMalloc((void**)&err, sizeof(int)));
-  Tmp eown;
-  eown.p = err;
-  HIPCHK(hipMemsetAsync(err, 0, sizeof(int), ctx->stream));
+  DevArray<int> err;
+  CHECK(err.alloc(ctx, 1, true));
   const int64_t nc = B->n;
   const int32_t *acp = A->csc.rowptr, *arv = A->csc.colind, *bcp = B->csc.rowptr, *brv = B->csc.colind;
   const double *av = A->csc.vals, *bv = B->csc.vals;
@@ -309,10 +293,8 @@ extern "C" int aggmg_sp_sub(aggmg_ctx* ctx, aggmg_op* A, aggmg_op* B, int kind, 
   if (A->m != B->m || A->n != B->n) return fail(ctx, AGGMG_ERR_DIMENSION, "aggmg_sp_sub: DimensionMismatch");
   HIPCHK(hipSetDevice(ctx->device));
   std::unique_ptr<aggmg_op> op;
-  int32_t* counts = nullptr;
+  DevArray<int32_t> counts;
   CHECK(new_op(ctx, A->m, A->n, kind, &op, &counts));
-  Tmp cown;
-  cown.p = counts;
   const int64_t nc = A->n;
   const int32_t *acp = A->csc.rowptr, *arv = A->csc.colind, *bcp = B->csc.rowptr, *brv = B->csc.colind;
   const double *av = A->csc.vals, *bv = B->csc.vals;
@@ -335,12 +317,11 @@ extern "C" int aggmg_sp_sub(aggmg_ctx* ctx, aggmg_op* A, aggmg_op* B, int kind, 
 extern "C" int aggmg_debug_scan_counts(aggmg_ctx* ctx, const int32_t* counts_host, int64_t n, int64_t* total) {
   if (!ctx || !counts_host || !total || n < 0 || n >= ((int64_t)1 << 31) - 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_debug_scan_counts: bad argument");
   HIPCHK(hipSetDevice(ctx->device));
-  Tmp c, p;
-  HIPCHK(hipMalloc(&c.p, (size_t)(n + 1) * sizeof(int32_t)));
-  HIPCHK(hipMalloc(&p.p, (size_t)(n + 1) * sizeof(int32_t)));
-  HIPCHK(hipMemsetAsync(c.p, 0, (size_t)(n + 1) * sizeof(int32_t), ctx->stream));
-  if (n) HIPCHK(hipMemcpyAsync(c.p, counts_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  return scan_counts(ctx, (int32_t*)c.p, (int32_t*)p.p, n, total, "aggmg_debug_scan_counts");
+  DevArray<int32_t> c, p;
+  CHECK(c.alloc(ctx, n + 1, true));
+  CHECK(p.alloc(ctx, n + 1));
+  if (n) HIPCHK(hipMemcpyAsync(c, counts_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  return scan_counts(ctx, c, p, n, total, "aggmg_debug_scan_counts");
 }
 
 // the transposed operator as an operator of its own (L' of L'*X*L): its CSC arrays are the row-gather CSR of
@@ -359,9 +340,9 @@ extern "C" int aggmg_op_transpose(aggmg_ctx* ctx, aggmg_op* A, int kind, aggmg_o
   op->csc.nrows = A->m;
   op->csc.ncols = A->n;
   op->csc.nnz = A->nnz;
-  HIPCHK(hipMalloc((void**)&op->csc.rowptr, (size_t)(A->m + 1) * sizeof(int32_t)));
-  HIPCHK(hipMalloc((void**)&op->csc.colind, (size_t)std::max<int64_t>(A->nnz, 1) * sizeof(int32_t)));
-  HIPCHK(hipMalloc((void**)&op->csc.vals, (size_t)std::max<int64_t>(A->nnz, 1) * sizeof(double)));
+  CHECK(op->csc.rowptr.alloc(ctx, A->m + 1));
+  CHECK(op->csc.colind.alloc(ctx, A->nnz));
+  CHECK(op->csc.vals.alloc(ctx, A->nnz));
   HIPCHK(hipMemcpyAsync(op->csc.rowptr, A->csr.rowptr, (size_t)(A->m + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
   if (A->nnz) {
     HIPCHK(hipMemcpyAsync(op->csc.colind, A->csr.colind, (size_t)A->nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));

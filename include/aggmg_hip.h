@@ -243,6 +243,10 @@ int aggmg_debug_scan_counts(aggmg_ctx* ctx, const int32_t* counts_host, int64_t 
  * coarsest solve's streaming steps (src/solvers.jl:39) are held against in DESIGN.md section 5. */
 int aggmg_debug_stream_copy(aggmg_ctx* ctx, void* dst, const void* src, int64_t nbytes, int workgroups, int mode,
                             double* ms_out);
+/* Test aid for leaks: the device allocations the library itself holds in this process at the moment -- their number and
+ * the bytes asked for -- over all contexts and handles (no context argument, like aggmg_version).  Caller-owned memory
+ * is not counted: aggmg_dev_alloc's, and all page-locked host memory.  Either pointer may be NULL. */
+int aggmg_debug_device_memory(int64_t* live_allocations, int64_t* live_bytes);
 
 /* ---- fused hot-path operations -------------------------------------------------------------- */
 /* nsweeps x  `u += apply_smoother(S, b - A*u; alpha)`   src/solvers.jl:32-35,43-46, :199 */

@@ -4,7 +4,8 @@
    the serial iterate must equal the unsanitized library's bit for bit;
  * the library's host-only planners (agglomerationmultigrid1d_amd/csrc/host_plan.hpp: cyclic-reduction step / stage plans,
    tile subsets of a launch, staging slices, the chunk route of a partitioned run) as a host-compiled unit test under
-   AddressSanitizer + UBSan.
+   AddressSanitizer + UBSan;
+ * the owner of the library's device memory (agglomerationmultigrid1d_amd/csrc/devmem.hpp) over malloc / free, the same way.
 Skipped (not failed) where a sanitizer runtime is missing from the toolchain."""
 import os
 import shutil
@@ -102,3 +103,17 @@ def test_host_planners_under_asan_ubsan():
     assert "host_plan OK" in r.stdout
     # the sweep of the checkpoint reservation saw the formula it replaces fall short (the defect it was written for)
     assert "former formula 2 ne / TE + 2: TE 128 halo 7 ratio 60 ne 7680 -> 128 tiles > 122 reserved" in r.stdout
+
+
+def test_device_memory_owner_under_asan_ubsan():
+    """moves, reserve, release / reset and a vector of structs holding owners; the leak check is the assertion that
+    nothing is lost"""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    d = os.path.join(ROOT, "tests", "host")
+    _make(d, "test_devmem")
+    r = subprocess.run([os.path.join(d, "test_devmem")], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert not any(s in r.stderr for s in BAD), r.stderr[-3000:]
+    assert "devmem OK" in r.stdout
