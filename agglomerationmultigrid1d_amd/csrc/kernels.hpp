@@ -818,8 +818,8 @@ __device__ __forceinline__ double group_bcast(double v, int j) {
 // the coupling entry scol_e[i] into sc.  Lane i reads only its own run D[i][i..M-1] of the packed triangle; a lower
 // entry D[i][j] is rebuilt from lane j's D[j][i], moved across the group by DPP (no LDS, no memory traffic).  The
 // coupling entry's mirror q_{e-1}[i] lies in lines the tile has loaded already; the escape is always taken at e = 0.
-// DICT: e is the element's class and lv holds the dictionary's arrays; the mirror row is the record's own copy.
-template <int M, bool DICT = false>
+// (The dictionary variant of btd_fused_kernel decodes its records with the same expressions, all slabs at once.)
+template <int M>
 __device__ __forceinline__ void sym_residual_row(const BtdLevel& lv, int64_t e, int i, double (&dk)[M], double& sc) {
   constexpr int T = M * (M + 1) / 2;
   const int64_t row = e * M + i;
@@ -839,7 +839,7 @@ __device__ __forceinline__ void sym_residual_row(const BtdLevel& lv, int64_t e, 
     if (j < i) dk[j] = d == kSymResidualEscape ? lv.dblk[row * M + j] : sym_residual_decode(mir, d);
   }
   const int dc = (int)(int8_t)(w >> 24);
-  sc = dc == kSymResidualEscape ? lv.scol[row] : sym_residual_decode(DICT ? lv.qmir[row] : lv.qrow[row - M], dc);
+  sc = dc == kSymResidualEscape ? lv.scol[row] : sym_residual_decode(lv.qrow[row - M], dc);
 }
 
 // sum of a * b over the group, W = 2, 4: the first step's addition fused to the lane's own product, fma(a, b, partner's
@@ -1004,7 +1004,9 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
   double* buf1 = lds + (TE + 2) * M + M;
 
   const int tid = threadIdx.x;
-  const bool active = tid < EPS * M;
+  // (dictionary variant: every thread holds a row where the slab fills the workgroup -- a compile-time fact there, so the
+  // slabs of a sweep share one basic block)
+  const bool active = (DICT && EPS * M == NT) || tid < EPS * M;
   const int le = tid / M;
   const int i = tid - le * M;
   const int64_t ne = a.lv.ne;
@@ -1012,7 +1014,7 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
   // owned elements x in [own0, own1) of the tile; with agglomerates of different sizes below, on agglomerate
   // boundaries (FusedArgs::agg_shift; two dependent index loads, issued here with the tile's other streams)
   int own0 = a.halo_left, own1 = a.halo_left + a.owned;
-  if (a.par_out && a.agg_shift >= 0 && (a.lf_out || a.ld_out)) {
+  if (!DICT && a.par_out && a.agg_shift >= 0 && (a.lf_out || a.ld_out)) {   // (dictionary launches: equal agglomerates)
     const int64_t n0 = e0 + a.halo_left, n1 = n0 + a.owned;
     const int64_t s0 = n0 < ne ? a.first_out[a.par_out[n0]] : ne;
     const int64_t s1 = n1 < ne ? a.first_out[a.par_out[n1]] : ne;
@@ -1042,116 +1044,222 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
   [[maybe_unused]] int ce[NS];                   // DICT: the elements' classes
 
   // ---- load phase: everything this tile needs from HBM, issued up front --------------------
+  if constexpr (DICT) {
+    // Dictionary variant, in two groups.  First the streams that depend on nothing the tile has loaded -- cls, b, u_in
+    // and the coarse pair (its index is arithmetic) -- for ALL slabs, straight-line: a lane outside the level reads
+    // the nearest element inside it and its values are masked afterwards, so no load sits behind a branch on valid[s]
+    // and none waits for another.  Then the records of all slabs, indexed by the classes, from cache; their one wait is
+    // at first use.  What the launcher guarantees of a dictionary launch is taken as fact here: two-mode transfers of
+    // equal agglomerates (mc == 2, rho > 0, no parent arrays), the packed inverse, no (L'D) restriction.
+    // The expressions of a valid element are the plain variant's.  A lane outside the level keeps the record of
+    // the element it read instead of zeros: its update is forced to zero in the sweeps and it owns no row, and no cross-lane sum
+    // mixes it with a valid element (the lanes of a group share one element).
+    constexpr int T = M * (M + 1) / 2;
+    const bool pro = a.lf_in != nullptr;
+    // x in [xlo, xhi] lies inside the level; a lane outside reads the nearest element that does -- every address is
+    // the tile's (launch-uniform) base plus a small lane offset.  (The launcher's tiles all own an element of the
+    // level, so xhi >= halo_left; a tile past the level would leave here, before any barrier.)
+    const int64_t rem = ne - 1 - e0;
+    if (rem < 0) return;
+    const int xlo = e0 < 0 ? (int)-e0 : 0, xhi = rem < TE - 1 ? (int)rem : TE - 1;
+    unsigned xc[NS];   // the element's place in the tile, or the nearest one inside the level
+    double2 u2[NS], l2[NS];
+    const uint16_t* const cls0 = a.lv.cls + e0;
+    const double* const b0 = a.b + e0 * M;
 #pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    const int x = s * EPS + le;
-    const int64_t e = e0 + x;
-    valid[s] = active && e >= 0 && e < ne;
-    const int64_t row = e * M + i;
-    uu[s] = 0.0;
-    bb[s] = 0.0;
+    for (int s = 0; s < NS; ++s) {
+      const int x = s * EPS + le;
+      valid[s] = active && x >= xlo && x <= xhi;   // 0 <= e0 + x < ne
+      xc[s] = (unsigned)(x < xlo ? xlo : x > xhi ? xhi : x);
+      ce[s] = (int)cls0[xc[s]];
+    }
 #pragma unroll
-    for (int j = 0; j < M; ++j) bi[s][j] = 0.0;
-    if constexpr (DICT) ce[s] = valid[s] ? (int)a.lv.cls[e] : 0;
-    // the operator's record: the element's own, or (DICT) its class's in the dictionary
-    const int64_t oe = DICT ? (int64_t)ce[s] : e;
-    const int64_t orow = oe * M + i;
-    if (valid[s]) {
-      if (need_g) {
-        if (SYM) {  // row i of the symmetric inverse out of its packed upper triangle
-          constexpr int T = M * (M + 1) / 2;
+    for (int s = 0; s < NS; ++s) bb[s] = b0[xc[s] * M + i];
+    {
+      // (no first iterate: the load goes to b's line, which is on its way already, and is dropped -- no branch, so the
+      // load group stays straight-line)
+      const double* const u0 = (a.u_in ? a.u_in : a.b) + e0 * M;
 #pragma unroll
-          for (int j = 0; j < M; ++j) {
-            const int lo_ = i < j ? i : j, hi_ = i < j ? j : i;
-            bi[s][j] = a.lv.bsym[oe * T + lo_ * M - (lo_ * (lo_ - 1)) / 2 + (hi_ - lo_)];
-          }
-        } else {
+      for (int s = 0; s < NS; ++s) uu[s] = u0[xc[s] * M + i];
+      if (!a.u_in) {
 #pragma unroll
-          for (int j = 0; j < M; ++j) bi[s][j] = AGGMG_LD(a.lv.binv[row * M + j]);
-        }
+        for (int s = 0; s < NS; ++s) uu[s] = 0.0;
       }
-      bb[s] = a.b[row];
-      if (a.u_in) uu[s] = a.u_in[row];
-      if (pre2) {
-        if (a.lf1_out && !a.ld_out) {   // unit first column: 1.0 * r is r, bit for bit what the stored 1.0 gives
-          l2x[s] = 1.0;
-          l2y[s] = AGGMG_LD(a.lf1_out[orow]);
-        } else {
-          const double2 t2 = *reinterpret_cast<const double2*>(lfo_pre + orow * 2);
-          l2x[s] = t2.x;
-          l2y[s] = t2.y;
-        }
-      }
-      if (CMP) {
-        if (SYM) {
-          if constexpr (DICT)
-            pc[s] = need_g ? a.lv.qmir[orow] : 0.0;
-          else
-            pc[s] = (need_g && e > 0) ? a.lv.qrow[(e - 1) * M + i] : 0.0;  // q_{e-1}[i]; B^{-1} applied below
-        } else {
-          pc[s] = need_g ? AGGMG_LD(a.lv.pcol[row]) : 0.0;
-        }
-        if (GRP) {
-          qv[s][0] = AGGMG_LD(a.lv.qrow[oe * M + i]);
-        } else {
+    }
+    if (pro) {
+      // J = e / rho_in, a 32-bit division wherever the level's elements count in 31 bits
+      int64_t J[NS];
+      if (ne <= 0x7fffffff) {
 #pragma unroll
-          for (int j = 0; j < (GRP ? 1 : M); ++j) qv[s][j] = a.lv.qrow[e * M + j];
-        }
-      } else if (DSYM) {
-        // park Sup_{e-1}[i][:] in Pr and Sup_e[i][:] in Qr; turned into P, Q rows after the loop
-#pragma unroll
-        for (int j = 0; j < M; ++j) {
-          Pr[s][j] = (need_g && e > 0) ? a.lv.sup[(row - M) * M + j] : 0.0;
-          Qr[s][j] = need_g ? a.lv.sup[row * M + j] : 0.0;
-        }
+        for (int s = 0; s < NS; ++s) J[s] = (int64_t)((unsigned)(e0 + xc[s]) / (unsigned)a.rho_in);
       } else {
 #pragma unroll
-        for (int j = 0; j < M; ++j) {
-          Pr[s][j] = need_g ? AGGMG_LD(a.lv.P[row * M + j]) : 0.0;
-          Qr[s][j] = need_g ? AGGMG_LD(a.lv.Q[row * M + j]) : 0.0;
-        }
+        for (int s = 0; s < NS; ++s) J[s] = (e0 + xc[s]) / a.rho_in;
       }
-      if (a.lf_in) {  // u += L uc : J = e / rho, ascending mode order (CSC scatter order)
-        const int64_t J = a.par_in ? (int64_t)a.par_in[e] : e / a.rho_in;
-        double add = 0.0;
-        if (a.mc_in == 2) {  // one 16-byte load each for the L row and the coarse pair
-          typedef double v2d __attribute__((ext_vector_type(2)));
-          double2 l2;
-          if (a.lf1_in) {
-            l2.x = 1.0;
-            l2.y = AGGMG_LD(a.lf1_in[orow]);
-          } else {
-            const v2d lv2 = AGGMG_LD(*reinterpret_cast<const v2d*>(a.lf_in + orow * 2));
-            l2.x = lv2.x;
-            l2.y = lv2.y;
-          }
-          const double2 u2 = *reinterpret_cast<const double2*>(a.uc + J * 2);
-          add = btd_prolong2(l2, u2);
-        } else {
-          for (int c = 0; c < a.mc_in; ++c) add += a.lf_in[row * a.mc_in + c] * a.uc[J * a.mc_in + c];
+#pragma unroll
+      for (int s = 0; s < NS; ++s) u2[s] = *reinterpret_cast<const double2*>(a.uc + J[s] * 2);
+    }
+    // the records, option by option (launch-uniform), the slabs of each side by side
+    if (need_g) {   // row i of the symmetric inverse out of its packed upper triangle; q_{e-1}[i], B^{-1} applied below
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+          const int lo_ = i < j ? i : j, hi_ = i < j ? j : i;
+          bi[s][j] = a.lv.bsym[(int64_t)ce[s] * T + lo_ * M - (lo_ * (lo_ - 1)) / 2 + (hi_ - lo_)];
         }
-        uu[s] += add;
+        pc[s] = a.lv.qmir[(int64_t)ce[s] * M + i];
       }
     } else {
-      if (CMP) {
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+#pragma unroll
+        for (int j = 0; j < M; ++j) bi[s][j] = 0.0;
         pc[s] = 0.0;
+      }
+    }
 #pragma unroll
-        for (int j = 0; j < (GRP ? 1 : M); ++j) qv[s][j] = 0.0;
+    for (int s = 0; s < NS; ++s) qv[s][0] = AGGMG_LD(a.lv.qrow[(int64_t)ce[s] * M + i]);
+    // (the rows of L' for the restriction are record words too: read with the residual's, not held through the sweeps)
+    if (pro) {   // the L row: its second entry, or one 16-byte load
+      if (a.lf1_in) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          l2[s].x = 1.0;
+          l2[s].y = AGGMG_LD(a.lf1_in[(int64_t)ce[s] * M + i]);
+        }
       } else {
+        typedef double v2d __attribute__((ext_vector_type(2)));
 #pragma unroll
-        for (int j = 0; j < M; ++j) {
-          Pr[s][j] = 0.0;
-          Qr[s][j] = 0.0;
+        for (int s = 0; s < NS; ++s) {
+          const v2d lv2 = AGGMG_LD(*reinterpret_cast<const v2d*>(a.lf_in + ((int64_t)ce[s] * M + i) * 2));
+          l2[s].x = lv2.x;
+          l2[s].y = lv2.y;
         }
       }
     }
-    binv_r[s] = 0.0;
 #pragma unroll
-    for (int j = 0; j < M; ++j)
-      if (j == a.lv.r_sup) binv_r[s] = bi[s][j];
-    if (active) {
-      buf0[x * M + i] = uu[s];
-      if (!GRP && !DSYM) buf1[x * M + i] = bb[s];
+    for (int s = 0; s < NS; ++s) {
+      const int x = s * EPS + le;
+      // u += L uc.  btd_prolong2's expression in the form the plain variant is compiled to -- the second product rounded,
+      // the first fused into the sum -- said explicitly, as group_dot says its own: which of the two products the
+      // contraction takes depends on the code around it (measured at M = 2: the other one here, a last-place difference)
+      if (pro) uu[s] += __fma_rn(l2[s].x, u2[s].x, l2[s].y * u2[s].y);
+      if (!valid[s]) {
+        uu[s] = 0.0;
+        bb[s] = 0.0;
+      }
+      binv_r[s] = 0.0;
+#pragma unroll
+      for (int j = 0; j < M; ++j)
+        if (j == a.lv.r_sup) binv_r[s] = bi[s][j];
+      if (active) buf0[x * M + i] = uu[s];
+    }
+  } else {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const int x = s * EPS + le;
+      const int64_t e = e0 + x;
+      valid[s] = active && e >= 0 && e < ne;
+      const int64_t row = e * M + i;
+      uu[s] = 0.0;
+      bb[s] = 0.0;
+#pragma unroll
+      for (int j = 0; j < M; ++j) bi[s][j] = 0.0;
+      if (valid[s]) {
+        if (need_g) {
+          if (SYM) {  // row i of the symmetric inverse out of its packed upper triangle
+            constexpr int T = M * (M + 1) / 2;
+#pragma unroll
+            for (int j = 0; j < M; ++j) {
+              const int lo_ = i < j ? i : j, hi_ = i < j ? j : i;
+              bi[s][j] = a.lv.bsym[e * T + lo_ * M - (lo_ * (lo_ - 1)) / 2 + (hi_ - lo_)];
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < M; ++j) bi[s][j] = AGGMG_LD(a.lv.binv[row * M + j]);
+          }
+        }
+        bb[s] = a.b[row];
+        if (a.u_in) uu[s] = a.u_in[row];
+        if (pre2) {
+          if (a.lf1_out && !a.ld_out) {   // unit first column: 1.0 * r is r, bit for bit what the stored 1.0 gives
+            l2x[s] = 1.0;
+            l2y[s] = AGGMG_LD(a.lf1_out[row]);
+          } else {
+            const double2 t2 = *reinterpret_cast<const double2*>(lfo_pre + row * 2);
+            l2x[s] = t2.x;
+            l2y[s] = t2.y;
+          }
+        }
+        if (CMP) {
+          if (SYM) {
+            pc[s] = (need_g && e > 0) ? a.lv.qrow[(e - 1) * M + i] : 0.0;  // q_{e-1}[i]; B^{-1} applied below
+          } else {
+            pc[s] = need_g ? AGGMG_LD(a.lv.pcol[row]) : 0.0;
+          }
+          if (GRP) {
+            qv[s][0] = AGGMG_LD(a.lv.qrow[e * M + i]);
+          } else {
+#pragma unroll
+            for (int j = 0; j < (GRP ? 1 : M); ++j) qv[s][j] = a.lv.qrow[e * M + j];
+          }
+        } else if (DSYM) {
+          // park Sup_{e-1}[i][:] in Pr and Sup_e[i][:] in Qr; turned into P, Q rows after the loop
+#pragma unroll
+          for (int j = 0; j < M; ++j) {
+            Pr[s][j] = (need_g && e > 0) ? a.lv.sup[(row - M) * M + j] : 0.0;
+            Qr[s][j] = need_g ? a.lv.sup[row * M + j] : 0.0;
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < M; ++j) {
+            Pr[s][j] = need_g ? AGGMG_LD(a.lv.P[row * M + j]) : 0.0;
+            Qr[s][j] = need_g ? AGGMG_LD(a.lv.Q[row * M + j]) : 0.0;
+          }
+        }
+        if (a.lf_in) {  // u += L uc : J = e / rho, ascending mode order (CSC scatter order)
+          const int64_t J = a.par_in ? (int64_t)a.par_in[e] : e / a.rho_in;
+          double add = 0.0;
+          if (a.mc_in == 2) {  // one 16-byte load each for the L row and the coarse pair
+            typedef double v2d __attribute__((ext_vector_type(2)));
+            double2 l2;
+            if (a.lf1_in) {
+              l2.x = 1.0;
+              l2.y = AGGMG_LD(a.lf1_in[row]);
+            } else {
+              const v2d lv2 = AGGMG_LD(*reinterpret_cast<const v2d*>(a.lf_in + row * 2));
+              l2.x = lv2.x;
+              l2.y = lv2.y;
+            }
+            const double2 u2 = *reinterpret_cast<const double2*>(a.uc + J * 2);
+            add = btd_prolong2(l2, u2);
+          } else {
+            for (int c = 0; c < a.mc_in; ++c) add += a.lf_in[row * a.mc_in + c] * a.uc[J * a.mc_in + c];
+          }
+          uu[s] += add;
+        }
+      } else {
+        if (CMP) {
+          pc[s] = 0.0;
+#pragma unroll
+          for (int j = 0; j < (GRP ? 1 : M); ++j) qv[s][j] = 0.0;
+        } else {
+#pragma unroll
+          for (int j = 0; j < M; ++j) {
+            Pr[s][j] = 0.0;
+            Qr[s][j] = 0.0;
+          }
+        }
+      }
+      binv_r[s] = 0.0;
+#pragma unroll
+      for (int j = 0; j < M; ++j)
+        if (j == a.lv.r_sup) binv_r[s] = bi[s][j];
+      if (active) {
+        buf0[x * M + i] = uu[s];
+        if (!GRP && !DSYM) buf1[x * M + i] = bb[s];
+      }
     }
   }
   if (GRP || DSYM) {
@@ -1222,9 +1330,9 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
   // (CMP) the row's entries from memory: the full arrays, or (sres) the lossless symmetric form -- the same bits
   [[maybe_unused]] auto load_row = [&](int s, int64_t row, double (&dk)[M], double& sc) {
     if constexpr (DICT) row = (int64_t)ce[s] * M + i;
-    if constexpr (SRES) {
+    if constexpr (SRES && !DICT) {   // (the dictionary variant's symmetric form: its own residual below)
       if (sres) {
-        sym_residual_row<M, DICT>(a.lv, row / M, i, dk, sc);
+        sym_residual_row<M>(a.lv, row / M, i, dk, sc);
         return;
       }
     }
@@ -1354,15 +1462,98 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
       const int x = s * EPS + le;
-      if (valid[s] && x >= xo0 && x < xo1) AGGMG_ST(a.u_out[(e0 + x) * M + i], uu[s]);
+      if (valid[s] && x >= xo0 && x < xo1) {
+        if constexpr (DICT)   // (the tile's base plus the lane's offset: no 64-bit row held through the sweeps)
+          AGGMG_ST((a.u_out + e0 * M)[(unsigned)(x * M + i)], uu[s]);
+        else
+          AGGMG_ST(a.u_out[(e0 + x) * M + i], uu[s]);
+      }
     }
   }
 
   if (!a.do_residual) return;
 
   double rr[NS];
+  if constexpr (DICT) {
+    // dictionary variant: the rows of L' of the restriction come from the cache-resident records, here
+    if (pre2) {
+      if (a.lf1_out) {   // unit first column: 1.0 * r is r, bit for bit what the stored 1.0 gives
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          l2x[s] = 1.0;
+          l2y[s] = AGGMG_LD(a.lf1_out[(int64_t)ce[s] * M + i]);
+        }
+      } else {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          const double2 t2 = *reinterpret_cast<const double2*>(lfo_pre + ((int64_t)ce[s] * M + i) * 2);
+          l2x[s] = t2.x;
+          l2y[s] = t2.y;
+        }
+      }
+    }
+  }
   const double* lfo = a.lf_out;
-  if (a.r_out || a.lf_out) {
+  if constexpr (DICT && SRES) {
+    // ---- explicit residual, dictionary variant (launched only on a level that has the symmetric form): the record
+    // words of ALL slabs -- corr, the row's run of dup and, unconditionally, the entries of the triangle in front of it
+    // (inside the record; dropped below), qmir -- issued before the first is used, every lane (one outside the level or
+    // the owned range decodes the record of its class and its row is dropped at the end: no branch around a load, the
+    // slabs side by side).  The escapes (the level's first element; a difference that does not fit) are patched in a
+    // second pass that the lanes without one skip.  sym_residual_row's decode and btd_apply_cmp's order of additions.
+    if (a.r_out || a.lf_out) {
+      constexpr int T = M * (M + 1) / 2;
+      uint32_t w[NS];
+      double dk[NS][M], sc[NS];
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const int64_t orow = (int64_t)ce[s] * M + i;
+        w[s] = a.lv.corr[orow];
+        const double* du = a.lv.dup + (int64_t)ce[s] * T + i * M - (i * (i - 1)) / 2 - i;   // du[j] = D[i][j], j >= i
+#pragma unroll
+        for (int j = 0; j < M; ++j) dk[s][j] = du[j];
+        sc[s] = a.lv.qmir[orow];
+      }
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const int x = s * EPS + le;
+        const bool own = valid[s] && x >= xo0 && x < xo1;
+        const int64_t orow = (int64_t)ce[s] * M + i;
+        // (the entries in front of the run become +0.0 by a mask on the bits: a select would let the compiler move the
+        // load behind a branch on the lane's row)
+#pragma unroll
+        for (int j = 0; j < M; ++j)
+          dk[s][j] = __longlong_as_double(__double_as_longlong(dk[s][j]) & (j >= i ? -1ll : 0ll));
+        bool esc = false;
+#pragma unroll
+        for (int j = 0; j < M - 1; ++j) {
+          double mir = 0.0;   // D[j][i], from lane j
+#pragma unroll
+          for (int c = j + 1; c < M; ++c) {
+            const double v = group_bcast<M>(dk[s][c], j);
+            if (i == c) mir = v;
+          }
+          const int d = (int)(int8_t)(w[s] >> (8 * j));
+          const double dec = sym_residual_decode(mir, d);
+          dk[s][j] = j < i ? dec : dk[s][j];
+          esc |= (j < i) & (d == kSymResidualEscape);
+        }
+        const int dc = (int)(int8_t)(w[s] >> 24);
+        sc[s] = sym_residual_decode(sc[s], dc);
+        esc |= dc == kSymResidualEscape;
+        if (__builtin_expect(own && esc, 0)) {
+#pragma unroll
+          for (int j = 0; j < M - 1; ++j)
+            if (j < i && (int)(int8_t)(w[s] >> (8 * j)) == kSymResidualEscape) dk[s][j] = a.lv.dblk[orow * M + j];
+          if (dc == kSymResidualEscape) sc[s] = a.lv.scol[orow];
+        }
+        const double t = btd_apply_cmp<M, GRP, true>(sc[s], dk[s], qv[s], cur + (x - 1) * M, cur + x * M, cur + (x + 1) * M,
+                                                     a.lv.c_sub, a.lv.r_sup, i);
+        rr[s] = own ? bb[s] - t : 0.0;
+        if (own && a.r_out) (a.r_out + e0 * M)[(unsigned)(x * M + i)] = rr[s];
+      }
+    }
+  } else if (a.r_out || a.lf_out) {
     // ---- explicit residual r = b - A u on the owned elements, ascending column order ---------
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -1412,7 +1603,7 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
     }
   }
   if (!lfo) return;
-  if (a.par_out) {
+  if (!DICT && a.par_out) {
     // ---- restriction onto agglomerates of different sizes: r through LDS, one thread per (J, mode) over the
     // part of the agglomerate this tile owns
     const int mc = a.mc_out;
@@ -1463,8 +1654,10 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
 
   const int rho = a.rho_out, mc = a.mc_out;
   const int ncoarse = a.owned / rho;  // owned coarse elements of this tile
-  const int64_t J0 = (fused_tile(a) * a.owned) / rho;
-  const int64_t nec = ne / rho;
+  // (dictionary variant: the same two numbers without a 64-bit division -- owned is ncoarse whole agglomerates, and the
+  // launch carries the coarse level's element count)
+  const int64_t J0 = DICT ? fused_tile(a) * ncoarse : (fused_tile(a) * a.owned) / rho;
+  const int64_t nec = DICT ? a.nec_out : ne / rho;
   if (pre2) {
     // ---- restriction, two coarse modes: every row thread forms its two products with the
     // preloaded L' entries; both iterate buffers are free once all threads are past the residual
@@ -1490,6 +1683,7 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
     }
     return;
   }
+  if constexpr (DICT) return;   // (a dictionary launch restricts onto two modes: the branch above)
   // ---- restriction rc = L' r, general mode count: r through LDS, one thread per (J, mode) ----
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
