@@ -32,6 +32,8 @@ RESTRICT_EXPLICIT, RESTRICT_PRECONDITIONED = 0, 1
 RESTRICT_PRECONDITIONED_MAX_ELEMS = 1 << 21
 # aggmg_hier_level_kind
 LEVEL_GENERIC, LEVEL_FUSED_BTD, LEVEL_FUSED_CHAIN, LEVEL_COARSEST = 0, 1, 2, 3
+# aggmg_hier_set_sweep_weights: most weights per half (include/aggmg_hip.h)
+MAX_SWEEP_WEIGHTS = 8
 RCCL_ID_BYTES = 128
 DIST_X0_GHOSTS_VALID, DIST_OVERLAP_NEXT, DIST_GRAPH = 1, 2, 4
 ALLGATHER_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p)
@@ -116,6 +118,7 @@ SYMBOLS = {
     "aggmg_restrict": (c_int, [_P, _P, _PD, _PD]),
     "aggmg_prolong_add": (c_int, [_P, _P, _PD, _PD]),
     "aggmg_smooth_dev": (c_int, [_P, _P, _P, _P, _P, c_double, c_int, _P]),
+    "aggmg_smooth_weighted_dev": (c_int, [_P, _P, _P, _P, _P, _PD, c_int, _P]),
     "aggmg_residual_dev": (c_int, [_P, _P, _P, _P, _P]),
     "aggmg_restrict_dev": (c_int, [_P, _P, _P, _P]),
     "aggmg_prolong_add_dev": (c_int, [_P, _P, _P, _P]),
@@ -148,6 +151,9 @@ SYMBOLS = {
     "aggmg_hier_level_paired_up": (c_int, [_P, _P, c_int, c_int, POINTER(c_int)]),
     "aggmg_hier_level_sym_residual": (c_int, [_P, _P, c_int, POINTER(c_int)]),
     "aggmg_hier_level_dictionary": (c_int, [_P, _P, c_int, POINTER(c_int)]),
+    "aggmg_hier_set_sweep_weights": (c_int, [_P, _P, c_int, _PD, c_int, _PD, c_int]),
+    "aggmg_hier_get_sweep_weights": (c_int, [_P, _P, c_int, _PD, POINTER(c_int), _PD, POINTER(c_int)]),
+    "aggmg_hier_estimate_lambda_max": (c_int, [_P, _P, c_int, _P, c_int, POINTER(c_double)]),
     "aggmg_hier_launch_bytes": (c_int, [_P, _P, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "aggmg_hier_multi_launch_bytes": (c_int, [_P, _P, c_int, c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_int64)]),
     "aggmg_smoother_launch_bytes": (c_int, [_P, _P, _P, c_int, POINTER(c_int64), POINTER(c_int64)]),

@@ -1122,6 +1122,68 @@ class MeshHierarchy:
         c = self.ctx
         c.check(c.lib.aggmg_hier_set_restriction(c.handle, self.handle, int(mode)))
 
+    # ---- sweep-weight schedules (EXTENSION: the reference damps every sweep of every level by the same alpha) ----
+    def set_sweep_weights(self, level, pre, post=None):
+        """Level `level` damps its i-th pre-smoothing sweep by pre[i] and its i-th post-smoothing sweep by post[i] in every
+        solver that runs the cycle on this hierarchy (vcycle, vcycles, multigrid, pcg, their K-column forms), in place of
+        their `alpha`; levels without a schedule keep `alpha` (C ABI aggmg_hier_set_sweep_weights).  post defaults to pre
+        reversed, which keeps the cycle a symmetric preconditioner for pcg; with an explicit post that is not pre
+        reversed, symmetry is the caller's responsibility.  A cycle's nPre / nPost must equal len(pre) / len(post)
+        (ArgumentError otherwise); at most _lib.MAX_SWEEP_WEIGHTS weights per half, all finite; the coarsest level has no
+        sweeps."""
+        pre = np.ascontiguousarray(np.atleast_1d(np.asarray(pre, dtype=np.float64)))
+        post = pre[::-1].copy() if post is None else np.ascontiguousarray(np.atleast_1d(np.asarray(post, dtype=np.float64)))
+        if pre.ndim != 1 or post.ndim != 1:
+            raise ArgumentError("set_sweep_weights: pre and post are sequences of numbers")
+        c = self.ctx
+        c.check(c.lib.aggmg_hier_set_sweep_weights(c.handle, self.handle, int(level), _pd(pre), pre.size, _pd(post), post.size))
+
+    def clear_sweep_weights(self, level=None):
+        """remove the schedule of `level`, or (None) of every level: the cycle is the entry point's `alpha` again"""
+        c = self.ctx
+        for k in (range(self.nlevels - 1) if level is None else [int(level)]):
+            c.check(c.lib.aggmg_hier_set_sweep_weights(c.handle, self.handle, k, None, 0, None, 0))
+
+    def sweep_weights(self, level):
+        """-> (pre, post) arrays of the level's schedule, or None when it has none (C ABI aggmg_hier_get_sweep_weights)"""
+        pre, post = np.zeros(_lib.MAX_SWEEP_WEIGHTS), np.zeros(_lib.MAX_SWEEP_WEIGHTS)
+        npre, npost = ctypes.c_int(0), ctypes.c_int(0)
+        c = self.ctx
+        c.check(c.lib.aggmg_hier_get_sweep_weights(c.handle, self.handle, int(level), _pd(pre), ctypes.byref(npre), _pd(post),
+                                                   ctypes.byref(npost)))
+        if npre.value + npost.value == 0:
+            return None
+        return pre[:npre.value].copy(), post[:npost.value].copy()
+
+    def estimate_lambda_max(self, level, iters=40, v0=None):
+        """largest eigenvalue of S^-1 A of `level` by `iters` steps of power iteration on the device, one host read at the
+        end (C ABI aggmg_hier_estimate_lambda_max).  v0: start vector (host array, DeviceVector, tensor or pointer), or
+        None for a fixed seeded one.  The estimate approaches the eigenvalue from below."""
+        c = self.ctx
+        keep = None
+        if v0 is not None and isinstance(v0, (np.ndarray, list, tuple)):
+            keep = c.to_device(v0)
+            v0 = keep
+        lam = ctypes.c_double(0.0)
+        try:
+            c.check(c.lib.aggmg_hier_estimate_lambda_max(c.handle, self.handle, int(level), None if v0 is None else _ptr(v0),
+                                                         int(iters), ctypes.byref(lam)))
+        finally:
+            if keep is not None:
+                keep.free()
+        return lam.value
+
+    def set_chebyshev_smoothing(self, levels=(0,), degree=3, ratio=10.0, iters=40):
+        """estimate_lambda_max on each of `levels`, then chebyshev_weights(lam, degree, ratio) as the level's pre-smoothing
+        schedule and its reverse as the post-smoothing one; -> {level: lambda_max estimate}.  The cycle then runs with
+        nPre = nPost = degree."""
+        out = {}
+        for k in levels:
+            lam = self.estimate_lambda_max(k, iters=iters)
+            self.set_sweep_weights(k, chebyshev_weights(lam, degree=degree, ratio=ratio))
+            out[int(k)] = lam
+        return out
+
     def get_restriction(self):
         v = ctypes.c_int(0)
         self.ctx.check(self.ctx.lib.aggmg_hier_get_restriction(self.ctx.handle, self.handle, ctypes.byref(v)))
@@ -1549,12 +1611,44 @@ def smoother_solve_dev(A_op, smoother, x0, b, maxiter, tol, alpha=1.0, check_eve
     return dx, nit.value, res, err
 
 
+def chebyshev_weights(lam_max, degree=3, ratio=10.0, safety=1.05):
+    """Sweep weights w_j = 1 / root_j of the degree-`degree` Chebyshev polynomial on [lo, hi] = [lam_max / ratio, safety *
+    lam_max], smallest first (EXTENSION, no reference counterpart): `degree` sweeps u += w_j S^-1 (b - A u) multiply an
+    error component of eigenvalue lam of S^-1 A by prod_j (1 - w_j lam), the polynomial with the smallest maximum over
+    the interval, 1 / T_degree((hi + lo) / (hi - lo)).  lam_max: largest eigenvalue of S^-1 A
+    (MeshHierarchy.estimate_lambda_max); safety covers an estimate from below."""
+    lam_max, ratio, safety = float(lam_max), float(ratio), float(safety)
+    if int(degree) != degree or degree < 1:
+        raise ArgumentError("chebyshev_weights: degree must be a positive integer")
+    if not (np.isfinite(lam_max) and lam_max > 0.0):
+        raise ArgumentError("chebyshev_weights: lam_max must be positive and finite")
+    if not (np.isfinite(ratio) and ratio > 1.0):
+        raise ArgumentError("chebyshev_weights: ratio must be > 1")
+    if not (np.isfinite(safety) and safety >= 1.0):
+        raise ArgumentError("chebyshev_weights: safety must be >= 1")
+    degree = int(degree)
+    hi, lo = safety * lam_max, lam_max / ratio
+    j = np.arange(degree)
+    return 1.0 / (0.5 * (hi + lo) + 0.5 * (hi - lo) * np.cos(np.pi * (2 * j + 1) / (2 * degree)))
+
+
 # stand-alone fused operations on host arrays (C ABI `aggmg_smooth`, `aggmg_residual`, ...)
 def smooth(A_op, S, u, b, alpha=2.0 / 3.0, nsweeps=1):
-    """nsweeps x `u += apply_smoother(S, b - A*u; alpha)` (src/solvers.jl:32-35) -> new vector"""
+    """nsweeps x `u += apply_smoother(S, b - A*u; alpha)` (src/solvers.jl:32-35) -> new vector.  EXTENSION: alpha may be
+    a sequence -- sweep s is damped by alpha[s], nsweeps is then its length (C ABI aggmg_smooth_weighted_dev)."""
     u = _f64(u).copy()
     b = _f64(b)
     c = A_op.ctx
+    if np.ndim(alpha) > 0:
+        w = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64).ravel())
+        du, db = c.to_device(u), c.to_device(b)
+        dout = c.alloc(u.size)
+        try:
+            c.check(c.lib.aggmg_smooth_weighted_dev(c.handle, A_op.handle, S.handle, du.ptr, db.ptr, _pd(w), w.size, dout.ptr))
+            return dout.download()
+        finally:
+            for v in (du, db, dout):
+                v.free()
     c.check(c.lib.aggmg_smooth(c.handle, A_op.handle, S.handle, _pd(u), _pd(b), float(alpha), int(nsweeps)))
     return u
 

@@ -477,7 +477,7 @@ static int launch_csr(aggmg_ctx* ctx, const CsrDev& A, const double* x, const do
 // rout / fused (optional): the residual b - A dst wanted next -- a banded operator's last launch forms it in the same pass
 // (one sweep less per launch so that the halo holds) and *fused says so; otherwise the caller launches it.
 static int launch_csr_jacobi_sweeps(aggmg_ctx* ctx, const CsrDev& A, const double* src, const double* b, const double* dg,
-                                    double alpha, int n, double* dst, double* tmp, double* rout = nullptr, bool* fused = nullptr) {
+                                    Damping alpha, int n, double* dst, double* tmp, double* rout = nullptr, bool* fused = nullptr) {
   if (fused) *fused = false;
   if (n <= 0 || A.nrows == 0) return AGGMG_OK;
   const bool want_r = rout && fused && A.bandblk && A.band_sweeps >= 2;
@@ -492,11 +492,11 @@ static int launch_csr_jacobi_sweeps(aggmg_ctx* ctx, const CsrDev& A, const doubl
     const bool with_r = want_r && l == nl - 1;
     if (A.bandblk && (s > 1 || with_r)) {
       hipLaunchKernelGGL((csr_band_kernel<kJacobi>), dim3((unsigned)A.nbandblk), dim3(kThreads), 0, ctx->stream, A.view(),
-                         (const int32_t*)A.bandblk, A.bw, s, src, b, dg, alpha, out, with_r ? rout : (double*)nullptr);
+                         (const int32_t*)A.bandblk, A.bw, s, src, b, dg, alpha.from(n - left).launch(s), out, with_r ? rout : (double*)nullptr);
       HIPCHK(hipGetLastError());
       if (with_r) *fused = true;
     } else {
-      CHECK(launch_csr<kJacobi>(ctx, A, src, b, dg, alpha, out));
+      CHECK(launch_csr<kJacobi>(ctx, A, src, b, dg, alpha.at(n - left), out));
     }
     src = out;
     left -= s;
@@ -557,8 +557,14 @@ static void xfer_out(FusedArgs& a, const TransferBtd& t) {
   a.agg_shift = xfer_agg_shift(t);
 }
 
+// A fused launch on the host: the kernel's argument struct and, beside it, the factors of its sweeps -- a kernel argument
+// of their own (SweepWeights, kernels.hpp)
+struct FusedLaunch : FusedArgs {
+  SweepWeights wts;
+};
+
 template <int M, bool CMP>
-static int launch_btd_t(aggmg_ctx* ctx, FusedArgs a, int halo, const TileSel& sel, CgtChk* chk_io) {
+static int launch_btd_t(aggmg_ctx* ctx, FusedLaunch a, int halo, const TileSel& sel, CgtChk* chk_io) {
   using T = BtdTile<M, CMP>;
   const bool vr = (a.lf_out || a.ld_out) && a.par_out;
   const int align = ((a.lf_out || a.ld_out) && !vr) ? a.rho_out : 1;
@@ -604,7 +610,7 @@ static int launch_btd_t(aggmg_ctx* ctx, FusedArgs a, int halo, const TileSel& se
   const bool sres = kSres && a.lv.dup && !a.gs && !chk && a.do_residual && (a.r_out || a.lf_out);
   // instantiations per (M, CMP): symmetric packing x (block-Jacobi / red-black GS / block-Jacobi with checkpoint)
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, static_cast<const FusedArgs&>(a), a.wts);
   };
   if constexpr (kGrp && CMP && M <= 4) {
     // the operator dictionary (fused_dictionary put its arrays in place of the full ones): block-Jacobi launches
@@ -674,7 +680,7 @@ static bool btd_with_tile(const BtdDev& b, F&& f) {
   return false;
 }
 
-static int launch_btd(aggmg_ctx* ctx, const BtdDev& b, const FusedArgs& a, int halo, const TileSel& sel = TileSel(),
+static int launch_btd(aggmg_ctx* ctx, const BtdDev& b, const FusedLaunch& a, int halo, const TileSel& sel = TileSel(),
                       CgtChk* chk = nullptr) {
   int rc = AGGMG_OK;
   if (!btd_with_tile(b, [&](auto t) { rc = launch_btd_t<decltype(t)::kM, decltype(t)::kCmp>(ctx, a, halo, sel, chk); }))
@@ -698,13 +704,14 @@ static FusedArgs btd_args(const BtdDev& b) {
 // ---- the arguments of a fused launch, part by part: every launch has the sweeps; an ascent adds the prolongation in
 // front of them, a descent the residual and its restriction behind them, a launch between two cycles both -----------
 // gs: 0 block Jacobi, 1 red-black Gauss-Seidel even elements first, 2 odd ones first
-static FusedArgs fused_sweeps(const BtdDev& b, const double* u_in, const double* rhs, double* u_out, double alpha, int nsweeps,
+static FusedLaunch fused_sweeps(const BtdDev& b, const double* u_in, const double* rhs, double* u_out, Damping alpha, int nsweeps,
                               int gs = 0) {
-  FusedArgs a = btd_args(b);
+  FusedLaunch a;
+  static_cast<FusedArgs&>(a) = btd_args(b);
   a.u_in = u_in;
   a.b = rhs;
   a.u_out = u_out;
-  a.alpha = alpha;
+  a.wts = alpha.launch(nsweeps);
   a.nsweeps = nsweeps;
   a.gs = gs;
   return a;
@@ -795,7 +802,7 @@ static bool btd_launch_ok(const aggmg_smoother& sm, int nsweeps, int residual, c
 }
 
 // structured: nsweeps sweeps from u_in (may be nullptr = zero) into u_out (!= u_in)
-static int btd_smooth(aggmg_ctx* ctx, const BtdDev& b, const double* u_in, const double* rhs, double alpha,
+static int btd_smooth(aggmg_ctx* ctx, const BtdDev& b, const double* u_in, const double* rhs, Damping alpha,
                       int nsweeps, double* u_out, int level, int64_t N, int gs = 0) {
   const int smax = std::max(1, btd_max_sweeps(b, 0) / (gs ? 2 : 1));
   const double* src = u_in;
@@ -817,7 +824,7 @@ static int btd_smooth(aggmg_ctx* ctx, const BtdDev& b, const double* u_in, const
   for (int c = 0; c < nchunks; ++c) {
     const int s = std::min(left, smax);
     double* dst = (c == nchunks - 1) ? u_out : (((nchunks - 1 - c) % 2 == 1) ? t0 : t1);
-    const FusedArgs a = fused_sweeps(b, src, rhs, dst, alpha, s, gs);
+    const FusedLaunch a = fused_sweeps(b, src, rhs, dst, alpha.from(nsweeps - left), s, gs);
     {
       ProfScope ps(ctx, AGGMG_KIND_SMOOTH, level);
       CHECK(launch_btd(ctx, b, a, s));
@@ -900,7 +907,7 @@ static int generic_sweep(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const 
 }
 
 // nsweeps generic point-Jacobi sweeps from src into dst (dst may be src); `other` is a second vector of the level
-static int generic_jacobi(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* src, const double* rhs, double alpha,
+static int generic_jacobi(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* src, const double* rhs, Damping alpha,
                           int nsweeps, double* dst, double* other, double* rout = nullptr, bool* fused = nullptr) {
   const int64_t N = A->m;
   if (fused) *fused = false;
@@ -935,8 +942,8 @@ static int check_pair(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const cha
   return AGGMG_OK;
 }
 
-extern "C" int aggmg_smooth_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* u_in,
-                                const double* b, double alpha, int nsweeps, double* u_out) {
+static int smooth_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* u_in, const double* b, Damping alpha,
+                      int nsweeps, double* u_out) {
   CHECK(check_pair(ctx, A, sm, "aggmg_smooth"));
   if (!b || !u_out || nsweeps < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth: bad argument");
   const int64_t N = A->m;
@@ -975,10 +982,26 @@ extern "C" int aggmg_smooth_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm,
     return generic_jacobi(ctx, A, sm, src, b, alpha, nsweeps, u_out, t);
   }
   for (int s = 0; s < nsweeps; ++s) {
-    CHECK(generic_sweep(ctx, A, sm, src, b, alpha, u_out, 0));
+    CHECK(generic_sweep(ctx, A, sm, src, b, alpha.at(s), u_out, 0));
     src = u_out;
   }
   return AGGMG_OK;
+}
+
+extern "C" int aggmg_smooth_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* u_in,
+                                const double* b, double alpha, int nsweeps, double* u_out) {
+  return smooth_dev(ctx, A, sm, u_in, b, Damping(alpha), nsweeps, u_out);
+}
+
+// EXTENSION (no reference counterpart): sweep s damped by w[s] -- the launches of aggmg_smooth_dev, each with its slice of w
+extern "C" int aggmg_smooth_weighted_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* u_in,
+                                         const double* b, const double* w, int nsweeps, double* u_out) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (nsweeps < 0 || (nsweeps > 0 && !w)) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_weighted: bad argument");
+  for (int s = 0; s < nsweeps; ++s)
+    if (!std::isfinite(w[s])) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_weighted: weight is not finite");
+  // (w is read while the launches are enqueued, not after; a run of zero sweeps has no array to point at)
+  return smooth_dev(ctx, A, sm, u_in, b, Damping(0.0, nsweeps ? w : nullptr), nsweeps, u_out);
 }
 
 extern "C" int aggmg_residual_dev(aggmg_ctx* ctx, aggmg_op* A, const double* u, const double* b, double* r_out) {
@@ -987,7 +1010,7 @@ extern "C" int aggmg_residual_dev(aggmg_ctx* ctx, aggmg_op* A, const double* u, 
   ProfScope ps(ctx, AGGMG_KIND_RESIDUAL, 0);
   if (A->cgt && r_out != u && r_out != b) return cgt_residual_ext(ctx, *A->cgt, u, b, r_out);
   if (A->btd && r_out != u && r_out != b) {  // index-free block-tridiagonal form, one fused pass
-    FusedArgs a = fused_sweeps(*A->btd, u, b, nullptr, 0.0, 0);
+    FusedLaunch a = fused_sweeps(*A->btd, u, b, nullptr, 0.0, 0);
     a.do_residual = 1;
     a.r_out = r_out;
     return launch_btd(ctx, *A->btd, a, 1);
@@ -1821,7 +1844,7 @@ static bool pair_ok(const aggmg_ctx* ctx, const aggmg_hier* h, int k, int nsweep
   return launch_has_tile(q);
 }
 
-static PairArgs pair_args(const aggmg_hier* h, int k, double alpha, int nsweeps) {
+static PairArgs pair_args(const aggmg_hier* h, int k, int nsweeps) {
   const Level& a = h->lv[k];
   const Level& b = h->lv[k + 1];
   PairArgs p;
@@ -1832,7 +1855,6 @@ static PairArgs pair_args(const aggmg_hier* h, int k, double alpha, int nsweeps)
   p.B = lev(*b.S->btd);
   p.ab = xf(*a.tb);
   p.bc = xf(*b.tb);
-  p.alpha = alpha;
   p.nsweeps = nsweeps;
   return p;
 }
@@ -1841,7 +1863,8 @@ static int launch_pair_down(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPre, doub
   Level& a = h->lv[k];
   Level& b = h->lv[k + 1];
   Level& c = h->lv[k + 2];
-  PairArgs p = pair_args(h, k, alpha, nPre);
+  PairArgs p = pair_args(h, k, nPre);
+  const SweepWeights wa = a.damp_pre(alpha).launch(nPre), wb = b.damp_pre(alpha).launch(nPre);   // the two levels' factors
   const PairTilePlan plan = pair_down_plan(nPre, p.ab.rho, p.bc.rho, kPairTEA, kPairTEB);   // host_plan.hpp
   if (plan.own <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: paired tile too small");
   p.own = plan.own;
@@ -1857,7 +1880,7 @@ static int launch_pair_down(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPre, doub
   const size_t lds = ((size_t)2 * (kPairTEA + 2) * kPairM + (size_t)kPairTEB * 2) * sizeof(double);
   ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
   hipLaunchKernelGGL((btd_pair_down_kernel<kPairM, kPairNSA, kPairNSB, kThreads>), dim3((unsigned)ntiles), dim3(kThreads), lds,
-                     ctx->stream, p);
+                     ctx->stream, p, wa, wb);
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
@@ -1872,7 +1895,8 @@ static int launch_pair_up(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPost, doubl
   Level& a = h->lv[k];
   Level& b = h->lv[k + 1];
   Level& c = h->lv[k + 2];
-  PairArgs p = pair_args(h, k, alpha, nPost);
+  PairArgs p = pair_args(h, k, nPost);
+  const SweepWeights wa = a.damp_post(alpha).launch(nPost), wb = b.damp_post(alpha).launch(nPost);
   PairTilePlan plan = pair_up_plan(nPost, p.ab.rho, kPairTEA, kPairTEB);   // host_plan.hpp
   if (plan.own <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: paired tile too small");
   p.hb = plan.hb;
@@ -1902,7 +1926,7 @@ static int launch_pair_up(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPost, doubl
   const size_t lds = ((size_t)2 * (kPairTEA + 2) * kPairM + (size_t)kPairTEB * 2) * sizeof(double);
   ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
   hipLaunchKernelGGL((btd_pair_up_kernel<kPairM, kPairNSA, kPairNSB, kThreads>), dim3((unsigned)ntiles), dim3(kThreads), lds,
-                     ctx->stream, p);
+                     ctx->stream, p, wa, wb);
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
@@ -1935,15 +1959,69 @@ extern "C" int aggmg_hier_level_dictionary(aggmg_ctx* ctx, const aggmg_hier* h, 
   return AGGMG_OK;
 }
 
+// ---- sweep-weight schedules (EXTENSION: the reference damps every sweep of every level by the same alpha,
+// src/solvers.jl:19-50) ------------------------------------------------------------------------------------------
+extern "C" int aggmg_hier_set_sweep_weights(aggmg_ctx* ctx, aggmg_hier* h, int level, const double* pre, int npre,
+                                            const double* post, int npost) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!h) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_set_sweep_weights: NULL argument");
+  if (level < 0 || level >= (int)h->lv.size() - 1)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_set_sweep_weights: level out of range (the coarsest level is solved, not smoothed)");
+  if (npre < 0 || npost < 0 || npre > AGGMG_MAX_SWEEP_WEIGHTS || npost > AGGMG_MAX_SWEEP_WEIGHTS)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_set_sweep_weights: between 0 and AGGMG_MAX_SWEEP_WEIGHTS weights per half");
+  if ((npre > 0 && !pre) || (npost > 0 && !post)) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_set_sweep_weights: NULL argument");
+  for (int i = 0; i < npre; ++i)
+    if (!std::isfinite(pre[i])) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_set_sweep_weights: weight is not finite");
+  for (int i = 0; i < npost; ++i)
+    if (!std::isfinite(post[i])) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_set_sweep_weights: weight is not finite");
+  Level& l = h->lv[level];
+  l.scheduled = npre + npost > 0;
+  l.w_pre.assign(pre, pre + npre);
+  l.w_post.assign(post, post + npost);
+  l.w_mid = l.w_post;
+  l.w_mid.insert(l.w_mid.end(), l.w_pre.begin(), l.w_pre.end());
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_hier_get_sweep_weights(aggmg_ctx* ctx, const aggmg_hier* h, int level, double* pre, int* npre,
+                                            double* post, int* npost) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!h || !pre || !npre || !post || !npost) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_get_sweep_weights: NULL argument");
+  if (level < 0 || level >= (int)h->lv.size() - 1)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_get_sweep_weights: level out of range");
+  const Level& l = h->lv[level];
+  *npre = (int)l.w_pre.size();
+  *npost = (int)l.w_post.size();
+  std::copy(l.w_pre.begin(), l.w_pre.end(), pre);
+  std::copy(l.w_post.begin(), l.w_post.end(), post);
+  return AGGMG_OK;
+}
+
+// A cycle's sweep counts against the schedules of levels k_first .. n - 2 (nPre / nPost < 0: that half is not run by the
+// caller): nothing is truncated or padded silently.
+static int schedule_check(aggmg_ctx* ctx, const aggmg_hier* h, int nPre, int nPost, int k_first = 0) {
+  for (int k = k_first; k < (int)h->lv.size() - 1; ++k) {
+    const Level& l = h->lv[k];
+    if (!l.scheduled) continue;
+    if ((nPre >= 0 && nPre != (int)l.w_pre.size()) || (nPost >= 0 && nPost != (int)l.w_post.size()))
+      return fail(ctx, AGGMG_ERR_ARGUMENT, "level " + std::to_string(k) + " has a sweep-weight schedule of " +
+                  std::to_string(l.w_pre.size()) + " pre- and " + std::to_string(l.w_post.size()) +
+                  " post-smoothing weights; the cycle asks for " + std::to_string(nPre) + " / " + std::to_string(nPost) + " sweeps");
+  }
+  return AGGMG_OK;
+}
+
 // ---- descend (src/solvers.jl:28-37): leaves u[k] in lv[k].u[0] and rhs[n] in lv[n-1].rhs ----------
 static int vcycle_down(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const double* b, int nPre, double alpha,
                        int k_first = 0) {
   const int n = (int)h->lv.size();
+  CHECK(schedule_check(ctx, h, nPre, -1, k_first));
   for (int k = k_first; k < n - 1; ++k) {
     Level& l = h->lv[k];
     Level& c = h->lv[k + 1];
     const double* rhs = k == 0 ? b : l.rhs;
     const double* uin = k == 0 ? x0 : nullptr;  // u[k] = zeros for k > 1 (:29-31)
+    const Damping damp = l.damp_pre(alpha);     // the level's schedule, or alpha for every sweep
     if (l.cgt_fused) {
       CHECK(cgt_down(ctx, h, k, uin, rhs, nPre, alpha));
       continue;
@@ -1956,7 +2034,7 @@ static int vcycle_down(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const do
     const bool structured = l.S->btd && l.S->A == l.A;
     if (structured && l.tb && btd_launch_ok(*l.S, nPre, 1, l.tb.get())) {
       // (Gauss-Seidel pre-smoothing: even elements, then odd ones)
-      FusedArgs a = fused_sweeps(*l.S->btd, uin, rhs, l.u[0], alpha, nPre, l.S->gs ? 1 : 0);
+      FusedLaunch a = fused_sweeps(*l.S->btd, uin, rhs, l.u[0], damp, nPre, l.S->gs ? 1 : 0);
       fused_descent(a, h, l, c.rhs);
       fused_dictionary(a, l);
       ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
@@ -1964,7 +2042,7 @@ static int vcycle_down(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const do
     } else {
       bool resid_done = false;
       if (structured) {
-        CHECK(btd_smooth(ctx, *l.S->btd, uin, rhs, alpha, nPre, l.u[0], k, l.N, l.S->gs ? 1 : 0));
+        CHECK(btd_smooth(ctx, *l.S->btd, uin, rhs, damp, nPre, l.u[0], k, l.N, l.S->gs ? 1 : 0));
       } else {
         // generic sweeps, result in l.u[0]
         const double* src = uin;
@@ -1978,10 +2056,10 @@ static int vcycle_down(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const do
           CHECK(op_ensure_csr(ctx, l.A));
           ProfScope ps(ctx, AGGMG_KIND_JACOBI, k);
           // (banded operators: the residual for the restriction comes out of the sweeps' own launch)
-          CHECK(generic_jacobi(ctx, l.A, l.S, src, rhs, alpha, nPre, l.u[0], l.u[1], l.tmp, &resid_done));
+          CHECK(generic_jacobi(ctx, l.A, l.S, src, rhs, damp, nPre, l.u[0], l.u[1], l.tmp, &resid_done));
         } else {
           for (int s = 0; s < nPre; ++s) {
-            CHECK(generic_sweep(ctx, l.A, l.S, src, rhs, alpha, l.u[0], k));
+            CHECK(generic_sweep(ctx, l.A, l.S, src, rhs, damp.at(s), l.u[0], k));
             src = l.u[0];
           }
         }
@@ -2012,6 +2090,7 @@ struct CoarseSplit {
 static int vcycle_up(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, double alpha, double* x_out,
                      int k_last = 0, const TileSel& sel = TileSel(), const CoarseSplit& cs = CoarseSplit()) {
   const int n = (int)h->lv.size();
+  CHECK(schedule_check(ctx, h, -1, nPost, k_last));
   if (cs.mode != 0) {
     const int k = n - 2;
     if (!(sel.mode == 0 && k - 1 >= std::max(k_last, 1) && pair_ok(ctx, h, k - 1, nPost, true)))
@@ -2034,6 +2113,7 @@ static int vcycle_up(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, 
     const double* rhs = k == 0 ? b : l.rhs;
     double* dst = k == 0 ? x_out : l.u[1];
     const double* uc = (k + 1 == n - 1) ? c.u[0] : c.u[1];
+    const Damping damp = l.damp_post(alpha);
     if (sel.mode == 0 && k - 1 >= std::max(k_last, 1) && pair_ok(ctx, h, k - 1, nPost, true)) {   // this level and the finer one in one launch
       CHECK(launch_pair_up(ctx, h, k - 1, nPost, alpha, h->lv[k - 1].u[1]));
       --k;
@@ -2048,7 +2128,7 @@ static int vcycle_up(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, 
     const bool structured = l.S->btd && l.S->A == l.A;
     if (structured && l.tb && btd_launch_ok(*l.S, nPost, 0, nullptr)) {
       // (Gauss-Seidel post-smoothing in the reverse colour order: the cycle stays symmetric)
-      FusedArgs a = fused_sweeps(*l.S->btd, l.u[0], rhs, dst, alpha, nPost, l.S->gs ? 2 : 0);
+      FusedLaunch a = fused_sweeps(*l.S->btd, l.u[0], rhs, dst, damp, nPost, l.S->gs ? 2 : 0);
       fused_ascent(a, l, uc);
       if (sel.mode == 0) fused_dictionary(a, l);   // (the partitioned cycle's tile selections keep the full arrays)
       ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
@@ -2062,7 +2142,7 @@ static int vcycle_up(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, 
         CHECK(launch_csr<kSpmvAdd>(ctx, l.L->csr, uc, nullptr, nullptr, 0.0, l.u[0]));
       }
       if (structured) {
-        CHECK(btd_smooth(ctx, *l.S->btd, l.u[0], rhs, alpha, nPost, dst, k, l.N, l.S->gs ? 2 : 0));
+        CHECK(btd_smooth(ctx, *l.S->btd, l.u[0], rhs, damp, nPost, dst, k, l.N, l.S->gs ? 2 : 0));
       } else {
         const double* src = l.u[0];
         if (nPost == 0) HIPCHK(hipMemcpyAsync(dst, src, l.N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
@@ -2070,11 +2150,11 @@ static int vcycle_up(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, 
         if (l.S->kind == 0 && nPost > 0) {
           CHECK(op_ensure_csr(ctx, l.A));
           ProfScope ps(ctx, AGGMG_KIND_JACOBI, k);
-          CHECK(generic_jacobi(ctx, l.A, l.S, src, rhs, alpha, nPost, dst, alt));
+          CHECK(generic_jacobi(ctx, l.A, l.S, src, rhs, damp, nPost, dst, alt));
         } else {
           for (int s = 0; s < nPost; ++s) {
             double* d2 = (s == nPost - 1) ? dst : l.u[0];
-            CHECK(generic_sweep(ctx, l.A, l.S, src, rhs, alpha, d2, k));
+            CHECK(generic_sweep(ctx, l.A, l.S, src, rhs, damp.at(s), d2, k));
             src = d2;
           }
         }
@@ -2102,6 +2182,7 @@ extern "C" int aggmg_vcycle_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0,
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle: hierarchy was created with AGGMG_COARSE_EXTERNAL; use "
                                          "aggmg_vcycle_down_dev / aggmg_vcycle_up_dev");
   const int n = (int)h->lv.size();
+  CHECK(schedule_check(ctx, h, nPre, nPost));   // (both halves before anything is enqueued)
   h->last_coarse_ms = 0.0;
   CHECK(vcycle_down(ctx, h, x0, b, nPre, alpha));
   {  // coarsest solve (src/solvers.jl:39)
@@ -2158,7 +2239,7 @@ static bool multi_ok(const aggmg_hier* h, int nPre, int nPost) {
 }
 
 template <int M, bool CMP, bool SYM>
-static int launch_multi_t(aggmg_ctx* ctx, MultiArgs m, int halo) {
+static int launch_multi_t(aggmg_ctx* ctx, MultiArgs m, const SweepWeights& wts, int halo) {
   constexpr int TE = kMultiNT / M;
   const int align = m.a.lf_out ? m.a.rho_out : 1;
   const int owned = multi_tile_owned(TE, halo, align);   // host_plan.hpp, as multi_level_ok
@@ -2169,7 +2250,7 @@ static int launch_multi_t(aggmg_ctx* ctx, MultiArgs m, int halo) {
   if (ntiles == 0) return AGGMG_OK;
   auto go = [&](auto kern, int kb) {
     const size_t lds = (size_t)2 * kb * (TE + 2) * M * sizeof(double);
-    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(kMultiNT), lds, ctx->stream, m);
+    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(kMultiNT), lds, ctx->stream, m, wts);
   };
   // the smallest instantiated group that holds the columns
   if (m.kc <= 1)
@@ -2184,11 +2265,11 @@ static int launch_multi_t(aggmg_ctx* ctx, MultiArgs m, int halo) {
   return AGGMG_OK;
 }
 
-static int launch_multi(aggmg_ctx* ctx, const BtdDev& b, const MultiArgs& m, int halo) {
+static int launch_multi(aggmg_ctx* ctx, const BtdDev& b, const MultiArgs& m, const SweepWeights& wts, int halo) {
   const bool sym = b.bsym != nullptr;
-  if (b.cmp && b.m == 4) return sym ? launch_multi_t<4, true, true>(ctx, m, halo) : launch_multi_t<4, true, false>(ctx, m, halo);
-  if (b.cmp && b.m == 2) return sym ? launch_multi_t<2, true, true>(ctx, m, halo) : launch_multi_t<2, true, false>(ctx, m, halo);
-  if (!b.cmp && b.m == 2) return sym ? launch_multi_t<2, false, true>(ctx, m, halo) : launch_multi_t<2, false, false>(ctx, m, halo);
+  if (b.cmp && b.m == 4) return sym ? launch_multi_t<4, true, true>(ctx, m, wts, halo) : launch_multi_t<4, true, false>(ctx, m, wts, halo);
+  if (b.cmp && b.m == 2) return sym ? launch_multi_t<2, true, true>(ctx, m, wts, halo) : launch_multi_t<2, true, false>(ctx, m, wts, halo);
+  if (!b.cmp && b.m == 2) return sym ? launch_multi_t<2, false, true>(ctx, m, wts, halo) : launch_multi_t<2, false, false>(ctx, m, wts, halo);
   return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: block size not instantiated for the K-column kernel");
 }
 
@@ -2223,7 +2304,8 @@ static int vcycle_multi_group(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, c
     MultiArgs m;
     std::memset(&m, 0, sizeof(m));
     // u[k] = zeros for k > 1 (:29-31)
-    m.a = fused_sweeps(*l.S->btd, k == 0 ? X0 : nullptr, k == 0 ? B : h->mu[k][2], h->mu[k][0], alpha, nPre);
+    const FusedLaunch f = fused_sweeps(*l.S->btd, k == 0 ? X0 : nullptr, k == 0 ? B : h->mu[k][2], h->mu[k][0], l.damp_pre(alpha), nPre);
+    m.a = f;
     fused_descent(m.a, h, l, h->mu[k + 1][2]);   // (lf: multi_level_ok refuses the levels that would take (L'D))
     m.kc = kc;
     m.ld_uin = ld;
@@ -2231,7 +2313,7 @@ static int vcycle_multi_group(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, c
     m.ld_uout = l.N;
     m.ld_rc = c.N;
     ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
-    CHECK(launch_multi(ctx, *l.S->btd, m, nPre + 1));
+    CHECK(launch_multi(ctx, *l.S->btd, m, f.wts, nPre + 1));
   }
   {  // coarsest solve (:39): one launch sequence for the group
     const int64_t Nc = h->lv[n - 1].N;
@@ -2242,7 +2324,8 @@ static int vcycle_multi_group(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, c
     Level& c = h->lv[k + 1];
     MultiArgs m;
     std::memset(&m, 0, sizeof(m));
-    m.a = fused_sweeps(*l.S->btd, h->mu[k][0], k == 0 ? B : h->mu[k][2], k == 0 ? X : h->mu[k][1], alpha, nPost);
+    const FusedLaunch f = fused_sweeps(*l.S->btd, h->mu[k][0], k == 0 ? B : h->mu[k][2], k == 0 ? X : h->mu[k][1], l.damp_post(alpha), nPost);
+    m.a = f;
     fused_ascent(m.a, l, (k + 1 == n - 1) ? h->mu[k + 1][0] : h->mu[k + 1][1]);
     m.kc = kc;
     m.ld_uin = l.N;
@@ -2250,7 +2333,7 @@ static int vcycle_multi_group(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, c
     m.ld_uout = k == 0 ? ld : l.N;
     m.ld_uc = c.N;
     ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
-    CHECK(launch_multi(ctx, *l.S->btd, m, nPost));
+    CHECK(launch_multi(ctx, *l.S->btd, m, f.wts, nPost));
   }
   return AGGMG_OK;
 }
@@ -2305,6 +2388,7 @@ extern "C" int aggmg_vcycle_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const doubl
       CHECK(aggmg_vcycle_dev(ctx, h, X0 ? X0 + j * ld : nullptr, B + j * ld, nPre, nPost, alpha, X + j * ld));
     return AGGMG_OK;
   }
+  CHECK(schedule_check(ctx, h, nPre, nPost));
   const int64_t group = std::min<int64_t>(ncols, kMultiKB);
   CHECK(multi_workspace(ctx, h, group));
   h->last_coarse_ms = 0.0;
@@ -2371,7 +2455,7 @@ struct FineLevel {
   int mid(const double* cur, double* alt, CgtChk* chk) const {
     if (chain) return cgt_mid(ctx, h, cur, alt, b, nPost + nPre, alpha, chk);
     const BtdDev& B0 = *l0().S->btd;
-    FusedArgs a = fused_sweeps(B0, cur, b, alt, alpha, nPost + nPre);
+    FusedLaunch a = fused_sweeps(B0, cur, b, alt, l0().damp_mid(alpha), nPost + nPre);
     fused_ascent(a, l0(), uc());
     fused_descent(a, h, l0(), h->lv[1].rhs);
     if (chk) fused_chk(a, *chk);
@@ -2383,7 +2467,7 @@ struct FineLevel {
   int up(const double* src, double* dst, CgtChk* chk) const {
     if (chain) return cgt_up(ctx, h, 0, b, nPost, alpha, dst, src, chk);
     const BtdDev& B0 = *l0().S->btd;
-    FusedArgs a = fused_sweeps(B0, src, b, dst, alpha, nPost);
+    FusedLaunch a = fused_sweeps(B0, src, b, dst, l0().damp_post(alpha), nPost);
     fused_ascent(a, l0(), uc());
     if (chk) fused_chk(a, *chk);
     fused_dictionary(a, l0());
@@ -2415,6 +2499,7 @@ static int cycle_loop(const FineLevel& f, const double* x0, int ncycles, double*
   aggmg_ctx* ctx = f.ctx;
   aggmg_hier* h = f.h;
   h->last_coarse_ms = 0.0;
+  CHECK(schedule_check(ctx, h, f.nPre, f.nPost));
   CHECK(vcycle_down(ctx, h, x0, f.b, f.nPre, f.alpha, 0));                    // cycle 1: every level down ...
   CHECK(coarse_levels(ctx, h, f.b, f.nPre, f.nPost, f.alpha, false));         // ... the coarsest solve and the coarser levels up
   double* cur = f.l0().u[0];   // pre-smoothed fine iterate of the current cycle
@@ -3010,6 +3095,56 @@ extern "C" int aggmg_norm2_dev(aggmg_ctx* ctx, const double* x, int64_t n, doubl
   return read_scalar(ctx, ctx->solv_sc + 15, out);
 }
 
+// EXTENSION (no reference counterpart): power iteration for the largest eigenvalue of S^-1 A of a level, what a
+// Chebyshev sweep-weight schedule is scaled by.  One step: t = A v (the residual launch on a zero right-hand side: -A v,
+// the sign changes no norm), w = S^-1 t (one sweep of the level's smoother with factor 1 from the zero iterate), then
+// ||w|| and v = w / ||w|| on the stream.  The estimate is ||w|| / ||v|| of the last step: one host read, at the end.
+extern "C" int aggmg_hier_estimate_lambda_max(aggmg_ctx* ctx, aggmg_hier* h, int level, const double* v0, int iters,
+                                              double* lambda_max) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!h || !lambda_max) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_estimate_lambda_max: NULL argument");
+  if (level < 0 || level >= (int)h->lv.size() - 1)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_estimate_lambda_max: level out of range (the coarsest level has no smoother)");
+  if (iters < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_estimate_lambda_max: iters must be >= 1");
+  HIPCHK(hipSetDevice(ctx->device));
+  Level& l = h->lv[level];
+  const int64_t N = l.N;
+  if (N == 0) {
+    *lambda_max = 0.0;
+    return AGGMG_OK;
+  }
+  CHECK(solv_scalars(ctx));
+  // work vectors of THIS call (allocated and freed per call: the estimate is made once per hierarchy, not per cycle): the
+  // iterate, A v, S^-1 A v, and the zero right-hand side that turns the residual launch into -A v
+  DevArray<double> v, t, w, zero;
+  CHECK(v.alloc(ctx, N));
+  CHECK(t.alloc(ctx, N));
+  CHECK(w.alloc(ctx, N));
+  CHECK(zero.alloc(ctx, N, true));
+  const unsigned nb = (unsigned)((N + kThreads - 1) / kThreads);
+  if (v0) {
+    HIPCHK(hipMemcpyAsync(v, v0, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  } else {   // a fixed start, made on the device
+    hipLaunchKernelGGL(seed_vector_kernel, dim3(nb), dim3(kThreads), 0, ctx->stream, N, (double*)v);
+    HIPCHK(hipGetLastError());
+  }
+  double* sc = ctx->solv_sc + 10;   // [0] ||w||, [1] ||v|| of the last step
+  for (int it = 0; it < iters; ++it) {
+    CHECK(aggmg_residual_dev(ctx, l.A, v, zero, t));
+    CHECK(smooth_dev(ctx, l.A, l.S, nullptr, t, Damping(1.0), 1, w));
+    if (it == iters - 1) CHECK(dev_dot(ctx, N, v, v, sc + 1, 1));
+    CHECK(dev_dot(ctx, N, w, w, sc, 1));
+    hipLaunchKernelGGL(div_scalar_kernel, dim3(nb), dim3(kThreads), 0, ctx->stream, N, (const double*)w, (const double*)sc,
+                       (double*)v);
+    HIPCHK(hipGetLastError());
+  }
+  double out[2] = {0.0, 0.0};
+  HIPCHK(hipMemcpyAsync(out, sc, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *lambda_max = out[1] > 0.0 ? out[0] / out[1] : 0.0;
+  return AGGMG_OK;
+}
+
 // ||b - A x||_2 on the device (work vector slot 0)
 static int residual_norm(aggmg_ctx* ctx, aggmg_op* A, const double* x, const double* b, double* out) {
   double* r = nullptr;
@@ -3198,7 +3333,7 @@ extern "C" int aggmg_smoother_solve_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoot
     auto sweeps = [&](const double* src, double* dst, int S, CgtChk* chk) -> int {
       if (chain) return cgt_smooth_ext(ctx, *sm->cgt, src, b, alpha, S, dst, 0, chk);
       if (!chk) return btd_smooth(ctx, *sm->btd, src, b, alpha, S, dst, 0, N, 0);
-      FusedArgs a = fused_sweeps(*sm->btd, src, b, dst, alpha, S);
+      FusedLaunch a = fused_sweeps(*sm->btd, src, b, dst, alpha, S);
       fused_chk(a, *chk);
       ProfScope ps(ctx, AGGMG_KIND_SMOOTH, 0);
       return launch_btd(ctx, *sm->btd, a, S + 1, TileSel(), chk);

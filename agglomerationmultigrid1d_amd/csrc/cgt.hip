@@ -70,17 +70,17 @@ static int cgt_max_sweeps(int m, int sw = 0) {
 int cgt_max_fused_sweeps(const CgtDev& g) { return cgt_max_sweeps(g.m, g.sw); }
 
 template <int M, int K>
-static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, int sw, CgtChk* chk_io);
+static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, const SweepWeights& wts, int sw, CgtChk* chk_io);
 
 template <int M>
-static int cgt_launch_t(aggmg_ctx* ctx, CgtArgs a, int sw, CgtChk* chk_io) {
+static int cgt_launch_t(aggmg_ctx* ctx, CgtArgs a, const SweepWeights& wts, int sw, CgtChk* chk_io) {
   if (a.nsweeps == 0) sw = 0;
-  if (sw == 3) return cgt_launch_tt<M, 2>(ctx, a, sw, chk_io);
-  return sw ? cgt_launch_tt<M, 1>(ctx, a, sw, chk_io) : cgt_launch_tt<M, 0>(ctx, a, sw, chk_io);
+  if (sw == 3) return cgt_launch_tt<M, 2>(ctx, a, wts, sw, chk_io);
+  return sw ? cgt_launch_tt<M, 1>(ctx, a, wts, sw, chk_io) : cgt_launch_tt<M, 0>(ctx, a, wts, sw, chk_io);
 }
 
 template <int M, int K>
-static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, int sw, CgtChk* chk_io) {
+static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, const SweepWeights& wts, int sw, CgtChk* chk_io) {
   using T = CgtTile<M, K>;
   // halo: one block per sweep and side (element Schwarz: the update of a block reads the residual of its two
   // neighbours, i.e. the iterate two blocks away); the residual needs one more valid neighbour on both sides,
@@ -119,7 +119,7 @@ static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, int sw, CgtChk* chk_io) {
     if constexpr (K == 0 && (M == 1 || M == 2 || M == 4)) {
       if (a.chk_part) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: dictionary launch of a checkpoint variant");
       lds += (size_t)(T::TE + 2) * sizeof(uint16_t);
-      hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 0, false, true>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a);
+      hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 0, false, true>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a, wts);
       HIPCHK(hipGetLastError());
       return AGGMG_OK;
     }
@@ -127,30 +127,30 @@ static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, int sw, CgtChk* chk_io) {
   }
   if constexpr (K == 0) {
     if (a.chk_part) {
-      hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 0, true>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a);
+      hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 0, true>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a, wts);
       HIPCHK(hipGetLastError());
       return AGGMG_OK;
     }
   }
   if constexpr (K == 2) {
-    hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 3>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a);
+    hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 3>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a, wts);
   } else if constexpr (K == 1) {
     if (sw == 1)
-      hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 1>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a);
+      hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 1>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a, wts);
     else
-      hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 2>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a);
+      hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 2>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a, wts);
   } else {
-    hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 0>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a);
+    hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 0>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a, wts);
   }
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
 
-static int cgt_launch(aggmg_ctx* ctx, const CgtDev& g, const CgtArgs& a, CgtChk* chk_io = nullptr) {
+static int cgt_launch(aggmg_ctx* ctx, const CgtDev& g, const CgtArgs& a, const SweepWeights& wts, CgtChk* chk_io = nullptr) {
   switch (g.m) {
 #define CASE(MM) \
   case MM:       \
-    return cgt_launch_t<MM>(ctx, a, g.sw, chk_io);
+    return cgt_launch_t<MM>(ctx, a, wts, g.sw, chk_io);
     CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
 #undef CASE
   }
@@ -212,7 +212,7 @@ struct CgtChain {
   int gs = 0;  // red-black element Gauss-Seidel: colour order of every sweep (1 forward, 2 reverse)
 };
 
-static int cgt_run(aggmg_ctx* ctx, const CgtDev& g, const CgtChain& c, double alpha, int nsweeps, const CgtArgs& first,
+static int cgt_run(aggmg_ctx* ctx, const CgtDev& g, const CgtChain& c, Damping alpha, int nsweeps, const CgtArgs& first,
                    const CgtArgs& last, int kind, int level, CgtChk* chk = nullptr, const CgtDictDev* dict = nullptr) {
   // at most smax sweeps per launch (2 * smax + 3 blocks of halo always fit a tile)
   const int smax = cgt_max_sweeps(g.m, g.sw);
@@ -224,9 +224,9 @@ static int cgt_run(aggmg_ctx* ctx, const CgtDev& g, const CgtChain& c, double al
   int left = nsweeps;
   for (int q = 0; q < nl; ++q) {
     CgtArgs a = cgt_args(g);
-    a.alpha = alpha;
     a.gs = c.gs;
     a.nsweeps = std::min(left, smax);
+    const SweepWeights wts = alpha.from(nsweeps - left).launch(a.nsweeps);   // this launch's slice of the run
     left -= a.nsweeps;
     a.u_in = src;
     a.b = c.b;
@@ -260,7 +260,7 @@ static int cgt_run(aggmg_ctx* ctx, const CgtDev& g, const CgtChain& c, double al
     cgt_dictionary(a, g, dict);   // (every chunk: the intermediate launches read the operator too)
     {
       ProfScope ps(ctx, q == nl - 1 ? kind : AGGMG_KIND_SMOOTH, level);
-      CHECK(cgt_launch(ctx, g, a, chk));
+      CHECK(cgt_launch(ctx, g, a, wts, chk));
     }
     src = dst;
     src_ext = false;
@@ -268,7 +268,7 @@ static int cgt_run(aggmg_ctx* ctx, const CgtDev& g, const CgtChain& c, double al
   return AGGMG_OK;
 }
 
-int cgt_smooth_ext(aggmg_ctx* ctx, const CgtDev& g, const double* u_in, const double* b, double alpha, int nsweeps,
+int cgt_smooth_ext(aggmg_ctx* ctx, const CgtDev& g, const double* u_in, const double* b, Damping alpha, int nsweeps,
                    double* u_out, int level, CgtChk* chk) {
   if (nsweeps == 0) {
     if (u_in)
@@ -300,7 +300,7 @@ int cgt_residual_ext(aggmg_ctx* ctx, const CgtDev& g, const double* u, const dou
   a.ext = kExtUin | kExtB | kExtRout;
   a.do_residual = 1;
   a.r_out = r_out;
-  return cgt_launch(ctx, g, a);
+  return cgt_launch(ctx, g, a, SweepWeights{});   // (no sweeps)
 }
 
 // descending half on a fused chain level (src/solvers.jl:28-37): nPre sweeps, residual, restriction
@@ -323,7 +323,7 @@ int cgt_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uin, const doub
   last.do_residual = 1;
   last.tout = cgt_xfer(*l.tc, c.native_io);
   last.rc_out = c.rhs;
-  return cgt_run(ctx, g, ch, alpha, nPre, none, last, AGGMG_KIND_FUSED_DOWN, k, nullptr, l.cdict.get());
+  return cgt_run(ctx, g, ch, l.damp_pre(alpha), nPre, none, last, AGGMG_KIND_FUSED_DOWN, k, nullptr, l.cdict.get());
 }
 
 // ascending half (src/solvers.jl:41-47): prolongation-add, nPost sweeps
@@ -350,7 +350,7 @@ int cgt_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* rhs, int nPost, d
   std::memset(&none, 0, sizeof(none));
   first.tin = cgt_xfer(*l.tc, c.native_io);
   first.uc = (k + 1 == n - 1) ? c.u[0] : c.u[1];
-  return cgt_run(ctx, g, ch, alpha, nPost, first, none, AGGMG_KIND_FUSED_UP, k, chk, l.cdict.get());
+  return cgt_run(ctx, g, ch, l.damp_post(alpha), nPost, first, none, AGGMG_KIND_FUSED_UP, k, chk, l.cdict.get());
 }
 
 // Between two cycles of multigrid()'s loop (src/solvers.jl:124-126) the fine level post-smooths and then
@@ -380,7 +380,7 @@ int cgt_mid(aggmg_ctx* ctx, aggmg_hier* h, const double* cur, double* alt, const
   last.do_residual = 1;
   last.tout = cgt_xfer(*l.tc, c.native_io);
   last.rc_out = c.rhs;
-  return cgt_run(ctx, g, ch, alpha, nsweeps, first, last, AGGMG_KIND_FUSED_MID, 0, chk, l.cdict.get());
+  return cgt_run(ctx, g, ch, l.damp_mid(alpha), nsweeps, first, last, AGGMG_KIND_FUSED_MID, 0, chk, l.cdict.get());
 }
 
 // ---- compulsory bytes: what the arrays of a launch hold, each read or written once -------------

@@ -64,7 +64,6 @@ struct CgtArgs {
   const double* u_in;   // nullptr: iterate starts at zero (src/solvers.jl:29-31)
   const double* b;
   double* u_out;        // nullptr: iterate not stored
-  double alpha;
   int nsweeps;
   CgtXfer tin;          // prolongation-add before the sweeps (src/solvers.jl:42)
   const double* uc;
@@ -113,7 +112,7 @@ __device__ __forceinline__ int64_t cgt_tile(const CgtArgs& a) {
 // the results are the same bits.  The tile's classes also sit in LDS for the restriction, which walks the rows of L of
 // other threads' blocks.
 template <int M, int NS, int NT, int SW = 0, bool CHK = false, bool DICT = false>
-__global__ __launch_bounds__(NT) void cgt_fused_kernel(CgtArgs a) {
+__global__ __launch_bounds__(NT) void cgt_fused_kernel(CgtArgs a, SweepWeights wts) {
   static_assert(!CHK || SW == 0, "the checkpoint variant is for point-Jacobi launches");
   static_assert(!DICT || (SW == 0 && !CHK && (M == 1 || M == 2 || M == 4)), "the dictionary variant's levels");
   // GRP: a block's rows sit in M = 2^k adjacent lanes; lane i keeps entry i of the block's
@@ -358,6 +357,7 @@ __global__ __launch_bounds__(NT) void cgt_fused_kernel(CgtArgs a) {
   };
   [[maybe_unused]] auto chk_due = [&](int sw) { return sw >= a.chk_sweep && (sw - a.chk_sweep) % a.chk_stride == 0; };
   for (int sw = 0; sw < (SW == 3 ? 2 * a.nsweeps : a.nsweeps); ++sw) {
+    const double wsw = wts.w[(unsigned)sw >> (SW == 3 ? 1 : 0)];   // this sweep's factor: wave-uniform, a scalar load
     if constexpr (CHK) {
       if (chk_due(sw)) checkpoint(cur);
     }
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(NT) void cgt_fused_kernel(CgtArgs a) {
               if (e > 0 && e < ne - 1) y = y / 2.0;  // mCountingMatrix: two elements share an interior vertex
             }
           }
-          double un = uu[s] + a.alpha * y;
+          double un = uu[s] + wsw * y;
           if (!valid[s]) un = 0.0;
           uu[s] = un;
           nxt[x * M + i] = un;
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(NT) void cgt_fused_kernel(CgtArgs a) {
         if (active) {
           const double r = bb[s] - row_Au(s, x, cur);
           const double y = r / dg[s];
-          double un = uu[s] + a.alpha * y;
+          double un = uu[s] + wsw * y;
           if (!valid[s]) un = 0.0;
           uu[s] = un;
           nxt[x * M + i] = un;

@@ -755,6 +755,10 @@ extern "C" int aggmg_dist_vcycle_dev(aggmg_ctx* ctx, aggmg_dist* d, double* x0, 
   if (!ctx || !d || !x0 || !b || !x_out) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_dist_vcycle_dev: NULL argument");
   if (nPre < 0 || nPost < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_dist_vcycle_dev: negative sweep count");
   if (x_out == x0 || x_out == b) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_dist_vcycle_dev: x_out must not alias x0 or b");
+  // sweep-weight schedules (aggmg_hier_set_sweep_weights) are refused here rather than honoured: the captured graphs are
+  // keyed by alpha alone, and the partitioned cycle has no bitwise test against a weighted single-device cycle
+  if (any_schedule(d->H))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_dist_vcycle_dev: the rank's hierarchy has a sweep-weight schedule");
   // hipGraph replay: a cycle with the same arguments was issued eagerly once (lazy allocations done)
   // and captured on its second call; host callbacks, the host coarsest solver and the event profiler
   // cannot be captured

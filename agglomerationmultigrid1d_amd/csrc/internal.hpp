@@ -243,6 +243,24 @@ struct CgtDictDev {
   DevArray<double> lp;       // agglomerating: [nclasses][mc]
 };
 
+// The damping of a run of sweeps on the host: one factor for all of them (w null -- the reference's alpha,
+// src/solvers.jl:19), or w[i] for sweep i of the run (a level's sweep-weight schedule, aggmg_hier_set_sweep_weights;
+// aggmg_smooth_weighted_dev).  Whatever cuts the run into launches hands each launch its slice: from(s).launch(n).
+struct Damping {
+  double alpha;
+  const double* w;
+  Damping(double a, const double* w_ = nullptr) : alpha(a), w(w_) {}
+  double at(int s) const { return w ? w[s] : alpha; }
+  Damping from(int s) const { return Damping(alpha, w ? w + s : nullptr); }
+  // the kernel argument of a launch of the run's first n sweeps (without a schedule every slot holds alpha)
+  SweepWeights launch(int n) const {
+    SweepWeights r;
+    for (int i = 0; i < kSweepWeights; ++i) r.w[i] = w ? (i < n ? w[i] : 0.0) : alpha;
+    return r;
+  }
+};
+static_assert(kSweepWeights == AGGMG_MAX_SWEEP_WEIGHTS, "the documented limit is the kernels' array");
+
 struct Level {
   aggmg_op* A = nullptr;
   aggmg_smoother* S = nullptr;
@@ -256,6 +274,13 @@ struct Level {
   bool cgt_fused = false;           // the level runs cgt_fused_kernel (chain form + structured transfer)
   bool native_io = false;           // rhs and u[1] are kept in block order (the finer level is a fused chain level)
   int64_t Nalloc = 0;               // length of the level's vectors (ne * m for chain levels)
+  // sweep-weight schedule (aggmg_hier_set_sweep_weights), or scheduled == false: the entry point's alpha.  w_mid = w_post
+  // ++ w_pre, the launch between two cycles (post-smoothing of one, pre-smoothing of the next)
+  bool scheduled = false;
+  std::vector<double> w_pre, w_post, w_mid;
+  Damping damp_pre(double alpha) const { return scheduled ? Damping(alpha, w_pre.data()) : Damping(alpha); }
+  Damping damp_post(double alpha) const { return scheduled ? Damping(alpha, w_post.data()) : Damping(alpha); }
+  Damping damp_mid(double alpha) const { return scheduled ? Damping(alpha, w_mid.data()) : Damping(alpha); }
 };
 
 struct BandedLU {
@@ -357,6 +382,13 @@ inline int scratch(aggmg_ctx* ctx, int slot, int64_t len, double** out) {
 // ---------------------------------------------------------------------------------------------
 // profiler (HIP events on the launch stream)
 // ---------------------------------------------------------------------------------------------
+// does any level carry a sweep-weight schedule?
+inline bool any_schedule(const aggmg_hier* h) {
+  for (const Level& l : h->lv)
+    if (l.scheduled) return true;
+  return false;
+}
+
 struct ProfScope {
   aggmg_ctx* ctx;
   int idx = -1;
@@ -403,7 +435,7 @@ int cgt_attach_schwarz(aggmg_ctx* ctx, aggmg_smoother* sm, int sw);
 int cgt_build_transfer(aggmg_ctx* ctx, const aggmg_op* L, const CgtDev& fine, const CgtDev* coarse, int hint_mc,
                        TransferCgt* out, bool* ok);
 // nsweeps sweeps on external (reference-numbered) vectors; u_in may be nullptr (zero), u_out != u_in
-int cgt_smooth_ext(aggmg_ctx* ctx, const CgtDev& g, const double* u_in, const double* b, double alpha, int nsweeps,
+int cgt_smooth_ext(aggmg_ctx* ctx, const CgtDev& g, const double* u_in, const double* b, Damping alpha, int nsweeps,
                    double* u_out, int level, CgtChk* chk = nullptr);
 int cgt_residual_ext(aggmg_ctx* ctx, const CgtDev& g, const double* u, const double* b, double* r_out);
 int cgt_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uin, const double* rhs, int nPre, double alpha);

@@ -18,6 +18,18 @@ namespace aggmg {
 
 constexpr int kThreads = 256;
 
+// Damping factors of the sweeps of ONE launch (EXTENSION: the reference damps every sweep by the same alpha,
+// src/solvers.jl:19-50): sweep s of the launch takes w[s] -- for red-black Gauss-Seidel both half-sweeps of sweep s.  A
+// launch without a schedule carries alpha in every slot, so there is one kernel body.  The array is part of the kernel
+// arguments and the sweep counter is wave-uniform: the factor arrives by a scalar load, no vector register holds it.
+// It is a kernel argument of its OWN beside the argument struct (the launchers carry it beside the struct too): a
+// member indexed at run time keeps the compiler from holding the rest of the struct in scalar registers as before
+// (measured on the build: other register counts for most instantiations, a reserved private segment for seven).
+constexpr int kSweepWeights = 8;   // most sweeps any family fuses into one launch (AGGMG_MAX_SWEEP_WEIGHTS)
+struct SweepWeights {
+  double w[kSweepWeights];
+};
+
 // ------------------------------------------------------------------------------------------
 // generic CSR
 // ------------------------------------------------------------------------------------------
@@ -253,7 +265,7 @@ constexpr int kBandWin = kThreads + 2 * kBandMaxBw;   // a tile's rows (block + 
 template <int MODE>
 __global__ __launch_bounds__(kThreads) void csr_band_kernel(CsrView A, const int32_t* __restrict__ bandblk, int bw, int S,
                                                             const double* __restrict__ x, const double* __restrict__ b,
-                                                            const double* __restrict__ dg, double alpha,
+                                                            const double* __restrict__ dg, SweepWeights alpha,
                                                             double* __restrict__ y, double* __restrict__ rout) {
   static_assert(MODE == kJacobi, "the multi-sweep window kernel runs point-Jacobi sweeps");
   // rout (may be null): the residual b - A y of the swept iterate on the block's rows, one more pass over the tile and
@@ -324,7 +336,7 @@ __global__ __launch_bounds__(kThreads) void csr_band_kernel(CsrView A, const int
       const double res = br - acc;
       if (s < S) {
         const double yy = res / dr;
-        const double val = xa[r - w0] + alpha * yy;
+        const double val = xa[r - w0] + alpha.w[s] * yy;
         if (s == S - 1 && own) y[r] = val;
         if (s < P - 1) xw[cur ^ 1][r - w0] = val;
       } else if (own) {
@@ -626,6 +638,24 @@ static __global__ __launch_bounds__(kThreads) void pcg_xr_kernel(int64_t n, doub
   r[i] += a * q[i];
 }
 
+// v = w / sc[0], sc on the device (a norm formed on the stream: power iteration, aggmg_hier_estimate_lambda_max)
+static __global__ __launch_bounds__(kThreads) void div_scalar_kernel(int64_t n, const double* __restrict__ w,
+                                                                     const double* __restrict__ sc, double* __restrict__ v) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i < n) v[i] = w[i] / sc[0];
+}
+
+// v[i] = a fixed pseudo-random value in (-1, 1): splitmix64 of the row number (the seeded start vector of the power iteration)
+static __global__ __launch_bounds__(kThreads) void seed_vector_kernel(int64_t n, double* __restrict__ v) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  uint64_t z = (uint64_t)(i + 1) * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  v[i] = (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+}
+
 // p = z + (rz_new / rz_old) p
 static __global__ __launch_bounds__(kThreads) void pcg_p_kernel(int64_t n, double* __restrict__ p,
                                                          const double* __restrict__ z,
@@ -683,7 +713,6 @@ struct FusedArgs {
   const double* u_in;  // nullptr: iterate starts at zero (src/solvers.jl:29-31)
   const double* b;
   double* u_out;       // nullptr: iterate not stored (residual-only call)
-  double alpha;
   int nsweeps;
   // optional prolongation-add before the sweeps: u += LF_in * uc   (src/solvers.jl:42)
   const double* lf_in;  // [N][mc_in] rows of L for the owning coarse element
@@ -979,7 +1008,7 @@ __device__ __forceinline__ double btd_prolong2(double2 l2, double2 u2) {
 // plain variant.  Two-mode transfers of equal agglomerates only (the launcher's condition).
 template <int M, bool CMP, int NS, bool SYM = false, int NT = kThreads, bool GS = false, bool CHK = false, bool SR = false,
           bool DICT = false>
-__global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kernel(FusedArgs a) {
+__global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kernel(FusedArgs a, SweepWeights wts) {
   static_assert(!SYM || M == 2 || M == 4 || M == 8, "symmetric packing needs the lane-group path");
   static_assert(!(CHK && GS), "the checkpoint is for block-Jacobi launches");
   static_assert(!DICT || (CMP && SYM && (M == 2 || M == 4) && !GS && !CHK), "the dictionary variant's levels");
@@ -1430,7 +1459,7 @@ __global__ __launch_bounds__(NT, CHK ? AGGMG_CHK_WAVES : 1) void btd_fused_kerne
           acc = btd_stencil_cmp<M, GRP, !GS>(g[s], pc[s], qv[s], binv_r[s], um, up, a.lv.c_sub, i);
         else
           acc = btd_stencil_dense<M>(g[s], Pr[s], Qr[s], um, up);
-        double un = btd_damped(uu[s], a.alpha, acc);
+        double un = btd_damped(uu[s], wts.w[(unsigned)sw >> (GS ? 1 : 0)], acc);
         if (!valid[s]) un = 0.0;
         if constexpr (!GS) {
           uu[s] = un;

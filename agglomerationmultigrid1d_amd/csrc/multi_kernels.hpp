@@ -27,7 +27,7 @@ struct MultiArgs {
 };
 
 template <int M, bool CMP, bool SYM, int KB, int NT>
-__global__ __launch_bounds__(NT) void btd_multi_kernel(MultiArgs ma) {
+__global__ __launch_bounds__(NT) void btd_multi_kernel(MultiArgs ma, SweepWeights wts) {
   static_assert(M == 2 || M == 4, "lane-group path only");
   static_assert(CMP || M == 2, "dense couplings: M = 2");
   constexpr bool GRP = CMP;
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(NT) void btd_multi_kernel(MultiArgs ma) {
         acc = btd_stencil_cmp<M, GRP>(g[k], pc, qv, binv_r, um, up, a.lv.c_sub, i);
       else
         acc = btd_stencil_dense<M>(g[k], Pr, Qr, um, up);
-      double un = btd_damped(uu[k], a.alpha, acc);
+      double un = btd_damped(uu[k], wts.w[sw], acc);
       if (!valid) un = 0.0;
       uu[k] = un;
       nxt[k * PL + x * M + i] = un;

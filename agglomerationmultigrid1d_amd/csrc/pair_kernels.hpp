@@ -37,7 +37,6 @@ struct PairXfer {      // two coarse modes per element
 struct PairArgs {
   PairLevel A, B;   // level a = k (finer), b = k + 1
   PairXfer ab, bc;  // a <-> b, b <-> b + 1
-  double alpha;
   int nsweeps;
   // descent: rhs_a in; u_a, rhs_b, u_b, rhs_c out.  ascent: rhs_a, rhs_b, u_a (pre-smoothed), u_b (pre-smoothed),
   // uc (level b + 1) in; ua_out (and ub_out when not null) out
@@ -104,7 +103,7 @@ __device__ __forceinline__ void pair_load_rows(const PairLevel& L, bool valid, i
 
 // nsweeps block-Jacobi sweeps of a tile in LDS (ping-pong, one barrier per sweep); uu[] carries the thread's own rows
 template <int M, int NS, int EPS>
-__device__ __forceinline__ void pair_sweeps(int nsweeps, double alpha, int le, int i, const bool (&valid)[NS], const double (&g)[NS],
+__device__ __forceinline__ void pair_sweeps(int nsweeps, const SweepWeights& alpha, int le, int i, const bool (&valid)[NS], const double (&g)[NS],
                                             const double (&Pr)[NS][M], const double (&Qr)[NS][M], double (&uu)[NS], double*& cur,
                                             double*& nxt) {
   for (int sw = 0; sw < nsweeps; ++sw) {
@@ -118,7 +117,7 @@ __device__ __forceinline__ void pair_sweeps(int nsweeps, double alpha, int le, i
       for (int j = 0; j < M; ++j) acc -= Pr[s][j] * um[j];
 #pragma unroll
       for (int j = 0; j < M; ++j) acc -= Qr[s][j] * up[j];
-      double un = uu[s] + alpha * (acc - uu[s]);
+      double un = uu[s] + alpha.w[sw] * (acc - uu[s]);
       if (!valid[s]) un = 0.0;
       uu[s] = un;
       nxt[x * M + i] = un;
@@ -158,7 +157,7 @@ __device__ __forceinline__ void pair_l2(const PairXfer& X, int64_t row, double& 
 // LDS: [ two iterate buffers of (TEA + 2) * M doubles, each padded by one zero element on both sides | level-b vector
 // of TEB * 2 doubles ]; the level-b iterate buffers reuse the front region
 template <int M, int NSA, int NSB, int NT>
-__global__ __launch_bounds__(NT) void btd_pair_down_kernel(PairArgs a) {
+__global__ __launch_bounds__(NT) void btd_pair_down_kernel(PairArgs a, SweepWeights wa, SweepWeights wb) {
   constexpr int MB = 2;
   constexpr int EPSA = NT / M, TEA = EPSA * NSA;
   constexpr int EPSB = NT / MB, TEB = EPSB * NSB;
@@ -202,7 +201,7 @@ __global__ __launch_bounds__(NT) void btd_pair_down_kernel(PairArgs a) {
     __syncthreads();
     double* cur = buf0;
     double* nxt = buf1;
-    pair_sweeps<M, NSA, EPSA>(a.nsweeps, a.alpha, le, i, valid, g, Pr, Qr, uu, cur, nxt);
+    pair_sweeps<M, NSA, EPSA>(a.nsweeps, wa, le, i, valid, g, Pr, Qr, uu, cur, nxt);
     // iterate of the children of the owned level-b elements
     const int xs0 = h + h * rhoA, xs1 = h + (h + a.own) * rhoA;
     double rr[NSA];
@@ -268,7 +267,7 @@ __global__ __launch_bounds__(NT) void btd_pair_down_kernel(PairArgs a) {
     __syncthreads();
     double* cur = b0;
     double* nxt = b1;
-    pair_sweeps<MB, NSB, EPSB>(a.nsweeps, a.alpha, le, i, valid, g, Pr, Qr, uu, cur, nxt);
+    pair_sweeps<MB, NSB, EPSB>(a.nsweeps, wb, le, i, valid, g, Pr, Qr, uu, cur, nxt);
     double rr[NSB];
 #pragma unroll
     for (int s = 0; s < NSB; ++s) {
@@ -304,7 +303,7 @@ __global__ __launch_bounds__(NT) void btd_pair_down_kernel(PairArgs a) {
 // ascent: level b (prolongation from level b + 1, nsweeps sweeps) then level a (prolongation from the level-b tile in
 // LDS, nsweeps sweeps)
 template <int M, int NSA, int NSB, int NT>
-__global__ __launch_bounds__(NT) void btd_pair_up_kernel(PairArgs a) {
+__global__ __launch_bounds__(NT) void btd_pair_up_kernel(PairArgs a, SweepWeights wa, SweepWeights wb) {
   constexpr int MB = 2;
   constexpr int EPSA = NT / M, TEA = EPSA * NSA;
   constexpr int EPSB = NT / MB, TEB = EPSB * NSB;
@@ -359,7 +358,7 @@ __global__ __launch_bounds__(NT) void btd_pair_up_kernel(PairArgs a) {
     __syncthreads();
     double* cur = b0;
     double* nxt = b1;
-    pair_sweeps<MB, NSB, EPSB>(ns, a.alpha, le, i, valid, g, Pr, Qr, uu, cur, nxt);
+    pair_sweeps<MB, NSB, EPSB>(ns, wb, le, i, valid, g, Pr, Qr, uu, cur, nxt);
     const int64_t ob0 = (tile * a.own) / rhoA, ob1 = ob0 + a.own / rhoA;   // the parents of the owned level-a range
 #pragma unroll
     for (int s = 0; s < NSB; ++s) {
@@ -413,7 +412,7 @@ __global__ __launch_bounds__(NT) void btd_pair_up_kernel(PairArgs a) {
     __syncthreads();
     double* cur = buf0;
     double* nxt = buf1;
-    pair_sweeps<M, NSA, EPSA>(ns, a.alpha, le, i, valid, g, Pr, Qr, uu, cur, nxt);
+    pair_sweeps<M, NSA, EPSA>(ns, wa, le, i, valid, g, Pr, Qr, uu, cur, nxt);
 #pragma unroll
     for (int s = 0; s < NSA; ++s) {
       const int x = s * EPSA + le;

@@ -261,6 +261,13 @@ int aggmg_prolong_add(aggmg_ctx* ctx, aggmg_op* L, const double* uc, double* u_i
 /* Device-pointer variants (asynchronous on the context stream).  u_out may equal u_in. */
 int aggmg_smooth_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* u_in,
                      const double* b, double alpha, int nsweeps, double* u_out);
+/* EXTENSION (no reference counterpart: its smoothing loops damp every sweep by the same alpha, src/solvers.jl:32-35):
+ * sweep s of the nsweeps sweeps is damped by w[s] (host array, finite values) -- the launches of aggmg_smooth_dev with
+ * the same chunking (fused block-tridiagonal and chain kernels, up to 8 sweeps per launch on banded CSR operators, one
+ * sweep per launch otherwise), each launch carrying its slice of w.  A red-black Gauss-Seidel sweep takes one weight for
+ * both colours.  w with every entry alpha gives aggmg_smooth_dev's bits. */
+int aggmg_smooth_weighted_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* u_in,
+                              const double* b, const double* w, int nsweeps, double* u_out);
 int aggmg_residual_dev(aggmg_ctx* ctx, aggmg_op* A, const double* u, const double* b,
                        double* r_out);
 int aggmg_restrict_dev(aggmg_ctx* ctx, aggmg_op* L, const double* r, double* rc_out);
@@ -424,6 +431,33 @@ int aggmg_hier_level_sym_residual(aggmg_ctx* ctx, const aggmg_hier* h, int level
 /* Distinct operator records of the level's dictionary (AGGMG_OPT_OPERATOR_DICTIONARY); 0: the level has none and its
  * launches read the full arrays. */
 int aggmg_hier_level_dictionary(aggmg_ctx* ctx, const aggmg_hier* h, int level, int* nclasses);
+/* Sweep-weight schedule of a level (EXTENSION: the reference damps every sweep of every level by the same alpha,
+ * src/solvers.jl:19-50).  pre / post: host arrays; afterwards the level's i-th pre-smoothing sweep is damped by pre[i]
+ * and its i-th post-smoothing sweep by post[i] in EVERY entry point that runs the cycle on this hierarchy -- aggmg_vcycle
+ * (_dev), aggmg_vcycles_dev, aggmg_multigrid_dev, aggmg_pcg_dev, the _multi_ forms, aggmg_vcycle_down_dev / _up_dev --
+ * in place of their alpha argument; levels without a schedule keep alpha.  A red-black Gauss-Seidel level takes one
+ * weight per sweep (both colours).  npre = npost = 0 clears the level.  The weights ride in the kernel arguments of the
+ * launches the unscheduled cycle runs (a launch that post-smooths one cycle and pre-smooths the next takes post ++
+ * pre), so a schedule whose weights all equal alpha gives the unscheduled bits.
+ * AGGMG_ERR_ARGUMENT: NULL, a level outside 0 .. nlevels - 2 (the coarsest level is solved, not smoothed), a count
+ * outside 0 .. AGGMG_MAX_SWEEP_WEIGHTS, a weight that is not finite.  A cycle whose nPre / nPost differs from npre /
+ * npost of a scheduled level returns AGGMG_ERR_ARGUMENT: nothing is truncated or padded.  aggmg_dist_vcycle_dev refuses
+ * a hierarchy that has a schedule (AGGMG_ERR_UNSUPPORTED).  With pcg the cycle is a symmetric preconditioner only when
+ * post is pre reversed: that is the caller's responsibility.
+ * aggmg_hier_get_sweep_weights: pre / post receive the schedule (room for AGGMG_MAX_SWEEP_WEIGHTS each), *npre = *npost
+ * = 0 on a level without one. */
+#define AGGMG_MAX_SWEEP_WEIGHTS 8 /* most weights per half: every kernel family fuses at most 8 sweeps per launch */
+int aggmg_hier_set_sweep_weights(aggmg_ctx* ctx, aggmg_hier* h, int level, const double* pre, int npre,
+                                 const double* post, int npost);
+int aggmg_hier_get_sweep_weights(aggmg_ctx* ctx, const aggmg_hier* h, int level, double* pre, int* npre, double* post,
+                                 int* npost);
+/* Largest eigenvalue of S^-1 A of a level by power iteration, on the device (EXTENSION; what a Chebyshev schedule is
+ * scaled by).  v0: device start vector of the level's length, or NULL for a fixed seeded one.  One step is w = S^-1 (A v)
+ * -- the operator launch, then one sweep of the level's smoother with factor 1 from the zero iterate --, the estimate
+ * ||w|| / ||v|| and v = w / ||w||; iters >= 1 steps, ONE host read at the end (synchronises).  The estimate approaches
+ * the eigenvalue from below (0.989 - 0.995 of it after 40 steps on the benchmark hierarchies). */
+int aggmg_hier_estimate_lambda_max(aggmg_ctx* ctx, aggmg_hier* h, int level, const double* v0, int iters,
+                                   double* lambda_max);
 /* Which coarsest solver a hierarchy uses: on_device (1 = cyclic reduction), its block size and the
  * largest pivot-block condition estimate met while factoring (0 for the host solver). */
 int aggmg_hier_coarse_info(aggmg_ctx* ctx, const aggmg_hier* h, int* on_device, int* block_size,

@@ -383,6 +383,45 @@ function multigrid_v_cycle(Hd::DeviceHierarchy, x0::DeviceVector, b::DeviceVecto
     return out
 end
 
+# ---- sweep-weight schedules (EXTENSION: the reference damps every sweep of every level by the same alpha,
+# src/solvers.jl:19-50; include/aggmg_hip.h, aggmg_hier_set_sweep_weights) ------------------------------------------
+# level (1-based, as H.mMeshes) damps its i-th pre-smoothing sweep by pre[i] and its i-th post-smoothing sweep by post[i]
+# in every solver that runs the cycle on Hd, in place of their alpha; post defaults to pre reversed (the cycle stays a
+# symmetric preconditioner; another post is the caller's responsibility).  Empty pre and post clear the level.  A cycle's
+# nPre / nPost must equal the lengths (ArgumentError otherwise).
+function set_sweep_weights!(Hd::DeviceHierarchy, level::Integer, pre::AbstractVector{<:Real},
+        post::AbstractVector{<:Real} = reverse(pre))
+    p = Vector{Float64}(pre)
+    q = Vector{Float64}(post)
+    check(Hd.ctx.h, ccall((:aggmg_hier_set_sweep_weights, LIB), Cint,
+        (Handle, Handle, Cint, Ptr{Float64}, Cint, Ptr{Float64}, Cint),
+        Hd.ctx.h, Hd.h, level - 1, p, length(p), q, length(q)))
+    return Hd
+end
+
+# largest eigenvalue of S^-1 A of a level (1-based) by power iteration on the device; v0: start vector in HBM, or nothing
+# for a fixed seeded one (aggmg_hier_estimate_lambda_max)
+function estimate_lambda_max(Hd::DeviceHierarchy, level::Integer; iters::Integer = 40,
+        v0::Union{Nothing,DeviceVector} = nothing)
+    lam = Ref{Float64}(0.0)
+    if v0 === nothing
+        check(Hd.ctx.h, ccall((:aggmg_hier_estimate_lambda_max, LIB), Cint,
+            (Handle, Handle, Cint, Ptr{Cvoid}, Cint, Ref{Float64}), Hd.ctx.h, Hd.h, level - 1, C_NULL, iters, lam))
+    else
+        GC.@preserve v0 check(Hd.ctx.h, ccall((:aggmg_hier_estimate_lambda_max, LIB), Cint,
+            (Handle, Handle, Cint, Ptr{Cvoid}, Cint, Ref{Float64}), Hd.ctx.h, Hd.h, level - 1, v0.p, iters, lam))
+    end
+    return lam[]
+end
+
+# reciprocals of the roots of the degree-`degree` Chebyshev polynomial on [lam_max / ratio, safety * lam_max], smallest
+# first: the weights of `degree` sweeps whose error polynomial has the smallest maximum over that interval
+function chebyshev_weights(lam_max::Real; degree::Integer = 3, ratio::Real = 10.0, safety::Real = 1.05)
+    (degree >= 1 && lam_max > 0 && ratio > 1 && safety >= 1) || throw(ArgumentError("chebyshev_weights: bad argument"))
+    hi, lo = safety * lam_max, lam_max / ratio
+    return [1.0 / (0.5 * (hi + lo) + 0.5 * (hi - lo) * cos(pi * (2j + 1) / (2degree))) for j in 0:degree-1]
+end
+
 # ldiv!(y, H, b) with y, b in HBM: one V-cycle from a zero guess written into y (y must not be b: the entry point
 # refuses aliased output; ldiv!(H, b) for a DeviceVector goes through a fresh vector and swaps the storage)
 function la.ldiv!(y::DeviceVector, Hd::DeviceHierarchy, b::DeviceVector)
