@@ -27,6 +27,7 @@ KIND_FUSED_DOWN, KIND_FUSED_UP, KIND_SMOOTH, KIND_RESIDUAL, KIND_RESTRICT, KIND_
 KIND_NAMES = ["fused_down", "fused_up", "smooth", "residual", "restrict", "prolong", "jacobi",
               "block_apply", "coarse", "fused_mid"]
 COARSE_HOST_BANDED, COARSE_DEVICE_CR, COARSE_AUTO, COARSE_EXTERNAL = 0, 1, 2, 3
+COARSE_DEVICE_CHAIN = 4   # the device cyclic reduction in element-chain order (CG operators)
 # aggmg_hier_set_restriction modes (include/aggmg_hip.h)
 RESTRICT_EXPLICIT, RESTRICT_PRECONDITIONED = 0, 1
 RESTRICT_PRECONDITIONED_MAX_ELEMS = 1 << 21
@@ -160,6 +161,7 @@ SYMBOLS = {
     "aggmg_hier_coarse_info": (c_int, [_P, _P, POINTER(c_int), POINTER(c_int), POINTER(c_double)]),
     "aggmg_hier_coarse_probe": (c_int, [_P, _P, POINTER(c_double)]),
     "aggmg_hier_coarse_tail": (c_int, [_P, _P, POINTER(c_int), POINTER(c_int64)]),
+    "aggmg_hier_coarse_chain": (c_int, [_P, _P, POINTER(c_int), POINTER(c_int), POINTER(c_int64)]),
     "aggmg_hier_last_coarse_ms": (c_int, [_P, _P, POINTER(c_double)]),
     "aggmg_copy_segments_dev": (c_int, [_P, c_int, POINTER(_P), POINTER(_P), POINTER(c_int64), POINTER(c_int64),
                                         POINTER(c_int64), POINTER(c_int64)]),

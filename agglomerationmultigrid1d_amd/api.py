@@ -1197,9 +1197,11 @@ class MeshHierarchy:
         return r.value, s_.value, n.value
 
     def coarse_info(self):
-        """-> dict(on_device, block_size, cond_est, probe_backward_error, tail, tail_blocks) of the coarsest direct solver;
-        probe_backward_error: ||d - A x|| / ||d|| of the probe solve that aggmg_hier_create accepts (< 1e-10) or rejects the
-        device factorisation on (-1: none attempted)"""
+        """-> dict(on_device, block_size, cond_est, probe_backward_error, tail, tail_blocks, order) of the coarsest direct
+        solver; probe_backward_error: ||d - A x|| / ||d|| of the probe solve that aggmg_hier_create accepts (< 1e-10) or
+        rejects the device factorisation on (-1: none attempted); order: "operator" -- the blocks are the operator's own
+        rows -- or "element chain" (COARSE_DEVICE_CHAIN; COARSE_AUTO where the host solver refuses the band): block_size
+        is then the degree p of the CG operator"""
         a, b, c = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0.0)
         self.ctx.check(self.ctx.lib.aggmg_hier_coarse_info(self.ctx.handle, self.handle, ctypes.byref(a),
                                                            ctypes.byref(b), ctypes.byref(c)))
@@ -1207,8 +1209,12 @@ class MeshHierarchy:
         self.ctx.check(self.ctx.lib.aggmg_hier_coarse_probe(self.ctx.handle, self.handle, ctypes.byref(e)))
         k, nb = ctypes.c_int(0), ctypes.c_int64(0)
         self.ctx.check(self.ctx.lib.aggmg_hier_coarse_tail(self.ctx.handle, self.handle, ctypes.byref(k), ctypes.byref(nb)))
+        on, cm, cb = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+        self.ctx.check(self.ctx.lib.aggmg_hier_coarse_chain(self.ctx.handle, self.handle, ctypes.byref(on), ctypes.byref(cm),
+                                                            ctypes.byref(cb)))
         return dict(on_device=bool(a.value), block_size=b.value, cond_est=c.value, probe_backward_error=e.value,
-                    tail=("none", "cyclic reduction", "parallel cyclic reduction")[k.value], tail_blocks=nb.value)
+                    tail=("none", "cyclic reduction", "parallel cyclic reduction")[k.value], tail_blocks=nb.value,
+                    order="element chain" if on.value else "operator")
 
     def last_coarse_ms(self):
         ms = ctypes.c_double(0.0)
@@ -1374,21 +1380,33 @@ class DirectSolver:
     """`A \\ b` for a device operator -- the fine-level direct solve behind the reference's `err` histories
     (`u_exact = H.mStiffness[1] \\ b`, src/solvers.jl:120; `uExact = A \\ b`, :194).  A one-level hierarchy of the operator
     IS the direct solve (src/solvers.jl:39): block cyclic reduction on the device when A is block-tridiagonal with
-    well-conditioned pivot blocks (every DG / agglomerated operator; accepted on a probe solve, include/aggmg_hip.h),
-    the library's host banded LU otherwise; operators neither can take (CG operators in the vertices-first numbering:
-    no band) are solved with SciPy's sparse LU on the host and the solution is uploaded -- once per call, not per cycle.
-    `where` says which: 'device', 'host banded LU', 'host sparse LU'."""
+    well-conditioned pivot blocks (every DG / agglomerated operator; accepted on a probe solve, include/aggmg_hip.h);
+    the same reduction in element-chain order when A is a CG operator of degree <= 8 (its vertices-first numbering has
+    no band; in the order [left vertex, interior nodes] of every element it is block-tridiagonal with p x p blocks:
+    COARSE_DEVICE_CHAIN, the chain form left by a chain smoother on the operator or detected in its pattern); the
+    library's host banded LU otherwise; operators none of them takes are solved with SciPy's sparse LU on the host and
+    the solution is uploaded -- once per call, not per cycle.
+    `where` says which, tried in this order: 'device', 'device (element chain)', 'host banded LU', 'host sparse LU'."""
 
     def __init__(self, op, host_matrix=None):
         self.op, self.ctx = op, op.ctx
         self._host = host_matrix
         self.H = None
         self._lu = None
-        try:
-            self.H = MeshHierarchy(None, [op], [], [], ctx=self.ctx, coarse_mode=_lib.COARSE_AUTO)
-            self.where = "device" if self.H.coarse_info()["on_device"] else "host banded LU"
-        except _lib.UnsupportedError:
+        # (each form once: the two device orders, then the host banded LU by name -- COARSE_AUTO would try both device
+        # orders again before it gets there; on a CG operator the host factorisation is O(N^3))
+        for mode in (_lib.COARSE_DEVICE_CR, _lib.COARSE_DEVICE_CHAIN, _lib.COARSE_HOST_BANDED):
+            try:
+                self.H = MeshHierarchy(None, [op], [], [], ctx=self.ctx, coarse_mode=mode)
+                break
+            except _lib.UnsupportedError:
+                pass
+        if self.H is None:
             self.where = "host sparse LU"
+        else:
+            info = self.H.coarse_info()
+            self.where = ("host banded LU" if not info["on_device"] else
+                          "device (element chain)" if info["order"] == "element chain" else "device")
 
     def solve_dev(self, b):
         """b: DeviceVector -> DeviceVector, or DeviceMatrix (N, K) -> DeviceMatrix (EXTENSION; Julia's `A \\ B` takes

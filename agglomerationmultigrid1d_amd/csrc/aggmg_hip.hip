@@ -1161,6 +1161,8 @@ extern "C" int aggmg_smoother_apply(aggmg_ctx* ctx, aggmg_smoother* sm, const do
 // ---------------------------------------------------------------------------------------------
 // coarsest-level direct solve (host, banded LU with partial pivoting = dgbtf2 / dgbtrs order)
 // ---------------------------------------------------------------------------------------------
+static bool banded_fits(int64_t kl, int64_t ku, int64_t n);   // the band storage stays below the solver's bound
+
 static int banded_factor(aggmg_ctx* ctx, const HostCsr& h, int64_t n, BandedLU* f) {
   int kl = 0, ku = 0;
   for (int64_t i = 0; i < n; ++i)
@@ -1170,7 +1172,7 @@ static int banded_factor(aggmg_ctx* ctx, const HostCsr& h, int64_t n, BandedLU* 
       ku = std::max<int64_t>(ku, j - i);
     }
   const int64_t ldab = 2 * (int64_t)kl + ku + 1;
-  if ((double)ldab * (double)n * 8.0 > 8e9)
+  if (!banded_fits(kl, ku, n))
     return fail(ctx, AGGMG_ERR_UNSUPPORTED,
                 "coarsest operator bandwidth too large for the host banded solver (kl=" + std::to_string(kl) +
                     ", ku=" + std::to_string(ku) + ", n=" + std::to_string(n) + ")");
@@ -1456,8 +1458,7 @@ static int cr_phase(aggmg_ctx* ctx, CrDev& cr, int phase, const double* d_owned,
   return fail(ctx, AGGMG_ERR_UNSUPPORTED, "cyclic reduction block size not instantiated");
 }
 
-static int cr_solve(aggmg_ctx* ctx, CrDev& cr, const double* rhs, double* out, int level) {
-  ProfScope ps(ctx, AGGMG_KIND_COARSE, level);
+static int cr_solve_blocks(aggmg_ctx* ctx, CrDev& cr, const double* rhs, double* out) {
   switch (cr.m) {
     case 1: return cr_solve_t<1>(ctx, cr, rhs, out);
     case 2: return cr_solve_t<2>(ctx, cr, rhs, out);
@@ -1469,6 +1470,22 @@ static int cr_solve(aggmg_ctx* ctx, CrDev& cr, const double* rhs, double* out, i
     case 8: return cr_solve_t<8>(ctx, cr, rhs, out);
   }
   return fail(ctx, AGGMG_ERR_UNSUPPORTED, "cyclic reduction block size not instantiated");
+}
+
+// rhs / out in the operator's numbering.  Element-chain order (cr.chain): one gather launch into the block-ordered d0
+// (padding rows 0), the reduction's launches, one scatter launch out of x0 -- rhs and out may be the same vector
+static int cr_solve(aggmg_ctx* ctx, CrDev& cr, const double* rhs, double* out, int level) {
+  ProfScope ps(ctx, AGGMG_KIND_COARSE, level);
+  if (!cr.chain) return cr_solve_blocks(ctx, cr, rhs, out);
+  const CgtDev& g = *cr.chain;
+  const int64_t Np = g.ne * g.m;
+  hipLaunchKernelGGL(cr_chain_gather_kernel<kCrThreads>, dim3((unsigned)((Np + kCrThreads - 1) / kCrThreads)), dim3(kCrThreads), 0,
+                     ctx->stream, rhs, (int64_t)0, (const int32_t*)g.perm, cr.d0.get(), (int64_t)0, Np);
+  CHECK(cr_solve_blocks(ctx, cr, cr.d0, cr.x0));
+  hipLaunchKernelGGL(cr_chain_scatter_kernel<kCrThreads>, dim3((unsigned)((g.N + kCrThreads - 1) / kCrThreads)), dim3(kCrThreads), 0,
+                     ctx->stream, (const double*)cr.x0, (int64_t)0, (const int32_t*)g.inv, out, (int64_t)0, g.N);
+  HIPCHK(hipGetLastError());
+  return AGGMG_OK;
 }
 
 
@@ -1533,7 +1550,8 @@ static int cr_solve_multi_t(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int6
   // without padding the caller's columns are used in place, as cr_solve_t does -- where every column starts on the 16 bytes
   // the kernels' paired loads and stores assume of a vector
   const bool aligned = (((uintptr_t)B | (uintptr_t)X) & 15) == 0 && ldb % 2 == 0 && ldx % 2 == 0;
-  const bool direct = Npad == cr.N && aligned && !(B < X + ((kc - 1) * ldx + cr.N) && X < B + ((kc - 1) * ldb + cr.N));
+  // (element-chain order: the staging vectors are the block-ordered columns, filled and emptied by the gather / scatter)
+  const bool direct = !cr.chain && Npad == cr.N && aligned && !(B < X + ((kc - 1) * ldx + cr.N) && X < B + ((kc - 1) * ldb + cr.N));
   CHECK(cr_multi_workspace(ctx, h, kc, !direct));
   std::vector<CrMultiStage> ws;
   CrMultiStage wt;
@@ -1545,8 +1563,12 @@ static int cr_solve_multi_t(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int6
     const int64_t sp = cr_even(Npad);
     double* d0 = h->crw_stage;
     x = h->crw_stage + h->crw_stage_cols * sp;
-    hipLaunchKernelGGL(cr_cols_copy_kernel<kCrThreads>, dim3((unsigned)((cr.N + kCrThreads - 1) / kCrThreads), kc), dim3(kCrThreads), 0,
-                       ctx->stream, B, ldb, d0, sp, cr.N);
+    if (cr.chain)
+      hipLaunchKernelGGL(cr_chain_gather_kernel<kCrThreads>, dim3((unsigned)((Npad + kCrThreads - 1) / kCrThreads), kc), dim3(kCrThreads), 0,
+                         ctx->stream, B, ldb, (const int32_t*)cr.chain->perm, d0, sp, Npad);
+    else
+      hipLaunchKernelGGL(cr_cols_copy_kernel<kCrThreads>, dim3((unsigned)((cr.N + kCrThreads - 1) / kCrThreads), kc), dim3(kCrThreads), 0,
+                         ctx->stream, B, ldb, d0, sp, cr.N);
     d = d0;
     cs_in = cs_out = sp;
   }
@@ -1602,7 +1624,10 @@ static int cr_solve_multi_t(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int6
                          (size_t)cr.st[s].lds_total * sizeof(double), ctx->stream, A, ds, dsb, (const double*)xq(s), xs);
     }
   }
-  if (!direct)
+  if (cr.chain)
+    hipLaunchKernelGGL(cr_chain_scatter_kernel<kCrThreads>, dim3((unsigned)((cr.chain->N + kCrThreads - 1) / kCrThreads), kc),
+                       dim3(kCrThreads), 0, ctx->stream, (const double*)x, cs_out, (const int32_t*)cr.chain->inv, X, ldx, cr.chain->N);
+  else if (!direct)
     hipLaunchKernelGGL(cr_cols_copy_kernel<kCrThreads>, dim3((unsigned)((cr.N + kCrThreads - 1) / kCrThreads), kc), dim3(kCrThreads), 0,
                        ctx->stream, (const double*)x, cs_out, X, ldx, cr.N);
   HIPCHK(hipGetLastError());
@@ -1619,6 +1644,146 @@ static int cr_solve_multi(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int64_
 #undef CASE
   }
   return fail(ctx, AGGMG_ERR_UNSUPPORTED, "cyclic reduction block size not instantiated");
+}
+
+// ---------------------------------------------------------------------------------------------
+// the coarsest factorisation, accepted on evidence
+// ---------------------------------------------------------------------------------------------
+static bool banded_fits(int64_t kl, int64_t ku, int64_t n) { return (double)(2 * kl + ku + 1) * (double)n * 8.0 <= 8e9; }
+
+// keeps or discards h->cr (and its parallel tail) on probe solves; the backward error goes to h->cr_probe_backward_error
+static int coarse_accept(aggmg_ctx* ctx, aggmg_hier* h) {
+  const int nlv = (int)h->lv.size();
+  aggmg_op* Ac = h->lv[nlv - 1].A;
+  const bool chain = (bool)h->cr.chain;
+  static const bool probe = [] {
+    const char* e = std::getenv("AGGMG_CR_PROBE");   // =0: debugging aid, accept the factorisation unchecked
+    return !(e && e[0] == '0');
+  }();
+  if (h->cr.valid && probe) {
+    // The cyclic reduction pivots inside the m x m blocks only (the reference's UMFPACK pivots across the whole
+    // matrix, src/solvers.jl:39): accept the factorisation on evidence, not on the per-block condition monitor
+    // alone -- solve one probe system and keep it only if the backward error is at round-off level.
+    Level& lc = h->lv[nlv - 1];
+    const int64_t Nc = lc.N;
+    const double tol = 1e-10;
+    // the operator's products.  Operator order: the deterministic gather of the uploaded CSC arrays, which relies on the
+    // block-tridiagonal pattern the set-up has established.  Chain order: the row-gather CSR in the OPERATOR's numbering --
+    // not the chain arrays the blocks were packed from, where a packing or permutation mistake would cancel
+    auto product = [&](const double* w, double* d) -> int {
+      if (chain) return launch_csr<kSpmvSet>(ctx, Ac->csr, w, nullptr, nullptr, 0.0, d);
+      HIPCHK(hipMemsetAsync(d, 0, (size_t)Nc * sizeof(double), ctx->stream));
+      return setup_band_matvec_add(ctx, Ac, h->cr.m, w, 1.0, d);
+    };
+    auto residual = [&](const double* x, const double* d, double* r) -> int {
+      if (chain) return launch_csr<kResidual>(ctx, Ac->csr, x, d, nullptr, 0.0, r);
+      HIPCHK(hipMemcpyAsync(r, d, (size_t)Nc * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+      return setup_band_matvec_add(ctx, Ac, h->cr.m, x, -1.0, r);
+    };
+    auto probe_once = [&]() -> int {
+      double nd = 0.0, nr = 0.0;
+      CHECK(setup_probe_vector(ctx, Nc, lc.u[1]));
+      CHECK(product(lc.u[1], lc.rhs));                                          // d = A w (deterministic gather)
+      CHECK(cr_solve(ctx, h->cr, lc.rhs, lc.u[0], nlv - 1));                // x = CR(d)
+      CHECK(residual(lc.u[0], lc.rhs, lc.tmp));                                 // r = d - A x
+      CHECK(aggmg_norm2_dev(ctx, lc.rhs, Nc, &nd));
+      CHECK(aggmg_norm2_dev(ctx, lc.tmp, Nc, &nr));
+      h->cr_probe_backward_error = nd > 0.0 ? nr / nd : 0.0;
+      for (double* p : {lc.u[0].get(), lc.u[1].get(), lc.rhs.get(), lc.tmp.get()}) HIPCHK(hipMemsetAsync(p, 0, (size_t)lc.Nalloc * sizeof(double), ctx->stream));
+      return AGGMG_OK;
+    };
+    CHECK(probe_once());
+    if (!(h->cr_probe_backward_error < tol) && h->cr.pcr.valid) {  // the tail once more in its register-blocked form
+      h->cr.pcr.valid = false;
+      CHECK(probe_once());
+    }
+    if (!(h->cr_probe_backward_error < tol)) cr_discard(&h->cr);              // NaN included
+    static const bool pcr_guard = [] {
+      const char* e = std::getenv("AGGMG_CR_PCR_GUARD");   // =0: testing aid, keep the parallel tail unexamined
+      return !(e && e[0] == '0');
+    }();
+    if (h->cr.valid && h->cr.pcr.valid && pcr_guard) {
+      // The parallel cyclic reduction of the tail accumulates like an inverse; on an ill-conditioned tail system (a
+      // small coarsest operator taken as a whole: Neumann end, Dirichlet penalty) its residual for a right-hand side
+      // with a large smooth solution was measured at 5000 x the register-blocked form's (1.8e-8 against 3.4e-12 of
+      // ||d||, tests/exp_pcr_accuracy.py), on the boundary systems of the benchmarked hierarchies at 1 - 4 x.  So it
+      // is kept on evidence as well: both forms solve one such system, and the parallel one stays only where its
+      // residual is within 8 x of the other's.
+      auto smooth_residual = [&](double* res) -> int {
+        double nd = 0.0, nr = 0.0;
+        CHECK(setup_smooth_vector(ctx, Nc, lc.rhs));
+        CHECK(cr_solve(ctx, h->cr, lc.rhs, lc.u[0], nlv - 1));
+        CHECK(residual(lc.u[0], lc.rhs, lc.tmp));
+        CHECK(aggmg_norm2_dev(ctx, lc.rhs, Nc, &nd));
+        CHECK(aggmg_norm2_dev(ctx, lc.tmp, Nc, &nr));
+        *res = nd > 0.0 ? nr / nd : 0.0;
+        return AGGMG_OK;
+      };
+      double rp = 0.0, rc = 0.0;
+      CHECK(smooth_residual(&rp));
+      h->cr.pcr.valid = false;
+      CHECK(smooth_residual(&rc));
+      h->cr.pcr.valid = rp <= 8.0 * rc + 1e-15;   // (NaN: false)
+      for (double* p : {lc.u[0].get(), lc.u[1].get(), lc.rhs.get(), lc.tmp.get()}) HIPCHK(hipMemsetAsync(p, 0, (size_t)lc.Nalloc * sizeof(double), ctx->stream));
+    }
+  }
+  return AGGMG_OK;
+}
+
+// The coarsest operator in element-chain order (AGGMG_COARSE_DEVICE_CHAIN; AGGMG_COARSE_AUTO where the band is too wide
+// for the host solver): the chain form a smoother left on the operator, or -- AGGMG_OPT_DETECT_CHAIN -- the one found from
+// its pattern; the same cyclic reduction on its blocks; the same probe.  Leaves h->cr invalid and says *why otherwise.
+static int coarse_factor_chain(aggmg_ctx* ctx, aggmg_hier* h, std::string* why) {
+  aggmg_op* Ac = h->lv.back().A;
+  cr_discard(&h->cr);
+  std::shared_ptr<CgtDev> g = Ac->cgt;
+  if (!g && ctx->detect_chain) {   // a throw-away point-Jacobi smoother: the detection wants one; the operator stays as it was
+    aggmg_smoother probe_sm;
+    probe_sm.A = Ac;
+    probe_sm.N = Ac->m;
+    const int st = cgt_detect(ctx, &probe_sm);
+    Ac->cgt = nullptr;
+    CHECK(st);
+    g = probe_sm.cgt;
+  }
+  if (!g) {
+    // the wording only: does the operator have the size and the entry count of a CG chain of a degree above 8 (the bounds
+    // of cgt_detect)?  No chain form is built for those
+    int64_t big = 0;
+    for (int64_t p = 9; p <= 64 && !big && Ac->m == Ac->n; ++p) {
+      if ((Ac->m - 1) % p || Ac->m < 3) continue;
+      const double full = (double)((Ac->m - 1) / p) * (double)((p + 1) * (p + 1));
+      if ((double)Ac->nnz <= full && (double)Ac->nnz >= 0.5 * full) big = p;
+    }
+    *why = std::string("the coarsest operator has no element-chain form (no chain smoother was built on it") +
+           (ctx->detect_chain ? ", none detected in its pattern)" : ", AGGMG_OPT_DETECT_CHAIN is off)");
+    if (big)
+      *why += "; its size and entry count would fit a chain with blocks of m = " + std::to_string(big) +
+              " rows, and m > 8 is not covered";
+    return AGGMG_OK;
+  }
+  if (g->m < 1 || g->m > 8) {   // (no CgtDev of today has such blocks)
+    *why = "the element chain has blocks of m = " + std::to_string(g->m) + " rows; m > 8 is not covered";
+    return AGGMG_OK;
+  }
+  CHECK(setup_cr_chain(ctx, *g, &h->cr));
+  if (!h->cr.valid) {
+    *why = "a pivot block of the chain-ordered operator is singular or close to it";
+    return AGGMG_OK;
+  }
+  h->cr.chain = g;
+  const bool had_csr = (bool)Ac->csr.rowptr;
+  CHECK(op_ensure_csr(ctx, Ac));
+  const int st = coarse_accept(ctx, h);
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (!had_csr) Ac->csr = CsrDev();   // built for the probe alone: the operator holds what it held before
+  CHECK(st);
+  if (!h->cr.valid) {
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "%.3e", h->cr_probe_backward_error);
+    *why = std::string("the probe solve refused the factorisation (backward error ") + buf + ", bound 1e-10)";
+  }
+  return AGGMG_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1641,7 +1806,7 @@ extern "C" int aggmg_hier_create(aggmg_ctx* ctx, int nlevels, aggmg_op* const* s
   if (nlevels > 1 && (!smoothers || !interpolation))
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_create: smoothers / interpolation missing");
   if (coarse_mode != AGGMG_COARSE_HOST_BANDED && coarse_mode != AGGMG_COARSE_DEVICE_CR &&
-      coarse_mode != AGGMG_COARSE_AUTO && coarse_mode != AGGMG_COARSE_EXTERNAL)
+      coarse_mode != AGGMG_COARSE_AUTO && coarse_mode != AGGMG_COARSE_EXTERNAL && coarse_mode != AGGMG_COARSE_DEVICE_CHAIN)
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_create: unknown coarse_mode");
   HIPCHK(hipSetDevice(ctx->device));
   std::unique_ptr<aggmg_hier> h(new aggmg_hier());
@@ -1704,82 +1869,36 @@ extern "C" int aggmg_hier_create(aggmg_ctx* ctx, int nlevels, aggmg_op* const* s
   for (int k = 0; k + 2 < nlevels; ++k)
     if (h->lv[k].cgt_fused && h->lv[k].tc->type == kTrChain && h->lv[k + 1].cgt_fused) h->lv[k + 1].native_io = true;
   // coarsest level: factor once (unless the caller solves it elsewhere)
-  if (coarse_mode != AGGMG_COARSE_EXTERNAL) {
+  if (coarse_mode == AGGMG_COARSE_DEVICE_CHAIN) {
+    std::string why;
+    CHECK(coarse_factor_chain(ctx, h.get(), &why));
+    if (!h->cr.valid) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_hier_create: AGGMG_COARSE_DEVICE_CHAIN: " + why);
+  } else if (coarse_mode != AGGMG_COARSE_EXTERNAL) {
     aggmg_op* Ac = h->lv[nlevels - 1].A;
+    std::string chain_why;   // AUTO: why the chain order was tried and refused
     if (coarse_mode != AGGMG_COARSE_HOST_BANDED) {
-      int hint = 0;
+      int hint = 0, band[2] = {0, 0};
       if (nlevels >= 2 && h->lv[nlevels - 2].tb) hint = h->lv[nlevels - 2].tb->mc;
-      CHECK(setup_cr(ctx, Ac, hint, &h->cr));
-      static const bool probe = [] {
-        const char* e = std::getenv("AGGMG_CR_PROBE");   // =0: debugging aid, accept the factorisation unchecked
-        return !(e && e[0] == '0');
-      }();
-      if (h->cr.valid && probe) {
-        // The cyclic reduction pivots inside the m x m blocks only (the reference's UMFPACK pivots across the whole
-        // matrix, src/solvers.jl:39): accept the factorisation on evidence, not on the per-block condition monitor
-        // alone -- solve one probe system and keep it only if the backward error is at round-off level.
-        Level& lc = h->lv[nlevels - 1];
-        const int64_t Nc = lc.N;
-        const double tol = 1e-10;
-        auto probe_once = [&]() -> int {
-          double nd = 0.0, nr = 0.0;
-          CHECK(setup_probe_vector(ctx, Nc, lc.u[1]));
-          HIPCHK(hipMemsetAsync(lc.rhs, 0, (size_t)Nc * sizeof(double), ctx->stream));
-          CHECK(setup_band_matvec_add(ctx, Ac, h->cr.m, lc.u[1], 1.0, lc.rhs));     // d = A w (deterministic gather)
-          CHECK(cr_solve(ctx, h->cr, lc.rhs, lc.u[0], nlevels - 1));                // x = CR(d)
-          HIPCHK(hipMemcpyAsync(lc.tmp, lc.rhs, (size_t)Nc * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-          CHECK(setup_band_matvec_add(ctx, Ac, h->cr.m, lc.u[0], -1.0, lc.tmp));    // r = d - A x
-          CHECK(aggmg_norm2_dev(ctx, lc.rhs, Nc, &nd));
-          CHECK(aggmg_norm2_dev(ctx, lc.tmp, Nc, &nr));
-          h->cr_probe_backward_error = nd > 0.0 ? nr / nd : 0.0;
-          for (double* p : {lc.u[0].get(), lc.u[1].get(), lc.rhs.get(), lc.tmp.get()}) HIPCHK(hipMemsetAsync(p, 0, (size_t)lc.Nalloc * sizeof(double), ctx->stream));
-          return AGGMG_OK;
-        };
-        CHECK(probe_once());
-        if (!(h->cr_probe_backward_error < tol) && h->cr.pcr.valid) {  // the tail once more in its register-blocked form
-          h->cr.pcr.valid = false;
-          CHECK(probe_once());
-        }
-        if (!(h->cr_probe_backward_error < tol)) cr_discard(&h->cr);              // NaN included
-        static const bool pcr_guard = [] {
-          const char* e = std::getenv("AGGMG_CR_PCR_GUARD");   // =0: testing aid, keep the parallel tail unexamined
-          return !(e && e[0] == '0');
-        }();
-        if (h->cr.valid && h->cr.pcr.valid && pcr_guard) {
-          // The parallel cyclic reduction of the tail accumulates like an inverse; on an ill-conditioned tail system (a
-          // small coarsest operator taken as a whole: Neumann end, Dirichlet penalty) its residual for a right-hand side
-          // with a large smooth solution was measured at 5000 x the register-blocked form's (1.8e-8 against 3.4e-12 of
-          // ||d||, tests/exp_pcr_accuracy.py), on the boundary systems of the benchmarked hierarchies at 1 - 4 x.  So it
-          // is kept on evidence as well: both forms solve one such system, and the parallel one stays only where its
-          // residual is within 8 x of the other's.
-          auto smooth_residual = [&](double* res) -> int {
-            double nd = 0.0, nr = 0.0;
-            CHECK(setup_smooth_vector(ctx, Nc, lc.rhs));
-            CHECK(cr_solve(ctx, h->cr, lc.rhs, lc.u[0], nlevels - 1));
-            HIPCHK(hipMemcpyAsync(lc.tmp, lc.rhs, (size_t)Nc * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-            CHECK(setup_band_matvec_add(ctx, Ac, h->cr.m, lc.u[0], -1.0, lc.tmp));
-            CHECK(aggmg_norm2_dev(ctx, lc.rhs, Nc, &nd));
-            CHECK(aggmg_norm2_dev(ctx, lc.tmp, Nc, &nr));
-            *res = nd > 0.0 ? nr / nd : 0.0;
-            return AGGMG_OK;
-          };
-          double rp = 0.0, rc = 0.0;
-          CHECK(smooth_residual(&rp));
-          h->cr.pcr.valid = false;
-          CHECK(smooth_residual(&rc));
-          h->cr.pcr.valid = rp <= 8.0 * rc + 1e-15;   // (NaN: false)
-          for (double* p : {lc.u[0].get(), lc.u[1].get(), lc.rhs.get(), lc.tmp.get()}) HIPCHK(hipMemsetAsync(p, 0, (size_t)lc.Nalloc * sizeof(double), ctx->stream));
-        }
-      }
+      CHECK(setup_cr(ctx, Ac, hint, &h->cr, band));
+      CHECK(coarse_accept(ctx, h.get()));
       if (!h->cr.valid && coarse_mode == AGGMG_COARSE_DEVICE_CR)
         return fail(ctx, AGGMG_ERR_UNSUPPORTED,
                     "aggmg_hier_create: coarsest operator is not block-tridiagonal with well-conditioned pivot "
                     "blocks; device cyclic reduction not applicable");
+      // AUTO, and only where the host banded LU below would refuse the operator for its band (a CG operator in the
+      // reference's vertices-first numbering): the element-chain order first.  Every other operator keeps its route.
+      if (!h->cr.valid && Ac->m > 0 && !banded_fits(band[0], band[1], Ac->m)) {
+        const double probe_before = h->cr_probe_backward_error;
+        CHECK(coarse_factor_chain(ctx, h.get(), &chain_why));
+        if (!h->cr.valid) h->cr_probe_backward_error = probe_before;
+      }
     }
     if (!h->cr.valid) {  // host banded LU with partial pivoting: the one set-up path that reads the operator back
       HostCsr hc;
       CHECK(op_host_csr(ctx, Ac, &hc));
-      CHECK(banded_factor(ctx, hc, Ac->m, &h->coarse));
+      const int st = banded_factor(ctx, hc, Ac->m, &h->coarse);
+      if (st != AGGMG_OK && !chain_why.empty()) ctx->err += "; the element-chain order was not taken: " + chain_why;
+      CHECK(st);
       h->h_coarse.assign(Ac->m, 0.0);
     }
   }
@@ -2970,6 +3089,15 @@ extern "C" int aggmg_hier_coarse_info(aggmg_ctx* ctx, const aggmg_hier* h, int* 
   return AGGMG_OK;
 }
 
+extern "C" int aggmg_hier_coarse_chain(aggmg_ctx* ctx, const aggmg_hier* h, int* on, int* m, int64_t* blocks) {
+  if (!ctx || !h) return AGGMG_ERR_ARGUMENT;
+  const bool c = h->cr.valid && h->cr.chain;
+  if (on) *on = c ? 1 : 0;
+  if (m) *m = c ? h->cr.m : 0;
+  if (blocks) *blocks = c ? h->cr.n0 : 0;
+  return AGGMG_OK;
+}
+
 extern "C" int aggmg_hier_coarse_tail(aggmg_ctx* ctx, const aggmg_hier* h, int* kind, int64_t* blocks) {
   if (!ctx || !h) return AGGMG_ERR_ARGUMENT;
   if (kind) *kind = !h->cr.valid ? 0 : h->cr.pcr.valid ? 2 : 1;
@@ -2982,7 +3110,7 @@ extern "C" int aggmg_coarse_plan(aggmg_ctx* ctx, const aggmg_hier* h, int* chunk
                                  int* block_size, int64_t* n_blocks) {
   if (!ctx || !h) return AGGMG_ERR_ARGUMENT;
   const CrDev& cr = h->cr;
-  const bool ok = cr.valid && !cr.st.empty() && cr.n0 * cr.m == cr.N;
+  const bool ok = cr.valid && !cr.st.empty() && cr.n0 * cr.m == cr.N && !cr.chain;   // (chain order: the blocks are not ranges of the operator's rows)
   if (chunk_log2) *chunk_log2 = ok ? cr.st[0].q : -1;
   if (n_boundary) *n_boundary = ok ? cr.st[0].n_out : 0;
   if (block_size) *block_size = cr.valid ? cr.m : 0;
@@ -2994,7 +3122,7 @@ static int coarse_phase_check(aggmg_ctx* ctx, aggmg_hier* h, int64_t blk_lo, int
   if (!ctx) return AGGMG_ERR_ARGUMENT;
   if (!h) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_coarse_*: NULL hierarchy");
   const CrDev& cr = h->cr;
-  if (!(cr.valid && !cr.st.empty() && cr.n0 * cr.m == cr.N))
+  if (!(cr.valid && !cr.st.empty() && cr.n0 * cr.m == cr.N && !cr.chain))
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_coarse_*: this hierarchy has no chunked cyclic-reduction plan");
   const int64_t mask = ((int64_t)1 << cr.st[0].q) - 1;
   if (blk_lo < 0 || blk_hi > cr.n0 || blk_lo > blk_hi || (blk_lo & mask) || ((blk_hi & mask) && blk_hi != cr.n0))

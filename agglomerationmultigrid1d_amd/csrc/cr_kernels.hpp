@@ -1111,4 +1111,25 @@ __global__ __launch_bounds__(NT) void cr_cols_copy_kernel(const double* __restri
   if (i < n) dst[(int64_t)blockIdx.y * ld_dst + i] = src[(int64_t)blockIdx.y * ld_src + i];
 }
 
+// element-chain order (CrDev::chain): the same grid, the columns of the caller's matrix in the operator's numbering on one
+// side and the block-ordered staging vectors on the other.  perm[q] in [0, N) or -1 (a padding row: right-hand side 0),
+// inv[o] in [0, np): checked when the chain form was built (chain_perm_kernel, perm_cover_kernel).
+template <int NT>
+__global__ __launch_bounds__(NT) void cr_chain_gather_kernel(const double* __restrict__ src, int64_t ld_src,
+                                                             const int32_t* __restrict__ perm, double* __restrict__ dst,
+                                                             int64_t ld_dst, int64_t np) {
+  const int64_t q = (int64_t)blockIdx.x * NT + threadIdx.x;
+  if (q >= np) return;
+  const int32_t o = perm[q];
+  dst[(int64_t)blockIdx.y * ld_dst + q] = o >= 0 ? src[(int64_t)blockIdx.y * ld_src + o] : 0.0;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void cr_chain_scatter_kernel(const double* __restrict__ src, int64_t ld_src,
+                                                              const int32_t* __restrict__ inv, double* __restrict__ dst,
+                                                              int64_t ld_dst, int64_t n) {
+  const int64_t o = (int64_t)blockIdx.x * NT + threadIdx.x;
+  if (o < n) dst[(int64_t)blockIdx.y * ld_dst + o] = src[(int64_t)blockIdx.y * ld_src + inv[o]];
+}
+
 }  // namespace aggmg

@@ -315,7 +315,11 @@ struct CrDev {
   const int32_t* perm_last = nullptr;
   std::vector<CrStage> st;      // chunk stages ...
   CrStage tail;                 // ... then the remaining levels in one workgroup
-  DevArray<double> d0, x0;              // staging for padded systems (N not a multiple of m) / in-place calls
+  DevArray<double> d0, x0;              // staging for padded systems (N not a multiple of m) / in-place calls / chain order
+  // element-chain order (AGGMG_COARSE_DEVICE_CHAIN, setup_cr_chain): the blocks are those of this chain form, N = ne * m is
+  // the length of the BLOCK-ordered vectors, and a solve gathers its right-hand side through chain->perm into d0 and
+  // scatters x0 back through chain->inv; null: the blocks are the operator's own rows
+  std::shared_ptr<CgtDev> chain;
   DevArray<unsigned int> ticket;        // last-arriving-workgroup counter of the fused forward + tail launch
   double cond_est = 0.0;
   // the tail's system by parallel cyclic reduction (cr_pcr_tail_kernel; block sizes 1, 2, up to 1024 blocks -- above 512
@@ -468,7 +472,9 @@ int setup_transfer_btd(aggmg_ctx* ctx, const aggmg_op* L, const BtdDev* Abtd, in
 int setup_op_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, std::unique_ptr<DictDev>* out);
 // the same for a fused chain level: blocks of 1, 2 or 4 rows, point-Jacobi sweeps, chain or agglomerating transfer
 int setup_cgt_dictionary(aggmg_ctx* ctx, const CgtDev& g, const TransferCgt& t, std::unique_ptr<CgtDictDev>* out);
-int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr);
+// band_out (optional): max(i - j), max(j - i) over the stored entries -- what the host banded LU would have to store
+int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr, int* band_out = nullptr);
+int setup_cr_chain(aggmg_ctx* ctx, const CgtDev& g, CrDev* cr);   // the same factorisation of the chain-ordered blocks
 int cgt_detect(aggmg_ctx* ctx, aggmg_smoother* sm);   // chain form from the operator's own pattern (no element lists)
 // chunk-interleaved boundary rows of the element-partitioned coarsest solve (aggmg_hip.hip; used by dist.hip)
 int coarse_chunk_forward_interleaved(aggmg_ctx* ctx, aggmg_hier* h, const double* rhs_owned, int64_t blk_lo, int64_t blk_hi, double* Z);

@@ -834,10 +834,13 @@ int setup_band_matvec_add(aggmg_ctx* ctx, const aggmg_op* A, int m, const double
   return AGGMG_OK;
 }
 
+static int cr_factor_blocks(aggmg_ctx* ctx, CrDev* cr, DevArray<double> a, DevArray<double> b, DevArray<double> c);
+
 // Sets cr->valid when the operator is block-tridiagonal for some block size m <= 8 and every pivot block is
 // comfortably invertible; leaves it false otherwise (the caller then keeps the host banded solver).
-int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr) {
+int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr, int* band_out) {
   cr->valid = false;
+  if (band_out) band_out[0] = band_out[1] = 0;
   const int64_t N = Ac->m;
   if (N == 0) return AGGMG_OK;
   const int32_t* cp = Ac->csc.rowptr;
@@ -849,6 +852,7 @@ int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr) {
   int band[4];
   CHECK(f.read(ctx, band));
   const int kl = band[0], ku = band[1];
+  if (band_out) band_out[0] = kl, band_out[1] = ku;
   Flags bad;
   CHECK(bad.init(ctx, 1));
   auto fits = [&](int mm_, bool* out) -> int {
@@ -882,9 +886,45 @@ int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr) {
   CHECK(b.alloc(ctx, n * mm2, true));
   CHECK(c.alloc(ctx, n * mm2, true));
   LAUNCH(cr_pack_kernel, n * m, N, m, cp, rv, vv, a, b, c);
+  return cr_factor_blocks(ctx, cr, std::move(a), std::move(b), std::move(c));
+}
+
+// the element-chain entrance: the blocks come from the chain form of a CG operator (CgtDev, internal.hpp) -- block e =
+// [left vertex of element e, its interior nodes], one trailing identity-padded block for the last vertex -- instead of
+// from the CSC arrays in the operator's own numbering.  cr->N is the length of the block-ordered vectors; the solve
+// permutes in and out through g.perm / g.inv (cr_solve, aggmg_hip.hip).
+int setup_cr_chain(aggmg_ctx* ctx, const CgtDev& g, CrDev* cr) {
+  cr->valid = false;
+  const int m = g.m;
+  const int64_t n = g.ne;
+  if (m < 1 || m > 8 || n < 1) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "setup_cr_chain: blocks of 1 .. 8 rows only");   // (the caller checks)
+  cr->m = m;
+  cr->n0 = n;
+  cr->N = n * m;
+  DevArray<double> a, b, c;
+  CHECK(a.alloc(ctx, n * m * m, true));
+  CHECK(b.alloc(ctx, n * m * m, true));
+  CHECK(c.alloc(ctx, n * m * m, true));
+  LAUNCH(cr_pack_chain_kernel, n * m, n, m, (const double*)g.dblk, (const double*)g.subrow, (const double*)g.supcol,
+         (const int32_t*)g.perm, a.get(), b.get(), c.get());
+  CHECK(cr_factor_blocks(ctx, cr, std::move(a), std::move(b), std::move(c)));
+  if (cr->valid) {  // the block-ordered right-hand side and solution of a solve
+    CHECK(cr->d0.alloc(ctx, n * m, true));
+    CHECK(cr->x0.alloc(ctx, n * m, true));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  return AGGMG_OK;
+}
+
+// levels, plan, arena and parallel tail of the n0 blocks (a, b, c) [n0][m][m] of cr->m rows; sets cr->valid, or leaves
+// it false where a pivot block is close to singular or the plan does not fit
+static int cr_factor_blocks(aggmg_ctx* ctx, CrDev* cr, DevArray<double> a, DevArray<double> b, DevArray<double> c) {
+  const int m = cr->m;
+  const int64_t n = cr->n0, N = cr->N;
+  Flags bad;
+  CHECK(bad.init(ctx, 1));
   DevArray<double> condt;
   CHECK(condt.alloc(ctx, 1, true));
-  CHECK(bad.clear(ctx));
   int st = AGGMG_OK;
   switch (m) {
 #define CASE(MM) \

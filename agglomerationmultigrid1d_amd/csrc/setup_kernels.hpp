@@ -788,6 +788,30 @@ __global__ __launch_bounds__(kSetupThreads) void cr_pack_kernel(int64_t N, int m
   }
 }
 
+// the same blocks from the chain form of a CG operator (CgtDev, internal.hpp): row q = e * m + i of the block order has its
+// diagonal-block entries in dblk[q][0..m), couples to block e - 1 only from its first row (subrow[e][0..m): the first row
+// of a_e) and to block e + 1 only through that block's first column (supcol[q]: the first column of c_e).  a, b, c
+// zero-initialised; a padding row (perm < 0) is an identity row whatever dblk holds.  One thread per row.
+__global__ __launch_bounds__(kSetupThreads) void cr_pack_chain_kernel(int64_t ne, int m, const double* __restrict__ dblk,
+                                                                      const double* __restrict__ subrow,
+                                                                      const double* __restrict__ supcol,
+                                                                      const int32_t* __restrict__ perm,
+                                                                      double* __restrict__ a, double* __restrict__ b,
+                                                                      double* __restrict__ c) {
+  const int64_t q = (int64_t)blockIdx.x * kSetupThreads + threadIdx.x;
+  if (q >= ne * m) return;
+  const int64_t e = q / m;
+  const int i = (int)(q - e * m);
+  if (perm[q] < 0) {
+    b[q * m + i] = 1.0;
+    return;
+  }
+  for (int j = 0; j < m; ++j) b[q * m + j] = dblk[q * m + j];
+  if (i == 0 && e > 0)
+    for (int j = 0; j < m; ++j) a[q * m + j] = subrow[e * m + j];
+  if (e + 1 < ne) c[q * m] = supcol[q];
+}
+
 // parity-split storage of one level's off-diagonal blocks: fe[j] = (a_{2j}, c_{2j}) (turned into the forward multipliers
 // by cr_even_multipliers_kernel), fo[j] = (a_{2j+1}, c_{2j+1})
 __global__ __launch_bounds__(kSetupThreads) void cr_split_kernel(int64_t n, int mm2, const double* __restrict__ a,

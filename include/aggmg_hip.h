@@ -286,7 +286,25 @@ int aggmg_prolong_add_dev(aggmg_ctx* ctx, aggmg_op* L, const double* uc, double*
 #define AGGMG_COARSE_EXTERNAL 3    /* no factorisation: the caller solves the coarsest system between
                                       aggmg_vcycle_down_dev and aggmg_vcycle_up_dev (multi-GPU driver) */
 #define AGGMG_COARSE_AUTO 2        /* device cyclic reduction when the operator is block-tridiagonal
-                                      with well-conditioned pivot blocks, host banded LU otherwise */
+                                      with well-conditioned pivot blocks, host banded LU otherwise;
+                                      where the host banded LU would refuse the operator for its band
+                                      (2 kl + ku + 1 rows of band storage above 8e9 bytes: a CG operator of
+                                      degree >= 2 in the reference's vertices-first numbering from a few
+                                      ten thousand rows on) the element-chain order below is tried first.
+                                      Every operator either solver takes today keeps its solver and its bits */
+#define AGGMG_COARSE_DEVICE_CHAIN 4 /* the same device cyclic reduction in ELEMENT-CHAIN order: the coarsest
+                                      operator is a CG operator whose chain form -- blocks of m = p rows [left
+                                      vertex of element e, its interior nodes], block-tridiagonal in that order
+                                      -- a chain smoother left on it (aggmg_jacobi_setup_elements, the Schwarz /
+                                      Gauss-Seidel set-ups on a CG mesh) or, with AGGMG_OPT_DETECT_CHAIN on, its
+                                      pattern shows.  Every solve gathers the right-hand side into block
+                                      order, reduces, scatters back: on the context's stream, nothing crosses
+                                      PCIe.  Accepted on the same probe (backward error < 1e-10, the product
+                                      formed from the operator in ITS numbering, not from the packed blocks).
+                                      AGGMG_ERR_UNSUPPORTED with the reason: no chain form, m > 8, a
+                                      near-singular pivot block, probe refused.  The phase-by-phase
+                                      entry points of the partitioned cycle (aggmg_coarse_plan ...) do not
+                                      take such a hierarchy */
 /* Mirrors the operator vectors of `struct MeshHierarchy` src/mesh_heirarchy.jl:17-28:
  * stiffness[nlevels], smoothers[nlevels-1] (the coarsest level is solved directly,
  * src/solvers.jl:39), interpolation[nlevels-1] with interpolation[k]: level k+1 -> level k.
@@ -469,6 +487,11 @@ int aggmg_hier_coarse_info(aggmg_ctx* ctx, const aggmg_hier* h, int* on_device, 
  * pivoting (AGGMG_COARSE_DEVICE_CR: AGGMG_ERR_UNSUPPORTED).  backward_error receives the probe's figure
  * (-1 when no device factorisation was attempted). */
 int aggmg_hier_coarse_probe(aggmg_ctx* ctx, const aggmg_hier* h, double* backward_error);
+/* Is the device factorisation one of the element-chain order (AGGMG_COARSE_DEVICE_CHAIN, or AGGMG_COARSE_AUTO on an
+ * operator whose band the host solver refuses)?  *on = 1 / 0, *m = rows per block (the degree p), *blocks = elements + 1
+ * (the trailing identity-padded block holds the last vertex); 0 / 0 / 0 otherwise.  aggmg_hier_coarse_info, _probe and
+ * _tail report this factorisation like any other: on_device 1, block_size m. */
+int aggmg_hier_coarse_chain(aggmg_ctx* ctx, const aggmg_hier* h, int* on, int* m, int64_t* blocks);
 /* How the device solve ends: the boundary system its chunk stages leave (or the whole system when it is small) goes to
  * ONE workgroup -- *kind = 2: parallel cyclic reduction (block sizes 1 and 2, up to 1024 blocks -- above 512 with one
  * ordinary reduction level around it; kept only where

@@ -262,7 +262,12 @@ function dictionary_levels(Hd::DeviceHierarchy)
     return out
 end
 
-# coarse_mode 2 = AGGMG_COARSE_AUTO
+# coarse_mode 2 = AGGMG_COARSE_AUTO; COARSE_DEVICE_CHAIN: the coarsest level is a CG level, solved in element-chain order
+const COARSE_HOST_BANDED = 0
+const COARSE_DEVICE_CR = 1
+const COARSE_AUTO = 2
+const COARSE_EXTERNAL = 3
+const COARSE_DEVICE_CHAIN = 4
 function DeviceHierarchy(H::MeshHierarchy; ctx::Context = default_context(), coarse_mode::Integer = 2)
     n = length(H.mMeshes)
     ops = [DeviceOperator(ctx, H.mStiffness[k], 0) for k in 1:n]
@@ -549,8 +554,9 @@ end
 # `A \\ b` of a device operator -- the fine-level direct solve behind the reference's `err` histories
 # (u_exact = H.mStiffness[1] \\ b, src/solvers.jl:120; uExact = A \\ b, :194).  A one-level hierarchy of the operator IS
 # the direct solve (:39): block cyclic reduction on the device when the operator is block-tridiagonal (every DG /
-# agglomerated operator), the library's host banded LU otherwise (coarse_mode 2 = AGGMG_COARSE_AUTO).  Operators that
-# neither takes (status -5: CG operators in the vertices-first numbering have no band) are solved on the host with the
+# agglomerated operator; COARSE_DEVICE_CR), the same reduction in element-chain order for a CG operator
+# (COARSE_DEVICE_CHAIN: its vertices-first numbering has no band, its element chain has blocks of p rows), the library's
+# host banded LU otherwise (COARSE_HOST_BANDED).  Operators none of them takes (status -5) are solved on the host with the
 # reference's own `\\` and uploaded -- once per call, never per cycle.
 mutable struct DirectSolver
     ctx::Context
@@ -567,14 +573,27 @@ end
 function DirectSolver(op::DeviceOperator)
     r = Ref{Handle}(C_NULL)
     oph = Handle[op.h]
-    st = GC.@preserve oph ccall((:aggmg_hier_create, LIB), Cint,
-        (Handle, Cint, Ptr{Handle}, Ptr{Handle}, Ptr{Handle}, Cint, Ref{Handle}),
-        op.ctx.h, 1, oph, C_NULL, C_NULL, 2, r)
-    st == -5 || check(op.ctx.h, st)             # -5: neither block-tridiagonal nor banded -> host `\\`
+    st = Cint(-5)
+    for mode in (COARSE_DEVICE_CR, COARSE_DEVICE_CHAIN, COARSE_HOST_BANDED)   # each form once: device, device (element chain), host banded LU
+        st = GC.@preserve oph ccall((:aggmg_hier_create, LIB), Cint,
+            (Handle, Cint, Ptr{Handle}, Ptr{Handle}, Ptr{Handle}, Cint, Ref{Handle}),
+            op.ctx.h, 1, oph, C_NULL, C_NULL, mode, r)
+        st == -5 || break
+    end
+    st == -5 || check(op.ctx.h, st)             # -5 from all three: no device form and no band -> host `\\`
     ds = DirectSolver(op.ctx, op, st == 0 ? r[] : C_NULL)
     finalizer(free!, ds)
     return ds
 end
+# (on, m, blocks) of a hierarchy handle's coarsest factorisation: is it one of the element-chain order, rows per block,
+# blocks (elements + 1)
+function coarse_chain(ctx::Context, h::Handle)
+    on = Ref{Cint}(0); m = Ref{Cint}(0); nb = Ref{Int64}(0)
+    check(ctx.h, ccall((:aggmg_hier_coarse_chain, LIB), Cint, (Handle, Handle, Ref{Cint}, Ref{Cint}, Ref{Int64}),
+        ctx.h, h, on, m, nb))
+    return on[] != 0, Int(m[]), nb[]
+end
+coarse_chain(ds::DirectSolver) = ds.h == C_NULL ? (false, 0, Int64(0)) : coarse_chain(ds.ctx, ds.h)
 # u = A \\ b as a DeviceVector; A_host: the reference's SparseMatrixCSC of the same operator (host fallback only)
 function solve(ds::DirectSolver, A_host, b::DeviceVector)
     ds.h == C_NULL && return DeviceVector(ds.ctx, A_host \\ download(b))
