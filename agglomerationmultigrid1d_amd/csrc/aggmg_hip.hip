@@ -755,14 +755,6 @@ static void fused_dictionary(FusedArgs& a, const Level& l) {
   if (a.lf_in) (d->lf_unit ? a.lf1_in : a.lf_in) = d->lf;
   if (a.lf_out) (d->lf_unit ? a.lf1_out : a.lf_out) = d->lf;
 }
-// Which restriction modes a fused descent serves, caller by caller.  vcycle_down takes any: without (L'D) it restricts
-// with lf whatever the mode.  The launch between two cycles (aggmg_vcycles_dev) wants the mode's own form to exist;
-// the checkpointed one (aggmg_multigrid_dev) forms residual rows for its norms and takes the explicit form alone.
-static bool vcycles_restriction_ok(const aggmg_hier* h, const Level& l) {
-  return l.tb->ld || h->restriction == AGGMG_RESTRICT_EXPLICIT;
-}
-static bool multigrid_restriction_ok(const aggmg_hier* h) { return h->restriction == AGGMG_RESTRICT_EXPLICIT; }
-
 // Checkpoints of a launch (the checkpoint variants of the fused kernel and of the chain kernel): after `sweep`,
 // sweep + stride, ... sweeps, and (final) after the last one; ntiles comes back from the launch.
 static void fused_chk(FusedArgs& a, const CgtChk& c) {
@@ -802,8 +794,9 @@ static bool btd_launch_ok(const aggmg_smoother& sm, int nsweeps, int residual, c
 }
 
 // structured: nsweeps sweeps from u_in (may be nullptr = zero) into u_out (!= u_in)
+// chk: the launch -- it has to be a single one -- forms these checkpoints (one more element of halo for their residual rows)
 static int btd_smooth(aggmg_ctx* ctx, const BtdDev& b, const double* u_in, const double* rhs, Damping alpha,
-                      int nsweeps, double* u_out, int level, int64_t N, int gs = 0) {
+                      int nsweeps, double* u_out, int level, int64_t N, int gs = 0, CgtChk* chk = nullptr) {
   const int smax = std::max(1, btd_max_sweeps(b, 0) / (gs ? 2 : 1));
   const double* src = u_in;
   int left = nsweeps;
@@ -816,6 +809,7 @@ static int btd_smooth(aggmg_ctx* ctx, const BtdDev& b, const double* u_in, const
   }
   // chunk chain: src -> (scratch0 / scratch1 alternating) -> ... -> u_out
   const int nchunks = (left + smax - 1) / smax;
+  if (chk && nchunks > 1) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: checkpoints in a chunked run of sweeps");
   double *t0 = nullptr, *t1 = nullptr;
   if (nchunks > 1) {
     CHECK(scratch(ctx, 0, N, &t0));
@@ -824,10 +818,11 @@ static int btd_smooth(aggmg_ctx* ctx, const BtdDev& b, const double* u_in, const
   for (int c = 0; c < nchunks; ++c) {
     const int s = std::min(left, smax);
     double* dst = (c == nchunks - 1) ? u_out : (((nchunks - 1 - c) % 2 == 1) ? t0 : t1);
-    const FusedLaunch a = fused_sweeps(b, src, rhs, dst, alpha.from(nsweeps - left), s, gs);
+    FusedLaunch a = fused_sweeps(b, src, rhs, dst, alpha.from(nsweeps - left), s, gs);
+    if (chk) fused_chk(a, *chk);
     {
       ProfScope ps(ctx, AGGMG_KIND_SMOOTH, level);
-      CHECK(launch_btd(ctx, b, a, s));
+      CHECK(launch_btd(ctx, b, a, s + (chk ? 1 : 0), TileSel(), chk));
     }
     src = dst;
     left -= s;
@@ -934,6 +929,36 @@ static int generic_jacobi(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const
   return launch_csr_jacobi_sweeps(ctx, A->csr, src, rhs, sm->diag, alpha, nsweeps, dst, other, rout, fused);
 }
 
+// n sweeps of a generic smoother from src (nullptr = zero) into dst.  Sweep s writes `work`, the last one dst: with
+// work == dst (aggmg_smooth_dev, the descent) every sweep but the first runs in place in dst; with work == src (the
+// ascent) every sweep but the last in src.  Part of the contract: generic_sweep takes the one-pass block sweep only where
+// input and output differ.  Point Jacobi: generic_jacobi between dst and `other` (rout / resid_done: the banded form's residual).
+static int generic_sweeps(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* src, const double* rhs, Damping damp,
+                          int n, double* dst, double* work, double* other, int level, double* rout = nullptr,
+                          bool* resid_done = nullptr) {
+  const int64_t N = A->m;
+  if (resid_done) *resid_done = false;
+  if (!src) {
+    HIPCHK(hipMemsetAsync(dst, 0, N * sizeof(double), ctx->stream));
+    src = dst;
+  }
+  if (n == 0) {
+    if (src != dst) HIPCHK(hipMemcpyAsync(dst, src, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    return AGGMG_OK;
+  }
+  if (sm->kind == 0) {   // point Jacobi: several sweeps per launch where the operator is banded
+    CHECK(op_ensure_csr(ctx, A));
+    ProfScope ps(ctx, AGGMG_KIND_JACOBI, level);
+    return generic_jacobi(ctx, A, sm, src, rhs, damp, n, dst, other, rout, resid_done);
+  }
+  for (int s = 0; s < n; ++s) {
+    double* d = (s == n - 1) ? dst : work;
+    CHECK(generic_sweep(ctx, A, sm, src, rhs, damp.at(s), d, level));
+    src = d;
+  }
+  return AGGMG_OK;
+}
+
 static int check_pair(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const char* who) {
   if (!ctx) return AGGMG_ERR_ARGUMENT;
   if (!A || !sm) return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": NULL handle");
@@ -948,44 +973,21 @@ static int smooth_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const dou
   if (!b || !u_out || nsweeps < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth: bad argument");
   const int64_t N = A->m;
   if (N == 0) return AGGMG_OK;
-  if (sm->cgt && sm->A == A) {  // CG chain form: fused point-Jacobi sweeps
-    if (u_out != u_in) return cgt_smooth_ext(ctx, *sm->cgt, u_in, b, alpha, nsweeps, u_out, 0);
-    double* t = nullptr;
-    CHECK(scratch(ctx, 2, N, &t));
-    CHECK(cgt_smooth_ext(ctx, *sm->cgt, u_in, b, alpha, nsweeps, t, 0));
-    HIPCHK(hipMemcpyAsync(u_out, t, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  const bool chain = sm->cgt && sm->A == A;   // CG chain form: fused point-Jacobi sweeps
+  if (chain || (sm->btd && sm->A == A)) {
+    // (the fused forms want u_out != u_in: an in-place request is staged through scratch, an extra copy)
+    double* dst = u_out;
+    if (u_out == u_in) CHECK(scratch(ctx, 2, N, &dst));
+    if (chain)
+      CHECK(cgt_smooth_ext(ctx, *sm->cgt, u_in, b, alpha, nsweeps, dst, 0));
+    else
+      CHECK(btd_smooth(ctx, *sm->btd, u_in, b, alpha, nsweeps, dst, 0, N, sm->gs ? 1 : 0));
+    if (dst != u_out) HIPCHK(hipMemcpyAsync(u_out, dst, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     return AGGMG_OK;
   }
-  if (sm->btd && sm->A == A) {
-    if (u_out != u_in) return btd_smooth(ctx, *sm->btd, u_in, b, alpha, nsweeps, u_out, 0, N, sm->gs ? 1 : 0);
-    double* t = nullptr;  // in-place request: stage through scratch (extra copy)
-    CHECK(scratch(ctx, 2, N, &t));
-    CHECK(btd_smooth(ctx, *sm->btd, u_in, b, alpha, nsweeps, t, 0, N, sm->gs ? 1 : 0));
-    HIPCHK(hipMemcpyAsync(u_out, t, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    return AGGMG_OK;
-  }
-  // generic path; point Jacobi ping-pongs through scratch 0
-  const double* src = u_in;
-  double* t = nullptr;
+  double* t = nullptr;   // point Jacobi ping-pongs through scratch 0
   CHECK(scratch(ctx, 0, N, &t));
-  if (!u_in) {
-    HIPCHK(hipMemsetAsync(u_out, 0, N * sizeof(double), ctx->stream));
-    src = u_out;
-  }
-  if (nsweeps == 0) {
-    if (src != u_out) HIPCHK(hipMemcpyAsync(u_out, src, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    return AGGMG_OK;
-  }
-  if (sm->kind == 0) {   // point Jacobi: several sweeps per launch on banded operators, ping-pong through scratch
-    CHECK(op_ensure_csr(ctx, A));
-    ProfScope ps(ctx, AGGMG_KIND_JACOBI, 0);
-    return generic_jacobi(ctx, A, sm, src, b, alpha, nsweeps, u_out, t);
-  }
-  for (int s = 0; s < nsweeps; ++s) {
-    CHECK(generic_sweep(ctx, A, sm, src, b, alpha.at(s), u_out, 0));
-    src = u_out;
-  }
-  return AGGMG_OK;
+  return generic_sweeps(ctx, A, sm, u_in, b, alpha, nsweeps, u_out, u_out, t, 0);
 }
 
 extern "C" int aggmg_smooth_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* u_in,
@@ -1938,8 +1940,9 @@ static int coarse_solve_multi(aggmg_ctx* ctx, aggmg_hier* h, const double* B, in
 constexpr int kPairM = 2, kPairNSA = AGGMG_PAIR_NSA, kPairNSB = AGGMG_PAIR_NSB;   // slabs per thread (tuning: tools/exp_pair_tiles.sh)
 constexpr int kPairTEA = (kThreads / kPairM) * kPairNSA, kPairTEB = (kThreads / 2) * kPairNSB;
 
-static bool pair_level_ok(const Level& l) {
-  return l.S && l.S->btd && l.S->A == l.A && l.tb && !l.S->gs && !l.S->btd->cmp && l.S->btd->m == kPairM && l.S->btd->bsym &&
+static bool pair_level_ok(const aggmg_hier* h, int k) {
+  const Level& l = h->lv[k];
+  return level_path(h, k) == LevelPath::FusedBtd && !l.S->gs && !l.S->btd->cmp && l.S->btd->m == kPairM && l.S->btd->bsym &&
          l.tb->mc == 2 && l.tb->rho > 0 && l.S->btd->ne == (int64_t)l.tb->rho * l.tb->nec;
 }
 
@@ -1951,7 +1954,7 @@ static bool pair_ok(const aggmg_ctx* ctx, const aggmg_hier* h, int k, int nsweep
   if (!ctx->pair_levels || k < 1 || k + 2 > n - 1 || nsweeps < 1 || nsweeps > 8) return false;
   const Level& a = h->lv[k];
   const Level& b = h->lv[k + 1];
-  if (!pair_level_ok(a) || !pair_level_ok(b) || b.S->btd->ne != a.tb->nec) return false;
+  if (!pair_level_ok(h, k) || !pair_level_ok(h, k + 1) || b.S->btd->ne != a.tb->nec) return false;
   if (h->restriction == AGGMG_RESTRICT_PRECONDITIONED && (a.tb->ld || b.tb->ld)) return false;
   TileQuery q;
   q.launch = up ? kTilePairUp : kTilePairDown;
@@ -2130,78 +2133,136 @@ static int schedule_check(aggmg_ctx* ctx, const aggmg_hier* h, int nPre, int nPo
   return AGGMG_OK;
 }
 
-// ---- descend (src/solvers.jl:28-37): leaves u[k] in lv[k].u[0] and rhs[n] in lv[n-1].rhs ----------
+// ---- half-cycles of one level, family by family: the chain path's are cgt_down / cgt_up / cgt_mid (cgt.hip), these take
+// the same arguments.  Down (src/solvers.jl:28-37): nPre sweeps from uin (null: zeros) into l.u[0], the restricted residual
+// into the next level's rhs.  Up (:41-47): the next level's result prolonged onto l.u[0], nPost sweeps into dst. ---------
+static const double* coarse_result(const aggmg_hier* h, int k) {   // what level k prolongs from
+  return (k + 2 == (int)h->lv.size()) ? h->lv[k + 1].u[0] : h->lv[k + 1].u[1];
+}
+// the generic launches around a level's sweeps: rc = L' (rhs - A u[0]) through l.tmp (resid_done: it holds the residual
+// already), and u[0] += L uc
+static int generic_restrict_residual(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* rhs, bool resid_done) {
+  Level& l = h->lv[k];
+  if (!resid_done) {
+    ProfScope ps(ctx, AGGMG_KIND_RESIDUAL, k);
+    CHECK(op_ensure_csr(ctx, l.A));
+    CHECK(launch_csr<kResidual>(ctx, l.A->csr, l.u[0], rhs, nullptr, 0.0, l.tmp));
+  }
+  ProfScope ps(ctx, AGGMG_KIND_RESTRICT, k);
+  CHECK(op_ensure_csc_blocks(ctx, l.L));
+  return launch_csr<kSpmvSet>(ctx, l.L->csc, l.tmp, nullptr, nullptr, 0.0, h->lv[k + 1].rhs);
+}
+static int generic_prolong_add(aggmg_ctx* ctx, aggmg_hier* h, int k) {
+  Level& l = h->lv[k];
+  ProfScope ps(ctx, AGGMG_KIND_PROLONG, k);
+  CHECK(op_ensure_csr(ctx, l.L));
+  return launch_csr<kSpmvAdd>(ctx, l.L->csr, coarse_result(h, k), nullptr, nullptr, 0.0, l.u[0]);
+}
+static int no_split_ascent(aggmg_ctx* ctx) {
+  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "split ascent needs the fused block-tridiagonal fine level");
+}
+
+// Block-tridiagonal levels (LevelPath::FusedBtd, BtdTransfer).  One fused launch where the level has the structured
+// transfer and the launch a tile; otherwise chunked sweeps and the generic launches around them.
+static int btd_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uin, const double* rhs, int nPre, double alpha) {
+  Level& l = h->lv[k];
+  const BtdDev& B = *l.S->btd;
+  const Damping damp = l.damp_pre(alpha);   // the level's schedule, or alpha for every sweep
+  const int gs = l.S->gs ? 1 : 0;           // Gauss-Seidel: even elements, then odd ones
+  if (l.tb && btd_launch_ok(*l.S, nPre, 1, l.tb.get())) {
+    FusedLaunch a = fused_sweeps(B, uin, rhs, l.u[0], damp, nPre, gs);
+    fused_descent(a, h, l, h->lv[k + 1].rhs);
+    fused_dictionary(a, l);
+    ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
+    return launch_btd(ctx, B, a, nPre + 1);   // (+ 1: the residual rows)
+  }
+  CHECK(btd_smooth(ctx, B, uin, rhs, damp, nPre, l.u[0], k, l.N, gs));
+  return generic_restrict_residual(ctx, h, k, rhs, false);
+}
+// src: the pre-smoothed iterate (default: l.u[0]).  chk: the launch forms a checkpoint's sums -- residual rows of the
+// FINAL iterate, one more element of halo -- and reports its tile count there.  sel (level 0): the tiles to run; the
+// dictionary serves no selection (the partitioned cycle keeps the full arrays) and no checkpoint (fused_dictionary's own test).
+static int btd_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* rhs, int nPost, double alpha, double* dst,
+                  const double* src = nullptr, CgtChk* chk = nullptr, const TileSel& sel = TileSel()) {
+  Level& l = h->lv[k];
+  const BtdDev& B = *l.S->btd;
+  const Damping damp = l.damp_post(alpha);
+  const int gs = l.S->gs ? 2 : 0;   // Gauss-Seidel in the reverse colour order: the cycle stays symmetric
+  if (l.tb && btd_launch_ok(*l.S, nPost, 0, nullptr)) {
+    FusedLaunch a = fused_sweeps(B, src ? src : l.u[0], rhs, dst, damp, nPost, gs);
+    fused_ascent(a, l, coarse_result(h, k));
+    if (chk) fused_chk(a, *chk);
+    if (sel.mode == 0) fused_dictionary(a, l);
+    ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
+    return launch_btd(ctx, B, a, nPost + (chk ? 1 : 0), sel, chk);
+  }
+  if (sel.mode == 1 || sel.mode == 2) return no_split_ascent(ctx);
+  if (src || chk) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: unfused ascent from another source or with a checkpoint");
+  CHECK(generic_prolong_add(ctx, h, k));
+  return btd_smooth(ctx, B, l.u[0], rhs, damp, nPost, dst, k, l.N, gs);
+}
+// Between two cycles, level 0 (fine_mid_ok said that the launch exists): post-smoothing of one cycle, pre-smoothing and
+// restriction of the next in ONE launch, cur -> alt; a checkpoint falls between the two runs of sweeps.
+static int btd_mid(aggmg_ctx* ctx, aggmg_hier* h, const double* cur, double* alt, const double* b, int nsweeps, double alpha,
+                   CgtChk* chk = nullptr) {
+  Level& l = h->lv[0];
+  FusedLaunch a = fused_sweeps(*l.S->btd, cur, b, alt, l.damp_mid(alpha), nsweeps);
+  fused_ascent(a, l, coarse_result(h, 0));
+  fused_descent(a, h, l, h->lv[1].rhs);
+  if (chk) fused_chk(a, *chk);
+  fused_dictionary(a, l);
+  ProfScope ps(ctx, AGGMG_KIND_FUSED_MID, 0);
+  return launch_btd(ctx, *l.S->btd, a, nsweeps + 1, TileSel(), chk);
+}
+
+// Generic levels: generic_sweeps between the generic launches.  The descent sweeps in place in l.u[0] (point Jacobi:
+// with l.u[1] as its second vector, the banded form's residual straight into l.tmp); the ascent keeps its intermediate
+// sweeps in l.u[0] and writes the last one to dst (point Jacobi: with whichever of l.u[1] / l.tmp is not dst).
+static int generic_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uin, const double* rhs, int nPre, double alpha) {
+  Level& l = h->lv[k];
+  bool resid_done = false;
+  CHECK(generic_sweeps(ctx, l.A, l.S, uin, rhs, l.damp_pre(alpha), nPre, l.u[0], l.u[0], l.u[1], k, l.tmp, &resid_done));
+  return generic_restrict_residual(ctx, h, k, rhs, resid_done);
+}
+static int generic_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* rhs, int nPost, double alpha, double* dst) {
+  Level& l = h->lv[k];
+  CHECK(generic_prolong_add(ctx, h, k));
+  double* other = (dst == l.u[1]) ? l.tmp : l.u[1];
+  return generic_sweeps(ctx, l.A, l.S, l.u[0], rhs, l.damp_post(alpha), nPost, dst, l.u[0], other, k);
+}
+
+// ---- descend: leaves u[k] in lv[k].u[0] and rhs[n] in lv[n-1].rhs -------------------------------
+// (a level that pairs with the next is a FusedBtd level: asking for the pair first loses no chain level)
 static int vcycle_down(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const double* b, int nPre, double alpha,
                        int k_first = 0) {
   const int n = (int)h->lv.size();
   CHECK(schedule_check(ctx, h, nPre, -1, k_first));
   for (int k = k_first; k < n - 1; ++k) {
-    Level& l = h->lv[k];
-    Level& c = h->lv[k + 1];
-    const double* rhs = k == 0 ? b : l.rhs;
+    const double* rhs = k == 0 ? b : h->lv[k].rhs;
     const double* uin = k == 0 ? x0 : nullptr;  // u[k] = zeros for k > 1 (:29-31)
-    const Damping damp = l.damp_pre(alpha);     // the level's schedule, or alpha for every sweep
-    if (l.cgt_fused) {
-      CHECK(cgt_down(ctx, h, k, uin, rhs, nPre, alpha));
-      continue;
-    }
     if (pair_ok(ctx, h, k, nPre, false)) {   // this level and the next in one launch
       CHECK(launch_pair_down(ctx, h, k, nPre, alpha));
       ++k;
       continue;
     }
-    const bool structured = l.S->btd && l.S->A == l.A;
-    if (structured && l.tb && btd_launch_ok(*l.S, nPre, 1, l.tb.get())) {
-      // (Gauss-Seidel pre-smoothing: even elements, then odd ones)
-      FusedLaunch a = fused_sweeps(*l.S->btd, uin, rhs, l.u[0], damp, nPre, l.S->gs ? 1 : 0);
-      fused_descent(a, h, l, c.rhs);
-      fused_dictionary(a, l);
-      ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
-      CHECK(launch_btd(ctx, *l.S->btd, a, nPre + 1));
-    } else {
-      bool resid_done = false;
-      if (structured) {
-        CHECK(btd_smooth(ctx, *l.S->btd, uin, rhs, damp, nPre, l.u[0], k, l.N, l.S->gs ? 1 : 0));
-      } else {
-        // generic sweeps, result in l.u[0]
-        const double* src = uin;
-        if (!src) {
-          HIPCHK(hipMemsetAsync(l.u[0], 0, l.N * sizeof(double), ctx->stream));
-          src = l.u[0];
-        }
-        if (nPre == 0 && src != l.u[0])
-          HIPCHK(hipMemcpyAsync(l.u[0], src, l.N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        if (l.S->kind == 0 && nPre > 0) {   // point Jacobi: several sweeps per launch where the operator is banded
-          CHECK(op_ensure_csr(ctx, l.A));
-          ProfScope ps(ctx, AGGMG_KIND_JACOBI, k);
-          // (banded operators: the residual for the restriction comes out of the sweeps' own launch)
-          CHECK(generic_jacobi(ctx, l.A, l.S, src, rhs, damp, nPre, l.u[0], l.u[1], l.tmp, &resid_done));
-        } else {
-          for (int s = 0; s < nPre; ++s) {
-            CHECK(generic_sweep(ctx, l.A, l.S, src, rhs, damp.at(s), l.u[0], k));
-            src = l.u[0];
-          }
-        }
-      }
-      if (!resid_done) {
-        ProfScope ps(ctx, AGGMG_KIND_RESIDUAL, k);
-        CHECK(op_ensure_csr(ctx, l.A));
-        CHECK(launch_csr<kResidual>(ctx, l.A->csr, l.u[0], rhs, nullptr, 0.0, l.tmp));
-      }
-      ProfScope ps(ctx, AGGMG_KIND_RESTRICT, k);
-      CHECK(op_ensure_csc_blocks(ctx, l.L));
-      CHECK(launch_csr<kSpmvSet>(ctx, l.L->csc, l.tmp, nullptr, nullptr, 0.0, c.rhs));
+    switch (level_path(h, k)) {
+      case LevelPath::FusedChain: CHECK(cgt_down(ctx, h, k, uin, rhs, nPre, alpha)); break;
+      case LevelPath::FusedBtd:
+      case LevelPath::BtdTransfer: CHECK(btd_down(ctx, h, k, uin, rhs, nPre, alpha)); break;
+      case LevelPath::Generic: CHECK(generic_down(ctx, h, k, uin, rhs, nPre, alpha)); break;
+      case LevelPath::Coarsest: break;
     }
   }
   return AGGMG_OK;
 }
 
-// ---- ascend (src/solvers.jl:41-47): expects the coarsest solution in lv[n-1].u[0] ---------------
+// ---- ascend: expects the coarsest solution in lv[n-1].u[0] ---------------------------------------
 // sel (fine level only): which tiles of the level-0 launch to run; with a selection the coarser
 // levels are skipped (the caller ran them with k_last = 1)
 // csplit (element-partitioned runs): the first launch of the ascent -- it has to be a two-level launch next to the coarsest
 // level -- in two parts around the exchange of the coarsest solution's ghost blocks: mode 2 runs ONLY its tiles that read
-// no ghost block (nothing else), mode 1 its remaining tiles and then the rest of the ascent
+// no ghost block (nothing else), mode 1 its remaining tiles and then the rest of the ascent, two-level launches all of it
+// (no further pairs are split)
 struct CoarseSplit {
   int mode = 0;
   int64_t gh_lo = 0, gh_hi = 0;
@@ -2210,74 +2271,29 @@ static int vcycle_up(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, 
                      int k_last = 0, const TileSel& sel = TileSel(), const CoarseSplit& cs = CoarseSplit()) {
   const int n = (int)h->lv.size();
   CHECK(schedule_check(ctx, h, -1, nPost, k_last));
-  if (cs.mode != 0) {
-    const int k = n - 2;
-    if (!(sel.mode == 0 && k - 1 >= std::max(k_last, 1) && pair_ok(ctx, h, k - 1, nPost, true)))
-      return fail(ctx, AGGMG_ERR_UNSUPPORTED, "split coarse ascent needs a two-level launch next to the coarsest level");
-    CHECK(launch_pair_up(ctx, h, k - 1, nPost, alpha, h->lv[k - 1].u[1], cs.mode, cs.gh_lo, cs.gh_hi));
-    if (cs.mode == 2) return AGGMG_OK;
-    for (int kk = k - 2; kk >= k_last; --kk) {   // the levels above the pair, as below (no further pairs are split)
-      if (kk - 1 >= std::max(k_last, 1) && pair_ok(ctx, h, kk - 1, nPost, true)) {
-        CHECK(launch_pair_up(ctx, h, kk - 1, nPost, alpha, h->lv[kk - 1].u[1]));
-        --kk;
-        continue;
-      }
-      return fail(ctx, AGGMG_ERR_UNSUPPORTED, "split coarse ascent: unpaired level above the coarse pair");
-    }
-    return AGGMG_OK;
-  }
+  int part = cs.mode;   // of the next two-level launch: the first one is the split one
   for (int k = (sel.mode != 0 ? 0 : n - 2); k >= k_last; --k) {
-    Level& l = h->lv[k];
-    Level& c = h->lv[k + 1];
-    const double* rhs = k == 0 ? b : l.rhs;
-    double* dst = k == 0 ? x_out : l.u[1];
-    const double* uc = (k + 1 == n - 1) ? c.u[0] : c.u[1];
-    const Damping damp = l.damp_post(alpha);
+    const double* rhs = k == 0 ? b : h->lv[k].rhs;
+    double* dst = k == 0 ? x_out : h->lv[k].u[1];
     if (sel.mode == 0 && k - 1 >= std::max(k_last, 1) && pair_ok(ctx, h, k - 1, nPost, true)) {   // this level and the finer one in one launch
-      CHECK(launch_pair_up(ctx, h, k - 1, nPost, alpha, h->lv[k - 1].u[1]));
+      CHECK(launch_pair_up(ctx, h, k - 1, nPost, alpha, h->lv[k - 1].u[1], part, cs.gh_lo, cs.gh_hi));
+      if (part == 2) return AGGMG_OK;
+      part = 0;
       --k;
       continue;
     }
-    if (l.cgt_fused) {
-      if (k == 0 && (sel.mode == 1 || sel.mode == 2))
-        return fail(ctx, AGGMG_ERR_UNSUPPORTED, "split ascent needs the fused block-tridiagonal fine level");
-      CHECK(cgt_up(ctx, h, k, rhs, nPost, alpha, dst));
-      continue;
-    }
-    const bool structured = l.S->btd && l.S->A == l.A;
-    if (structured && l.tb && btd_launch_ok(*l.S, nPost, 0, nullptr)) {
-      // (Gauss-Seidel post-smoothing in the reverse colour order: the cycle stays symmetric)
-      FusedLaunch a = fused_sweeps(*l.S->btd, l.u[0], rhs, dst, damp, nPost, l.S->gs ? 2 : 0);
-      fused_ascent(a, l, uc);
-      if (sel.mode == 0) fused_dictionary(a, l);   // (the partitioned cycle's tile selections keep the full arrays)
-      ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
-      CHECK(launch_btd(ctx, *l.S->btd, a, std::max(nPost, 0), k == 0 ? sel : TileSel()));
-    } else {
-      if (k == 0 && (sel.mode == 1 || sel.mode == 2))
-        return fail(ctx, AGGMG_ERR_UNSUPPORTED, "split ascent needs the fused block-tridiagonal fine level");
-      {
-        ProfScope ps(ctx, AGGMG_KIND_PROLONG, k);
-        CHECK(op_ensure_csr(ctx, l.L));
-        CHECK(launch_csr<kSpmvAdd>(ctx, l.L->csr, uc, nullptr, nullptr, 0.0, l.u[0]));
-      }
-      if (structured) {
-        CHECK(btd_smooth(ctx, *l.S->btd, l.u[0], rhs, damp, nPost, dst, k, l.N, l.S->gs ? 2 : 0));
-      } else {
-        const double* src = l.u[0];
-        if (nPost == 0) HIPCHK(hipMemcpyAsync(dst, src, l.N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        double* alt = (dst == l.u[1]) ? l.tmp : l.u[1];
-        if (l.S->kind == 0 && nPost > 0) {
-          CHECK(op_ensure_csr(ctx, l.A));
-          ProfScope ps(ctx, AGGMG_KIND_JACOBI, k);
-          CHECK(generic_jacobi(ctx, l.A, l.S, src, rhs, damp, nPost, dst, alt));
-        } else {
-          for (int s = 0; s < nPost; ++s) {
-            double* d2 = (s == nPost - 1) ? dst : l.u[0];
-            CHECK(generic_sweep(ctx, l.A, l.S, src, rhs, damp.at(s), d2, k));
-            src = d2;
-          }
-        }
-      }
+    if (cs.mode != 0)
+      return fail(ctx, AGGMG_ERR_UNSUPPORTED, part != 0 ? "split coarse ascent needs a two-level launch next to the coarsest level"
+                                                        : "split coarse ascent: unpaired level above the coarse pair");
+    const LevelPath path = level_path(h, k);
+    const bool btd = path == LevelPath::FusedBtd || path == LevelPath::BtdTransfer;
+    if (!btd && (sel.mode == 1 || sel.mode == 2)) return no_split_ascent(ctx);
+    switch (path) {
+      case LevelPath::FusedChain: CHECK(cgt_up(ctx, h, k, rhs, nPost, alpha, dst)); break;
+      case LevelPath::FusedBtd:   // (refuses a selection itself where the fused launch has no tile)
+      case LevelPath::BtdTransfer: CHECK(btd_up(ctx, h, k, rhs, nPost, alpha, dst, nullptr, nullptr, sel)); break;
+      case LevelPath::Generic: CHECK(generic_up(ctx, h, k, rhs, nPost, alpha, dst)); break;
+      case LevelPath::Coarsest: break;
     }
   }
   return AGGMG_OK;
@@ -2331,7 +2347,7 @@ static_assert(kMultiKB == 1 || kMultiKB == 2 || kMultiKB == 4 || kMultiKB == 8, 
 
 static bool multi_level_ok(const aggmg_hier* h, int k, int nPre, int nPost) {
   const Level& l = h->lv[k];
-  if (!(l.S && l.S->btd && l.S->A == l.A && l.tb) || l.cgt_fused || l.S->gs) return false;
+  if (level_path(h, k) != LevelPath::FusedBtd || l.S->gs) return false;
   const BtdDev& b = *l.S->btd;
   const TransferBtd& t = *l.tb;
   if (b.cmp ? !(b.m == 2 || b.m == 4) : b.m != 2) return false;
@@ -2567,38 +2583,44 @@ struct FineLevel {
   const double* b;
   int nPre, nPost;
   double alpha;
-  bool chain;
+  bool chain() const { return level_path(h, 0) == LevelPath::FusedChain; }
   Level& l0() const { return h->lv[0]; }
-  const double* uc() const { return h->lv.size() == 2 ? h->lv[1].u[0] : h->lv[1].u[1]; }
   // post-smoothing of one cycle, pre-smoothing and restriction of the next: cur -> alt
   int mid(const double* cur, double* alt, CgtChk* chk) const {
-    if (chain) return cgt_mid(ctx, h, cur, alt, b, nPost + nPre, alpha, chk);
-    const BtdDev& B0 = *l0().S->btd;
-    FusedLaunch a = fused_sweeps(B0, cur, b, alt, l0().damp_mid(alpha), nPost + nPre);
-    fused_ascent(a, l0(), uc());
-    fused_descent(a, h, l0(), h->lv[1].rhs);
-    if (chk) fused_chk(a, *chk);
-    fused_dictionary(a, l0());
-    ProfScope ps(ctx, AGGMG_KIND_FUSED_MID, 0);
-    return launch_btd(ctx, B0, a, nPost + nPre + 1, TileSel(), chk);
+    return (chain() ? cgt_mid : btd_mid)(ctx, h, cur, alt, b, nPost + nPre, alpha, chk);
   }
   // the ascent alone: src -> dst
   int up(const double* src, double* dst, CgtChk* chk) const {
-    if (chain) return cgt_up(ctx, h, 0, b, nPost, alpha, dst, src, chk);
-    const BtdDev& B0 = *l0().S->btd;
-    FusedLaunch a = fused_sweeps(B0, src, b, dst, l0().damp_post(alpha), nPost);
-    fused_ascent(a, l0(), uc());
-    if (chk) fused_chk(a, *chk);
-    fused_dictionary(a, l0());
-    ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, 0);
-    // (a checkpoint here forms residual rows of the FINAL iterate: one more element of halo, as a residual)
-    return launch_btd(ctx, B0, a, nPost + (chk ? 1 : 0), TileSel(), chk);
+    return chain() ? cgt_up(ctx, h, 0, b, nPost, alpha, dst, src, chk) : btd_up(ctx, h, 0, b, nPost, alpha, dst, src, chk);
   }
   int64_t chk_tiles() const {
-    return chain ? cgt_chk_tiles(*l0().S->cgt, nPost + nPre, l0().tc ? l0().tc->rho : 1)
+    return chain() ? cgt_chk_tiles(*l0().S->cgt, nPost + nPre, l0().tc ? l0().tc->rho : 1)
                  : btd_chk_tiles(*l0().S->btd, nPost + nPre, l0().tb.get());
   }
 };
+
+// Does level 0 have the launch between two cycles (cgt_mid / btd_mid) that cycle_loop is built on -- for plain cycles
+// (aggmg_vcycles_dev) or with the checkpoints of aggmg_multigrid_dev?  Otherwise the callers run cycle by cycle.
+enum class MidFor { PlainCycles, Checkpointed };
+static bool fine_mid_ok(const aggmg_hier* h, int nPre, int nPost, MidFor purpose) {
+  const bool chk = purpose == MidFor::Checkpointed;
+  const Level& l0 = h->lv[0];
+  if (h->coarse_mode == AGGMG_COARSE_EXTERNAL) return false;   // the loop runs the coarsest solve itself
+  switch (level_path(h, 0)) {
+    case LevelPath::FusedChain:
+      // sweeps: the checkpoint variant of the chain kernel is point Jacobi's (sw 0); plain cycles take all but red-black GS (3)
+      if (chk ? l0.S->cgt->sw != 0 : l0.S->cgt->sw == 3) return false;
+      // a checkpoint needs its sweeps in ONE launch; plain cycles chunk a longer run (cgt_mid)
+      return !chk || nPost + nPre <= cgt_max_fused_sweeps(*l0.S->cgt);
+    case LevelPath::FusedBtd:
+      if (l0.S->gs) return false;
+      // restriction: checkpoints form residual rows for their norms -- the explicit form alone; plain cycles want the
+      // mode's own form to exist (a single descent, btd_down, takes any: without (L'D) it restricts with lf)
+      if (h->restriction != AGGMG_RESTRICT_EXPLICIT && (chk || !l0.tb->ld)) return false;
+      return btd_launch_ok(*l0.S, nPre + nPost, 1, l0.tb.get());   // (no tile: a ratio the halo leaves no room for)
+    default: return false;
+  }
+}
 
 // Histories and stopping test of launches with checkpoints (with the outer solver loops below)
 struct ChkHist {
@@ -2665,19 +2687,12 @@ extern "C" int aggmg_vcycles_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0
   if (x_out == x0 || x_out == b) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycles: x_out must not alias x0 or b");
   if (h->coarse_mode == AGGMG_COARSE_EXTERNAL)
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycles: hierarchy was created with AGGMG_COARSE_EXTERNAL");
-  const int n = (int)h->lv.size();
-  Level& l0 = h->lv[0];
-  // (no tile for the launch between two cycles -- a fine-level ratio its halo leaves no room for: the plain sequence)
-  const bool fusable = n >= 2 && l0.S && l0.S->btd && l0.S->A == l0.A && l0.tb && vcycles_restriction_ok(h, l0) &&
-                       btd_launch_ok(*l0.S, nPre + nPost, 1, l0.tb.get()) && !l0.S->gs;
-  // CG chain fine level: the same cross-cycle fusion with the chain kernel
-  const bool chain = n >= 2 && l0.cgt_fused && ncycles > 1 && l0.S->cgt->sw != 3;
-  if (chain || (fusable && ncycles > 1))
-    return cycle_loop(FineLevel{ctx, h, b, nPre, nPost, alpha, chain}, x0, ncycles, x_out, 0, nullptr, nullptr);
+  if (ncycles > 1 && fine_mid_ok(h, nPre, nPost, MidFor::PlainCycles))   // (a single cycle has no launch between two)
+    return cycle_loop(FineLevel{ctx, h, b, nPre, nPost, alpha}, x0, ncycles, x_out, 0, nullptr, nullptr);
   // plain sequence; intermediate iterates ping-pong between two vectors owned by the hierarchy
   if (ncycles > 1)
     for (auto& p : h->cyc)
-      if (!p) CHECK(p.alloc(ctx, l0.N));
+      if (!p) CHECK(p.alloc(ctx, h->lv[0].N));
   const double* src = x0;
   for (int c = 0; c < ncycles; ++c) {
     double* dst = (c == ncycles - 1) ? x_out : h->cyc[c & 1];
@@ -2717,9 +2732,7 @@ extern "C" int aggmg_vcycle_up_split_dev(aggmg_ctx* ctx, aggmg_hier* h, const do
     all.mode = 3;
     return vcycle_up(ctx, h, b, nPost, alpha, x_out, 0, all);
   }
-  Level& l = h->lv[0];
-  if (!(l.S && l.S->btd && l.S->A == l.A && l.tb && btd_launch_ok(*l.S, nPost, 0, nullptr)))
-    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "split ascent needs the fused block-tridiagonal fine level");
+  if (!(level_path(h, 0) == LevelPath::FusedBtd && btd_launch_ok(*h->lv[0].S, nPost, 0, nullptr))) return no_split_ascent(ctx);
   if (part == 0) return h->lv.size() > 2 ? vcycle_up(ctx, h, b, nPost, alpha, x_out, 1) : AGGMG_OK;
   TileSel sel;
   sel.mode = part;  // 1 ends, 2 middle
@@ -2951,14 +2964,13 @@ extern "C" int aggmg_vcycle(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, con
 extern "C" int aggmg_hier_level_kind(aggmg_ctx* ctx, const aggmg_hier* h, int level, int* kind) {
   if (!ctx || !h || !kind) return AGGMG_ERR_ARGUMENT;
   if (level < 0 || level >= (int)h->lv.size()) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_kind: level out of range");
-  const Level& l = h->lv[level];
-  *kind = AGGMG_LEVEL_GENERIC;
-  if (level == (int)h->lv.size() - 1)
-    *kind = AGGMG_LEVEL_COARSEST;
-  else if (l.cgt_fused)
-    *kind = AGGMG_LEVEL_FUSED_CHAIN;
-  else if (l.S && l.S->btd && l.S->A == l.A && l.tb)
-    *kind = AGGMG_LEVEL_FUSED_BTD;
+  switch (level_path(h, level)) {
+    case LevelPath::Coarsest: *kind = AGGMG_LEVEL_COARSEST; break;
+    case LevelPath::FusedChain: *kind = AGGMG_LEVEL_FUSED_CHAIN; break;
+    case LevelPath::FusedBtd: *kind = AGGMG_LEVEL_FUSED_BTD; break;
+    case LevelPath::BtdTransfer:   // (several launches per half-cycle, as the generic kernels)
+    case LevelPath::Generic: *kind = AGGMG_LEVEL_GENERIC; break;
+  }
   return AGGMG_OK;
 }
 
@@ -3014,8 +3026,9 @@ extern "C" int aggmg_hier_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int 
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_launch_bytes: kind must be AGGMG_KIND_FUSED_DOWN / _UP / _MID");
   const Level& l = h->lv[level];
   const bool down = kind != AGGMG_KIND_FUSED_UP, up = kind != AGGMG_KIND_FUSED_DOWN;
-  if (l.cgt_fused) return cgt_launch_bytes(ctx, h, level, down, up, has_x0 != 0, read_bytes, write_bytes);
-  if (!(l.S && l.S->btd && l.S->A == l.A && l.tb))
+  const LevelPath path = level_path(h, level);
+  if (path == LevelPath::FusedChain) return cgt_launch_bytes(ctx, h, level, down, up, has_x0 != 0, read_bytes, write_bytes);
+  if (path != LevelPath::FusedBtd)
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_hier_launch_bytes: the level runs the generic kernels (several launches)");
   const bool pre = l.tb->ld && h->restriction == AGGMG_RESTRICT_PRECONDITIONED;
   btd_launch_bytes(*l.S->btd, true, up || has_x0, down, false, up ? l.tb.get() : nullptr, down ? l.tb.get() : nullptr, pre,
@@ -3033,7 +3046,7 @@ extern "C" int aggmg_hier_multi_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_launch_bytes: kind must be AGGMG_KIND_FUSED_DOWN / _UP");
   if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_launch_bytes: ncols must be >= 1");
   const Level& l = h->lv[level];
-  if (l.cgt_fused || !(l.S && l.S->btd && l.S->A == l.A && l.tb))
+  if (level_path(h, level) != LevelPath::FusedBtd)
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_hier_multi_launch_bytes: the level has no fused block-tridiagonal launch");
   const bool down = kind == AGGMG_KIND_FUSED_DOWN;
   const bool pre = l.tb->ld && h->restriction == AGGMG_RESTRICT_PRECONDITIONED;
@@ -3372,14 +3385,8 @@ extern "C" int aggmg_multigrid_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* 
   // store of the iterate and a few reductions instead of a residual launch over the fine operator and a cycle without
   // the cross-cycle fusion (AGGMG_OPT_MG_CHECKPOINT = 0: the form below, for A/B runs and tests).
   // The CG chain fine level (point-Jacobi): the same loop with the chain kernel's checkpoint variant.
-  const int n = (int)h->lv.size();
-  Level& l0 = h->lv[0];
-  const bool fusable = n >= 2 && l0.S && l0.S->btd && l0.S->A == l0.A && l0.tb && multigrid_restriction_ok(h) &&
-                       btd_launch_ok(*l0.S, nPre + nPost, 1, l0.tb.get()) && !l0.S->gs && h->coarse_mode != AGGMG_COARSE_EXTERNAL;
-  const bool chain = !fusable && n >= 2 && l0.cgt_fused && l0.S->cgt->sw == 0 && h->coarse_mode != AGGMG_COARSE_EXTERNAL &&
-                     nPost + nPre <= cgt_max_fused_sweeps(*l0.S->cgt);
-  if (ctx->mg_checkpoint && (fusable || chain)) {
-    const FineLevel f{ctx, h, b, nPre, nPost, alpha, chain};
+  if (ctx->mg_checkpoint && fine_mid_ok(h, nPre, nPost, MidFor::Checkpointed)) {
+    const FineLevel f{ctx, h, b, nPre, nPost, alpha};
     ChkHist H;
     CHECK(chk_buffers(ctx, 1, f.chk_tiles(), ctx->solv_sc + 8, &H));   // [8] ||A x - b||  [9] ||x - u_exact||
     H.u_exact = u_exact;
@@ -3457,14 +3464,10 @@ extern "C" int aggmg_smoother_solve_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoot
     H.tol_nb = tol * nb;
     H.res = res_hist;
     H.err = err_hist;
-    // S sweeps src -> dst in one launch; chk: with its checkpoints (one more element of halo for their residual rows)
+    // S sweeps src -> dst in one launch; chk: with its checkpoints
     auto sweeps = [&](const double* src, double* dst, int S, CgtChk* chk) -> int {
-      if (chain) return cgt_smooth_ext(ctx, *sm->cgt, src, b, alpha, S, dst, 0, chk);
-      if (!chk) return btd_smooth(ctx, *sm->btd, src, b, alpha, S, dst, 0, N, 0);
-      FusedLaunch a = fused_sweeps(*sm->btd, src, b, dst, alpha, S);
-      fused_chk(a, *chk);
-      ProfScope ps(ctx, AGGMG_KIND_SMOOTH, 0);
-      return launch_btd(ctx, *sm->btd, a, S + 1, TileSel(), chk);
+      return chain ? cgt_smooth_ext(ctx, *sm->cgt, src, b, alpha, S, dst, 0, chk)
+                   : btd_smooth(ctx, *sm->btd, src, b, alpha, S, dst, 0, N, 0, chk);
     };
     while (done < maxiter) {
       const int S = std::min(smax, maxiter - done);

@@ -377,6 +377,23 @@ struct aggmg_hier {
 // AGGMG_RESTRICT_PRECONDITIONED_MAX_ELEMS fine elements.
 inline int default_restriction() { return AGGMG_RESTRICT_EXPLICIT; }
 
+// How level k of a hierarchy runs its half of a cycle -- the one place that reads it off the level's fields.  Whether a
+// given launch has a tile depends on the sweep counts as well: the half-cycle functions ask that, call by call.
+enum class LevelPath {
+  Coarsest,     // solved, not smoothed
+  FusedChain,   // CG chain form + structured transfer: cgt_down / cgt_up / cgt_mid (cgt.hip)
+  FusedBtd,     // block-tridiagonal form + structured transfer: btd_down / btd_up / btd_mid
+  BtdTransfer,  // block-tridiagonal sweeps, generic residual / restriction / prolongation (the same three functions)
+  Generic       // generic_down / generic_up
+};
+inline LevelPath level_path(const aggmg_hier* h, int k) {
+  const Level& l = h->lv[k];
+  if (k == (int)h->lv.size() - 1) return LevelPath::Coarsest;
+  if (l.cgt_fused) return LevelPath::FusedChain;
+  if (l.S && l.S->btd && l.S->A == l.A) return l.tb ? LevelPath::FusedBtd : LevelPath::BtdTransfer;
+  return LevelPath::Generic;
+}
+
 inline int scratch(aggmg_ctx* ctx, int slot, int64_t len, double** out) {
   CHECK(ctx->scratch[slot].reserve(ctx, len));
   *out = ctx->scratch[slot];
