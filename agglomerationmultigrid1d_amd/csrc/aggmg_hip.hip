@@ -1799,6 +1799,8 @@ extern "C" int aggmg_hier_free(aggmg_ctx* ctx, aggmg_hier* h) {
   return AGGMG_OK;
 }
 
+static bool pair_level_ok(const aggmg_hier* h, int k);   // (with the two-level launches, below)
+
 extern "C" int aggmg_hier_create(aggmg_ctx* ctx, int nlevels, aggmg_op* const* stiffness,
                                  aggmg_smoother* const* smoothers, aggmg_op* const* interpolation,
                                  int coarse_mode, aggmg_hier** out) {
@@ -1848,6 +1850,11 @@ extern "C" int aggmg_hier_create(aggmg_ctx* ctx, int nlevels, aggmg_op* const* s
     if (ok) l.tb = std::move(tb);
     // the level's distinct operator records, where they are few (AGGMG_OPT_OPERATOR_DICTIONARY)
     if (l.tb && ctx->op_dict) CHECK(setup_op_dictionary(ctx, *l.S->btd, *l.tb, &l.dict));
+  }
+  // the same for the levels a two-level launch may take (pair_ok: below the finest, above the coarsest)
+  for (int k = 1; ctx->op_dict && k + 1 < nlevels; ++k) {
+    Level& l = h->lv[k];
+    if (pair_level_ok(h.get(), k)) CHECK(setup_pair_dictionary(ctx, *l.S->btd, *l.tb, &l.pdict));
   }
   // CG chain levels: structured transfer to the next level; a level is fused when it has both
   for (int k = 0; k + 1 < nlevels; ++k) {
@@ -1981,6 +1988,23 @@ static PairArgs pair_args(const aggmg_hier* h, int k, int nsweeps) {
   return p;
 }
 
+// The two levels' operator dictionaries in place of their full arrays (after pair_args), when BOTH levels have one:
+// btd_pair_*_dict_kernel reads the same bits from them.  Otherwise both keep the full arrays.
+static bool pair_dictionary(PairArgs& p, PairDict& d, const Level& a, const Level& b) {
+  const PairDictDev *da = a.pdict.get(), *db = b.pdict.get();
+  if (!da || !db) return false;
+  auto lev = [](const PairDictDev& x, int64_t ne) { return PairLevel{x.bsym, x.dblk, x.sub, x.sup, ne}; };
+  auto xf = [](const PairDictDev& x, const PairXfer& t) {
+    return PairXfer{x.lf_unit ? nullptr : x.lf.get(), x.lf_unit ? x.lf.get() : nullptr, t.rho, t.nec};
+  };
+  p.A = lev(*da, p.A.ne);
+  p.B = lev(*db, p.B.ne);
+  p.ab = xf(*da, p.ab);
+  p.bc = xf(*db, p.bc);
+  d = PairDict{da->cls, db->cls, da->sback, db->sback};
+  return true;
+}
+
 static int launch_pair_down(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPre, double alpha) {
   Level& a = h->lv[k];
   Level& b = h->lv[k + 1];
@@ -2000,9 +2024,15 @@ static int launch_pair_down(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPre, doub
   const int64_t ntiles = (p.B.ne + plan.own - 1) / plan.own;
   if (ntiles == 0) return AGGMG_OK;
   const size_t lds = ((size_t)2 * (kPairTEA + 2) * kPairM + (size_t)kPairTEB * 2) * sizeof(double);
+  PairDict d;
+  const bool dict = pair_dictionary(p, d, a, b);
   ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
-  hipLaunchKernelGGL((btd_pair_down_kernel<kPairM, kPairNSA, kPairNSB, kThreads>), dim3((unsigned)ntiles), dim3(kThreads), lds,
-                     ctx->stream, p, wa, wb);
+  if (dict)
+    hipLaunchKernelGGL((btd_pair_down_dict_kernel<kPairM, kPairNSA, kPairNSB, kThreads>), dim3((unsigned)ntiles), dim3(kThreads),
+                       lds, ctx->stream, p, wa, wb, d);
+  else
+    hipLaunchKernelGGL((btd_pair_down_kernel<kPairM, kPairNSA, kPairNSB, kThreads>), dim3((unsigned)ntiles), dim3(kThreads), lds,
+                       ctx->stream, p, wa, wb);
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
@@ -2046,9 +2076,15 @@ static int launch_pair_up(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPost, doubl
   }
   if (ntiles == 0) return AGGMG_OK;
   const size_t lds = ((size_t)2 * (kPairTEA + 2) * kPairM + (size_t)kPairTEB * 2) * sizeof(double);
+  PairDict d;
+  const bool dict = part == 0 && pair_dictionary(p, d, a, b);   // (the element-partitioned cycle keeps the full arrays)
   ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
-  hipLaunchKernelGGL((btd_pair_up_kernel<kPairM, kPairNSA, kPairNSB, kThreads>), dim3((unsigned)ntiles), dim3(kThreads), lds,
-                     ctx->stream, p, wa, wb);
+  if (dict)
+    hipLaunchKernelGGL((btd_pair_up_dict_kernel<kPairM, kPairNSA, kPairNSB, kThreads>), dim3((unsigned)ntiles), dim3(kThreads),
+                       lds, ctx->stream, p, wa, wb, d);
+  else
+    hipLaunchKernelGGL((btd_pair_up_kernel<kPairM, kPairNSA, kPairNSB, kThreads>), dim3((unsigned)ntiles), dim3(kThreads), lds,
+                       ctx->stream, p, wa, wb);
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
@@ -2077,7 +2113,7 @@ extern "C" int aggmg_hier_level_dictionary(aggmg_ctx* ctx, const aggmg_hier* h, 
   if (!ctx || !h || !nclasses) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_dictionary: NULL argument");
   if (level < 0 || level >= (int)h->lv.size()) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_dictionary: level out of range");
   const Level& l = h->lv[level];
-  *nclasses = l.dict ? l.dict->nclasses : (l.cdict ? l.cdict->nclasses : 0);
+  *nclasses = l.dict ? l.dict->nclasses : (l.cdict ? l.cdict->nclasses : (l.pdict ? l.pdict->nclasses : 0));
   return AGGMG_OK;
 }
 

@@ -224,6 +224,19 @@ struct DictDev {
   bool lf_unit = false;      // lf holds the lf1 form
 };
 
+// operator dictionary of a level the two-level launches take (PairLevel::cls in pair_kernels.hpp; the same search as
+// DictDev's): one copy of every distinct record -- every operator word a pair kernel reads on behalf of the element,
+// [nclasses][...] in the layouts of the full arrays -- and the class of every element.  sback holds the sup rows of the
+// element before (zeros at the first one): what the kernels read as sup[e - 1].  The full arrays stay; the level's
+// launches on its own, the K-column, Gauss-Seidel and element-partitioned ones read them.
+struct PairDictDev {
+  int nclasses = 0;
+  DevArray<uint16_t> cls;    // [ne]
+  DevArray<double> bsym, sup, sback, sub, dblk;
+  DevArray<double> lf;       // [nclasses][2] second entries (the transfer has lf1), else [nclasses][2][2] rows of L
+  bool lf_unit = false;      // lf holds the lf1 form
+};
+
 // structured transfer of a CG chain level (CgtXfer in cgt_kernels.hpp)
 struct TransferCgt {
   int type = 0, mc = 0, rho = 1;
@@ -271,6 +284,7 @@ struct Level {
   std::unique_ptr<TransferCgt> tc;  // CG chain level: structured transfer to level k+1, or null
   std::unique_ptr<DictDev> dict;    // operator dictionary of the level's fused launches, or null
   std::unique_ptr<CgtDictDev> cdict;  // the same of a fused chain level's point-Jacobi launches, or null
+  std::unique_ptr<PairDictDev> pdict; // the same of the two-level launches that take the level, or null
   bool cgt_fused = false;           // the level runs cgt_fused_kernel (chain form + structured transfer)
   bool native_io = false;           // rhs and u[1] are kept in block order (the finer level is a fused chain level)
   int64_t Nalloc = 0;               // length of the level's vectors (ne * m for chain levels)
@@ -487,6 +501,9 @@ int setup_transfer_btd(aggmg_ctx* ctx, const aggmg_op* L, const BtdDev* Abtd, in
 // classes of identical per-element operator records of a fused level; *out stays null where the level does not take the
 // form: other block sizes / packings, agglomerates of different sizes, more than kDictMaxClasses distinct records
 int setup_op_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, std::unique_ptr<DictDev>* out);
+// the same for a level of the two-level launches (the caller has checked pair_level_ok: dense blocks of 2 rows, packed
+// inverses, two-mode transfer of equal agglomerates)
+int setup_pair_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, std::unique_ptr<PairDictDev>* out);
 // the same for a fused chain level: blocks of 1, 2 or 4 rows, point-Jacobi sweeps, chain or agglomerating transfer
 int setup_cgt_dictionary(aggmg_ctx* ctx, const CgtDev& g, const TransferCgt& t, std::unique_ptr<CgtDictDev>* out);
 // band_out (optional): max(i - j), max(j - i) over the stored entries -- what the host banded LU would have to store

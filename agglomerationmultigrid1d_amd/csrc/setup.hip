@@ -635,6 +635,29 @@ int setup_op_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, s
   return AGGMG_OK;
 }
 
+int setup_pair_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, std::unique_ptr<PairDictDev>* out) {
+  out->reset();
+  const int m = b.m;
+  // the levels of btd_pair_down_kernel / btd_pair_up_kernel: dense blocks of 2 rows, packed inverses, two modes on equal
+  // agglomerates
+  if (!(!b.cmp && m == 2 && b.bsym && b.sup && b.sub && b.dblk) || b.ne < 1) return AGGMG_OK;
+  if (!(t.rho > 0 && t.mc == 2 && t.lf)) return AGGMG_OK;
+  auto d = std::make_unique<PairDictDev>();
+  d->lf_unit = t.lf1 != nullptr;
+  // the record: bsym[e] (3), the rows of sup[e] (m*m), those of sup[e-1] (m*m; zeros at e = 0) in an array of its own
+  // (sback), the rows of sub[e] and dblk[e] (m*m each) and the element's rows of the transfer (lf1, or the rows of lf)
+  DictFields F(b.ne);
+  F.add(b.bsym, &d->bsym, m * (m + 1) / 2);
+  F.add(b.sup, &d->sup, m * m);
+  F.add(b.sup, &d->sback, m * m, true);
+  F.add(b.sub, &d->sub, m * m);
+  F.add(b.dblk, &d->dblk, m * m);
+  F.add(t.lf1 ? t.lf1 : t.lf, &d->lf, m * (t.lf1 ? 1 : 2));
+  CHECK(dict_build(ctx, F, &d->cls, &d->nclasses));
+  if (d->nclasses > 0) *out = std::move(d);
+  return AGGMG_OK;
+}
+
 int setup_cgt_dictionary(aggmg_ctx* ctx, const CgtDev& g, const TransferCgt& t, std::unique_ptr<CgtDictDev>* out) {
   out->reset();
   const int m = g.m;

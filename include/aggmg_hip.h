@@ -111,6 +111,12 @@ int aggmg_synchronize(aggmg_ctx* ctx);
  * when the sweeps are split over several launches, the partitioned cycle's local levels included -- index operator and
  * transfer by the block's class.  Checkpoint launches, element Schwarz and element Gauss-Seidel levels, other block
  * sizes, the K-column launches and the operator-level entries (aggmg_smooth, aggmg_residual) keep the full arrays.
+ * The levels the two-level launches take (AGGMG_OPT_PAIR_LEVELS: dense blocks of 2 rows, packed inverses, a two-mode
+ * transfer onto equal agglomerates; below the finest level) get a dictionary of their own: the record of an element is
+ * its packed inverse, its super-diagonal rows and the element before's, its sub-diagonal and diagonal rows and its rows
+ * of the transfer.  A two-level launch of a cycle indexes both levels by class when BOTH have a dictionary; the ascent
+ * of the element-partitioned cycle, the K-column and Gauss-Seidel launches and a level that runs on its own keep the
+ * full arrays.
  * Hierarchies created afterwards; aggmg_hier_level_dictionary reports the levels.  aggmg_hier_launch_bytes keeps
  * counting the full arrays (DESIGN.md sections 4 and 5). */
 #define AGGMG_OPT_OPERATOR_DICTIONARY 7
@@ -446,7 +452,8 @@ int aggmg_hier_level_paired_up(aggmg_ctx* ctx, const aggmg_hier* h, int level, i
 /* Whether level `level`'s fused kernel forms its explicit residual from the lossless symmetric form of the operator's
  * entries (AGGMG_OPT_SYMMETRIC_RESIDUAL): 1 when it was built at set-up, 0 otherwise. */
 int aggmg_hier_level_sym_residual(aggmg_ctx* ctx, const aggmg_hier* h, int level, int* on);
-/* Distinct operator records of the level's dictionary (AGGMG_OPT_OPERATOR_DICTIONARY); 0: the level has none and its
+/* Distinct operator records of the level's dictionary (AGGMG_OPT_OPERATOR_DICTIONARY; a fused level's, a chain level's
+ * or the one the two-level launches read); 0: the level has none and its
  * launches read the full arrays. */
 int aggmg_hier_level_dictionary(aggmg_ctx* ctx, const aggmg_hier* h, int level, int* nclasses);
 /* Sweep-weight schedule of a level (EXTENSION: the reference damps every sweep of every level by the same alpha,
