@@ -418,7 +418,8 @@ extern "C" int aggmg_smoother_is_structured(aggmg_ctx* ctx, const aggmg_smoother
   return AGGMG_OK;
 }
 
-static int cr_env_int_early(const char* name, int dflt) {
+// an integer tuning knob from the environment
+static int env_int(const char* name, int dflt) {
   const char* e = std::getenv(name);
   return e && *e ? std::atoi(e) : dflt;
 }
@@ -434,10 +435,10 @@ static int launch_csr(aggmg_ctx* ctx, const CsrDev& A, const double* x, const do
   // kernel's extra LDS and barrier make one sweep 121 us against 105 us; it pays from two sweeps per launch on)
   // every row short: one thread per row, no LDS staging -- AGGMG_CSR_ROWTHREAD=1 (the default until the stream kernel's
   // blocks were reshaped: 92 us against its 75 us on config 2's residual; kept for A/B runs, the same bits)
-  static const bool rowthread = cr_env_int_early("AGGMG_CSR_ROWTHREAD", 0) != 0;
+  static const bool rowthread = env_int("AGGMG_CSR_ROWTHREAD", 0) != 0;
   if (rowthread && A.maxrow >= 0 && A.maxrow <= kRowThreadMax && A.nrows < ((int64_t)1 << 31) * kThreads) {
     const unsigned nb = (unsigned)((A.nrows + kThreads - 1) / kThreads);
-    static const bool bandrow = cr_env_int_early("AGGMG_CSR_BANDROW", 1) != 0;
+    static const bool bandrow = env_int("AGGMG_CSR_BANDROW", 1) != 0;
     if (bandrow && A.bw >= 0 && A.bw <= kBandMaxBw && A.nrows == A.ncols && y != x)   // banded: the x window through LDS
       hipLaunchKernelGGL((csr_rowthread_band_kernel<MODE>), dim3(nb), dim3(kThreads), 0, ctx->stream, A.view(), A.bw, x, b, dg, alpha, y);
     else
@@ -544,7 +545,7 @@ static void xfer_in(FusedArgs& a, const TransferBtd& t) {
 // agglomerates of different sizes: the elements a tile may move to stand on an agglomerate boundary (-1: none)
 static int xfer_agg_shift(const TransferBtd& t) {
   // (AGGMG_AGG_ALIGN=0: the two-part atomic restriction for every size, as before r03)
-  static const int max_shift = cr_env_int_early("AGGMG_AGG_ALIGN", 1) ? 8 : -1;
+  static const int max_shift = env_int("AGGMG_AGG_ALIGN", 1) ? 8 : -1;
   return (!t.rho && t.maxagg >= 1 && t.maxagg - 1 <= max_shift) ? t.maxagg - 1 : -1;
 }
 static void xfer_out(FusedArgs& a, const TransferBtd& t) {
@@ -592,7 +593,7 @@ static int launch_btd_t(aggmg_ctx* ctx, FusedLaunch a, int halo, const TileSel& 
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: checkpoint launch of more tiles than its partial sums have room for");
   a.chk_tiles = ntiles;
   if (chk) {   // measurement aid (tools/exp_outer_loop.py): the checkpoint variant's code with no checkpoint ever due
-    static const int never = cr_env_int_early("AGGMG_CHK_NEVER", 0);
+    static const int never = env_int("AGGMG_CHK_NEVER", 0);
     if (never) {
       a.chk_sweep = 1 << 29;
       a.chk_final = 0;
@@ -843,7 +844,7 @@ static int generic_sweep(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const 
   CHECK(op_ensure_csr(ctx, A));
   // (AGGMG_BLOCK_SWEEP=0: the earlier form -- CSR residual, zeroed vector, batched block apply with atomic adds where the
   // lists overlap, update: four launches -- for A/B runs)
-  static const bool onepass = cr_env_int_early("AGGMG_BLOCK_SWEEP", 1) != 0;
+  static const bool onepass = env_int("AGGMG_BLOCK_SWEEP", 1) != 0;
   if (onepass && A->csr.maxrow >= 0 && A->csr.maxrow <= 4 * kRowThreadMax && sm->m <= kThreads) {
     // residual rows and block solves in ONE pass (block_sweep_kernel): the residual never reaches HBM
     const int bpw = kThreads / (int)sm->m;
@@ -1246,12 +1247,8 @@ static void banded_solve(const BandedLU& f, double* b) {
 // coarsest-level direct solve on the device: block cyclic reduction (factored once on the device,
 // setup_cr in setup.hip; solved per cycle here)
 // ---------------------------------------------------------------------------------------------
-static int cr_env_int(const char* name, int dflt) {
-  const char* e = std::getenv(name);
-  return e && *e ? std::atoi(e) : dflt;
-}
 static int cr_stage_threads() {
-  static const int t = std::min(std::max(cr_env_int("AGGMG_CR_THREADS", kCrThreads), 64), kCrThreads);
+  static const int t = std::min(std::max(env_int("AGGMG_CR_THREADS", kCrThreads), 64), kCrThreads);
   return t;
 }
 
@@ -1281,12 +1278,36 @@ static bool cr_fuse_tail() {
   return on;
 }
 
-static CrStageArgs cr_make_args(const CrDev& cr, const CrStage& S, bool tail) {
+// kc columns in h->crw, which cr_multi_workspace has laid out for h->crw_cols >= kc of them
+static CrRun cr_run_cols(const aggmg_hier* h, int kc) {
+  const CrDev& cr = h->cr;
+  std::vector<CrMultiStage> ws;
+  CrMultiStage wt;
+  cr_multi_layout(cr.st, cr.tail, cr.m, h->crw_cols, &ws, &wt);
+  double* const w = h->crw;
+  auto at = [&](int64_t stride, int64_t off) -> double* { return stride ? w + off : nullptr; };
+  CrRun run;
+  run.kc = kc;
+  run.st.reserve(ws.size());
+  for (const CrMultiStage& W : ws) {
+    double* const part = w + W.part_off;
+    run.st.push_back({part, part + W.part / 3, part + 2 * (W.part / 3), at(W.stack, W.stack_off), at(W.mid, W.mid_off), W.part,
+                      W.stack, W.mid});
+  }
+  run.tail.mid = at(wt.mid, wt.mid_off);
+  run.tail.cs_mid = wt.mid;
+  return run;
+}
+
+// the arguments of a launch of stage S (or the tail) on the run's entry R for it; what depends on where the stage's input
+// and output lie (cs_d, cs_x, dstride, ostride, c0) is the caller's
+enum CrKind { kCrForward = 0, kCrTail = 1, kCrBackward = 2 };   // (the tracing build's trace_kind)
+static CrStageArgs cr_make_args(const CrDev& cr, const CrStagePlan& S, const CrRunStage& R, CrKind kind) {
   CrStageArgs A;
   std::memset(&A, 0, sizeof(A));
 #ifdef AGGMG_CR_TRACE
   A.trace = g_cr_trace;
-  A.trace_kind = tail ? 1 : 0;
+  A.trace_kind = kind;
 #endif
   A.q = S.q;
   for (int l = 0; l < S.q; ++l) A.lv[l] = cr.lv[S.l0 + l];
@@ -1298,13 +1319,16 @@ static CrStageArgs cr_make_args(const CrDev& cr, const CrStage& S, bool tail) {
   }
   A.lds_total = S.lds_total;
   A.n_out = S.n_out;
-  A.stack = S.stack;
+  A.stack = R.stack;
   A.stack_stride = S.stack_stride;
-  A.mid = S.mid;
+  A.mid = R.mid;
   for (int s = 0; s <= kCrMaxSteps; ++s) A.mid_off[s] = S.mid_off[s];
-  A.tail = tail ? 1 : 0;
+  A.tail = kind == kCrTail ? 1 : 0;
   A.lu_last = cr.lu_last;
   A.perm_last = cr.perm_last;
+  A.cs_o = A.cs_xq = R.cs_part;
+  A.cs_stack = R.cs_stack;
+  A.cs_mid = R.cs_mid;
   return A;
 }
 
@@ -1342,189 +1366,134 @@ static void cr_launch_tail(aggmg_ctx* ctx, CrDev& cr, const CrStageArgs& T, size
   hipLaunchKernelGGL((cr_tail_kernel<M>), dim3(1, kc), dim3(kCrThreads), tail_lds, ctx->stream, T, d, db, x);
 }
 
-// Stages s0.. and the tail for the right-hand side d (+ db) of stage s0's input system into x:
-// forward launches stage by stage (the last one goes on to solve the tail system in its
-// last-arriving workgroup), then the back substitutions in reverse.
+// one launch of a stage's forward / backward kernel: chunks A.c0 .. A.c0 + grid of kc columns
+template <int M, bool FUSE_TAIL = false>
+static void cr_launch_forward(aggmg_ctx* ctx, const CrStageArgs& A, unsigned grid, int kc, const double* d, const double* db,
+                              double* partR, double* partL, const CrStageArgs& T, size_t tail_lds = 0, double* xt = nullptr,
+                              unsigned int* ticket = nullptr) {
+  hipLaunchKernelGGL((cr_stage_forward_kernel<M, FUSE_TAIL>), dim3(grid, kc), dim3(cr_stage_threads()),
+                     std::max((size_t)A.lds_total * sizeof(double), tail_lds), ctx->stream, A, d, db, partR, partL, T, xt, ticket);
+}
+template <int M>
+static void cr_launch_backward(aggmg_ctx* ctx, const CrStageArgs& A, unsigned grid, int kc, const double* d, const double* db,
+                               const double* xq, double* x) {
+  hipLaunchKernelGGL((cr_stage_backward_kernel<M>), dim3(grid, kc), dim3(cr_stage_threads()), (size_t)A.lds_total * sizeof(double),
+                     ctx->stream, A, d, db, xq, x);
+}
+
+// Stages s0.. and the tail for the right-hand sides d (+ db) of stage s0's input system into x, for the run's columns:
+// forward launches stage by stage, the tail system (AGGMG_CR_FUSE_TAIL=1, one column: in the last forward launch's
+// last-arriving workgroup), then the back substitutions in reverse.  Stage s0 reads and writes the caller's vectors, every
+// later stage the boundary system of the stage before it.
+// cs_in / cs_out: doubles between consecutive columns of d (db) / x
 // dstride: doubles between consecutive blocks of d / db (0 = M; 2 M: the chunk-interleaved boundary rows of an
 // element-partitioned run, gathered in place)
 template <int M>
-static int cr_solve_from(aggmg_ctx* ctx, CrDev& cr, int s0, const double* d, const double* db, double* x, int dstride = 0) {
-  const int ns = (int)cr.st.size();
-  CrStageArgs T = cr_make_args(cr, cr.tail, true);
-  if (s0 >= ns) T.dstride = dstride;
+static int cr_walk(aggmg_ctx* ctx, CrDev& cr, const CrRun& run, int s0, const double* d, const double* db, double* x,
+                   int64_t cs_in, int64_t cs_out, int dstride) {
+  const int ns = (int)cr.st.size(), kc = run.kc;
+  CrStageArgs T = cr_make_args(cr, cr.tail, run.tail, kCrTail);
   const size_t tail_lds = (size_t)cr.tail.lds_total * sizeof(double);
-  const bool fuse_tail = cr_fuse_tail();
   if (s0 >= ns) {
-    cr_launch_tail<M>(ctx, cr, T, tail_lds, d, db, x);
+    T.dstride = dstride;
+    T.cs_d = cs_in;
+    T.cs_x = cs_out;
+    cr_launch_tail<M>(ctx, cr, T, tail_lds, d, db, x, kc);
     HIPCHK(hipGetLastError());
     return AGGMG_OK;
   }
-  const double *din = d, *dinb = db;
+  struct Io {
+    const double *d, *db;
+    double* x;
+    int64_t cs_d, cs_x;
+    int dstride;
+  };
+  auto io = [&](int s) -> Io {
+    if (s == s0) return {d, db, x, cs_in, cs_out, dstride};
+    const CrRunStage& P = run.st[s - 1];
+    return {P.partR, P.partL, P.xq, P.cs_part, P.cs_part, 0};
+  };
+  const bool fuse_tail = kc == 1 && cr_fuse_tail();
   for (int s = s0; s < ns; ++s) {
-    const CrStage& S = cr.st[s];
-    CrStageArgs A = cr_make_args(cr, S, false);
-    if (s == s0) A.dstride = dstride;
-    const unsigned grid = (unsigned)std::max<int64_t>(S.n_out, 1);
-    const size_t lds = (size_t)S.lds_total * sizeof(double);
+    const CrRunStage& R = run.st[s];
+    const Io in = io(s);
+    CrStageArgs A = cr_make_args(cr, cr.st[s], R, kCrForward);
+    A.cs_d = in.cs_d;
+    A.dstride = in.dstride;
+    const unsigned grid = (unsigned)std::max<int64_t>(A.n_out, 1);
     if (s == ns - 1 && fuse_tail) {
-      hipLaunchKernelGGL((cr_stage_forward_kernel<M, true>), dim3(grid), dim3(cr_stage_threads()), std::max(lds, tail_lds),
-                         ctx->stream, A, din, dinb, S.partR, S.partL, T, S.xq, cr.ticket);
+      cr_launch_forward<M, true>(ctx, A, grid, kc, in.d, in.db, R.partR, R.partL, T, tail_lds, R.xq, cr.ticket);
     } else {
-      hipLaunchKernelGGL((cr_stage_forward_kernel<M, false>), dim3(grid), dim3(cr_stage_threads()), lds, ctx->stream, A, din,
-                         dinb, S.partR, S.partL, T, (double*)nullptr, (unsigned int*)nullptr);
-      if (s == ns - 1)
-        cr_launch_tail<M>(ctx, cr, T, tail_lds, (const double*)S.partR, (const double*)S.partL, S.xq);
+      cr_launch_forward<M>(ctx, A, grid, kc, in.d, in.db, R.partR, R.partL, T);
+      if (s == ns - 1) {
+        T.cs_d = T.cs_x = R.cs_part;
+        cr_launch_tail<M>(ctx, cr, T, tail_lds, R.partR, R.partL, R.xq, kc);
+      }
     }
-    din = S.partR;
-    dinb = S.partL;
   }
   for (int s = ns - 1; s >= s0; --s) {
-    const CrStage& S = cr.st[s];
-    CrStageArgs A = cr_make_args(cr, S, false);
-#ifdef AGGMG_CR_TRACE
-    A.trace_kind = 2;
-#endif
-    if (s == s0) A.dstride = dstride;
-    const unsigned grid = (unsigned)std::max<int64_t>(S.n_out, 1);
-    const double* ds = s == s0 ? d : cr.st[s - 1].partR;
-    const double* dsb = s == s0 ? db : cr.st[s - 1].partL;
-    double* xs = s == s0 ? x : cr.st[s - 1].xq;
-    hipLaunchKernelGGL((cr_stage_backward_kernel<M>), dim3(grid), dim3(cr_stage_threads()), (size_t)S.lds_total * sizeof(double),
-                       ctx->stream, A, ds, dsb, (const double*)S.xq, xs);
+    const Io in = io(s);
+    CrStageArgs A = cr_make_args(cr, cr.st[s], run.st[s], kCrBackward);
+    A.cs_d = in.cs_d;
+    A.cs_x = in.cs_x;
+    A.dstride = in.dstride;
+    cr_launch_backward<M>(ctx, A, (unsigned)std::max<int64_t>(A.n_out, 1), kc, in.d, in.db, run.st[s].xq, in.x);
   }
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
 
+// ---- stage 0 for the chunks of a block range alone (element-partitioned runs: every rank eliminates / back-substitutes
+// only the stage-0 chunks of its own blocks; the boundary system in between is gathered and solved redundantly: cr_walk
+// from stage 1).  The boundary rows are the caller's: partR / partL written (block stride ostride, 0 = M), xq read ------
 template <int M>
-static int cr_solve_t(aggmg_ctx* ctx, CrDev& cr, const double* rhs, double* out) {
-  const int64_t Npad = cr.n0 * M;
-  // without padding the caller's vectors are used in place (no staging copies)
-  const bool direct = (Npad == cr.N) && rhs != out;
-  if (direct) return cr_solve_from<M>(ctx, cr, 0, rhs, nullptr, out);
-  if (!cr.d0) {  // in-place call on an unpadded system: staging vectors on first use
-    for (DevArray<double>* p : {&cr.d0, &cr.x0}) CHECK(p->alloc(ctx, Npad));
-  }
-  double *d0 = cr.d0, *x0 = cr.x0;
-  if (Npad > cr.N) HIPCHK(hipMemsetAsync(d0 + cr.N, 0, (Npad - cr.N) * sizeof(double), ctx->stream));
-  HIPCHK(hipMemcpyAsync(d0, rhs, cr.N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  CHECK(cr_solve_from<M>(ctx, cr, 0, d0, nullptr, x0));
-  HIPCHK(hipMemcpyAsync(out, x0, cr.N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  return AGGMG_OK;
-}
-
-// ---- the three phases of the chunked solve, separately (element-partitioned runs: every rank
-// eliminates / back-substitutes only the stage-0 chunks of its own block range, the boundary system
-// is gathered and solved redundantly: later stages + tail) ---------------------------------------
-template <int M>
-static int cr_phase_t(aggmg_ctx* ctx, CrDev& cr, int phase, const double* d_owned, int64_t blk_lo, int64_t blk_hi,
-                      double* partR, double* partL, const double* xq, double* x_owned, int pstride) {
-  if (phase == 1)  // boundary system
-    return cr_solve_from<M>(ctx, cr, 1, partR, partL, const_cast<double*>(xq), pstride);
+static int cr_chunks(aggmg_ctx* ctx, CrDev& cr, bool backward, const double* d_owned, int64_t blk_lo, int64_t blk_hi,
+                     double* partR, double* partL, const double* xq, double* x_owned, int ostride) {
   const CrStage& S = cr.st[0];
-  CrStageArgs A = cr_make_args(cr, S, false);
-  A.ostride = pstride;
-  const int q = S.q;
-  A.c0 = blk_lo >> q;
-  const int64_t c1 = (blk_hi + ((int64_t)1 << q) - 1) >> q;
+  CrStageArgs A = cr_make_args(cr, S, cr_run_stage(S), backward ? kCrBackward : kCrForward);
+  A.ostride = ostride;
+  A.c0 = blk_lo >> S.q;
+  const int64_t c1 = (blk_hi + ((int64_t)1 << S.q) - 1) >> S.q;
   const unsigned grid = (unsigned)std::max<int64_t>(c1 - A.c0, 0);
   if (!grid) return AGGMG_OK;
   const double* d0 = d_owned - blk_lo * M;  // global block indexing; only owned blocks are touched
-  const size_t lds = (size_t)S.lds_total * sizeof(double);
-  if (phase == 0) {
+  if (backward) {
+    cr_launch_backward<M>(ctx, A, grid, 1, d0, nullptr, xq, x_owned - blk_lo * M);
+  } else {
     CrStageArgs T;
     std::memset(&T, 0, sizeof(T));
-    hipLaunchKernelGGL((cr_stage_forward_kernel<M, false>), dim3(grid), dim3(cr_stage_threads()), lds, ctx->stream, A, d0,
-                       (const double*)nullptr, partR, partL, T, (double*)nullptr, (unsigned int*)nullptr);
-  } else {
-#ifdef AGGMG_CR_TRACE
-    A.trace_kind = 2;
-#endif
-    hipLaunchKernelGGL((cr_stage_backward_kernel<M>), dim3(grid), dim3(cr_stage_threads()), lds, ctx->stream, A, d0,
-                       (const double*)nullptr, xq, x_owned - blk_lo * M);
+    cr_launch_forward<M>(ctx, A, grid, 1, d0, nullptr, partR, partL, T);
   }
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
 
-static int cr_phase(aggmg_ctx* ctx, CrDev& cr, int phase, const double* d_owned, int64_t blk_lo, int64_t blk_hi,
-                    double* partR, double* partL, const double* xq, double* x_owned, int pstride = 0) {
-  ProfScope ps(ctx, AGGMG_KIND_COARSE, 0);
+// f(std::integral_constant<int, M>) -> status, for the factorisation's block size
+template <class F>
+static int cr_with_m(aggmg_ctx* ctx, const CrDev& cr, F&& f) {
   switch (cr.m) {
 #define CASE(MM) \
   case MM:       \
-    return cr_phase_t<MM>(ctx, cr, phase, d_owned, blk_lo, blk_hi, partR, partL, xq, x_owned, pstride);
+    return f(std::integral_constant<int, MM>());
     CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
 #undef CASE
   }
   return fail(ctx, AGGMG_ERR_UNSUPPORTED, "cyclic reduction block size not instantiated");
 }
 
-static int cr_solve_blocks(aggmg_ctx* ctx, CrDev& cr, const double* rhs, double* out) {
-  switch (cr.m) {
-    case 1: return cr_solve_t<1>(ctx, cr, rhs, out);
-    case 2: return cr_solve_t<2>(ctx, cr, rhs, out);
-    case 3: return cr_solve_t<3>(ctx, cr, rhs, out);
-    case 4: return cr_solve_t<4>(ctx, cr, rhs, out);
-    case 5: return cr_solve_t<5>(ctx, cr, rhs, out);
-    case 6: return cr_solve_t<6>(ctx, cr, rhs, out);
-    case 7: return cr_solve_t<7>(ctx, cr, rhs, out);
-    case 8: return cr_solve_t<8>(ctx, cr, rhs, out);
-  }
-  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "cyclic reduction block size not instantiated");
+// phase 0: chunk forward, 1: boundary system, 2: chunk backward; pstride: block stride of partR / partL
+static int cr_phase(aggmg_ctx* ctx, CrDev& cr, int phase, const double* d_owned, int64_t blk_lo, int64_t blk_hi,
+                    double* partR, double* partL, const double* xq, double* x_owned, int pstride = 0) {
+  ProfScope ps(ctx, AGGMG_KIND_COARSE, 0);
+  return cr_with_m(ctx, cr, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    if (phase == 1) return cr_walk<M>(ctx, cr, cr.run, 1, partR, partL, const_cast<double*>(xq), 0, 0, pstride);
+    return cr_chunks<M>(ctx, cr, phase == 2, d_owned, blk_lo, blk_hi, partR, partL, xq, x_owned, pstride);
+  });
 }
 
-// rhs / out in the operator's numbering.  Element-chain order (cr.chain): one gather launch into the block-ordered d0
-// (padding rows 0), the reduction's launches, one scatter launch out of x0 -- rhs and out may be the same vector
-static int cr_solve(aggmg_ctx* ctx, CrDev& cr, const double* rhs, double* out, int level) {
-  ProfScope ps(ctx, AGGMG_KIND_COARSE, level);
-  if (!cr.chain) return cr_solve_blocks(ctx, cr, rhs, out);
-  const CgtDev& g = *cr.chain;
-  const int64_t Np = g.ne * g.m;
-  hipLaunchKernelGGL(cr_chain_gather_kernel<kCrThreads>, dim3((unsigned)((Np + kCrThreads - 1) / kCrThreads)), dim3(kCrThreads), 0,
-                     ctx->stream, rhs, (int64_t)0, (const int32_t*)g.perm, cr.d0.get(), (int64_t)0, Np);
-  CHECK(cr_solve_blocks(ctx, cr, cr.d0, cr.x0));
-  hipLaunchKernelGGL(cr_chain_scatter_kernel<kCrThreads>, dim3((unsigned)((g.N + kCrThreads - 1) / kCrThreads)), dim3(kCrThreads), 0,
-                     ctx->stream, (const double*)cr.x0, (int64_t)0, (const int32_t*)g.inv, out, (int64_t)0, g.N);
-  HIPCHK(hipGetLastError());
-  return AGGMG_OK;
-}
-
-
-// ---- the same solve for a group of kc columns in ONE launch sequence (EXTENSION: the K-column cycle's coarsest level)
-// Workgroup (chunk, col) of every launch runs what workgroup `chunk` of cr_solve_from's launch runs, on column col's
-// vectors (cr_kernels.hpp): the factors are shared, every per-solve buffer has a copy per column in h->crw.
-static int64_t cr_even(int64_t v) { return (v + 1) & ~(int64_t)1; }
-
-// doubles per column and (off) start of the stage's [cols][stride] regions in h->crw; -> doubles in all
-struct CrMultiStage {
-  int64_t part = 0, stack = 0, mid = 0;              // per column: partR | partL | xq, stack, mid
-  int64_t part_off = 0, stack_off = 0, mid_off = 0;
-};
-static int64_t cr_multi_layout(const CrDev& cr, int64_t cols, std::vector<CrMultiStage>* st, CrMultiStage* tail) {
-  int64_t o = 0;
-  st->assign(cr.st.size(), CrMultiStage());
-  auto region = [&](int64_t stride, int64_t* off) {
-    *off = o;
-    o += cols * stride;
-  };
-  for (size_t s = 0; s < cr.st.size(); ++s) {
-    const CrStage& S = cr.st[s];
-    CrMultiStage& W = (*st)[s];
-    W.part = 3 * ((S.n_out * cr.m + 31) & ~(int64_t)31);   // as set-up lays out the one-column vectors (setup_cr)
-    W.stack = S.stack ? cr_even((S.n_out + 1) * (int64_t)S.stack_stride) : 0;
-    W.mid = S.mid ? cr_even(S.mid_total) : 0;
-    region(W.part, &W.part_off);
-    region(W.stack, &W.stack_off);
-    region(W.mid, &W.mid_off);
-  }
-  *tail = CrMultiStage();
-  tail->mid = cr.tail.mid ? cr_even(cr.tail.mid_total) : 0;
-  region(tail->mid, &tail->mid_off);
-  return o;
-}
-
-// grown to the largest group asked for; a call with no more columns than before allocates nothing
+// the K-column buffers (cr_run_cols) and staging vectors: grown to the largest group asked for; a call with no more
+// columns than before allocates nothing
 static int cr_multi_workspace(aggmg_ctx* ctx, aggmg_hier* h, int64_t cols, bool staging) {
   const CrDev& cr = h->cr;
   if (h->crw_cols < cols) {
@@ -1532,7 +1501,7 @@ static int cr_multi_workspace(aggmg_ctx* ctx, aggmg_hier* h, int64_t cols, bool 
     h->crw_cols = 0;
     std::vector<CrMultiStage> st;
     CrMultiStage tail;
-    CHECK(h->crw.alloc(ctx, cr_multi_layout(cr, cols, &st, &tail), true));   // (partL[0] of every column is never written: stays zero)
+    CHECK(h->crw.alloc(ctx, cr_multi_layout(cr.st, cr.tail, cr.m, cols, &st, &tail), true));   // (partL[0] of every column is never written: stays zero)
     h->crw_cols = cols;
   }
   if (staging && h->crw_stage_cols < cols) {
@@ -1544,108 +1513,75 @@ static int cr_multi_workspace(aggmg_ctx* ctx, aggmg_hier* h, int64_t cols, bool 
   return AGGMG_OK;
 }
 
-// column j of X (leading dimension ldx) = cr_solve of column j of B (ldb), bit for bit, for 2 <= kc columns
+// the staging launches, rows x kc columns.  Element-chain order: the operator's numbering -> block order and back
+static dim3 cr_cols_grid(int64_t n, int kc) { return dim3((unsigned)((n + kCrThreads - 1) / kCrThreads), kc); }
+static void cr_chain_gather(aggmg_ctx* ctx, const CgtDev& g, int64_t n, int kc, const double* B, int64_t ldb, double* d0, int64_t sp) {
+  hipLaunchKernelGGL(cr_chain_gather_kernel<kCrThreads>, cr_cols_grid(n, kc), dim3(kCrThreads), 0, ctx->stream, B, ldb,
+                     (const int32_t*)g.perm, d0, sp, n);
+}
+static void cr_chain_scatter(aggmg_ctx* ctx, const CgtDev& g, int kc, const double* x0, int64_t sp, double* X, int64_t ldx) {
+  hipLaunchKernelGGL(cr_chain_scatter_kernel<kCrThreads>, cr_cols_grid(g.N, kc), dim3(kCrThreads), 0, ctx->stream, x0, sp,
+                     (const int32_t*)g.inv, X, ldx, g.N);
+}
+static void cr_cols_copy(aggmg_ctx* ctx, int64_t n, int kc, const double* src, int64_t ld_src, double* dst, int64_t ld_dst) {
+  hipLaunchKernelGGL(cr_cols_copy_kernel<kCrThreads>, cr_cols_grid(n, kc), dim3(kCrThreads), 0, ctx->stream, src, ld_src, dst, ld_dst, n);
+}
+
+// Column j < kc of X (leading dimension ldx) = the solve of column j of B (ldb), in the operator's numbering; one launch
+// sequence for the group (EXTENSION: the K-column cycle's coarsest level), every column with the bits of a one-column call
+// (which passes ldb = ldx = 0).  Workgroup (chunk, col) of every launch runs what workgroup `chunk` of a one-column launch
+// runs, on column col's vectors (cr_kernels.hpp).
+// The caller's columns are used in place unless the system is padded (N no multiple of M), B and X overlap (one column:
+// are the same vector), the blocks are in element-chain order, or a column of a group lies off the 16 bytes the kernels'
+// paired loads and stores assume of a vector.  Then the walk runs on block-ordered staging vectors with zero pad rows -- one column: cr.d0 / cr.x0, filled and
+// emptied by copies; a group: h->crw_stage, by one copy launch each way; chain order: by the gather / scatter launches.
 template <int M>
-static int cr_solve_multi_t(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int64_t ldb, double* X, int64_t ldx, int kc) {
+static int cr_solve_cols(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int64_t ldb, double* X, int64_t ldx, int kc) {
   CrDev& cr = h->cr;
   const int64_t Npad = cr.n0 * M;
-  // without padding the caller's columns are used in place, as cr_solve_t does -- where every column starts on the 16 bytes
-  // the kernels' paired loads and stores assume of a vector
-  const bool aligned = (((uintptr_t)B | (uintptr_t)X) & 15) == 0 && ldb % 2 == 0 && ldx % 2 == 0;
-  // (element-chain order: the staging vectors are the block-ordered columns, filled and emptied by the gather / scatter)
-  const bool direct = !cr.chain && Npad == cr.N && aligned && !(B < X + ((kc - 1) * ldx + cr.N) && X < B + ((kc - 1) * ldb + cr.N));
-  CHECK(cr_multi_workspace(ctx, h, kc, !direct));
-  std::vector<CrMultiStage> ws;
-  CrMultiStage wt;
-  cr_multi_layout(cr, h->crw_cols, &ws, &wt);
+  const bool aligned = kc == 1 || ((((uintptr_t)B | (uintptr_t)X) & 15) == 0 && ldb % 2 == 0 && ldx % 2 == 0);
+  const bool overlap = kc == 1 ? B == X : B < X + ((kc - 1) * ldx + cr.N) && X < B + ((kc - 1) * ldb + cr.N);
+  const bool direct = !cr.chain && Npad == cr.N && aligned && !overlap;
+  if (kc > 1) {
+    CHECK(cr_multi_workspace(ctx, h, kc, !direct));
+  } else if (!direct && !cr.d0) {  // in-place call on an unpadded system: staging vectors on first use
+    for (DevArray<double>* p : {&cr.d0, &cr.x0}) CHECK(p->alloc(ctx, Npad));
+  }
   const double* d = B;
   double* x = X;
   int64_t cs_in = ldb, cs_out = ldx;
   if (!direct) {
-    const int64_t sp = cr_even(Npad);
-    double* d0 = h->crw_stage;
-    x = h->crw_stage + h->crw_stage_cols * sp;
-    if (cr.chain)
-      hipLaunchKernelGGL(cr_chain_gather_kernel<kCrThreads>, dim3((unsigned)((Npad + kCrThreads - 1) / kCrThreads), kc), dim3(kCrThreads), 0,
-                         ctx->stream, B, ldb, (const int32_t*)cr.chain->perm, d0, sp, Npad);
-    else
-      hipLaunchKernelGGL(cr_cols_copy_kernel<kCrThreads>, dim3((unsigned)((cr.N + kCrThreads - 1) / kCrThreads), kc), dim3(kCrThreads), 0,
-                         ctx->stream, B, ldb, d0, sp, cr.N);
+    const int64_t sp = kc == 1 ? 0 : cr_even(Npad);
+    double* d0 = kc == 1 ? cr.d0.get() : h->crw_stage.get();
+    x = kc == 1 ? cr.x0.get() : h->crw_stage + h->crw_stage_cols * sp;
+    if (cr.chain) {
+      cr_chain_gather(ctx, *cr.chain, Npad, kc, B, ldb, d0, sp);
+    } else if (kc == 1) {
+      if (Npad > cr.N) HIPCHK(hipMemsetAsync(d0 + cr.N, 0, (Npad - cr.N) * sizeof(double), ctx->stream));
+      HIPCHK(hipMemcpyAsync(d0, B, cr.N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+      cr_cols_copy(ctx, cr.N, kc, B, ldb, d0, sp);
+    }
     d = d0;
     cs_in = cs_out = sp;
   }
-  const int ns = (int)cr.st.size();
-  CrStageArgs T = cr_make_args(cr, cr.tail, true);
-  T.mid = wt.mid ? h->crw + wt.mid_off : nullptr;
-  T.cs_mid = wt.mid;
-  const size_t tail_lds = (size_t)cr.tail.lds_total * sizeof(double);
-  auto stage_args = [&](int s) {
-    const CrStage& S = cr.st[s];
-    const CrMultiStage& W = ws[s];
-    CrStageArgs A = cr_make_args(cr, S, false);
-    A.stack = W.stack ? h->crw + W.stack_off : nullptr;
-    A.cs_stack = W.stack;
-    A.mid = W.mid ? h->crw + W.mid_off : nullptr;
-    A.cs_mid = W.mid;
-    A.cs_d = s == 0 ? cs_in : ws[s - 1].part;
-    return A;
-  };
-  auto partR = [&](int s) { return h->crw + ws[s].part_off; };
-  auto partL = [&](int s) { return h->crw + ws[s].part_off + ws[s].part / 3; };
-  auto xq = [&](int s) { return h->crw + ws[s].part_off + 2 * (ws[s].part / 3); };
-  if (ns == 0) {
-    T.cs_d = cs_in;
-    T.cs_x = cs_out;
-    cr_launch_tail<M>(ctx, cr, T, tail_lds, d, nullptr, x, kc);
-  } else {
-    const double *din = d, *dinb = nullptr;
-    for (int s = 0; s < ns; ++s) {
-      CrStageArgs A = stage_args(s);
-      A.cs_o = ws[s].part;
-      const unsigned grid = (unsigned)std::max<int64_t>(cr.st[s].n_out, 1);
-      hipLaunchKernelGGL((cr_stage_forward_kernel<M, false>), dim3(grid, kc), dim3(cr_stage_threads()),
-                         (size_t)cr.st[s].lds_total * sizeof(double), ctx->stream, A, din, dinb, partR(s), partL(s), T,
-                         (double*)nullptr, (unsigned int*)nullptr);
-      din = partR(s);
-      dinb = partL(s);
-    }
-    T.cs_d = T.cs_x = ws[ns - 1].part;
-    cr_launch_tail<M>(ctx, cr, T, tail_lds, (const double*)partR(ns - 1), (const double*)partL(ns - 1), xq(ns - 1), kc);
-    for (int s = ns - 1; s >= 0; --s) {
-      CrStageArgs A = stage_args(s);
-#ifdef AGGMG_CR_TRACE
-      A.trace_kind = 2;
-#endif
-      A.cs_xq = ws[s].part;
-      A.cs_x = s == 0 ? cs_out : ws[s - 1].part;
-      const unsigned grid = (unsigned)std::max<int64_t>(cr.st[s].n_out, 1);
-      const double* ds = s == 0 ? d : partR(s - 1);
-      const double* dsb = s == 0 ? nullptr : partL(s - 1);
-      double* xs = s == 0 ? x : xq(s - 1);
-      hipLaunchKernelGGL((cr_stage_backward_kernel<M>), dim3(grid, kc), dim3(cr_stage_threads()),
-                         (size_t)cr.st[s].lds_total * sizeof(double), ctx->stream, A, ds, dsb, (const double*)xq(s), xs);
-    }
+  CrRun cols;
+  if (kc > 1) cols = cr_run_cols(h, kc);
+  CHECK(cr_walk<M>(ctx, cr, kc == 1 ? cr.run : cols, 0, d, nullptr, x, cs_in, cs_out, 0));
+  if (cr.chain) {
+    cr_chain_scatter(ctx, *cr.chain, kc, x, cs_out, X, ldx);
+  } else if (!direct && kc == 1) {
+    HIPCHK(hipMemcpyAsync(X, x, cr.N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  } else if (!direct) {
+    cr_cols_copy(ctx, cr.N, kc, x, cs_out, X, ldx);
   }
-  if (cr.chain)
-    hipLaunchKernelGGL(cr_chain_scatter_kernel<kCrThreads>, dim3((unsigned)((cr.chain->N + kCrThreads - 1) / kCrThreads), kc),
-                       dim3(kCrThreads), 0, ctx->stream, (const double*)x, cs_out, (const int32_t*)cr.chain->inv, X, ldx, cr.chain->N);
-  else if (!direct)
-    hipLaunchKernelGGL(cr_cols_copy_kernel<kCrThreads>, dim3((unsigned)((cr.N + kCrThreads - 1) / kCrThreads), kc), dim3(kCrThreads), 0,
-                       ctx->stream, (const double*)x, cs_out, X, ldx, cr.N);
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
 
-static int cr_solve_multi(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int64_t ldb, double* X, int64_t ldx, int kc, int level) {
-  ProfScope ps(ctx, AGGMG_KIND_COARSE, level);
-  switch (h->cr.m) {
-#define CASE(MM) \
-  case MM:       \
-    return cr_solve_multi_t<MM>(ctx, h, B, ldb, X, ldx, kc);
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-#undef CASE
-  }
-  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "cyclic reduction block size not instantiated");
+static int cr_solve(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int64_t ldb, double* X, int64_t ldx, int kc) {
+  ProfScope ps(ctx, AGGMG_KIND_COARSE, (int)h->lv.size() - 1);
+  return cr_with_m(ctx, h->cr, [&](auto m) { return cr_solve_cols<decltype(m)::value>(ctx, h, B, ldb, X, ldx, kc); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1686,7 +1622,7 @@ static int coarse_accept(aggmg_ctx* ctx, aggmg_hier* h) {
       double nd = 0.0, nr = 0.0;
       CHECK(setup_probe_vector(ctx, Nc, lc.u[1]));
       CHECK(product(lc.u[1], lc.rhs));                                          // d = A w (deterministic gather)
-      CHECK(cr_solve(ctx, h->cr, lc.rhs, lc.u[0], nlv - 1));                // x = CR(d)
+      CHECK(cr_solve(ctx, h, lc.rhs, 0, lc.u[0], 0, 1));                        // x = CR(d)
       CHECK(residual(lc.u[0], lc.rhs, lc.tmp));                                 // r = d - A x
       CHECK(aggmg_norm2_dev(ctx, lc.rhs, Nc, &nd));
       CHECK(aggmg_norm2_dev(ctx, lc.tmp, Nc, &nr));
@@ -1714,7 +1650,7 @@ static int coarse_accept(aggmg_ctx* ctx, aggmg_hier* h) {
       auto smooth_residual = [&](double* res) -> int {
         double nd = 0.0, nr = 0.0;
         CHECK(setup_smooth_vector(ctx, Nc, lc.rhs));
-        CHECK(cr_solve(ctx, h->cr, lc.rhs, lc.u[0], nlv - 1));
+        CHECK(cr_solve(ctx, h, lc.rhs, 0, lc.u[0], 0, 1));
         CHECK(residual(lc.u[0], lc.rhs, lc.tmp));
         CHECK(aggmg_norm2_dev(ctx, lc.rhs, Nc, &nd));
         CHECK(aggmg_norm2_dev(ctx, lc.tmp, Nc, &nr));
@@ -1916,7 +1852,7 @@ extern "C" int aggmg_hier_create(aggmg_ctx* ctx, int nlevels, aggmg_op* const* s
 }
 
 static int coarse_solve(aggmg_ctx* ctx, aggmg_hier* h, const double* rhs_dev, double* u_dev) {
-  if (h->cr.valid) return cr_solve(ctx, h->cr, rhs_dev, u_dev, (int)h->lv.size() - 1);
+  if (h->cr.valid) return cr_solve(ctx, h, rhs_dev, 0, u_dev, 0, 1);
   const int64_t n = h->coarse.n;
   HIPCHK(hipMemcpyAsync(h->h_coarse.data(), rhs_dev, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1932,7 +1868,7 @@ static int coarse_solve(aggmg_ctx* ctx, aggmg_hier* h, const double* rhs_dev, do
 // column by column on the host banded LU, under AGGMG_CR_FUSE_TAIL=1 (its ticket counts the chunks of one solve) and for
 // a group of one -- the same bits either way
 static int coarse_solve_multi(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int64_t ldb, double* X, int64_t ldx, int kc) {
-  if (h->cr.valid && kc > 1 && !cr_fuse_tail()) return cr_solve_multi(ctx, h, B, ldb, X, ldx, kc, (int)h->lv.size() - 1);
+  if (h->cr.valid && kc > 1 && !cr_fuse_tail()) return cr_solve(ctx, h, B, ldb, X, ldx, kc);
   for (int j = 0; j < kc; ++j) CHECK(coarse_solve(ctx, h, B + j * ldb, X + j * ldx));
   return AGGMG_OK;
 }
@@ -2369,7 +2305,7 @@ extern "C" int aggmg_vcycle_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0,
 // vectors, src/solvers.jl:19,63,84) ------------------------------------------------------------------------------
 // The columns go in groups of at most kMultiKB; every non-coarsest level runs ONE btd_multi_kernel launch per group
 // on the way down and one on the way up (no two-level launches here), and the coarsest solve one launch sequence per
-// group (cr_solve_multi).  A hierarchy with a level outside the kernel's coverage runs the single-column cycle on every
+// group (cr_solve).  A hierarchy with a level outside the kernel's coverage runs the single-column cycle on every
 // column instead (a one-level hierarchy, whose cycle is the coarsest solve alone, still in groups): the same bits either
 // way (multi_kernels.hpp), aggmg_hier_multi_info says which.
 #ifndef AGGMG_MULTI_KB
@@ -3155,11 +3091,14 @@ extern "C" int aggmg_hier_coarse_tail(aggmg_ctx* ctx, const aggmg_hier* h, int* 
 }
 
 // ---- chunked coarsest solve, phase by phase (multi-GPU driver) --------------------------------
+// can the stage-0 chunks of a block range be run alone?  (chain order: the blocks are not ranges of the operator's rows)
+static bool cr_chunked_plan(const CrDev& cr) { return cr.valid && !cr.st.empty() && cr.n0 * cr.m == cr.N && !cr.chain; }
+
 extern "C" int aggmg_coarse_plan(aggmg_ctx* ctx, const aggmg_hier* h, int* chunk_log2, int64_t* n_boundary,
                                  int* block_size, int64_t* n_blocks) {
   if (!ctx || !h) return AGGMG_ERR_ARGUMENT;
   const CrDev& cr = h->cr;
-  const bool ok = cr.valid && !cr.st.empty() && cr.n0 * cr.m == cr.N && !cr.chain;   // (chain order: the blocks are not ranges of the operator's rows)
+  const bool ok = cr_chunked_plan(cr);
   if (chunk_log2) *chunk_log2 = ok ? cr.st[0].q : -1;
   if (n_boundary) *n_boundary = ok ? cr.st[0].n_out : 0;
   if (block_size) *block_size = cr.valid ? cr.m : 0;
@@ -3171,7 +3110,7 @@ static int coarse_phase_check(aggmg_ctx* ctx, aggmg_hier* h, int64_t blk_lo, int
   if (!ctx) return AGGMG_ERR_ARGUMENT;
   if (!h) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_coarse_*: NULL hierarchy");
   const CrDev& cr = h->cr;
-  if (!(cr.valid && !cr.st.empty() && cr.n0 * cr.m == cr.N && !cr.chain))
+  if (!cr_chunked_plan(cr))
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_coarse_*: this hierarchy has no chunked cyclic-reduction plan");
   const int64_t mask = ((int64_t)1 << cr.st[0].q) - 1;
   if (blk_lo < 0 || blk_hi > cr.n0 || blk_lo > blk_hi || (blk_lo & mask) || ((blk_hi & mask) && blk_hi != cr.n0))

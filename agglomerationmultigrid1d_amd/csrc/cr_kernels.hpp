@@ -33,7 +33,9 @@
 // K right-hand sides (EXTENSION, the K-column cycle's coarsest level): every launch takes the column from blockIdx.y.
 // Workgroup (chunk, col) runs what workgroup `chunk` runs for one column, on column col's vectors -- the factors are
 // shared, the per-solve buffers are addressed with per-column strides from the launch arguments (CrStageArgs::cs_*,
-// PcrArgs::cs_*) -- so a group of columns costs the launches of one and every column keeps its bits.
+// PcrArgs::cs_*) -- so a group of columns costs the launches of one and every column keeps its bits.  The host walks the
+// stages once for any number of columns (cr_walk, aggmg_hip.hip): where a run's buffers lie and how far apart its columns
+// are is its CrRun, from which cr_make_args sets the pointers and the cs_* strides.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

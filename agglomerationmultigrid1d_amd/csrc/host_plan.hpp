@@ -122,6 +122,53 @@ inline bool cr_plan_solve(const std::vector<int64_t>& level_n, int m, int tail_r
   return true;
 }
 
+// What one right-hand side needs of a stage besides the shared factors, in doubles: `part` = each of the three boundary
+// vectors partR | partL | xq (n_out blocks, rounded up to 32 doubles: they share an allocation and each starts on 256
+// bytes), the per-chunk stack (n_out + 1 chunks) and mid.  The tail takes mid alone.
+struct CrStageBuffers {
+  int64_t part = 0, stack = 0, mid = 0;
+};
+inline CrStageBuffers cr_stage_buffers(const CrStagePlan& S, int m) {
+  CrStageBuffers b;
+  b.part = (S.n_out * m + 31) & ~(int64_t)31;
+  b.stack = S.stack_stride > 0 ? (S.n_out + 1) * (int64_t)S.stack_stride : 0;
+  b.mid = S.mid_total;
+  return b;
+}
+
+// The same buffers for a group of columns in ONE allocation: per stage the regions [cols][part] (partR | partL | xq of a
+// column side by side), [cols][stack], [cols][mid], then the tail's [cols][mid]; every per-column stride even, so that
+// every column starts on the 16 bytes the kernels' paired loads assume.  Stage: CrStagePlan or a type derived from it.
+inline int64_t cr_even(int64_t v) { return (v + 1) & ~(int64_t)1; }
+struct CrMultiStage {
+  int64_t part = 0, stack = 0, mid = 0;              // doubles per column
+  int64_t part_off = 0, stack_off = 0, mid_off = 0;  // start of the region
+};
+template <class Stage>
+inline int64_t cr_multi_layout(const std::vector<Stage>& stages, const CrStagePlan& tail_plan, int m, int64_t cols,
+                               std::vector<CrMultiStage>* st, CrMultiStage* tail) {
+  int64_t o = 0;
+  auto region = [&](int64_t stride, int64_t* off) {
+    *off = o;
+    o += cols * stride;
+  };
+  st->assign(stages.size(), CrMultiStage());
+  for (size_t s = 0; s < stages.size(); ++s) {
+    const CrStageBuffers b = cr_stage_buffers(stages[s], m);
+    CrMultiStage& W = (*st)[s];
+    W.part = 3 * b.part;
+    W.stack = cr_even(b.stack);
+    W.mid = cr_even(b.mid);
+    region(W.part, &W.part_off);
+    region(W.stack, &W.stack_off);
+    region(W.mid, &W.mid_off);
+  }
+  *tail = CrMultiStage();
+  tail->mid = cr_even(cr_stage_buffers(tail_plan, m).mid);
+  region(tail->mid, &tail->mid_off);
+  return o;
+}
+
 // ---- generic CSR kernels: row blocks -------------------------------------------------------------------------------
 // csr_stream_kernel: runs of consecutive rows holding at most max_nnz entries and at most max_rows rows; a row longer
 // than max_nnz stands alone (the kernel reduces it across the workgroup).  -> block boundaries, blocks + 1 entries

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kernels.hpp"
@@ -314,6 +315,20 @@ struct CrStage : CrStagePlan {    // the host-side plan (host_plan.hpp) + the st
   DevArray<double> mid;         // per step and sub-chunk: reduced right-hand sides of the inner sub-levels' odd rows
 };
 
+// Where one solve's launches read and write: per stage and for the tail the per-solve buffers and the doubles between
+// consecutive columns of each (the factors are shared; partR / partL / xq of a stage share a stride)
+struct CrRunStage {
+  double *partR = nullptr, *partL = nullptr, *xq = nullptr, *stack = nullptr, *mid = nullptr;
+  int64_t cs_part = 0, cs_stack = 0, cs_mid = 0;
+};
+struct CrRun {
+  int kc = 1;   // columns: blockIdx.y of every launch
+  std::vector<CrRunStage> st;
+  CrRunStage tail;   // mid alone
+};
+// one column in the buffers set-up allocated: every column stride 0
+inline CrRunStage cr_run_stage(const CrStage& S) { return {S.partR, S.partL, S.xq, S.stack, S.mid}; }
+
 struct CrDev {
   bool valid = false;
   int m = 0;
@@ -329,6 +344,7 @@ struct CrDev {
   const int32_t* perm_last = nullptr;
   std::vector<CrStage> st;      // chunk stages ...
   CrStage tail;                 // ... then the remaining levels in one workgroup
+  CrRun run;                    // one column in the buffers of st and tail (set-up fills it in)
   DevArray<double> d0, x0;              // staging for padded systems (N not a multiple of m) / in-place calls / chain order
   // element-chain order (AGGMG_COARSE_DEVICE_CHAIN, setup_cr_chain): the blocks are those of this chain form, N = ne * m is
   // the length of the BLOCK-ordered vectors, and a solve gathers its right-hand side through chain->perm into d0 and
@@ -367,7 +383,7 @@ struct aggmg_hier {
   // side (mu[k][2], levels >= 1); the coarsest level's solution goes to mu[n-1][0]
   std::vector<std::array<DevArray<double>, 3>> mu;
   int64_t multi_cols = 0;
-  // the coarsest solve of a column group in one launch sequence (cr_solve_multi; lazy, grown like mu): per column of the
+  // the coarsest solve of a column group in one launch sequence (cr_run_cols; lazy, grown like mu): per column of the
   // group what a CrStage holds for one (partR / partL / xq, stack, mid of every stage, the tail's mid) in ONE zeroed
   // allocation, and -- only when a call needs them -- the padded staging vectors d0 / x0 of every column in another
   DevArray<double> crw;

@@ -1007,16 +1007,16 @@ static int cr_factor_blocks(aggmg_ctx* ctx, CrDev* cr, DevArray<double> a, DevAr
   for (const CrStagePlan& P : plan.stages) {
     CrStage S;
     static_cast<CrStagePlan&>(S) = P;
-    const int64_t nb = (S.n_out * m + 31) & ~(int64_t)31;  // the three boundary vectors in one allocation
-    CHECK(dz(3 * nb, &S.partR));
-    S.partL = S.partR + nb;  // partL[0] is never written: stays zero
-    S.xq = S.partL + nb;
-    if (S.stack_stride > 0) CHECK(dz((S.n_out + 1) * (int64_t)S.stack_stride, &S.stack));
-    if (S.mid_total > 0) CHECK(dz(S.mid_total, &S.mid));
+    const CrStageBuffers b = cr_stage_buffers(P, m);
+    CHECK(dz(3 * b.part, &S.partR));  // the three boundary vectors in one allocation
+    S.partL = S.partR + b.part;       // partL[0] is never written: stays zero
+    S.xq = S.partL + b.part;
+    if (b.stack > 0) CHECK(dz(b.stack, &S.stack));
+    if (b.mid > 0) CHECK(dz(b.mid, &S.mid));
     cr->st.push_back(std::move(S));
   }
   static_cast<CrStagePlan&>(cr->tail) = plan.tail;
-  if (cr->tail.mid_total > 0) CHECK(dz(cr->tail.mid_total, &cr->tail.mid));
+  if (const int64_t mid = cr_stage_buffers(plan.tail, m).mid; mid > 0) CHECK(dz(mid, &cr->tail.mid));
   // The small levels (the tail and the last steps of the stage before it) are worked through by a
   // few threads, one dependent step after the other: their factors go into ONE allocation, so that a
   // step touches a couple of pages instead of four arrays per level each on a page of its own -- an
@@ -1078,6 +1078,9 @@ static int cr_factor_blocks(aggmg_ctx* ctx, CrDev* cr, DevArray<double> a, DevAr
   }
   CHECK(cr->ticket.alloc(ctx, 1, true));
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  cr->run = CrRun();
+  for (const CrStage& S : cr->st) cr->run.st.push_back(cr_run_stage(S));
+  cr->run.tail = cr_run_stage(cr->tail);
   cr->valid = true;
   return AGGMG_OK;
 }

@@ -87,6 +87,59 @@ static void test_cr_plans() {
         }
 }
 
+// the per-solve buffers of a plan: one column as set-up allocates them, a group of columns in one allocation
+static void test_cr_buffers() {
+  struct Case {
+    int64_t n0;
+    int m, tail_rows, max_q, stages;   // stages < 0: whatever the planner gives, at least one
+  };
+  const Case cases[] = {{4096, 2, 4096, 12, 1},            // one stage + tail
+                        {1000, 1, 4096, 12, 0},            // tail only
+                        {4096, 1, 16, 3, 3},               // three stages
+                        {3000, 3, 4096, 12, 1},            // a block count that is no power of two
+                        {5000, 3, 16, 3, -1},       {(1 << 14) + 7, 2, 32, 4, -1}, {1 << 15, 1, 64, 5, -1},
+                        {5000, 8, 16, 3, -1},       {(1 << 16) + 1, 8, 4096, 12, -1}};
+  for (const Case& c : cases) {
+    std::vector<int64_t> ln;
+    for (int64_t n = c.n0; n > 1; n = (n + 1) / 2) ln.push_back(n);
+    CrSolvePlan P;
+    EXPECT(cr_plan_solve(ln, c.m, c.tail_rows, c.max_q, 12, 256, &P));
+    EXPECT(c.stages < 0 ? !P.stages.empty() : (int)P.stages.size() == c.stages);
+    const int64_t m = c.m;
+    // one column: the expressions set-up allocated by before there was a function for them
+    for (const CrStagePlan& S : P.stages) {
+      const CrStageBuffers b = cr_stage_buffers(S, c.m);
+      EXPECT(b.part == ((S.n_out * m + 31) & ~(int64_t)31));
+      EXPECT(b.part >= S.n_out * m && b.part % 32 == 0);
+      EXPECT(b.stack == (S.stack_stride > 0 ? (S.n_out + 1) * (int64_t)S.stack_stride : 0));
+      EXPECT(b.mid == S.mid_total);
+    }
+    EXPECT(cr_stage_buffers(P.tail, c.m).mid == P.tail.mid_total);
+    // a group: regions back to back in the order part, stack, mid of every stage, then the tail's mid; every per-column
+    // stride even and large enough for the column's buffer
+    for (int64_t cols : {1, 3, 8}) {
+      std::vector<CrMultiStage> st;
+      CrMultiStage tail;
+      const int64_t total = cr_multi_layout(P.stages, P.tail, c.m, cols, &st, &tail);
+      EXPECT(st.size() == P.stages.size());
+      int64_t o = 0;
+      auto region = [&](int64_t stride, int64_t off, int64_t need) {
+        EXPECT(off == o && stride % 2 == 0 && stride >= need && stride <= need + 1);
+        o += cols * stride;
+      };
+      for (size_t s = 0; s < st.size() && s < P.stages.size(); ++s) {
+        const CrStagePlan& S = P.stages[s];
+        region(st[s].part, st[s].part_off, 3 * ((S.n_out * m + 31) & ~(int64_t)31));
+        region(st[s].stack, st[s].stack_off, S.stack_stride > 0 ? (S.n_out + 1) * (int64_t)S.stack_stride : 0);
+        region(st[s].mid, st[s].mid_off, S.mid_total);
+      }
+      EXPECT(tail.part == 0 && tail.stack == 0);
+      region(tail.mid, tail.mid_off, P.tail.mid_total);
+      EXPECT(o == total);
+    }
+  }
+}
+
 static void test_lds_cap() {
   EXPECT(cr_max_stage_levels(1) == 12 && cr_max_stage_levels(2) == 12 && cr_max_stage_levels(4) == 12);
   for (int m = 5; m <= 8; ++m) EXPECT(cr_max_stage_levels(m) == 11);   // 2^12-block chunks would ask for 164 ... 262 KB
@@ -488,6 +541,7 @@ static void test_chunk_route() {
 
 int main() {
   test_cr_plans();
+  test_cr_buffers();
   test_lds_cap();
   test_row_blocks();
   test_tile_subsets();

@@ -1,4 +1,4 @@
-"""The coarsest direct solve of a column group in one launch sequence (cr_solve_multi in csrc/aggmg_hip.hip, the column
+"""The coarsest direct solve of a column group in one launch sequence (cr_solve_cols / cr_walk in csrc/aggmg_hip.hip, the column
 dimension of csrc/cr_kernels.hpp; C ABI aggmg_hier_coarse_solve_multi_dev; EXTENSION: the reference's `A_n \\ rhs_n`,
 src/solvers.jl:39, takes one vector per cycle).  The contract is bitwise: column j of the batched solve is the single-column
 solve of column j -- every column keeps the single-column arithmetic, only the launches are shared -- on every path of the
@@ -10,6 +10,8 @@ dimensions N, N + 3 (columns off the 16-byte grid: staged) and N + 4 (in place),
 Through the public solvers on a 65536-element hierarchy (its coarsest system, 4096 blocks of 2, has a stage):
 multigrid_v_cycle, pcg and multigrid on K = 8 columns against the single-vector calls, and the profiler's launch-scope count:
 ONE (coarse, level) scope per group of a K-column cycle, where the column loop opened one per column."""
+import ctypes
+
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -207,6 +209,56 @@ def test_host_banded_lu_stays_column_by_column(mg, ctx, oracle):
         x = ctx.alloc(N)
         H.vcycle_dev(z, ctx.to_device(B[:, j]), x, 0, 0, 1.0)
         assert np.array_equal(X[:, j], x.download()), j
+    H.free()
+
+
+def _stage0_plan(mg, ctx, A):
+    """(log2 chunk, blocks of stage 0's boundary system) of the one-level hierarchy of A, through aggmg_coarse_plan"""
+    from agglomerationmultigrid1d_amd import _lib
+    H = mg.MeshHierarchy(None, [mg.DeviceOperator(A, _lib.OP_STIFFNESS, ctx)], [], [], ctx=ctx, keep_host=False,
+                         coarse_mode=_lib.COARSE_DEVICE_CR)
+    q, nq, mb, nblk = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int64(0)
+    ctx.check(ctx.lib.aggmg_coarse_plan(ctx.handle, H.handle, ctypes.byref(q), ctypes.byref(nq), ctypes.byref(mb),
+                                        ctypes.byref(nblk)))
+    return H, q.value, nq.value
+
+
+@pytest.mark.parametrize("nb,m,tail_rows,max_q,ragged", [(1 << 15, 1, 64, 5, 0), ((1 << 14) + 7, 2, 32, 4, 1), (5000, 3, 16, 3, 0)])
+def test_batched_solve_on_a_several_stage_plan(mg, ctx, oracle, monkeypatch, nb, m, tail_rows, max_q, ragged):
+    """the plans of tests/test_gpu_coarse_cr.py::test_cr_several_stages (the boundary system of one chunk stage is the input
+    of the next; the knobs shrink tail and chunks so that a small system takes such a plan), for a group of columns: every
+    later stage reads and writes the K-column work space with its per-column strides.  ragged: one trailing row dropped, the
+    group goes through the padded staging vectors.  K = 3, ld = N (in place where the system is not padded) and ld = N + 3
+    (every other column off the 16 bytes: staged): every column bitwise the single-column solve, gap rows untouched"""
+    monkeypatch.setenv("AGGMG_CR_TAIL_ROWS", str(tail_rows))
+    monkeypatch.setenv("AGGMG_CR_MAX_Q", str(max_q))
+    A = block_tridiag(nb, m, seed=nb + m, ragged=ragged)
+    N, K = A.shape[0], 3
+    H, q, nq = _stage0_plan(mg, ctx, A)
+    if ragged:
+        # aggmg_coarse_plan reports the chunks of a system whose blocks are all complete (the partitioned phases take no
+        # other); the plan itself depends on the block count, the block size and the knobs alone: ask the complete system
+        assert q == -1
+        Hfull, q, nq = _stage0_plan(mg, ctx, block_tridiag(nb, m, seed=nb + m))
+        Hfull.free()
+    assert 0 < q <= max_q and nq * m > tail_rows          # more than one stage
+    info = H.coarse_info()
+    assert info["on_device"] and info["block_size"] == m and (N + m - 1) // m == nb, info
+    B = _rhs(oracle, N)[:, :K]
+    z = ctx.to_device(np.zeros(N))
+    ref = np.empty((N, K))
+    for j in range(K):
+        x = ctx.alloc(N)
+        H.vcycle_dev(z, ctx.to_device(B[:, j]), x, 0, 0, 1.0)
+        ref[:, j] = x.download()
+    for ld in (N, N + 3):
+        dB = _upload(ctx, B, ld)
+        dX = ctx.to_device(np.full(ld * K, np.nan))
+        H.coarse_solve_multi_dev(dB, dX, K, ld)
+        got = dX.download().reshape((ld, K), order="F")
+        for j in range(K):
+            assert np.array_equal(got[:N, j], ref[:, j]), (ld - N, j, float(np.max(np.abs(got[:N, j] - ref[:, j]))))
+        assert np.isnan(got[N:]).all()
     H.free()
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The coarsest direct solve of a column group: one launch sequence per group (cr_solve_multi) against the column loop.
+"""The coarsest direct solve of a column group: one launch sequence per group (cr_solve with kc columns) against the column loop.
 
     python tools/exp_multi_coarse.py --out new.jsonl                       # this checkout
     python tools/exp_multi_coarse.py --tree ../parent --out old.jsonl      # a checkout of the parent commit, same box
