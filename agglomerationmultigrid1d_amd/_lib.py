@@ -35,6 +35,8 @@ RESTRICT_PRECONDITIONED_MAX_ELEMS = 1 << 21
 LEVEL_GENERIC, LEVEL_FUSED_BTD, LEVEL_FUSED_CHAIN, LEVEL_COARSEST = 0, 1, 2, 3
 # aggmg_hier_set_sweep_weights: most weights per half (include/aggmg_hip.h)
 MAX_SWEEP_WEIGHTS = 8
+# aggmg_fgmres_dev: longest restart cycle (include/aggmg_hip.h)
+FGMRES_MAX_RESTART = 64
 RCCL_ID_BYTES = 128
 DIST_X0_GHOSTS_VALID, DIST_OVERLAP_NEXT, DIST_GRAPH = 1, 2, 4
 ALLGATHER_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p)
@@ -191,6 +193,9 @@ SYMBOLS = {
     "aggmg_smoother_solve_dev": (c_int, [_P, _P, _P, _P, _P, c_int, c_double, c_double, c_int, _P,
                                          _PD, POINTER(c_int), POINTER(c_int), _P, _PD]),
     "aggmg_pcg_dev": (c_int, [_P, _P, _P, _P, c_int, c_double, c_int, c_int, c_double, _PD, POINTER(c_int)]),
+    "aggmg_multi_dot_dev": (c_int, [_P, _P, c_int64, c_int64, c_int64, _P, _PD]),
+    "aggmg_multi_axpy_norm_dev": (c_int, [_P, _P, c_int64, c_int64, c_int64, _PD, _P, _PD]),
+    "aggmg_fgmres_dev": (c_int, [_P, _P, _P, _P, c_int, c_int, c_double, c_int, c_int, c_double, _PD, POINTER(c_int)]),
     "aggmg_residual_multi_dev": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P]),
     "aggmg_dot_cols_dev": (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, _PD]),
     "aggmg_norm2_cols_dev": (c_int, [_P, _P, c_int64, c_int64, c_int64, _PD]),

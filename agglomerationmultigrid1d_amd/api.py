@@ -151,6 +151,33 @@ class Context:
         self.check(self.lib.aggmg_norm2_cols_dev(self.handle, _ptr(X), int(n), int(ncols), int(ld), _pd(out)))
         return out
 
+    def multi_dot(self, V, w, n=None, nvec=None, ld=None):
+        """V[:, i] . w for every column of V with one pass over w per group of 8 columns (C ABI aggmg_multi_dot_dev;
+        EXTENSION: the orthogonalisation of fgmres): V DeviceMatrix of at most 65 columns (or a column-major device
+        buffer with n, nvec, ld given), w DeviceVector; entry i is bit for bit dot() of column i and w.
+        -> array of nvec"""
+        n, nvec, ld = _cols_shape("multi_dot", V, n, nvec, ld)
+        if isinstance(w, DeviceVector) and w.n < n:
+            raise DimensionMismatch("multi_dot: w is shorter than the columns of V")
+        out = np.zeros(max(1, int(nvec)))
+        self.check(self.lib.aggmg_multi_dot_dev(self.handle, _ptr(V), int(n), int(nvec), int(ld), _ptr(w), _pd(out)))
+        return out
+
+    def multi_axpy_norm(self, V, coef, w, n=None, nvec=None, ld=None, norm=True):
+        """w += V @ coef in place, one fused multiply-add per column in ascending order, with one pass over w per group
+        of 8 columns (C ABI aggmg_multi_axpy_norm_dev; EXTENSION: the orthogonalisation of fgmres).  -> ||w||_2 of the
+        stored vector, summed by the pass that stores it (bit for bit norm2(w) afterwards); None with norm=False"""
+        n, nvec, ld = _cols_shape("multi_axpy_norm", V, n, nvec, ld)
+        if isinstance(w, DeviceVector) and w.n < n:
+            raise DimensionMismatch("multi_axpy_norm: w is shorter than the columns of V")
+        c = _f64(coef).ravel()
+        if c.size != nvec:
+            raise DimensionMismatch("multi_axpy_norm: one coefficient per column of V")
+        out = ctypes.c_double(0.0)
+        self.check(self.lib.aggmg_multi_axpy_norm_dev(self.handle, _ptr(V), int(n), int(nvec), int(ld), _pd(c), _ptr(w),
+                                                      ctypes.byref(out) if norm else None))
+        return out.value if norm else None
+
     def profile_enable(self, on=True):
         """True / 1: HIP events around every launch; 2: only the fine-level fused-down launch;
         False / 0: off"""
@@ -1575,7 +1602,10 @@ def _pcg_multi(H, B, X0, maxiter, tol, nPre, nPost, alpha):
 def pcg(H, b, x0=None, maxiter=50, tol=1e-10, nPre=3, nPost=3, alpha=2.0 / 3.0):
     """Conjugate gradients with ldiv!(y, H, r) (src/solvers.jl:84-92) as the preconditioner,
     resident on the device (C ABI aggmg_pcg_dev).  EXTENSION: the reference offers ldiv! for this
-    use but has no Krylov loop.  -> (x, iter, res)"""
+    use but has no Krylov loop.  -> (x, iter, res)
+    Needs a symmetric positive definite operator AND a symmetric cycle (nPre == nPost, a sweep-weight schedule whose post
+    half is the pre half reversed, no hybrid Schwarz level); nothing checks that, and on another cycle the result is
+    wrong without an error: use fgmres there."""
     if isinstance(b, DeviceMatrix) or (not isinstance(b, DeviceVector) and np.ndim(b) == 2):
         return _pcg_multi(H, b, x0, maxiter, tol, nPre, nPost, alpha)
     b = _f64(b)
@@ -1590,6 +1620,46 @@ def pcg(H, b, x0=None, maxiter=50, tol=1e-10, nPre=3, nPost=3, alpha=2.0 / 3.0):
     c.check(c.lib.aggmg_pcg_dev(c.handle, H.handle, db.ptr, dx.ptr, int(maxiter), float(tol), int(nPre), int(nPost),
                                 float(alpha), _pd(hist), ctypes.byref(it)))
     return dx.download(), it.value, hist[:it.value].tolist()
+
+
+def fgmres(H, b, x0=None, restart=30, maxiter=200, tol=1e-10, nPre=3, nPost=3, alpha=2.0 / 3.0):
+    """Right-preconditioned flexible GMRES(restart) with one V-cycle from a zero guess as the preconditioner, resident on
+    the device (C ABI aggmg_fgmres_dev).  EXTENSION: the reference has no Krylov loop.  Valid for EVERY cycle -- nPre !=
+    nPost, unsymmetric sweep-weight schedules, hybrid Schwarz and Gauss-Seidel levels -- where pcg needs a symmetric one.
+    -> (x, iter, res): res[i] the residual norm of the least-squares problem after iteration i; the loop stops when it is
+    < tol ||b|| or after maxiter iterations.  b, x0 host arrays -> x a host array; DeviceVectors -> a DeviceVector.  x0
+    (None: zeros) is not modified.  restart: iterations before the basis is dropped and the method starts again from the
+    current residual, 1 .. 64; the work space is (2 restart + 2) vectors on the device.  Small values can stagnate where
+    the default converges (restart 1 and 2 do on V(2,1) of the agglomerated DG hierarchy).  One
+    right-hand side only."""
+    if isinstance(b, DeviceMatrix) or isinstance(x0, DeviceMatrix) or \
+            (not isinstance(b, DeviceVector) and np.ndim(b) != 1):
+        raise ArgumentError("fgmres: b must be one vector; K right-hand sides are out of scope of fgmres (pcg and "
+                            "multigrid take N x K matrices)")
+    c = H.ctx
+    N = H._ops[0].shape[0]
+    on_device = isinstance(b, DeviceVector)
+    if x0 is not None and isinstance(x0, DeviceVector) != on_device:
+        raise ArgumentError("fgmres: b and x0 must be both DeviceVectors or both host arrays")
+    db = b if on_device else c.to_device(_f64(b))
+    if db.n != N:
+        raise DimensionMismatch("fgmres: b does not match the fine operator")
+    if on_device:
+        dx = DeviceVector(c, N)                 # (aggmg_dev_alloc zeroes: the zero guess)
+        if x0 is not None:
+            if x0.n != N:
+                raise DimensionMismatch("fgmres: x0 does not match the fine operator")
+            _copy_dev(c, dx.ptr.value, x0.ptr.value, N)
+    else:
+        x0 = np.zeros(N) if x0 is None else _f64(x0)
+        if x0.shape != (N,):
+            raise DimensionMismatch("fgmres: x0 does not match the fine operator")
+        dx = c.to_device(x0)
+    hist = np.zeros(max(1, int(maxiter)))
+    it = ctypes.c_int(0)
+    c.check(c.lib.aggmg_fgmres_dev(c.handle, H.handle, db.ptr, dx.ptr, int(restart), int(maxiter), float(tol), int(nPre),
+                                   int(nPost), float(alpha), _pd(hist), ctypes.byref(it)))
+    return (dx if on_device else dx.download()), it.value, hist[:it.value].tolist()
 
 
 def iterative_smoother_solve(A, smoother, x0, b, maxiter=1000, tol=1e-6, alpha=1.0, exact=True, check_every=1):

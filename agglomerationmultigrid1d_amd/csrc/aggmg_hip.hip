@@ -9,6 +9,8 @@
 #include "multi_kernels.hpp"
 #include "multi_solve_kernels.hpp"
 #include "pair_kernels.hpp"
+#include "krylov_kernels.hpp"
+#include "host_gmres.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // context
@@ -3617,6 +3619,212 @@ extern "C" int aggmg_dot_cols_dev(aggmg_ctx* ctx, const double* X, const double*
 }
 extern "C" int aggmg_norm2_cols_dev(aggmg_ctx* ctx, const double* X, int64_t n, int64_t ncols, int64_t ld, double* out_host) {
   return dot_cols_entry(ctx, "aggmg_norm2_cols_dev", X, X, n, ncols, ld, out_host, 1);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Flexible GMRES around the cycle (EXTENSION: the reference has no Krylov loop).  Conjugate gradients above need a
+// symmetric cycle; a minimal-residual method is valid for every cycle -- nPre != nPost, sweep-weight schedules whose
+// post half is not the pre half reversed, hybrid Schwarz and Gauss-Seidel levels -- and for a preconditioner that
+// changes from one application to the next.  The two streaming passes of its orthogonalisation are
+// krylov_kernels.hpp, the small dense part is host_gmres.hpp.
+// ---------------------------------------------------------------------------------------------
+constexpr int64_t kKryMaxVec = AGGMG_FGMRES_MAX_RESTART + 1;
+// device scalars of the Krylov passes: [0 .. 65] the dots of a pass and, behind them, the norm of the update;
+// [kKryCoef .. + 64] coefficients that came from the host; [kKryBeta] ||r|| of a restart
+constexpr int kKryCoef = 128, kKryBeta = 200, kKryScalars = 256;
+static_assert(HostGmres::kMaxRestart == AGGMG_FGMRES_MAX_RESTART, "host_gmres.hpp and the header disagree");
+
+static int kry_scalars(aggmg_ctx* ctx) {
+  CHECK(solv_scalars(ctx));
+  if (!ctx->kry_part) CHECK(ctx->kry_part.alloc(ctx, (kKryMaxVec + 1) * kDotBlocks));
+  if (!ctx->kry_sc) CHECK(ctx->kry_sc.alloc(ctx, kKryScalars, true));
+  return AGGMG_OK;
+}
+
+template <int G>
+static void launch_multi_dot(aggmg_ctx* ctx, int64_t n, const double* V, int64_t ld, const double* w, double* part) {
+  hipLaunchKernelGGL(multi_dot_partial_kernel<G>, dim3(kDotBlocks), dim3(kThreads), 0, ctx->stream, n, V, ld, w, part);
+}
+template <int G>
+static void launch_multi_axpy(aggmg_ctx* ctx, int64_t n, const double* V, int64_t ld, const double* coef, double scale,
+                              double* w, double* part) {
+  if (part)
+    hipLaunchKernelGGL((multi_axpy_kernel<G, true>), dim3(kDotBlocks), dim3(kThreads), 0, ctx->stream, n, V, ld, coef, scale, w,
+                       part);
+  else
+    hipLaunchKernelGGL((multi_axpy_kernel<G, false>), dim3(kDotBlocks), dim3(kThreads), 0, ctx->stream, n, V, ld, coef, scale, w,
+                       part);
+}
+#define KRY_GROUP_SWITCH(g, CALL) \
+  switch (g) {                    \
+    case 1: CALL(1); break;       \
+    case 2: CALL(2); break;       \
+    case 3: CALL(3); break;       \
+    case 4: CALL(4); break;       \
+    case 5: CALL(5); break;       \
+    case 6: CALL(6); break;       \
+    case 7: CALL(7); break;       \
+    default: CALL(8); break;      \
+  }
+
+// out[i] = V_i . w, i < nvec <= kKryMaxVec (out on the device): one pass over w per group of 8 vectors, then one
+// workgroup per dot; everything stays on the stream
+static int dev_multi_dot(aggmg_ctx* ctx, int64_t n, int64_t nvec, const double* V, int64_t ld, const double* w, double* out) {
+  for (int64_t i0 = 0; i0 < nvec; i0 += kKrylovGroup) {
+    const int g = (int)std::min<int64_t>(kKrylovGroup, nvec - i0);
+#define KRY_CALL(G) launch_multi_dot<G>(ctx, n, V + i0 * ld, ld, w, ctx->kry_part + i0 * kDotBlocks)
+    KRY_GROUP_SWITCH(g, KRY_CALL)
+#undef KRY_CALL
+  }
+  hipLaunchKernelGGL(dot_cols_final_kernel, dim3((unsigned)nvec), dim3(kThreads), 0, ctx->stream, kDotBlocks,
+                     (const double*)ctx->kry_part, out, 0);
+  HIPCHK(hipGetLastError());
+  return AGGMG_OK;
+}
+
+// w += V (scale coef), coef[0 .. nvec - 1] on the device, in groups of 8 (ascending); norm_out (device, or null)
+// receives ||w||_2 of the stored vector, summed by the pass of the last group
+static int dev_multi_axpy(aggmg_ctx* ctx, int64_t n, int64_t nvec, const double* V, int64_t ld, const double* coef, double scale,
+                          double* w, double* norm_out) {
+  double* part = ctx->kry_part + kKryMaxVec * kDotBlocks;
+  for (int64_t i0 = 0; i0 < nvec; i0 += kKrylovGroup) {
+    const int g = (int)std::min<int64_t>(kKrylovGroup, nvec - i0);
+    double* p = (norm_out && i0 + g == nvec) ? part : nullptr;
+#define KRY_CALL(G) launch_multi_axpy<G>(ctx, n, V + i0 * ld, ld, coef + i0, scale, w, p)
+    KRY_GROUP_SWITCH(g, KRY_CALL)
+#undef KRY_CALL
+  }
+  if (norm_out)
+    hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, kDotBlocks, (const double*)part, norm_out, 1);
+  HIPCHK(hipGetLastError());
+  return AGGMG_OK;
+}
+
+static int kry_args(aggmg_ctx* ctx, const char* who, const double* V, int64_t n, int64_t nvec, int64_t ld, const double* w,
+                    const void* host) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!V || !w || !host) return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": NULL argument");
+  if (n < 0 || nvec < 1 || nvec > kKryMaxVec)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": needs n >= 0 and 1 <= nvec <= " + std::to_string(kKryMaxVec));
+  if (ld < n) return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": ld must be >= n");
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_multi_dot_dev(aggmg_ctx* ctx, const double* V, int64_t n, int64_t nvec, int64_t ld, const double* w,
+                                   double* out_host) {
+  CHECK(kry_args(ctx, "aggmg_multi_dot_dev", V, n, nvec, ld, w, out_host));
+  HIPCHK(hipSetDevice(ctx->device));
+  CHECK(kry_scalars(ctx));
+  CHECK(dev_multi_dot(ctx, n, nvec, V, ld, w, ctx->kry_sc));
+  return read_scalars(ctx, ctx->kry_sc, nvec, out_host);
+}
+
+extern "C" int aggmg_multi_axpy_norm_dev(aggmg_ctx* ctx, const double* V, int64_t n, int64_t nvec, int64_t ld,
+                                         const double* coef_host, double* w_inout, double* norm_out_host) {
+  CHECK(kry_args(ctx, "aggmg_multi_axpy_norm_dev", V, n, nvec, ld, w_inout, coef_host));
+  if (ranges_overlap(V, (nvec - 1) * ld + n, w_inout, n))
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_multi_axpy_norm_dev: w must not overlap V");
+  HIPCHK(hipSetDevice(ctx->device));
+  CHECK(kry_scalars(ctx));
+  double* coef = ctx->kry_sc + kKryCoef;
+  HIPCHK(hipMemcpyAsync(coef, coef_host, (size_t)nvec * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  CHECK(dev_multi_axpy(ctx, n, nvec, V, ld, coef, 1.0, w_inout, norm_out_host ? ctx->kry_sc.get() : nullptr));
+  if (norm_out_host) return read_scalar(ctx, ctx->kry_sc, norm_out_host);
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // (coef_host has been read when this returns)
+  return AGGMG_OK;
+}
+
+// Right-preconditioned flexible GMRES(restart), classical Gram-Schmidt in one pass: per iteration one cycle
+// z_j = M^-1 v_j, one operator product, the fused dots h = V' w, the fused update w -= V h that also yields
+// h_{j+1,j} = ||w||, one read-back of the column, v_{j+1} = w / h_{j+1,j}.  The operator product is the residual launch
+// on a zero right-hand side, w = -A z_j (as in aggmg_pcg_dev): the Arnoldi relation is therefore kept for -A,
+// (-A) Z = V Hbar, the least-squares problem min || beta e_1 - Hbar y || is the usual one, and the correction enters
+// with the other sign: x -= Z y gives r_new = r - (-A Z) y = V (beta e_1 - Hbar y).  Every sign change is exact, so
+// the history is what the recurrence on +A gives.
+extern "C" int aggmg_fgmres_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* b, double* x_inout, int restart, int maxiter,
+                                double tol, int nPre, int nPost, double alpha, double* res_hist, int* n_iters) {
+  CHECK(vcycle_args(ctx, h, x_inout, b, nPre, nPost));
+  if (!res_hist || !n_iters || maxiter < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_fgmres_dev: bad argument");
+  if (restart < 1 || restart > AGGMG_FGMRES_MAX_RESTART)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_fgmres_dev: restart must be 1 .. " + std::to_string(AGGMG_FGMRES_MAX_RESTART));
+  if (x_inout == b) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_fgmres_dev: x must not alias b");
+  if (h->coarse_mode == AGGMG_COARSE_EXTERNAL)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_fgmres_dev: hierarchy was created with AGGMG_COARSE_EXTERNAL");
+  CHECK(schedule_check(ctx, h, nPre, nPost));
+  HIPCHK(hipSetDevice(ctx->device));
+  *n_iters = 0;
+  if (maxiter == 0) return AGGMG_OK;
+  CHECK(kry_scalars(ctx));
+  aggmg_op* A = h->lv[0].A;
+  const int64_t N = A->m;
+  // work space: V (restart + 1 vectors), Z (restart), and w, which holds r between the cycles; kept for the next call
+  // of the same size, exchanged for another size
+  const int64_t need = (2 * (int64_t)restart + 2) * N;
+  if (ctx->kry_work.size() != need || !ctx->kry_work) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    (void)ctx->kry_work.reset(ctx);
+    if (int st = ctx->kry_work.alloc(ctx, need))
+      return fail(ctx, st, "aggmg_fgmres_dev: no device memory for the work space of " + std::to_string(need * 8) +
+                               " bytes (restart " + std::to_string(restart) + ", " + std::to_string(2 * restart + 2) +
+                               " vectors of " + std::to_string(N) + "): " + ctx->err);
+  }
+  double* V = ctx->kry_work;
+  double* Z = V + ((int64_t)restart + 1) * N;
+  double* w = Z + (int64_t)restart * N;
+  double* zero = nullptr;
+  CHECK(solv_vec(ctx, 4, N, &zero));
+  HIPCHK(hipMemsetAsync(zero, 0, N * sizeof(double), ctx->stream));
+  double* sc = ctx->kry_sc;
+  const unsigned grid = (unsigned)((N + kThreads - 1) / kThreads);
+  double nb = 0.0;
+  CHECK(dev_dot(ctx, N, b, b, sc + kKryBeta, 1));
+  CHECK(read_scalar(ctx, sc + kKryBeta, &nb));
+  HostGmres ls;
+  double col[AGGMG_FGMRES_MAX_RESTART + 2], y[AGGMG_FGMRES_MAX_RESTART];
+  int it = 0;
+  bool done = false;
+  while (!done && it < maxiter) {
+    double beta = 0.0;
+    CHECK(aggmg_residual_dev(ctx, A, x_inout, b, w));                      // every cycle starts from r = b - A x
+    CHECK(dev_dot(ctx, N, w, w, sc + kKryBeta, 1));
+    CHECK(read_scalar(ctx, sc + kKryBeta, &beta));
+    if (beta == 0.0 || beta < tol * nb || !std::isfinite(beta)) break;     // (at entry: x untouched, n_iters = 0)
+    hipLaunchKernelGGL(div_scalar_kernel, dim3(grid), dim3(kThreads), 0, ctx->stream, N, (const double*)w,
+                       (const double*)(sc + kKryBeta), V);                // v_0 = r / beta
+    ls.start(beta);
+    const int len = std::min(restart, maxiter - it);
+    bool finite = true;
+    for (int j = 0; j < len; ++j) {
+      double* zj = Z + (int64_t)j * N;
+      CHECK(aggmg_vcycle_dev(ctx, h, nullptr, V + (int64_t)j * N, nPre, nPost, alpha, zj));   // z_j = M^-1 v_j
+      CHECK(aggmg_residual_dev(ctx, A, zj, zero, w));                                          // w = -A z_j
+      CHECK(dev_multi_dot(ctx, N, j + 1, V, N, w, sc));                                        // h = V' w
+      CHECK(dev_multi_axpy(ctx, N, j + 1, V, N, sc, -1.0, w, sc + j + 1));                     // w -= V h; ||w||
+      CHECK(read_scalars(ctx, sc, j + 2, col));
+      const double res = ls.push(col);
+      res_hist[it++] = res;
+      *n_iters = it;
+      if (!std::isfinite(res)) {
+        finite = false;
+        done = true;
+        break;
+      }
+      if (res < tol * nb || col[j + 1] == 0.0) {   // converged, or the Krylov space is exhausted (no division by 0)
+        done = true;
+        break;
+      }
+      if (j + 1 < len)
+        hipLaunchKernelGGL(div_scalar_kernel, dim3(grid), dim3(kThreads), 0, ctx->stream, N, (const double*)w,
+                           (const double*)(sc + j + 1), V + (int64_t)(j + 1) * N);
+    }
+    if (!finite) break;   // (x keeps the value of the last finished cycle)
+    ls.solve(y);
+    HIPCHK(hipMemcpyAsync(sc + kKryCoef, y, (size_t)ls.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    CHECK(dev_multi_axpy(ctx, N, ls.size(), Z, N, sc + kKryCoef, -1.0, x_inout, nullptr));     // x += Z y (for -A: -=)
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // (y is read before it changes)
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return AGGMG_OK;
 }
 
 // ---- K-column residual -------------------------------------------------------------------------

@@ -85,6 +85,10 @@ struct aggmg_ctx {
   DevArray<double> cols_part, cols_sc;
   DevArray<int> cols_map;
   int64_t cols_cap = 0;
+  // flexible GMRES (aggmg_fgmres_dev, aggmg_multi_dot_dev, aggmg_multi_axpy_norm_dev): the partial sums of up to 65 dots
+  // and one norm, the device scalars, and the solver's (2 restart + 2) N work space -- kept between calls of the same
+  // size, exchanged when another size is asked for, freed with the context
+  DevArray<double> kry_part, kry_sc, kry_work;
   // owned-range reductions of the partitioned conjugate-gradient loop (aggmg_owned_dot_dev, aggmg_pcg_xr_owned_dev):
   // kOwnedBlocks partial sums per range, then the scalar; lazy, freed with the context
   DevArray<double> own_part;

@@ -657,6 +657,45 @@ int aggmg_smoother_solve_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, co
  * res_hist (host, >= maxiter entries): ||r|| of the recurrence after every iteration. */
 int aggmg_pcg_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* b, double* x_inout, int maxiter, double tol,
                   int nPre, int nPost, double alpha, double* res_hist, int* n_iters);
+/* ---- flexible GMRES around the cycle (EXTENSION: the reference has no Krylov loop).  aggmg_pcg_dev needs a symmetric
+ * cycle and checks nothing: with nPre != nPost, a sweep-weight schedule whose post half is not the pre half reversed, a
+ * hybrid Schwarz or Gauss-Seidel level with unequal counts, it returns a wrong answer.  A minimal-residual method is
+ * valid for every cycle. ---- */
+/* The two streaming passes of its orthogonalisation, over a device basis V (column-major, vector i at V + i * ld,
+ * ld >= n, 1 <= nvec <= AGGMG_FGMRES_MAX_RESTART + 1) and a device vector w.  Both synchronous.
+ * aggmg_multi_dot_dev: out_host[i] = V_i . w, i < nvec, with ONE pass over w per group of 8 vectors; entry i is bit
+ * for bit aggmg_dot_dev(V_i, w, n).
+ * aggmg_multi_axpy_norm_dev: w[r] <- fma(c[nvec-1], V_{nvec-1}[r], ... fma(c[0], V_0[r], w[r])) for r < n (ascending i,
+ * in place, groups of 8, one pass over w per group; rows >= n are not touched); *norm_out_host (may be NULL) receives
+ * ||w||_2 of the stored vector, summed by the pass that stores it: bit for bit aggmg_norm2_dev(w, n) afterwards.
+ * Fixed slices and summation trees, no atomics: the same bits run to run.  AGGMG_ERR_ARGUMENT: NULL, n < 0, nvec
+ * outside 1 .. 65, ld < n, w overlapping V. */
+int aggmg_multi_dot_dev(aggmg_ctx* ctx, const double* V, int64_t n, int64_t nvec, int64_t ld, const double* w,
+                        double* out_host);
+int aggmg_multi_axpy_norm_dev(aggmg_ctx* ctx, const double* V, int64_t n, int64_t nvec, int64_t ld, const double* coef_host,
+                              double* w_inout, double* norm_out_host);
+/* Right-preconditioned flexible GMRES(restart) on A x = b with one V-cycle from a zero guess as M^-1
+ * (aggmg_vcycle_dev(h, NULL, v, ...): sweep-weight schedules apply as in every other solver); x_inout holds the initial
+ * guess and the result.  Classical Gram-Schmidt, one pass, no re-orthogonalisation.  Per iteration j of a restart cycle:
+ * z_j = M^-1 v_j, w = A z_j, h = V' w (aggmg_multi_dot_dev's pass), w -= V h and h_{j+1,j} = ||w|| (aggmg_multi_axpy_norm_dev's
+ * pass), one read-back of the column, v_{j+1} = w / h_{j+1,j}.  The Hessenberg matrix, its Givens rotations and the
+ * back-substitution (at most 65 x 64 doubles) are on the host.  res_hist (host, >= maxiter entries): res_hist[it] =
+ * |g_{j+1}|, the residual norm of the least-squares problem after iteration it; the loop stops when it is
+ * < tol ||b||, at maxiter iterations, or when it is not finite (x then keeps the value of the last finished restart
+ * cycle).  x += Z y at the end of every restart cycle and at the stop; every restart cycle starts from the explicit
+ * residual b - A x.  ||r|| < tol ||b|| or ||r|| == 0 at entry: *n_iters = 0, x untouched.  ||w|| == 0 (the Krylov
+ * space is exhausted): the entry is recorded, the cycle is finished and the loop stops; nothing is divided by it.
+ * Small restart lengths can stagnate where a long one converges (restart 1 and 2 do on unsymmetric cycles of the
+ * agglomerated DG hierarchy).
+ * Work space: (2 restart + 2) N doubles on the context (V: restart + 1 vectors, Z: restart, and w) -- restart 30 at
+ * 2^24 fine elements of p = 3 (N = 6.7e7) is 33 GB -- kept between calls of the same size, released when another size
+ * is asked for and at aggmg_destroy.  When it cannot be allocated: AGGMG_ERR_HIP, the message names the bytes and the
+ * restart length.  AGGMG_ERR_ARGUMENT, before anything is enqueued: NULL, restart outside
+ * 1 .. AGGMG_FGMRES_MAX_RESTART, maxiter < 0, negative sweep counts, x_inout == b, a hierarchy created with
+ * AGGMG_COARSE_EXTERNAL. */
+#define AGGMG_FGMRES_MAX_RESTART 64
+int aggmg_fgmres_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* b, double* x_inout, int restart, int maxiter, double tol,
+                     int nPre, int nPost, double alpha, double* res_hist, int* n_iters);
 /* ---- K right-hand sides through the outer loops (EXTENSION: the reference's solvers take vectors,
  * src/solvers.jl:116-139).  All matrices: device, column-major, leading dimension ld >= N (>= n). ---- */
 /* out_host[j] = X[:, j] . Y[:, j] / ||X[:, j]||_2, j < ncols, each in one pass over the matrices: bit for bit

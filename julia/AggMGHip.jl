@@ -689,6 +689,7 @@ end
 # pcg(H, B; X0, maxiter, tol) on device matrices -> X::DeviceMatrix, iters::Vector{Int}, res (one Vector per column):
 # K conjugate-gradient recurrences in lockstep, preconditioned by one K-column cycle from zero guesses
 # (aggmg_pcg_multi_dev); column j is the single-vector recurrence on column j.  X0 = nothing: zero guesses.
+# Needs a symmetric cycle (nothing checks it; a wrong answer without an error otherwise): fgmres takes every cycle.
 function pcg(Hd::DeviceHierarchy, B::DeviceMatrix; X0::Union{Nothing,DeviceMatrix} = nothing, maxiter::Integer = 50,
         tol::AbstractFloat = 1e-10, nPre::Integer = 3, nPost::Integer = 3, alpha::AbstractFloat = 2.0 / 3.0)
     K = B.k
@@ -699,6 +700,27 @@ function pcg(Hd::DeviceHierarchy, B::DeviceMatrix; X0::Union{Nothing,DeviceMatri
          Ref{Int64}),
         Hd.ctx.h, Hd.h, B.p, X.p, K, B.n, maxiter, Float64(tol), nPre, nPost, Float64(alpha), res, its, work))
     return X, Int.(its), [res[1:its[j], j] for j in 1:K]
+end
+
+# fgmres(H, b; x0, restart, maxiter, tol) -> x, iter, res: right-preconditioned flexible GMRES(restart) with one V-cycle
+# from a zero guess as the preconditioner (aggmg_fgmres_dev; EXTENSION: the reference has no Krylov loop).  Valid for
+# every cycle -- nPre != nPost, unsymmetric sweep-weight schedules, hybrid Schwarz levels -- where pcg needs a symmetric
+# one and returns a wrong answer without an error on any other.  res[i]: the residual norm of the least-squares problem
+# after iteration i.  b, x0 DeviceVectors -> x a DeviceVector, host vectors -> a host vector; x0 = nothing: zeros; x0 is
+# not modified.  restart 1 .. 64: the work space is (2 restart + 2) device vectors; small values can stagnate where the
+# default converges (DESIGN.md 18).  One right-hand side only: K columns are out of scope.
+function fgmres(Hd::DeviceHierarchy, b::Union{AbstractVector,DeviceVector};
+        x0::Union{Nothing,AbstractVector,DeviceVector} = nothing, restart::Integer = 30, maxiter::Integer = 200,
+        tol::AbstractFloat = 1e-10, nPre::Integer = 3, nPost::Integer = 3, alpha::AbstractFloat = 2.0 / 3.0)
+    on_device = b isa DeviceVector
+    db = on_device ? b : DeviceVector(Hd.ctx, b)
+    x = x0 === nothing ? DeviceVector(Hd.ctx, db.n) :                      # (fresh memory is zeroed)
+        DeviceVector(Hd.ctx, x0 isa DeviceVector ? download(x0) : x0)     # (a copy: x0 stays as it is)
+    res = zeros(max(maxiter, 1)); it = Ref{Cint}(0)
+    GC.@preserve db x res check(Hd.ctx.h, ccall((:aggmg_fgmres_dev, LIB), Cint,
+        (Handle, Handle, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Float64, Cint, Cint, Float64, Ptr{Float64}, Ref{Cint}),
+        Hd.ctx.h, Hd.h, db.p, x.p, restart, maxiter, Float64(tol), nPre, nPost, Float64(alpha), res, it))
+    return (on_device ? x : download(x)), Int(it[]), res[1:it[]]
 end
 
 # iterative_smoother_solve(A, smoother, x0, b; maxiter = 1000, tol = 1e-6, alpha = 1.0) -> x, iter, res, err

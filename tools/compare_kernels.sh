@@ -1,8 +1,10 @@
 #!/bin/bash
 # Are the gfx950 kernels of two builds of libaggmg_hip.so the same kernels?  (a host-side refactor must leave them alone)
 #   tools/compare_kernels.sh old/libaggmg_hip.so new/libaggmg_hip.so
-# Compares, per kernel symbol, the disassembled instruction stream and the metadata note (VGPR, SGPR, scratch, LDS, ...);
-# prints one line and exits 0 when the symbol sets and all of that are identical.
+# Compares, per kernel symbol and translation unit, the disassembled instruction stream (without the addresses the
+# disassembler prints beside it: they move when a kernel is added in front) and the metadata note (VGPR, SGPR, scratch,
+# LDS, ...); prints one line and exits 0 when every kernel of the old build is in the new one with all of that identical.
+# Kernels only the new build has are additions: counted, not an error.
 set -e
 LLVM=/opt/rocm/lib/llvm/bin
 tmp=$(mktemp -d /tmp/kcmp.XXXXXX)
@@ -27,25 +29,30 @@ PY
 import re, sys
 d = sys.argv[1]
 # instruction streams keyed by symbol, branch targets kept as the disassembler prints them (symbol + offset)
-syms, cur = {}, None
+# (a static kernel of a shared header has one copy per translation unit that launches it: #0, #1, ... in file order)
+syms, cur, seen = {}, None, {}
 for line in open(f"{d}/isa.raw"):
     m = re.match(r"^<(\S+)>:", line)
     if m:
-        cur = m.group(1)
+        k = seen.get(m.group(1), 0)
+        seen[m.group(1)] = k + 1
+        cur = f"{m.group(1)}#{k}"
         syms[cur] = []
     elif cur and line.strip():
-        syms[cur].append(line.strip())
+        syms[cur].append(re.sub(r"// [0-9A-Fa-f]+:", "//", line.strip()))
 with open(f"{d}/isa.txt", "w") as f:
     for k in sorted(syms):
         f.write(f"== {k}\n" + "\n".join(syms[k]) + "\n")
 # metadata: one block per kernel (from ".name:" of a kernel entry), sorted by symbol
 txt = open(f"{d}/notes.raw").read()
 blocks = re.split(r"\n(?=\s+- \.agpr_count:|\s+- \.args:)", txt)
-kern = {}
+kern, seen = {}, {}
 for b in blocks:
     m = re.search(r"\.symbol:\s+(\S+)", b)
     if m:
-        kern[m.group(1)] = re.sub(r"amdhsa\.target:.*|amdhsa\.version:.*(\n\s+- \d+)*|\.\.\.|---|Displaying notes.*|\s+Owner.*|\s+AMDGPU.*|\s+AMDGPU Metadata.*", "", b).rstrip()
+        k = seen.get(m.group(1), 0)
+        seen[m.group(1)] = k + 1
+        kern[f"{m.group(1)}#{k}"] = re.sub(r"amdhsa\.target:.*|amdhsa\.version:.*(\n\s+- \d+)*|\.\.\.|---|Displaying notes.*|\s+Owner.*|\s+AMDGPU.*|\s+AMDGPU Metadata.*", "", b).rstrip()
 with open(f"{d}/meta.txt", "w") as f:
     for k in sorted(kern):
         f.write(f"== {k}\n{kern[k]}\n")
@@ -55,9 +62,34 @@ PY
 }
 dump $1 $tmp/a
 dump $2 $tmp/b
-rc=0
-cmp -s $tmp/a/symbols.txt $tmp/b/symbols.txt || { echo "kernel symbol sets differ"; diff $tmp/a/symbols.txt $tmp/b/symbols.txt | head -20; rc=1; }
-cmp -s $tmp/a/isa.txt $tmp/b/isa.txt || { echo "instruction streams differ"; diff $tmp/a/isa.txt $tmp/b/isa.txt | grep "^[<>] ==" | head -20; rc=1; }
-cmp -s $tmp/a/meta.txt $tmp/b/meta.txt || { echo "kernel metadata differs"; diff $tmp/a/meta.txt $tmp/b/meta.txt | head -20; rc=1; }
-[ $rc = 0 ] && echo "identical: $(wc -l < $tmp/a/symbols.txt) kernels, $(grep -vc '^==' $tmp/a/isa.txt) instructions, metadata (VGPR, SGPR, scratch, LDS) equal"
-exit $rc
+python3 - $tmp/a $tmp/b <<'PY'
+import sys
+def load(p):
+    d, cur = {}, None
+    for line in open(p):
+        if line.startswith("== "):
+            cur = line[3:].strip()
+            d[cur] = []
+        else:
+            d[cur].append(line)
+    return d
+a, b = sys.argv[1], sys.argv[2]
+rc = 0
+ia, ib, ma, mb = load(f"{a}/isa.txt"), load(f"{b}/isa.txt"), load(f"{a}/meta.txt"), load(f"{b}/meta.txt")
+gone = sorted(k for k in ia if k not in ib)
+if gone:
+    print(f"{len(gone)} kernels of the old build are missing from the new one:", *gone[:20], sep="\n  ")
+    rc = 1
+for what, x, y in (("instruction streams differ", ia, ib), ("kernel metadata differs", ma, mb)):
+    bad = sorted(k for k in x if k in y and x[k] != y[k])
+    if bad:
+        print(f"{what} in {len(bad)} kernels:", *bad[:20], sep="\n  ")
+        rc = 1
+added = sorted(k for k in ib if k not in ia)
+if rc == 0:
+    print(f"identical: {len(ia)} kernels, {sum(map(len, ia.values()))} instructions, metadata (VGPR, SGPR, scratch, LDS) equal"
+          + (f"; {len(added)} kernels added" if added else ""))
+    for k in added:
+        print("  +", k)
+sys.exit(rc)
+PY
