@@ -813,14 +813,14 @@ static int btd_smooth(aggmg_ctx* ctx, const BtdDev& b, const double* u_in, const
   // chunk chain: src -> (scratch0 / scratch1 alternating) -> ... -> u_out
   const int nchunks = (left + smax - 1) / smax;
   if (chk && nchunks > 1) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: checkpoints in a chunked run of sweeps");
-  double *t0 = nullptr, *t1 = nullptr;
+  WorkLease t0, t1;
   if (nchunks > 1) {
-    CHECK(scratch(ctx, 0, N, &t0));
-    if (nchunks > 2) CHECK(scratch(ctx, 1, N, &t1));
+    CHECK(scratch_lease(ctx, kScratchPing, N, "btd_smooth", &t0));
+    if (nchunks > 2) CHECK(scratch_lease(ctx, kScratchPong, N, "btd_smooth", &t1));
   }
   for (int c = 0; c < nchunks; ++c) {
     const int s = std::min(left, smax);
-    double* dst = (c == nchunks - 1) ? u_out : (((nchunks - 1 - c) % 2 == 1) ? t0 : t1);
+    double* dst = (c == nchunks - 1) ? u_out : (((nchunks - 1 - c) % 2 == 1) ? t0.get() : t1.get());
     FusedLaunch a = fused_sweeps(b, src, rhs, dst, alpha.from(nsweeps - left), s, gs);
     if (chk) fused_chk(a, *chk);
     {
@@ -862,11 +862,11 @@ static int generic_sweep(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const 
       return AGGMG_OK;
     }
     CHECK(setup_block_cover(ctx, sm));
-    double* Y = nullptr;
-    CHECK(scratch(ctx, 1, std::max<int64_t>(N, sm->nb * sm->m), &Y));
+    WorkLease Y;
+    CHECK(scratch_lease(ctx, kScratchPong, std::max<int64_t>(N, sm->nb * sm->m), "generic_sweep", &Y));
     if (nwg)
       hipLaunchKernelGGL((block_sweep_kernel<false>), dim3(nwg), dim3(kThreads), 0, ctx->stream, A->csr.view(), sm->binv, sm->inds,
-                         (int)sm->m, sm->nb, u_in, rhs, alpha, Y);
+                         (int)sm->m, sm->nb, u_in, rhs, alpha, Y.get());
     HIPCHK(hipGetLastError());
     const unsigned nb2 = (unsigned)((N + kThreads - 1) / kThreads);
     if (nb2)
@@ -875,9 +875,10 @@ static int generic_sweep(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const 
     HIPCHK(hipGetLastError());
     return AGGMG_OK;
   }
-  double *r = nullptr, *y = nullptr;
-  CHECK(scratch(ctx, 1, N, &r));
-  CHECK(scratch(ctx, 2, N, &y));
+  WorkLease lr, ly;
+  CHECK(scratch_lease(ctx, kScratchPong, N, "generic_sweep", &lr));
+  CHECK(scratch_lease(ctx, kScratchStage, N, "generic_sweep", &ly));
+  double *r = lr, *y = ly;
   {
     ProfScope ps(ctx, AGGMG_KIND_RESIDUAL, level);
     CHECK(launch_csr<kResidual>(ctx, A->csr, u_in, rhs, nullptr, 0.0, r));
@@ -979,8 +980,9 @@ static int smooth_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const dou
   const bool chain = sm->cgt && sm->A == A;   // CG chain form: fused point-Jacobi sweeps
   if (chain || (sm->btd && sm->A == A)) {
     // (the fused forms want u_out != u_in: an in-place request is staged through scratch, an extra copy)
-    double* dst = u_out;
-    if (u_out == u_in) CHECK(scratch(ctx, 2, N, &dst));
+    WorkLease stage;
+    if (u_out == u_in) CHECK(scratch_lease(ctx, kScratchStage, N, "aggmg_smooth", &stage));
+    double* dst = stage.held() ? stage.get() : u_out;
     if (chain)
       CHECK(cgt_smooth_ext(ctx, *sm->cgt, u_in, b, alpha, nsweeps, dst, 0));
     else
@@ -988,8 +990,8 @@ static int smooth_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const dou
     if (dst != u_out) HIPCHK(hipMemcpyAsync(u_out, dst, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     return AGGMG_OK;
   }
-  double* t = nullptr;   // point Jacobi ping-pongs through scratch 0
-  CHECK(scratch(ctx, 0, N, &t));
+  WorkLease t;   // point Jacobi ping-pongs through it
+  CHECK(scratch_lease(ctx, kScratchPing, N, "aggmg_smooth", &t));
   return generic_sweeps(ctx, A, sm, u_in, b, alpha, nsweeps, u_out, u_out, t, 0);
 }
 
@@ -1134,8 +1136,9 @@ extern "C" int aggmg_smoother_apply(aggmg_ctx* ctx, aggmg_smoother* sm, const do
       // overlapping lists (additive / hybrid Schwarz, src/smoother.jl:6-46): the block results kept apart, then added
       // up per row in list order -- no atomics, the same bits run to run (r03: atomic adds into a zeroed vector)
       CHECK(setup_block_cover(ctx, sm));
-      double* Yf = nullptr;
-      CHECK(scratch(ctx, 1, std::max<int64_t>(N, sm->nb * sm->m), &Yf));
+      WorkLease lease;
+      CHECK(scratch_lease(ctx, kScratchPong, std::max<int64_t>(N, sm->nb * sm->m), "aggmg_smoother_apply", &lease));
+      double* Yf = lease;
       const unsigned nblk = (unsigned)((sm->nb * sm->m + kThreads - 1) / kThreads);
       if (nblk)
         hipLaunchKernelGGL(block_apply_flat_kernel, dim3(nblk), dim3(kThreads), 0, ctx->stream, sm->binv, sm->inds, (int)sm->m,
@@ -1146,14 +1149,9 @@ extern "C" int aggmg_smoother_apply(aggmg_ctx* ctx, aggmg_smoother* sm, const do
     } else {
       HIPCHK(hipMemsetAsync(dT.p, 0, N * sizeof(double), ctx->stream));
       const unsigned nblk = (unsigned)((sm->nb * sm->m + kThreads - 1) / kThreads);
-      if (nblk) {
-        if (sm->overlapping)
-          hipLaunchKernelGGL((block_apply_kernel<true>), dim3(nblk), dim3(kThreads), 0, ctx->stream, sm->binv,
-                             sm->inds, (int)sm->m, sm->nb, bc, dT.p);
-        else
-          hipLaunchKernelGGL((block_apply_kernel<false>), dim3(nblk), dim3(kThreads), 0, ctx->stream, sm->binv,
-                             sm->inds, (int)sm->m, sm->nb, bc, dT.p);
-      }
+      if (nblk)   // (lists that do not overlap: the branch above took the others)
+        hipLaunchKernelGGL((block_apply_kernel<false>), dim3(nblk), dim3(kThreads), 0, ctx->stream, sm->binv,
+                           sm->inds, (int)sm->m, sm->nb, bc, dT.p);
       hipLaunchKernelGGL(axpy_scaled_kernel, dim3(nb2), dim3(kThreads), 0, ctx->stream, N, (const double*)nullptr,
                          (const double*)dT.p, sm->kind == 2 ? (const double*)sm->counts : (const double*)nullptr,
                          alpha, yc);
@@ -2598,8 +2596,9 @@ static bool fine_mid_ok(const aggmg_hier* h, int nPre, int nPost, MidFor purpose
 
 // Histories and stopping test of launches with checkpoints (with the outer solver loops below)
 struct ChkHist {
+  WorkLease hold;                                          // part and mid lie in it (chk_buffers)
   double *part = nullptr, *mid = nullptr, *sc = nullptr;   // on the device: tile sums, their partial reduction, the norms
-  int64_t cap = 0;                                         // tiles `part` has room for (per checkpoint)
+  int64_t cap = 0;                                       // tiles `part` has room for (per checkpoint)
   const double* u_exact = nullptr;
   double tol_nb = 0.0;
   double *res = nullptr, *err = nullptr;
@@ -3167,22 +3166,19 @@ extern "C" int aggmg_hier_last_coarse_ms(aggmg_ctx* ctx, const aggmg_hier* h, do
 // iterative_smoother_solve (src/solvers.jl:189-213) without the per-iteration host round trips of
 // the iterate, and ldiv! (src/solvers.jl:63-92) as the preconditioner of a conjugate-gradient loop
 // ---------------------------------------------------------------------------------------------
-static int solv_vec(aggmg_ctx* ctx, int slot, int64_t len, double** out) {
-  CHECK(ctx->solv[slot].reserve(ctx, len));
-  *out = ctx->solv[slot];
-  return AGGMG_OK;
-}
-
 static int solv_scalars(aggmg_ctx* ctx) {
   if (!ctx->solv_part) CHECK(ctx->solv_part.alloc(ctx, kDotBlocks));
-  if (!ctx->solv_sc) CHECK(ctx->solv_sc.alloc(ctx, 48));   // [16 .. 47]: checkpoint norms of a launch
+  if (!ctx->solv_sc) CHECK(ctx->solv_sc.alloc(ctx, kSolvScalars));   // (the names: workspace.hpp)
   return AGGMG_OK;
 }
 
-// sc_out[0] = x . y  (or its square root); everything stays on the stream
-static int dev_dot(aggmg_ctx* ctx, int64_t n, const double* x, const double* y, double* sc_out, int take_sqrt) {
+// sc_out[0] = x . y  (or its square root); everything stays on the stream.  `first`: the pass over the vectors --
+// diff2_partial_kernel makes it the sum of (x - y)^2
+using PartialKernel = void (*)(int64_t, const double*, const double*, double*);
+static int dev_dot(aggmg_ctx* ctx, int64_t n, const double* x, const double* y, double* sc_out, int take_sqrt,
+                   PartialKernel first = dot_partial_kernel) {
   CHECK(solv_scalars(ctx));
-  hipLaunchKernelGGL(dot_partial_kernel, dim3(kDotBlocks), dim3(kThreads), 0, ctx->stream, n, x, y, ctx->solv_part);
+  hipLaunchKernelGGL(first, dim3(kDotBlocks), dim3(kThreads), 0, ctx->stream, n, x, y, (double*)ctx->solv_part);
   hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, kDotBlocks,
                      (const double*)ctx->solv_part, sc_out, take_sqrt);
   HIPCHK(hipGetLastError());
@@ -3195,22 +3191,28 @@ static int read_scalar(aggmg_ctx* ctx, const double* sc, double* out) {
   return AGGMG_OK;
 }
 
+// reduce, then read back at once: *host_out = x . y (or its square root) when this returns.  Every such value passes
+// through the one scalar kScReadBack; it is on the host before anything else can touch the slot.
+static int reduce_read(aggmg_ctx* ctx, int64_t n, const double* x, const double* y, int take_sqrt, double* host_out,
+                       PartialKernel first = dot_partial_kernel) {
+  CHECK(solv_scalars(ctx));
+  double* sc = ctx->solv_sc + kScReadBack.at;
+  CHECK(dev_dot(ctx, n, x, y, sc, take_sqrt, first));
+  return read_scalar(ctx, sc, host_out);
+}
+
 extern "C" int aggmg_dot_dev(aggmg_ctx* ctx, const double* x, const double* y, int64_t n, double* out) {
   if (!ctx) return AGGMG_ERR_ARGUMENT;
   if (!x || !y || !out || n < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_dot_dev: bad argument");
   HIPCHK(hipSetDevice(ctx->device));
-  CHECK(solv_scalars(ctx));
-  CHECK(dev_dot(ctx, n, x, y, ctx->solv_sc + 15, 0));
-  return read_scalar(ctx, ctx->solv_sc + 15, out);
+  return reduce_read(ctx, n, x, y, 0, out);
 }
 
 extern "C" int aggmg_norm2_dev(aggmg_ctx* ctx, const double* x, int64_t n, double* out) {
   if (!ctx) return AGGMG_ERR_ARGUMENT;
   if (!x || !out || n < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_norm2_dev: bad argument");
   HIPCHK(hipSetDevice(ctx->device));
-  CHECK(solv_scalars(ctx));
-  CHECK(dev_dot(ctx, n, x, x, ctx->solv_sc + 15, 1));
-  return read_scalar(ctx, ctx->solv_sc + 15, out);
+  return reduce_read(ctx, n, x, x, 1, out);
 }
 
 // EXTENSION (no reference counterpart): power iteration for the largest eigenvalue of S^-1 A of a level, what a
@@ -3246,7 +3248,7 @@ extern "C" int aggmg_hier_estimate_lambda_max(aggmg_ctx* ctx, aggmg_hier* h, int
     hipLaunchKernelGGL(seed_vector_kernel, dim3(nb), dim3(kThreads), 0, ctx->stream, N, (double*)v);
     HIPCHK(hipGetLastError());
   }
-  double* sc = ctx->solv_sc + 10;   // [0] ||w||, [1] ||v|| of the last step
+  double* sc = ctx->solv_sc + kScLambda.at;   // [0] ||w||, [1] ||v|| of the last step
   for (int it = 0; it < iters; ++it) {
     CHECK(aggmg_residual_dev(ctx, l.A, v, zero, t));
     CHECK(smooth_dev(ctx, l.A, l.S, nullptr, t, Damping(1.0), 1, w));
@@ -3263,30 +3265,23 @@ extern "C" int aggmg_hier_estimate_lambda_max(aggmg_ctx* ctx, aggmg_hier* h, int
   return AGGMG_OK;
 }
 
-// ||b - A x||_2 on the device (work vector slot 0)
+// ||b - A x||_2 on the device
 static int residual_norm(aggmg_ctx* ctx, aggmg_op* A, const double* x, const double* b, double* out) {
-  double* r = nullptr;
-  CHECK(solv_vec(ctx, 0, A->m, &r));
+  WorkLease r;
+  CHECK(solv_lease(ctx, kSolvR, A->m, "residual_norm", &r));
   CHECK(aggmg_residual_dev(ctx, A, x, b, r));
-  CHECK(dev_dot(ctx, A->m, r, r, ctx->solv_sc + 14, 1));
-  return read_scalar(ctx, ctx->solv_sc + 14, out);
+  return reduce_read(ctx, A->m, r, r, 1, out);
 }
 
 // ||x - y||_2 on the device: one entry of the `err` history (src/solvers.jl:128, :202)
 static int diff_norm(aggmg_ctx* ctx, int64_t n, const double* x, const double* y, double* out) {
-  CHECK(solv_scalars(ctx));
-  hipLaunchKernelGGL(diff2_partial_kernel, dim3(kDotBlocks), dim3(kThreads), 0, ctx->stream, n, x, y, ctx->solv_part);
-  hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, kDotBlocks,
-                     (const double*)ctx->solv_part, ctx->solv_sc + 12, 1);
-  HIPCHK(hipGetLastError());
-  return read_scalar(ctx, ctx->solv_sc + 12, out);
+  return reduce_read(ctx, n, x, y, 1, out, diff2_partial_kernel);
 }
 
 extern "C" int aggmg_residual_norm_dev(aggmg_ctx* ctx, aggmg_op* A, const double* x, const double* b, double* out) {
   if (!ctx) return AGGMG_ERR_ARGUMENT;
   if (!A || !x || !b || !out) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_residual_norm_dev: NULL argument");
   HIPCHK(hipSetDevice(ctx->device));
-  CHECK(solv_scalars(ctx));
   return residual_norm(ctx, A, x, b, out);
 }
 
@@ -3302,20 +3297,22 @@ static int chk_reduce(aggmg_ctx* ctx, int nchk, int64_t ntiles, const double* pa
 }
 
 // room for launches of up to nchk_max checkpoints over at most `tiles` tiles; sc: where their norms go
-static int chk_buffers(aggmg_ctx* ctx, int nchk_max, int64_t tiles, double* sc, ChkHist* H) {
+static int chk_buffers(aggmg_ctx* ctx, int nchk_max, int64_t tiles, ScalarRange sc, ChkHist* H) {
+  if (2 * nchk_max > sc.n) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: more checkpoints than their scalars hold");
   const int64_t npart = (int64_t)nchk_max * 2 * tiles;
-  CHECK(solv_vec(ctx, 2, npart + (int64_t)nchk_max * 2 * kChkReduceGroups, &H->part));
+  CHECK(solv_lease(ctx, kSolvP, npart + (int64_t)nchk_max * 2 * kChkReduceGroups, "chk_buffers", &H->hold));
+  H->part = H->hold;
   H->mid = H->part + npart;
   H->cap = tiles;
-  H->sc = sc;
+  H->sc = ctx->solv_sc + sc.at;
   return AGGMG_OK;
 }
 
-// The nchk (<= 16) checkpoints of a launch, in order, into the histories up to the first one that meets the tolerance:
-// *met is its index, or -1.
+// The nchk (<= kChkMax) checkpoints of a launch, in order, into the histories up to the first one that meets the
+// tolerance: *met is its index, or -1.
 static int chk_collect(aggmg_ctx* ctx, ChkHist& H, int nchk, int64_t ntiles, int* met) {
   CHECK(chk_reduce(ctx, nchk, ntiles, H.part, H.mid, H.sc));
-  double host[32];   // per checkpoint: ||A x - b||, ||x - u_exact||
+  double host[2 * kChkMax];   // per checkpoint: ||A x - b||, ||x - u_exact||
   HIPCHK(hipMemcpyAsync(host, H.sc, (size_t)2 * nchk * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   *met = -1;
@@ -3327,35 +3324,93 @@ static int chk_collect(aggmg_ctx* ctx, ChkHist& H, int nchk, int64_t ntiles, int
   return AGGMG_OK;
 }
 
+// A run of multigrid() (src/solvers.jl:116-139) or iterative_smoother_solve (:189-213) on the device: `maxiter` steps
+// from x0 into x_out, the residual test (and the error norm) after every check_every-th one.  What the two entry points
+// share is written here once; their fused paths, which form the checks inside their launches, stay with them.
+struct CheckedRun {
+  aggmg_ctx* ctx;
+  aggmg_op* A;
+  const double *x0, *b;
+  double* x_out;
+  int maxiter;
+  double tol;
+  int check_every;
+  const double* u_exact;
+  double *res_hist, *err_hist;
+  int *n_done, *n_checks;
+  int64_t N = 0;
+  double tol_nb = 0.0;   // tol ||b||
+  WorkLease alt;         // the iterate ping-pongs between x_out and this vector (a step wants distinct input and output)
+
+  // the arguments (who: the entry point, as its messages name it), ||b||, the alternate iterate; *returned: maxiter == 0,
+  // the reference returns its initial `x = zeros(length(x0))` (src/solvers.jl:119, :192)
+  int begin(const char* who, bool* returned) {
+    const std::string w(who);
+    if (!x_out || !res_hist || !n_done || !n_checks || maxiter < 0 || check_every < 1)
+      return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": bad argument");
+    if (x_out == x0 || x_out == b) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": x_out must not alias x0 or b");
+    if ((u_exact == nullptr) != (err_hist == nullptr))
+      return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": u_exact and err_hist come together (or both NULL)");
+    HIPCHK(hipSetDevice(ctx->device));
+    N = A->m;
+    double nb = 0.0;
+    CHECK(reduce_read(ctx, N, b, b, 1, &nb));
+    tol_nb = tol * nb;
+    CHECK(solv_lease(ctx, kSolvZ, N, who, &alt));
+    *n_done = 0;
+    *n_checks = 0;
+    *returned = maxiter == 0;
+    if (*returned) {
+      HIPCHK(hipMemsetAsync(x_out, 0, N * sizeof(double), ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    return AGGMG_OK;
+  }
+  // histories and stopping test of a fused path's checkpoints
+  void fill(ChkHist* H) const {
+    H->u_exact = u_exact;
+    H->tol_nb = tol_nb;
+    H->res = res_hist;
+    H->err = err_hist;
+  }
+  // the result is in `cur`: into x_out, and the counts
+  int end(const double* cur, int done, int checks) {
+    if (cur != x_out) HIPCHK(hipMemcpyAsync(x_out, cur, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *n_done = done;
+    *n_checks = checks;
+    return AGGMG_OK;
+  }
+  // the unfused loop: step(src, k, dst) takes k steps; then the norms on the device, the histories, the test
+  template <class Step>
+  int loop(Step&& step) {
+    const double* cur = x0;
+    int done = 0, checks = 0;
+    while (done < maxiter) {
+      const int k = std::min(check_every, maxiter - done);
+      double* dst = (cur == x_out) ? alt.get() : x_out;
+      CHECK(step(cur, k, dst));
+      cur = dst;
+      done += k;
+      double res = 0.0;
+      if (u_exact) CHECK(diff_norm(ctx, N, cur, u_exact, &err_hist[checks]));  // err[i] = ||x - u_exact||, src/solvers.jl:128, :202
+      CHECK(residual_norm(ctx, A, cur, b, &res));
+      res_hist[checks++] = res;
+      if (res < tol_nb) break;  // src/solvers.jl:131, :206
+    }
+    return end(cur, done, checks);
+  }
+};
+
 extern "C" int aggmg_multigrid_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const double* b, int maxiter,
                                    double tol, int check_every, int nPre, int nPost, double alpha, double* x_out,
                                    double* res_hist, int* n_cycles, int* n_checks, const double* u_exact,
                                    double* err_hist) {
   CHECK(vcycle_args(ctx, h, x0, b, nPre, nPost));
-  if (!x_out || !res_hist || !n_cycles || !n_checks || maxiter < 0 || check_every < 1)
-    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_multigrid_dev: bad argument");
-  if (x_out == x0 || x_out == b) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_multigrid_dev: x_out must not alias x0 or b");
-  if ((u_exact == nullptr) != (err_hist == nullptr))
-    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_multigrid_dev: u_exact and err_hist come together (or both NULL)");
-  HIPCHK(hipSetDevice(ctx->device));
-  CHECK(solv_scalars(ctx));
-  aggmg_op* A = h->lv[0].A;
-  const int64_t N = A->m;
-  double nb = 0.0;
-  CHECK(dev_dot(ctx, N, b, b, ctx->solv_sc + 13, 1));
-  CHECK(read_scalar(ctx, ctx->solv_sc + 13, &nb));
-  // iterate ping-pong: x_out and work vector 1 (the V-cycle wants distinct input and output)
-  double* alt = nullptr;
-  CHECK(solv_vec(ctx, 1, N, &alt));
-  const double* cur = x0;
-  int done = 0, checks = 0;
-  *n_cycles = 0;
-  *n_checks = 0;
-  if (maxiter == 0) {  // the reference returns its initial `x = zeros(length(x0))` (src/solvers.jl:119)
-    HIPCHK(hipMemsetAsync(x_out, 0, N * sizeof(double), ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return AGGMG_OK;
-  }
+  CheckedRun R{ctx, h->lv[0].A, x0, b, x_out, maxiter, tol, check_every, u_exact, res_hist, err_hist, n_cycles, n_checks};
+  bool returned = false;
+  CHECK(R.begin("aggmg_multigrid_dev", &returned));
+  if (returned) return AGGMG_OK;
   // Fused block-tridiagonal fine level: the residual test (and the error norm) of a checked cycle are formed INSIDE the
   // fine-level launch that post-smooths it -- the launch that goes on to pre-smooth the next cycle (aggmg_vcycles_dev's
   // cross-cycle fusion) -- so a check after every cycle, the reference's semantics (src/solvers.jl:124-131), costs a
@@ -3365,34 +3420,13 @@ extern "C" int aggmg_multigrid_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* 
   if (ctx->mg_checkpoint && fine_mid_ok(h, nPre, nPost, MidFor::Checkpointed)) {
     const FineLevel f{ctx, h, b, nPre, nPost, alpha};
     ChkHist H;
-    CHECK(chk_buffers(ctx, 1, f.chk_tiles(), ctx->solv_sc + 8, &H));   // [8] ||A x - b||  [9] ||x - u_exact||
-    H.u_exact = u_exact;
-    H.tol_nb = tol * nb;
-    H.res = res_hist;
-    H.err = err_hist;
+    CHECK(chk_buffers(ctx, 1, f.chk_tiles(), kScMgChk, &H));
+    R.fill(&H);
+    int done = 0;
     CHECK(cycle_loop(f, x0, maxiter, x_out, check_every, &H, &done));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    *n_cycles = done;
-    *n_checks = H.checks;
-    return AGGMG_OK;
+    return R.end(x_out, done, H.checks);
   }
-  while (done < maxiter) {
-    const int k = std::min(check_every, maxiter - done);
-    double* dst = (cur == x_out) ? alt : x_out;
-    CHECK(aggmg_vcycles_dev(ctx, h, cur, b, k, nPre, nPost, alpha, dst));
-    cur = dst;
-    done += k;
-    double res = 0.0;
-    if (u_exact) CHECK(diff_norm(ctx, N, cur, u_exact, &err_hist[checks]));  // err[i] = ||x - u_exact||, src/solvers.jl:128
-    CHECK(residual_norm(ctx, A, cur, b, &res));
-    res_hist[checks++] = res;
-    if (res < tol * nb) break;  // src/solvers.jl:131
-  }
-  if (cur != x_out) HIPCHK(hipMemcpyAsync(x_out, cur, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  *n_cycles = done;
-  *n_checks = checks;
-  return AGGMG_OK;
+  return R.loop([&](const double* src, int k, double* dst) { return aggmg_vcycles_dev(ctx, h, src, b, k, nPre, nPost, alpha, dst); });
 }
 
 extern "C" int aggmg_smoother_solve_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* x0,
@@ -3400,28 +3434,12 @@ extern "C" int aggmg_smoother_solve_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoot
                                         double* x_out, double* res_hist, int* n_iters, int* n_checks,
                                         const double* u_exact, double* err_hist) {
   CHECK(check_pair(ctx, A, sm, "aggmg_smoother_solve_dev"));
-  if (!x0 || !b || !x_out || !res_hist || !n_iters || !n_checks || maxiter < 0 || check_every < 1)
-    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smoother_solve_dev: bad argument");
-  if (x_out == x0 || x_out == b) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smoother_solve_dev: x_out must not alias x0 or b");
-  if ((u_exact == nullptr) != (err_hist == nullptr))
-    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smoother_solve_dev: u_exact and err_hist come together (or both NULL)");
-  HIPCHK(hipSetDevice(ctx->device));
-  CHECK(solv_scalars(ctx));
-  const int64_t N = A->m;
-  double nb = 0.0;
-  CHECK(dev_dot(ctx, N, b, b, ctx->solv_sc + 13, 1));
-  CHECK(read_scalar(ctx, ctx->solv_sc + 13, &nb));
-  double* alt = nullptr;
-  CHECK(solv_vec(ctx, 1, N, &alt));
-  const double* cur = x0;
-  int done = 0, checks = 0;
-  *n_iters = 0;
-  *n_checks = 0;
-  if (maxiter == 0) {  // the reference returns its initial `x = zeros(length(x0))` (src/solvers.jl:192)
-    HIPCHK(hipMemsetAsync(x_out, 0, N * sizeof(double), ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return AGGMG_OK;
-  }
+  if (!x0 || !b) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smoother_solve_dev: bad argument");   // (a sweep has no zero guess)
+  CheckedRun R{ctx, A, x0, b, x_out, maxiter, tol, check_every, u_exact, res_hist, err_hist, n_iters, n_checks};
+  bool returned = false;
+  CHECK(R.begin("aggmg_smoother_solve_dev", &returned));
+  if (returned) return AGGMG_OK;
+  const int64_t N = R.N;
   // Fused block-tridiagonal smoother on its own operator: launches of up to S sweeps with the residual test (and the error
   // norm) of every checked sweep formed INSIDE the launch (the checkpoint variant of the fused kernel, as
   // aggmg_multigrid_dev) -- the reference's test after every sweep (src/solvers.jl:198-206) at the multi-sweep smoother's
@@ -3433,14 +3451,12 @@ extern "C" int aggmg_smoother_solve_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoot
   const bool chain = !fused && ctx->mg_checkpoint && sm->cgt && sm->A == A && sm->cgt->sw == 0 && cgt_max_fused_sweeps(*sm->cgt) >= 2;
   if (fused || chain) {
     // (one less than a launch takes: the residual rows of the last sweep's iterate)
-    const int smax = std::min(fused ? btd_max_sweeps(*sm->btd, 1) : cgt_max_fused_sweeps(*sm->cgt) - 1, 16);
+    const int smax = std::min(fused ? btd_max_sweeps(*sm->btd, 1) : cgt_max_fused_sweeps(*sm->cgt) - 1, kChkMax);
     ChkHist H;
-    CHECK(chk_buffers(ctx, smax, fused ? btd_chk_tiles(*sm->btd, smax, nullptr) : cgt_chk_tiles(*sm->cgt, smax, 1), ctx->solv_sc + 16,
-                      &H));
-    H.u_exact = u_exact;
-    H.tol_nb = tol * nb;
-    H.res = res_hist;
-    H.err = err_hist;
+    CHECK(chk_buffers(ctx, smax, fused ? btd_chk_tiles(*sm->btd, smax, nullptr) : cgt_chk_tiles(*sm->cgt, smax, 1), kScSmChk, &H));
+    R.fill(&H);
+    const double* cur = x0;
+    int done = 0;
     // S sweeps src -> dst in one launch; chk: with its checkpoints
     auto sweeps = [&](const double* src, double* dst, int S, CgtChk* chk) -> int {
       return chain ? cgt_smooth_ext(ctx, *sm->cgt, src, b, alpha, S, dst, 0, chk)
@@ -3448,7 +3464,7 @@ extern "C" int aggmg_smoother_solve_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoot
     };
     while (done < maxiter) {
       const int S = std::min(smax, maxiter - done);
-      double* dst = (cur == x_out) ? alt : x_out;
+      double* dst = (cur == x_out) ? R.alt.get() : x_out;
       // checked iteration counts in (done, done + S]: multiples of check_every, and maxiter
       CgtChk chk;
       chk.sweep = check_every - done % check_every;   // sweeps of this launch before its first check
@@ -3472,29 +3488,10 @@ extern "C" int aggmg_smoother_solve_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoot
       cur = dst;
       if (stop >= 0) break;
     }
-    if (cur != x_out) HIPCHK(hipMemcpyAsync(x_out, cur, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    *n_iters = done;
-    *n_checks = H.checks;
-    return AGGMG_OK;
+    return R.end(cur, done, H.checks);
   }
-  while (done < maxiter) {
-    const int k = std::min(check_every, maxiter - done);
-    double* dst = (cur == x_out) ? alt : x_out;
-    CHECK(aggmg_smooth_dev(ctx, A, sm, cur, b, alpha, k, dst));  // k x (x += alpha S (b - A x)), :200
-    cur = dst;
-    done += k;
-    double res = 0.0;
-    if (u_exact) CHECK(diff_norm(ctx, N, cur, u_exact, &err_hist[checks]));  // err[i] = ||x - uExact||, src/solvers.jl:202
-    CHECK(residual_norm(ctx, A, cur, b, &res));
-    res_hist[checks++] = res;
-    if (res < tol * nb) break;  // src/solvers.jl:206
-  }
-  if (cur != x_out) HIPCHK(hipMemcpyAsync(x_out, cur, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  *n_iters = done;
-  *n_checks = checks;
-  return AGGMG_OK;
+  // k x (x += alpha S (b - A x)), src/solvers.jl:200
+  return R.loop([&](const double* src, int k, double* dst) { return aggmg_smooth_dev(ctx, A, sm, src, b, alpha, k, dst); });
 }
 
 // Conjugate gradients on A x = b preconditioned by one V-cycle from a zero guess, i.e. by
@@ -3512,18 +3509,14 @@ extern "C" int aggmg_pcg_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* b, dou
   CHECK(solv_scalars(ctx));
   aggmg_op* A = h->lv[0].A;
   const int64_t N = A->m;
-  double *r = nullptr, *z = nullptr, *pv = nullptr, *q = nullptr, *zero = nullptr;
-  CHECK(solv_vec(ctx, 0, N, &r));
-  CHECK(solv_vec(ctx, 1, N, &z));
-  CHECK(solv_vec(ctx, 2, N, &pv));
-  CHECK(solv_vec(ctx, 3, N, &q));
-  CHECK(solv_vec(ctx, 4, N, &zero));
+  WorkLease vec[kSolvSlots];
+  for (int s = 0; s < kSolvSlots; ++s) CHECK(solv_lease(ctx, (SolvSlot)s, N, "aggmg_pcg_dev", &vec[s]));
+  double *r = vec[kSolvR], *z = vec[kSolvZ], *pv = vec[kSolvP], *q = vec[kSolvQ], *zero = vec[kSolvZero];
   HIPCHK(hipMemsetAsync(zero, 0, N * sizeof(double), ctx->stream));
-  double* sc = ctx->solv_sc;  // [0] rz  [1] p.q  [2] rz_new  [3] ||r||  [13] ||b||
+  double* sc = ctx->solv_sc + kScPcg.at;  // [0] rz  [1] p.q  [2] rz_new
   const unsigned grid = (unsigned)((N + kThreads - 1) / kThreads);
   double nb = 0.0, res = 0.0;
-  CHECK(dev_dot(ctx, N, b, b, sc + 13, 1));
-  CHECK(read_scalar(ctx, sc + 13, &nb));
+  CHECK(reduce_read(ctx, N, b, b, 1, &nb));
   *n_iters = 0;
   CHECK(aggmg_residual_dev(ctx, A, x_inout, b, r));                       // r = b - A x
   CHECK(aggmg_vcycle_dev(ctx, h, nullptr, r, nPre, nPost, alpha, z));     // z = M^-1 r  (ldiv!: zero initial guess)
@@ -3534,8 +3527,7 @@ extern "C" int aggmg_pcg_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* b, dou
     CHECK(dev_dot(ctx, N, pv, q, sc + 1, 0));
     hipLaunchKernelGGL(pcg_xr_kernel, dim3(grid), dim3(kThreads), 0, ctx->stream, N, x_inout, r, (const double*)pv,
                        (const double*)q, (const double*)(sc + 0), (const double*)(sc + 1));
-    CHECK(dev_dot(ctx, N, r, r, sc + 3, 1));
-    CHECK(read_scalar(ctx, sc + 3, &res));
+    CHECK(reduce_read(ctx, N, r, r, 1, &res));
     res_hist[it] = res;
     *n_iters = it + 1;
     if (res < tol * nb) break;
@@ -3553,8 +3545,12 @@ extern "C" int aggmg_pcg_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* b, dou
 // K right-hand sides through the outer loops (EXTENSION: the reference's solvers take vectors,
 // src/solvers.jl:116-139; every column keeps the single-vector entry point's arithmetic and bits)
 // ---------------------------------------------------------------------------------------------
-constexpr int kColsScalars = 8;   // per column: [0] rz  [1] p.q  [2] rz_new  [3] ||r||  [4] ||x - u_exact||  [5] ||b||
-constexpr int64_t kColsGridMax = 65535;
+// launches with the columns in blockIdx.y: f(c0, kc) for every chunk [c0, c0 + kc) of K columns that a grid holds
+template <class F>
+static void for_col_chunks(int64_t K, F&& f) {
+  constexpr int64_t kColsGridMax = 65535;
+  for (int64_t c0 = 0; c0 < K; c0 += kColsGridMax) f(c0, (unsigned)std::min<int64_t>(kColsGridMax, K - c0));
+}
 
 static int cols_scalars(aggmg_ctx* ctx, int64_t K) {
   CHECK(solv_scalars(ctx));
@@ -3567,31 +3563,29 @@ static int cols_scalars(aggmg_ctx* ctx, int64_t K) {
   ctx->cols_cap = K;
   return AGGMG_OK;
 }
-static double* cols_sc(aggmg_ctx* ctx, int which) { return ctx->cols_sc + (int64_t)which * ctx->cols_cap; }
+static double* cols_sc(aggmg_ctx* ctx, ColsScalar which) { return ctx->cols_sc + (int64_t)which * ctx->cols_cap; }
 
 // out[c] = X[:, c] . Y[:, c] (or its square root), c < K <= cols_cap; everything stays on the stream
 static int dev_dot_cols(aggmg_ctx* ctx, int64_t n, int64_t K, const double* x, int64_t ldx, const double* y, int64_t ldy,
                         double* out, int take_sqrt) {
-  for (int64_t c0 = 0; c0 < K; c0 += kColsGridMax) {
-    const unsigned kc = (unsigned)std::min<int64_t>(kColsGridMax, K - c0);
+  for_col_chunks(K, [&](int64_t c0, unsigned kc) {
     hipLaunchKernelGGL(dot_cols_partial_kernel, dim3(kDotBlocks, kc), dim3(kThreads), 0, ctx->stream, n, x + c0 * ldx, ldx,
                        y + c0 * ldy, ldy, ctx->cols_part + c0 * kDotBlocks);
     hipLaunchKernelGGL(dot_cols_final_kernel, dim3(kc), dim3(kThreads), 0, ctx->stream, kDotBlocks,
                        (const double*)(ctx->cols_part + c0 * kDotBlocks), out + c0, take_sqrt);
-  }
+  });
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
 // out[c] = ||X[:, c] - Y[:, ycol ? ycol[c] : c]||_2
 static int dev_diff_cols(aggmg_ctx* ctx, int64_t n, int64_t K, const double* x, int64_t ldx, const double* y, int64_t ldy,
                          const int* ycol, double* out) {
-  for (int64_t c0 = 0; c0 < K; c0 += kColsGridMax) {
-    const unsigned kc = (unsigned)std::min<int64_t>(kColsGridMax, K - c0);
+  for_col_chunks(K, [&](int64_t c0, unsigned kc) {
     hipLaunchKernelGGL(diff2_cols_partial_kernel, dim3(kDotBlocks, kc), dim3(kThreads), 0, ctx->stream, n, x + c0 * ldx, ldx,
                        ycol ? y : y + c0 * ldy, ldy, ycol ? ycol + c0 : nullptr, ctx->cols_part + c0 * kDotBlocks);
     hipLaunchKernelGGL(dot_cols_final_kernel, dim3(kc), dim3(kThreads), 0, ctx->stream, kDotBlocks,
                        (const double*)(ctx->cols_part + c0 * kDotBlocks), out + c0, 1);
-  }
+  });
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
@@ -3610,8 +3604,8 @@ static int dot_cols_entry(aggmg_ctx* ctx, const char* who, const double* X, cons
   if (ld < n) return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": ld must be >= n");
   HIPCHK(hipSetDevice(ctx->device));
   CHECK(cols_scalars(ctx, ncols));
-  CHECK(dev_dot_cols(ctx, n, ncols, X, ld, Y, ld, cols_sc(ctx, 3), take_sqrt));
-  return read_scalars(ctx, cols_sc(ctx, 3), ncols, out);
+  CHECK(dev_dot_cols(ctx, n, ncols, X, ld, Y, ld, cols_sc(ctx, kColRes), take_sqrt));
+  return read_scalars(ctx, cols_sc(ctx, kColRes), ncols, out);
 }
 extern "C" int aggmg_dot_cols_dev(aggmg_ctx* ctx, const double* X, const double* Y, int64_t n, int64_t ncols, int64_t ld,
                                   double* out_host) {
@@ -3771,14 +3765,13 @@ extern "C" int aggmg_fgmres_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* b, 
   double* V = ctx->kry_work;
   double* Z = V + ((int64_t)restart + 1) * N;
   double* w = Z + (int64_t)restart * N;
-  double* zero = nullptr;
-  CHECK(solv_vec(ctx, 4, N, &zero));
+  WorkLease zero;
+  CHECK(solv_lease(ctx, kSolvZero, N, "aggmg_fgmres_dev", &zero));
   HIPCHK(hipMemsetAsync(zero, 0, N * sizeof(double), ctx->stream));
   double* sc = ctx->kry_sc;
   const unsigned grid = (unsigned)((N + kThreads - 1) / kThreads);
   double nb = 0.0;
-  CHECK(dev_dot(ctx, N, b, b, sc + kKryBeta, 1));
-  CHECK(read_scalar(ctx, sc + kKryBeta, &nb));
+  CHECK(reduce_read(ctx, N, b, b, 1, &nb));
   HostGmres ls;
   double col[AGGMG_FGMRES_MAX_RESTART + 2], y[AGGMG_FGMRES_MAX_RESTART];
   int it = 0;
@@ -3868,12 +3861,12 @@ static int launch_res_multi_t(aggmg_ctx* ctx, ResMultiArgs m) {
 static int residual_multi(aggmg_ctx* ctx, aggmg_op* A, const double* X, int64_t ldx, const double* B, int64_t ldb, int64_t ncols,
                           double* R, int64_t ldr) {
   if (!res_multi_ok(A)) {   // column by column: the single-vector residual on every column slice
-    double* zero = nullptr;
+    WorkLease zero;
     if (!B) {
-      CHECK(solv_vec(ctx, 4, A->m, &zero));
+      CHECK(solv_lease(ctx, kSolvZero, A->m, "residual_multi", &zero));
       HIPCHK(hipMemsetAsync(zero, 0, A->m * sizeof(double), ctx->stream));
     }
-    for (int64_t j = 0; j < ncols; ++j) CHECK(aggmg_residual_dev(ctx, A, X + j * ldx, B ? B + j * ldb : zero, R + j * ldr));
+    for (int64_t j = 0; j < ncols; ++j) CHECK(aggmg_residual_dev(ctx, A, X + j * ldx, B ? B + j * ldb : zero.get(), R + j * ldr));
     return AGGMG_OK;
   }
   const BtdDev& b = *A->btd;
@@ -3988,12 +3981,11 @@ extern "C" int aggmg_pcg_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* 
   if (ranges_overlap(X, span, B, span)) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_pcg_multi_dev: X must not overlap B");
   HIPCHK(hipSetDevice(ctx->device));
   CHECK(cols_scalars(ctx, K));
-  double *R = nullptr, *Z = nullptr, *P = nullptr, *Q = nullptr;
-  CHECK(solv_vec(ctx, 0, N * K, &R));
-  CHECK(solv_vec(ctx, 1, N * K, &Z));
-  CHECK(solv_vec(ctx, 2, N * K, &P));
-  CHECK(solv_vec(ctx, 3, N * K, &Q));
-  double *rz = cols_sc(ctx, 0), *pq = cols_sc(ctx, 1), *rzn = cols_sc(ctx, 2), *nr = cols_sc(ctx, 3), *nbd = cols_sc(ctx, 5);
+  WorkLease vec[4];   // (kSolvZero stays free: residual_multi takes it)
+  for (int s = 0; s < 4; ++s) CHECK(solv_lease(ctx, (SolvSlot)s, N * K, "aggmg_pcg_multi_dev", &vec[s]));
+  double *R = vec[kSolvR], *Z = vec[kSolvZ], *P = vec[kSolvP], *Q = vec[kSolvQ];
+  double *rz = cols_sc(ctx, kColRz), *pq = cols_sc(ctx, kColPq), *rzn = cols_sc(ctx, kColRzNew), *nr = cols_sc(ctx, kColRes),
+         *nbd = cols_sc(ctx, kColNormB);
   const unsigned grid = (unsigned)((N + kThreads - 1) / kThreads);
   std::vector<double> nb((size_t)K), res((size_t)K);
   std::vector<char> fin((size_t)K);
@@ -4012,12 +4004,11 @@ extern "C" int aggmg_pcg_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* 
     CHECK(act.upload(ctx));
     CHECK(residual_multi(ctx, A, P, N, nullptr, 0, na, Q, N));                             // q = -A p
     CHECK(dev_dot_cols(ctx, N, na, P, N, Q, N, pq, 0));
-    for (int64_t c0 = 0; c0 < na; c0 += kColsGridMax) {
-      const unsigned kc = (unsigned)std::min<int64_t>(kColsGridMax, na - c0);
+    for_col_chunks(na, [&](int64_t c0, unsigned kc) {
       hipLaunchKernelGGL(pcg_xr_cols_kernel, dim3(grid, kc), dim3(kThreads), 0, ctx->stream, N, X, ld,
                          (const int*)(ctx->cols_map + c0), R + c0 * N, (const double*)(P + c0 * N), (const double*)(Q + c0 * N), N,
                          (const double*)(rz + c0), (const double*)(pq + c0));
-    }
+    });
     HIPCHK(hipGetLastError());
     CHECK(dev_dot_cols(ctx, N, na, R, N, R, N, nr, 1));
     CHECK(read_scalars(ctx, nr, na, res.data()));
@@ -4043,11 +4034,10 @@ extern "C" int aggmg_pcg_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* 
     CHECK(aggmg_vcycle_multi_dev(ctx, h, nullptr, R, nn, N, nPre, nPost, alpha, Z));
     work += nn;
     CHECK(dev_dot_cols(ctx, N, nn, R, N, Z, N, rzn, 0));
-    for (int64_t c0 = 0; c0 < nn; c0 += kColsGridMax) {
-      const unsigned kc = (unsigned)std::min<int64_t>(kColsGridMax, nn - c0);
+    for_col_chunks(nn, [&](int64_t c0, unsigned kc) {
       hipLaunchKernelGGL(pcg_p_cols_kernel, dim3(grid, kc), dim3(kThreads), 0, ctx->stream, N, P + c0 * N, (const double*)(Z + c0 * N), N,
                          (const double*)(rzn + c0), (const double*)(rz + c0));
-    }
+    });
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(rz, rzn, (size_t)nn * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
   }
@@ -4081,12 +4071,10 @@ extern "C" int aggmg_multigrid_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const do
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return AGGMG_OK;
   }
-  double *Xa = nullptr, *Xb = nullptr, *Bw = nullptr, *R = nullptr;
-  CHECK(solv_vec(ctx, 0, N * K, &R));
-  CHECK(solv_vec(ctx, 1, N * K, &Xa));
-  CHECK(solv_vec(ctx, 2, N * K, &Xb));
-  CHECK(solv_vec(ctx, 3, N * K, &Bw));
-  double *nr = cols_sc(ctx, 3), *ne = cols_sc(ctx, 4), *nbd = cols_sc(ctx, 5);
+  WorkLease vec[4];
+  for (int s = 0; s < 4; ++s) CHECK(solv_lease(ctx, (SolvSlot)s, N * K, "aggmg_multigrid_multi_dev", &vec[s]));
+  double *R = vec[kSolvR], *Xa = vec[kSolvZ], *Xb = vec[kSolvP], *Bw = vec[kSolvQ];
+  double *nr = cols_sc(ctx, kColRes), *ne = cols_sc(ctx, kColErr), *nbd = cols_sc(ctx, kColNormB);
   std::vector<double> nb((size_t)K), res((size_t)K), err((size_t)K);
   std::vector<char> fin((size_t)K);
   CHECK(dev_dot_cols(ctx, N, K, B, ld, B, ld, nbd, 1));

@@ -284,9 +284,12 @@ int cgt_smooth_ext(aggmg_ctx* ctx, const CgtDev& g, const double* u_in, const do
   c.b_ext = true;
   c.dst = u_out;
   c.dst_ext = true;
+  WorkLease t0, t1;   // (held across cgt_run: the chain keeps raw pointers)
   if (nsweeps > cgt_max_sweeps(g.m, g.sw)) {
-    CHECK(scratch(ctx, 0, g.ne * g.m, &c.t0));
-    CHECK(scratch(ctx, 1, g.ne * g.m, &c.t1));
+    CHECK(scratch_lease(ctx, kScratchPing, g.ne * g.m, "cgt_smooth_ext", &t0));
+    CHECK(scratch_lease(ctx, kScratchPong, g.ne * g.m, "cgt_smooth_ext", &t1));
+    c.t0 = t0;
+    c.t1 = t1;
   }
   CgtArgs none;
   std::memset(&none, 0, sizeof(none));
@@ -371,7 +374,11 @@ int cgt_mid(aggmg_ctx* ctx, aggmg_hier* h, const double* cur, double* alt, const
   ch.dst = alt;
   ch.dst_ext = false;
   ch.t0 = l.tmp;
-  if (nsweeps > 2 * cgt_max_sweeps(g.m, g.sw)) CHECK(scratch(ctx, 0, g.ne * g.m, &ch.t1));
+  WorkLease t1;   // (held across cgt_run)
+  if (nsweeps > 2 * cgt_max_sweeps(g.m, g.sw)) {
+    CHECK(scratch_lease(ctx, kScratchPing, g.ne * g.m, "cgt_mid", &t1));
+    ch.t1 = t1;
+  }
   CgtArgs first, last;
   std::memset(&first, 0, sizeof(first));
   std::memset(&last, 0, sizeof(last));

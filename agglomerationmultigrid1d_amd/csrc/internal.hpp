@@ -1,6 +1,6 @@
 // Shared internals of libaggmg_hip: the objects behind the opaque handles of include/aggmg_hip.h
 // and the small host helpers every translation unit of the library uses (error reporting, the
-// owner of device memory, scratch vectors, the HIP-event profiler, the set-up thread pool).
+// owner of device memory, the leased work vectors, the HIP-event profiler, the set-up thread pool).
 #pragma once
 #include "../../include/aggmg_hip.h"
 
@@ -47,6 +47,7 @@ inline int fail(aggmg_ctx* ctx, int code, const std::string& msg);   // (defined
   } while (0)
 
 #include "devmem.hpp"
+#include "workspace.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // objects behind the opaque handles
@@ -73,11 +74,11 @@ struct aggmg_ctx {
   int profiling = 0;  // 0 off, 1 every launch, 2 only the fine-level fused-down launch (dominant kernel)
   std::vector<ProfEvent> prof;
   std::vector<hipEvent_t> ev_pool;
-  // scratch vectors for ping-pong / temporaries, grown on demand
-  DevArray<double> scratch[3];
-  // outer-solver work space (aggmg_multigrid_dev, aggmg_pcg_dev, ...): vectors, dot-product
-  // partials and the device-resident scalars
-  DevArray<double> solv[5];
+  // scratch vectors for ping-pong / temporaries, grown on demand, leased slot by slot (workspace.hpp: ScratchSlot)
+  WorkVectors<kScratchSlots> scratch;
+  // outer-solver work space (aggmg_multigrid_dev, aggmg_pcg_dev, ...): leased vectors (SolvSlot), dot-product
+  // partials and the device-resident scalars (kSc*)
+  WorkVectors<kSolvSlots> solv;
   DevArray<double> solv_part, solv_sc;
   // K-column solver loops (aggmg_pcg_multi_dev, aggmg_multigrid_multi_dev, aggmg_dot_cols_dev): for cols_cap columns,
   // kDotBlocks partials and kColsScalars scalars per column, and the slot -> column maps of the active set; lazy, grown
@@ -428,10 +429,22 @@ inline LevelPath level_path(const aggmg_hier* h, int k) {
   return LevelPath::Generic;
 }
 
-inline int scratch(aggmg_ctx* ctx, int slot, int64_t len, double** out) {
-  CHECK(ctx->scratch[slot].reserve(ctx, len));
-  *out = ctx->scratch[slot];
-  return AGGMG_OK;
+// A slot of the context's shared vectors for `who` (a string literal), held until *lease goes out of scope.  A slot that
+// is held already is a defect of the library, not of the caller: the entry point fails instead of sharing the memory.
+template <int NSLOT>
+inline int lease_work(aggmg_ctx* ctx, WorkVectors<NSLOT>& w, const char* family, int slot, int64_t len, const char* who,
+                      WorkLease* lease) {
+  const WorkTake t = w.take(ctx, slot, len, who, lease);
+  if (t.refused())
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, std::string("internal: work vector ") + family + "[" + std::to_string(slot) +
+                                                "] wanted by " + t.wanted_by + " is held by " + t.held_by);
+  return t.code;
+}
+inline int scratch_lease(aggmg_ctx* ctx, ScratchSlot slot, int64_t len, const char* who, WorkLease* lease) {
+  return lease_work(ctx, ctx->scratch, "scratch", slot, len, who, lease);
+}
+inline int solv_lease(aggmg_ctx* ctx, SolvSlot slot, int64_t len, const char* who, WorkLease* lease) {
+  return lease_work(ctx, ctx->solv, "solv", slot, len, who, lease);
 }
 
 // ---------------------------------------------------------------------------------------------

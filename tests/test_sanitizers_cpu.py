@@ -5,7 +5,8 @@
  * the library's host-only planners (agglomerationmultigrid1d_amd/csrc/host_plan.hpp: cyclic-reduction step / stage plans,
    tile subsets of a launch, staging slices, the chunk route of a partitioned run) as a host-compiled unit test under
    AddressSanitizer + UBSan;
- * the owner of the library's device memory (agglomerationmultigrid1d_amd/csrc/devmem.hpp) over malloc / free, the same way.
+ * the owner of the library's device memory (agglomerationmultigrid1d_amd/csrc/devmem.hpp) over malloc / free, the same way;
+ * the leased work vectors of the context (agglomerationmultigrid1d_amd/csrc/workspace.hpp), the same way.
 Skipped (not failed) where a sanitizer runtime is missing from the toolchain."""
 import os
 import shutil
@@ -117,3 +118,18 @@ def test_device_memory_owner_under_asan_ubsan():
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert not any(s in r.stderr for s in BAD), r.stderr[-3000:]
     assert "devmem OK" in r.stdout
+
+
+def test_leased_work_vectors_under_asan_ubsan():
+    """take / release, a refused second take that names both holders, release through an early return and through moves,
+    pointers into the other slots while one grows (written through afterwards), the wait counted only where a non-empty
+    array grows, nothing live at exit; the static_asserts of the two scalar tables compile with the header"""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    d = os.path.join(ROOT, "tests", "host")
+    _make(d, "test_workspace")
+    r = subprocess.run([os.path.join(d, "test_workspace")], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert not any(s in r.stderr for s in BAD), r.stderr[-3000:]
+    assert "workspace OK" in r.stdout
