@@ -597,6 +597,42 @@ class HybridSchwarzSmoother(_BlockSmoother):
     _kind = 1
 
 
+def element_patch_lists(m, ne, width=2):
+    """index lists (1-based, (w m) x nb, column e = patch {e, .., e + w - 1}, w = min(width, ne)) of the element
+    patches ElementPatchSchwarz smooths with: what HybridSchwarzSmoother(A, lists) takes for the same smoother"""
+    w = min(int(width), int(ne))
+    nb = int(ne) - w + 1
+    return np.arange(nb, dtype=np.int64)[None, :] * int(m) + np.arange(1, w * int(m) + 1, dtype=np.int64)[:, None]
+
+
+class ElementPatchSchwarz(AbstractSmoother):
+    """EXTENSION: Schwarz smoother of a DG level on overlapping patches of `width` consecutive elements (C ABI
+    aggmg_patch_schwarz_setup) -- the arithmetic of HybridSchwarzSmoother (hybrid=True: the summed patch corrections
+    divided by the number of patches covering the element, src/smoother.jl:24-46) or AdditiveSchwarzSmoother
+    (hybrid=False) on element_patch_lists(m, ne, width).  width = 2 on an operator that is block tridiagonal in the
+    blocking of ne elements of m rows runs the fused, LDS-tiled sweep kernel (`.fused`); everything else the generic
+    kernels on the lists, with the same results to round-off.
+    The smoothed cycle is not a symmetric preconditioner: use fgmres, not pcg, around it."""
+
+    def __init__(self, A, m, ne, width=2, hybrid=True, ctx=None):
+        self.A = _as_op(A, ctx=ctx)
+        self.m, self.ne = int(m), int(ne)
+        h = ctypes.c_void_p()
+        c = self.A.ctx
+        c.check(c.lib.aggmg_patch_schwarz_setup(c.handle, self.A.handle, self.m, self.ne, int(width), int(bool(hybrid)),
+                                                ctypes.byref(h)))
+        self.handle = h
+        w, hy, fu = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        c.check(c.lib.aggmg_smoother_patch_info(c.handle, h, ctypes.byref(w), ctypes.byref(hy), ctypes.byref(fu)))
+        self.width, self.hybrid, self.fused = w.value, bool(hy.value), bool(fu.value)
+        self.mBlockInds = element_patch_lists(self.m, self.ne, self.width)
+
+    def inverse_blocks(self):
+        """the explicit inverses of the patch blocks, (nb, w m, w m) (C ABI aggmg_smoother_download_blocks)"""
+        bm, nb = self.mBlockInds.shape
+        return _download_blocks(self.A.ctx, self.handle, nb, bm)
+
+
 class _BlockObject(AbstractSmoother):
     """device handle of a block-diagonal matrix or of its factorisation"""
 
@@ -738,6 +774,9 @@ def dg_smoother(dgMesh, A, smootherType, ctx=None):
         return BlockJacobi(A, _mesh_block_inds(dgMesh), ctx)
     if smootherType == 'blockGS':    # extension, see BlockGaussSeidel
         return BlockGaussSeidel(A, _mesh_block_inds(dgMesh), ctx)
+    if smootherType == 'patchSchwarz':    # extension, see ElementPatchSchwarz: hybrid patches of two elements
+        m, ne = _mesh_block_inds(dgMesh).shape
+        return ElementPatchSchwarz(A, m, ne, ctx=ctx)
     raise ArgumentError(f"dg_smoother: unknown smoother type {smootherType!r}")
 
 
@@ -854,7 +893,7 @@ class MeshHierarchy:
 
     @classmethod
     def from_dg_operators(cls, mMeshes, A, G, D, C, mInterpolation, mMassMatrices, ctx=None, keep_host=True,
-                          coarse_mode=_lib.COARSE_AUTO):
+                          coarse_mode=_lib.COARSE_AUTO, smoothers='blockJac'):
         """MeshHierarchy(mMeshes, mBdConds, A, G, D, C; nDG, nAgg) (src/mesh_heirarchy.jl:140-181, with the
         agglomerated levels of SURVEY D4) given the interpolation matrices L_k and the mass matrices
         (BlockDiagonal) of the coarser levels: the recurrences of :79-84 / :98-103 run on the device --
@@ -866,11 +905,16 @@ class MeshHierarchy:
         (aggmg_op_transpose, aggmg_sp_matmul, aggmg_bd_sp_apply, aggmg_sp_sub, aggmg_blockjacobi_setup).
         mMeshes[k] need `mBlockInds` (or `mElements` / `mP`); mMassMatrices[k] is the BlockDiagonal of
         level k + 1.  The Galerkin operators stay in HBM; H.mGradient / mDivergence / mC / mStiffness hold
-        DeviceOperators (`.to_scipy()` reads one back)."""
+        DeviceOperators (`.to_scipy()` reads one back).
+        smoothers: the dg_smoother type of every smoothed level, or a list of one per level ('blockJac', the
+        reference's; 'patchSchwarz', 'blockGS', 'jac': extensions / other reference types)."""
         ctx = ctx or default_context()
         n = len(mMeshes)
         if n < 1:
             raise ArgumentError("At least one DG mesh required.")
+        kinds = [smoothers] * (n - 1) if isinstance(smoothers, str) else list(smoothers)
+        if len(kinds) != n - 1:
+            raise ArgumentError("smoothers: one smoother type per non-coarsest level")
         if len(mInterpolation) != n - 1 or len(mMassMatrices) != n - 1:
             raise ArgumentError("Length of vector of meshes does not match inputed number of DG and "
                                 "agglomerated meshes.")
@@ -887,7 +931,7 @@ class MeshHierarchy:
             Mlu = M if isinstance(M, BlockDiagonalLU) else M.lu()
             St.append(Cs[k + 1].sub(Ds[k + 1].matmul(Mlu.solve(Gs[k + 1]))))
             Lt.free()
-        sms = [BlockJacobi(St[k], _mesh_block_inds(mMeshes[k]), ctx) for k in range(n - 1)]
+        sms = [dg_smoother(mMeshes[k], St[k], kinds[k], ctx) for k in range(n - 1)]
         H = cls(mMeshes, St, sms, Ls, mGradient=Gs, mDivergence=Ds, mC=Cs, ctx=ctx, keep_host=keep_host,
                 coarse_mode=coarse_mode)
         return H

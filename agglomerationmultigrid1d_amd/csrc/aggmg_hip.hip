@@ -9,6 +9,7 @@
 #include "multi_kernels.hpp"
 #include "multi_solve_kernels.hpp"
 #include "pair_kernels.hpp"
+#include "patch_kernels.hpp"
 #include "krylov_kernels.hpp"
 #include "host_gmres.hpp"
 
@@ -416,7 +417,7 @@ extern "C" int aggmg_smoother_free(aggmg_ctx* ctx, aggmg_smoother* sm) {
 
 extern "C" int aggmg_smoother_is_structured(aggmg_ctx* ctx, const aggmg_smoother* sm, int* out) {
   if (!ctx || !sm || !out) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smoother_is_structured: NULL");
-  *out = (sm->btd || sm->cgt) ? 1 : 0;
+  *out = (sm->btd || sm->cgt || sm->patch) ? 1 : 0;
   return AGGMG_OK;
 }
 
@@ -833,11 +834,192 @@ static int btd_smooth(aggmg_ctx* ctx, const BtdDev& b, const double* u_in, const
   return AGGMG_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// element-patch Schwarz (patch_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+static_assert(kPatchMaxSweeps == kSweepWeights, "a patch launch takes as many sweeps as its weights array holds");
+
+// The (M, couplings) patch_sweep_kernel is instantiated for: every element-block form set-up produces (compressed
+// couplings 2 .. 9, dense ones 1 .. 5) up to 8 rows per element.  None of them needs scratch.
+static bool patch_instantiated(int m, bool cmp) { return cmp ? (m >= 2 && m <= 8) : (m >= 1 && m <= 5); }
+
+template <int M, bool CMP>
+static int launch_patch_t(aggmg_ctx* ctx, PatchArgs a, const SweepWeights& wts, bool hybrid) {
+  constexpr int NS = PatchSlabs<M>::NS;
+  static_assert(NS == patch_slabs(M), "the planner sizes the tile the kernel is instantiated for");
+  const PatchTilePlan plan = patch_tile_plan(M, a.nsweeps);   // host_plan.hpp
+  if (plan.owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: patch sweep launch without a tile");
+  a.owned = plan.owned;
+  a.halo = plan.halo;
+  const int64_t ntiles = patch_tiles(a.ne, plan.owned);
+  if (ntiles == 0) return AGGMG_OK;
+  if (hybrid)
+    hipLaunchKernelGGL((patch_sweep_kernel<M, CMP, NS, true>), dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, a, wts);
+  else
+    hipLaunchKernelGGL((patch_sweep_kernel<M, CMP, NS, false>), dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, a, wts);
+  HIPCHK(hipGetLastError());
+  return AGGMG_OK;
+}
+
+static int launch_patch(aggmg_ctx* ctx, const PatchDev& P, const PatchArgs& a, const SweepWeights& wts) {
+  const bool cmp = P.btd->cmp;
+#define CASE(MM)                                                             \
+  case MM:                                                                   \
+    return cmp ? launch_patch_t<MM, true>(ctx, a, wts, P.hybrid) : launch_patch_t<MM, false>(ctx, a, wts, P.hybrid);
+#define CASE_C(MM) \
+  case MM:         \
+    if (cmp) return launch_patch_t<MM, true>(ctx, a, wts, P.hybrid); \
+    break;
+  switch (P.m) {
+    case 1:
+      if (!cmp) return launch_patch_t<1, false>(ctx, a, wts, P.hybrid);
+      break;
+      CASE(2) CASE(3) CASE(4) CASE(5) CASE_C(6) CASE_C(7) CASE_C(8)
+  }
+#undef CASE
+#undef CASE_C
+  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: block size not instantiated for the patch sweep kernel");
+}
+
+// nsweeps sweeps from u_in (may be nullptr = zero) into u_out (!= u_in), in launches of up to patch_max_sweeps
+static int patch_smooth(aggmg_ctx* ctx, const PatchDev& P, const double* u_in, const double* rhs, Damping alpha, int nsweeps,
+                        double* u_out, int level) {
+  const int64_t N = P.ne * P.m;
+  if (nsweeps == 0) {
+    if (u_in && u_in != u_out)
+      HIPCHK(hipMemcpyAsync(u_out, u_in, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    else if (!u_in)
+      HIPCHK(hipMemsetAsync(u_out, 0, N * sizeof(double), ctx->stream));
+    return AGGMG_OK;
+  }
+  const int smax = patch_max_sweeps(P.m);
+  const int nchunks = patch_chunks(nsweeps, smax);
+  if (nchunks == 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: patch sweeps without a tile");
+  // chunk chain: src -> (scratch0 / scratch1 alternating) -> ... -> u_out
+  WorkLease t0, t1;
+  if (nchunks > 1) {
+    CHECK(scratch_lease(ctx, kScratchPing, N, "patch_smooth", &t0));
+    if (nchunks > 2) CHECK(scratch_lease(ctx, kScratchPong, N, "patch_smooth", &t1));
+  }
+  const BtdDev& b = *P.btd;
+  const double* src = u_in;
+  for (int c = 0; c < nchunks; ++c) {
+    const int s = patch_chunk_sweeps(nsweeps, smax, c);
+    double* dst = (c == nchunks - 1) ? u_out : (((nchunks - 1 - c) % 2 == 1) ? t0.get() : t1.get());
+    PatchArgs a{b.dblk, b.scol, b.qrow, b.sub, b.sup, P.zrows, P.ne, b.c_sub, b.r_sup, src, rhs, dst, s, 0, 0};
+    {
+      ProfScope ps(ctx, AGGMG_KIND_SMOOTH, level);
+      CHECK(launch_patch(ctx, P, a, alpha.from(c * smax).launch(s)));
+    }
+    src = dst;
+  }
+  return AGGMG_OK;
+}
+
+// index lists of the patches {e, .., e + width - 1}, e = 0 .. ne - width (a level of fewer elements: one patch of all)
+static void patch_lists(int64_t m, int64_t ne, int width, std::vector<int64_t>* lists, int64_t* bm, int64_t* nb) {
+  const int64_t w = std::min<int64_t>(width, ne);
+  *bm = w * m;
+  *nb = ne - w + 1;
+  lists->resize((size_t)(*nb * *bm));
+  for (int64_t p = 0; p < *nb; ++p)
+    for (int64_t j = 0; j < *bm; ++j) (*lists)[p * *bm + j] = p * m + j;
+}
+
+extern "C" int aggmg_patch_schwarz_setup(aggmg_ctx* ctx, aggmg_op* A, int64_t m, int64_t ne, int width, int hybrid,
+                                         aggmg_smoother** out) {
+  if (!ctx || !A || !out) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_patch_schwarz_setup: NULL argument");
+  *out = nullptr;
+  if (A->m != A->n) return fail(ctx, AGGMG_ERR_DIMENSION, "aggmg_patch_schwarz_setup: operator is not square");
+  if (width < 2 || width > 4) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_patch_schwarz_setup: width must be 2, 3 or 4");
+  if (m < 1 || ne < 1 || m * width > 64)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_patch_schwarz_setup: rows per element must be in 1 .. 64 / width, elements >= 1");
+  if (A->m != m * ne) return fail(ctx, AGGMG_ERR_DIMENSION, "aggmg_patch_schwarz_setup: operator size is not m * ne");
+  if (A->m * width >= ((int64_t)1 << 31)) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_patch_schwarz_setup: width * m * ne >= 2^31");
+  HIPCHK(hipSetDevice(ctx->device));
+  std::vector<int64_t> lists;
+  int64_t bm = 0, nb = 0;
+  // the fused form: patches of two elements on an operator that is block tridiagonal in the element blocking, in a block
+  // size the kernel is instantiated for.  The element blocks come from the block-Jacobi set-up of the element lists
+  // (scatter, pattern detection, A->btd); that smoother itself is not kept.
+  std::shared_ptr<BtdDev> eb;
+  if (width == 2 && ne >= 2 && m <= 9) {
+    patch_lists(m, ne, 1, &lists, &bm, &nb);
+    aggmg_smoother* elem = nullptr;
+    const int st = aggmg_blockjacobi_setup(ctx, A, m, ne, lists.data(), 0, 0, &elem);
+    if (st != AGGMG_OK && st != AGGMG_ERR_SINGULAR) return st;   // (a singular element block: the patches may still be regular)
+    if (elem && elem->btd && patch_instantiated((int)m, elem->btd->cmp) && patch_max_sweeps((int)m) >= 1) eb = elem->btd;
+    if (elem) CHECK(aggmg_smoother_free(ctx, elem));
+  }
+  if (!eb) {   // the generic route on the lists, as everywhere: the same results to round-off
+    patch_lists(m, ne, width, &lists, &bm, &nb);
+    CHECK(aggmg_blockjacobi_setup(ctx, A, bm, nb, lists.data(), 0, hybrid ? 1 : 0, out));
+    (*out)->patch_width = width;
+    return AGGMG_OK;
+  }
+  auto sm = std::make_unique<aggmg_smoother>();
+  sm->kind = hybrid ? 2 : 1;
+  sm->A = A;
+  sm->N = A->m;
+  sm->m = 2 * m;
+  sm->nb = ne - 1;
+  sm->overlapping = true;
+  sm->patch_width = 2;
+  auto P = std::make_shared<PatchDev>();
+  P->m = (int)m;
+  P->ne = ne;
+  P->hybrid = hybrid != 0;
+  P->btd = eb;
+  {
+    const int64_t words = (ne - 1) * 4 * m * m;
+    DevArray<double> blocks, zinv;
+    CHECK(blocks.alloc(ctx, words));
+    CHECK(zinv.alloc(ctx, words));
+    hipLaunchKernelGGL(patch_assemble_kernel, dim3((unsigned)((words + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream,
+                       words, (int)m, eb->cmp ? 1 : 0, eb->c_sub, eb->r_sup, (const double*)eb->dblk, (const double*)eb->scol,
+                       (const double*)eb->qrow, (const double*)eb->sub, (const double*)eb->sup, blocks.get());
+    HIPCHK(hipGetLastError());
+    int64_t sing = -1;
+    CHECK(setup_invert_blocks(ctx, ne - 1, (int)(2 * m), blocks, 0, zinv, &sing));
+    if (sing >= 0)
+      return fail(ctx, AGGMG_ERR_SINGULAR,
+                  "aggmg_patch_schwarz_setup: singular patch " + std::to_string(sing + 1) + " (SingularException)");
+    const int64_t zw = A->m * 4 * m;
+    CHECK(P->zrows.alloc(ctx, zw));
+    hipLaunchKernelGGL(patch_zrows_kernel, dim3((unsigned)((zw + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream, zw,
+                       (int)m, ne, (const double*)zinv, P->zrows.get());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // the temporaries go out of scope
+  }
+  sm->patch = P;
+  *out = sm.release();
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_smoother_patch_info(aggmg_ctx* ctx, const aggmg_smoother* sm, int* width, int* hybrid, int* fused) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!sm || !width || !hybrid || !fused) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smoother_patch_info: NULL argument");
+  *width = sm->patch_width;   // 0: not an element-patch Schwarz smoother
+  *hybrid = sm->patch_width && sm->kind == 2 ? 1 : 0;
+  *fused = sm->patch ? 1 : 0;
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_patch_tile_plan(int m, int nsweeps, int* tile_elems, int* owned, int* max_sweeps) {
+  if (!tile_elems || !owned || !max_sweeps) return AGGMG_ERR_ARGUMENT;
+  const PatchTilePlan p = patch_tile_plan(m, nsweeps);   // host_plan.hpp: what launch_patch_t runs
+  *tile_elems = p.te;
+  *owned = p.owned;
+  *max_sweeps = patch_max_sweeps(m);
+  return AGGMG_OK;
+}
+
 // generic: one sweep u_out = u_in + alpha * S^{-1}(b - A u_in); u_out may alias u_in for block
 // smoothers, must differ for point Jacobi.
 static int generic_sweep(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* u_in, const double* rhs,
                          double alpha, double* u_out, int level) {
   const int64_t N = A->m;
+  if (sm->patch) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: generic sweep of a fused element-patch Schwarz smoother");
   if (sm->kind == 0) {
     ProfScope ps(ctx, AGGMG_KIND_JACOBI, level);
     CHECK(op_ensure_csr(ctx, A));
@@ -978,13 +1160,17 @@ static int smooth_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const dou
   const int64_t N = A->m;
   if (N == 0) return AGGMG_OK;
   const bool chain = sm->cgt && sm->A == A;   // CG chain form: fused point-Jacobi sweeps
-  if (chain || (sm->btd && sm->A == A)) {
+  const bool patch = sm->patch && sm->A == A;   // fused element-patch Schwarz sweeps
+  if (sm->patch && !patch) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth: the smoother was set up on another operator");
+  if (chain || patch || (sm->btd && sm->A == A)) {
     // (the fused forms want u_out != u_in: an in-place request is staged through scratch, an extra copy)
     WorkLease stage;
     if (u_out == u_in) CHECK(scratch_lease(ctx, kScratchStage, N, "aggmg_smooth", &stage));
     double* dst = stage.held() ? stage.get() : u_out;
     if (chain)
       CHECK(cgt_smooth_ext(ctx, *sm->cgt, u_in, b, alpha, nsweeps, dst, 0));
+    else if (patch)
+      CHECK(patch_smooth(ctx, *sm->patch, u_in, b, alpha, nsweeps, dst, 0));
     else
       CHECK(btd_smooth(ctx, *sm->btd, u_in, b, alpha, nsweeps, dst, 0, N, sm->gs ? 1 : 0));
     if (dst != u_out) HIPCHK(hipMemcpyAsync(u_out, dst, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
@@ -1128,7 +1314,10 @@ extern "C" int aggmg_smoother_apply(aggmg_ctx* ctx, aggmg_smoother* sm, const do
     const double* bc = dB.p + c * N;
     double* yc = dY.p + c * N;
     ProfScope ps(ctx, AGGMG_KIND_BLOCK_APPLY, 0);
-    if (sm->kind == 0) {
+    if (sm->patch) {
+      // fused element-patch Schwarz: one sweep of weight alpha from the zero iterate is alpha * S^{-1} b
+      CHECK(patch_smooth(ctx, *sm->patch, nullptr, bc, Damping(alpha), 1, yc, 0));
+    } else if (sm->kind == 0) {
       // alpha * (Diagonal \ B): reuse the scaled-axpy kernel with counts := diag
       hipLaunchKernelGGL(axpy_scaled_kernel, dim3(nb2), dim3(kThreads), 0, ctx->stream, N, (const double*)nullptr,
                          bc, (const double*)sm->diag, alpha, yc);
@@ -1776,16 +1965,17 @@ extern "C" int aggmg_hier_create(aggmg_ctx* ctx, int nlevels, aggmg_op* const* s
   // structured transfers between consecutive levels whose fine side runs the fused kernel
   for (int k = 0; k + 1 < nlevels; ++k) {
     Level& l = h->lv[k];
-    if (!(l.S->btd && l.S->A == l.A)) continue;
+    const BtdDev* eb = level_btd(l);   // the block-Jacobi smoother's form, or the element blocks of a patch smoother
+    if (!eb) continue;
     int hint = 0;
-    if (k + 2 < nlevels && h->lv[k + 1].S && h->lv[k + 1].S->btd) hint = h->lv[k + 1].S->btd->m;
+    if (k + 2 < nlevels && level_btd(h->lv[k + 1])) hint = level_btd(h->lv[k + 1])->m;
     auto tb = std::make_unique<TransferBtd>();
     bool ok = false;
     // every fine row's stored columns must lie in the mc modes of coarse element (fine element) / rho
-    CHECK(setup_transfer_btd(ctx, l.L, l.S->btd.get(), l.S->btd->m, l.S->btd->ne, hint, tb.get(), &ok));
+    CHECK(setup_transfer_btd(ctx, l.L, eb, eb->m, eb->ne, hint, tb.get(), &ok));
     if (ok) l.tb = std::move(tb);
-    // the level's distinct operator records, where they are few (AGGMG_OPT_OPERATOR_DICTIONARY)
-    if (l.tb && ctx->op_dict) CHECK(setup_op_dictionary(ctx, *l.S->btd, *l.tb, &l.dict));
+    // the level's distinct operator records, where they are few (AGGMG_OPT_OPERATOR_DICTIONARY): block-Jacobi levels
+    if (l.tb && l.S->btd && ctx->op_dict) CHECK(setup_op_dictionary(ctx, *l.S->btd, *l.tb, &l.dict));
   }
   // the same for the levels a two-level launch may take (pair_ok: below the finest, above the coarsest)
   for (int k = 1; ctx->op_dict && k + 1 < nlevels; ++k) {
@@ -2187,6 +2377,54 @@ static int btd_mid(aggmg_ctx* ctx, aggmg_hier* h, const double* cur, double* alt
   return launch_btd(ctx, *l.S->btd, a, nsweeps + 1, TileSel(), chk);
 }
 
+// Element-patch Schwarz levels (LevelPath::Patch): chunked patch sweeps, and around them the zero-sweep fused launch of the
+// element-block form -- residual + restriction (the launch of aggmg_residual_dev with a restriction behind it), or the
+// prolongation -- where the level has the structured transfer and that launch a tile; otherwise the generic launches.
+static bool patch_transfer_ok(const Level& l, int residual, const TransferBtd* tout) {
+  if (!l.tb) return false;
+  const BtdDev& B = *l.S->patch->btd;
+  TileQuery q;
+  q.launch = kTileFused;
+  q.te = btd_tile_elems(B);
+  q.halo = residual;
+  if (tout) {
+    q.var_agg = tout->rho == 0;
+    q.align = tout->rho ? tout->rho : 1;
+    q.agg_shift = xfer_agg_shift(*tout);
+  }
+  return launch_has_tile(q);
+}
+static int patch_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uin, const double* rhs, int nPre, double alpha) {
+  Level& l = h->lv[k];
+  const PatchDev& P = *l.S->patch;
+  CHECK(patch_smooth(ctx, P, uin, rhs, l.damp_pre(alpha), nPre, l.u[0], k));
+  if (patch_transfer_ok(l, 1, l.tb.get())) {
+    FusedLaunch a = fused_sweeps(*P.btd, l.u[0], rhs, nullptr, 0.0, 0);
+    fused_descent(a, h, l, h->lv[k + 1].rhs);
+    a.ld_out = nullptr;   // the explicit residual's restriction: (L'D) belongs to the block-Jacobi stencil form
+    a.lf_out = l.tb->lf;
+    ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
+    return launch_btd(ctx, *P.btd, a, 1);
+  }
+  return generic_restrict_residual(ctx, h, k, rhs, false);
+}
+static int patch_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* rhs, int nPost, double alpha, double* dst) {
+  Level& l = h->lv[k];
+  const PatchDev& P = *l.S->patch;
+  // the prolonged iterate goes through l.tmp: the fused launch wants another vector than its input, the sweeps too
+  if (patch_transfer_ok(l, 0, nullptr)) {
+    FusedLaunch a = fused_sweeps(*P.btd, l.u[0], rhs, l.tmp, 0.0, 0);
+    fused_ascent(a, l, coarse_result(h, k));
+    {
+      ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
+      CHECK(launch_btd(ctx, *P.btd, a, 0));
+    }
+    return patch_smooth(ctx, P, l.tmp, rhs, l.damp_post(alpha), nPost, dst, k);
+  }
+  CHECK(generic_prolong_add(ctx, h, k));
+  return patch_smooth(ctx, P, l.u[0], rhs, l.damp_post(alpha), nPost, dst, k);
+}
+
 // Generic levels: generic_sweeps between the generic launches.  The descent sweeps in place in l.u[0] (point Jacobi:
 // with l.u[1] as its second vector, the banded form's residual straight into l.tmp); the ascent keeps its intermediate
 // sweeps in l.u[0] and writes the last one to dst (point Jacobi: with whichever of l.u[1] / l.tmp is not dst).
@@ -2221,6 +2459,7 @@ static int vcycle_down(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const do
       case LevelPath::FusedChain: CHECK(cgt_down(ctx, h, k, uin, rhs, nPre, alpha)); break;
       case LevelPath::FusedBtd:
       case LevelPath::BtdTransfer: CHECK(btd_down(ctx, h, k, uin, rhs, nPre, alpha)); break;
+      case LevelPath::Patch: CHECK(patch_down(ctx, h, k, uin, rhs, nPre, alpha)); break;
       case LevelPath::Generic: CHECK(generic_down(ctx, h, k, uin, rhs, nPre, alpha)); break;
       case LevelPath::Coarsest: break;
     }
@@ -2264,6 +2503,7 @@ static int vcycle_up(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, 
       case LevelPath::FusedChain: CHECK(cgt_up(ctx, h, k, rhs, nPost, alpha, dst)); break;
       case LevelPath::FusedBtd:   // (refuses a selection itself where the fused launch has no tile)
       case LevelPath::BtdTransfer: CHECK(btd_up(ctx, h, k, rhs, nPost, alpha, dst, nullptr, nullptr, sel)); break;
+      case LevelPath::Patch: CHECK(patch_up(ctx, h, k, rhs, nPost, alpha, dst)); break;
       case LevelPath::Generic: CHECK(generic_up(ctx, h, k, rhs, nPost, alpha, dst)); break;
       case LevelPath::Coarsest: break;
     }
@@ -2590,8 +2830,12 @@ static bool fine_mid_ok(const aggmg_hier* h, int nPre, int nPost, MidFor purpose
       // mode's own form to exist (a single descent, btd_down, takes any: without (L'D) it restricts with lf)
       if (h->restriction != AGGMG_RESTRICT_EXPLICIT && (chk || !l0.tb->ld)) return false;
       return btd_launch_ok(*l0.S, nPre + nPost, 1, l0.tb.get());   // (no tile: a ratio the halo leaves no room for)
-    default: return false;
+    case LevelPath::Patch:         // (no launch between two cycles: the loops run cycle by cycle, as on a generic fine level)
+    case LevelPath::BtdTransfer:
+    case LevelPath::Generic:
+    case LevelPath::Coarsest: break;
   }
+  return false;
 }
 
 // Histories and stopping test of launches with checkpoints (with the outer solver loops below)
@@ -2941,6 +3185,9 @@ extern "C" int aggmg_hier_level_kind(aggmg_ctx* ctx, const aggmg_hier* h, int le
     case LevelPath::Coarsest: *kind = AGGMG_LEVEL_COARSEST; break;
     case LevelPath::FusedChain: *kind = AGGMG_LEVEL_FUSED_CHAIN; break;
     case LevelPath::FusedBtd: *kind = AGGMG_LEVEL_FUSED_BTD; break;
+    case LevelPath::Patch:   // (fused sweeps; the level counts as fused where its transfer launches are)
+      *kind = h->lv[level].tb ? AGGMG_LEVEL_FUSED_BTD : AGGMG_LEVEL_GENERIC;
+      break;
     case LevelPath::BtdTransfer:   // (several launches per half-cycle, as the generic kernels)
     case LevelPath::Generic: *kind = AGGMG_LEVEL_GENERIC; break;
   }
@@ -3001,6 +3248,8 @@ extern "C" int aggmg_hier_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int 
   const bool down = kind != AGGMG_KIND_FUSED_UP, up = kind != AGGMG_KIND_FUSED_DOWN;
   const LevelPath path = level_path(h, level);
   if (path == LevelPath::FusedChain) return cgt_launch_bytes(ctx, h, level, down, up, has_x0 != 0, read_bytes, write_bytes);
+  if (path == LevelPath::Patch)   // (its sweep launch: aggmg_smoother_launch_bytes)
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_hier_launch_bytes: an element-patch Schwarz level runs its sweeps and its transfer in several launches");
   if (path != LevelPath::FusedBtd)
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_hier_launch_bytes: the level runs the generic kernels (several launches)");
   const bool pre = l.tb->ld && h->restriction == AGGMG_RESTRICT_PRECONDITIONED;
@@ -3036,6 +3285,13 @@ extern "C" int aggmg_smoother_launch_bytes(aggmg_ctx* ctx, aggmg_op* A, aggmg_sm
   const int64_t N = A->m, D = sizeof(double);
   if (what == 0 && sm->cgt && sm->A == A) return cgt_op_launch_bytes(*sm->cgt, true, read_bytes, write_bytes);
   if (what == 1 && A->cgt) return cgt_op_launch_bytes(*A->cgt, false, read_bytes, write_bytes);
+  if (what == 0 && sm->patch && sm->A == A) {
+    // b, u and the new u; per row its 4m inverse-row words, its m entries of D_e and its couplings
+    const int64_t m = sm->patch->m, ne = sm->patch->ne;
+    *read_bytes = 2 * N * D + N * 4 * m * D + N * m * D + (sm->patch->btd->cmp ? N * D + ne * m * D : 2 * N * m * D);
+    *write_bytes = N * D;
+    return AGGMG_OK;
+  }
   if (what == 0 && sm->btd && sm->A == A) {
     btd_launch_bytes(*sm->btd, true, true, false, false, nullptr, nullptr, false, read_bytes, write_bytes);
     return AGGMG_OK;

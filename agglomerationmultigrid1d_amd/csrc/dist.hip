@@ -381,6 +381,10 @@ extern "C" int aggmg_dist_create(aggmg_ctx* ctx, aggmg_hier* local, aggmg_hier* 
   if (local->coarse_mode != AGGMG_COARSE_EXTERNAL)
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_dist_create: the local hierarchy must be created with AGGMG_COARSE_EXTERNAL");
   if (coarse_global->lv.size() != 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_dist_create: the coarse hierarchy must have one level");
+  // an element-patch Schwarz sweep reaches two elements (and wider patches more): the halo plans know reaches of one
+  for (const Level& l : local->lv)
+    if (l.S && l.S->patch_width)
+      return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_dist_create: element-patch Schwarz levels are not partitioned (a sweep reaches past the ghost layer)");
   HIPCHK(hipSetDevice(ctx->device));
   std::unique_ptr<aggmg_dist> d(new aggmg_dist());
   d->H = local;

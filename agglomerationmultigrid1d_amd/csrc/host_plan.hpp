@@ -314,15 +314,49 @@ inline void pair_up_split(PairTilePlan* p, int nPost, int rho_ab, int rho_bc, in
 // multiple of `align` (the ratio of an agglomerating restriction, 1 otherwise)
 inline int chain_tile_owned(int te, int hl, int hr, int align) { return std::max(0, ((te - hl - hr) / align) * align); }
 
+// ---- element-patch Schwarz sweeps (patch_kernels.hpp) ---------------------------------------------------------------
+// A workgroup of `threads` threads holds ns slabs of threads / m elements.  A sweep reaches two elements to each side,
+// so a launch of S sweeps keeps 2 S elements of halo on either side of the owned ones.  The most sweeps a launch
+// takes: as many as its weights array holds and the halos leave half the tile to own (at least one sweep where one
+// sweep leaves a tile at all; 0: no tile).  LDS: two iterate buffers and the residual, each padded by one element a side.
+constexpr int kPatchMaxSweeps = 8;   // == kSweepWeights (kernels.hpp; asserted where both are seen)
+struct PatchTilePlan {
+  int te = 0;      // elements a workgroup holds
+  int halo = 0;    // per side
+  int owned = 0;   // 0: no tile
+  size_t lds_bytes = 0;
+};
+constexpr int patch_slabs(int m) { return m <= 3 ? 4 : (m == 4 ? 3 : (m <= 6 ? 2 : 1)); }   // PatchSlabs<M>::NS
+inline int patch_tile_elems(int m, int threads = 256) { return m >= 1 && m <= threads ? (threads / m) * patch_slabs(m) : 0; }
+inline int patch_owned(int te, int sweeps) { return std::max(0, te - 4 * sweeps); }
+inline PatchTilePlan patch_tile_plan(int m, int sweeps, int threads = 256) {
+  PatchTilePlan p;
+  p.te = patch_tile_elems(m, threads);
+  if (p.te <= 0 || sweeps < 1 || sweeps > kPatchMaxSweeps) return p;
+  p.halo = 2 * sweeps;
+  p.owned = patch_owned(p.te, sweeps);
+  p.lds_bytes = (size_t)3 * (p.te + 2) * m * sizeof(double);
+  return p;
+}
+inline int patch_max_sweeps(int m, int threads = 256) {
+  const int te = patch_tile_elems(m, threads);
+  if (patch_tile_plan(m, 1, threads).owned <= 0) return 0;
+  return std::max(1, std::min(kPatchMaxSweeps, te / 8));
+}
+inline int64_t patch_tiles(int64_t ne, int owned) { return owned > 0 ? (ne + owned - 1) / owned : 0; }
+// a run of `sweeps` sweeps in launches of at most smax: launch c of patch_chunks takes patch_chunk_sweeps
+inline int patch_chunks(int sweeps, int smax) { return sweeps <= 0 || smax <= 0 ? 0 : (sweeps + smax - 1) / smax; }
+inline int patch_chunk_sweeps(int sweeps, int smax, int c) { return std::min(smax, sweeps - c * smax); }
+
 // ---- does a launch have a tile? ----------------------------------------------------------------------------------
 // One question for every tiled launch, answered by the planner its launcher runs: the callers that choose between a
 // launch and its fallback (two levels or one per launch, fused or unfused sequence, K columns or column by column) ask
 // here, so a launch that was chosen never finds "no tile".
-enum TileLaunch { kTileFused = 0, kTileMulti = 1, kTilePairDown = 2, kTilePairUp = 3 };
+enum TileLaunch { kTileFused = 0, kTileMulti = 1, kTilePairDown = 2, kTilePairUp = 3, kTilePatch = 4 };
 struct TileQuery {
   int launch = kTileFused;
   int te = 0, te_b = 0;   // elements a workgroup holds (pairs: of level A and of level B)
-  int halo = 0;           // fused / K-column: elements kept each side; pairs: the sweeps
+  int halo = 0;           // fused / K-column: elements kept each side; pairs, patch sweeps: the sweeps
   int align = 1;          // fused / K-column: see fused_tile_plan; pairs: rho_ab
   int rho_bc = 1;         // descent of a pair
   bool var_agg = false;   // fused: see fused_tile_plan
@@ -335,6 +369,7 @@ inline bool launch_has_tile(const TileQuery& q) {
     case kTileMulti: return multi_tile_owned(q.te, q.halo, q.align) > 0;
     case kTilePairDown: return pair_down_plan(q.halo, q.align, q.rho_bc, q.te, q.te_b).own > 0;
     case kTilePairUp: return pair_up_plan(q.halo, q.align, q.te, q.te_b).own > 0;
+    case kTilePatch: return q.halo >= 1 && q.halo <= kPatchMaxSweeps && patch_owned(q.te, q.halo) > 0;
   }
   return false;
 }

@@ -176,6 +176,16 @@ struct CgtDev {
   DevArray<double> zlast;   // [ne][m+1]    its last row (the right vertex) at e + 1: with the block that owns the vertex
 };
 
+// fused form of an element-patch Schwarz smoother (aggmg_patch_schwarz_setup, patch_kernels.hpp): overlapping patches of two
+// consecutive elements on a block-tridiagonal operator
+struct PatchDev {
+  int m = 0;         // rows per element
+  int64_t ne = 0;
+  bool hybrid = true;
+  std::shared_ptr<BtdDev> btd;   // the element blocks of A: the sweeps' residual rows and the level's transfer launches
+  DevArray<double> zrows;        // [N][2][2m] per row the two inverse rows it applies (zeros where a patch does not exist)
+};
+
 struct aggmg_op {
   int64_t m = 0, n = 0, nnz = 0;
   int kind = AGGMG_OP_STIFFNESS;
@@ -203,6 +213,10 @@ struct aggmg_smoother {
   bool gs = false;  // red-black block Gauss-Seidel (extension): needs the structured form
   std::shared_ptr<BtdDev> btd;  // structured fused form, or null
   std::shared_ptr<CgtDev> cgt;  // CG chain form (point Jacobi with the element lists), or null
+  // element-patch Schwarz (aggmg_patch_schwarz_setup): elements per patch (0: another smoother) and, for the fused form
+  // (width 2), its arrays -- btd above stays null then (a non-null btd is a block-Jacobi level), binv / inds are not kept
+  int patch_width = 0;
+  std::shared_ptr<PatchDev> patch;
 };
 
 struct TransferBtd {
@@ -419,12 +433,20 @@ enum class LevelPath {
   FusedChain,   // CG chain form + structured transfer: cgt_down / cgt_up / cgt_mid (cgt.hip)
   FusedBtd,     // block-tridiagonal form + structured transfer: btd_down / btd_up / btd_mid
   BtdTransfer,  // block-tridiagonal sweeps, generic residual / restriction / prolongation (the same three functions)
+  Patch,        // fused element-patch Schwarz sweeps, zero-sweep fused transfer launches or the generic ones: patch_down / patch_up
   Generic       // generic_down / generic_up
 };
+// the element-block form a level's structured transfer is built on: the block-Jacobi smoother's, or the patch smoother's
+inline const BtdDev* level_btd(const Level& l) {
+  if (!l.S || l.S->A != l.A) return nullptr;
+  if (l.S->btd) return l.S->btd.get();
+  return l.S->patch ? l.S->patch->btd.get() : nullptr;
+}
 inline LevelPath level_path(const aggmg_hier* h, int k) {
   const Level& l = h->lv[k];
   if (k == (int)h->lv.size() - 1) return LevelPath::Coarsest;
   if (l.cgt_fused) return LevelPath::FusedChain;
+  if (l.S && l.S->patch && l.S->A == l.A) return LevelPath::Patch;
   if (l.S && l.S->btd && l.S->A == l.A) return l.tb ? LevelPath::FusedBtd : LevelPath::BtdTransfer;
   return LevelPath::Generic;
 }

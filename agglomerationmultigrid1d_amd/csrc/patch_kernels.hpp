@@ -1,0 +1,205 @@
+// Element-patch Schwarz smoother of a DG level (aggmg_patch_schwarz_setup): overlapping patches of
+// two consecutive elements P_e = {e, e + 1}, e = 0 .. ne - 2, on an operator that is block tridiagonal in the element
+// blocking.  One sweep with weight w:
+//   r = b - A u                                       (ascending columns, the operator's own entries: btd_apply_cmp / _dense)
+//   t_row = (Z_{e-1} r[P_{e-1}])[M + i] + (Z_e r[P_e])[i]   (patch e - 1 first, each dot product in ascending j)
+//   u += w (t / c_e)   hybrid, c_e = patches covering element e (1 at both ends, 2 inside);   u += w t   additive
+// -- the arithmetic of the generic route (block_sweep_kernel + block_combine_kernel) on the same lists, without index
+// lists, without a CSR operator, and S sweeps per launch.
+#pragma once
+#include "kernels.hpp"
+
+namespace aggmg {
+
+// zrows [N][2][2M]: per row (e, i) the two inverse rows it applies -- row M + i of Z_{e-1}, then row i of Z_e; zeros where
+// the patch does not exist (e = 0 / e = ne - 1)
+struct PatchArgs {
+  const double *dblk, *scol, *qrow, *sub, *sup;   // the element blocks of A (BtdLevel's arrays; compressed or dense couplings)
+  const double* zrows;
+  int64_t ne;
+  int c_sub, r_sup;
+  const double* u_in;   // nullptr: the iterate starts at zero
+  const double* b;
+  double* u_out;
+  int nsweeps;
+  int owned;            // owned elements per tile; the tile keeps `halo` = 2 * nsweeps more on either side
+  int halo;
+};
+
+// slabs of 256 / M elements a workgroup holds: what the registers of a thread afford (per slab the row's 4M inverse-row
+// words, its M entries of D_e, its couplings, b and u)
+template <int M>
+struct PatchSlabs {
+  static constexpr int NS = M <= 3 ? 4 : (M == 4 ? 3 : (M <= 6 ? 2 : 1));
+};
+
+// 256 threads, one per DoF row of a slab, NS slabs: the tile's iterate (ping-pong) and its residual in LDS, each padded by
+// one zero element on both sides; the row's operator entries, inverse rows, b and damping in registers, loaded once.
+// Temporal blocking: a sweep reaches two elements to each side (the residual reads u[e +- 1], the patch solves r[e +- 1]),
+// so after S sweeps the elements 2S and more away from the tile's ends hold what a sweep over the whole level gives.
+template <int M, bool CMP, int NS, bool HYB>
+__global__ __launch_bounds__(kThreads) void patch_sweep_kernel(PatchArgs a, SweepWeights wts) {
+  constexpr int EPS = kThreads / M;   // elements per slab
+  constexpr int TE = EPS * NS;        // elements per tile (owned + halos)
+  constexpr int PL = (TE + 2) * M;    // a padded vector of the tile: index x * M + j, x in [-1, TE]
+  extern __shared__ double lds[];
+  double* cur = lds + M;
+  double* nxt = cur + PL;
+  double* res = nxt + PL;
+
+  const int tid = threadIdx.x;
+  const bool active = tid < EPS * M;
+  const int le = tid / M;
+  const int i = tid - le * M;
+  const int64_t ne = a.ne;
+  const int64_t e0 = (int64_t)blockIdx.x * a.owned - a.halo;   // element at x = 0
+
+  if (tid < M) {
+    cur[-M + tid] = 0.0;
+    cur[TE * M + tid] = 0.0;
+    nxt[-M + tid] = 0.0;
+    nxt[TE * M + tid] = 0.0;
+    res[-M + tid] = 0.0;
+    res[TE * M + tid] = 0.0;
+  }
+
+  double dk[NS][M], lo[NS][CMP ? 1 : M], hi[NS][M], z[NS][4 * M], bb[NS], uu[NS];
+  bool valid[NS], inner[NS];
+
+  // ---- load phase: everything the tile needs from HBM, once ----------------------------------------------------------
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int x = s * EPS + le;
+    const int64_t e = e0 + x;
+    valid[s] = active && e >= 0 && e < ne;
+    inner[s] = e > 0 && e < ne - 1;
+    bb[s] = 0.0;
+    uu[s] = 0.0;
+#pragma unroll
+    for (int j = 0; j < M; ++j) dk[s][j] = hi[s][j] = 0.0;
+#pragma unroll
+    for (int j = 0; j < (CMP ? 1 : M); ++j) lo[s][j] = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4 * M; ++j) z[s][j] = 0.0;
+    if (valid[s]) {
+      const int64_t row = e * M + i;
+      const double* zr = a.zrows + row * (4 * M);
+#pragma unroll
+      for (int j = 0; j < 4 * M; ++j) z[s][j] = AGGMG_LD(zr[j]);
+#pragma unroll
+      for (int j = 0; j < M; ++j) dk[s][j] = AGGMG_LD(a.dblk[row * M + j]);
+      if constexpr (CMP) {
+        lo[s][0] = AGGMG_LD(a.scol[row]);
+        if (i == a.r_sup) {
+#pragma unroll
+          for (int j = 0; j < M; ++j) hi[s][j] = a.qrow[e * M + j];
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < M; ++j) lo[s][j] = AGGMG_LD(a.sub[row * M + j]);
+#pragma unroll
+        for (int j = 0; j < M; ++j) hi[s][j] = AGGMG_LD(a.sup[row * M + j]);
+      }
+      bb[s] = a.b[row];
+      if (a.u_in) uu[s] = a.u_in[row];
+    }
+    if (active) cur[x * M + i] = uu[s];
+  }
+  __syncthreads();
+
+  for (int sw = 0; sw < a.nsweeps; ++sw) {
+    const double w = wts.w[sw];   // this sweep's factor: wave-uniform, a scalar load
+    // residual rows of the tile (zero outside the level)
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!active) continue;
+      const int x = s * EPS + le;
+      const double *um = cur + (x - 1) * M, *ux = cur + x * M, *up = cur + (x + 1) * M;
+      double t;
+      if constexpr (CMP)
+        t = btd_apply_cmp<M, false>(lo[s][0], dk[s], hi[s], um, ux, up, a.c_sub, a.r_sup, i);
+      else
+        t = btd_apply_dense<M>(lo[s], dk[s], hi[s], um, ux, up);
+      res[x * M + i] = valid[s] ? bb[s] - t : 0.0;
+    }
+    __syncthreads();
+    // the two patch solves covering the row, patch e - 1 first
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!active) continue;
+      const int x = s * EPS + le;
+      const double *ra = res + (x - 1) * M, *rb = res + x * M;
+      double ya = 0.0, yb = 0.0;
+#pragma unroll
+      for (int j = 0; j < 2 * M; ++j) ya += z[s][j] * ra[j];
+#pragma unroll
+      for (int j = 0; j < 2 * M; ++j) yb += z[s][2 * M + j] * rb[j];
+      double v = 0.0;
+      v += ya;
+      v += yb;
+      if (HYB && inner[s]) v = v * 0.5;   // c_e = 2: the division, exactly
+      v = w * v;
+      const double un = valid[s] ? uu[s] + v : 0.0;
+      uu[s] = un;
+      nxt[x * M + i] = un;
+    }
+    __syncthreads();
+    double* t2 = cur;
+    cur = nxt;
+    nxt = t2;
+  }
+
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int x = s * EPS + le;
+    if (valid[s] && x >= a.halo && x < a.halo + a.owned) AGGMG_ST(a.u_out[(e0 + x) * M + i], uu[s]);
+  }
+}
+
+// ---- set-up ---------------------------------------------------------------------------------------------------------------
+// the dense patch blocks A[P_p, P_p], [ne - 1][2m][2m] row-major, from the element blocks of A: one thread per entry
+static __global__ __launch_bounds__(kThreads) void patch_assemble_kernel(int64_t total, int m, int cmp, int c_sub, int r_sup,
+                                                                         const double* __restrict__ dblk,
+                                                                         const double* __restrict__ scol,
+                                                                         const double* __restrict__ qrow,
+                                                                         const double* __restrict__ sub,
+                                                                         const double* __restrict__ sup, double* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (t >= total) return;
+  const int m2 = 2 * m;
+  const int64_t p = t / (m2 * m2);
+  const int rc = (int)(t - p * (m2 * m2));
+  const int ri = rc / m2, cj = rc - ri * m2;
+  const int ei = ri / m, ii = ri - ei * m, ej = cj / m, jj = cj - ej * m;
+  const int64_t row = (p + ei) * m + ii;   // the operator's row
+  double v;
+  if (ei == ej)
+    v = dblk[row * m + jj];
+  else if (ei == 0)   // Sup_p
+    v = cmp ? (ii == r_sup ? qrow[p * m + jj] : 0.0) : sup[row * m + jj];
+  else                // Sub_{p + 1}
+    v = cmp ? (jj == c_sub ? scol[row] : 0.0) : sub[row * m + jj];
+  out[t] = v;
+}
+
+// zrows from the patch inverses zinv [ne - 1][2m][2m]: one thread per word
+static __global__ __launch_bounds__(kThreads) void patch_zrows_kernel(int64_t total, int m, int64_t ne,
+                                                                      const double* __restrict__ zinv, double* __restrict__ zrows) {
+  const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (t >= total) return;
+  const int m2 = 2 * m;
+  const int64_t row = t / (2 * m2);
+  const int sj = (int)(t - row * (2 * m2));
+  const int slot = sj / m2, j = sj - slot * m2;
+  const int64_t e = row / m;
+  const int i = (int)(row - e * m);
+  double v = 0.0;
+  if (slot == 0) {
+    if (e >= 1) v = zinv[((e - 1) * m2 + m + i) * m2 + j];
+  } else {
+    if (e + 1 < ne) v = zinv[(e * m2 + i) * m2 + j];
+  }
+  zrows[t] = v;
+}
+
+}  // namespace aggmg

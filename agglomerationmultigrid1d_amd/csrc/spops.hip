@@ -367,6 +367,21 @@ extern "C" int aggmg_op_download_csc(aggmg_ctx* ctx, const aggmg_op* op, int32_t
 // inverses (or matrices) of a block object, [nb][m][m] row-major: evidence for the device LU (K6)
 extern "C" int aggmg_smoother_download_blocks(aggmg_ctx* ctx, const aggmg_smoother* sm, double* out) {
   if (!ctx || !sm || !out) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smoother_download_blocks: NULL");
+  if (sm->patch) {
+    // fused element-patch Schwarz keeps the inverses row by row (PatchDev::zrows): rows 0 .. m-1 of patch p are the second
+    // inverse rows of element p's rows, rows m .. 2m-1 the first ones of element p + 1's
+    const PatchDev& P = *sm->patch;
+    const int64_t m = P.m, w = 2 * m, N = P.ne * m;
+    std::vector<double> z((size_t)(N * 2 * w));
+    if (!z.empty()) HIPCHK(hipMemcpyAsync(z.data(), P.zrows, z.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int64_t p = 0; p + 1 < P.ne; ++p)
+      for (int64_t i = 0; i < m; ++i) {
+        std::memcpy(out + (p * w + i) * w, z.data() + ((p * m + i) * 2 + 1) * w, (size_t)w * sizeof(double));
+        std::memcpy(out + (p * w + m + i) * w, z.data() + (((p + 1) * m + i) * 2) * w, (size_t)w * sizeof(double));
+      }
+    return AGGMG_OK;
+  }
   if (!sm->binv) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smoother_download_blocks: not a block smoother");
   const int64_t cnt = sm->nb * sm->m * sm->m;
   if (cnt) HIPCHK(hipMemcpyAsync(out, sm->binv, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

@@ -626,19 +626,25 @@ class UniformDgAggHierarchy:
 def build_device_hierarchy(U, ctx=None, keep_host=False, smoother="blockJac", csc=None):
     """Upload a UniformDgAggHierarchy through the CSC boundary and return the product
     MeshHierarchy (block-Jacobi on every smoothed level, src/mesh_heirarchy.jl:58,73,85,104;
-    smoother="blockGS": the labelled red-black block Gauss-Seidel extension).
+    smoother="blockGS": the labelled red-black block Gauss-Seidel extension; "patchSchwarz" / "patchSchwarz0": the
+    element-patch Schwarz extension on every smoothed level / on the fine level only).
     csc = (stiffness list, interpolation list): matrices already assembled by the caller (bench.py times
     the generator and the library set-up apart)."""
-    from .api import BlockGaussSeidel, BlockJacobi, DeviceOperator, MeshHierarchy
+    from .api import BlockGaussSeidel, BlockJacobi, DeviceOperator, ElementPatchSchwarz, MeshHierarchy
     from . import _lib
-    BlockJacobi = {"blockJac": BlockJacobi, "blockGS": BlockGaussSeidel}[smoother]
+
+    def patch(op, inds, ctx):   # hybrid patches of two elements (ElementPatchSchwarz)
+        return ElementPatchSchwarz(op, inds.shape[0], inds.shape[1], ctx=ctx)
+
+    # "patchSchwarz": on every smoothed level; "patchSchwarz0": on the fine level, block-Jacobi below
+    make = {"blockJac": BlockJacobi, "blockGS": BlockGaussSeidel, "patchSchwarz": patch, "patchSchwarz0": patch}[smoother]
     n = U.nlevels
     ops, sms = [], []
     for k in range(n):
         op = DeviceOperator(csc[0][k] if csc else U.stiffness_csc(k), _lib.OP_STIFFNESS, ctx)
         ops.append(op)
         if k < n - 1:
-            sms.append(BlockJacobi(op, U.descriptor(k).mBlockInds, ctx))
+            sms.append((BlockJacobi if smoother == "patchSchwarz0" and k > 0 else make)(op, U.descriptor(k).mBlockInds, ctx))
     Ls = [DeviceOperator(csc[1][k] if csc else U.interpolation_csc(k), _lib.OP_TRANSFER, ctx) for k in range(n - 1)]
     H = MeshHierarchy([U.descriptor(k) for k in range(n)], ops, sms, Ls, ctx=ctx, keep_host=keep_host)
     return H

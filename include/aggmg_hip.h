@@ -207,6 +207,37 @@ int aggmg_jacobi_setup_elements(aggmg_ctx* ctx, aggmg_op* A, int64_t nodes_per_e
  * aggmg_smoother_apply(..., alpha = 1).  A singular block -> AGGMG_ERR_SINGULAR. */
 int aggmg_blockdiag_setup(aggmg_ctx* ctx, int64_t m, int64_t nb, const double* blocks, int factorize,
                           aggmg_smoother** out);
+/* EXTENSION: element-patch Schwarz smoother of a DG level -- the arithmetic of HybridSchwarzSmoother /
+ * AdditiveSchwarzSmoother (src/smoother.jl:1-46) on lists the call generates itself.  The level has ne elements
+ * of m rows, contiguous and aligned (A is (m ne) x (m ne)); the patches are {e, .., e + width - 1},
+ * e = 0 .. ne - width (one patch of all elements where ne < width), width = 2, 3 or 4 (anything else:
+ * AGGMG_ERR_ARGUMENT).  hybrid != 0: the summed patch corrections of a row are divided by the number of patches
+ * covering its element (1 at both ends of the level, `width` well inside); hybrid = 0: added as they are (at
+ * alpha = 2/3 that form diverges in a V-cycle: DESIGN.md section 19).
+ *   width = 2 on an operator that is block tridiagonal in the element blocking, m = 1 .. 8 in the coupling forms
+ * the block-Jacobi set-up produces (compressed 2 .. 8, dense 1 .. 5), ne >= 2: the FUSED form.  The ne - 1 dense
+ * patch blocks are assembled on the device from the element blocks, inverted by the kernel of every other block
+ * smoother, and kept per row as the two inverse rows the row applies (zeros where a patch does not exist); sweeps
+ * run in patch_sweep_kernel -- the tile's iterate and residual in LDS, up to AGGMG_MAX_SWEEP_WEIGHTS sweeps per
+ * launch -- with no index list and no CSR operator.  A->btd is set as by a block-Jacobi set-up (aggmg_residual takes
+ * the fused residual), and a hierarchy runs the level's transfers in the fused block-tridiagonal launches.
+ * MEMORY: the inverse rows take 32 m bytes per row (4 m doubles), i.e. 128 m^2 bytes per element: 8.6 GB at 2^24
+ * elements of m = 4; set-up holds the dense blocks and their inverses (another 64 m bytes per row) until it returns.
+ *   Everything else -- wider patches, another block size, an operator that is not block tridiagonal -- takes the
+ * generic route: the call builds the lists and the smoother aggmg_blockjacobi_setup(kind 0 / 1) makes of them.
+ * Same results to round-off; aggmg_smoother_patch_info reports fused = 0.
+ * A singular patch -> AGGMG_ERR_SINGULAR naming it (1-based).
+ * The smoothed V-cycle is NOT a symmetric preconditioner (the division by the cover counts does not commute with
+ * the patch solves): aggmg_pcg_dev is not valid on a hierarchy holding such a level, aggmg_fgmres_dev is.
+ * aggmg_dist_create refuses such a hierarchy (AGGMG_ERR_UNSUPPORTED): a sweep reaches two elements. */
+int aggmg_patch_schwarz_setup(aggmg_ctx* ctx, aggmg_op* A, int64_t m, int64_t ne, int width, int hybrid,
+                              aggmg_smoother** out);
+/* width (0: sm is not an element-patch Schwarz smoother), hybrid (1 / 0) and whether sm runs the fused form */
+int aggmg_smoother_patch_info(aggmg_ctx* ctx, const aggmg_smoother* sm, int* width, int* hybrid, int* fused);
+/* The tiles of the fused sweep launch on elements of m rows (no device call; tests and tools size their cases with
+ * it): a launch of nsweeps sweeps holds tile_elems elements per workgroup, of which it owns `owned` (0: no such
+ * launch); runs of more than max_sweeps sweeps are cut into launches of at most that many. */
+int aggmg_patch_tile_plan(int m, int nsweeps, int* tile_elems, int* owned, int* max_sweeps);
 int aggmg_smoother_free(aggmg_ctx* ctx, aggmg_smoother* sm);
 /* apply_smoother(S, B; alpha) -> alpha * (S \ B), B is N x ncols column-major, result in Y.
  * src/smoother.jl:6-18,30-46,56-58,69-81.  Host pointers. */

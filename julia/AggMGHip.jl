@@ -148,6 +148,17 @@ function device_block_smoother(op::DeviceOperator, mBlockInds::AbstractMatrix{<:
     return _wrap_smoother(op.ctx, op, r[])
 end
 
+# Element-patch Schwarz (extension): hybrid Schwarz on overlapping patches of `width` consecutive elements of a DG
+# level of ne elements of m rows; the library generates the lists.  width = 2 on a block-tridiagonal operator runs the
+# fused sweep kernel.  The smoothed cycle is not symmetric: fgmres, not pcg, around it.
+function device_patch_smoother(op::DeviceOperator, m::Integer, ne::Integer; width::Integer = 2, hybrid::Bool = true)
+    r = Ref{Handle}(C_NULL)
+    check(op.ctx.h, ccall((:aggmg_patch_schwarz_setup, LIB), Cint,
+        (Handle, Handle, Int64, Int64, Cint, Cint, Ref{Handle}),
+        op.ctx.h, op.h, m, ne, width, hybrid ? 1 : 0, r))
+    return _wrap_smoother(op.ctx, op, r[])
+end
+
 # the reference's smoother objects -> device smoothers (used by DeviceHierarchy(H))
 function device_smoother(op::DeviceOperator, S::AbstractSmoother, mesh = nothing)
     S isa DeviceSmoother && return S
@@ -162,6 +173,10 @@ function dg_smoother(dgMesh, A::DeviceOperator, smootherType::Symbol)
     smootherType == :jac && return device_jacobi(A)
     smootherType == :blockJac && return device_block_smoother(A, element_nodes(dgMesh), 0)
     smootherType == :blockGS && return device_block_smoother(A, element_nodes(dgMesh), 2)   # extension
+    if smootherType == :patchSchwarz   # extension
+        inds = element_nodes(dgMesh)
+        return device_patch_smoother(A, size(inds, 1), size(inds, 2))
+    end
     throw(ArgumentError("dg_smoother: unknown smoother type $smootherType"))
 end
 # cg_smoother(cgMesh, A, :jac | :addSchwarz | :hybridSchwarz)   src/smoother.jl:88-139

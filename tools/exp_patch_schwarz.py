@@ -1,0 +1,155 @@
+#!/usr/bin/env python3
+"""Element-patch Schwarz smoother (aggmg_patch_schwarz_setup) on the config 3 hierarchy (DG p = 3 ->
+AggDG 4:1 -> 2:1 -> 2:1) and on the ragged one (jittered mesh, agglomerates of different sizes):
+
+    python tools/exp_patch_schwarz.py [--log2-elems 20 22] [--ragged-log2 20] [--reps 20] [--no-solve]
+
+Times are HIP events on the context's stream (a torch stream the context is given), 3 warm-up calls, medians of --reps;
+the variants of a comparison alternate in one process.
+
+launch: the fused sweep launch on the fine level for S = 1, 3, 6 sweeps, its compulsory bytes
+(aggmg_smoother_launch_bytes) and the fraction of 8 TB/s they make of the launch's time.
+
+cycle: one V(3,3) cycle from a zero guess with, on level 0, the fused patch smoother, the generic route on the same lists
+(HybridSchwarzSmoother; only up to --generic-max-log2 elements), block-Jacobi, and block-Jacobi with a Chebyshev
+schedule.  GATE at 2^20 elements: fused <= 0.5 generic.
+
+solve: time and iterations to 1e-8 ||b|| of multigrid V(3,3), fgmres V(1,1) and V(3,3) with the patch smoother, against
+multigrid with block-Jacobi, with its Chebyshev schedule, and pcg with block-Jacobi.  One JSON line per measurement."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+PEAK = 8.0e12
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--log2-elems", type=int, nargs="*", default=[20, 22])
+    ap.add_argument("--ragged-log2", type=int, nargs="*", default=[20])
+    ap.add_argument("--generic-max-log2", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--no-solve", action="store_true")
+    args = ap.parse_args()
+    import torch
+    import agglomerationmultigrid1d_amd as mg
+    from agglomerationmultigrid1d_amd import _lib, uniform
+    ctx = mg.Context(0)
+    stream = torch.cuda.Stream()
+    ctx.set_stream(stream.cuda_stream)
+    lib, h = ctx.lib, ctx.handle
+    pd = ctypes.POINTER(ctypes.c_double)
+
+    def timed_all(fns, reps=None, warm=3):
+        """median ms of every fn of the dict, the fns alternating inside every repetition"""
+        for _ in range(warm):
+            for fn in fns.values():
+                fn()
+        ms = {k: [] for k in fns}
+        for _ in range(reps or args.reps):
+            for k, fn in fns.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ctx.synchronize()
+                a.record(stream)
+                fn()
+                b.record(stream)
+                b.synchronize()
+                ms[k].append(a.elapsed_time(b))
+        return {k: float(np.median(v)) for k, v in ms.items()}
+
+    def launches(tag, E, op, S, m, ne):
+        N = op.shape[0]
+        rng = np.random.default_rng(E)
+        du, db, dout = ctx.to_device(rng.standard_normal(N)), ctx.to_device(rng.standard_normal(N)), ctx.alloc(N)
+        rd, wr = mg.smoother_launch_bytes(op, S, "sweeps")
+        t = timed_all({s: (lambda s=s: ctx.check(lib.aggmg_smooth_dev(h, op.handle, S.handle, du.ptr, db.ptr, 2.0 / 3.0, s, dout.ptr)))
+                       for s in (1, 3, 6)})
+        for s, ms in t.items():
+            print(json.dumps({"what": "launch", "hierarchy": tag, "log2_elems": E, "m": m, "sweeps": s, "ms": round(ms, 4),
+                              "bytes": rd + wr, "bytes_per_element": round((rd + wr) / ne, 1),
+                              "of_8TBs": round((rd + wr) / (ms * 1e-3) / PEAK, 3)}), flush=True)
+        for v in (du, db, dout):
+            v.free()
+
+    for E in args.log2_elems:
+        ne = 2 ** E
+        U = uniform.UniformDgAggHierarchy(ne, p=3, pAgg=1, ratios=(4, 2, 2))
+        csc = ([U.stiffness_csc(k) for k in range(U.nlevels)], [U.interpolation_csc(k) for k in range(U.nlevels - 1)])
+        b = U.rhs()
+        nb = float(np.linalg.norm(b))
+        Hs = {"patch": uniform.build_device_hierarchy(U, ctx, smoother="patchSchwarz0", csc=csc),
+              "blockjac": uniform.build_device_hierarchy(U, ctx, csc=csc),
+              "blockjac_cheb": uniform.build_device_hierarchy(U, ctx, csc=csc)}
+        lam = Hs["blockjac_cheb"].estimate_lambda_max(0)
+        Hs["blockjac_cheb"].set_sweep_weights(0, mg.chebyshev_weights(lam, degree=3), mg.chebyshev_weights(lam, degree=3)[::-1])
+        if E <= args.generic_max_log2:   # the generic route on the same lists: level 0 only, block-Jacobi below
+            ops = [mg.DeviceOperator(csc[0][k], _lib.OP_STIFFNESS, ctx) for k in range(U.nlevels)]
+            sms = [mg.HybridSchwarzSmoother(ops[0], mg.element_patch_lists(4, ne), ctx)]
+            sms += [mg.BlockJacobi(ops[k], U.descriptor(k).mBlockInds, ctx) for k in range(1, U.nlevels - 1)]
+            Ls = [mg.DeviceOperator(csc[1][k], _lib.OP_TRANSFER, ctx) for k in range(U.nlevels - 1)]
+            Hs["generic"] = mg.MeshHierarchy([U.descriptor(k) for k in range(U.nlevels)], ops, sms, Ls, ctx=ctx, keep_host=False)
+        assert Hs["patch"].mSmoothers[0].fused and Hs["patch"].level_kinds()[0] == "fused_btd"
+        launches("config3", E, Hs["patch"]._ops[0], Hs["patch"].mSmoothers[0], 4, ne)
+        N = len(b)
+        db, dx, zero = ctx.to_device(b), ctx.alloc(N), ctx.alloc(N)
+        t = timed_all({k: (lambda H=H: H.vcycle_dev(None, db, dx, 3, 3)) for k, H in Hs.items()})
+        row = {"what": "cycle", "log2_elems": E, "cycle": "V(3,3)", "ms": {k: round(v, 4) for k, v in t.items()}}
+        if "generic" in t:
+            row["fused_over_generic"] = round(t["patch"] / t["generic"], 4)
+            row["gate_fused_at_most_half_of_generic"] = bool(t["patch"] <= 0.5 * t["generic"])
+        print(json.dumps(row), flush=True)
+        if not args.no_solve:
+            hist = np.zeros(400)
+            it, nchk = ctypes.c_int(0), ctypes.c_int(0)
+
+            def solve(H, kind, nPre, nPost):
+                def run():
+                    ctx.check(lib.aggmg_copy_segments_dev(h, 1, (ctypes.c_void_p * 1)(zero.ptr.value),
+                                                          (ctypes.c_void_p * 1)(dx.ptr.value), (ctypes.c_int64 * 1)(1),
+                                                          (ctypes.c_int64 * 1)(N), (ctypes.c_int64 * 1)(N), (ctypes.c_int64 * 1)(N)))
+                    if kind == "multigrid":
+                        ctx.check(lib.aggmg_multigrid_dev(h, H.handle, zero.ptr, db.ptr, 400, 1e-8, 1, nPre, nPost, 2.0 / 3.0,
+                                                          dx.ptr, hist.ctypes.data_as(pd), ctypes.byref(it), ctypes.byref(nchk),
+                                                          None, None))
+                    elif kind == "pcg":
+                        ctx.check(lib.aggmg_pcg_dev(h, H.handle, db.ptr, dx.ptr, 400, 1e-8, nPre, nPost, 2.0 / 3.0,
+                                                    hist.ctypes.data_as(pd), ctypes.byref(it)))
+                    else:
+                        ctx.check(lib.aggmg_fgmres_dev(h, H.handle, db.ptr, dx.ptr, 30, 400, 1e-8, nPre, nPost, 2.0 / 3.0,
+                                                       hist.ctypes.data_as(pd), ctypes.byref(it)))
+                return run
+
+            for name, kind, nPre, nPost in (("patch", "multigrid", 3, 3), ("patch", "fgmres", 1, 1), ("patch", "fgmres", 3, 3),
+                                            ("blockjac", "multigrid", 3, 3), ("blockjac_cheb", "multigrid", 3, 3),
+                                            ("blockjac", "pcg", 3, 3)):
+                ms = timed_all({"s": solve(Hs[name], kind, nPre, nPost)}, reps=max(3, args.reps // 4), warm=1)["s"]
+                true = float(np.linalg.norm(mg.residual(Hs[name]._ops[0], dx.download(), b))) if E <= 22 else None
+                print(json.dumps({"what": "solve", "log2_elems": E, "level0": name, "solver": kind, "cycle": f"V({nPre},{nPost})",
+                                  "iterations": it.value, "ms": round(ms, 3),
+                                  "true_residual_over_b": None if true is None else true / nb}), flush=True)
+        for v in (db, dx, zero):
+            v.free()
+        for H in Hs.values():
+            H.free()
+        del Hs
+
+    for E in args.ragged_log2:
+        ne = 2 ** E
+        H, b, _ = uniform.build_device_ragged_hierarchy(ne, ctx)
+        op = H._ops[0]
+        S = mg.ElementPatchSchwarz(op, 4, ne, ctx=ctx)
+        assert S.fused
+        launches("ragged", E, op, S, 4, ne)
+        S.free()
+        H.free()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
