@@ -625,6 +625,11 @@ class ElementPatchSchwarz(AbstractSmoother):
         w, hy, fu = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
         c.check(c.lib.aggmg_smoother_patch_info(c.handle, h, ctypes.byref(w), ctypes.byref(hy), ctypes.byref(fu)))
         self.width, self.hybrid, self.fused = w.value, bool(hy.value), bool(fu.value)
+        # distinct operator records of the fused form's dictionary (AGGMG_OPT_OPERATOR_DICTIONARY; C ABI
+        # aggmg_smoother_patch_dictionary): 0 = the sweeps read the full arrays
+        nc = ctypes.c_int(0)
+        c.check(c.lib.aggmg_smoother_patch_dictionary(c.handle, h, ctypes.byref(nc)))
+        self.dictionary_classes = nc.value
         self.mBlockInds = element_patch_lists(self.m, self.ne, self.width)
 
     def inverse_blocks(self):
@@ -1021,6 +1026,16 @@ class MeshHierarchy:
             self.ctx.check(self.ctx.lib.aggmg_hier_level_dictionary(self.ctx.handle, self.handle, k, ctypes.byref(v)))
             if v.value:
                 out[k] = v.value
+        return out
+
+    def patch_dictionary_levels(self):
+        """{level: distinct operator records} of the levels whose fused element-patch Schwarz smoother sweeps through
+        a dictionary of its own (ElementPatchSchwarz.dictionary_classes, C ABI aggmg_smoother_patch_dictionary)"""
+        out = {}
+        for k, S in enumerate(self.mSmoothers):
+            nc = getattr(S, "dictionary_classes", 0)
+            if nc:
+                out[k] = nc
         return out
 
     def paired_levels(self, nsweeps=3, direction="down"):

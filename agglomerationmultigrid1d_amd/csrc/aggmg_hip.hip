@@ -843,8 +843,9 @@ static_assert(kPatchMaxSweeps == kSweepWeights, "a patch launch takes as many sw
 // couplings 2 .. 9, dense ones 1 .. 5) up to 8 rows per element.  None of them needs scratch.
 static bool patch_instantiated(int m, bool cmp) { return cmp ? (m >= 2 && m <= 8) : (m >= 1 && m <= 5); }
 
+// cls: the classes of the smoother's dictionary -- a's operator arrays are the dictionary's then (patch_smooth) -- or null
 template <int M, bool CMP>
-static int launch_patch_t(aggmg_ctx* ctx, PatchArgs a, const SweepWeights& wts, bool hybrid) {
+static int launch_patch_t(aggmg_ctx* ctx, PatchArgs a, const SweepWeights& wts, bool hybrid, const uint16_t* cls) {
   constexpr int NS = PatchSlabs<M>::NS;
   static_assert(NS == patch_slabs(M), "the planner sizes the tile the kernel is instantiated for");
   const PatchTilePlan plan = patch_tile_plan(M, a.nsweeps);   // host_plan.hpp
@@ -853,7 +854,12 @@ static int launch_patch_t(aggmg_ctx* ctx, PatchArgs a, const SweepWeights& wts, 
   a.halo = plan.halo;
   const int64_t ntiles = patch_tiles(a.ne, plan.owned);
   if (ntiles == 0) return AGGMG_OK;
-  if (hybrid)
+  if (cls) {
+    if (hybrid)
+      hipLaunchKernelGGL((patch_sweep_dict_kernel<M, CMP, NS, true>), dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, a, wts, cls);
+    else
+      hipLaunchKernelGGL((patch_sweep_dict_kernel<M, CMP, NS, false>), dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, a, wts, cls);
+  } else if (hybrid)
     hipLaunchKernelGGL((patch_sweep_kernel<M, CMP, NS, true>), dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, a, wts);
   else
     hipLaunchKernelGGL((patch_sweep_kernel<M, CMP, NS, false>), dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, a, wts);
@@ -861,18 +867,18 @@ static int launch_patch_t(aggmg_ctx* ctx, PatchArgs a, const SweepWeights& wts, 
   return AGGMG_OK;
 }
 
-static int launch_patch(aggmg_ctx* ctx, const PatchDev& P, const PatchArgs& a, const SweepWeights& wts) {
+static int launch_patch(aggmg_ctx* ctx, const PatchDev& P, const PatchArgs& a, const SweepWeights& wts, const uint16_t* cls) {
   const bool cmp = P.btd->cmp;
 #define CASE(MM)                                                             \
   case MM:                                                                   \
-    return cmp ? launch_patch_t<MM, true>(ctx, a, wts, P.hybrid) : launch_patch_t<MM, false>(ctx, a, wts, P.hybrid);
+    return cmp ? launch_patch_t<MM, true>(ctx, a, wts, P.hybrid, cls) : launch_patch_t<MM, false>(ctx, a, wts, P.hybrid, cls);
 #define CASE_C(MM) \
   case MM:         \
-    if (cmp) return launch_patch_t<MM, true>(ctx, a, wts, P.hybrid); \
+    if (cmp) return launch_patch_t<MM, true>(ctx, a, wts, P.hybrid, cls); \
     break;
   switch (P.m) {
     case 1:
-      if (!cmp) return launch_patch_t<1, false>(ctx, a, wts, P.hybrid);
+      if (!cmp) return launch_patch_t<1, false>(ctx, a, wts, P.hybrid, cls);
       break;
       CASE(2) CASE(3) CASE(4) CASE(5) CASE_C(6) CASE_C(7) CASE_C(8)
   }
@@ -907,9 +913,19 @@ static int patch_smooth(aggmg_ctx* ctx, const PatchDev& P, const double* u_in, c
     const int s = patch_chunk_sweeps(nsweeps, smax, c);
     double* dst = (c == nchunks - 1) ? u_out : (((nchunks - 1 - c) % 2 == 1) ? t0.get() : t1.get());
     PatchArgs a{b.dblk, b.scol, b.qrow, b.sub, b.sup, P.zrows, P.ne, b.c_sub, b.r_sup, src, rhs, dst, s, 0, 0};
+    // the smoother's operator dictionary in place of the full arrays: the same bits, read by the element's class
+    const PatchDictDev* d = P.dict.get();
+    if (d) {
+      a.dblk = d->dblk;
+      a.scol = d->scol;
+      a.qrow = d->qrow;
+      a.sub = d->sub;
+      a.sup = d->sup;
+      a.zrows = d->zrows;
+    }
     {
       ProfScope ps(ctx, AGGMG_KIND_SMOOTH, level);
-      CHECK(launch_patch(ctx, P, a, alpha.from(c * smax).launch(s)));
+      CHECK(launch_patch(ctx, P, a, alpha.from(c * smax).launch(s), d ? d->cls.get() : nullptr));
     }
     src = dst;
   }
@@ -991,6 +1007,8 @@ extern "C" int aggmg_patch_schwarz_setup(aggmg_ctx* ctx, aggmg_op* A, int64_t m,
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));   // the temporaries go out of scope
   }
+  // the smoother's distinct operator records, where they are few (AGGMG_OPT_OPERATOR_DICTIONARY)
+  if (ctx->op_dict) CHECK(setup_patch_dictionary(ctx, *P));
   sm->patch = P;
   *out = sm.release();
   return AGGMG_OK;
@@ -1002,6 +1020,13 @@ extern "C" int aggmg_smoother_patch_info(aggmg_ctx* ctx, const aggmg_smoother* s
   *width = sm->patch_width;   // 0: not an element-patch Schwarz smoother
   *hybrid = sm->patch_width && sm->kind == 2 ? 1 : 0;
   *fused = sm->patch ? 1 : 0;
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_smoother_patch_dictionary(aggmg_ctx* ctx, const aggmg_smoother* sm, int* nclasses) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!sm || !nclasses) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smoother_patch_dictionary: NULL argument");
+  *nclasses = (sm->patch && sm->patch->dict) ? sm->patch->dict->nclasses : 0;
   return AGGMG_OK;
 }
 
@@ -1974,8 +1999,9 @@ extern "C" int aggmg_hier_create(aggmg_ctx* ctx, int nlevels, aggmg_op* const* s
     // every fine row's stored columns must lie in the mc modes of coarse element (fine element) / rho
     CHECK(setup_transfer_btd(ctx, l.L, eb, eb->m, eb->ne, hint, tb.get(), &ok));
     if (ok) l.tb = std::move(tb);
-    // the level's distinct operator records, where they are few (AGGMG_OPT_OPERATOR_DICTIONARY): block-Jacobi levels
-    if (l.tb && l.S->btd && ctx->op_dict) CHECK(setup_op_dictionary(ctx, *l.S->btd, *l.tb, &l.dict));
+    // the level's distinct operator records, where they are few (AGGMG_OPT_OPERATOR_DICTIONARY): block-Jacobi levels,
+    // and the transfer launches of a patch level (patch_down / patch_up)
+    if (l.tb && ctx->op_dict) CHECK(setup_op_dictionary(ctx, *eb, *l.tb, &l.dict));
   }
   // the same for the levels a two-level launch may take (pair_ok: below the finest, above the coarsest)
   for (int k = 1; ctx->op_dict && k + 1 < nlevels; ++k) {
@@ -2403,6 +2429,7 @@ static int patch_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uin, c
     fused_descent(a, h, l, h->lv[k + 1].rhs);
     a.ld_out = nullptr;   // the explicit residual's restriction: (L'D) belongs to the block-Jacobi stencil form
     a.lf_out = l.tb->lf;
+    fused_dictionary(a, l);
     ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
     return launch_btd(ctx, *P.btd, a, 1);
   }
@@ -2415,6 +2442,7 @@ static int patch_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* rhs, int
   if (patch_transfer_ok(l, 0, nullptr)) {
     FusedLaunch a = fused_sweeps(*P.btd, l.u[0], rhs, l.tmp, 0.0, 0);
     fused_ascent(a, l, coarse_result(h, k));
+    fused_dictionary(a, l);
     {
       ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
       CHECK(launch_btd(ctx, *P.btd, a, 0));
@@ -3286,9 +3314,12 @@ extern "C" int aggmg_smoother_launch_bytes(aggmg_ctx* ctx, aggmg_op* A, aggmg_sm
   if (what == 0 && sm->cgt && sm->A == A) return cgt_op_launch_bytes(*sm->cgt, true, read_bytes, write_bytes);
   if (what == 1 && A->cgt) return cgt_op_launch_bytes(*A->cgt, false, read_bytes, write_bytes);
   if (what == 0 && sm->patch && sm->A == A) {
-    // b, u and the new u; per row its 4m inverse-row words, its m entries of D_e and its couplings
+    // b, u and the new u; per row its 4m inverse-row words, its m entries of D_e and its couplings -- or, with the
+    // smoother's dictionary, those of every class once and 2 bytes of class per element
     const int64_t m = sm->patch->m, ne = sm->patch->ne;
-    *read_bytes = 2 * N * D + N * 4 * m * D + N * m * D + (sm->patch->btd->cmp ? N * D + ne * m * D : 2 * N * m * D);
+    const int64_t rec = m * 4 * m * D + m * m * D + (sm->patch->btd->cmp ? m * D + m * D : 2 * m * m * D);   // per element
+    const PatchDictDev* d = sm->patch->dict.get();
+    *read_bytes = 2 * N * D + (d ? ne * 2 + (int64_t)d->nclasses * rec : ne * rec);
     *write_bytes = N * D;
     return AGGMG_OK;
   }

@@ -176,6 +176,17 @@ struct CgtDev {
   DevArray<double> zlast;   // [ne][m+1]    its last row (the right vertex) at e + 1: with the block that owns the vertex
 };
 
+// operator dictionary of a fused element-patch Schwarz smoother (patch_sweep_dict_kernel in patch_kernels.hpp; the same
+// search as DictDev's below): one copy of every distinct record -- every operator word patch_sweep_kernel reads on behalf
+// of the element: its rows of zrows, of the diagonal block and of the couplings in the form the level has (scol + qrow, or
+// sub + sup), [nclasses][...] in the layouts of the full arrays -- and the class of every element.  Belongs to the
+// smoother: the record spans its arrays only, and every entry point that sweeps takes it.  The full arrays stay.
+struct PatchDictDev {
+  int nclasses = 0;
+  DevArray<uint16_t> cls;    // [ne]
+  DevArray<double> zrows, dblk, scol, qrow, sub, sup;
+};
+
 // fused form of an element-patch Schwarz smoother (aggmg_patch_schwarz_setup, patch_kernels.hpp): overlapping patches of two
 // consecutive elements on a block-tridiagonal operator
 struct PatchDev {
@@ -184,6 +195,7 @@ struct PatchDev {
   bool hybrid = true;
   std::shared_ptr<BtdDev> btd;   // the element blocks of A: the sweeps' residual rows and the level's transfer launches
   DevArray<double> zrows;        // [N][2][2m] per row the two inverse rows it applies (zeros where a patch does not exist)
+  std::unique_ptr<PatchDictDev> dict;   // operator dictionary of the sweep launches (AGGMG_OPT_OPERATOR_DICTIONARY), or null
 };
 
 struct aggmg_op {
@@ -561,6 +573,9 @@ int setup_op_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, s
 int setup_pair_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, std::unique_ptr<PairDictDev>* out);
 // the same for a fused chain level: blocks of 1, 2 or 4 rows, point-Jacobi sweeps, chain or agglomerating transfer
 int setup_cgt_dictionary(aggmg_ctx* ctx, const CgtDev& g, const TransferCgt& t, std::unique_ptr<CgtDictDev>* out);
+// the same for the sweep launches of a fused element-patch Schwarz smoother: P.dict, or null where the smoother has more
+// than kDictMaxClasses distinct records (the full arrays stay in either case)
+int setup_patch_dictionary(aggmg_ctx* ctx, PatchDev& P);
 // band_out (optional): max(i - j), max(j - i) over the stored entries -- what the host banded LU would have to store
 int setup_cr(aggmg_ctx* ctx, const aggmg_op* Ac, int hint_m, CrDev* cr, int* band_out = nullptr);
 int setup_cr_chain(aggmg_ctx* ctx, const CgtDev& g, CrDev* cr);   // the same factorisation of the chain-ordered blocks

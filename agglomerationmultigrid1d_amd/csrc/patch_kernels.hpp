@@ -12,7 +12,7 @@
 namespace aggmg {
 
 // zrows [N][2][2M]: per row (e, i) the two inverse rows it applies -- row M + i of Z_{e-1}, then row i of Z_e; zeros where
-// the patch does not exist (e = 0 / e = ne - 1)
+// the patch does not exist (e = 0 / e = ne - 1).  patch_sweep_dict_kernel: the six operator arrays are the dictionary's.
 struct PatchArgs {
   const double *dblk, *scol, *qrow, *sub, *sup;   // the element blocks of A (BtdLevel's arrays; compressed or dense couplings)
   const double* zrows;
@@ -99,6 +99,142 @@ __global__ __launch_bounds__(kThreads) void patch_sweep_kernel(PatchArgs a, Swee
         for (int j = 0; j < M; ++j) lo[s][j] = AGGMG_LD(a.sub[row * M + j]);
 #pragma unroll
         for (int j = 0; j < M; ++j) hi[s][j] = AGGMG_LD(a.sup[row * M + j]);
+      }
+      bb[s] = a.b[row];
+      if (a.u_in) uu[s] = a.u_in[row];
+    }
+    if (active) cur[x * M + i] = uu[s];
+  }
+  __syncthreads();
+
+  for (int sw = 0; sw < a.nsweeps; ++sw) {
+    const double w = wts.w[sw];   // this sweep's factor: wave-uniform, a scalar load
+    // residual rows of the tile (zero outside the level)
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!active) continue;
+      const int x = s * EPS + le;
+      const double *um = cur + (x - 1) * M, *ux = cur + x * M, *up = cur + (x + 1) * M;
+      double t;
+      if constexpr (CMP)
+        t = btd_apply_cmp<M, false>(lo[s][0], dk[s], hi[s], um, ux, up, a.c_sub, a.r_sup, i);
+      else
+        t = btd_apply_dense<M>(lo[s], dk[s], hi[s], um, ux, up);
+      res[x * M + i] = valid[s] ? bb[s] - t : 0.0;
+    }
+    __syncthreads();
+    // the two patch solves covering the row, patch e - 1 first
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!active) continue;
+      const int x = s * EPS + le;
+      const double *ra = res + (x - 1) * M, *rb = res + x * M;
+      double ya = 0.0, yb = 0.0;
+#pragma unroll
+      for (int j = 0; j < 2 * M; ++j) ya += z[s][j] * ra[j];
+#pragma unroll
+      for (int j = 0; j < 2 * M; ++j) yb += z[s][2 * M + j] * rb[j];
+      double v = 0.0;
+      v += ya;
+      v += yb;
+      if (HYB && inner[s]) v = v * 0.5;   // c_e = 2: the division, exactly
+      v = w * v;
+      const double un = valid[s] ? uu[s] + v : 0.0;
+      uu[s] = un;
+      nxt[x * M + i] = un;
+    }
+    __syncthreads();
+    double* t2 = cur;
+    cur = nxt;
+    nxt = t2;
+  }
+
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int x = s * EPS + le;
+    if (valid[s] && x >= a.halo && x < a.halo + a.owned) AGGMG_ST(a.u_out[(e0 + x) * M + i], uu[s]);
+  }
+}
+
+// The same sweeps with the operator read through the smoother's dictionary (PatchDictDev; set-up: setup.hip,
+// setup_patch_dictionary): a's six operator arrays are the dictionary's, [nclasses][...] in the layouts of the full ones,
+// and cls[ne] holds the class of every element.  Tile, LDS layout, sweep loop, arithmetic and store phase are
+// patch_sweep_kernel's, line by line; the load phase reads the classes of all slabs first and then the record words at
+// c * stride + ... in place of e * stride + ..., with ordinary cached loads (the dictionary is re-read by every tile;
+// b, u_in and the store keep the plain kernel's forms).  The loads return the bits the full arrays hold, so every result
+// is patch_sweep_kernel's bit for bit.  (A kernel of its own text: with the body shared through an inlined function the
+// compiler allocates the plain kernels' registers differently, and those are held identical to their earlier build.)
+template <int M, bool CMP, int NS, bool HYB>
+__global__ __launch_bounds__(kThreads) void patch_sweep_dict_kernel(PatchArgs a, SweepWeights wts,
+                                                                    const uint16_t* __restrict__ cls) {
+  constexpr int EPS = kThreads / M;   // elements per slab
+  constexpr int TE = EPS * NS;        // elements per tile (owned + halos)
+  constexpr int PL = (TE + 2) * M;    // a padded vector of the tile: index x * M + j, x in [-1, TE]
+  extern __shared__ double lds[];
+  double* cur = lds + M;
+  double* nxt = cur + PL;
+  double* res = nxt + PL;
+
+  const int tid = threadIdx.x;
+  const bool active = tid < EPS * M;
+  const int le = tid / M;
+  const int i = tid - le * M;
+  const int64_t ne = a.ne;
+  const int64_t e0 = (int64_t)blockIdx.x * a.owned - a.halo;   // element at x = 0
+
+  if (tid < M) {
+    cur[-M + tid] = 0.0;
+    cur[TE * M + tid] = 0.0;
+    nxt[-M + tid] = 0.0;
+    nxt[TE * M + tid] = 0.0;
+    res[-M + tid] = 0.0;
+    res[TE * M + tid] = 0.0;
+  }
+
+  double dk[NS][M], lo[NS][CMP ? 1 : M], hi[NS][M], z[NS][4 * M], bb[NS], uu[NS];
+  bool valid[NS], inner[NS];
+  int c[NS];
+
+  // ---- load phase: the classes first (the record loads depend on them), then the tile's vectors from HBM and its
+  // operator words from the dictionary, once --------------------------------------------------------------------------
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int64_t e = e0 + s * EPS + le;
+    valid[s] = active && e >= 0 && e < ne;
+    c[s] = valid[s] ? (int)cls[e] : 0;
+  }
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int x = s * EPS + le;
+    const int64_t e = e0 + x;
+    inner[s] = e > 0 && e < ne - 1;
+    bb[s] = 0.0;
+    uu[s] = 0.0;
+#pragma unroll
+    for (int j = 0; j < M; ++j) dk[s][j] = hi[s][j] = 0.0;
+#pragma unroll
+    for (int j = 0; j < (CMP ? 1 : M); ++j) lo[s][j] = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4 * M; ++j) z[s][j] = 0.0;
+    if (valid[s]) {
+      const int64_t row = e * M + i;
+      const int crow = c[s] * M + i;   // the row in its class's record (c < kDictMaxClasses: 32-bit offsets)
+      const double* zr = a.zrows + crow * (4 * M);
+#pragma unroll
+      for (int j = 0; j < 4 * M; ++j) z[s][j] = zr[j];
+#pragma unroll
+      for (int j = 0; j < M; ++j) dk[s][j] = a.dblk[crow * M + j];
+      if constexpr (CMP) {
+        lo[s][0] = a.scol[crow];
+        if (i == a.r_sup) {
+#pragma unroll
+          for (int j = 0; j < M; ++j) hi[s][j] = a.qrow[c[s] * M + j];
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < M; ++j) lo[s][j] = a.sub[crow * M + j];
+#pragma unroll
+        for (int j = 0; j < M; ++j) hi[s][j] = a.sup[crow * M + j];
       }
       bb[s] = a.b[row];
       if (a.u_in) uu[s] = a.u_in[row];

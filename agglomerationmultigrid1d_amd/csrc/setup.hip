@@ -682,6 +682,30 @@ int setup_cgt_dictionary(aggmg_ctx* ctx, const CgtDev& g, const TransferCgt& t, 
   return AGGMG_OK;
 }
 
+int setup_patch_dictionary(aggmg_ctx* ctx, PatchDev& P) {
+  P.dict.reset();
+  if (!P.btd || !P.zrows || P.ne < 1) return AGGMG_OK;
+  const BtdDev& b = *P.btd;
+  const int m = P.m;
+  if (!(b.dblk && (b.cmp ? (b.scol && b.qrow) : (b.sub && b.sup)))) return AGGMG_OK;
+  auto d = std::make_unique<PatchDictDev>();
+  // the record of element e: its rows of zrows (4 m*m: the rows of Z_{e-1} and of Z_e they apply), of dblk (m*m) and of
+  // the couplings -- scol[e] (m) and qrow[e] (m), or the rows of sub[e] and sup[e] (m*m each); all at index e
+  DictFields F(P.ne);
+  F.add(P.zrows, &d->zrows, 4 * m * m);
+  F.add(b.dblk, &d->dblk, m * m);
+  if (b.cmp) {
+    F.add(b.scol, &d->scol, m);
+    F.add(b.qrow, &d->qrow, m);
+  } else {
+    F.add(b.sub, &d->sub, m * m);
+    F.add(b.sup, &d->sup, m * m);
+  }
+  CHECK(dict_build(ctx, F, &d->cls, &d->nclasses));
+  if (d->nclasses > 0) P.dict = std::move(d);
+  return AGGMG_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // cyclic-reduction factorisation of the coarsest operator
 // ---------------------------------------------------------------------------------------------

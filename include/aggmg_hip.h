@@ -117,6 +117,14 @@ int aggmg_synchronize(aggmg_ctx* ctx);
  * of the transfer.  A two-level launch of a cycle indexes both levels by class when BOTH have a dictionary; the ascent
  * of the element-partitioned cycle, the K-column and Gauss-Seidel launches and a level that runs on its own keep the
  * full arrays.
+ * A fused element-patch Schwarz smoother (aggmg_patch_schwarz_setup, width 2) gets a dictionary of its own, owned by
+ * the smoother: the record of an element is every operator word the sweep kernel reads for it -- its rows of the two
+ * patch inverses, of the diagonal block and of the couplings.  Every sweep launch with the smoother (aggmg_smooth*,
+ * aggmg_smoother_apply, aggmg_smoother_solve_dev, the eigenvalue estimate, the V-cycles) then reads the operator by the
+ * element's class (patch_sweep_dict_kernel); aggmg_smoother_patch_dictionary reports the classes, and
+ * aggmg_smoother_launch_bytes counts the dictionary launch.  The option is read when the smoother is set up.  On a
+ * hierarchy's patch level the zero-sweep transfer launches (residual + restriction, prolongation) take the level's
+ * dictionary of the first paragraph where the level has that form.
  * Hierarchies created afterwards; aggmg_hier_level_dictionary reports the levels.  aggmg_hier_launch_bytes keeps
  * counting the full arrays (DESIGN.md sections 4 and 5). */
 #define AGGMG_OPT_OPERATOR_DICTIONARY 7
@@ -223,6 +231,10 @@ int aggmg_blockdiag_setup(aggmg_ctx* ctx, int64_t m, int64_t nb, const double* b
  * the fused residual), and a hierarchy runs the level's transfers in the fused block-tridiagonal launches.
  * MEMORY: the inverse rows take 32 m bytes per row (4 m doubles), i.e. 128 m^2 bytes per element: 8.6 GB at 2^24
  * elements of m = 4; set-up holds the dense blocks and their inverses (another 64 m bytes per row) until it returns.
+ * With AGGMG_OPT_OPERATOR_DICTIONARY set, set-up then looks for the classes of bitwise identical per-element records
+ * (inverse rows, diagonal block, couplings); where there are at most 1024, the sweeps read one copy of each by a 16-bit
+ * class per element -- the same bits, so the same results bit for bit.  More classes: the full arrays, no error.  The
+ * full arrays stay allocated in either case.
  *   Everything else -- wider patches, another block size, an operator that is not block tridiagonal -- takes the
  * generic route: the call builds the lists and the smoother aggmg_blockjacobi_setup(kind 0 / 1) makes of them.
  * Same results to round-off; aggmg_smoother_patch_info reports fused = 0.
@@ -234,6 +246,9 @@ int aggmg_patch_schwarz_setup(aggmg_ctx* ctx, aggmg_op* A, int64_t m, int64_t ne
                               aggmg_smoother** out);
 /* width (0: sm is not an element-patch Schwarz smoother), hybrid (1 / 0) and whether sm runs the fused form */
 int aggmg_smoother_patch_info(aggmg_ctx* ctx, const aggmg_smoother* sm, int* width, int* hybrid, int* fused);
+/* Distinct operator records of the smoother's dictionary (AGGMG_OPT_OPERATOR_DICTIONARY): 0 when sm is not a fused
+ * element-patch Schwarz smoother or has no dictionary -- its sweep launches then read the full arrays. */
+int aggmg_smoother_patch_dictionary(aggmg_ctx* ctx, const aggmg_smoother* sm, int* nclasses);
 /* The tiles of the fused sweep launch on elements of m rows (no device call; tests and tools size their cases with
  * it): a launch of nsweeps sweeps holds tile_elems elements per workgroup, of which it owns `owned` (0: no such
  * launch); runs of more than max_sweeps sweeps are cut into launches of at most that many. */

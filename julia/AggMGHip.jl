@@ -158,6 +158,12 @@ function device_patch_smoother(op::DeviceOperator, m::Integer, ne::Integer; widt
         op.ctx.h, op.h, m, ne, width, hybrid ? 1 : 0, r))
     return _wrap_smoother(op.ctx, op, r[])
 end
+# distinct operator records of the fused patch smoother's dictionary (0: none, its sweeps read the full arrays)
+function patch_dictionary_classes(S::DeviceSmoother)
+    r = Ref{Cint}(0)
+    check(S.ctx.h, ccall((:aggmg_smoother_patch_dictionary, LIB), Cint, (Handle, Handle, Ref{Cint}), S.ctx.h, S.h, r))
+    return Int(r[])
+end
 
 # the reference's smoother objects -> device smoothers (used by DeviceHierarchy(H))
 function device_smoother(op::DeviceOperator, S::AbstractSmoother, mesh = nothing)

@@ -3,6 +3,7 @@
 AggDG 4:1 -> 2:1 -> 2:1) and on the ragged one (jittered mesh, agglomerates of different sizes):
 
     python tools/exp_patch_schwarz.py [--log2-elems 20 22] [--ragged-log2 20] [--reps 20] [--no-solve]
+    python tools/exp_patch_schwarz.py --dictionary [--log2-elems 20 22] [--reps 10]
 
 Times are HIP events on the context's stream (a torch stream the context is given), 3 warm-up calls, medians of --reps;
 the variants of a comparison alternate in one process.
@@ -15,7 +16,14 @@ cycle: one V(3,3) cycle from a zero guess with, on level 0, the fused patch smoo
 schedule.  GATE at 2^20 elements: fused <= 0.5 generic.
 
 solve: time and iterations to 1e-8 ||b|| of multigrid V(3,3), fgmres V(1,1) and V(3,3) with the patch smoother, against
-multigrid with block-Jacobi, with its Chebyshev schedule, and pcg with block-Jacobi.  One JSON line per measurement."""
+multigrid with block-Jacobi, with its Chebyshev schedule, and pcg with block-Jacobi.
+
+--dictionary: the smoother's operator dictionary (AGGMG_OPT_OPERATOR_DICTIONARY) on / off -- two contexts with the option
+on and two with it off in one process, on one stream, the four legs alternating inside every repetition: set-up time of
+aggmg_patch_schwarz_setup (host clock around the synchronous call) and class counts, the sweep launch for S = 1, 3, 6 with
+its compulsory bytes each way, one V(3,3) cycle, the multigrid and fgmres V(3,3) solves.  The second off leg runs the
+same kernels as the first: the spread between the two is the noise margin beside every on / off ratio.  GATE at 2^22
+elements, S = 3: on <= off (within that margin).  One JSON line per measurement."""
 import argparse
 import ctypes
 import json
@@ -36,6 +44,7 @@ def main():
     ap.add_argument("--generic-max-log2", type=int, default=20)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--no-solve", action="store_true")
+    ap.add_argument("--dictionary", action="store_true")
     args = ap.parse_args()
     import torch
     import agglomerationmultigrid1d_amd as mg
@@ -43,6 +52,10 @@ def main():
     ctx = mg.Context(0)
     stream = torch.cuda.Stream()
     ctx.set_stream(stream.cuda_stream)
+    if args.dictionary:
+        dictionary_legs(args, torch, mg, _lib, uniform, stream)
+        ctx.close()
+        return
     lib, h = ctx.lib, ctx.handle
     pd = ctypes.POINTER(ctypes.c_double)
 
@@ -149,6 +162,127 @@ def main():
         S.free()
         H.free()
     ctx.close()
+
+
+def dictionary_legs(args, torch, mg, _lib, uniform, stream):
+    import time
+    pd = ctypes.POINTER(ctypes.c_double)
+    legs = {"on": 1, "off": 0, "on2": 1, "off2": 0}
+    ctxs = {}
+    for name, v in legs.items():
+        ctxs[name] = mg.Context(0)
+        ctxs[name].set_stream(stream.cuda_stream)
+        ctxs[name].set_option(_lib.OPT_OPERATOR_DICTIONARY, v)
+
+    def timed_all(fns, reps, warm=3):
+        for _ in range(warm):
+            for fn in fns.values():
+                fn()
+        ms = {k: [] for k in fns}
+        for _ in range(reps):
+            for k, fn in fns.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record(stream)
+                fn()
+                b.record(stream)
+                b.synchronize()
+                ms[k].append(a.elapsed_time(b))
+        return {k: float(np.median(v)) for k, v in ms.items()}
+
+    def ratios(t):
+        """on / off and, beside it, the spread of the two legs that run the same kernels"""
+        return {"on_over_off": round(t["on"] / t["off"], 4), "on2_over_off2": round(t["on2"] / t["off2"], 4),
+                "off2_over_off": round(t["off2"] / t["off"], 4), "on2_over_on": round(t["on2"] / t["on"], 4)}
+
+    for E in args.log2_elems:
+        ne = 2 ** E
+        U = uniform.UniformDgAggHierarchy(ne, p=3, pAgg=1, ratios=(4, 2, 2))
+        csc = ([U.stiffness_csc(k) for k in range(U.nlevels)], [U.interpolation_csc(k) for k in range(U.nlevels - 1)])
+        b = U.rhs()
+        N = len(b)
+        # set-up of the smoother alone, on an operator of its own per leg: 1 warm-up + 3 timed, legs alternating
+        setup = {k: [] for k in legs}
+        for r in range(4):
+            for name, c in ctxs.items():
+                op = mg.DeviceOperator(csc[0][0], _lib.OP_STIFFNESS, c)
+                c.synchronize()
+                t0 = time.perf_counter()
+                S = mg.ElementPatchSchwarz(op, 4, ne, ctx=c)
+                c.synchronize()
+                if r:
+                    setup[name].append((time.perf_counter() - t0) * 1e3)
+                S.free()
+                op.free()
+        print(json.dumps({"what": "setup", "log2_elems": E, "ms": {k: round(float(np.median(v)), 2) for k, v in setup.items()}}),
+              flush=True)
+        Hs = {k: uniform.build_device_hierarchy(U, c, smoother="patchSchwarz0", csc=csc) for k, c in ctxs.items()}
+        print(json.dumps({"what": "classes", "log2_elems": E,
+                          "patch": {k: H.patch_dictionary_levels() for k, H in Hs.items()},
+                          "level": {k: H.dictionary_levels() for k, H in Hs.items()}}), flush=True)
+        rng = np.random.default_rng(E)
+        u0, rhs = rng.standard_normal(N), rng.standard_normal(N)
+        vec = {k: (c.to_device(u0), c.to_device(rhs), c.alloc(N), c.to_device(b), c.alloc(N), c.alloc(N)) for k, c in ctxs.items()}
+        by = {k: sum(mg.smoother_launch_bytes(H._ops[0], H.mSmoothers[0], "sweeps")) for k, H in Hs.items()}
+        for s in (1, 3, 6):
+            def launch(k, s=s):
+                c, H = ctxs[k], Hs[k]
+                du, dr, dout = vec[k][:3]
+                return lambda: c.check(c.lib.aggmg_smooth_dev(c.handle, H._ops[0].handle, H.mSmoothers[0].handle, du.ptr, dr.ptr,
+                                                              2.0 / 3.0, s, dout.ptr))
+            t = timed_all({k: launch(k) for k in legs}, args.reps)
+            row = {"what": "launch", "log2_elems": E, "sweeps": s, "ms": {k: round(v, 4) for k, v in t.items()},
+                   "bytes_per_element": {k: round(by[k] / ne, 1) for k in legs},
+                   "of_8TBs": {k: round(by[k] / (t[k] * 1e-3) / PEAK, 3) for k in legs}}
+            row.update(ratios(t))
+            if E == 22 and s == 3:
+                margin = abs(t["off2"] / t["off"] - 1.0)
+                row["gate_margin"] = round(margin, 4)
+                row["gate_on_not_slower_than_off"] = bool(t["on"] <= t["off"] * (1.0 + margin))
+            print(json.dumps(row), flush=True)
+        t = timed_all({k: (lambda k=k: Hs[k].vcycle_dev(None, vec[k][3], vec[k][4], 3, 3)) for k in legs}, args.reps)
+        row = {"what": "cycle", "log2_elems": E, "cycle": "V(3,3)", "ms": {k: round(v, 4) for k, v in t.items()}}
+        row.update(ratios(t))
+        print(json.dumps(row), flush=True)
+        if not args.no_solve:
+            hist = np.zeros(400)
+            its = {k: ctypes.c_int(0) for k in legs}
+            nchk = ctypes.c_int(0)
+
+            def solve(k, kind):
+                c, H = ctxs[k], Hs[k]
+                db, dx, zero = vec[k][3:]
+
+                def run():
+                    c.check(c.lib.aggmg_copy_segments_dev(c.handle, 1, (ctypes.c_void_p * 1)(zero.ptr.value),
+                                                          (ctypes.c_void_p * 1)(dx.ptr.value), (ctypes.c_int64 * 1)(1),
+                                                          (ctypes.c_int64 * 1)(N), (ctypes.c_int64 * 1)(N), (ctypes.c_int64 * 1)(N)))
+                    if kind == "multigrid":
+                        c.check(c.lib.aggmg_multigrid_dev(c.handle, H.handle, zero.ptr, db.ptr, 400, 1e-8, 1, 3, 3, 2.0 / 3.0,
+                                                          dx.ptr, hist.ctypes.data_as(pd), ctypes.byref(its[k]), ctypes.byref(nchk),
+                                                          None, None))
+                    else:
+                        c.check(c.lib.aggmg_fgmres_dev(c.handle, H.handle, db.ptr, dx.ptr, 30, 400, 1e-8, 3, 3, 2.0 / 3.0,
+                                                       hist.ctypes.data_as(pd), ctypes.byref(its[k])))
+                return run
+
+            for kind in ("multigrid", "fgmres"):
+                t = timed_all({k: solve(k, kind) for k in legs}, max(3, args.reps // 3), warm=1)
+                row = {"what": "solve", "log2_elems": E, "solver": kind, "cycle": "V(3,3)",
+                       "iterations": {k: its[k].value for k in legs}, "ms": {k: round(v, 3) for k, v in t.items()}}
+                row.update(ratios(t))
+                print(json.dumps(row), flush=True)
+        for vs in vec.values():
+            for v in vs:
+                v.free()
+        for H in Hs.values():
+            sms, ops, Ls = list(H.mSmoothers), list(H._ops), list(H._Ls)
+            H.free()
+            for x in sms + ops + Ls:
+                x.free()
+        del Hs
+    for c in ctxs.values():
+        c.close()
 
 
 if __name__ == "__main__":
