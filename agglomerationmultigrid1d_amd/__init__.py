@@ -8,7 +8,7 @@ from ._lib import (AggmgError, ArgumentError, DimensionMismatch, HipError, Singu
 from .api import (AbstractSmoother, AdditiveSchwarzSmoother, BlockDiagonal, BlockDiagonalLU, BlockGaussSeidel,
                   BlockJacobi, Context,
                   DeviceOperator,
-                  DeviceMatrix, DeviceVector, DirectSolver, ElementPatchSchwarz, HybridSchwarzSmoother, JacobiSmoother, MeshHierarchy,
+                  DeviceMatrix, DeviceVector, DirectSolver, ElementPatchGaussSeidel, ElementPatchSchwarz, HybridSchwarzSmoother, JacobiSmoother, MeshHierarchy,
                   apply_smoother, cg_smoother, default_context, dg_smoother, element_patch_lists,
                   dot, fgmres, iterative_smoother_solve, ldiv, multigrid, multigrid_dev, multigrid_v_cycle, norm2, pcg,
                   prolong_add, residual, restrict, smooth, smoother_launch_bytes, smoother_solve_dev,

@@ -115,6 +115,9 @@ SYMBOLS = {
     "aggmg_smoother_patch_info": (c_int, [_P, _P, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "aggmg_smoother_patch_dictionary": (c_int, [_P, _P, POINTER(c_int)]),
     "aggmg_patch_tile_plan": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "aggmg_patch_gs_setup": (c_int, [_P, _P, c_int64, c_int64, POINTER(_P)]),
+    "aggmg_smoother_patch_kind": (c_int, [_P, _P, POINTER(c_int)]),
+    "aggmg_patch_gs_tile_plan": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "aggmg_jacobi_setup": (c_int, [_P, _P, POINTER(_P)]),
     "aggmg_jacobi_setup_elements": (c_int, [_P, _P, c_int64, c_int64, POINTER(c_int64), c_int, POINTER(_P)]),
     "aggmg_smoother_free": (c_int, [_P, _P]),

@@ -612,7 +612,9 @@ class ElementPatchSchwarz(AbstractSmoother):
     (hybrid=False) on element_patch_lists(m, ne, width).  width = 2 on an operator that is block tridiagonal in the
     blocking of ne elements of m rows runs the fused, LDS-tiled sweep kernel (`.fused`); everything else the generic
     kernels on the lists, with the same results to round-off.
-    The smoothed cycle is not a symmetric preconditioner: use fgmres, not pcg, around it."""
+    The smoothed cycle is not a symmetric preconditioner: use fgmres, not pcg, around it -- or ElementPatchGaussSeidel,
+    the multiplicative sweeps over the same patches, whose cycle is symmetric when nPre == nPost and the post weights
+    are the pre weights reversed."""
 
     def __init__(self, A, m, ne, width=2, hybrid=True, ctx=None):
         self.A = _as_op(A, ctx=ctx)
@@ -634,6 +636,36 @@ class ElementPatchSchwarz(AbstractSmoother):
 
     def inverse_blocks(self):
         """the explicit inverses of the patch blocks, (nb, w m, w m) (C ABI aggmg_smoother_download_blocks)"""
+        bm, nb = self.mBlockInds.shape
+        return _download_blocks(self.A.ctx, self.handle, nb, bm)
+
+
+class ElementPatchGaussSeidel(AbstractSmoother):
+    """EXTENSION: multiplicative two-colour smoother of a DG level on the patches {e, e + 1} of two consecutive elements
+    (C ABI aggmg_patch_gs_setup): a forward sweep of weight w is, for the colours c = 0, 1,
+    r = b - A u and u[P_e] += w inv(A[P_e, P_e]) r[P_e] for every patch e = c (mod 2); post-smoothing runs the colours
+    in reverse order.  The same inverses, element blocks and dictionary records as ElementPatchSchwarz, in a fused
+    sweep kernel of its own; there is no generic route (UnsupportedError where the operator is not block tridiagonal in
+    the blocking of ne >= 2 elements of m rows, or m is not instantiated).
+    The smoothed cycle is a symmetric preconditioner when nPre == nPost and the post weights are the pre weights
+    reversed: pcg is valid around it."""
+
+    def __init__(self, A, m, ne, ctx=None):
+        self.A = _as_op(A, ctx=ctx)
+        self.m, self.ne = int(m), int(ne)
+        h = ctypes.c_void_p()
+        c = self.A.ctx
+        c.check(c.lib.aggmg_patch_gs_setup(c.handle, self.A.handle, self.m, self.ne, ctypes.byref(h)))
+        self.handle = h
+        kind, nc = ctypes.c_int(0), ctypes.c_int(0)
+        c.check(c.lib.aggmg_smoother_patch_kind(c.handle, h, ctypes.byref(kind)))
+        c.check(c.lib.aggmg_smoother_patch_dictionary(c.handle, h, ctypes.byref(nc)))
+        self.width, self.fused, self.kind = 2, kind.value == 3, kind.value
+        self.dictionary_classes = nc.value   # 0: the sweeps read the full arrays
+        self.mBlockInds = element_patch_lists(self.m, self.ne, 2)
+
+    def inverse_blocks(self):
+        """the explicit inverses of the patch blocks, (ne - 1, 2 m, 2 m) (C ABI aggmg_smoother_download_blocks)"""
         bm, nb = self.mBlockInds.shape
         return _download_blocks(self.A.ctx, self.handle, nb, bm)
 
@@ -782,6 +814,9 @@ def dg_smoother(dgMesh, A, smootherType, ctx=None):
     if smootherType == 'patchSchwarz':    # extension, see ElementPatchSchwarz: hybrid patches of two elements
         m, ne = _mesh_block_inds(dgMesh).shape
         return ElementPatchSchwarz(A, m, ne, ctx=ctx)
+    if smootherType == 'patchGS':    # extension, see ElementPatchGaussSeidel: multiplicative patches of two elements
+        m, ne = _mesh_block_inds(dgMesh).shape
+        return ElementPatchGaussSeidel(A, m, ne, ctx=ctx)
     raise ArgumentError(f"dg_smoother: unknown smoother type {smootherType!r}")
 
 
@@ -912,7 +947,7 @@ class MeshHierarchy:
         level k + 1.  The Galerkin operators stay in HBM; H.mGradient / mDivergence / mC / mStiffness hold
         DeviceOperators (`.to_scipy()` reads one back).
         smoothers: the dg_smoother type of every smoothed level, or a list of one per level ('blockJac', the
-        reference's; 'patchSchwarz', 'blockGS', 'jac': extensions / other reference types)."""
+        reference's; 'patchSchwarz', 'patchGS', 'blockGS', 'jac': extensions / other reference types)."""
         ctx = ctx or default_context()
         n = len(mMeshes)
         if n < 1:
@@ -1030,7 +1065,8 @@ class MeshHierarchy:
 
     def patch_dictionary_levels(self):
         """{level: distinct operator records} of the levels whose fused element-patch Schwarz smoother sweeps through
-        a dictionary of its own (ElementPatchSchwarz.dictionary_classes, C ABI aggmg_smoother_patch_dictionary)"""
+        a dictionary of its own (ElementPatchSchwarz / ElementPatchGaussSeidel.dictionary_classes, C ABI
+        aggmg_smoother_patch_dictionary)"""
         out = {}
         for k, S in enumerate(self.mSmoothers):
             nc = getattr(S, "dictionary_classes", 0)
@@ -1663,7 +1699,8 @@ def pcg(H, b, x0=None, maxiter=50, tol=1e-10, nPre=3, nPost=3, alpha=2.0 / 3.0):
     resident on the device (C ABI aggmg_pcg_dev).  EXTENSION: the reference offers ldiv! for this
     use but has no Krylov loop.  -> (x, iter, res)
     Needs a symmetric positive definite operator AND a symmetric cycle (nPre == nPost, a sweep-weight schedule whose post
-    half is the pre half reversed, no hybrid Schwarz level); nothing checks that, and on another cycle the result is
+    half is the pre half reversed, no hybrid Schwarz level -- the multiplicative patch smoother, ElementPatchGaussSeidel,
+    gives a symmetric cycle under the same two conditions); nothing checks that, and on another cycle the result is
     wrong without an error: use fgmres there."""
     if isinstance(b, DeviceMatrix) or (not isinstance(b, DeviceVector) and np.ndim(b) == 2):
         return _pcg_multi(H, b, x0, maxiter, tol, nPre, nPost, alpha)

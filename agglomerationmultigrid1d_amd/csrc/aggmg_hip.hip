@@ -887,9 +887,51 @@ static int launch_patch(aggmg_ctx* ctx, const PatchDev& P, const PatchArgs& a, c
   return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: block size not instantiated for the patch sweep kernel");
 }
 
+// the multiplicative two-colour sweeps (aggmg_patch_gs_setup): patch_gs_kernel in the tile of patch_gs_tile_plan
+template <int M, bool CMP>
+static int launch_patch_gs_t(aggmg_ctx* ctx, PatchArgs a, const SweepWeights& wts, bool reverse, const uint16_t* cls) {
+  constexpr int NS = PatchSlabs<M>::NS;
+  static_assert(NS == patch_slabs(M), "the planner sizes the tile the kernel is instantiated for");
+  const PatchTilePlan plan = patch_gs_tile_plan(M, a.nsweeps);   // host_plan.hpp
+  if (plan.owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: multiplicative patch sweep launch without a tile");
+  a.owned = plan.owned;
+  a.halo = plan.halo;
+  const int64_t ntiles = patch_tiles(a.ne, plan.owned);
+  if (ntiles == 0) return AGGMG_OK;
+  const PatchGsArgs g{a, reverse ? 1 : 0};
+  if (cls)
+    hipLaunchKernelGGL((patch_gs_dict_kernel<M, CMP, NS>), dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, g, wts, cls);
+  else
+    hipLaunchKernelGGL((patch_gs_kernel<M, CMP, NS>), dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, g, wts);
+  HIPCHK(hipGetLastError());
+  return AGGMG_OK;
+}
+
+static int launch_patch_gs(aggmg_ctx* ctx, const PatchDev& P, const PatchArgs& a, const SweepWeights& wts, bool reverse,
+                           const uint16_t* cls) {
+  const bool cmp = P.btd->cmp;
+#define CASE(MM)                                                             \
+  case MM:                                                                   \
+    return cmp ? launch_patch_gs_t<MM, true>(ctx, a, wts, reverse, cls) : launch_patch_gs_t<MM, false>(ctx, a, wts, reverse, cls);
+#define CASE_C(MM) \
+  case MM:         \
+    if (cmp) return launch_patch_gs_t<MM, true>(ctx, a, wts, reverse, cls); \
+    break;
+  switch (P.m) {
+    case 1:
+      if (!cmp) return launch_patch_gs_t<1, false>(ctx, a, wts, reverse, cls);
+      break;
+      CASE(2) CASE(3) CASE(4) CASE(5) CASE_C(6) CASE_C(7) CASE_C(8)
+  }
+#undef CASE
+#undef CASE_C
+  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: block size not instantiated for the multiplicative patch sweep kernel");
+}
+
 // nsweeps sweeps from u_in (may be nullptr = zero) into u_out (!= u_in), in launches of up to patch_max_sweeps
+// (multiplicative: patch_gs_max_sweeps; reverse: its colours in the order 1, 0 -- post-smoothing; the others ignore it)
 static int patch_smooth(aggmg_ctx* ctx, const PatchDev& P, const double* u_in, const double* rhs, Damping alpha, int nsweeps,
-                        double* u_out, int level) {
+                        double* u_out, int level, bool reverse = false) {
   const int64_t N = P.ne * P.m;
   if (nsweeps == 0) {
     if (u_in && u_in != u_out)
@@ -898,7 +940,7 @@ static int patch_smooth(aggmg_ctx* ctx, const PatchDev& P, const double* u_in, c
       HIPCHK(hipMemsetAsync(u_out, 0, N * sizeof(double), ctx->stream));
     return AGGMG_OK;
   }
-  const int smax = patch_max_sweeps(P.m);
+  const int smax = P.multiplicative ? patch_gs_max_sweeps(P.m) : patch_max_sweeps(P.m);
   const int nchunks = patch_chunks(nsweeps, smax);
   if (nchunks == 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: patch sweeps without a tile");
   // chunk chain: src -> (scratch0 / scratch1 alternating) -> ... -> u_out
@@ -925,7 +967,11 @@ static int patch_smooth(aggmg_ctx* ctx, const PatchDev& P, const double* u_in, c
     }
     {
       ProfScope ps(ctx, AGGMG_KIND_SMOOTH, level);
-      CHECK(launch_patch(ctx, P, a, alpha.from(c * smax).launch(s), d ? d->cls.get() : nullptr));
+      const uint16_t* cls = d ? d->cls.get() : nullptr;
+      if (P.multiplicative)
+        CHECK(launch_patch_gs(ctx, P, a, alpha.from(c * smax).launch(s), reverse, cls));
+      else
+        CHECK(launch_patch(ctx, P, a, alpha.from(c * smax).launch(s), cls));
     }
     src = dst;
   }
@@ -940,6 +986,53 @@ static void patch_lists(int64_t m, int64_t ne, int width, std::vector<int64_t>* 
   lists->resize((size_t)(*nb * *bm));
   for (int64_t p = 0; p < *nb; ++p)
     for (int64_t j = 0; j < *bm; ++j) (*lists)[p * *bm + j] = p * m + j;
+}
+
+// The fused form of a patch smoother on the element blocks eb of A: the patch blocks assembled from them, inverted, and
+// their rows laid out per DoF row (zrows); then the smoother's operator dictionary where the option is on.  The hybrid /
+// additive sweeps (patch_sweep_kernel) and the multiplicative ones (patch_gs_kernel) read the same arrays.
+static int patch_fused_setup(aggmg_ctx* ctx, aggmg_op* A, int64_t m, int64_t ne, const std::shared_ptr<BtdDev>& eb, bool hybrid,
+                             bool multiplicative, const char* who, aggmg_smoother** out) {
+  auto sm = std::make_unique<aggmg_smoother>();
+  sm->kind = hybrid ? 2 : 1;   // (multiplicative: 1 -- aggmg_smoother_patch_info's hybrid stays 0)
+  sm->A = A;
+  sm->N = A->m;
+  sm->m = 2 * m;
+  sm->nb = ne - 1;
+  sm->overlapping = true;
+  sm->patch_width = 2;
+  auto P = std::make_shared<PatchDev>();
+  P->m = (int)m;
+  P->ne = ne;
+  P->hybrid = hybrid;
+  P->multiplicative = multiplicative;
+  P->btd = eb;
+  {
+    const int64_t words = (ne - 1) * 4 * m * m;
+    DevArray<double> blocks, zinv;
+    CHECK(blocks.alloc(ctx, words));
+    CHECK(zinv.alloc(ctx, words));
+    hipLaunchKernelGGL(patch_assemble_kernel, dim3((unsigned)((words + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream,
+                       words, (int)m, eb->cmp ? 1 : 0, eb->c_sub, eb->r_sup, (const double*)eb->dblk, (const double*)eb->scol,
+                       (const double*)eb->qrow, (const double*)eb->sub, (const double*)eb->sup, blocks.get());
+    HIPCHK(hipGetLastError());
+    int64_t sing = -1;
+    CHECK(setup_invert_blocks(ctx, ne - 1, (int)(2 * m), blocks, 0, zinv, &sing));
+    if (sing >= 0)
+      return fail(ctx, AGGMG_ERR_SINGULAR,
+                  std::string(who) + ": singular patch " + std::to_string(sing + 1) + " (SingularException)");
+    const int64_t zw = A->m * 4 * m;
+    CHECK(P->zrows.alloc(ctx, zw));
+    hipLaunchKernelGGL(patch_zrows_kernel, dim3((unsigned)((zw + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream, zw,
+                       (int)m, ne, (const double*)zinv, P->zrows.get());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // the temporaries go out of scope
+  }
+  // the smoother's distinct operator records, where they are few (AGGMG_OPT_OPERATOR_DICTIONARY)
+  if (ctx->op_dict) CHECK(setup_patch_dictionary(ctx, *P));
+  sm->patch = P;
+  *out = sm.release();
+  return AGGMG_OK;
 }
 
 extern "C" int aggmg_patch_schwarz_setup(aggmg_ctx* ctx, aggmg_op* A, int64_t m, int64_t ne, int width, int hybrid,
@@ -973,44 +1066,49 @@ extern "C" int aggmg_patch_schwarz_setup(aggmg_ctx* ctx, aggmg_op* A, int64_t m,
     (*out)->patch_width = width;
     return AGGMG_OK;
   }
-  auto sm = std::make_unique<aggmg_smoother>();
-  sm->kind = hybrid ? 2 : 1;
-  sm->A = A;
-  sm->N = A->m;
-  sm->m = 2 * m;
-  sm->nb = ne - 1;
-  sm->overlapping = true;
-  sm->patch_width = 2;
-  auto P = std::make_shared<PatchDev>();
-  P->m = (int)m;
-  P->ne = ne;
-  P->hybrid = hybrid != 0;
-  P->btd = eb;
-  {
-    const int64_t words = (ne - 1) * 4 * m * m;
-    DevArray<double> blocks, zinv;
-    CHECK(blocks.alloc(ctx, words));
-    CHECK(zinv.alloc(ctx, words));
-    hipLaunchKernelGGL(patch_assemble_kernel, dim3((unsigned)((words + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream,
-                       words, (int)m, eb->cmp ? 1 : 0, eb->c_sub, eb->r_sup, (const double*)eb->dblk, (const double*)eb->scol,
-                       (const double*)eb->qrow, (const double*)eb->sub, (const double*)eb->sup, blocks.get());
-    HIPCHK(hipGetLastError());
-    int64_t sing = -1;
-    CHECK(setup_invert_blocks(ctx, ne - 1, (int)(2 * m), blocks, 0, zinv, &sing));
-    if (sing >= 0)
-      return fail(ctx, AGGMG_ERR_SINGULAR,
-                  "aggmg_patch_schwarz_setup: singular patch " + std::to_string(sing + 1) + " (SingularException)");
-    const int64_t zw = A->m * 4 * m;
-    CHECK(P->zrows.alloc(ctx, zw));
-    hipLaunchKernelGGL(patch_zrows_kernel, dim3((unsigned)((zw + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream, zw,
-                       (int)m, ne, (const double*)zinv, P->zrows.get());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));   // the temporaries go out of scope
-  }
-  // the smoother's distinct operator records, where they are few (AGGMG_OPT_OPERATOR_DICTIONARY)
-  if (ctx->op_dict) CHECK(setup_patch_dictionary(ctx, *P));
-  sm->patch = P;
-  *out = sm.release();
+  return patch_fused_setup(ctx, A, m, ne, eb, hybrid != 0, false, "aggmg_patch_schwarz_setup", out);
+}
+
+extern "C" int aggmg_patch_gs_setup(aggmg_ctx* ctx, aggmg_op* A, int64_t m, int64_t ne, aggmg_smoother** out) {
+  if (!ctx || !A || !out) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_patch_gs_setup: NULL argument");
+  *out = nullptr;
+  if (A->m != A->n) return fail(ctx, AGGMG_ERR_DIMENSION, "aggmg_patch_gs_setup: operator is not square");
+  if (m < 1 || ne < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_patch_gs_setup: rows per element and elements must be >= 1");
+  if (A->m != m * ne) return fail(ctx, AGGMG_ERR_DIMENSION, "aggmg_patch_gs_setup: operator size is not m * ne");
+  if (A->m * 2 >= ((int64_t)1 << 31)) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_patch_gs_setup: 2 * m * ne >= 2^31");
+  // the fused form or none: the sweeps exist as patch_gs_kernel only
+  if (ne < 2)
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_patch_gs_setup: a level of one element has no patch of two elements");
+  if (m > 9 || patch_gs_max_sweeps((int)m) < 1)
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED,
+                "aggmg_patch_gs_setup: the sweep kernel is not instantiated for " + std::to_string(m) + " rows per element");
+  HIPCHK(hipSetDevice(ctx->device));
+  std::vector<int64_t> lists;
+  int64_t bm = 0, nb = 0;
+  patch_lists(m, ne, 1, &lists, &bm, &nb);
+  aggmg_smoother* elem = nullptr;
+  const int st = aggmg_blockjacobi_setup(ctx, A, m, ne, lists.data(), 0, 0, &elem);
+  if (st != AGGMG_OK && !elem) return st;   // (the element blocks come from that set-up: without them, its error stands)
+  std::shared_ptr<BtdDev> eb = elem ? elem->btd : nullptr;
+  if (elem) CHECK(aggmg_smoother_free(ctx, elem));
+  if (!eb)
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_patch_gs_setup: the operator is not block tridiagonal in the element blocking");
+  if (!patch_instantiated((int)m, eb->cmp))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED,
+                "aggmg_patch_gs_setup: the sweep kernel is not instantiated for " + std::to_string(m) + " rows per element with " +
+                    (eb->cmp ? "compressed" : "dense") + " couplings");
+  return patch_fused_setup(ctx, A, m, ne, eb, false, true, "aggmg_patch_gs_setup", out);
+}
+
+extern "C" int aggmg_smoother_patch_kind(aggmg_ctx* ctx, const aggmg_smoother* sm, int* kind) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!sm || !kind) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smoother_patch_kind: NULL argument");
+  if (!sm->patch_width)
+    *kind = 0;
+  else if (sm->patch && sm->patch->multiplicative)
+    *kind = 3;
+  else
+    *kind = sm->kind == 2 ? 2 : 1;
   return AGGMG_OK;
 }
 
@@ -1027,6 +1125,16 @@ extern "C" int aggmg_smoother_patch_dictionary(aggmg_ctx* ctx, const aggmg_smoot
   if (!ctx) return AGGMG_ERR_ARGUMENT;
   if (!sm || !nclasses) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smoother_patch_dictionary: NULL argument");
   *nclasses = (sm->patch && sm->patch->dict) ? sm->patch->dict->nclasses : 0;
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_patch_gs_tile_plan(int m, int nsweeps, int* tile_elems, int* owned, int* halo, int* max_sweeps) {
+  if (!tile_elems || !owned || !halo || !max_sweeps) return AGGMG_ERR_ARGUMENT;
+  const PatchTilePlan p = patch_gs_tile_plan(m, nsweeps);   // host_plan.hpp: what launch_patch_gs_t runs
+  *tile_elems = p.te;
+  *owned = p.owned;
+  *halo = p.halo;
+  *max_sweeps = patch_gs_max_sweeps(m);
   return AGGMG_OK;
 }
 
@@ -2438,6 +2546,7 @@ static int patch_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uin, c
 static int patch_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* rhs, int nPost, double alpha, double* dst) {
   Level& l = h->lv[k];
   const PatchDev& P = *l.S->patch;
+  // (post-smoothing: the multiplicative sweeps run their colours in reverse order, patch_down's in forward order)
   // the prolonged iterate goes through l.tmp: the fused launch wants another vector than its input, the sweeps too
   if (patch_transfer_ok(l, 0, nullptr)) {
     FusedLaunch a = fused_sweeps(*P.btd, l.u[0], rhs, l.tmp, 0.0, 0);
@@ -2447,10 +2556,10 @@ static int patch_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* rhs, int
       ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
       CHECK(launch_btd(ctx, *P.btd, a, 0));
     }
-    return patch_smooth(ctx, P, l.tmp, rhs, l.damp_post(alpha), nPost, dst, k);
+    return patch_smooth(ctx, P, l.tmp, rhs, l.damp_post(alpha), nPost, dst, k, true);
   }
   CHECK(generic_prolong_add(ctx, h, k));
-  return patch_smooth(ctx, P, l.u[0], rhs, l.damp_post(alpha), nPost, dst, k);
+  return patch_smooth(ctx, P, l.u[0], rhs, l.damp_post(alpha), nPost, dst, k, true);
 }
 
 // Generic levels: generic_sweeps between the generic launches.  The descent sweeps in place in l.u[0] (point Jacobi:

@@ -348,11 +348,38 @@ inline int64_t patch_tiles(int64_t ne, int owned) { return owned > 0 ? (ne + own
 inline int patch_chunks(int sweeps, int smax) { return sweeps <= 0 || smax <= 0 ? 0 : (sweeps + smax - 1) / smax; }
 inline int patch_chunk_sweeps(int sweeps, int smax, int c) { return std::min(smax, sweeps - c * smax); }
 
+// ---- multiplicative two-colour patch sweeps (patch_gs_kernel) ---------------------------------------------------------
+// The same tile of elements.  A sweep is two half-sweeps, each a residual and the patch solves of one colour: together
+// they reach 3 elements to one side and 2 to the other (which side depends on the element's parity and the direction),
+// and the wide sides of consecutive sweeps alternate: S sweeps reach 2 S + 1 elements, the halo of a launch.  The most
+// sweeps a launch takes: as many as its weights array holds and the halos leave half the tile to own (at least one
+// where one sweep leaves a tile at all; 0: no tile).  LDS: the iterate, updated in place, and the residual, each
+// padded by one element a side.  A longer run is chunked as the hybrid sweeps are: patch_chunks / patch_chunk_sweeps
+// with patch_gs_max_sweeps.
+inline int patch_gs_halo(int sweeps) { return 2 * sweeps + 1; }
+inline int patch_gs_owned(int te, int sweeps) { return std::max(0, te - 2 * patch_gs_halo(sweeps)); }
+inline PatchTilePlan patch_gs_tile_plan(int m, int sweeps, int threads = 256) {
+  PatchTilePlan p;
+  p.te = patch_tile_elems(m, threads);
+  if (p.te <= 0 || sweeps < 1 || sweeps > kPatchMaxSweeps) return p;
+  p.halo = patch_gs_halo(sweeps);
+  p.owned = patch_gs_owned(p.te, sweeps);
+  p.lds_bytes = (size_t)2 * (p.te + 2) * m * sizeof(double);
+  return p;
+}
+inline int patch_gs_max_sweeps(int m, int threads = 256) {
+  const int te = patch_tile_elems(m, threads);
+  if (patch_gs_tile_plan(m, 1, threads).owned <= 0) return 0;
+  int s = 1;
+  while (s < kPatchMaxSweeps && 2 * patch_gs_owned(te, s + 1) >= te) ++s;
+  return s;
+}
+
 // ---- does a launch have a tile? ----------------------------------------------------------------------------------
 // One question for every tiled launch, answered by the planner its launcher runs: the callers that choose between a
 // launch and its fallback (two levels or one per launch, fused or unfused sequence, K columns or column by column) ask
 // here, so a launch that was chosen never finds "no tile".
-enum TileLaunch { kTileFused = 0, kTileMulti = 1, kTilePairDown = 2, kTilePairUp = 3, kTilePatch = 4 };
+enum TileLaunch { kTileFused = 0, kTileMulti = 1, kTilePairDown = 2, kTilePairUp = 3, kTilePatch = 4, kTilePatchGs = 5 };
 struct TileQuery {
   int launch = kTileFused;
   int te = 0, te_b = 0;   // elements a workgroup holds (pairs: of level A and of level B)
@@ -370,6 +397,7 @@ inline bool launch_has_tile(const TileQuery& q) {
     case kTilePairDown: return pair_down_plan(q.halo, q.align, q.rho_bc, q.te, q.te_b).own > 0;
     case kTilePairUp: return pair_up_plan(q.halo, q.align, q.te, q.te_b).own > 0;
     case kTilePatch: return q.halo >= 1 && q.halo <= kPatchMaxSweeps && patch_owned(q.te, q.halo) > 0;
+    case kTilePatchGs: return q.halo >= 1 && q.halo <= kPatchMaxSweeps && patch_gs_owned(q.te, q.halo) > 0;
   }
   return false;
 }

@@ -193,6 +193,7 @@ struct PatchDev {
   int m = 0;         // rows per element
   int64_t ne = 0;
   bool hybrid = true;
+  bool multiplicative = false;   // aggmg_patch_gs_setup: two-colour sweeps over the same patches (patch_gs_kernel)
   std::shared_ptr<BtdDev> btd;   // the element blocks of A: the sweeps' residual rows and the level's transfer launches
   DevArray<double> zrows;        // [N][2][2m] per row the two inverse rows it applies (zeros where a patch does not exist)
   std::unique_ptr<PatchDictDev> dict;   // operator dictionary of the sweep launches (AGGMG_OPT_OPERATOR_DICTIONARY), or null

@@ -292,6 +292,181 @@ __global__ __launch_bounds__(kThreads) void patch_sweep_dict_kernel(PatchArgs a,
   }
 }
 
+// ---- multiplicative two-colour sweeps (aggmg_patch_gs_setup) -------------------------------------
+// The same patches, inverse rows and element blocks, applied one colour at a time: a forward sweep of weight w is the
+// half-sweeps c = 0, 1 (a reverse one: c = 1, 0), each
+//   r = b - A u                          (from the current u; ascending columns: btd_apply_cmp / _dense)
+//   u[P_e] += w Z_e r[P_e]               for every patch e = c (mod 2), each dot product in ascending j
+// The patches of a colour are disjoint, so a row applies one inverse row per half-sweep: slot 1 of its zrows (row i of
+// Z_e, against r[e], r[e + 1]) where e = c (mod 2) and e <= ne - 2, slot 0 (row M + i of Z_{e-1}, against r[e - 1], r[e])
+// where e != c (mod 2) and e >= 1; an element no patch of the colour covers keeps its value.
+struct PatchGsArgs {
+  PatchArgs p;   // owned / halo: the tile keeps halo = 2 * nsweeps + 1 elements on either side (patch_gs_tile_plan)
+  int reverse;   // 0: colours 0, 1; 1: colours 1, 0 (post-smoothing) -- the same in every lane
+};
+
+// Tile, load phase and operator registers of patch_sweep_kernel (DICT: of patch_sweep_dict_kernel).  A row writes only
+// its own entry of the iterate and reads only the residual while it does, so the iterate is updated in place: one iterate
+// and one residual vector in LDS, each padded by one zero element a side.  Temporal blocking: a half-sweep reads
+// u[e - 1 .. e + 2] (first element of its patch) or u[e - 2 .. e + 1] (second), so a sweep reaches 3 elements to one side
+// and 2 to the other and S sweeps reach 2 S + 1: the elements 2 S + 1 and more away from the tile's ends hold what sweeps
+// over the whole level give.  Plain C++ per row -- no atomics, no cross-lane operations -- so no result depends on where
+// the tiles lie.
+template <int M, bool CMP, int NS, bool DICT>
+__device__ __forceinline__ void patch_gs_body(const PatchGsArgs& g, const SweepWeights& wts, const uint16_t* __restrict__ cls) {
+  const PatchArgs& a = g.p;
+  constexpr int EPS = kThreads / M;   // elements per slab
+  constexpr int TE = EPS * NS;        // elements per tile (owned + halos)
+  constexpr int PL = (TE + 2) * M;    // a padded vector of the tile: index x * M + j, x in [-1, TE]
+  extern __shared__ double lds[];
+  double* cur = lds + M;
+  double* res = cur + PL;
+
+  const int tid = threadIdx.x;
+  const bool active = tid < EPS * M;
+  const int le = tid / M;
+  const int i = tid - le * M;
+  const int64_t ne = a.ne;
+  const int64_t e0 = (int64_t)blockIdx.x * a.owned - a.halo;   // element at x = 0
+
+  if (tid < M) {
+    cur[-M + tid] = 0.0;
+    cur[TE * M + tid] = 0.0;
+    res[-M + tid] = 0.0;
+    res[TE * M + tid] = 0.0;
+  }
+
+  double dk[NS][M], lo[NS][CMP ? 1 : M], hi[NS][M], z[NS][4 * M], bb[NS], uu[NS];
+  bool valid[NS], with_prev[NS], with_next[NS];   // the patches {e - 1, e} and {e, e + 1} exist
+  int par[NS];                                    // e mod 2
+  int c[NS];
+
+  // ---- load phase: everything the tile needs from HBM (DICT: its operator words from the dictionary), once ----------------
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int64_t e = e0 + s * EPS + le;
+    valid[s] = active && e >= 0 && e < ne;
+    c[s] = (DICT && valid[s]) ? (int)cls[e] : 0;
+  }
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int x = s * EPS + le;
+    const int64_t e = e0 + x;
+    par[s] = (int)(e & 1);
+    with_prev[s] = valid[s] && e >= 1;
+    with_next[s] = valid[s] && e <= ne - 2;
+    bb[s] = 0.0;
+    uu[s] = 0.0;
+#pragma unroll
+    for (int j = 0; j < M; ++j) dk[s][j] = hi[s][j] = 0.0;
+#pragma unroll
+    for (int j = 0; j < (CMP ? 1 : M); ++j) lo[s][j] = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4 * M; ++j) z[s][j] = 0.0;
+    if (valid[s]) {
+      const int64_t row = e * M + i;
+      if constexpr (DICT) {
+        const int crow = c[s] * M + i;   // the row in its class's record (c < kDictMaxClasses: 32-bit offsets)
+        const double* zr = a.zrows + crow * (4 * M);
+#pragma unroll
+        for (int j = 0; j < 4 * M; ++j) z[s][j] = zr[j];
+#pragma unroll
+        for (int j = 0; j < M; ++j) dk[s][j] = a.dblk[crow * M + j];
+        if constexpr (CMP) {
+          lo[s][0] = a.scol[crow];
+          if (i == a.r_sup) {
+#pragma unroll
+            for (int j = 0; j < M; ++j) hi[s][j] = a.qrow[c[s] * M + j];
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < M; ++j) lo[s][j] = a.sub[crow * M + j];
+#pragma unroll
+          for (int j = 0; j < M; ++j) hi[s][j] = a.sup[crow * M + j];
+        }
+      } else {
+        const double* zr = a.zrows + row * (4 * M);
+#pragma unroll
+        for (int j = 0; j < 4 * M; ++j) z[s][j] = AGGMG_LD(zr[j]);
+#pragma unroll
+        for (int j = 0; j < M; ++j) dk[s][j] = AGGMG_LD(a.dblk[row * M + j]);
+        if constexpr (CMP) {
+          lo[s][0] = AGGMG_LD(a.scol[row]);
+          if (i == a.r_sup) {
+#pragma unroll
+            for (int j = 0; j < M; ++j) hi[s][j] = a.qrow[e * M + j];
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < M; ++j) lo[s][j] = AGGMG_LD(a.sub[row * M + j]);
+#pragma unroll
+          for (int j = 0; j < M; ++j) hi[s][j] = AGGMG_LD(a.sup[row * M + j]);
+        }
+      }
+      bb[s] = a.b[row];
+      if (a.u_in) uu[s] = a.u_in[row];
+    }
+    if (active) cur[x * M + i] = uu[s];
+  }
+  __syncthreads();
+
+  for (int sw = 0; sw < a.nsweeps; ++sw) {
+    const double w = wts.w[sw];   // this sweep's factor, for both of its halves: wave-uniform, a scalar load
+    for (int h = 0; h < 2; ++h) {
+      const int colour = h ^ g.reverse;
+      // residual rows of the tile (zero outside the level)
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        if (!active) continue;
+        const int x = s * EPS + le;
+        const double *um = cur + (x - 1) * M, *ux = cur + x * M, *up = cur + (x + 1) * M;
+        double t;
+        if constexpr (CMP)
+          t = btd_apply_cmp<M, false>(lo[s][0], dk[s], hi[s], um, ux, up, a.c_sub, a.r_sup, i);
+        else
+          t = btd_apply_dense<M>(lo[s], dk[s], hi[s], um, ux, up);
+        res[x * M + i] = valid[s] ? bb[s] - t : 0.0;
+      }
+      __syncthreads();
+      // the one patch of this colour covering the row: the element is its first one (slot 1) or its second (slot 0)
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        if (!active) continue;
+        const int x = s * EPS + le;
+        const bool first = par[s] == colour;
+        const double* r = res + (first ? x : x - 1) * M;
+        double y = 0.0;
+#pragma unroll
+        for (int j = 0; j < 2 * M; ++j) y += (first ? z[s][2 * M + j] : z[s][j]) * r[j];
+        if (first ? with_next[s] : with_prev[s]) {
+          uu[s] = uu[s] + w * y;
+          cur[x * M + i] = uu[s];
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int x = s * EPS + le;
+    if (valid[s] && x >= a.halo && x < a.halo + a.owned) AGGMG_ST(a.u_out[(e0 + x) * M + i], uu[s]);
+  }
+}
+
+template <int M, bool CMP, int NS>
+__global__ __launch_bounds__(kThreads) void patch_gs_kernel(PatchGsArgs g, SweepWeights wts) {
+  patch_gs_body<M, CMP, NS, false>(g, wts, nullptr);
+}
+
+// the operator read through the smoother's dictionary, as patch_sweep_dict_kernel reads it: the same bits, so every
+// result is patch_gs_kernel's
+template <int M, bool CMP, int NS>
+__global__ __launch_bounds__(kThreads) void patch_gs_dict_kernel(PatchGsArgs g, SweepWeights wts,
+                                                                 const uint16_t* __restrict__ cls) {
+  patch_gs_body<M, CMP, NS, true>(g, wts, cls);
+}
+
 // ---- set-up ---------------------------------------------------------------------------------------------------------------
 // the dense patch blocks A[P_p, P_p], [ne - 1][2m][2m] row-major, from the element blocks of A: one thread per entry
 static __global__ __launch_bounds__(kThreads) void patch_assemble_kernel(int64_t total, int m, int cmp, int c_sub, int r_sup,

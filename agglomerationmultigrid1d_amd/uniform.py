@@ -627,24 +627,29 @@ def build_device_hierarchy(U, ctx=None, keep_host=False, smoother="blockJac", cs
     """Upload a UniformDgAggHierarchy through the CSC boundary and return the product
     MeshHierarchy (block-Jacobi on every smoothed level, src/mesh_heirarchy.jl:58,73,85,104;
     smoother="blockGS": the labelled red-black block Gauss-Seidel extension; "patchSchwarz" / "patchSchwarz0": the
-    element-patch Schwarz extension on every smoothed level / on the fine level only).
+    element-patch Schwarz extension on every smoothed level / on the fine level only; "patchGS" / "patchGS0": its
+    multiplicative two-colour form, ElementPatchGaussSeidel, likewise).
     csc = (stiffness list, interpolation list): matrices already assembled by the caller (bench.py times
     the generator and the library set-up apart)."""
-    from .api import BlockGaussSeidel, BlockJacobi, DeviceOperator, ElementPatchSchwarz, MeshHierarchy
+    from .api import BlockGaussSeidel, BlockJacobi, DeviceOperator, ElementPatchGaussSeidel, ElementPatchSchwarz, MeshHierarchy
     from . import _lib
 
     def patch(op, inds, ctx):   # hybrid patches of two elements (ElementPatchSchwarz)
         return ElementPatchSchwarz(op, inds.shape[0], inds.shape[1], ctx=ctx)
 
-    # "patchSchwarz": on every smoothed level; "patchSchwarz0": on the fine level, block-Jacobi below
-    make = {"blockJac": BlockJacobi, "blockGS": BlockGaussSeidel, "patchSchwarz": patch, "patchSchwarz0": patch}[smoother]
+    def patch_gs(op, inds, ctx):   # multiplicative patches of two elements (ElementPatchGaussSeidel)
+        return ElementPatchGaussSeidel(op, inds.shape[0], inds.shape[1], ctx=ctx)
+
+    # "patchSchwarz" / "patchGS": on every smoothed level; "patchSchwarz0" / "patchGS0": on the fine level, block-Jacobi below
+    make = {"blockJac": BlockJacobi, "blockGS": BlockGaussSeidel, "patchSchwarz": patch, "patchSchwarz0": patch,
+            "patchGS": patch_gs, "patchGS0": patch_gs}[smoother]
     n = U.nlevels
     ops, sms = [], []
     for k in range(n):
         op = DeviceOperator(csc[0][k] if csc else U.stiffness_csc(k), _lib.OP_STIFFNESS, ctx)
         ops.append(op)
         if k < n - 1:
-            sms.append((BlockJacobi if smoother == "patchSchwarz0" and k > 0 else make)(op, U.descriptor(k).mBlockInds, ctx))
+            sms.append((BlockJacobi if smoother in ("patchSchwarz0", "patchGS0") and k > 0 else make)(op, U.descriptor(k).mBlockInds, ctx))
     Ls = [DeviceOperator(csc[1][k] if csc else U.interpolation_csc(k), _lib.OP_TRANSFER, ctx) for k in range(n - 1)]
     H = MeshHierarchy([U.descriptor(k) for k in range(n)], ops, sms, Ls, ctx=ctx, keep_host=keep_host)
     return H

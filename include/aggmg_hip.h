@@ -240,7 +240,8 @@ int aggmg_blockdiag_setup(aggmg_ctx* ctx, int64_t m, int64_t nb, const double* b
  * Same results to round-off; aggmg_smoother_patch_info reports fused = 0.
  * A singular patch -> AGGMG_ERR_SINGULAR naming it (1-based).
  * The smoothed V-cycle is NOT a symmetric preconditioner (the division by the cover counts does not commute with
- * the patch solves): aggmg_pcg_dev is not valid on a hierarchy holding such a level, aggmg_fgmres_dev is.
+ * the patch solves): aggmg_pcg_dev is not valid on a hierarchy holding such a level, aggmg_fgmres_dev is.  (The
+ * multiplicative sweeps over the same patches, aggmg_patch_gs_setup, give a symmetric cycle.)
  * aggmg_dist_create refuses such a hierarchy (AGGMG_ERR_UNSUPPORTED): a sweep reaches two elements. */
 int aggmg_patch_schwarz_setup(aggmg_ctx* ctx, aggmg_op* A, int64_t m, int64_t ne, int width, int hybrid,
                               aggmg_smoother** out);
@@ -253,6 +254,31 @@ int aggmg_smoother_patch_dictionary(aggmg_ctx* ctx, const aggmg_smoother* sm, in
  * it): a launch of nsweeps sweeps holds tile_elems elements per workgroup, of which it owns `owned` (0: no such
  * launch); runs of more than max_sweeps sweeps are cut into launches of at most that many. */
 int aggmg_patch_tile_plan(int m, int nsweeps, int* tile_elems, int* owned, int* max_sweeps);
+/* EXTENSION: MULTIPLICATIVE two-colour element-patch smoother of a DG level: the patches
+ * P_e = {e, e + 1}, e = 0 .. ne - 2, of aggmg_patch_schwarz_setup's fused form -- the same element blocks, the same
+ * inverse rows, the same dictionary records -- applied one colour at a time.  A forward sweep of weight w is the
+ * half-sweeps c = 0, 1, each
+ *     r = b - A u  (from the current u);   u[P_e] += w inv(A[P_e, P_e]) r[P_e]  for every patch e = c (mod 2)
+ * (the patches of a colour are disjoint; an element none of them covers keeps its value); a reverse sweep runs c = 1, 0.
+ * aggmg_smooth(_weighted)_dev, aggmg_smoother_solve_dev, aggmg_smoother_apply, aggmg_hier_estimate_lambda_max and the
+ * pre-smoothing of a cycle run forward sweeps, the post-smoothing of a cycle reverse ones; a weight schedule applies
+ * w_s to both halves of sweep s.  The sweeps run in patch_gs_kernel, up to AGGMG_MAX_SWEEP_WEIGHTS per launch (see
+ * aggmg_patch_gs_tile_plan).  With nPre == nPost and the post weights the pre weights reversed, the V-cycle is a
+ * SYMMETRIC preconditioner on a symmetric operator: aggmg_pcg_dev is valid on such a hierarchy.
+ *   There is no generic route.  AGGMG_ERR_UNSUPPORTED, the message naming the reason, where the fused form does not
+ * apply: ne < 2, an operator that is not block tridiagonal in the element blocking, a block size the kernel is not
+ * instantiated for (compressed couplings 2 .. 8, dense 1 .. 5).  A singular patch -> AGGMG_ERR_SINGULAR naming it
+ * (1-based).  Memory, dictionary, aggmg_smoother_download_blocks, aggmg_smoother_patch_info (width 2, hybrid 0,
+ * fused 1), aggmg_smoother_launch_bytes and the refusals of aggmg_dist_create / aggmg_hier_launch_bytes are those of
+ * the fused form of aggmg_patch_schwarz_setup; K columns run column by column. */
+int aggmg_patch_gs_setup(aggmg_ctx* ctx, aggmg_op* A, int64_t m, int64_t ne, aggmg_smoother** out);
+/* kind: 0 sm is not an element-patch smoother, 1 additive, 2 hybrid (aggmg_patch_schwarz_setup), 3 multiplicative
+ * (aggmg_patch_gs_setup) */
+int aggmg_smoother_patch_kind(aggmg_ctx* ctx, const aggmg_smoother* sm, int* kind);
+/* The tiles of the multiplicative sweep launch, as aggmg_patch_tile_plan gives the hybrid one's: a launch of nsweeps
+ * sweeps holds tile_elems elements per workgroup, keeps `halo` = 2 nsweeps + 1 of them on either side and owns `owned`
+ * (0: no such launch); runs of more than max_sweeps sweeps are cut into launches of at most that many. */
+int aggmg_patch_gs_tile_plan(int m, int nsweeps, int* tile_elems, int* owned, int* halo, int* max_sweeps);
 int aggmg_smoother_free(aggmg_ctx* ctx, aggmg_smoother* sm);
 /* apply_smoother(S, B; alpha) -> alpha * (S \ B), B is N x ncols column-major, result in Y.
  * src/smoother.jl:6-18,30-46,56-58,69-81.  Host pointers. */

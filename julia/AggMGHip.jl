@@ -158,6 +158,14 @@ function device_patch_smoother(op::DeviceOperator, m::Integer, ne::Integer; widt
         op.ctx.h, op.h, m, ne, width, hybrid ? 1 : 0, r))
     return _wrap_smoother(op.ctx, op, r[])
 end
+# Multiplicative two-colour sweeps over the same patches of two elements (extension, aggmg_patch_gs_setup): fused form
+# only (UnsupportedError otherwise).  The cycle is symmetric for nPre == nPost: pcg is valid around it.
+function device_patch_gs_smoother(op::DeviceOperator, m::Integer, ne::Integer)
+    r = Ref{Handle}(C_NULL)
+    check(op.ctx.h, ccall((:aggmg_patch_gs_setup, LIB), Cint, (Handle, Handle, Int64, Int64, Ref{Handle}),
+        op.ctx.h, op.h, m, ne, r))
+    return _wrap_smoother(op.ctx, op, r[])
+end
 # distinct operator records of the fused patch smoother's dictionary (0: none, its sweeps read the full arrays)
 function patch_dictionary_classes(S::DeviceSmoother)
     r = Ref{Cint}(0)
@@ -182,6 +190,10 @@ function dg_smoother(dgMesh, A::DeviceOperator, smootherType::Symbol)
     if smootherType == :patchSchwarz   # extension
         inds = element_nodes(dgMesh)
         return device_patch_smoother(A, size(inds, 1), size(inds, 2))
+    end
+    if smootherType == :patchGS   # extension
+        inds = element_nodes(dgMesh)
+        return device_patch_gs_smoother(A, size(inds, 1), size(inds, 2))
     end
     throw(ArgumentError("dg_smoother: unknown smoother type $smootherType"))
 end

@@ -23,7 +23,14 @@ on and two with it off in one process, on one stream, the four legs alternating 
 aggmg_patch_schwarz_setup (host clock around the synchronous call) and class counts, the sweep launch for S = 1, 3, 6 with
 its compulsory bytes each way, one V(3,3) cycle, the multigrid and fgmres V(3,3) solves.  The second off leg runs the
 same kernels as the first: the spread between the two is the noise margin beside every on / off ratio.  GATE at 2^22
-elements, S = 3: on <= off (within that margin).  One JSON line per measurement."""
+elements, S = 3: on <= off (within that margin).  One JSON line per measurement.
+
+--gs: the multiplicative two-colour smoother (aggmg_patch_gs_setup) against the hybrid one, for the
+operator dictionary on and then off: contexts "hybrid", "hybrid2" (patchSchwarz0 twice: the spread of the two is the noise
+margin), "gs0" (patchGS0) and "gs" (patchGS on every smoothed level) on one stream, alternating inside every repetition.
+The sweep launch for S = 1, 3, 6, one V(3,3) cycle, and the solves to 1e-8 ||b||: multigrid V(3,3) and V(2,2) on the hybrid
+legs and on gs0, fgmres V(3,3) on the hybrid leg, pcg V(3,3), V(2,2), V(1,1) on gs0 and gs.  CONDITION at 2^20 elements with
+the dictionary on: multigrid V(3,3) on gs0 takes no longer than on hybrid, by more than that margin."""
 import argparse
 import ctypes
 import json
@@ -45,6 +52,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--no-solve", action="store_true")
     ap.add_argument("--dictionary", action="store_true")
+    ap.add_argument("--gs", action="store_true")
     args = ap.parse_args()
     import torch
     import agglomerationmultigrid1d_amd as mg
@@ -52,8 +60,8 @@ def main():
     ctx = mg.Context(0)
     stream = torch.cuda.Stream()
     ctx.set_stream(stream.cuda_stream)
-    if args.dictionary:
-        dictionary_legs(args, torch, mg, _lib, uniform, stream)
+    if args.dictionary or args.gs:
+        (dictionary_legs if args.dictionary else gs_legs)(args, torch, mg, _lib, uniform, stream)
         ctx.close()
         return
     lib, h = ctx.lib, ctx.handle
@@ -283,6 +291,114 @@ def dictionary_legs(args, torch, mg, _lib, uniform, stream):
         del Hs
     for c in ctxs.values():
         c.close()
+
+
+def gs_legs(args, torch, mg, _lib, uniform, stream):
+    pd = ctypes.POINTER(ctypes.c_double)
+    smoothers = {"hybrid": "patchSchwarz0", "hybrid2": "patchSchwarz0", "gs0": "patchGS0", "gs": "patchGS"}
+
+    def timed_all(fns, reps, warm=3):
+        for _ in range(warm):
+            for fn in fns.values():
+                fn()
+        ms = {k: [] for k in fns}
+        for _ in range(reps):
+            for k, fn in fns.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record(stream)
+                fn()
+                b.record(stream)
+                b.synchronize()
+                ms[k].append(a.elapsed_time(b))
+        return {k: float(np.median(v)) for k, v in ms.items()}
+
+    def rounded(t):
+        return {k: round(v, 4) for k, v in t.items()}
+
+    for E in args.log2_elems:
+        ne = 2 ** E
+        U = uniform.UniformDgAggHierarchy(ne, p=3, pAgg=1, ratios=(4, 2, 2))
+        csc = ([U.stiffness_csc(k) for k in range(U.nlevels)], [U.interpolation_csc(k) for k in range(U.nlevels - 1)])
+        b = U.rhs()
+        nb = float(np.linalg.norm(b))
+        N = len(b)
+        for dictionary in (1, 0):
+            ctxs = {}
+            for name in smoothers:
+                ctxs[name] = mg.Context(0)
+                ctxs[name].set_stream(stream.cuda_stream)
+                ctxs[name].set_option(_lib.OPT_OPERATOR_DICTIONARY, dictionary)
+            Hs = {k: uniform.build_device_hierarchy(U, c, smoother=smoothers[k], csc=csc) for k, c in ctxs.items()}
+            tag = {"log2_elems": E, "dictionary": dictionary}
+            print(json.dumps(dict(tag, what="classes", patch={k: H.patch_dictionary_levels() for k, H in Hs.items()})), flush=True)
+            rng = np.random.default_rng(E)
+            u0, rhs = rng.standard_normal(N), rng.standard_normal(N)
+            vec = {k: (c.to_device(u0), c.to_device(rhs), c.alloc(N), c.to_device(b), c.alloc(N), c.alloc(N)) for k, c in ctxs.items()}
+            three = ("hybrid", "hybrid2", "gs0")
+            for s in (1, 3, 6):
+                def launch(k, s=s):
+                    c, H = ctxs[k], Hs[k]
+                    du, dr, dout = vec[k][:3]
+                    return lambda: c.check(c.lib.aggmg_smooth_dev(c.handle, H._ops[0].handle, H.mSmoothers[0].handle, du.ptr, dr.ptr,
+                                                                  2.0 / 3.0, s, dout.ptr))
+                t = timed_all({k: launch(k) for k in three}, args.reps)
+                print(json.dumps(dict(tag, what="launch", sweeps=s, ms=rounded(t), gs0_over_hybrid=round(t["gs0"] / t["hybrid"], 4),
+                                      hybrid2_over_hybrid=round(t["hybrid2"] / t["hybrid"], 4))), flush=True)
+            t = timed_all({k: (lambda k=k: Hs[k].vcycle_dev(None, vec[k][3], vec[k][4], 3, 3)) for k in three}, args.reps)
+            print(json.dumps(dict(tag, what="cycle", cycle="V(3,3)", ms=rounded(t), gs0_over_hybrid=round(t["gs0"] / t["hybrid"], 4),
+                                  hybrid2_over_hybrid=round(t["hybrid2"] / t["hybrid"], 4))), flush=True)
+            if not args.no_solve:
+                hist = np.zeros(400)
+                its = {k: ctypes.c_int(0) for k in smoothers}
+                nchk = ctypes.c_int(0)
+
+                def solve(k, kind, n):
+                    c, H = ctxs[k], Hs[k]
+                    db, dx, zero = vec[k][3:]
+
+                    def run():
+                        c.check(c.lib.aggmg_copy_segments_dev(c.handle, 1, (ctypes.c_void_p * 1)(zero.ptr.value),
+                                                              (ctypes.c_void_p * 1)(dx.ptr.value), (ctypes.c_int64 * 1)(1),
+                                                              (ctypes.c_int64 * 1)(N), (ctypes.c_int64 * 1)(N), (ctypes.c_int64 * 1)(N)))
+                        if kind == "multigrid":
+                            c.check(c.lib.aggmg_multigrid_dev(c.handle, H.handle, zero.ptr, db.ptr, 400, 1e-8, 1, n, n, 2.0 / 3.0,
+                                                              dx.ptr, hist.ctypes.data_as(pd), ctypes.byref(its[k]), ctypes.byref(nchk),
+                                                              None, None))
+                        elif kind == "pcg":
+                            c.check(c.lib.aggmg_pcg_dev(c.handle, H.handle, db.ptr, dx.ptr, 400, 1e-8, n, n, 2.0 / 3.0,
+                                                        hist.ctypes.data_as(pd), ctypes.byref(its[k])))
+                        else:
+                            c.check(c.lib.aggmg_fgmres_dev(c.handle, H.handle, db.ptr, dx.ptr, 30, 400, 1e-8, n, n, 2.0 / 3.0,
+                                                           hist.ctypes.data_as(pd), ctypes.byref(its[k])))
+                    return run
+
+                for kind, n, names in (("multigrid", 3, three), ("multigrid", 2, three), ("fgmres", 3, ("hybrid", "hybrid2")),
+                                       ("pcg", 3, ("gs0", "gs")), ("pcg", 2, ("gs0", "gs")), ("pcg", 1, ("gs0", "gs"))):
+                    t = timed_all({k: solve(k, kind, n) for k in names}, max(3, args.reps // 3), warm=1)
+                    row = dict(tag, what="solve", solver=kind, cycle=f"V({n},{n})", iterations={k: its[k].value for k in names},
+                               ms=rounded(t))
+                    if E <= 22:
+                        row["true_residual_over_b"] = {
+                            k: float(np.linalg.norm(mg.residual(Hs[k]._ops[0], vec[k][4].download(), b))) / nb for k in names}
+                    if kind == "multigrid":
+                        margin = abs(t["hybrid2"] / t["hybrid"] - 1.0)
+                        row["gs0_over_hybrid"] = round(t["gs0"] / t["hybrid"], 4)
+                        row["margin"] = round(margin, 4)
+                        if n == 3 and E == 20 and dictionary:
+                            row["condition_gs0_no_slower_than_hybrid"] = bool(t["gs0"] <= t["hybrid"] * (1.0 + margin))
+                    print(json.dumps(row), flush=True)
+            for vs in vec.values():
+                for v in vs:
+                    v.free()
+            for H in Hs.values():
+                sms, ops, Ls = list(H.mSmoothers), list(H._ops), list(H._Ls)
+                H.free()
+                for x in sms + ops + Ls:
+                    x.free()
+            del Hs
+            for c in ctxs.values():
+                c.close()
 
 
 if __name__ == "__main__":
