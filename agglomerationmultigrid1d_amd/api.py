@@ -1236,6 +1236,15 @@ class MeshHierarchy:
         c.check(c.lib.aggmg_vcycle_up_split_dev(c.handle, self.handle, _ptr(b), int(nPost), float(alpha), _ptr(x_out),
                                                 int(head_elems), int(tail_elem), int(part)))
 
+    def can_split_up(self, nPost=3):
+        """whether parts 0 - 2 of vcycle_up_split_dev exist for this hierarchy and sweep count (C ABI
+        aggmg_vcycle_up_split_ok): a fused block-tridiagonal fine level, or a multiplicative element-patch level with a
+        one-ratio transfer and 1 <= nPost <= the sweeps of one launch"""
+        ok = ctypes.c_int(0)
+        c = self.ctx
+        c.check(c.lib.aggmg_vcycle_up_split_ok(c.handle, self.handle, int(nPost), ctypes.byref(ok)))
+        return bool(ok.value)
+
     def set_restriction(self, mode):
         """_lib.RESTRICT_EXPLICIT (default: the reference's arithmetic for L'(rhs - A u)) or
         _lib.RESTRICT_PRECONDITIONED (cheaper; UnsupportedError above

@@ -928,6 +928,49 @@ static int launch_patch_gs(aggmg_ctx* ctx, const PatchDev& P, const PatchArgs& a
   return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: block size not instantiated for the multiplicative patch sweep kernel");
 }
 
+// the one-launch ascent of a multiplicative patch level (patch_gs_up_kernel): prolongation and nsweeps <= patch_gs_max_sweeps
+// reverse sweeps on the tiles sel chooses (fused_tile_subset with the sweep launch's owned size), the same tile plan
+template <int M, bool CMP>
+static int launch_patch_gs_up_t(aggmg_ctx* ctx, PatchGsUpArgs u, const SweepWeights& wts, const TileSel& sel, const uint16_t* cls) {
+  constexpr int NS = PatchSlabs<M>::NS;
+  PatchArgs& a = u.g.p;
+  const PatchTilePlan plan = patch_gs_tile_plan(M, a.nsweeps);   // host_plan.hpp
+  if (plan.owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: multiplicative patch ascent launch without a tile");
+  a.owned = plan.owned;
+  a.halo = plan.halo;
+  const TileSubset sub = fused_tile_subset(a.ne, plan.owned, sel.mode == 3 ? 0 : sel.mode, sel.head, sel.tail);
+  u.tile_split = sub.split;
+  u.tile_skip = sub.skip;
+  if (sub.ntiles == 0) return AGGMG_OK;
+  if (cls)
+    hipLaunchKernelGGL((patch_gs_up_dict_kernel<M, CMP, NS>), dim3((unsigned)sub.ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, u, wts, cls);
+  else
+    hipLaunchKernelGGL((patch_gs_up_kernel<M, CMP, NS>), dim3((unsigned)sub.ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, u, wts);
+  HIPCHK(hipGetLastError());
+  return AGGMG_OK;
+}
+
+static int launch_patch_gs_up(aggmg_ctx* ctx, const PatchDev& P, const PatchGsUpArgs& u, const SweepWeights& wts, const TileSel& sel,
+                              const uint16_t* cls) {
+  const bool cmp = P.btd->cmp;
+#define CASE(MM)                                                             \
+  case MM:                                                                   \
+    return cmp ? launch_patch_gs_up_t<MM, true>(ctx, u, wts, sel, cls) : launch_patch_gs_up_t<MM, false>(ctx, u, wts, sel, cls);
+#define CASE_C(MM) \
+  case MM:         \
+    if (cmp) return launch_patch_gs_up_t<MM, true>(ctx, u, wts, sel, cls); \
+    break;
+  switch (P.m) {
+    case 1:
+      if (!cmp) return launch_patch_gs_up_t<1, false>(ctx, u, wts, sel, cls);
+      break;
+      CASE(2) CASE(3) CASE(4) CASE(5) CASE_C(6) CASE_C(7) CASE_C(8)
+  }
+#undef CASE
+#undef CASE_C
+  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: block size not instantiated for the multiplicative patch ascent kernel");
+}
+
 // nsweeps sweeps from u_in (may be nullptr = zero) into u_out (!= u_in), in launches of up to patch_max_sweeps
 // (multiplicative: patch_gs_max_sweeps; reverse: its colours in the order 1, 0 -- post-smoothing; the others ignore it)
 static int patch_smooth(aggmg_ctx* ctx, const PatchDev& P, const double* u_in, const double* rhs, Damping alpha, int nsweeps,
@@ -2455,7 +2498,8 @@ static int generic_prolong_add(aggmg_ctx* ctx, aggmg_hier* h, int k) {
   return launch_csr<kSpmvAdd>(ctx, l.L->csr, coarse_result(h, k), nullptr, nullptr, 0.0, l.u[0]);
 }
 static int no_split_ascent(aggmg_ctx* ctx) {
-  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "split ascent needs the fused block-tridiagonal fine level");
+  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "split ascent needs the fused block-tridiagonal fine level (or a multiplicative patch level "
+                                          "with a one-ratio transfer and a single launch of post sweeps)");
 }
 
 // Block-tridiagonal levels (LevelPath::FusedBtd, BtdTransfer).  One fused launch where the level has the structured
@@ -2562,6 +2606,48 @@ static int patch_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* rhs, int
   return patch_smooth(ctx, P, l.u[0], rhs, l.damp_post(alpha), nPost, dst, k, true);
 }
 
+// The fine-level ascent of a multiplicative patch level in ONE launch per tile selection (element-partitioned runs: the
+// tiles at the two ends on one stream, the ones in between on another -- each writes only its own tiles of dst and no
+// scratch vector is shared).  Offered where patch_up would prolong with the zero-sweep fused launch -- whose bits the
+// launch repeats -- through a structured transfer of one ratio, and the post sweeps are a single launch with a tile.
+static bool patch_split_ok(const aggmg_hier* h, int nPost) {
+  if (h->lv.size() < 2 || level_path(h, 0) != LevelPath::Patch) return false;
+  const Level& l = h->lv[0];
+  const PatchDev& P = *l.S->patch;
+  if (!P.multiplicative || !l.tb || l.tb->rho <= 0 || P.ne != (int64_t)l.tb->rho * l.tb->nec) return false;
+  if (!patch_transfer_ok(l, 0, nullptr)) return false;
+  if (nPost < 1 || nPost > patch_gs_max_sweeps(P.m)) return false;
+  TileQuery q;
+  q.launch = kTilePatchGs;
+  q.te = patch_tile_elems(P.m);
+  q.halo = nPost;
+  return launch_has_tile(q);
+}
+static int patch_up_split(aggmg_ctx* ctx, aggmg_hier* h, const double* rhs, int nPost, double alpha, double* dst, const TileSel& sel) {
+  Level& l = h->lv[0];
+  const PatchDev& P = *l.S->patch;
+  const BtdDev& b = *P.btd;
+  PatchGsUpArgs u{};
+  u.g.p = PatchArgs{b.dblk, b.scol, b.qrow, b.sub, b.sup, P.zrows, P.ne, b.c_sub, b.r_sup, l.u[0], rhs, dst, nPost, 0, 0};
+  u.g.reverse = 1;   // post-smoothing: the colours in reverse order
+  const PatchDictDev* d = P.dict.get();
+  if (d) {   // the smoother's operator dictionary in place of the full arrays, as patch_smooth takes it
+    u.g.p.dblk = d->dblk;
+    u.g.p.scol = d->scol;
+    u.g.p.qrow = d->qrow;
+    u.g.p.sub = d->sub;
+    u.g.p.sup = d->sup;
+    u.g.p.zrows = d->zrows;
+  }
+  u.uc = coarse_result(h, 0);
+  u.lf = l.tb->lf;
+  u.lf1 = l.tb->lf1;
+  u.mc = l.tb->mc;
+  u.rho = l.tb->rho;
+  ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, 0);
+  return launch_patch_gs_up(ctx, P, u, l.damp_post(alpha).from(0).launch(nPost), sel, d ? d->cls.get() : nullptr);
+}
+
 // Generic levels: generic_sweeps between the generic launches.  The descent sweeps in place in l.u[0] (point Jacobi:
 // with l.u[1] as its second vector, the banded form's residual straight into l.tmp); the ascent keeps its intermediate
 // sweeps in l.u[0] and writes the last one to dst (point Jacobi: with whichever of l.u[1] / l.tmp is not dst).
@@ -2635,7 +2721,11 @@ static int vcycle_up(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, 
                                                         : "split coarse ascent: unpaired level above the coarse pair");
     const LevelPath path = level_path(h, k);
     const bool btd = path == LevelPath::FusedBtd || path == LevelPath::BtdTransfer;
-    if (!btd && (sel.mode == 1 || sel.mode == 2)) return no_split_ascent(ctx);
+    if (!btd && (sel.mode == 1 || sel.mode == 2)) {
+      // a multiplicative patch level: prolongation and sweeps of the selected tiles in one launch
+      if (k == 0 && path == LevelPath::Patch && patch_split_ok(h, nPost)) return patch_up_split(ctx, h, rhs, nPost, alpha, dst, sel);
+      return no_split_ascent(ctx);
+    }
     switch (path) {
       case LevelPath::FusedChain: CHECK(cgt_up(ctx, h, k, rhs, nPost, alpha, dst)); break;
       case LevelPath::FusedBtd:   // (refuses a selection itself where the fused launch has no tile)
@@ -3071,6 +3161,20 @@ extern "C" int aggmg_vcycle_up_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* 
   return vcycle_up(ctx, h, b, nPost, alpha, x_out);
 }
 
+// Does the fine level have the split ascent for nPost sweeps?  A fused block-tridiagonal level whose ascent is one fused
+// launch, or a multiplicative patch level with the one-launch ascent (patch_split_ok).
+static bool split_up_ok(const aggmg_hier* h, int nPost) {
+  if (h->lv.size() < 2) return false;
+  if (level_path(h, 0) == LevelPath::FusedBtd && btd_launch_ok(*h->lv[0].S, nPost, 0, nullptr)) return true;
+  return patch_split_ok(h, nPost);
+}
+extern "C" int aggmg_vcycle_up_split_ok(aggmg_ctx* ctx, const aggmg_hier* h, int nPost, int* ok) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!h || !ok) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_up_split_ok: NULL argument");
+  *ok = nPost >= 0 && split_up_ok(h, nPost) ? 1 : 0;
+  return AGGMG_OK;
+}
+
 // The ascent in three calls: part 0 the coarser levels (n-2 .. 1), part 1 the fine-level tiles that
 // hold elements [0, head_elems) and [tail_elem, ne), part 2 the remaining fine-level tiles.  Parts
 // 1 and 2 are independent of each other (tiles are), so they may run on different streams; the
@@ -3086,7 +3190,7 @@ extern "C" int aggmg_vcycle_up_split_dev(aggmg_ctx* ctx, aggmg_hier* h, const do
     all.mode = 3;
     return vcycle_up(ctx, h, b, nPost, alpha, x_out, 0, all);
   }
-  if (!(level_path(h, 0) == LevelPath::FusedBtd && btd_launch_ok(*h->lv[0].S, nPost, 0, nullptr))) return no_split_ascent(ctx);
+  if (!split_up_ok(h, nPost)) return no_split_ascent(ctx);
   if (part == 0) return h->lv.size() > 2 ? vcycle_up(ctx, h, b, nPost, alpha, x_out, 1) : AGGMG_OK;
   TileSel sel;
   sel.mode = part;  // 1 ends, 2 middle

@@ -381,10 +381,27 @@ extern "C" int aggmg_dist_create(aggmg_ctx* ctx, aggmg_hier* local, aggmg_hier* 
   if (local->coarse_mode != AGGMG_COARSE_EXTERNAL)
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_dist_create: the local hierarchy must be created with AGGMG_COARSE_EXTERNAL");
   if (coarse_global->lv.size() != 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_dist_create: the coarse hierarchy must have one level");
-  // an element-patch Schwarz sweep reaches two elements (and wider patches more): the halo plans know reaches of one
-  for (const Level& l : local->lv)
-    if (l.S && l.S->patch_width)
-      return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_dist_create: element-patch Schwarz levels are not partitioned (a sweep reaches past the ghost layer)");
+  // Element-patch levels: the fused sweeps on patches of two elements only -- their reach per sweep is what the halo plans
+  // know (host_plan.hpp, dist_sweep_reach); the two colours of the multiplicative sweeps are the parity of the LOCAL
+  // element index, so such a level's local range starts on an even element.
+  for (int k = 0; k < nlevels; ++k) {
+    const Level& l = local->lv[k];
+    if (!(l.S && l.S->patch_width)) continue;
+    const std::string lev = " (level " + std::to_string(k + 1) + ")";
+    if (!l.S->patch)
+      return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_dist_create: an element-patch smoother on the generic route is not partitioned" + lev);
+    if (l.S->patch_width != 2)
+      return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_dist_create: element patches wider than two elements are not partitioned" + lev);
+    // (layers that cannot carry a single sweep of the level's smoother admit no smoothed cycle: refused here, once,
+    // rather than by every aggmg_dist_vcycle_dev)
+    const int reach1 = dist_sweep_reach(l.S->patch->multiplicative ? kDistPatchGs : kDistPatchSchwarz, 1, false);
+    if (W[k] < reach1)
+      return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_dist_create: ghost layers too thin for one patch sweep: W = " + std::to_string(W[k]) +
+                                              ", a sweep reaches " + std::to_string(reach1) + " elements" + lev);
+    if (l.S->patch->multiplicative && (loc_lo[k] & 1))
+      return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_dist_create: a multiplicative element-patch level must start on an even element: "
+                                              "its local range starts at the odd element " + std::to_string(loc_lo[k]) + lev);
+  }
   HIPCHK(hipSetDevice(ctx->device));
   std::unique_ptr<aggmg_dist> d(new aggmg_dist());
   d->H = local;
@@ -649,6 +666,37 @@ extern "C" int aggmg_dist_info(aggmg_ctx* ctx, const aggmg_dist* d, int64_t* exc
   return AGGMG_OK;
 }
 
+// Hierarchies with an element-patch level: are the ghost layers wide enough for these sweep counts?  The margin
+// recurrences of distributed.halo_widths (host_plan.hpp, dist_halo_ok) over d->W, the ratios read off the owned ranges and
+// every level's reach.  Hierarchies without a patch level are not asked: their callers size the layers (no call changes).
+static int patch_halo_check(aggmg_ctx* ctx, const aggmg_dist* d, int nPre, int nPost) {
+  const aggmg_hier* H = d->H;
+  bool any = false;
+  for (int k = 0; k < d->nl - 1; ++k) any = any || (H->lv[k].S && H->lv[k].S->patch_width);
+  if (!any) return AGGMG_OK;
+  std::vector<int> kind(d->nl, kDistBlockJac), ratio(d->nl, 1);
+  std::vector<int64_t> W(d->W.begin(), d->W.end());
+  for (int k = 0; k < d->nl - 1; ++k) {
+    const aggmg_smoother* S = H->lv[k].S;
+    if (S && S->patch_width) {
+      kind[k] = S->patch && S->patch->multiplicative ? kDistPatchGs : kDistPatchSchwarz;
+    } else if (S && S->gs) {
+      kind[k] = kDistBlockGs;
+    }
+    const int64_t fine = d->own_hi[k] - d->own_lo[k], coarse = d->own_hi[k + 1] - d->own_lo[k + 1];
+    if (coarse <= 0 || fine % coarse != 0) {
+      if (S && S->patch_width)
+        return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_dist_vcycle_dev: element-patch levels need one agglomeration ratio per level");
+      continue;
+    }
+    ratio[k] = (int)(fine / coarse);
+  }
+  if (!dist_halo_ok(d->nl, W.data(), ratio.data(), kind.data(), nPre, nPost))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_dist_vcycle_dev: ghost layers too thin for " + std::to_string(nPre) + " + " +
+                                                std::to_string(nPost) + " patch sweeps");
+  return AGGMG_OK;
+}
+
 // one cycle, issued launch by launch on ctx->stream (and the side stream for the overlapped exchange,
 // which is joined back before returning: the cycle is self-contained, hence capturable)
 static int dist_vcycle_eager(aggmg_ctx* ctx, aggmg_dist* d, double* x0, const double* b, double* x_out, int nPre,
@@ -763,6 +811,7 @@ extern "C" int aggmg_dist_vcycle_dev(aggmg_ctx* ctx, aggmg_dist* d, double* x0, 
   // keyed by alpha alone, and the partitioned cycle has no bitwise test against a weighted single-device cycle
   if (any_schedule(d->H))
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_dist_vcycle_dev: the rank's hierarchy has a sweep-weight schedule");
+  CHECK(patch_halo_check(ctx, d, nPre, nPost));   // (hierarchies with an element-patch level only)
   // hipGraph replay: a cycle with the same arguments was issued eagerly once (lazy allocations done)
   // and captured on its second call; host callbacks, the host coarsest solver and the event profiler
   // cannot be captured

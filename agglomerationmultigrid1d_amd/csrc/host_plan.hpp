@@ -450,4 +450,42 @@ inline int dist_chunk_route(int q, int plan_m, int64_t plan_blocks, int m, int64
   return 1;
 }
 
+// ---- element-partitioned cycle: are the ghost layers wide enough? -------------------------------------------------
+// The margin recurrences of distributed.halo_widths over given widths W[0 .. nl) (elements per side; nl - 1 smoothed
+// levels, ratio[k] elements of level k per element of level k + 1).  Elements per side by which S sweeps shrink the
+// valid part of a local domain: block Jacobi S; red-black block Gauss-Seidel and the hybrid element patches 2 S; each
+// of the three one less from a zero iterate, whose first residual reads no neighbour; the multiplicative patches
+// 2 S + 1 (patch_gs_halo; no saving claimed from a zero start).  No sweep, no reach.
+enum DistSmoother { kDistBlockJac = 0, kDistBlockGs = 1, kDistPatchSchwarz = 2, kDistPatchGs = 3 };
+inline int dist_sweep_reach(int kind, int sweeps, bool zero_start) {
+  if (sweeps <= 0) return 0;
+  switch (kind) {
+    case kDistBlockJac: return zero_start ? sweeps - 1 : sweeps;
+    case kDistBlockGs:
+    case kDistPatchSchwarz: return zero_start ? 2 * sweeps - 1 : 2 * sweeps;
+    default: return patch_gs_halo(sweeps);
+  }
+}
+// Descending: the margin of the pre-smoothed iterate (elements beyond the owned boundary that hold the single-domain
+// values) must leave one valid neighbour for the residual; the restricted right-hand side keeps (margin - 1) / ratio.
+// Ascending: the coarsest solution is exact on all its ghosts; a prolonged level is valid where both the coarse values
+// and its own pre-smoothed iterate are, less the reach of the post sweeps -- which must not eat into the owned elements.
+inline bool dist_halo_ok(int nl, const int64_t* W, const int* ratio, const int* kind, int nPre, int nPost) {
+  if (nl < 2 || nl > 64) return false;
+  int64_t pu[64];
+  int64_t rm = W[0];   // the fine right-hand side is valid on the whole local domain
+  for (int k = 0; k < nl - 1; ++k) {
+    if (ratio[k] < 1) return false;
+    pu[k] = std::min(rm, W[k]) - dist_sweep_reach(kind[k], nPre, k > 0);   // (levels below the finest start from zero)
+    if (pu[k] < 1) return false;
+    rm = (pu[k] - 1) / ratio[k];
+  }
+  int64_t v = W[nl - 1];
+  for (int k = nl - 2; k >= 0; --k) {
+    v = std::min(pu[k], ratio[k] * v) - dist_sweep_reach(kind[k], nPost, false);
+    if (v < 0) return false;
+  }
+  return true;
+}
+
 }  // namespace aggmg

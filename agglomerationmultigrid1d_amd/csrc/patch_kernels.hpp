@@ -467,6 +467,205 @@ __global__ __launch_bounds__(kThreads) void patch_gs_dict_kernel(PatchGsArgs g, 
   patch_gs_body<M, CMP, NS, true>(g, wts, cls);
 }
 
+// ---- one-launch ascent of a multiplicative patch level (split ascent of the element-partitioned cycle) ----
+// patch_gs_body with two additions.  The prolongation in the load phase: a row starts from u_in[row] + sum_c L[row][c]
+// uc[J mc + c], J = e / rho (uniform agglomerates), with the arithmetic and the summation order of the zero-sweep fused
+// launch that patch_up runs in front of the sweeps -- halo elements included, whose prolonged values the owned ones read --
+// so the result is that two-launch sequence's bit for bit.  And the tile of a workgroup is selectable as fused_tile()'s
+// is: workgroup w runs tile w + (w >= tile_split ? tile_skip : 0) -- the tiles at the two ends of the level, or the ones
+// in between (fused_tile_subset) -- and writes only its own tile's owned rows of u_out; no scratch vector is shared
+// between two launches.  The smoother's dictionary is read by class as patch_gs_dict_kernel reads it; the transfer rows
+// come from the level's full lf / lf1 arrays.  A body of its own text: patch_gs_body's kernels keep their code.
+struct PatchGsUpArgs {
+  PatchGsArgs g;      // g.p.u_in: the pre-smoothed iterate (never null); reverse = 1
+  const double* uc;   // the coarse level's result
+  const double* lf;   // [N][mc] rows of L
+  const double* lf1;  // [N] their second entries when mc == 2 and every first entry is exactly 1.0, else null
+  int mc, rho;
+  int tile_split;
+  int64_t tile_skip;
+};
+__device__ __forceinline__ int64_t patch_up_tile(const PatchGsUpArgs& a) {
+  return (int64_t)blockIdx.x + ((int)blockIdx.x >= a.tile_split ? a.tile_skip : 0);
+}
+// the second product rounded, the first fused into the sum: what btd_prolong2 is compiled to in the fused kernel
+// (kernels.hpp says the same of its dictionary variant), said explicitly
+__device__ __forceinline__ double patch_up_prolong2(double2 l2, double2 u2) { return __fma_rn(l2.x, u2.x, l2.y * u2.y); }
+
+template <int M, bool CMP, int NS, bool DICT>
+__device__ __forceinline__ void patch_gs_up_body(const PatchGsUpArgs& ga, const SweepWeights& wts, const uint16_t* __restrict__ cls) {
+  const PatchGsArgs& g = ga.g;
+  const PatchArgs& a = g.p;
+  constexpr int EPS = kThreads / M;   // elements per slab
+  constexpr int TE = EPS * NS;        // elements per tile (owned + halos)
+  constexpr int PL = (TE + 2) * M;    // a padded vector of the tile: index x * M + j, x in [-1, TE]
+  extern __shared__ double lds[];
+  double* cur = lds + M;
+  double* res = cur + PL;
+
+  const int tid = threadIdx.x;
+  const bool active = tid < EPS * M;
+  const int le = tid / M;
+  const int i = tid - le * M;
+  const int64_t ne = a.ne;
+  const int64_t e0 = patch_up_tile(ga) * a.owned - a.halo;   // element at x = 0
+
+  if (tid < M) {
+    cur[-M + tid] = 0.0;
+    cur[TE * M + tid] = 0.0;
+    res[-M + tid] = 0.0;
+    res[TE * M + tid] = 0.0;
+  }
+
+  double dk[NS][M], lo[NS][CMP ? 1 : M], hi[NS][M], z[NS][4 * M], bb[NS], uu[NS];
+  bool valid[NS], with_prev[NS], with_next[NS];   // the patches {e - 1, e} and {e, e + 1} exist
+  int par[NS];                                    // e mod 2
+  int c[NS];
+
+  // ---- load phase: everything the tile needs from HBM (DICT: its operator words from the dictionary), once ----------------
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int64_t e = e0 + s * EPS + le;
+    valid[s] = active && e >= 0 && e < ne;
+    c[s] = (DICT && valid[s]) ? (int)cls[e] : 0;
+  }
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int x = s * EPS + le;
+    const int64_t e = e0 + x;
+    par[s] = (int)(e & 1);
+    with_prev[s] = valid[s] && e >= 1;
+    with_next[s] = valid[s] && e <= ne - 2;
+    bb[s] = 0.0;
+    uu[s] = 0.0;
+#pragma unroll
+    for (int j = 0; j < M; ++j) dk[s][j] = hi[s][j] = 0.0;
+#pragma unroll
+    for (int j = 0; j < (CMP ? 1 : M); ++j) lo[s][j] = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4 * M; ++j) z[s][j] = 0.0;
+    if (valid[s]) {
+      const int64_t row = e * M + i;
+      if constexpr (DICT) {
+        const int crow = c[s] * M + i;   // the row in its class's record (c < kDictMaxClasses: 32-bit offsets)
+        const double* zr = a.zrows + crow * (4 * M);
+#pragma unroll
+        for (int j = 0; j < 4 * M; ++j) z[s][j] = zr[j];
+#pragma unroll
+        for (int j = 0; j < M; ++j) dk[s][j] = a.dblk[crow * M + j];
+        if constexpr (CMP) {
+          lo[s][0] = a.scol[crow];
+          if (i == a.r_sup) {
+#pragma unroll
+            for (int j = 0; j < M; ++j) hi[s][j] = a.qrow[c[s] * M + j];
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < M; ++j) lo[s][j] = a.sub[crow * M + j];
+#pragma unroll
+          for (int j = 0; j < M; ++j) hi[s][j] = a.sup[crow * M + j];
+        }
+      } else {
+        const double* zr = a.zrows + row * (4 * M);
+#pragma unroll
+        for (int j = 0; j < 4 * M; ++j) z[s][j] = AGGMG_LD(zr[j]);
+#pragma unroll
+        for (int j = 0; j < M; ++j) dk[s][j] = AGGMG_LD(a.dblk[row * M + j]);
+        if constexpr (CMP) {
+          lo[s][0] = AGGMG_LD(a.scol[row]);
+          if (i == a.r_sup) {
+#pragma unroll
+            for (int j = 0; j < M; ++j) hi[s][j] = a.qrow[e * M + j];
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < M; ++j) lo[s][j] = AGGMG_LD(a.sub[row * M + j]);
+#pragma unroll
+          for (int j = 0; j < M; ++j) hi[s][j] = AGGMG_LD(a.sup[row * M + j]);
+        }
+      }
+      bb[s] = a.b[row];
+      uu[s] = a.u_in[row];
+      {  // u += L uc : J = e / rho, ascending mode order -- the zero-sweep fused ascent's expressions (kernels.hpp)
+        const int64_t J = e / ga.rho;
+        double add = 0.0;
+        if (ga.mc == 2) {  // one 16-byte load each for the L row and the coarse pair
+          typedef double v2d __attribute__((ext_vector_type(2)));
+          double2 l2;
+          if (ga.lf1) {
+            l2.x = 1.0;
+            l2.y = AGGMG_LD(ga.lf1[row]);
+          } else {
+            const v2d lv2 = AGGMG_LD(*reinterpret_cast<const v2d*>(ga.lf + row * 2));
+            l2.x = lv2.x;
+            l2.y = lv2.y;
+          }
+          const double2 u2 = *reinterpret_cast<const double2*>(ga.uc + J * 2);
+          add = patch_up_prolong2(l2, u2);
+        } else {
+          for (int c2 = 0; c2 < ga.mc; ++c2) add += ga.lf[row * ga.mc + c2] * ga.uc[J * ga.mc + c2];
+        }
+        uu[s] += add;
+      }
+    }
+    if (active) cur[x * M + i] = uu[s];
+  }
+  __syncthreads();
+
+  for (int sw = 0; sw < a.nsweeps; ++sw) {
+    const double w = wts.w[sw];   // this sweep's factor, for both of its halves: wave-uniform, a scalar load
+    for (int h = 0; h < 2; ++h) {
+      const int colour = h ^ g.reverse;
+      // residual rows of the tile (zero outside the level)
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        if (!active) continue;
+        const int x = s * EPS + le;
+        const double *um = cur + (x - 1) * M, *ux = cur + x * M, *up = cur + (x + 1) * M;
+        double t;
+        if constexpr (CMP)
+          t = btd_apply_cmp<M, false>(lo[s][0], dk[s], hi[s], um, ux, up, a.c_sub, a.r_sup, i);
+        else
+          t = btd_apply_dense<M>(lo[s], dk[s], hi[s], um, ux, up);
+        res[x * M + i] = valid[s] ? bb[s] - t : 0.0;
+      }
+      __syncthreads();
+      // the one patch of this colour covering the row: the element is its first one (slot 1) or its second (slot 0)
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        if (!active) continue;
+        const int x = s * EPS + le;
+        const bool first = par[s] == colour;
+        const double* r = res + (first ? x : x - 1) * M;
+        double y = 0.0;
+#pragma unroll
+        for (int j = 0; j < 2 * M; ++j) y += (first ? z[s][2 * M + j] : z[s][j]) * r[j];
+        if (first ? with_next[s] : with_prev[s]) {
+          uu[s] = uu[s] + w * y;
+          cur[x * M + i] = uu[s];
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int x = s * EPS + le;
+    if (valid[s] && x >= a.halo && x < a.halo + a.owned) AGGMG_ST(a.u_out[(e0 + x) * M + i], uu[s]);
+  }
+}
+
+template <int M, bool CMP, int NS>
+__global__ __launch_bounds__(kThreads) void patch_gs_up_kernel(PatchGsUpArgs g, SweepWeights wts) {
+  patch_gs_up_body<M, CMP, NS, false>(g, wts, nullptr);
+}
+template <int M, bool CMP, int NS>
+__global__ __launch_bounds__(kThreads) void patch_gs_up_dict_kernel(PatchGsUpArgs g, SweepWeights wts,
+                                                                    const uint16_t* __restrict__ cls) {
+  patch_gs_up_body<M, CMP, NS, true>(g, wts, cls);
+}
+
 // ---- set-up ---------------------------------------------------------------------------------------------------------------
 // the dense patch blocks A[P_p, P_p], [ne - 1][2m][2m] row-major, from the element blocks of A: one thread per entry
 static __global__ __launch_bounds__(kThreads) void patch_assemble_kernel(int64_t total, int m, int cmp, int c_sub, int r_sup,

@@ -23,6 +23,8 @@ elements on 8 ranks).  `halo_widths` derives the widths from (ratios, nPre, nPos
 how far validity shrinks: a sweep costs one element per side (two for the red-black Gauss-Seidel
 extension), the residual one more, a transfer divides / multiplies by the ratio.  Owned values are
 bitwise those of the single-GPU run (same per-row arithmetic, tiles only differ in where they start).
+Element-patch levels (ElementPatchSchwarz / ElementPatchGaussSeidel) take part with the reach of
+their own sweeps: `halo_widths(..., smoothers=[...])`, `RankLayout(..., smoothers=)`, `build_local_uniform(..., smoother=)`.
 
 Two drivers of the same schedule:
   * NativeDistributedVCycle -- the schedule inside libaggmg_hip.so (csrc/dist.hip, C ABI aggmg_dist_*):
@@ -49,18 +51,55 @@ import numpy as np
 # ------------------------------------------------------------------------------------------
 # layout
 # ------------------------------------------------------------------------------------------
-def halo_widths(ratios, nPre, nPost, gs=False):
+SMOOTHER_KINDS = ("blockJac", "blockGS", "patchSchwarz", "patchGS")
+
+
+def sweep_reach(kind, S, zero_start=False):
+    """Elements per side by which S sweeps of a smoother shrink the valid part of a local domain.  blockJac: one per
+    sweep; blockGS (two half-sweeps) and patchSchwarz (the residual reads u[e +- 1], the patch solves r[e +- 1]): two per
+    sweep; each of the three saves one from a zero iterate, whose first residual reads no neighbour.  patchGS: 2 S + 1
+    (the planner's patch_gs_halo; no saving claimed from a zero start).  No sweep, no reach."""
+    if S <= 0:
+        return 0
+    if kind == "blockJac":
+        return S - 1 if zero_start else S
+    if kind in ("blockGS", "patchSchwarz"):
+        return 2 * S - 1 if zero_start else 2 * S
+    if kind == "patchGS":
+        return 2 * S + 1
+    raise ValueError(f"smoother kind {kind!r}: one of {SMOOTHER_KINDS}")
+
+
+def smoother_kinds(smoother, nsmoothed):
+    """build_local_uniform's / build_device_hierarchy's smoother spelling as the per-level list halo_widths takes
+    ("...0": the patch smoother on level 0, block-Jacobi below)"""
+    if smoother in ("patchSchwarz0", "patchGS0"):
+        return [smoother[:-1]] + ["blockJac"] * (nsmoothed - 1)
+    if smoother not in SMOOTHER_KINDS:
+        raise ValueError(f"smoother {smoother!r}")
+    return [smoother] * nsmoothed
+
+
+def halo_widths(ratios, nPre, nPost, gs=False, smoothers=None):
     """Ghost elements per side for levels 0..len(ratios) (last = coarsest, held replicated but
     copied locally with W ghosts), nested so that a local level is exactly the children of the
     local next-coarser level: W_k = ratios[k] * W_{k+1}.  Smallest widths for which the owned part
     of the V-cycle result is exact with a single exchange of x0 and the coarsest gather.
     gs: red-black block Gauss-Seidel sweeps (the labelled extension) -- a sweep is two half-sweeps
-    and moves information by two elements (one when it starts from a zero iterate)."""
+    and moves information by two elements (one when it starts from a zero iterate).
+    smoothers: the smoother of every smoothed level (SMOOTHER_KINDS; len(ratios) names) -- the margin a
+    level's sweeps consume is then sweep_reach of its own smoother; None: block-Jacobi (gs: blockGS) on
+    every level."""
     nl = len(ratios) + 1
-    per = 2 if gs else 1
-    # (gs: the two colours are the parity of the LOCAL element index, so local ranges must start on even
+    if smoothers is None:
+        smoothers = ["blockGS" if gs else "blockJac"] * (nl - 1)
+    smoothers = list(smoothers)
+    if len(smoothers) != nl - 1:
+        raise ValueError("halo_widths: one smoother name per smoothed level")
+    # (two-colour smoothers: the colours are the parity of the LOCAL element index, so local ranges must start on even
     # elements: even widths on every level)
-    for w in range(0, 4096, 2 if gs else 1):
+    even = any(s in ("blockGS", "patchGS") for s in smoothers)
+    for w in range(0, 4096, 2 if even else 1):
         W = [0] * nl
         W[nl - 1] = w
         for k in range(nl - 2, -1, -1):
@@ -72,7 +111,7 @@ def halo_widths(ratios, nPre, nPost, gs=False):
         for k in range(nl - 1):
             # levels below the finest start from u = 0 (src/solvers.jl:29-31): their first sweep
             # reads no neighbour and costs no margin
-            Pu[k] = min(Rm, W[k]) - (per * nPre if k == 0 else max(per * nPre - 1, 0))
+            Pu[k] = min(Rm, W[k]) - sweep_reach(smoothers[k], nPre, zero_start=k > 0)
             if Pu[k] < 1:               # the residual needs one more valid neighbour
                 ok = False
                 break
@@ -82,7 +121,7 @@ def halo_widths(ratios, nPre, nPost, gs=False):
         # ascending: margin of the post-smoothed u; coarsest solution is exact on all W ghosts
         V = W[nl - 1]
         for k in range(nl - 2, -1, -1):
-            V = min(Pu[k], ratios[k] * V) - per * nPost
+            V = min(Pu[k], ratios[k] * V) - sweep_reach(smoothers[k], nPost)
             if V < 0:
                 ok = False
                 break
@@ -96,14 +135,15 @@ class RankLayout:
     own[k] = (lo, hi) owned elements, loc[k] = (lo, hi) local domain (owned + ghosts, clipped to
     the global domain), m[k] = DoFs per element, ne[k] = global element count."""
 
-    def __init__(self, n_fine, ratios, block_sizes, world, rank, nPre=3, nPost=3, gs=False):
+    def __init__(self, n_fine, ratios, block_sizes, world, rank, nPre=3, nPost=3, gs=False, smoothers=None):
         tot = int(np.prod(ratios)) if len(ratios) else 1
         if n_fine % (tot * world):
             raise ValueError("fine element count must be divisible by world_size * prod(ratios)")
         self.world, self.rank = world, rank
         self.ratios = tuple(ratios)
         self.m = list(block_sizes)
-        self.W = halo_widths(ratios, nPre, nPost, gs)
+        self.smoothers = None if smoothers is None else list(smoothers)
+        self.W = halo_widths(ratios, nPre, nPost, gs, smoothers)
         self.gs = gs
         self.nPre, self.nPost = nPre, nPost
         self.ne, self.own, self.loc = [], [], []
@@ -121,6 +161,8 @@ class RankLayout:
             self.loc.append((max(0, lo - self.W[k]), min(ne, hi + self.W[k])))
             if gs and k < len(ratios) and self.loc[-1][0] % 2:
                 raise ValueError("block Gauss-Seidel: a rank's local element range must start on an even element")
+            if smoothers is not None and k < len(ratios) and smoothers[k] == "patchGS" and self.loc[-1][0] % 2:
+                raise ValueError("patchGS: a rank's local element range must start on an even element")
 
     def ghosts(self, k):
         return self.own[k][0] - self.loc[k][0], self.loc[k][1] - self.own[k][1]
@@ -772,7 +814,9 @@ class NativeDistributedVCycle:
     def vcycle(self, x0, b, x_out, nPre=3, nPost=3, alpha=2.0 / 3.0, x0_ghosts_valid=False, overlap_next=False,
                graph=False):
         from . import _lib
-        if nPre > self.L.nPre or nPost > self.L.nPost:
+        # (layouts sized for a smoother list -- element-patch levels -- are checked by the library, width by width:
+        # UnsupportedError "ghost layers too thin")
+        if (nPre > self.L.nPre or nPost > self.L.nPost) and getattr(self.L, "smoothers", None) is None:
             raise ValueError("halo widths were sized for fewer sweeps")
         flags = ((_lib.DIST_X0_GHOSTS_VALID if x0_ghosts_valid else 0) | (_lib.DIST_OVERLAP_NEXT if overlap_next else 0) |
                  (_lib.DIST_GRAPH if graph else 0))
@@ -954,7 +998,9 @@ class HipEngine:
     def can_split_up(self, nPost):
         # opt-in: on one GPU with loop-back collectives the second stream's event hand-offs cost
         # ~25 us per cycle, about what one small RCCL all-gather is expected to take
-        return bool(self.H.structured_levels()[0]) and os.environ.get("AGGMG_DIST_OVERLAP", "0") == "1"
+        # (the library's own predicate: a fused block-tridiagonal fine level, or a multiplicative patch level with
+        # the one-launch ascent for this sweep count -- C ABI aggmg_vcycle_up_split_ok)
+        return os.environ.get("AGGMG_DIST_OVERLAP", "0") == "1" and self.H.can_split_up(nPost)
 
     def up_split(self, b, x_out, nPost, alpha, head, tail, part):
         # the library launches on whatever stream is current in torch (side_stream() switches both)
@@ -1138,12 +1184,32 @@ def _replicated_coarse_hierarchy(Ac, ctx, world):
 def build_local_uniform(n, p, pAgg, ratios, layout, ctx, comm, smoother="blockJac"):
     """Local operators of this rank for the uniform model problem, uploaded through the CSC
     boundary, plus the global coarsest operator assembled from every rank's owned block rows.
+    smoother: "blockJac", "blockGS", or the element-patch smoothers in uniform.build_device_hierarchy's spellings --
+    "patchSchwarz" / "patchGS" on every smoothed level, "patchSchwarz0" / "patchGS0" on level 0 with block-Jacobi
+    below -- built on the LOCAL operators (a patch inverse at a local, non-global end differs from the global one only
+    in rows of the outermost ghost element, inside the consumed margin).  The layout must have been sized for the
+    smoother list (RankLayout(..., smoothers=smoother_kinds(smoother, len(ratios)))): ValueError otherwise.
     -> (HipEngine, U_local)"""
     import torch
     from . import _lib
-    from .api import BlockGaussSeidel, BlockJacobi, DeviceOperator, MeshHierarchy
+    from .api import (BlockGaussSeidel, BlockJacobi, DeviceOperator, ElementPatchGaussSeidel, ElementPatchSchwarz,
+                      MeshHierarchy)
     from .uniform import UniformDgAggHierarchy, block_tridiag_to_csc, _csc
-    Smoother = {"blockJac": BlockJacobi, "blockGS": BlockGaussSeidel}[smoother]
+    kinds = smoother_kinds(smoother, len(layout.ratios))
+    if smoother not in ("blockJac", "blockGS"):
+        need = halo_widths(layout.ratios, layout.nPre, layout.nPost, smoothers=kinds)
+        if any(w < v for w, v in zip(layout.W, need)):
+            raise ValueError(f"the layout's ghost layers {layout.W} were not sized for {smoother!r} sweeps (needs {need})")
+        if any(kd == "patchGS" and layout.loc[k][0] % 2 for k, kd in enumerate(kinds)):
+            raise ValueError("patchGS: a rank's local element range must start on an even element")
+
+    def make(kind, op, inds):
+        if kind == "patchSchwarz":
+            return ElementPatchSchwarz(op, inds.shape[0], inds.shape[1], ctx=ctx)
+        if kind == "patchGS":
+            return ElementPatchGaussSeidel(op, inds.shape[0], inds.shape[1], ctx=ctx)
+        return {"blockJac": BlockJacobi, "blockGS": BlockGaussSeidel}[kind](op, inds, ctx)
+
     lo, hi = layout.loc[0]
     U = UniformDgAggHierarchy(n, p=p, pAgg=pAgg, ratios=ratios, elem_range=(lo, hi))
     nl = U.nlevels
@@ -1152,7 +1218,7 @@ def build_local_uniform(n, p, pAgg, ratios, layout, ctx, comm, smoother="blockJa
         op = DeviceOperator(U.stiffness_csc(k), _lib.OP_STIFFNESS, ctx)
         ops.append(op)
         if k < nl - 1:
-            sms.append(Smoother(op, U.descriptor(k).mBlockInds, ctx))
+            sms.append(make(kinds[k], op, U.descriptor(k).mBlockInds))
     Ls = [DeviceOperator(U.interpolation_csc(k), _lib.OP_TRANSFER, ctx) for k in range(nl - 1)]
     H = MeshHierarchy([U.descriptor(k) for k in range(nl)], ops, sms, Ls, ctx=ctx, keep_host=False,
                       coarse_mode=_lib.COARSE_EXTERNAL)

@@ -242,7 +242,8 @@ int aggmg_blockdiag_setup(aggmg_ctx* ctx, int64_t m, int64_t nb, const double* b
  * The smoothed V-cycle is NOT a symmetric preconditioner (the division by the cover counts does not commute with
  * the patch solves): aggmg_pcg_dev is not valid on a hierarchy holding such a level, aggmg_fgmres_dev is.  (The
  * multiplicative sweeps over the same patches, aggmg_patch_gs_setup, give a symmetric cycle.)
- * aggmg_dist_create refuses such a hierarchy (AGGMG_ERR_UNSUPPORTED): a sweep reaches two elements. */
+ * aggmg_dist_create takes the fused form (ghost widths sized for a reach of two elements per sweep) and refuses the
+ * generic route (AGGMG_ERR_UNSUPPORTED). */
 int aggmg_patch_schwarz_setup(aggmg_ctx* ctx, aggmg_op* A, int64_t m, int64_t ne, int width, int hybrid,
                               aggmg_smoother** out);
 /* width (0: sm is not an element-patch Schwarz smoother), hybrid (1 / 0) and whether sm runs the fused form */
@@ -473,10 +474,16 @@ int aggmg_vcycle_up_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPos
  * part 1 = the fine-level tiles holding elements [0, head_elems) and [tail_elem, ne), part 2 = the
  * remaining fine-level tiles.  Parts 1 and 2 do not depend on each other (they may be issued on
  * different streams, aggmg_set_stream); together they are bitwise aggmg_vcycle_up_dev.
- * AGGMG_ERR_UNSUPPORTED unless the fine level runs the fused block-tridiagonal kernel.  part 3: the finest level alone,
+ * Offered where the fine level runs the fused block-tridiagonal kernel, and where it is a multiplicative element-patch
+ * level (aggmg_patch_gs_setup) with a structured transfer of one ratio and 1 <= nPost <= the sweeps of one launch
+ * (aggmg_patch_gs_tile_plan's max_sweeps): parts 1 and 2 are then one launch each that prolongs and sweeps its tiles.
+ * AGGMG_ERR_UNSUPPORTED, with nothing launched, everywhere else -- hybrid patch levels, agglomerates of different sizes,
+ * chunked sweep counts, nPost == 0 (aggmg_vcycle_up_split_ok answers beforehand).  part 3: the finest level alone,
  * every tile, whatever kernel runs it (after the coarser levels went through part 0 or aggmg_vcycle_up_coarse_dev). */
 int aggmg_vcycle_up_split_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, double alpha,
                               double* x_out, int64_t head_elems, int64_t tail_elem, int part);
+/* *ok = 1 where parts 0 - 2 of aggmg_vcycle_up_split_dev exist for this hierarchy and nPost, else 0 */
+int aggmg_vcycle_up_split_ok(aggmg_ctx* ctx, const aggmg_hier* h, int nPost, int* ok);
 /* The ascent below the finest level in two parts around the exchange of the coarsest solution's ghost blocks
  * (element-partitioned runs; src/solvers.jl:41-47 for the levels between the coarsest and the finest): part 2 runs the
  * tiles of the first launch that read none of the first ghosts_lo / last ghosts_hi elements of the coarsest level -- they
@@ -600,7 +607,15 @@ int aggmg_copy_segments_dev(aggmg_ctx* ctx, int nseg, const double* const* src, 
  * side + replicated solve).  Layout arrays have nlevels entries (level 0 finest): owned element range
  * [own_lo, own_hi), local range [loc_lo, loc_hi) (owned + ghosts, clipped to the domain), global
  * element counts ne, DoFs per element m, ghost widths W.  Vectors are LOCAL (loc range) device vectors.
- * Owned results are bitwise those of the single-GPU cycle (tests/test_distributed_gpu.py). */
+ * Owned results are bitwise those of the single-GPU cycle (tests/test_distributed_gpu.py).
+ *   Element-patch levels (aggmg_patch_schwarz_setup's fused form, aggmg_patch_gs_setup) are accepted: their sweeps
+ * reach 2 S elements per side (multiplicative: 2 S + 1), which the caller's ghost widths must cover -- aggmg_dist_vcycle_dev
+ * checks W against its sweep counts before the first launch on a hierarchy that has such a level and returns
+ * AGGMG_ERR_UNSUPPORTED ("ghost layers too thin") otherwise.  aggmg_dist_create refuses, with AGGMG_ERR_UNSUPPORTED and
+ * the reason in the message: a patch smoother on the generic route, patches wider than two elements, a patch level
+ * whose W cannot carry one sweep of its smoother (W < 2, multiplicative: W < 3 -- no smoothed cycle would ever pass the
+ * check above), and a multiplicative patch level whose loc_lo is odd (its colours are the parity of the LOCAL element
+ * index). */
 typedef struct aggmg_dist aggmg_dist;
 int aggmg_dist_create(aggmg_ctx* ctx, aggmg_hier* local, aggmg_hier* coarse_global, int world, int rank, int nlevels,
                       const int64_t* own_lo, const int64_t* own_hi, const int64_t* loc_lo, const int64_t* loc_hi,
