@@ -10,6 +10,7 @@
 #include "multi_solve_kernels.hpp"
 #include "pair_kernels.hpp"
 #include "patch_kernels.hpp"
+#include "elem_kernels.hpp"
 #include "krylov_kernels.hpp"
 #include "host_gmres.hpp"
 
@@ -168,6 +169,9 @@ extern "C" int aggmg_set_option(aggmg_ctx* ctx, int option, int value) {
       return AGGMG_OK;
     case AGGMG_OPT_OPERATOR_DICTIONARY:
       ctx->op_dict = value != 0;
+      return AGGMG_OK;
+    case AGGMG_OPT_ELEMENT_THREADS:
+      ctx->elem_threads = value != 0;
       return AGGMG_OK;
   }
   return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_set_option: unknown option");
@@ -575,7 +579,17 @@ static int launch_btd_t(aggmg_ctx* ctx, FusedLaunch a, int halo, const TileSel& 
   if (a.gs) halo += a.nsweeps;  // two half-sweeps per sweep, one element of halo each
   if (vr && (sel.mode == 1 || sel.mode == 2))
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, "tile selection on a level with agglomerates of different sizes");
-  const FusedTilePlan plan = fused_tile_plan(T::TE, halo, align, vr, a.agg_shift);   // host_plan.hpp
+  const bool chk = a.chk_part != nullptr;   // checkpoint variant (multigrid's per-cycle residual test inside the launch)
+  // The element-thread kernel (elem_kernels.hpp, AGGMG_OPT_ELEMENT_THREADS) in place of the row-thread dictionary variant,
+  // the one place that chooses: blocks of 4 rows, a dictionary launch (fused_dictionary's conditions, checked again
+  // below) of block-Jacobi sweeps -- at least one -- over all tiles of the level, whose residual is restricted and not stored.
+  // Its tile is one slab of kElemThreads elements, planned like any other.
+  bool elem = false;
+  if constexpr (M == 4 && CMP)
+    elem = ctx->elem_threads && a.lv.cls && a.lv.bsym && !a.gs && !chk && a.nsweeps >= 1 && sel.mode == 0 && !a.r_out &&
+           !a.par_in && !a.par_out && !a.ld_out && (!a.lf_in || a.mc_in == 2) && (!a.lf_out || a.mc_out == 2) &&
+           (!a.do_residual || a.lf_out) && fused_tile_plan(kElemThreads, halo, align, vr, a.agg_shift).owned > 0;
+  const FusedTilePlan plan = fused_tile_plan(elem ? kElemThreads : T::TE, halo, align, vr, a.agg_shift);   // host_plan.hpp
   a.agg_shift = plan.agg_shift;
   if (vr && plan.agg_shift < 0)   // agglomerates cut by a tile boundary are summed from two tiles
     HIPCHK(hipMemsetAsync(a.rc_out, 0, (size_t)a.nec_out * a.mc_out * sizeof(double), ctx->stream));
@@ -589,7 +603,6 @@ static int launch_btd_t(aggmg_ctx* ctx, FusedLaunch a, int halo, const TileSel& 
   a.tile_skip = sub.skip;
   if (chk_io) chk_io->ntiles = ntiles;
   if (ntiles == 0) return AGGMG_OK;
-  const bool chk = a.chk_part != nullptr;   // checkpoint variant (multigrid's per-cycle residual test inside the launch)
   if (chk && a.gs) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: checkpoint launch with Gauss-Seidel sweeps");
   // every tile stores its sums at chk_part[(checkpoint * ntiles + tile) * 2]: never past what was reserved
   if (chk && (!chk_io || ntiles > chk_io->cap))
@@ -623,6 +636,21 @@ static int launch_btd_t(aggmg_ctx* ctx, FusedLaunch a, int halo, const TileSel& 
       // the variant indexes the transfer's rows by class only on its two-mode, equal-agglomerate paths
       if (a.par_in || a.par_out || a.ld_out || (a.lf_in && a.mc_in != 2) || (a.lf_out && a.mc_out != 2))
         return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: dictionary launch with a transfer the variant does not index by class");
+      if constexpr (M == 4) {
+        if (elem) {
+          auto go_elem = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(kElemThreads), elem_lds_bytes<M>(), ctx->stream,
+                               static_cast<const FusedArgs&>(a), a.wts);
+          };
+          if (sres)
+            go_elem(btd_elem_dict_kernel<M, true>);
+          else
+            go_elem(btd_elem_dict_kernel<M, false>);
+          HIPCHK(hipGetLastError());
+          ++ctx->elem_launches;
+          return AGGMG_OK;
+        }
+      }
       if (sres)
         go(btd_fused_kernel<M, CMP, T::NS, true, T::NT, false, false, true, true>);
       else
@@ -2409,6 +2437,12 @@ extern "C" int aggmg_hier_level_sym_residual(aggmg_ctx* ctx, const aggmg_hier* h
   if (level < 0 || level >= (int)h->lv.size()) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_sym_residual: level out of range");
   const Level& l = h->lv[level];
   *on = (l.S && l.S->btd && l.S->btd->dup) ? 1 : 0;
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_element_thread_launches(aggmg_ctx* ctx, int64_t* count) {
+  if (!ctx || !count) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_element_thread_launches: NULL argument");
+  *count = ctx->elem_launches;
   return AGGMG_OK;
 }
 

@@ -71,6 +71,8 @@ struct aggmg_ctx {
   bool pair_levels = [] { const char* e = std::getenv("AGGMG_PAIR"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_PAIR_LEVELS
   bool sym_residual = [] { const char* e = std::getenv("AGGMG_SYM_RESIDUAL"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_SYMMETRIC_RESIDUAL
   bool op_dict = [] { const char* e = std::getenv("AGGMG_OP_DICT"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_OPERATOR_DICTIONARY
+  bool elem_threads = [] { const char* e = std::getenv("AGGMG_ELEM_THREADS"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_ELEMENT_THREADS
+  int64_t elem_launches = 0;   // launches of the element-thread kernel so far (aggmg_element_thread_launches)
   int profiling = 0;  // 0 off, 1 every launch, 2 only the fine-level fused-down launch (dominant kernel)
   std::vector<ProfEvent> prof;
   std::vector<hipEvent_t> ev_pool;

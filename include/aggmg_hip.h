@@ -128,7 +128,19 @@ int aggmg_synchronize(aggmg_ctx* ctx);
  * Hierarchies created afterwards; aggmg_hier_level_dictionary reports the levels.  aggmg_hier_launch_bytes keeps
  * counting the full arrays (DESIGN.md sections 4 and 5). */
 #define AGGMG_OPT_OPERATOR_DICTIONARY 7
+/* AGGMG_OPT_ELEMENT_THREADS (default 1; environment AGGMG_ELEM_THREADS=0 makes the default 0): the dictionary launches
+ * of a cycle on a level with blocks of 4 rows (DG p = 3: descent, ascent, the launch between two cycles; block-Jacobi,
+ * at least one sweep, all tiles of the level) run the kernel in which one THREAD owns an element -- its four rows, their
+ * right-hand side, iterate and stencil words in registers, tiles of 256 elements -- instead of one thread per row: the
+ * per-element index, class and address arithmetic is done once and the 4 x 4 products need no cross-lane move.  The
+ * row-thread kernel is bound by the issue rate of its vector instructions, not by memory (profiles/r26_element_threads.md).
+ * Every result is bit for bit the same.  Read at every launch; 0: the row-thread dictionary kernel for every launch.
+ * Blocks of 2 rows, launches without sweeps, tile selections, checkpoint, Gauss-Seidel, K-column and two-level launches
+ * keep their kernels either way.  aggmg_element_thread_launches counts the launches the kernel has served. */
+#define AGGMG_OPT_ELEMENT_THREADS 8
 int aggmg_set_option(aggmg_ctx* ctx, int option, int value);
+/* Launches of the element-thread kernel (AGGMG_OPT_ELEMENT_THREADS) on this context so far. */
+int aggmg_element_thread_launches(aggmg_ctx* ctx, int64_t* count);
 /* Raw device memory owned by the context's device (plumbing for harnesses without torch, and the storage of the
  * Julia shim's DeviceVector).  aggmg_dev_alloc returns ZEROED memory: a fresh vector is the zero initial guess of
  * ldiv! (src/solvers.jl:66,87). */

@@ -278,6 +278,15 @@ end
 # AGGMG_OP_DICT=0 makes the default 0): hierarchies created afterwards keep one copy of every distinct per-element
 # operator record of a fused level and index the operator by the element's class -- the same bits, read from cache.
 const OPT_OPERATOR_DICTIONARY = 7
+# AGGMG_OPT_ELEMENT_THREADS (default 1; environment AGGMG_ELEM_THREADS=0 makes the default 0): the dictionary launches of
+# a cycle on a level with blocks of 4 rows run the kernel in which one thread owns an element -- the same bits; 0 keeps
+# the row-thread kernel.  element_thread_launches(ctx): how many launches that kernel has served.
+const OPT_ELEMENT_THREADS = 8
+function element_thread_launches(ctx::Context)
+    r = Ref{Int64}(0)
+    check(ctx.h, ccall((:aggmg_element_thread_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
+    return r[]
+end
 function set_option!(ctx::Context, option::Integer, value::Integer)
     check(ctx.h, ccall((:aggmg_set_option, LIB), Cint, (Handle, Cint, Cint), ctx.h, option, value))
     return ctx

@@ -45,7 +45,8 @@ def period(seq, windows=5):
 
 def roles_of(window):
     """window: list of short kernel names of one cycle"""
-    fused = [i for i, k in enumerate(window) if "fused_kernel" in k or "btd_pair_" in k]
+    # (btd_elem_dict_kernel, r26: the element-thread form of a fused launch -- the same roles)
+    fused = [i for i, k in enumerate(window) if "fused_kernel" in k or "btd_pair_" in k or "btd_elem_" in k]
     coarse = [i for i, k in enumerate(window) if "cr_" in k]
     first_c = coarse[0] if coarse else len(window)
     names = []
