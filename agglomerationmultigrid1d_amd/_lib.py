@@ -22,6 +22,7 @@ OPT_MG_CHECKPOINT = 5
 OPT_SYMMETRIC_RESIDUAL = 6
 OPT_OPERATOR_DICTIONARY = 7
 OPT_ELEMENT_THREADS = 8
+OPT_PAIR_ELEMENT_THREADS = 9
 PROFILE_NTAGS = 256
 KIND_FUSED_DOWN, KIND_FUSED_UP, KIND_SMOOTH, KIND_RESIDUAL, KIND_RESTRICT, KIND_PROLONG, \
     KIND_JACOBI, KIND_BLOCK_APPLY, KIND_COARSE, KIND_FUSED_MID = range(10)
@@ -91,6 +92,7 @@ SYMBOLS = {
     "aggmg_synchronize": (c_int, [_P]),
     "aggmg_set_option": (c_int, [_P, c_int, c_int]),
     "aggmg_element_thread_launches": (c_int, [_P, POINTER(c_int64)]),
+    "aggmg_pair_element_thread_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_dev_alloc": (c_int, [_P, c_int64, POINTER(_P)]),
     "aggmg_dev_free": (c_int, [_P, _P]),
     "aggmg_memcpy_h2d": (c_int, [_P, _P, _P, c_int64]),

@@ -93,6 +93,13 @@ class Context:
         self.check(self.lib.aggmg_element_thread_launches(self.handle, ctypes.byref(n)))
         return int(n.value)
 
+    def pair_element_thread_launches(self):
+        """launches of the element-thread two-level kernels on this context so far (C ABI
+        aggmg_pair_element_thread_launches, AGGMG_OPT_PAIR_ELEMENT_THREADS)"""
+        n = ctypes.c_int64(0)
+        self.check(self.lib.aggmg_pair_element_thread_launches(self.handle, ctypes.byref(n)))
+        return int(n.value)
+
     def option(self, option, default):
         """the value last given to set_option (the C ABI has no getter), `default` when it never was set"""
         return self.__dict__.get("_options", {}).get(int(option), default)

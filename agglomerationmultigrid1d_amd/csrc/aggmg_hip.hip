@@ -11,6 +11,7 @@
 #include "pair_kernels.hpp"
 #include "patch_kernels.hpp"
 #include "elem_kernels.hpp"
+#include "pair_elem_kernels.hpp"
 #include "krylov_kernels.hpp"
 #include "host_gmres.hpp"
 
@@ -172,6 +173,9 @@ extern "C" int aggmg_set_option(aggmg_ctx* ctx, int option, int value) {
       return AGGMG_OK;
     case AGGMG_OPT_ELEMENT_THREADS:
       ctx->elem_threads = value != 0;
+      return AGGMG_OK;
+    case AGGMG_OPT_PAIR_ELEMENT_THREADS:
+      ctx->pair_elem_threads = value != 0;
       return AGGMG_OK;
   }
   return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_set_option: unknown option");
@@ -2336,6 +2340,20 @@ static bool pair_dictionary(PairArgs& p, PairDict& d, const Level& a, const Leve
   return true;
 }
 
+// The element-thread kernels (pair_elem_kernels.hpp, AGGMG_OPT_PAIR_ELEMENT_THREADS) in place of the row-thread dictionary
+// ones: both levels have their packed records (at most kPairElemMaxClasses classes each) and the element-thread tile has
+// a plan for these ratios and sweeps.  p holds the launch's vectors; the plan's tile replaces the row-thread one.
+static bool pair_element_threads(const aggmg_ctx* ctx, PairArgs& p, PairElemDict& e, const Level& a, const Level& b, const PairTilePlan& plan) {
+  const PairDictDev *da = a.pdict.get(), *db = b.pdict.get();
+  if (!ctx->pair_elem_threads || !da || !db || !da->rec || !db->rec || plan.own <= 0) return false;
+  e = PairElemDict{da->cls, db->cls, da->rec, db->rec, da->nclasses, db->nclasses};
+  p.own = plan.own;
+  p.te_a = plan.te_a;
+  p.te_b = plan.te_b;
+  p.hb = plan.hb;
+  return true;
+}
+
 static int launch_pair_down(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPre, double alpha) {
   Level& a = h->lv[k];
   Level& b = h->lv[k + 1];
@@ -2352,13 +2370,20 @@ static int launch_pair_down(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPre, doub
   p.rhs_b = b.rhs;
   p.u_b = b.u[0];
   p.rhs_c = c.rhs;
-  const int64_t ntiles = (p.B.ne + plan.own - 1) / plan.own;
+  int64_t ntiles = (p.B.ne + plan.own - 1) / plan.own;
   if (ntiles == 0) return AGGMG_OK;
   const size_t lds = ((size_t)2 * (kPairTEA + 2) * kPairM + (size_t)kPairTEB * 2) * sizeof(double);
   PairDict d;
   const bool dict = pair_dictionary(p, d, a, b);
+  PairElemDict ed;
+  const bool elem = dict && pair_element_threads(ctx, p, ed, a, b, pair_down_plan(nPre, p.ab.rho, p.bc.rho, kPairElemTEA, kPairElemTEB));
   ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
-  if (dict)
+  if (elem) {
+    ntiles = (p.B.ne + p.own - 1) / p.own;
+    hipLaunchKernelGGL((btd_pair_down_elem_kernel<kPairElemThreads>), dim3((unsigned)ntiles), dim3(kPairElemThreads),
+                       pair_elem_lds_bytes(ed.nca, ed.ncb), ctx->stream, p, wa, wb, ed);
+    ++ctx->pair_elem_launches;
+  } else if (dict)
     hipLaunchKernelGGL((btd_pair_down_dict_kernel<kPairM, kPairNSA, kPairNSB, kThreads>), dim3((unsigned)ntiles), dim3(kThreads),
                        lds, ctx->stream, p, wa, wb, d);
   else
@@ -2409,8 +2434,15 @@ static int launch_pair_up(aggmg_ctx* ctx, aggmg_hier* h, int k, int nPost, doubl
   const size_t lds = ((size_t)2 * (kPairTEA + 2) * kPairM + (size_t)kPairTEB * 2) * sizeof(double);
   PairDict d;
   const bool dict = part == 0 && pair_dictionary(p, d, a, b);   // (the element-partitioned cycle keeps the full arrays)
+  PairElemDict ed;
+  const bool elem = dict && pair_element_threads(ctx, p, ed, a, b, pair_up_plan(nPost, p.ab.rho, kPairElemTEA, kPairElemTEB));
   ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
-  if (dict)
+  if (elem) {
+    ntiles = (p.A.ne + p.own - 1) / p.own;
+    hipLaunchKernelGGL((btd_pair_up_elem_kernel<kPairElemThreads>), dim3((unsigned)ntiles), dim3(kPairElemThreads),
+                       pair_elem_lds_bytes(ed.nca, ed.ncb), ctx->stream, p, wa, wb, ed);
+    ++ctx->pair_elem_launches;
+  } else if (dict)
     hipLaunchKernelGGL((btd_pair_up_dict_kernel<kPairM, kPairNSA, kPairNSB, kThreads>), dim3((unsigned)ntiles), dim3(kThreads),
                        lds, ctx->stream, p, wa, wb, d);
   else
@@ -2443,6 +2475,12 @@ extern "C" int aggmg_hier_level_sym_residual(aggmg_ctx* ctx, const aggmg_hier* h
 extern "C" int aggmg_element_thread_launches(aggmg_ctx* ctx, int64_t* count) {
   if (!ctx || !count) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_element_thread_launches: NULL argument");
   *count = ctx->elem_launches;
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_pair_element_thread_launches(aggmg_ctx* ctx, int64_t* count) {
+  if (!ctx || !count) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_pair_element_thread_launches: NULL argument");
+  *count = ctx->pair_elem_launches;
   return AGGMG_OK;
 }
 

@@ -73,6 +73,8 @@ struct aggmg_ctx {
   bool op_dict = [] { const char* e = std::getenv("AGGMG_OP_DICT"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_OPERATOR_DICTIONARY
   bool elem_threads = [] { const char* e = std::getenv("AGGMG_ELEM_THREADS"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_ELEMENT_THREADS
   int64_t elem_launches = 0;   // launches of the element-thread kernel so far (aggmg_element_thread_launches)
+  bool pair_elem_threads = [] { const char* e = std::getenv("AGGMG_PAIR_ELEM_THREADS"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_PAIR_ELEMENT_THREADS
+  int64_t pair_elem_launches = 0;   // launches of the element-thread pair kernels so far (aggmg_pair_element_thread_launches)
   int profiling = 0;  // 0 off, 1 every launch, 2 only the fine-level fused-down launch (dominant kernel)
   std::vector<ProfEvent> prof;
   std::vector<hipEvent_t> ev_pool;
@@ -270,6 +272,9 @@ struct PairDictDev {
   DevArray<double> bsym, sup, sback, sub, dblk;
   DevArray<double> lf;       // [nclasses][2] second entries (the transfer has lf1), else [nclasses][2][2] rows of L
   bool lf_unit = false;      // lf holds the lf1 form
+  // the same words once more, one record of kPairRecWords per class (pair_elem_kernels.hpp: what the element-thread
+  // launches copy into LDS); only for a level of at most kPairElemMaxClasses classes, else null
+  DevArray<double> rec;
 };
 
 // structured transfer of a CG chain level (CgtXfer in cgt_kernels.hpp)

@@ -7,6 +7,7 @@
 
 #include "internal.hpp"
 #include "setup_kernels.hpp"
+#include "pair_elem_kernels.hpp"
 
 namespace {
 
@@ -654,6 +655,40 @@ int setup_pair_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t,
   F.add(b.dblk, &d->dblk, m * m);
   F.add(t.lf1 ? t.lf1 : t.lf, &d->lf, m * (t.lf1 ? 1 : 2));
   CHECK(dict_build(ctx, F, &d->cls, &d->nclasses));
+  if (d->nclasses > 0 && d->nclasses <= kPairElemMaxClasses) {
+    // the record of every class once more in the element-thread pair kernels' layout (pair_elem_kernels.hpp): a few KB,
+    // repacked on the host
+    const int nc = d->nclasses, nl = d->lf_unit ? m : 2 * m;
+    std::vector<double> hb(3 * nc), hsb(4 * nc), hsp(4 * nc), hsu(4 * nc), hd(4 * nc), hl((size_t)nl * nc);
+    std::vector<double> rec((size_t)nc * kPairRecWords, 0.0);
+    auto down = [&](std::vector<double>& v, const double* src) {
+      return hipMemcpyAsync(v.data(), src, v.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    };
+    HIPCHK(down(hb, d->bsym));
+    HIPCHK(down(hsb, d->sback));
+    HIPCHK(down(hsp, d->sup));
+    HIPCHK(down(hsu, d->sub));
+    HIPCHK(down(hd, d->dblk));
+    HIPCHK(down(hl, d->lf));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int c = 0; c < nc; ++c) {
+      double* r = rec.data() + (size_t)c * kPairRecWords;
+      for (int j = 0; j < 3; ++j) r[kPairRecBsym + j] = hb[c * 3 + j];
+      for (int j = 0; j < 4; ++j) {
+        r[kPairRecSback + j] = hsb[c * 4 + j];
+        r[kPairRecSup + j] = hsp[c * 4 + j];
+        r[kPairRecSub + j] = hsu[c * 4 + j];
+        r[kPairRecDblk + j] = hd[c * 4 + j];
+      }
+      for (int i = 0; i < 2; ++i) {   // (a unit first column: the 1.0 it stands for)
+        r[kPairRecLf + 2 * i] = d->lf_unit ? 1.0 : hl[(c * 2 + i) * 2];
+        r[kPairRecLf + 2 * i + 1] = d->lf_unit ? hl[c * 2 + i] : hl[(c * 2 + i) * 2 + 1];
+      }
+    }
+    CHECK(d->rec.alloc(ctx, (int64_t)rec.size()));
+    HIPCHK(hipMemcpyAsync(d->rec, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // (the host vector is done with)
+  }
   if (d->nclasses > 0) *out = std::move(d);
   return AGGMG_OK;
 }

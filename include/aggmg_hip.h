@@ -138,9 +138,20 @@ int aggmg_synchronize(aggmg_ctx* ctx);
  * Blocks of 2 rows, launches without sweeps, tile selections, checkpoint, Gauss-Seidel, K-column and two-level launches
  * keep their kernels either way.  aggmg_element_thread_launches counts the launches the kernel has served. */
 #define AGGMG_OPT_ELEMENT_THREADS 8
+/* AGGMG_OPT_PAIR_ELEMENT_THREADS (default 1; environment AGGMG_PAIR_ELEM_THREADS=0 makes the default 0): the two-level
+ * launches of a cycle (AGGMG_OPT_PAIR_LEVELS) whose two levels both have a dictionary of at most 32 classes run the
+ * kernels in which one THREAD owns an element -- a level-a element in level a's phase, a level-b element in level b's,
+ * both rows, right-hand side, iterate and the rows of B^{-1} Sub, B^{-1} Sup in registers -- and the class records of
+ * both levels are copied into LDS once per workgroup (profiles/r27_pair_element_threads.md).  Every result is bit for
+ * bit the same.  Read at every launch; 0: the row-thread dictionary kernels.  Levels with more classes, levels without
+ * a dictionary and the partitioned cycle's tile selections keep their kernels either way.
+ * aggmg_pair_element_thread_launches counts the launches these kernels have served. */
+#define AGGMG_OPT_PAIR_ELEMENT_THREADS 9
 int aggmg_set_option(aggmg_ctx* ctx, int option, int value);
 /* Launches of the element-thread kernel (AGGMG_OPT_ELEMENT_THREADS) on this context so far. */
 int aggmg_element_thread_launches(aggmg_ctx* ctx, int64_t* count);
+/* Launches of the element-thread two-level kernels (AGGMG_OPT_PAIR_ELEMENT_THREADS) on this context so far. */
+int aggmg_pair_element_thread_launches(aggmg_ctx* ctx, int64_t* count);
 /* Raw device memory owned by the context's device (plumbing for harnesses without torch, and the storage of the
  * Julia shim's DeviceVector).  aggmg_dev_alloc returns ZEROED memory: a fresh vector is the zero initial guess of
  * ldiv! (src/solvers.jl:66,87). */

@@ -287,6 +287,16 @@ function element_thread_launches(ctx::Context)
     check(ctx.h, ccall((:aggmg_element_thread_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
     return r[]
 end
+# AGGMG_OPT_PAIR_ELEMENT_THREADS (default 1; environment AGGMG_PAIR_ELEM_THREADS=0 makes the default 0): the two-level
+# launches whose levels both have a dictionary of at most 32 classes run the kernels in which one thread owns an element,
+# the class records in LDS -- the same bits; 0 keeps the row-thread kernels.  pair_element_thread_launches(ctx): how many
+# launches those kernels have served.
+const OPT_PAIR_ELEMENT_THREADS = 9
+function pair_element_thread_launches(ctx::Context)
+    r = Ref{Int64}(0)
+    check(ctx.h, ccall((:aggmg_pair_element_thread_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
+    return r[]
+end
 function set_option!(ctx::Context, option::Integer, value::Integer)
     check(ctx.h, ccall((:aggmg_set_option, LIB), Cint, (Handle, Cint, Cint), ctx.h, option, value))
     return ctx

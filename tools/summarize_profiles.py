@@ -52,8 +52,9 @@ def roles_of(window):
     names = []
     down = [i for i in fused if i < first_c]
     up = [i for i in fused if i > first_c]
-    # a two-level launch (btd_pair_*_kernel, r04) carries its level and the next coarser one: levels are counted
-    # through it
+    # a two-level launch (btd_pair_*_kernel, r04; its dictionary form btd_pair_*_dict_kernel, r19, and its
+    # element-thread form btd_pair_*_elem_kernel, r27 -- the same roles) carries its level and the next coarser one:
+    # levels are counted through it
     lev, lv = {}, 0
     for i in down:
         lev[i] = lv
