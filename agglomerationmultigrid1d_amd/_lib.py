@@ -23,9 +23,11 @@ OPT_SYMMETRIC_RESIDUAL = 6
 OPT_OPERATOR_DICTIONARY = 7
 OPT_ELEMENT_THREADS = 8
 OPT_PAIR_ELEMENT_THREADS = 9
+OPT_REPLAY_PRESMOOTH = 10
 PROFILE_NTAGS = 256
 KIND_FUSED_DOWN, KIND_FUSED_UP, KIND_SMOOTH, KIND_RESIDUAL, KIND_RESTRICT, KIND_PROLONG, \
     KIND_JACOBI, KIND_BLOCK_APPLY, KIND_COARSE, KIND_FUSED_MID = range(10)
+KIND_REPLAY_DOWN, KIND_REPLAY_UP = 10, 11   # aggmg_hier_launch_bytes only: the launches of a replayed cycle (no profile tag)
 KIND_NAMES = ["fused_down", "fused_up", "smooth", "residual", "restrict", "prolong", "jacobi",
               "block_apply", "coarse", "fused_mid"]
 COARSE_HOST_BANDED, COARSE_DEVICE_CR, COARSE_AUTO, COARSE_EXTERNAL = 0, 1, 2, 3
@@ -93,6 +95,7 @@ SYMBOLS = {
     "aggmg_set_option": (c_int, [_P, c_int, c_int]),
     "aggmg_element_thread_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_pair_element_thread_launches": (c_int, [_P, POINTER(c_int64)]),
+    "aggmg_replay_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_dev_alloc": (c_int, [_P, c_int64, POINTER(_P)]),
     "aggmg_dev_free": (c_int, [_P, _P]),
     "aggmg_memcpy_h2d": (c_int, [_P, _P, _P, c_int64]),

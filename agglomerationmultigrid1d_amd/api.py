@@ -100,6 +100,13 @@ class Context:
         self.check(self.lib.aggmg_pair_element_thread_launches(self.handle, ctypes.byref(n)))
         return int(n.value)
 
+    def replay_launches(self):
+        """cycles of vcycle_dev that replayed their pre-smoothing on this context so far (C ABI aggmg_replay_launches,
+        AGGMG_OPT_REPLAY_PRESMOOTH)"""
+        n = ctypes.c_int64(0)
+        self.check(self.lib.aggmg_replay_launches(self.handle, ctypes.byref(n)))
+        return int(n.value)
+
     def option(self, option, default):
         """the value last given to set_option (the C ABI has no getter), `default` when it never was set"""
         return self.__dict__.get("_options", {}).get(int(option), default)
@@ -1117,8 +1124,11 @@ class MeshHierarchy:
 
     def launch_bytes(self, level, kind, has_x0=None):
         """(read, write) compulsory HBM bytes of the fused launch of `level`: kind 'down' / 'up' / 'mid'
-        (C ABI aggmg_hier_launch_bytes) -- every array of the launch counted once, as stored."""
-        kk = {"down": _lib.KIND_FUSED_DOWN, "up": _lib.KIND_FUSED_UP, "mid": _lib.KIND_FUSED_MID}[kind]
+        (C ABI aggmg_hier_launch_bytes) -- every array of the launch counted once, as stored.  'down' and 'up' are the
+        launches that store the pre-smoothed iterate and read it back; 'replay_down' / 'replay_up' those of a cycle
+        that replays its pre-smoothing (AGGMG_OPT_REPLAY_PRESMOOTH)."""
+        kk = {"down": _lib.KIND_FUSED_DOWN, "up": _lib.KIND_FUSED_UP, "mid": _lib.KIND_FUSED_MID,
+              "replay_down": _lib.KIND_REPLAY_DOWN, "replay_up": _lib.KIND_REPLAY_UP}[kind]
         r, w = ctypes.c_int64(0), ctypes.c_int64(0)
         x0 = (level == 0) if has_x0 is None else bool(has_x0)
         self.ctx.check(self.ctx.lib.aggmg_hier_launch_bytes(self.ctx.handle, self.handle, int(level), kk, int(x0),

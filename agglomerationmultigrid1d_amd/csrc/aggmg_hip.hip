@@ -177,6 +177,9 @@ extern "C" int aggmg_set_option(aggmg_ctx* ctx, int option, int value) {
     case AGGMG_OPT_PAIR_ELEMENT_THREADS:
       ctx->pair_elem_threads = value != 0;
       return AGGMG_OK;
+    case AGGMG_OPT_REPLAY_PRESMOOTH:
+      ctx->replay_presmooth = value != 0;
+      return AGGMG_OK;
   }
   return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_set_option: unknown option");
 }
@@ -575,6 +578,15 @@ struct FusedLaunch : FusedArgs {
   SweepWeights wts;
 };
 
+// What the element-thread kernel (elem_kernels.hpp) asks of a launch's arguments, on a level with compressed couplings
+// and blocks of 4 rows: a dictionary launch of block-Jacobi sweeps -- at least one -- over all tiles of the level, two-mode
+// transfers of equal agglomerates, a residual that is restricted and not stored.  (Its tile is the caller's to plan.)
+static bool elem_thread_args(const aggmg_ctx* ctx, const FusedArgs& a, bool chk, int sel_mode) {
+  return ctx->elem_threads && a.lv.cls && a.lv.bsym && !a.gs && !chk && a.nsweeps >= 1 && sel_mode == 0 && !a.r_out &&
+         !a.par_in && !a.par_out && !a.ld_out && (!a.lf_in || a.mc_in == 2) && (!a.lf_out || a.mc_out == 2) &&
+         (!a.do_residual || a.lf_out);
+}
+
 template <int M, bool CMP>
 static int launch_btd_t(aggmg_ctx* ctx, FusedLaunch a, int halo, const TileSel& sel, CgtChk* chk_io) {
   using T = BtdTile<M, CMP>;
@@ -590,9 +602,7 @@ static int launch_btd_t(aggmg_ctx* ctx, FusedLaunch a, int halo, const TileSel& 
   // Its tile is one slab of kElemThreads elements, planned like any other.
   bool elem = false;
   if constexpr (M == 4 && CMP)
-    elem = ctx->elem_threads && a.lv.cls && a.lv.bsym && !a.gs && !chk && a.nsweeps >= 1 && sel.mode == 0 && !a.r_out &&
-           !a.par_in && !a.par_out && !a.ld_out && (!a.lf_in || a.mc_in == 2) && (!a.lf_out || a.mc_out == 2) &&
-           (!a.do_residual || a.lf_out) && fused_tile_plan(kElemThreads, halo, align, vr, a.agg_shift).owned > 0;
+    elem = elem_thread_args(ctx, a, chk, sel.mode) && fused_tile_plan(kElemThreads, halo, align, vr, a.agg_shift).owned > 0;
   const FusedTilePlan plan = fused_tile_plan(elem ? kElemThreads : T::TE, halo, align, vr, a.agg_shift);   // host_plan.hpp
   a.agg_shift = plan.agg_shift;
   if (vr && plan.agg_shift < 0)   // agglomerates cut by a tile boundary are summed from two tiles
@@ -2484,6 +2494,12 @@ extern "C" int aggmg_pair_element_thread_launches(aggmg_ctx* ctx, int64_t* count
   return AGGMG_OK;
 }
 
+extern "C" int aggmg_replay_launches(aggmg_ctx* ctx, int64_t* count) {
+  if (!ctx || !count) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_replay_launches: NULL argument");
+  *count = ctx->replay_launches;
+  return AGGMG_OK;
+}
+
 extern "C" int aggmg_hier_level_dictionary(aggmg_ctx* ctx, const aggmg_hier* h, int level, int* nclasses) {
   if (!ctx || !h || !nclasses) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_dictionary: NULL argument");
   if (level < 0 || level >= (int)h->lv.size()) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_dictionary: level out of range");
@@ -2513,6 +2529,8 @@ extern "C" int aggmg_hier_set_sweep_weights(aggmg_ctx* ctx, aggmg_hier* h, int l
   l.w_post.assign(post, post + npost);
   l.w_mid = l.w_post;
   l.w_mid.insert(l.w_mid.end(), l.w_pre.begin(), l.w_pre.end());
+  l.w_replay = l.w_pre;
+  l.w_replay.insert(l.w_replay.end(), l.w_post.begin(), l.w_post.end());
   return AGGMG_OK;
 }
 
@@ -2576,13 +2594,15 @@ static int no_split_ascent(aggmg_ctx* ctx) {
 
 // Block-tridiagonal levels (LevelPath::FusedBtd, BtdTransfer).  One fused launch where the level has the structured
 // transfer and the launch a tile; otherwise chunked sweeps and the generic launches around them.
-static int btd_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uin, const double* rhs, int nPre, double alpha) {
+// store = false (a replayed cycle, replay_ok said so): the fused launch keeps the pre-smoothed iterate to itself.
+static int btd_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uin, const double* rhs, int nPre, double alpha,
+                    bool store = true) {
   Level& l = h->lv[k];
   const BtdDev& B = *l.S->btd;
   const Damping damp = l.damp_pre(alpha);   // the level's schedule, or alpha for every sweep
   const int gs = l.S->gs ? 1 : 0;           // Gauss-Seidel: even elements, then odd ones
   if (l.tb && btd_launch_ok(*l.S, nPre, 1, l.tb.get())) {
-    FusedLaunch a = fused_sweeps(B, uin, rhs, l.u[0], damp, nPre, gs);
+    FusedLaunch a = fused_sweeps(B, uin, rhs, store ? l.u[0].get() : nullptr, damp, nPre, gs);
     fused_descent(a, h, l, h->lv[k + 1].rhs);
     fused_dictionary(a, l);
     ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
@@ -2625,6 +2645,71 @@ static int btd_mid(aggmg_ctx* ctx, aggmg_hier* h, const double* cur, double* alt
   fused_dictionary(a, l);
   ProfScope ps(ctx, AGGMG_KIND_FUSED_MID, 0);
   return launch_btd(ctx, *l.S->btd, a, nsweeps + 1, TileSel(), chk);
+}
+
+// ---- the replayed cycle (AGGMG_OPT_REPLAY_PRESMOOTH; elem_kernels.hpp, btd_elem_replay_up_kernel): level 0's descent
+// stores no iterate and its ascent rebuilds it from the cycle's first iterate -- a vector less written and the same
+// vector count read, the same bits.  Only aggmg_vcycle_dev asks; every other caller of the half-cycles keeps the stored
+// iterate (the loops over cycles, the split entry points, the partitioned and K-column cycles).
+// The arguments of level 0's two launches as btd_down / btd_up would build them: x0 stands where the ascent reads l.u[0].
+static FusedLaunch replay_down_args(aggmg_hier* h, const double* x0, const double* b, int nPre, double alpha) {
+  Level& l = h->lv[0];
+  FusedLaunch a = fused_sweeps(*l.S->btd, x0, b, nullptr, l.damp_pre(alpha), nPre);
+  fused_descent(a, h, l, h->lv[1].rhs);
+  fused_dictionary(a, l);
+  return a;
+}
+static FusedLaunch replay_up_args(aggmg_hier* h, const double* x0, const double* b, int nPre, int nPost, double alpha, double* dst) {
+  Level& l = h->lv[0];
+  FusedLaunch a = fused_sweeps(*l.S->btd, x0, b, dst, l.damp_replay(alpha), nPre + nPost);
+  fused_ascent(a, l, coarse_result(h, 0));
+  fused_dictionary(a, l);
+  return a;
+}
+// Does this cycle replay?  Level 0 is a fused block-tridiagonal level (never part of a two-level launch: pair_ok starts
+// at level 1) whose descent and ascent are both single launches of the element-thread kernel, there are sweeps on both
+// sides and a weight for each, the replaying launch has a tile, and x_out's range is disjoint from x0's -- the ascent
+// reads x0's halos while other workgroups store x_out; a partial overlap, harmless on the storing path, would race here.
+// Not on a hierarchy whose half-cycle entry points have been used (aggmg_hier::halves_used): an ascent on its own may
+// follow a whole cycle and read the iterate that cycle stored.
+static bool replay_ok(const aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const double* b, int nPre, int nPost, double alpha,
+                      const double* x_out) {
+  if (!ctx->replay_presmooth || !ctx->elem_threads || h->halves_used || h->lv.size() < 2 || level_path(h, 0) != LevelPath::FusedBtd) return false;
+  if (nPre < 1 || nPost < 1 || nPre + nPost > kSweepWeights) return false;
+  const Level& l = h->lv[0];
+  const BtdDev& B = *l.S->btd;
+  if (B.m != 4 || !B.cmp || l.S->gs || !l.tb || !btd_launch_ok(*l.S, nPre, 1, l.tb.get()) || !btd_launch_ok(*l.S, nPost, 0, nullptr)) return false;
+  const FusedLaunch dn = replay_down_args(h, x0, b, nPre, alpha), up = replay_up_args(h, x0, b, nPre, nPost, alpha, nullptr);
+  if (!elem_thread_args(ctx, dn, false, 0) || !elem_thread_args(ctx, up, false, 0)) return false;
+  if (fused_tile_plan(kElemThreads, nPre + 1, dn.rho_out, false, dn.agg_shift).owned <= 0 ||
+      fused_tile_plan(kElemThreads, nPost, 1, false, up.agg_shift).owned <= 0 ||
+      fused_tile_plan(kElemThreads, nPre + nPost, 1, false, up.agg_shift).owned <= 0)
+    return false;
+  if (x0) {
+    const uintptr_t p = reinterpret_cast<uintptr_t>(x0), q = reinterpret_cast<uintptr_t>(x_out), len = (uintptr_t)l.N * sizeof(double);
+    if (p < q + len && q < p + len) return false;
+  }
+  return true;
+}
+static int btd_replay_up(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const double* b, int nPre, int nPost, double alpha,
+                         double* dst) {
+  FusedLaunch a = replay_up_args(h, x0, b, nPre, nPost, alpha, dst);
+  const FusedTilePlan plan = fused_tile_plan(kElemThreads, nPre + nPost, 1, false, a.agg_shift);
+  if (plan.owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: replayed ascent without a tile");
+  a.agg_shift = plan.agg_shift;
+  a.owned = plan.owned;
+  a.halo_left = plan.halo_left;
+  const TileSubset sub = fused_tile_subset(a.lv.ne, plan.owned, 0, 0, 0);
+  a.tile_split = sub.split;
+  a.tile_skip = sub.skip;
+  if (sub.ntiles == 0) return AGGMG_OK;
+  ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, 0);
+  hipLaunchKernelGGL(btd_elem_replay_up_kernel<4>, dim3((unsigned)sub.ntiles), dim3(kElemThreads), elem_lds_bytes<4>(), ctx->stream,
+                     static_cast<const FusedArgs&>(a), a.wts, nPre);
+  HIPCHK(hipGetLastError());
+  ++ctx->elem_launches;
+  ++ctx->replay_launches;
+  return AGGMG_OK;
 }
 
 // Element-patch Schwarz levels (LevelPath::Patch): chunked patch sweeps, and around them the zero-sweep fused launch of the
@@ -2742,6 +2827,7 @@ static int vcycle_down(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const do
                        int k_first = 0) {
   const int n = (int)h->lv.size();
   CHECK(schedule_check(ctx, h, nPre, -1, k_first));
+  if (k_first == 0) h->fine_iterate_absent = false;   // (this descent stores level 0's pre-smoothed iterate)
   for (int k = k_first; k < n - 1; ++k) {
     const double* rhs = k == 0 ? b : h->lv[k].rhs;
     const double* uin = k == 0 ? x0 : nullptr;  // u[k] = zeros for k > 1 (:29-31)
@@ -2830,14 +2916,27 @@ extern "C" int aggmg_vcycle_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0,
   const int n = (int)h->lv.size();
   CHECK(schedule_check(ctx, h, nPre, nPost));   // (both halves before anything is enqueued)
   h->last_coarse_ms = 0.0;
-  CHECK(vcycle_down(ctx, h, x0, b, nPre, alpha));
+  // decided once, before anything is enqueued: level 0's descent stores no iterate and its ascent replays the pre-smoothing
+  // from x0 (replay_ok).  Level 0's u[0] then holds nothing defined after this call.  Its readers follow a descent of
+  // their own call sequence (the ascents of a cycle, the launch between two cycles) -- all but an ascent called on its own
+  // after a whole cycle (aggmg_vcycle_up_dev / _up_split_dev), which is refused while fine_iterate_absent says so.
+  const bool replay = replay_ok(ctx, h, x0, b, nPre, nPost, alpha, x_out);
+  if (replay) {
+    h->fine_iterate_absent = true;
+    CHECK(btd_down(ctx, h, 0, x0, b, nPre, alpha, false));
+    CHECK(vcycle_down(ctx, h, nullptr, b, nPre, alpha, 1));
+  } else {
+    CHECK(vcycle_down(ctx, h, x0, b, nPre, alpha));
+  }
   {  // coarsest solve (src/solvers.jl:39)
     Level& c = h->lv[n - 1];
     const double* rhs = n == 1 ? b : c.rhs;
     double* dst = n == 1 ? x_out : c.u[0];
     CHECK(coarse_solve(ctx, h, rhs, dst));
   }
-  return vcycle_up(ctx, h, b, nPost, alpha, x_out);
+  if (!replay) return vcycle_up(ctx, h, b, nPost, alpha, x_out);
+  CHECK(vcycle_up(ctx, h, b, nPost, alpha, nullptr, 1));
+  return btd_replay_up(ctx, h, x0, b, nPre, nPost, alpha, x_out);
 }
 
 // ---- K right-hand sides in one pass over the operators (EXTENSION: the reference's multigrid_v_cycle / ldiv! take
@@ -3222,7 +3321,18 @@ extern "C" int aggmg_vcycle_down_dev(aggmg_ctx* ctx, aggmg_hier* h, const double
                                      double alpha) {
   CHECK(vcycle_args(ctx, h, x0, b, nPre, 0));
   if (h->lv.size() < 2) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_down_dev: needs at least two levels");
+  h->halves_used = true;
   return vcycle_down(ctx, h, x0, b, nPre, alpha);
+}
+
+// An ascent called on its own reads level 0's stored pre-smoothed iterate: from now on this hierarchy's cycles store it
+// (aggmg_hier::halves_used), and there has to be one -- not after a replayed aggmg_vcycle_dev with no descent since.
+static int fine_ascent_alone(aggmg_ctx* ctx, aggmg_hier* h, const char* who) {
+  h->halves_used = true;
+  if (h->fine_iterate_absent)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": the last aggmg_vcycle_dev on this hierarchy replayed its pre-smoothing "
+                "(AGGMG_OPT_REPLAY_PRESMOOTH) and stored no fine-level iterate for an ascent on its own; call aggmg_vcycle_down_dev first");
+  return AGGMG_OK;
 }
 
 extern "C" int aggmg_vcycle_up_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* b, int nPost, double alpha,
@@ -3230,6 +3340,7 @@ extern "C" int aggmg_vcycle_up_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* 
   CHECK(vcycle_args(ctx, h, b, x_out, nPost, 0));
   if (h->lv.size() < 2) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_up_dev: needs at least two levels");
   if (x_out == b) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_up_dev: x_out must not alias b");
+  CHECK(fine_ascent_alone(ctx, h, "aggmg_vcycle_up_dev"));
   return vcycle_up(ctx, h, b, nPost, alpha, x_out);
 }
 
@@ -3257,6 +3368,7 @@ extern "C" int aggmg_vcycle_up_split_dev(aggmg_ctx* ctx, aggmg_hier* h, const do
   if (h->lv.size() < 2) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_up_split_dev: needs at least two levels");
   if (x_out == b) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_up_split_dev: x_out must not alias b");
   if (part < 0 || part > 3) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_up_split_dev: part is 0, 1, 2 or 3");
+  CHECK(fine_ascent_alone(ctx, h, "aggmg_vcycle_up_split_dev"));
   if (part == 3) {   // the finest level alone, every tile (the coarser levels were run by part 0 / aggmg_vcycle_up_coarse_dev)
     TileSel all;
     all.mode = 3;
@@ -3555,8 +3667,16 @@ extern "C" int aggmg_hier_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int 
   if (!ctx || !h || !read_bytes || !write_bytes) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_launch_bytes: NULL argument");
   if (level < 0 || level + 1 >= (int)h->lv.size())
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_launch_bytes: level out of range (the coarsest level has no fused launch)");
+  // the launches of a replayed cycle (AGGMG_OPT_REPLAY_PRESMOOTH): the descent without its iterate store; the ascent reads
+  // the first iterate where the storing one reads the stored iterate -- a vector only where there is a first iterate
+  const bool replay = kind == AGGMG_KIND_REPLAY_DOWN || kind == AGGMG_KIND_REPLAY_UP;
+  if (replay) {
+    if (level_path(h, level) != LevelPath::FusedBtd)
+      return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_hier_launch_bytes: only a fused block-tridiagonal level replays its pre-smoothing");
+    kind = kind == AGGMG_KIND_REPLAY_DOWN ? AGGMG_KIND_FUSED_DOWN : AGGMG_KIND_FUSED_UP;
+  }
   if (kind != AGGMG_KIND_FUSED_DOWN && kind != AGGMG_KIND_FUSED_UP && kind != AGGMG_KIND_FUSED_MID)
-    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_launch_bytes: kind must be AGGMG_KIND_FUSED_DOWN / _UP / _MID");
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_launch_bytes: kind must be AGGMG_KIND_FUSED_DOWN / _UP / _MID or AGGMG_KIND_REPLAY_DOWN / _UP");
   const Level& l = h->lv[level];
   const bool down = kind != AGGMG_KIND_FUSED_UP, up = kind != AGGMG_KIND_FUSED_DOWN;
   const LevelPath path = level_path(h, level);
@@ -3566,8 +3686,9 @@ extern "C" int aggmg_hier_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int 
   if (path != LevelPath::FusedBtd)
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_hier_launch_bytes: the level runs the generic kernels (several launches)");
   const bool pre = l.tb->ld && h->restriction == AGGMG_RESTRICT_PRECONDITIONED;
-  btd_launch_bytes(*l.S->btd, true, up || has_x0, down, false, up ? l.tb.get() : nullptr, down ? l.tb.get() : nullptr, pre,
+  btd_launch_bytes(*l.S->btd, true, (up && !replay) || has_x0, down, false, up ? l.tb.get() : nullptr, down ? l.tb.get() : nullptr, pre,
                    read_bytes, write_bytes);
+  if (replay && down) *write_bytes -= l.N * (int64_t)sizeof(double);   // the pre-smoothed iterate stays in the launch
   return AGGMG_OK;
 }
 

@@ -308,4 +308,164 @@ __global__ __launch_bounds__(kElemThreads) void btd_elem_dict_kernel(FusedArgs a
   }
 }
 
+// The ascent that REPLAYS the pre-smoothing (AGGMG_OPT_REPLAY_PRESMOOTH): what the descent stores only for the ascent to
+// read back -- the pre-smoothed iterate, a vector written and a vector read per cycle -- is rebuilt here from the
+// descent's own inputs.  The launch reads u_in where the ascent reads the stored iterate (the cycle's first iterate;
+// null: zeros, read not at all), runs the descent's npre sweeps, adds the prolongation, and goes on with the post sweeps:
+// a.nsweeps = npre + npost sweeps with the weights wts.w[0 .. npre) ++ wts.w[npre .. nsweeps), a halo of nsweeps elements.
+// The same arithmetic on the same inputs in the same order as btd_elem_dict_kernel's descent and ascent, so the SAME
+// BITS.  The prolongation's terms fma(lx, ucx, rnd(ly ucy)) are formed with the loads -- four words held over the
+// pre-sweeps -- and added where the last pre-sweep writes its result: u_pre + L uc is what the ascent forms from the
+// stored u_pre, and no barrier is spent on it.  Lanes outside the level stay 0.0, as the sweeps leave them.
+// What the launcher guarantees: btd_elem_dict_kernel's conditions for an ascent (lf_in, uc, no residual),
+// 1 <= npre < a.nsweeps <= kSweepWeights, and u_in's range disjoint from u_out's (the launch reads u_in's halos while
+// other workgroups store).
+template <int M>
+__global__ __launch_bounds__(kElemThreads) void btd_elem_replay_up_kernel(FusedArgs a, SweepWeights wts, int npre) {
+  static_assert(M == 4, "the element-thread kernel's block size");
+  constexpr int TE = kElemThreads;
+  constexpr int S = TE + 2;            // words of one component in a buffer
+  constexpr int T = M * (M + 1) / 2;
+  extern __shared__ double lds[];
+  double* cur = lds + 1;               // (j, x) at cur[j * S + x]
+  double* nxt = lds + M * S + 1;
+
+  const int x = threadIdx.x;
+  const int64_t ne = a.lv.ne;
+  const int64_t e0 = fused_tile(a) * a.owned - a.halo_left;   // element at x = 0
+  const int own0 = a.halo_left, own1 = a.halo_left + a.owned;
+  const int64_t rem = ne - 1 - e0;
+  if (rem < 0) return;   // a tile wholly past the level: before any barrier
+  const int xlo = e0 < 0 ? (int)-e0 : 0, xhi = rem < TE - 1 ? (int)rem : TE - 1;
+  const bool valid = x >= xlo && x <= xhi;
+  const bool own = valid && x >= own0 && x < own1;
+  const unsigned xc = (unsigned)(x < xlo ? xlo : x > xhi ? xhi : x);
+
+  if (x < 4 * M) {   // the zero elements at the ends of both buffers
+    const int j = x & (M - 1), w = x / M;
+    (w & 2 ? nxt : cur)[j * S + (w & 1 ? TE : -1)] = 0.0;
+  }
+
+  // ---- loads, straight-line: cls, b, u_in, the coarse pair; then the class record from cache -------------------------
+  const int64_t ce = (int64_t)(a.lv.cls + e0)[xc];
+  double bb[M], uu[M];
+  {
+    const double* const bp = a.b + e0 * M + xc * M;
+    const double* const up = (a.u_in ? a.u_in : a.b) + e0 * M + xc * M;   // (no first iterate: b's line again, dropped)
+#pragma unroll
+    for (int j = 0; j < M; j += 2) elem_ld2(bp + j, bb[j], bb[j + 1]);
+#pragma unroll
+    for (int j = 0; j < M; j += 2) elem_ld2(up + j, uu[j], uu[j + 1]);
+    if (!a.u_in) {
+#pragma unroll
+      for (int j = 0; j < M; ++j) uu[j] = 0.0;
+    }
+  }
+  double ucx, ucy;
+  {
+    const int64_t J = ne <= 0x7fffffff ? (int64_t)((unsigned)(e0 + xc) / (unsigned)a.rho_in) : (e0 + xc) / a.rho_in;
+    elem_ld2(a.uc + J * 2, ucx, ucy);
+  }
+  double tri[T], qm[M], q[M];
+#pragma unroll
+  for (int k = 0; k < T; k += 2) elem_ld2(a.lv.bsym + ce * T + k, tri[k], tri[k + 1]);
+#pragma unroll
+  for (int j = 0; j < M; j += 2) elem_ld2(a.lv.qmir + ce * M + j, qm[j], qm[j + 1]);
+#pragma unroll
+  for (int j = 0; j < M; j += 2) elem_ld2(a.lv.qrow + ce * M + j, q[j], q[j + 1]);
+  // L uc of the element's rows: the second product rounded, the first fused into the sum
+  double luc[M];
+  {
+    double lx[M], ly[M];
+    if (a.lf1_in) {
+#pragma unroll
+      for (int j = 0; j < M; j += 2) elem_ld2(a.lf1_in + ce * M + j, ly[j], ly[j + 1]);
+#pragma unroll
+      for (int j = 0; j < M; ++j) lx[j] = 1.0;
+    } else {
+#pragma unroll
+      for (int j = 0; j < M; ++j) elem_ld2(a.lf_in + (ce * M + j) * 2, lx[j], ly[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < M; ++j) luc[j] = __fma_rn(lx[j], ucx, __dmul_rn(ly[j], ucy));
+  }
+  if (!valid) {
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      uu[j] = 0.0;
+      bb[j] = 0.0;
+    }
+  }
+  // g = B^{-1} b, pcol = B^{-1} q_{e-1}, column r_sup of B^{-1} (symmetric: its row)
+  double g[M], pc[M], br[M];
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    g[i] = elem_sym_row_apply<M>(tri, i, bb);
+    pc[i] = elem_sym_row_apply<M>(tri, i, qm);
+    br[i] = 0.0;
+    cur[i * S + x] = uu[i];
+  }
+  auto sym_col = [&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+#pragma unroll
+    for (int i = 0; i < M; ++i) br[i] = tri[i < j ? elem_tri<M>(i, j) : elem_tri<M>(j, i)];
+  };
+  switch (a.lv.r_sup) {
+    case 0: sym_col(std::integral_constant<int, 0>()); break;
+    case 1: sym_col(std::integral_constant<int, 1>()); break;
+    case 2: sym_col(std::integral_constant<int, 2>()); break;
+    case 3: sym_col(std::integral_constant<int, 3>()); break;
+  }
+  __syncthreads();
+
+  // ---- block-Jacobi sweeps, LDS ping-pong: u + w (g - pcol u-[c_sub] - B^{-1}[:, r_sup] (q . u+) - u); the last
+  // pre-sweep leaves u + L uc ------------------------------------------------------------------------------------------
+  // (the sweep is written once and placed three times -- the pre-sweeps but the last, the last one, the post-sweeps -- so
+  // that the sweeps that add nothing carry no select for it: a conditional add per row in one common loop cost the launch
+  // 7.12 instead of 5.51 vector instructions per element, profiles/r28_replay.md)
+  const int c_sub = a.lv.c_sub;
+  auto sweep = [&](int sw, auto add_luc) {
+    const double um = cur[c_sub * S + x - 1];
+    double up[M];
+#pragma unroll
+    for (int j = 0; j < M; ++j) up[j] = cur[j * S + x + 1];
+    double dlo, dhi;
+    elem_group_dot4(q, up, dlo, dhi);
+    const double w = wts.w[(unsigned)sw];
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      double acc = __fma_rn(-pc[i], um, g[i]);
+      acc = __fma_rn(-br[i], i < 2 ? dlo : dhi, acc);
+      double un = __fma_rn(w, __dadd_rn(acc, -uu[i]), uu[i]);
+      if constexpr (decltype(add_luc)::value) un = __dadd_rn(un, luc[i]);
+      if (!valid) un = 0.0;
+      uu[i] = un;
+      nxt[i * S + x] = un;
+    }
+    __syncthreads();
+    double* t = cur;
+    cur = nxt;
+    nxt = t;
+  };
+  for (int sw = 0; sw < npre - 1; ++sw) sweep(sw, std::false_type());
+  sweep(npre - 1, std::true_type());
+  for (int sw = npre; sw < a.nsweeps; ++sw) sweep(sw, std::false_type());
+
+  // ---- the iterate of the owned elements -------------------------------------------------------------------------
+  if (own) {
+    double* const op = a.u_out + e0 * M + (unsigned)(x * M);
+#pragma unroll
+    for (int j = 0; j < M; j += 2) {
+      elem_v2d v;
+      v.x = uu[j];
+      v.y = uu[j + 1];
+#if AGGMG_NT & 2
+      __builtin_nontemporal_store(v, reinterpret_cast<elem_v2d*>(op + j));
+#else
+      *reinterpret_cast<elem_v2d*>(op + j) = v;
+#endif
+    }
+  }
+}
+
 }  // namespace aggmg

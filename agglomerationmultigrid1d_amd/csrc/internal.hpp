@@ -75,6 +75,8 @@ struct aggmg_ctx {
   int64_t elem_launches = 0;   // launches of the element-thread kernel so far (aggmg_element_thread_launches)
   bool pair_elem_threads = [] { const char* e = std::getenv("AGGMG_PAIR_ELEM_THREADS"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_PAIR_ELEMENT_THREADS
   int64_t pair_elem_launches = 0;   // launches of the element-thread pair kernels so far (aggmg_pair_element_thread_launches)
+  bool replay_presmooth = [] { const char* e = std::getenv("AGGMG_REPLAY_PRESMOOTH"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_REPLAY_PRESMOOTH
+  int64_t replay_launches = 0;   // replayed cycles so far (aggmg_replay_launches)
   int profiling = 0;  // 0 off, 1 every launch, 2 only the fine-level fused-down launch (dominant kernel)
   std::vector<ProfEvent> prof;
   std::vector<hipEvent_t> ev_pool;
@@ -329,12 +331,14 @@ struct Level {
   bool native_io = false;           // rhs and u[1] are kept in block order (the finer level is a fused chain level)
   int64_t Nalloc = 0;               // length of the level's vectors (ne * m for chain levels)
   // sweep-weight schedule (aggmg_hier_set_sweep_weights), or scheduled == false: the entry point's alpha.  w_mid = w_post
-  // ++ w_pre, the launch between two cycles (post-smoothing of one, pre-smoothing of the next)
+  // ++ w_pre, the launch between two cycles (post-smoothing of one, pre-smoothing of the next); w_replay = w_pre ++ w_post,
+  // the ascent that replays the pre-smoothing (AGGMG_OPT_REPLAY_PRESMOOTH)
   bool scheduled = false;
-  std::vector<double> w_pre, w_post, w_mid;
+  std::vector<double> w_pre, w_post, w_mid, w_replay;
   Damping damp_pre(double alpha) const { return scheduled ? Damping(alpha, w_pre.data()) : Damping(alpha); }
   Damping damp_post(double alpha) const { return scheduled ? Damping(alpha, w_post.data()) : Damping(alpha); }
   Damping damp_mid(double alpha) const { return scheduled ? Damping(alpha, w_mid.data()) : Damping(alpha); }
+  Damping damp_replay(double alpha) const { return scheduled ? Damping(alpha, w_replay.data()) : Damping(alpha); }
 };
 
 struct BandedLU {
@@ -430,6 +434,12 @@ struct aggmg_hier {
   DevArray<double> crw_stage;
   int64_t crw_stage_cols = 0;
   int restriction = 0;  // AGGMG_RESTRICT_EXPLICIT (default) / AGGMG_RESTRICT_PRECONDITIONED
+  // The replayed cycle (AGGMG_OPT_REPLAY_PRESMOOTH) leaves no pre-smoothed iterate in lv[0].u[0], and one caller can see
+  // that: an ascent of its own (aggmg_vcycle_up_dev, aggmg_vcycle_up_split_dev) after a whole aggmg_vcycle_dev reads the
+  // iterate that cycle's descent stored.  So a hierarchy on which a half-cycle entry point has been called keeps storing
+  // (halves_used, for good), and an ascent on its own after a replayed cycle is refused instead of reading what is not
+  // there (fine_iterate_absent: set by a replayed cycle, cleared by every descent that stores).
+  bool halves_used = false, fine_iterate_absent = false;
   std::vector<double> h_coarse;
   double last_coarse_ms = 0.0;
   double cr_probe_backward_error = -1.0;  // ||d - A CR(d)|| / ||d|| of the set-up probe (-1: no device factorisation tried)

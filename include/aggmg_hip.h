@@ -147,11 +147,30 @@ int aggmg_synchronize(aggmg_ctx* ctx);
  * a dictionary and the partitioned cycle's tile selections keep their kernels either way.
  * aggmg_pair_element_thread_launches counts the launches these kernels have served. */
 #define AGGMG_OPT_PAIR_ELEMENT_THREADS 9
+/* AGGMG_OPT_REPLAY_PRESMOOTH (default 1; environment AGGMG_REPLAY_PRESMOOTH=0 makes the default 0): in aggmg_vcycle_dev
+ * the fine level's descent does not store the pre-smoothed iterate -- a vector written only for the ascent to read back
+ * -- and the ascent rebuilds it: it reads x0 where it read the stored iterate (x0 == NULL: nothing), runs the nPre
+ * pre-sweeps itself, adds the prolongation and goes on with the nPost post-sweeps (btd_elem_replay_up_kernel; the same
+ * arithmetic on the same inputs in the same order, every result bit for bit the same).  A cycle replays when level 0 is
+ * a fused block-tridiagonal level whose descent and ascent both run the element-thread kernel
+ * (AGGMG_OPT_ELEMENT_THREADS and its conditions), nPre >= 1, nPost >= 1, nPre + nPost <= AGGMG_MAX_SWEEP_WEIGHTS, and
+ * the ranges [x0, x0 + N) and [x_out, x_out + N) are disjoint; every other cycle, and every other entry point
+ * (aggmg_vcycles_dev, aggmg_multigrid_dev, aggmg_vcycle_down_dev / _up_dev, the K-column and partitioned cycles), stores
+ * the iterate as before.  Read at every call.  After a replayed cycle the fine level's internal iterate vector holds
+ * nothing defined.  One call sequence reads that vector from an earlier call: an ascent on its own
+ * (aggmg_vcycle_up_dev, aggmg_vcycle_up_split_dev) after a whole aggmg_vcycle_dev.  Right after a replayed cycle such an
+ * ascent returns AGGMG_ERR_ARGUMENT (call aggmg_vcycle_down_dev first), and from the first call of a half-cycle entry
+ * point on (aggmg_vcycle_down_dev, _up_dev, _up_split_dev) the hierarchy's cycles store the iterate for good, so
+ * programs that compose halves and whole cycles see what they saw before.  aggmg_replay_launches counts the replayed cycles;
+ * the replaying ascent counts in aggmg_element_thread_launches like the launch it replaces. */
+#define AGGMG_OPT_REPLAY_PRESMOOTH 10
 int aggmg_set_option(aggmg_ctx* ctx, int option, int value);
 /* Launches of the element-thread kernel (AGGMG_OPT_ELEMENT_THREADS) on this context so far. */
 int aggmg_element_thread_launches(aggmg_ctx* ctx, int64_t* count);
 /* Launches of the element-thread two-level kernels (AGGMG_OPT_PAIR_ELEMENT_THREADS) on this context so far. */
 int aggmg_pair_element_thread_launches(aggmg_ctx* ctx, int64_t* count);
+/* Cycles of aggmg_vcycle_dev that replayed their pre-smoothing (AGGMG_OPT_REPLAY_PRESMOOTH) on this context so far. */
+int aggmg_replay_launches(aggmg_ctx* ctx, int64_t* count);
 /* Raw device memory owned by the context's device (plumbing for harnesses without torch, and the storage of the
  * Julia shim's DeviceVector).  aggmg_dev_alloc returns ZEROED memory: a fresh vector is the zero initial guess of
  * ldiv! (src/solvers.jl:66,87). */
@@ -875,6 +894,10 @@ int aggmg_multigrid_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, c
 #define AGGMG_KIND_BLOCK_APPLY 7 /* generic gather block apply */
 #define AGGMG_KIND_COARSE 8      /* device coarsest solve (all its launches) */
 #define AGGMG_KIND_FUSED_MID 9   /* prolong-add -> nPost + nPre sweeps -> restriction (between cycles) */
+/* aggmg_hier_launch_bytes only (no profile tag: the launches are timed as _FUSED_DOWN / _FUSED_UP): the two launches of
+ * a replayed cycle (AGGMG_OPT_REPLAY_PRESMOOTH) */
+#define AGGMG_KIND_REPLAY_DOWN 10 /* _FUSED_DOWN without the store of the pre-smoothed iterate */
+#define AGGMG_KIND_REPLAY_UP 11   /* [u=0|x0] -> nPre sweeps -> prolong-add -> nPost sweeps */
 /* on: 0 = off, 1 = every launch, 2 = only the fine-level fused-down launch (the dominant kernel:
  * one event pair per cycle, so that timing it does not disturb the cycle being timed -- an event pair
  * costs ~7 us of stream time on MI355X). */
@@ -887,6 +910,10 @@ int aggmg_profile_collect(aggmg_ctx* ctx, double* total_ms, int64_t* counts);
  * aggmg_hier_launch_bytes: the fused launch of `level` (not the coarsest) that aggmg_vcycle_dev enqueues, kind =
  * AGGMG_KIND_FUSED_DOWN (src/solvers.jl:28-37), _UP (:41-47) or _MID (both, between the cycles of aggmg_vcycles_dev);
  * has_x0: the descent reads an initial guess (level 0).  AGGMG_ERR_UNSUPPORTED on a level that runs the generic kernels.
+ * _FUSED_DOWN and _FUSED_UP describe the launches that STORE the pre-smoothed iterate and read it back; a cycle that
+ * replays its pre-smoothing (AGGMG_OPT_REPLAY_PRESMOOTH, the default of aggmg_vcycle_dev where it applies) runs
+ * AGGMG_KIND_REPLAY_DOWN -- the same without that store -- and AGGMG_KIND_REPLAY_UP, which reads the first iterate in
+ * the stored one's place (has_x0 = 0: no iterate at all).
  * aggmg_smoother_launch_bytes: what = 0 one launch of aggmg_smooth_dev (any number of sweeps that fit one launch),
  * what = 1 aggmg_residual_dev (sm may be NULL). */
 int aggmg_hier_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int level, int kind, int has_x0, int64_t* read_bytes,

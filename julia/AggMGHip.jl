@@ -297,6 +297,15 @@ function pair_element_thread_launches(ctx::Context)
     check(ctx.h, ccall((:aggmg_pair_element_thread_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
     return r[]
 end
+# AGGMG_OPT_REPLAY_PRESMOOTH (default 1; environment AGGMG_REPLAY_PRESMOOTH=0 makes the default 0): a V-cycle whose fine
+# level runs the element-thread kernel does not store the pre-smoothed iterate; its ascent reads the first iterate and
+# runs the pre-sweeps again -- the same bits, a vector less written.  replay_launches(ctx): how many cycles replayed.
+const OPT_REPLAY_PRESMOOTH = 10
+function replay_launches(ctx::Context)
+    r = Ref{Int64}(0)
+    check(ctx.h, ccall((:aggmg_replay_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
+    return r[]
+end
 function set_option!(ctx::Context, option::Integer, value::Integer)
     check(ctx.h, ccall((:aggmg_set_option, LIB), Cint, (Handle, Cint, Cint), ctx.h, option, value))
     return ctx

@@ -45,7 +45,8 @@ def period(seq, windows=5):
 
 def roles_of(window):
     """window: list of short kernel names of one cycle"""
-    # (btd_elem_dict_kernel, r26: the element-thread form of a fused launch -- the same roles)
+    # (btd_elem_dict_kernel, r26: the element-thread form of a fused launch -- the same roles; btd_elem_replay_up_kernel,
+    # r28: the fine ascent that replays the pre-smoothing, after the coarsest solve like the launch it replaces: fused_up_L0)
     fused = [i for i, k in enumerate(window) if "fused_kernel" in k or "btd_pair_" in k or "btd_elem_" in k]
     coarse = [i for i, k in enumerate(window) if "cr_" in k]
     first_c = coarse[0] if coarse else len(window)
