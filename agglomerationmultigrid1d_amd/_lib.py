@@ -24,6 +24,7 @@ OPT_OPERATOR_DICTIONARY = 7
 OPT_ELEMENT_THREADS = 8
 OPT_PAIR_ELEMENT_THREADS = 9
 OPT_REPLAY_PRESMOOTH = 10
+OPT_PATCH_MULTI = 11
 PROFILE_NTAGS = 256
 KIND_FUSED_DOWN, KIND_FUSED_UP, KIND_SMOOTH, KIND_RESIDUAL, KIND_RESTRICT, KIND_PROLONG, \
     KIND_JACOBI, KIND_BLOCK_APPLY, KIND_COARSE, KIND_FUSED_MID = range(10)
@@ -96,6 +97,7 @@ SYMBOLS = {
     "aggmg_element_thread_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_pair_element_thread_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_replay_launches": (c_int, [_P, POINTER(c_int64)]),
+    "aggmg_patch_multi_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_dev_alloc": (c_int, [_P, c_int64, POINTER(_P)]),
     "aggmg_dev_free": (c_int, [_P, _P]),
     "aggmg_memcpy_h2d": (c_int, [_P, _P, _P, c_int64]),
@@ -125,6 +127,8 @@ SYMBOLS = {
     "aggmg_patch_gs_setup": (c_int, [_P, _P, c_int64, c_int64, POINTER(_P)]),
     "aggmg_smoother_patch_kind": (c_int, [_P, _P, POINTER(c_int)]),
     "aggmg_patch_gs_tile_plan": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "aggmg_patch_gs_multi_tile_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                               POINTER(c_int)]),
     "aggmg_jacobi_setup": (c_int, [_P, _P, POINTER(_P)]),
     "aggmg_jacobi_setup_elements": (c_int, [_P, _P, c_int64, c_int64, POINTER(c_int64), c_int, POINTER(_P)]),
     "aggmg_smoother_free": (c_int, [_P, _P]),
@@ -136,6 +140,7 @@ SYMBOLS = {
     "aggmg_prolong_add": (c_int, [_P, _P, _PD, _PD]),
     "aggmg_smooth_dev": (c_int, [_P, _P, _P, _P, _P, c_double, c_int, _P]),
     "aggmg_smooth_weighted_dev": (c_int, [_P, _P, _P, _P, _P, _PD, c_int, _P]),
+    "aggmg_smooth_multi_dev": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, _PD, c_int, c_int, _P]),
     "aggmg_residual_dev": (c_int, [_P, _P, _P, _P, _P]),
     "aggmg_restrict_dev": (c_int, [_P, _P, _P, _P]),
     "aggmg_prolong_add_dev": (c_int, [_P, _P, _P, _P]),

@@ -107,6 +107,13 @@ class Context:
         self.check(self.lib.aggmg_replay_launches(self.handle, ctypes.byref(n)))
         return int(n.value)
 
+    def patch_multi_launches(self):
+        """launches of the K-column multiplicative patch sweep kernel on this context so far (C ABI
+        aggmg_patch_multi_launches; ElementPatchGaussSeidel.sweeps_multi_dev, AGGMG_OPT_PATCH_MULTI)"""
+        n = ctypes.c_int64(0)
+        self.check(self.lib.aggmg_patch_multi_launches(self.handle, ctypes.byref(n)))
+        return int(n.value)
+
     def option(self, option, default):
         """the value last given to set_option (the C ABI has no getter), `default` when it never was set"""
         return self.__dict__.get("_options", {}).get(int(option), default)
@@ -689,6 +696,26 @@ class ElementPatchGaussSeidel(AbstractSmoother):
         """the explicit inverses of the patch blocks, (ne - 1, 2 m, 2 m) (C ABI aggmg_smoother_download_blocks)"""
         bm, nb = self.mBlockInds.shape
         return _download_blocks(self.A.ctx, self.handle, nb, bm)
+
+    def sweeps_multi_dev(self, U0, B, U, weights, reverse=False, ncols=None, ld=None):
+        """len(weights) sweeps on K columns in one pass over the operator per column group (C ABI aggmg_smooth_multi_dev;
+        EXTENSION): U0 (None: the zero iterate), B, U are DeviceMatrix / column-major device buffers with leading
+        dimension ld (default N); sweep s is damped by weights[s]; reverse: the colour order of post-smoothing.  Column j
+        of U is bit for bit the single-column sweeps of column j.  UnsupportedError for element blocks outside the
+        kernel's coverage (compressed couplings with 2 or 4 rows, dense ones with 2).  Asynchronous on the context
+        stream."""
+        N = self.m * self.ne
+        if ncols is None:
+            ncols = B.k if isinstance(B, DeviceMatrix) else None
+        if ncols is None:
+            raise ArgumentError("sweeps_multi_dev: ncols is needed for raw device pointers")
+        if ld is None:
+            ld = N
+        w = np.ascontiguousarray(np.atleast_1d(weights), dtype=np.float64)
+        c = self.A.ctx
+        c.check(c.lib.aggmg_smooth_multi_dev(c.handle, self.A.handle, self.handle, _ptr(U0), _ptr(B), int(ncols), int(ld),
+                                             w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(w.size), 1 if reverse else 0,
+                                             _ptr(U)))
 
 
 class _BlockObject(AbstractSmoother):

@@ -10,6 +10,7 @@
 #include "multi_solve_kernels.hpp"
 #include "pair_kernels.hpp"
 #include "patch_kernels.hpp"
+#include "patch_multi_kernels.hpp"
 #include "elem_kernels.hpp"
 #include "pair_elem_kernels.hpp"
 #include "krylov_kernels.hpp"
@@ -179,6 +180,9 @@ extern "C" int aggmg_set_option(aggmg_ctx* ctx, int option, int value) {
       return AGGMG_OK;
     case AGGMG_OPT_REPLAY_PRESMOOTH:
       ctx->replay_presmooth = value != 0;
+      return AGGMG_OK;
+    case AGGMG_OPT_PATCH_MULTI:
+      ctx->patch_multi = value != 0;
       return AGGMG_OK;
   }
   return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_set_option: unknown option");
@@ -1063,6 +1067,106 @@ static int patch_smooth(aggmg_ctx* ctx, const PatchDev& P, const double* u_in, c
   return AGGMG_OK;
 }
 
+// ---- the multiplicative sweeps on K columns (patch_multi_kernels.hpp) ---------------------------------
+// the element-block forms patch_gs_multi_kernel is instantiated for: those of the K-column transfer kernel (launch_multi)
+static bool patch_multi_form_ok(const PatchDev& P) {
+  return P.multiplicative && P.btd && (P.btd->cmp ? (P.m == 2 || P.m == 4) : P.m == 2);
+}
+// the smallest instantiated column group that holds kc columns
+static int patch_multi_group(int kc) { return kc <= 1 ? 1 : (kc <= 2 ? 2 : (kc <= 4 ? 4 : 8)); }
+
+template <int M, bool CMP>
+static int launch_patch_gs_multi_t(aggmg_ctx* ctx, PatchGsMultiArgs m, const SweepWeights& wts, const uint16_t* cls) {
+  PatchArgs& a = m.g.p;
+  const int kb = patch_multi_group(m.kc);
+  const PatchTilePlan plan = patch_gs_multi_tile_plan(M, a.nsweeps, kb);   // host_plan.hpp
+  if (plan.owned <= 0 || m.kc < 1 || m.kc > kb)
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column multiplicative patch sweep launch without a tile");
+  a.owned = plan.owned;
+  a.halo = plan.halo;
+  const int64_t ntiles = patch_tiles(a.ne, plan.owned);
+  if (ntiles == 0) return AGGMG_OK;
+  auto go = [&](auto plain, auto dict) {
+    if (cls)
+      hipLaunchKernelGGL(dict, dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, m, wts, cls);
+    else
+      hipLaunchKernelGGL(plain, dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, m, wts, cls);
+  };
+  switch (kb) {
+    case 1: go(patch_gs_multi_kernel<M, CMP, 1, false>, patch_gs_multi_kernel<M, CMP, 1, true>); break;
+    case 2: go(patch_gs_multi_kernel<M, CMP, 2, false>, patch_gs_multi_kernel<M, CMP, 2, true>); break;
+    case 4: go(patch_gs_multi_kernel<M, CMP, 4, false>, patch_gs_multi_kernel<M, CMP, 4, true>); break;
+    default: go(patch_gs_multi_kernel<M, CMP, 8, false>, patch_gs_multi_kernel<M, CMP, 8, true>); break;
+  }
+  HIPCHK(hipGetLastError());
+  ++ctx->patch_multi_launches;
+  return AGGMG_OK;
+}
+
+static int launch_patch_gs_multi(aggmg_ctx* ctx, const PatchDev& P, const PatchGsMultiArgs& m, const SweepWeights& wts,
+                                 const uint16_t* cls) {
+  if (patch_multi_form_ok(P)) {
+    if (P.btd->cmp && P.m == 4) return launch_patch_gs_multi_t<4, true>(ctx, m, wts, cls);
+    if (P.btd->cmp && P.m == 2) return launch_patch_gs_multi_t<2, true>(ctx, m, wts, cls);
+    if (!P.btd->cmp && P.m == 2) return launch_patch_gs_multi_t<2, false>(ctx, m, wts, cls);
+  }
+  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: block size not instantiated for the K-column multiplicative patch sweep kernel");
+}
+
+// One column-major vector of a K-column run: column 0 and the doubles between two columns.
+struct ColsPtr {
+  double* p = nullptr;
+  int64_t ld = 0;
+};
+// nsweeps >= 1 sweeps on kc <= 8 columns from U0 (p null: zero) into U, in launches of up to patch_gs_multi_max_sweeps, each
+// with its slice of the weights, as patch_smooth chunks a single column's run.  A chunked run alternates between U and
+// `other` (kc columns, neither U0 nor U; p null: leased from the context's scratch) so that the last launch writes U.
+static int patch_smooth_multi(aggmg_ctx* ctx, const PatchDev& P, const double* U0, int64_t ld_u0, const double* B, int64_t ld_b,
+                              Damping alpha, int nsweeps, bool reverse, ColsPtr U, ColsPtr other, int kc, int level) {
+  const int64_t N = P.ne * P.m;
+  const int smax = patch_gs_multi_max_sweeps(P.m);
+  const int nchunks = patch_chunks(nsweeps, smax);
+  if (nchunks == 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column patch sweeps without a tile");
+  WorkLease t0;
+  if (nchunks > 1 && !other.p) {
+    CHECK(scratch_lease(ctx, kScratchPing, N * kc, "patch_smooth_multi", &t0));
+    other.p = t0.get();
+    other.ld = N;
+  }
+  const BtdDev& b = *P.btd;
+  const double* src = U0;
+  int64_t ld_src = ld_u0;
+  for (int c = 0; c < nchunks; ++c) {
+    const int s = patch_chunk_sweeps(nsweeps, smax, c);
+    const ColsPtr dst = ((nchunks - 1 - c) % 2 == 0) ? U : other;
+    PatchGsMultiArgs m;
+    std::memset(&m, 0, sizeof(m));
+    m.g.p = PatchArgs{b.dblk, b.scol, b.qrow, b.sub, b.sup, P.zrows, P.ne, b.c_sub, b.r_sup, src, B, dst.p, s, 0, 0};
+    m.g.reverse = reverse ? 1 : 0;
+    m.ld_uin = ld_src;
+    m.ld_b = ld_b;
+    m.ld_uout = dst.ld;
+    m.kc = kc;
+    // the smoother's operator dictionary in place of the full arrays, as patch_smooth takes it
+    const PatchDictDev* d = P.dict.get();
+    if (d) {
+      m.g.p.dblk = d->dblk;
+      m.g.p.scol = d->scol;
+      m.g.p.qrow = d->qrow;
+      m.g.p.sub = d->sub;
+      m.g.p.sup = d->sup;
+      m.g.p.zrows = d->zrows;
+    }
+    {
+      ProfScope ps(ctx, AGGMG_KIND_SMOOTH, level);
+      CHECK(launch_patch_gs_multi(ctx, P, m, alpha.from(c * smax).launch(s), d ? d->cls.get() : nullptr));
+    }
+    src = dst.p;
+    ld_src = dst.ld;
+  }
+  return AGGMG_OK;
+}
+
 // index lists of the patches {e, .., e + width - 1}, e = 0 .. ne - width (a level of fewer elements: one patch of all)
 static void patch_lists(int64_t m, int64_t ne, int width, std::vector<int64_t>* lists, int64_t* bm, int64_t* nb) {
   const int64_t w = std::min<int64_t>(width, ne);
@@ -1220,6 +1324,22 @@ extern "C" int aggmg_patch_gs_tile_plan(int m, int nsweeps, int* tile_elems, int
   *owned = p.owned;
   *halo = p.halo;
   *max_sweeps = patch_gs_max_sweeps(m);
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_patch_gs_multi_tile_plan(int m, int nsweeps, int kb, int* tile_elems, int* owned, int* halo, int* max_sweeps) {
+  if (!tile_elems || !owned || !halo || !max_sweeps) return AGGMG_ERR_ARGUMENT;
+  const PatchTilePlan p = patch_gs_multi_tile_plan(m, nsweeps, kb);   // host_plan.hpp: what launch_patch_gs_multi_t runs
+  *tile_elems = p.te;
+  *owned = p.owned;
+  *halo = p.halo;
+  *max_sweeps = patch_gs_multi_max_sweeps(m);
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_patch_multi_launches(aggmg_ctx* ctx, int64_t* count) {
+  if (!ctx || !count) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_patch_multi_launches: NULL argument");
+  *count = ctx->patch_multi_launches;
   return AGGMG_OK;
 }
 
@@ -2945,7 +3065,8 @@ extern "C" int aggmg_vcycle_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0,
 // on the way down and one on the way up (no two-level launches here), and the coarsest solve one launch sequence per
 // group (cr_solve).  A hierarchy with a level outside the kernel's coverage runs the single-column cycle on every
 // column instead (a one-level hierarchy, whose cycle is the coarsest solve alone, still in groups): the same bits either
-// way (multi_kernels.hpp), aggmg_hier_multi_info says which.
+// way (multi_kernels.hpp), aggmg_hier_multi_info says which.  Under AGGMG_OPT_PATCH_MULTI a multiplicative element-patch
+// level runs in groups too: the K-column sweeps (patch_multi_kernels.hpp) between zero-sweep btd_multi_kernel launches.
 #ifndef AGGMG_MULTI_KB
 #define AGGMG_MULTI_KB 8
 #endif
@@ -2955,8 +3076,39 @@ extern "C" int aggmg_vcycle_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0,
 constexpr int kMultiKB = AGGMG_MULTI_KB, kMultiNT = AGGMG_MULTI_NT;
 static_assert(kMultiKB == 1 || kMultiKB == 2 || kMultiKB == 4 || kMultiKB == 8, "column groups of 1, 2, 4 or 8");
 
-static bool multi_level_ok(const aggmg_hier* h, int k, int nPre, int nPost) {
+// A multiplicative patch level in column groups (AGGMG_OPT_PATCH_MULTI): the K-column sweeps (patch_gs_multi_kernel) and,
+// around them, the zero-sweep launches of the K-column transfer kernel on the smoother's element-block form -- where the
+// single-column cycle runs its zero-sweep fused launches (patch_transfer_ok), whose bits those repeat.
+static bool multi_patch_level_ok(const aggmg_hier* h, int k, int nPre, int nPost) {
   const Level& l = h->lv[k];
+  const PatchDev& P = *l.S->patch;
+  if (!patch_multi_form_ok(P) || !l.tb) return false;
+  const TransferBtd& t = *l.tb;
+  if (t.mc != 2 || t.rho <= 0 || P.ne != (int64_t)t.rho * t.nec) return false;
+  if (!patch_transfer_ok(l, 1, &t) || !patch_transfer_ok(l, 0, nullptr)) return false;
+  TileQuery down, up;
+  down.launch = up.launch = kTileMulti;
+  down.te = up.te = kMultiNT / P.m;
+  down.halo = 1;
+  down.align = t.rho;
+  up.halo = 0;
+  if (!launch_has_tile(down) || !launch_has_tile(up)) return false;
+  // every chunk of the two runs of sweeps under the K-column plan
+  const int smax = patch_gs_multi_max_sweeps(P.m);
+  for (int n : {nPre, nPost})
+    for (int c = 0; c < patch_chunks(n, smax); ++c) {
+      TileQuery q;
+      q.launch = kTilePatchGsMulti;
+      q.te = patch_gs_multi_tile_elems(P.m);
+      q.halo = patch_chunk_sweeps(n, smax, c);
+      if (!launch_has_tile(q)) return false;
+    }
+  return (nPre == 0 && nPost == 0) || smax >= 1;
+}
+
+static bool multi_level_ok(const aggmg_hier* h, int k, int nPre, int nPost, bool patch_multi) {
+  const Level& l = h->lv[k];
+  if (patch_multi && level_path(h, k) == LevelPath::Patch) return multi_patch_level_ok(h, k, nPre, nPost);
   if (level_path(h, k) != LevelPath::FusedBtd || l.S->gs) return false;
   const BtdDev& b = *l.S->btd;
   const TransferBtd& t = *l.tb;
@@ -2975,11 +3127,11 @@ static bool multi_level_ok(const aggmg_hier* h, int k, int nPre, int nPost) {
   return launch_has_tile(down) && launch_has_tile(up);
 }
 
-static bool multi_ok(const aggmg_hier* h, int nPre, int nPost) {
+static bool multi_ok(const aggmg_ctx* ctx, const aggmg_hier* h, int nPre, int nPost) {
   const int n = (int)h->lv.size();
   if (n < 2 || h->coarse_mode == AGGMG_COARSE_EXTERNAL) return false;
   for (int k = 0; k < n - 1; ++k)
-    if (!multi_level_ok(h, k, nPre, nPost)) return false;
+    if (!multi_level_ok(h, k, nPre, nPost, ctx->patch_multi)) return false;
   return true;
 }
 
@@ -3029,14 +3181,71 @@ static int multi_workspace(aggmg_ctx* ctx, aggmg_hier* h, int64_t cols) {
   h->mu.resize(n);
   for (int k = 0; k < n; ++k) {
     const bool coarsest = k == n - 1;
-    for (int s = 0; s < 3; ++s) {
+    for (int s = 0; s < 4; ++s) {
       if (s == 1 && (k == 0 || coarsest)) continue;   // the ascent's output: the caller's X at level 0, none at the coarsest
       if (s == 2 && k == 0) continue;                 // level 0's right-hand side is the caller's B
+      if (s == 3 && level_path(h, k) != LevelPath::Patch) continue;   // a patch level's prolonged iterate / second sweep vector
       CHECK(h->mu[k][s].alloc(ctx, h->lv[k].N * cols));
     }
   }
   h->multi_cols = cols;
   return AGGMG_OK;
+}
+
+// A multiplicative patch level of the K-column cycle (multi_patch_level_ok), the launches of patch_down / patch_up for kc
+// columns each.  Descent: the pre sweeps from U0 (null: zero; none at nPre == 0) into mu[k][0], then the zero-sweep K-column
+// launch on the smoother's element blocks -- explicit residual and its restriction into the next level's right-hand
+// sides (always the explicit residual, as patch_down).
+static int multi_patch_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* U0, const double* B, int64_t ld_b, int nPre,
+                            double alpha, int kc) {
+  Level& l = h->lv[k];
+  Level& c = h->lv[k + 1];
+  const PatchDev& P = *l.S->patch;
+  const int64_t ld_u0 = k == 0 ? ld_b : l.N;   // (level 0: the caller's X0 and B share a leading dimension)
+  if (nPre > 0)
+    CHECK(patch_smooth_multi(ctx, P, U0, ld_u0, B, ld_b, l.damp_pre(alpha), nPre, false, ColsPtr{h->mu[k][0].get(), l.N},
+                             ColsPtr{h->mu[k][3].get(), l.N}, kc, k));
+  MultiArgs m;
+  std::memset(&m, 0, sizeof(m));
+  // (no sweep: the launch also copies the iterate the ascent starts from)
+  const FusedLaunch f = nPre > 0 ? fused_sweeps(*P.btd, h->mu[k][0], B, nullptr, 0.0, 0) : fused_sweeps(*P.btd, U0, B, h->mu[k][0], 0.0, 0);
+  m.a = f;
+  fused_descent(m.a, h, l, h->mu[k + 1][2]);
+  m.a.ld_out = nullptr;   // the explicit residual's restriction, as patch_down
+  m.a.lf_out = l.tb->lf;
+  m.kc = kc;
+  m.ld_uin = nPre > 0 ? l.N : ld_u0;
+  m.ld_b = ld_b;
+  m.ld_uout = l.N;
+  m.ld_rc = c.N;
+  ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
+  return launch_multi(ctx, *P.btd, m, f.wts, 1);
+}
+// Ascent: the zero-sweep K-column prolong-add of mu[k][0] into the scratch vector mu[k][3], then the reverse sweeps into
+// dst (mu[k][0], read for the last time by the prolongation, is the second vector of a chunked run); no sweep: the
+// prolonged iterate goes to dst at once.
+static int multi_patch_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uc, const double* B, int64_t ld_b, int nPost,
+                          double alpha, ColsPtr dst, int kc) {
+  Level& l = h->lv[k];
+  Level& c = h->lv[k + 1];
+  const PatchDev& P = *l.S->patch;
+  const ColsPtr mid = nPost > 0 ? ColsPtr{h->mu[k][3].get(), l.N} : dst;
+  {
+    MultiArgs m;
+    std::memset(&m, 0, sizeof(m));
+    const FusedLaunch f = fused_sweeps(*P.btd, h->mu[k][0], B, mid.p, 0.0, 0);
+    m.a = f;
+    fused_ascent(m.a, l, uc);
+    m.kc = kc;
+    m.ld_uin = l.N;
+    m.ld_b = ld_b;
+    m.ld_uout = mid.ld;
+    m.ld_uc = c.N;
+    ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
+    CHECK(launch_multi(ctx, *P.btd, m, f.wts, 0));
+  }
+  if (nPost == 0) return AGGMG_OK;
+  return patch_smooth_multi(ctx, P, mid.p, mid.ld, B, ld_b, l.damp_post(alpha), nPost, true, dst, ColsPtr{h->mu[k][0].get(), l.N}, kc, k);
 }
 
 // columns [c0, c0 + kc) of a K-column cycle whose every non-coarsest level multi_level_ok accepts
@@ -3046,6 +3255,10 @@ static int vcycle_multi_group(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, c
   for (int k = 0; k < n - 1; ++k) {   // descent (src/solvers.jl:28-37)
     Level& l = h->lv[k];
     Level& c = h->lv[k + 1];
+    if (level_path(h, k) == LevelPath::Patch) {
+      CHECK(multi_patch_down(ctx, h, k, k == 0 ? X0 : nullptr, k == 0 ? B : h->mu[k][2], k == 0 ? ld : l.N, nPre, alpha, kc));
+      continue;
+    }
     MultiArgs m;
     std::memset(&m, 0, sizeof(m));
     // u[k] = zeros for k > 1 (:29-31)
@@ -3067,6 +3280,12 @@ static int vcycle_multi_group(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, c
   for (int k = n - 2; k >= 0; --k) {   // ascent (:41-47)
     Level& l = h->lv[k];
     Level& c = h->lv[k + 1];
+    if (level_path(h, k) == LevelPath::Patch) {
+      const double* uc = (k + 1 == n - 1) ? h->mu[k + 1][0] : h->mu[k + 1][1];
+      CHECK(multi_patch_up(ctx, h, k, uc, k == 0 ? B : h->mu[k][2], k == 0 ? ld : l.N, nPost, alpha,
+                           ColsPtr{k == 0 ? X : h->mu[k][1].get(), k == 0 ? ld : l.N}, kc));
+      continue;
+    }
     MultiArgs m;
     std::memset(&m, 0, sizeof(m));
     const FusedLaunch f = fused_sweeps(*l.S->btd, h->mu[k][0], k == 0 ? B : h->mu[k][2], k == 0 ? X : h->mu[k][1], l.damp_post(alpha), nPost);
@@ -3128,7 +3347,7 @@ extern "C" int aggmg_vcycle_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const doubl
   if (h->coarse_mode == AGGMG_COARSE_EXTERNAL)
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: hierarchy was created with AGGMG_COARSE_EXTERNAL");
   if (h->lv.size() == 1) return coarse_solve_cols(ctx, h, B, ncols, ld, X);   // the cycle is the coarsest solve (:39)
-  if (!multi_ok(h, nPre, nPost)) {   // column by column: the single-column cycle on every column slice
+  if (!multi_ok(ctx, h, nPre, nPost)) {   // column by column: the single-column cycle on every column slice
     for (int64_t j = 0; j < ncols; ++j)
       CHECK(aggmg_vcycle_dev(ctx, h, X0 ? X0 + j * ld : nullptr, B + j * ld, nPre, nPost, alpha, X + j * ld));
     return AGGMG_OK;
@@ -3150,9 +3369,51 @@ extern "C" int aggmg_hier_multi_info(aggmg_ctx* ctx, const aggmg_hier* h, int64_
   if (!h || !fused || !group) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_info: NULL argument");
   if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_info: ncols must be >= 1");
   if (nPre < 0 || nPost < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_info: negative sweep count");
-  const bool f = multi_ok(h, nPre, nPost);
+  const bool f = multi_ok(ctx, h, nPre, nPost);
   *fused = f ? 1 : 0;
   *group = f ? (int)std::min<int64_t>(ncols, kMultiKB) : 1;
+  return AGGMG_OK;
+}
+
+// EXTENSION: sweeps of a fused multiplicative patch smoother on ncols columns, in the cycle's column groups
+extern "C" int aggmg_smooth_multi_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* U0, const double* B,
+                                      int64_t ncols, int64_t ld, const double* weights, int nsweeps, int reverse, double* U) {
+  CHECK(check_pair(ctx, A, sm, "aggmg_smooth_multi_dev"));
+  if (!B || !U) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: NULL argument");
+  if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: ncols must be >= 1");
+  if (nsweeps < 0 || (nsweeps > 0 && !weights)) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: negative sweep count or no weights");
+  for (int s = 0; s < nsweeps; ++s)
+    if (!std::isfinite(weights[s])) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: weight is not finite");
+  const int64_t N = A->m;
+  if (ld < N) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: ld must be >= N (" + std::to_string(N) + ")");
+  const int64_t span = (ncols - 1) * ld + N;
+  if (ranges_overlap(U, span, U0, span) || ranges_overlap(U, span, B, span))
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: U must not overlap U0 or B");
+  if (sm->patch && sm->A != A) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: the smoother was set up on another operator");
+  if (!sm->patch)
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_smooth_multi_dev: the smoother is not a fused element-patch smoother (K-column sweeps "
+                                            "exist for the multiplicative patch smoother of aggmg_patch_gs_setup)");
+  const PatchDev& P = *sm->patch;
+  if (!P.multiplicative)
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_smooth_multi_dev: the smoother is an additive / hybrid patch smoother, not the multiplicative one");
+  if (!patch_multi_form_ok(P))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED,
+                "aggmg_smooth_multi_dev: the K-column sweep kernel is not instantiated for " + std::to_string(P.m) + " rows per element with " +
+                    (P.btd->cmp ? "compressed" : "dense") + " couplings (compressed: 2 or 4, dense: 2)");
+  if (N == 0) return AGGMG_OK;
+  if (nsweeps == 0) {   // the iterate as it is
+    if (U0)
+      HIPCHK(hipMemcpy2DAsync(U, ld * sizeof(double), U0, ld * sizeof(double), N * sizeof(double), (size_t)ncols, hipMemcpyDeviceToDevice, ctx->stream));
+    else
+      HIPCHK(hipMemset2DAsync(U, ld * sizeof(double), 0, N * sizeof(double), (size_t)ncols, ctx->stream));
+    return AGGMG_OK;
+  }
+  const int64_t group = std::min<int64_t>(ncols, kMultiKB);
+  for (int64_t c0 = 0; c0 < ncols; c0 += group) {
+    const int kc = (int)std::min<int64_t>(group, ncols - c0);
+    CHECK(patch_smooth_multi(ctx, P, U0 ? U0 + c0 * ld : nullptr, ld, B + c0 * ld, ld, Damping(0.0, weights), nsweeps, reverse != 0,
+                             ColsPtr{U + c0 * ld, ld}, ColsPtr{}, kc, 0));
+  }
   return AGGMG_OK;
 }
 

@@ -375,11 +375,35 @@ inline int patch_gs_max_sweeps(int m, int threads = 256) {
   return s;
 }
 
+// ---- the same sweeps on K columns at once (patch_gs_multi_kernel, patch_multi_kernels.hpp) -----------------------------
+// One slab: a workgroup of `threads` threads holds threads / m elements, for the block sizes the K-column transfer kernel
+// covers (m = 2, 4), and kb = 1, 2, 4 or 8 columns of them.  Reach, halo and the most sweeps per launch follow the
+// single-column rules above (neither depends on kb).  LDS: per column an iterate plane, updated in place, and a residual
+// plane, each padded by one element a side -- 2 kb (te + 2) m doubles, 33 KiB at kb = 8: four workgroups per compute unit.
+inline int patch_gs_multi_tile_elems(int m, int threads = 256) { return (m == 2 || m == 4) ? threads / m : 0; }
+inline bool patch_gs_multi_group(int kb) { return kb == 1 || kb == 2 || kb == 4 || kb == 8; }
+inline PatchTilePlan patch_gs_multi_tile_plan(int m, int sweeps, int kb, int threads = 256) {
+  PatchTilePlan p;
+  p.te = patch_gs_multi_tile_elems(m, threads);
+  if (p.te <= 0 || !patch_gs_multi_group(kb) || sweeps < 1 || sweeps > kPatchMaxSweeps) return p;
+  p.halo = patch_gs_halo(sweeps);
+  p.owned = patch_gs_owned(p.te, sweeps);
+  p.lds_bytes = (size_t)2 * kb * (p.te + 2) * m * sizeof(double);
+  return p;
+}
+inline int patch_gs_multi_max_sweeps(int m, int threads = 256) {
+  const int te = patch_gs_multi_tile_elems(m, threads);
+  if (patch_gs_multi_tile_plan(m, 1, 1, threads).owned <= 0) return 0;
+  int s = 1;
+  while (s < kPatchMaxSweeps && 2 * patch_gs_owned(te, s + 1) >= te) ++s;
+  return s;
+}
+
 // ---- does a launch have a tile? ----------------------------------------------------------------------------------
 // One question for every tiled launch, answered by the planner its launcher runs: the callers that choose between a
 // launch and its fallback (two levels or one per launch, fused or unfused sequence, K columns or column by column) ask
 // here, so a launch that was chosen never finds "no tile".
-enum TileLaunch { kTileFused = 0, kTileMulti = 1, kTilePairDown = 2, kTilePairUp = 3, kTilePatch = 4, kTilePatchGs = 5 };
+enum TileLaunch { kTileFused = 0, kTileMulti = 1, kTilePairDown = 2, kTilePairUp = 3, kTilePatch = 4, kTilePatchGs = 5, kTilePatchGsMulti = 6 };
 struct TileQuery {
   int launch = kTileFused;
   int te = 0, te_b = 0;   // elements a workgroup holds (pairs: of level A and of level B)
@@ -398,6 +422,7 @@ inline bool launch_has_tile(const TileQuery& q) {
     case kTilePairUp: return pair_up_plan(q.halo, q.align, q.te, q.te_b).own > 0;
     case kTilePatch: return q.halo >= 1 && q.halo <= kPatchMaxSweeps && patch_owned(q.te, q.halo) > 0;
     case kTilePatchGs: return q.halo >= 1 && q.halo <= kPatchMaxSweeps && patch_gs_owned(q.te, q.halo) > 0;
+    case kTilePatchGsMulti: return q.halo >= 1 && q.halo <= kPatchMaxSweeps && patch_gs_owned(q.te, q.halo) > 0;   // te: patch_gs_multi_tile_elems
   }
   return false;
 }

@@ -77,6 +77,8 @@ struct aggmg_ctx {
   int64_t pair_elem_launches = 0;   // launches of the element-thread pair kernels so far (aggmg_pair_element_thread_launches)
   bool replay_presmooth = [] { const char* e = std::getenv("AGGMG_REPLAY_PRESMOOTH"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_REPLAY_PRESMOOTH
   int64_t replay_launches = 0;   // replayed cycles so far (aggmg_replay_launches)
+  bool patch_multi = [] { const char* e = std::getenv("AGGMG_PATCH_MULTI"); return e && e[0] == '1'; }();  // AGGMG_OPT_PATCH_MULTI (default 0)
+  int64_t patch_multi_launches = 0;   // launches of patch_gs_multi_kernel so far (aggmg_patch_multi_launches)
   int profiling = 0;  // 0 off, 1 every launch, 2 only the fine-level fused-down launch (dominant kernel)
   std::vector<ProfEvent> prof;
   std::vector<hipEvent_t> ev_pool;
@@ -423,8 +425,10 @@ struct aggmg_hier {
   DevArray<double> io[3];   // x0, b, x_out of the host-pointer entry aggmg_vcycle (lazy)
   // K-column cycles (aggmg_vcycle_multi_dev, lazy, grown to the largest column group asked for): per level, multi_cols
   // columns of the pre-smoothed iterate (mu[k][0]), the post-smoothed one (mu[k][1], levels 1 .. n-2) and the right-hand
-  // side (mu[k][2], levels >= 1); the coarsest level's solution goes to mu[n-1][0]
-  std::vector<std::array<DevArray<double>, 3>> mu;
+  // side (mu[k][2], levels >= 1); the coarsest level's solution goes to mu[n-1][0]; a multiplicative patch level
+  // (AGGMG_OPT_PATCH_MULTI) has one more, mu[k][3]: the prolonged iterate in front of its post sweeps, and the second
+  // vector of a chunked run of sweeps
+  std::vector<std::array<DevArray<double>, 4>> mu;
   int64_t multi_cols = 0;
   // the coarsest solve of a column group in one launch sequence (cr_run_cols; lazy, grown like mu): per column of the
   // group what a CrStage holds for one (partR / partL / xq, stack, mid of every stage, the tail's mid) in ONE zeroed

@@ -164,6 +164,16 @@ int aggmg_synchronize(aggmg_ctx* ctx);
  * programs that compose halves and whole cycles see what they saw before.  aggmg_replay_launches counts the replayed cycles;
  * the replaying ascent counts in aggmg_element_thread_launches like the launch it replaces. */
 #define AGGMG_OPT_REPLAY_PRESMOOTH 10
+/* AGGMG_OPT_PATCH_MULTI (default 0; environment AGGMG_PATCH_MULTI=1 makes the default 1): the K-column cycle
+ * (aggmg_vcycle_multi_dev, and aggmg_pcg_multi_dev / aggmg_multigrid_multi_dev through it) also takes levels smoothed
+ * by a fused multiplicative element-patch smoother (aggmg_patch_gs_setup) in column groups: their sweeps run
+ * patch_gs_multi_kernel, which reads a row's operator words once for up to 8 columns, and their transfers the
+ * zero-sweep launches of the K-column block-tridiagonal kernel.  A patch level qualifies when its element blocks have
+ * compressed couplings with 2 or 4 rows or dense ones with 2, its transfer has two coarse modes and one agglomeration
+ * ratio, and every launch has a tile; hybrid patch levels and all others keep the hierarchy column by column
+ * (aggmg_hier_multi_info says which).  Every result is bit for bit the same with the option on or off.  Read at every
+ * call.  aggmg_patch_multi_launches counts the launches of the K-column sweep kernel. */
+#define AGGMG_OPT_PATCH_MULTI 11
 int aggmg_set_option(aggmg_ctx* ctx, int option, int value);
 /* Launches of the element-thread kernel (AGGMG_OPT_ELEMENT_THREADS) on this context so far. */
 int aggmg_element_thread_launches(aggmg_ctx* ctx, int64_t* count);
@@ -171,6 +181,9 @@ int aggmg_element_thread_launches(aggmg_ctx* ctx, int64_t* count);
 int aggmg_pair_element_thread_launches(aggmg_ctx* ctx, int64_t* count);
 /* Cycles of aggmg_vcycle_dev that replayed their pre-smoothing (AGGMG_OPT_REPLAY_PRESMOOTH) on this context so far. */
 int aggmg_replay_launches(aggmg_ctx* ctx, int64_t* count);
+/* Launches of the K-column multiplicative patch sweep kernel (aggmg_smooth_multi_dev, and the patch levels of the
+ * K-column cycle under AGGMG_OPT_PATCH_MULTI) on this context so far. */
+int aggmg_patch_multi_launches(aggmg_ctx* ctx, int64_t* count);
 /* Raw device memory owned by the context's device (plumbing for harnesses without torch, and the storage of the
  * Julia shim's DeviceVector).  aggmg_dev_alloc returns ZEROED memory: a fresh vector is the zero initial guess of
  * ldiv! (src/solvers.jl:66,87). */
@@ -313,7 +326,7 @@ int aggmg_patch_tile_plan(int m, int nsweeps, int* tile_elems, int* owned, int* 
  * instantiated for (compressed couplings 2 .. 8, dense 1 .. 5).  A singular patch -> AGGMG_ERR_SINGULAR naming it
  * (1-based).  Memory, dictionary, aggmg_smoother_download_blocks, aggmg_smoother_patch_info (width 2, hybrid 0,
  * fused 1), aggmg_smoother_launch_bytes and the refusals of aggmg_dist_create / aggmg_hier_launch_bytes are those of
- * the fused form of aggmg_patch_schwarz_setup; K columns run column by column. */
+ * the fused form of aggmg_patch_schwarz_setup; K columns run column by column unless AGGMG_OPT_PATCH_MULTI is set. */
 int aggmg_patch_gs_setup(aggmg_ctx* ctx, aggmg_op* A, int64_t m, int64_t ne, aggmg_smoother** out);
 /* kind: 0 sm is not an element-patch smoother, 1 additive, 2 hybrid (aggmg_patch_schwarz_setup), 3 multiplicative
  * (aggmg_patch_gs_setup) */
@@ -322,6 +335,23 @@ int aggmg_smoother_patch_kind(aggmg_ctx* ctx, const aggmg_smoother* sm, int* kin
  * sweeps holds tile_elems elements per workgroup, keeps `halo` = 2 nsweeps + 1 of them on either side and owns `owned`
  * (0: no such launch); runs of more than max_sweeps sweeps are cut into launches of at most that many. */
 int aggmg_patch_gs_tile_plan(int m, int nsweeps, int* tile_elems, int* owned, int* halo, int* max_sweeps);
+/* The tiles of the K-column multiplicative sweep launch (patch_gs_multi_kernel; needs no context): a launch of nsweeps
+ * sweeps on a group of kb = 1, 2, 4 or 8 columns of a level with m = 2 or 4 rows per element holds tile_elems = 256 / m
+ * elements per workgroup, keeps `halo` = 2 nsweeps + 1 of them on either side and owns `owned` (0: no such launch --
+ * another m or kb, nsweeps outside 1 .. max_sweeps' range); runs of more than max_sweeps sweeps are cut into launches of
+ * at most that many. */
+int aggmg_patch_gs_multi_tile_plan(int m, int nsweeps, int kb, int* tile_elems, int* owned, int* halo, int* max_sweeps);
+/* EXTENSION: nsweeps sweeps of a fused multiplicative element-patch smoother (aggmg_patch_gs_setup) on ncols column-major
+ * columns (column j of U0, B, U starts ld doubles after column j - 1; ld >= N), device pointers, asynchronous on the
+ * context stream.  U0 == NULL: the zero iterate.  weights: one factor per sweep (host array, finite values).
+ * reverse = 1: the colour order of post-smoothing.  The columns go in groups of up to 8 through patch_gs_multi_kernel,
+ * which reads every row's operator words once per group; runs of more sweeps than one launch takes
+ * (aggmg_patch_gs_multi_tile_plan) are cut as aggmg_smooth_dev cuts them.  Column j of U is, bit for bit, what the
+ * single-column sweeps give on column j.  AGGMG_ERR_UNSUPPORTED, naming the reason, for any other smoother and for
+ * element blocks outside the kernel's coverage (compressed couplings with 2 or 4 rows, dense ones with 2);
+ * AGGMG_ERR_ARGUMENT for ld < N, ncols < 1, nsweeps < 0 and U overlapping U0 or B. */
+int aggmg_smooth_multi_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* U0, const double* B,
+                           int64_t ncols, int64_t ld, const double* weights, int nsweeps, int reverse, double* U);
 int aggmg_smoother_free(aggmg_ctx* ctx, aggmg_smoother* sm);
 /* apply_smoother(S, B; alpha) -> alpha * (S \ B), B is N x ncols column-major, result in Y.
  * src/smoother.jl:6-18,30-46,56-58,69-81.  Host pointers. */

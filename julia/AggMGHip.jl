@@ -306,6 +306,15 @@ function replay_launches(ctx::Context)
     check(ctx.h, ccall((:aggmg_replay_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
     return r[]
 end
+# AGGMG_OPT_PATCH_MULTI (default 0; environment AGGMG_PATCH_MULTI=1 makes the default 1): the K-column cycle also takes
+# levels smoothed by the multiplicative element-patch smoother (:patchGS) in column groups -- the same bits, each level's
+# operator words read once per group.  patch_multi_launches(ctx): how many launches the K-column sweep kernel has served.
+const OPT_PATCH_MULTI = 11
+function patch_multi_launches(ctx::Context)
+    r = Ref{Int64}(0)
+    check(ctx.h, ccall((:aggmg_patch_multi_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
+    return r[]
+end
 function set_option!(ctx::Context, option::Integer, value::Integer)
     check(ctx.h, ccall((:aggmg_set_option, LIB), Cint, (Handle, Cint, Cint), ctx.h, option, value))
     return ctx
@@ -554,6 +563,20 @@ function multigrid_v_cycle(Hd::DeviceHierarchy, X0::DeviceMatrix, B::DeviceMatri
         (Handle, Handle, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Cint, Float64, Ptr{Cvoid}),
         Hd.ctx.h, Hd.h, X0.p, B.p, B.k, B.n, nPre, nPost, Float64(alpha), X.p))
     return X
+end
+# length(weights) sweeps of a multiplicative element-patch smoother (:patchGS) on the columns of U0 (nothing: the zero
+# iterate) with right-hand sides B, sweep s damped by weights[s]; reverse: the colour order of post-smoothing
+# (aggmg_smooth_multi_dev).  A new DeviceMatrix comes back; column j is bit for bit the single-column sweeps of column j.
+function sweeps_multi(S::DeviceSmoother, U0::Union{Nothing,DeviceMatrix}, B::DeviceMatrix, weights::AbstractVector;
+        reverse::Bool = false)
+    (U0 === nothing || size(U0) == size(B)) || throw(DimensionMismatch("sweeps_multi: U0 and B differ in size"))
+    w = Vector{Float64}(weights)
+    U = DeviceMatrix(S.ctx, B.n, B.k)
+    u0 = U0 === nothing ? C_NULL : U0.p
+    GC.@preserve U0 B U w check(S.ctx.h, ccall((:aggmg_smooth_multi_dev, LIB), Cint,
+        (Handle, Handle, Handle, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Cint, Cint, Ptr{Cvoid}),
+        S.ctx.h, S.A.h, S.h, u0, B.p, B.k, B.n, w, length(w), reverse ? 1 : 0, U.p))
+    return U
 end
 # host matrices: through device copies, a new Matrix comes back
 function multigrid_v_cycle(Hd::DeviceHierarchy, X0::AbstractMatrix, B::AbstractMatrix;
