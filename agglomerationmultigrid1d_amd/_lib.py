@@ -25,6 +25,7 @@ OPT_ELEMENT_THREADS = 8
 OPT_PAIR_ELEMENT_THREADS = 9
 OPT_REPLAY_PRESMOOTH = 10
 OPT_PATCH_MULTI = 11
+OPT_CHAIN_MULTI = 12
 PROFILE_NTAGS = 256
 KIND_FUSED_DOWN, KIND_FUSED_UP, KIND_SMOOTH, KIND_RESIDUAL, KIND_RESTRICT, KIND_PROLONG, \
     KIND_JACOBI, KIND_BLOCK_APPLY, KIND_COARSE, KIND_FUSED_MID = range(10)
@@ -98,6 +99,9 @@ SYMBOLS = {
     "aggmg_pair_element_thread_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_replay_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_patch_multi_launches": (c_int, [_P, POINTER(c_int64)]),
+    "aggmg_chain_multi_launches": (c_int, [_P, POINTER(c_int64)]),
+    "aggmg_chain_multi_tile_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                            POINTER(c_int), POINTER(c_int)]),
     "aggmg_dev_alloc": (c_int, [_P, c_int64, POINTER(_P)]),
     "aggmg_dev_free": (c_int, [_P, _P]),
     "aggmg_memcpy_h2d": (c_int, [_P, _P, _P, c_int64]),

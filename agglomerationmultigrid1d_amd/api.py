@@ -114,6 +114,13 @@ class Context:
         self.check(self.lib.aggmg_patch_multi_launches(self.handle, ctypes.byref(n)))
         return int(n.value)
 
+    def chain_multi_launches(self):
+        """launches of the K-column chain kernel on this context so far (C ABI aggmg_chain_multi_launches; the chain levels
+        of the K-column cycle under AGGMG_OPT_CHAIN_MULTI)"""
+        n = ctypes.c_int64(0)
+        self.check(self.lib.aggmg_chain_multi_launches(self.handle, ctypes.byref(n)))
+        return int(n.value)
+
     def option(self, option, default):
         """the value last given to set_option (the C ABI has no getter), `default` when it never was set"""
         return self.__dict__.get("_options", {}).get(int(option), default)

@@ -184,6 +184,9 @@ extern "C" int aggmg_set_option(aggmg_ctx* ctx, int option, int value) {
     case AGGMG_OPT_PATCH_MULTI:
       ctx->patch_multi = value != 0;
       return AGGMG_OK;
+    case AGGMG_OPT_CHAIN_MULTI:
+      ctx->chain_multi = value != 0;
+      return AGGMG_OK;
   }
   return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_set_option: unknown option");
 }
@@ -1334,6 +1337,24 @@ extern "C" int aggmg_patch_gs_multi_tile_plan(int m, int nsweeps, int kb, int* t
   *owned = p.owned;
   *halo = p.halo;
   *max_sweeps = patch_gs_multi_max_sweeps(m);
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_chain_multi_tile_plan(int m, int nsweeps, int restrict_kind, int rho, int kb, int* tile_blocks, int* owned,
+                                           int* halo_left, int* halo_right, int* max_sweeps) {
+  if (!tile_blocks || !owned || !halo_left || !halo_right || !max_sweeps) return AGGMG_ERR_ARGUMENT;
+  const ChainMultiPlan p = chain_multi_tile_plan(m, nsweeps, restrict_kind, rho, kb);   // host_plan.hpp: what cgt_multi_launch_t runs
+  *tile_blocks = p.te;
+  *owned = p.owned;
+  *halo_left = p.halo_left;
+  *halo_right = p.halo_right;
+  *max_sweeps = chain_multi_max_sweeps(m);
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_chain_multi_launches(aggmg_ctx* ctx, int64_t* count) {
+  if (!ctx || !count) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_chain_multi_launches: NULL argument");
+  *count = ctx->chain_multi_launches;
   return AGGMG_OK;
 }
 
@@ -3106,9 +3127,30 @@ static bool multi_patch_level_ok(const aggmg_hier* h, int k, int nPre, int nPost
   return (nPre == 0 && nPost == 0) || smax >= 1;
 }
 
-static bool multi_level_ok(const aggmg_hier* h, int k, int nPre, int nPost, bool patch_multi) {
+// A fused chain level in column groups (AGGMG_OPT_CHAIN_MULTI): point-Jacobi sweeps on blocks of 1, 2 or 4 rows, each half
+// one launch of cgt_multi_kernel with a tile (the planner its launcher runs; a group of kMultiKB columns: the tile does not
+// depend on the group).
+static bool multi_chain_level_ok(const aggmg_hier* h, int k, int nPre, int nPost) {
+  const Level& l = h->lv[k];
+  const CgtDev& g = *l.S->cgt;
+  if (g.sw != 0 || !(g.m == 1 || g.m == 2 || g.m == 4) || !l.tc || l.tc->type == kTrNone) return false;
+  const int smax = chain_multi_max_sweeps(g.m);
+  if (nPre > smax || nPost > smax) return false;
+  TileQuery down, up;
+  down.launch = up.launch = kTileChainMulti;
+  down.te = up.te = g.m;
+  down.kb = up.kb = kMultiKB;
+  down.halo = nPre;
+  down.restrict_kind = l.tc->type == kTrChain ? kChainToChain : kChainToAgg;
+  down.align = l.tc->type == kTrAgg ? std::max(l.tc->rho, 1) : 1;
+  up.halo = nPost;
+  return launch_has_tile(down) && launch_has_tile(up);
+}
+
+static bool multi_level_ok(const aggmg_hier* h, int k, int nPre, int nPost, bool patch_multi, bool chain_multi) {
   const Level& l = h->lv[k];
   if (patch_multi && level_path(h, k) == LevelPath::Patch) return multi_patch_level_ok(h, k, nPre, nPost);
+  if (chain_multi && level_path(h, k) == LevelPath::FusedChain) return multi_chain_level_ok(h, k, nPre, nPost);
   if (level_path(h, k) != LevelPath::FusedBtd || l.S->gs) return false;
   const BtdDev& b = *l.S->btd;
   const TransferBtd& t = *l.tb;
@@ -3131,7 +3173,7 @@ static bool multi_ok(const aggmg_ctx* ctx, const aggmg_hier* h, int nPre, int nP
   const int n = (int)h->lv.size();
   if (n < 2 || h->coarse_mode == AGGMG_COARSE_EXTERNAL) return false;
   for (int k = 0; k < n - 1; ++k)
-    if (!multi_level_ok(h, k, nPre, nPost, ctx->patch_multi)) return false;
+    if (!multi_level_ok(h, k, nPre, nPost, ctx->patch_multi, ctx->chain_multi)) return false;
   return true;
 }
 
@@ -3185,7 +3227,11 @@ static int multi_workspace(aggmg_ctx* ctx, aggmg_hier* h, int64_t cols) {
       if (s == 1 && (k == 0 || coarsest)) continue;   // the ascent's output: the caller's X at level 0, none at the coarsest
       if (s == 2 && k == 0) continue;                 // level 0's right-hand side is the caller's B
       if (s == 3 && level_path(h, k) != LevelPath::Patch) continue;   // a patch level's prolonged iterate / second sweep vector
-      CHECK(h->mu[k][s].alloc(ctx, h->lv[k].N * cols));
+      // a chain level's vectors (and those a chain level keeps in block order): Nalloc doubles per column, the padding rows
+      // of the trailing block included, and zero-filled like the level's own (aggmg_hier_create) -- the kernels rely on
+      // zeros in the padding rows
+      const bool chain = level_path(h, k) == LevelPath::FusedChain || h->lv[k].native_io;
+      CHECK(h->mu[k][s].alloc(ctx, (chain ? h->lv[k].Nalloc : h->lv[k].N) * cols, chain));
     }
   }
   h->multi_cols = cols;
@@ -3259,6 +3305,10 @@ static int vcycle_multi_group(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, c
       CHECK(multi_patch_down(ctx, h, k, k == 0 ? X0 : nullptr, k == 0 ? B : h->mu[k][2], k == 0 ? ld : l.N, nPre, alpha, kc));
       continue;
     }
+    if (level_path(h, k) == LevelPath::FusedChain) {
+      CHECK(cgt_multi_down(ctx, h, k, k == 0 ? X0 : nullptr, ld, k == 0 ? B : h->mu[k][2], k == 0 ? ld : l.Nalloc, nPre, alpha, kc));
+      continue;
+    }
     MultiArgs m;
     std::memset(&m, 0, sizeof(m));
     // u[k] = zeros for k > 1 (:29-31)
@@ -3284,6 +3334,12 @@ static int vcycle_multi_group(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, c
       const double* uc = (k + 1 == n - 1) ? h->mu[k + 1][0] : h->mu[k + 1][1];
       CHECK(multi_patch_up(ctx, h, k, uc, k == 0 ? B : h->mu[k][2], k == 0 ? ld : l.N, nPost, alpha,
                            ColsPtr{k == 0 ? X : h->mu[k][1].get(), k == 0 ? ld : l.N}, kc));
+      continue;
+    }
+    if (level_path(h, k) == LevelPath::FusedChain) {
+      const double* uc = (k + 1 == n - 1) ? h->mu[k + 1][0] : h->mu[k + 1][1];
+      CHECK(cgt_multi_up(ctx, h, k, uc, c.Nalloc, k == 0 ? B : h->mu[k][2], k == 0 ? ld : l.Nalloc, nPost, alpha,
+                         k == 0 ? X : h->mu[k][1].get(), k == 0 ? ld : l.Nalloc, kc));
       continue;
     }
     MultiArgs m;
@@ -3963,9 +4019,11 @@ extern "C" int aggmg_hier_multi_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_launch_bytes: kind must be AGGMG_KIND_FUSED_DOWN / _UP");
   if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_launch_bytes: ncols must be >= 1");
   const Level& l = h->lv[level];
+  const bool down = kind == AGGMG_KIND_FUSED_DOWN;
+  if (level_path(h, level) == LevelPath::FusedChain)   // (a launch of cgt_multi_kernel, AGGMG_OPT_CHAIN_MULTI)
+    return cgt_multi_launch_bytes(ctx, h, level, down, has_x0 != 0, ncols, read_bytes, write_bytes);
   if (level_path(h, level) != LevelPath::FusedBtd)
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_hier_multi_launch_bytes: the level has no fused block-tridiagonal launch");
-  const bool down = kind == AGGMG_KIND_FUSED_DOWN;
   const bool pre = l.tb->ld && h->restriction == AGGMG_RESTRICT_PRECONDITIONED;
   btd_launch_bytes(*l.S->btd, true, !down || has_x0, down, false, down ? nullptr : l.tb.get(), down ? l.tb.get() : nullptr, pre,
                    read_bytes, write_bytes, ncols);

@@ -9,6 +9,7 @@
 // re-packs the operator -- every stored entry is read from the uploaded matrix, nothing is assumed
 // about the mesh beyond "consecutive elements share exactly one node".
 #include "internal.hpp"
+#include "cgt_multi_kernels.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // tiles
@@ -68,6 +69,63 @@ static int cgt_max_sweeps(int m, int sw = 0) {
 }
 
 int cgt_max_fused_sweeps(const CgtDev& g) { return cgt_max_sweeps(g.m, g.sw); }
+
+// ---------------------------------------------------------------------------------------------
+// K columns per launch (AGGMG_OPT_CHAIN_MULTI; cgt_multi_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+// the most columns a launch of block size M takes (a variant that spilled would get a lower ceiling here; the cycle's
+// group stays what it is and goes in several launches)
+template <int M>
+constexpr int cgt_multi_kb_ceiling() { return 8; }
+
+template <int M>
+static int cgt_multi_launch_t(aggmg_ctx* ctx, CgtMultiArgs m, const SweepWeights& wts) {
+  constexpr int NT = 256;
+  CgtArgs& a = m.a;
+  if (a.do_residual && a.tout.type == kTrNone) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column chain launch with a residual and no restriction");
+  const int kind = !a.do_residual ? kChainNoRestrict : (a.tout.type == kTrChain ? kChainToChain : kChainToAgg);
+  const int rho = kind == kChainToAgg ? a.tout.rho : 1;
+  const int kc_all = m.kc;
+  for (int c0 = 0; c0 < kc_all; c0 += cgt_multi_kb_ceiling<M>()) {
+    const int kc = std::min(kc_all - c0, cgt_multi_kb_ceiling<M>());
+    const int kb = kc <= 1 ? 1 : (kc <= 2 ? 2 : (kc <= 4 ? 4 : 8));   // the smallest instantiated group that holds the columns
+    const ChainMultiPlan p = chain_multi_tile_plan(M, a.nsweeps, kind, rho, kb, a.cls != nullptr, NT);   // host_plan.hpp, as multi_level_ok
+    if (p.owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column chain tile too small for the requested halo");
+    CgtMultiArgs q = m;
+    q.kc = kc;
+    q.a.owned = p.owned;
+    q.a.halo_left = p.halo_left;
+    if (q.a.u_in) q.a.u_in += c0 * m.ld_uin;
+    q.a.b += c0 * m.ld_b;
+    if (q.a.u_out) q.a.u_out += c0 * m.ld_uout;
+    if (q.a.uc) q.a.uc += c0 * m.ld_uc;
+    if (q.a.rc_out) q.a.rc_out += c0 * m.ld_rc;
+    const int64_t ntiles = (a.lv.ne + p.owned - 1) / p.owned;
+    if (ntiles == 0) return AGGMG_OK;
+    if (ntiles >= ((int64_t)1 << 31)) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "grid too large");
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(NT), p.lds_bytes, ctx->stream, q, wts); };
+    const bool dict = a.cls != nullptr;
+    switch (kb) {
+      case 1: dict ? go(cgt_multi_kernel<M, 1, NT, true>) : go(cgt_multi_kernel<M, 1, NT, false>); break;
+      case 2: dict ? go(cgt_multi_kernel<M, 2, NT, true>) : go(cgt_multi_kernel<M, 2, NT, false>); break;
+      case 4: dict ? go(cgt_multi_kernel<M, 4, NT, true>) : go(cgt_multi_kernel<M, 4, NT, false>); break;
+      default: dict ? go(cgt_multi_kernel<M, 8, NT, true>) : go(cgt_multi_kernel<M, 8, NT, false>); break;
+    }
+    HIPCHK(hipGetLastError());
+    ++ctx->chain_multi_launches;
+  }
+  return AGGMG_OK;
+}
+
+static int cgt_multi_launch(aggmg_ctx* ctx, const CgtDev& g, const CgtMultiArgs& m, const SweepWeights& wts) {
+  if (g.sw != 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column chain launch on element-block sweeps");
+  switch (g.m) {
+    case 1: return cgt_multi_launch_t<1>(ctx, m, wts);
+    case 2: return cgt_multi_launch_t<2>(ctx, m, wts);
+    case 4: return cgt_multi_launch_t<4>(ctx, m, wts);
+  }
+  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: chain block size not instantiated for the K-column kernel");
+}
 
 template <int M, int K>
 static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, const SweepWeights& wts, int sw, CgtChk* chk_io);
@@ -390,6 +448,68 @@ int cgt_mid(aggmg_ctx* ctx, aggmg_hier* h, const double* cur, double* alt, const
   return cgt_run(ctx, g, ch, l.damp_mid(alpha), nsweeps, first, last, AGGMG_KIND_FUSED_MID, 0, chk, l.cdict.get());
 }
 
+// ---- K columns per launch: the halves of a chain level of the K-column cycle (the launcher: above, beside cgt_launch) ----
+// descending half of kc columns on a fused chain level: nPre sweeps from U0 (level 0 only: the caller's X0, or null --
+// zero), residual, restriction into the next level's right-hand sides; the pre-smoothed iterates go to mu[k][0] in block
+// order.  The ext flags are cgt_down's.
+int cgt_multi_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* U0, int64_t ld_u0, const double* B, int64_t ld_b, int nPre,
+                   double alpha, int kc) {
+  Level& l = h->lv[k];
+  Level& c = h->lv[k + 1];
+  const CgtDev& g = *l.S->cgt;
+  CgtMultiArgs m;
+  std::memset(&m, 0, sizeof(m));
+  m.a = cgt_args(g);
+  CgtArgs& a = m.a;
+  a.nsweeps = nPre;
+  a.u_in = U0;
+  a.b = B;
+  a.ext = (U0 ? kExtUin : 0) | ((k == 0 || !l.native_io) ? kExtB : 0);
+  a.u_out = h->mu[k][0];
+  a.do_residual = 1;
+  a.tout = cgt_xfer(*l.tc, c.native_io);
+  a.rc_out = h->mu[k + 1][2];
+  cgt_dictionary(a, g, l.cdict.get());
+  m.kc = kc;
+  m.ld_uin = ld_u0;
+  m.ld_b = ld_b;
+  m.ld_uout = l.Nalloc;
+  m.ld_rc = c.Nalloc;
+  const SweepWeights wts = l.damp_pre(alpha).launch(nPre);
+  ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
+  return cgt_multi_launch(ctx, g, m, wts);
+}
+
+// ascending half: prolongation-add of uc onto the pre-smoothed iterates (mu[k][0], block order), nPost sweeps, into dst --
+// the caller's numbering at level 0 and on a level whose vectors are not kept in block order, as cgt_up
+int cgt_multi_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uc, int64_t ld_uc, const double* B, int64_t ld_b, int nPost,
+                 double alpha, double* dst, int64_t ld_dst, int kc) {
+  Level& l = h->lv[k];
+  Level& c = h->lv[k + 1];
+  const CgtDev& g = *l.S->cgt;
+  CgtMultiArgs m;
+  std::memset(&m, 0, sizeof(m));
+  m.a = cgt_args(g);
+  CgtArgs& a = m.a;
+  a.nsweeps = nPost;
+  a.u_in = h->mu[k][0];
+  a.b = B;
+  const bool ext = (k == 0) || !l.native_io;
+  a.ext = (ext ? kExtB : 0) | (ext ? kExtUout : 0);
+  a.u_out = dst;
+  a.tin = cgt_xfer(*l.tc, c.native_io);
+  a.uc = uc;
+  cgt_dictionary(a, g, l.cdict.get());
+  m.kc = kc;
+  m.ld_uin = l.Nalloc;
+  m.ld_b = ld_b;
+  m.ld_uout = ld_dst;
+  m.ld_uc = ld_uc;
+  const SweepWeights wts = l.damp_post(alpha).launch(nPost);
+  ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
+  return cgt_multi_launch(ctx, g, m, wts);
+}
+
 // ---- compulsory bytes: what the arrays of a launch hold, each read or written once -------------
 static int64_t cgt_operator_bytes(const CgtDev& g, bool sweeps) {
   const int64_t D = sizeof(double), rows = g.ne * g.m;
@@ -429,6 +549,32 @@ int cgt_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int level, bool down, 
   w += (up && !down ? vec : rows) * D;                                 // iterate out
   *rd = r;
   *wr = w;
+  return AGGMG_OK;
+}
+
+// the same for a launch of ncols columns (cgt_multi_down / cgt_multi_up): the operator and transfer arrays and the index
+// arrays once, every vector once per column; at ncols = 1 the figures of cgt_launch_bytes
+int cgt_multi_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int level, bool down, bool has_x0, int64_t ncols, int64_t* rd, int64_t* wr) {
+  const Level& l = h->lv[level];
+  const Level& c = h->lv[level + 1];
+  if (!l.S || !l.S->cgt || !l.tc) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_hier_multi_launch_bytes: not a fused chain level");
+  const CgtDev& g = *l.S->cgt;
+  const int64_t D = sizeof(double), rows = g.ne * g.m;
+  const bool up = !down;
+  const bool ext = (level == 0) || !l.native_io;
+  const int64_t vec = ext ? g.N : rows;
+  const int64_t nc = l.tc->nec * l.tc->mc;
+  const bool cp = l.tc->type == kTrChain && !c.native_io && l.tc->cperm;
+  int64_t once = cgt_operator_bytes(g, true) + cgt_xfer_bytes(*l.tc, g);   // operator, rows of L
+  if (ext && !g.affine) once += rows * 4;                                  // block order -> caller's numbering
+  if (cp) once += nc * 4;                                                  // coarse block order -> caller's numbering
+  int64_t r = vec * D, w = 0;                                              // per column: right-hand side
+  if (up || has_x0) r += (up ? rows : g.N) * D;                            // iterate in
+  if (up) r += nc * D;                                                     // coarse iterate
+  if (down) w += nc * D;                                                   // restricted residual
+  w += (up ? vec : rows) * D;                                              // iterate out
+  *rd = once + ncols * r;
+  *wr = ncols * w;
   return AGGMG_OK;
 }
 

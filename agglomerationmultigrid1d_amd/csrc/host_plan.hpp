@@ -399,11 +399,44 @@ inline int patch_gs_multi_max_sweeps(int m, int threads = 256) {
   return s;
 }
 
+// ---- the chain kernel on K columns at once (cgt_multi_kernel, cgt_multi_kernels.hpp) -------------------------------------
+// One slab: a workgroup of `threads` threads holds threads / m blocks, for m = 1, 2, 4 (lane groups of m) and kb = 1, 2, 4
+// or 8 columns of them.  The halos are the single-column launch's (cgt_launch_tt): a block per sweep and side, one more a
+// side for a residual, one more on the left for a chain restriction, on the right for an agglomerating one, whose ratio the
+// owned blocks are a multiple of.  The most sweeps per launch follow the single-column rule.  LDS: kb iterate planes per
+// ping-pong buffer, each padded by one block a side, and (dictionary variant) the tile's classes behind them.
+enum ChainRestrict { kChainNoRestrict = 0, kChainToChain = 1, kChainToAgg = 2 };
+struct ChainMultiPlan {
+  int te = 0;                        // blocks a workgroup holds (0: block size not covered)
+  int halo_left = 0, halo_right = 0;
+  int owned = 0;                     // 0: no tile
+  size_t lds_bytes = 0;
+};
+inline int chain_multi_tile_blocks(int m, int threads = 256) { return (m == 1 || m == 2 || m == 4) ? threads / m : 0; }
+inline bool chain_multi_group(int kb) { return kb == 1 || kb == 2 || kb == 4 || kb == 8; }
+inline ChainMultiPlan chain_multi_tile_plan(int m, int nsweeps, int restrict_kind, int rho, int kb, bool dict = false,
+                                            int threads = 256) {
+  ChainMultiPlan p;
+  p.te = chain_multi_tile_blocks(m, threads);
+  if (p.te <= 0 || !chain_multi_group(kb) || nsweeps < 0 || nsweeps > kPatchMaxSweeps || rho < 1) return p;
+  if (restrict_kind < kChainNoRestrict || restrict_kind > kChainToAgg) return p;
+  p.halo_left = nsweeps + (restrict_kind != kChainNoRestrict ? 1 : 0) + (restrict_kind == kChainToChain ? 1 : 0);
+  p.halo_right = nsweeps + (restrict_kind != kChainNoRestrict ? 1 : 0) + (restrict_kind == kChainToAgg ? 1 : 0);
+  p.owned = chain_tile_owned(p.te, p.halo_left, p.halo_right, restrict_kind == kChainToAgg ? rho : 1);
+  p.lds_bytes = (size_t)2 * kb * (p.te + 2) * m * sizeof(double) + (dict ? (size_t)(p.te + 2) * 2 : 0);
+  return p;
+}
+// (cgt_max_sweeps of cgt.hip on the one-slab tile: 2 * smax + 3 blocks of halo always fit it)
+inline int chain_multi_max_sweeps(int m, int threads = 256) {
+  const int te = chain_multi_tile_blocks(m, threads);
+  return te <= 0 ? 0 : std::max(1, std::min(kPatchMaxSweeps, te / 8));
+}
+
 // ---- does a launch have a tile? ----------------------------------------------------------------------------------
 // One question for every tiled launch, answered by the planner its launcher runs: the callers that choose between a
 // launch and its fallback (two levels or one per launch, fused or unfused sequence, K columns or column by column) ask
 // here, so a launch that was chosen never finds "no tile".
-enum TileLaunch { kTileFused = 0, kTileMulti = 1, kTilePairDown = 2, kTilePairUp = 3, kTilePatch = 4, kTilePatchGs = 5, kTilePatchGsMulti = 6 };
+enum TileLaunch { kTileFused = 0, kTileMulti = 1, kTilePairDown = 2, kTilePairUp = 3, kTilePatch = 4, kTilePatchGs = 5, kTilePatchGsMulti = 6, kTileChainMulti = 7 };
 struct TileQuery {
   int launch = kTileFused;
   int te = 0, te_b = 0;   // elements a workgroup holds (pairs: of level A and of level B)
@@ -412,6 +445,8 @@ struct TileQuery {
   int rho_bc = 1;         // descent of a pair
   bool var_agg = false;   // fused: see fused_tile_plan
   int agg_shift = -1;
+  int restrict_kind = 0;  // K-column chain launch: ChainRestrict (there te = the block size m, halo = the sweeps, align = rho)
+  int kb = 1;             // K-column chain launch: the column group
 };
 inline bool launch_has_tile(const TileQuery& q) {
   if (q.te <= 0 || q.align < 1 || q.rho_bc < 1 || q.halo < 0) return false;
@@ -423,6 +458,7 @@ inline bool launch_has_tile(const TileQuery& q) {
     case kTilePatch: return q.halo >= 1 && q.halo <= kPatchMaxSweeps && patch_owned(q.te, q.halo) > 0;
     case kTilePatchGs: return q.halo >= 1 && q.halo <= kPatchMaxSweeps && patch_gs_owned(q.te, q.halo) > 0;
     case kTilePatchGsMulti: return q.halo >= 1 && q.halo <= kPatchMaxSweeps && patch_gs_owned(q.te, q.halo) > 0;   // te: patch_gs_multi_tile_elems
+    case kTileChainMulti: return chain_multi_tile_plan(q.te, q.halo, q.restrict_kind, q.align, q.kb).owned > 0;   // te: the block size
   }
   return false;
 }

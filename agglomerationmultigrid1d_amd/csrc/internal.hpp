@@ -79,6 +79,8 @@ struct aggmg_ctx {
   int64_t replay_launches = 0;   // replayed cycles so far (aggmg_replay_launches)
   bool patch_multi = [] { const char* e = std::getenv("AGGMG_PATCH_MULTI"); return e && e[0] == '1'; }();  // AGGMG_OPT_PATCH_MULTI (default 0)
   int64_t patch_multi_launches = 0;   // launches of patch_gs_multi_kernel so far (aggmg_patch_multi_launches)
+  bool chain_multi = [] { const char* e = std::getenv("AGGMG_CHAIN_MULTI"); return e && e[0] == '1'; }();  // AGGMG_OPT_CHAIN_MULTI (default 0)
+  int64_t chain_multi_launches = 0;   // launches of cgt_multi_kernel so far (aggmg_chain_multi_launches)
   int profiling = 0;  // 0 off, 1 every launch, 2 only the fine-level fused-down launch (dominant kernel)
   std::vector<ProfEvent> prof;
   std::vector<hipEvent_t> ev_pool;
@@ -569,6 +571,13 @@ int cgt_mid(aggmg_ctx* ctx, aggmg_hier* h, const double* cur, double* alt, const
             CgtChk* chk = nullptr);
 // compulsory bytes (every array of the launch once) of a chain level's fused launches / of a stand-alone sweep or residual launch
 int cgt_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int level, bool down, bool up, bool has_x0, int64_t* rd, int64_t* wr);
+// K columns per launch (AGGMG_OPT_CHAIN_MULTI): the halves of a fused chain level of the K-column cycle, on the vectors of
+// multi_workspace (h->mu; leading dimension Nalloc on a chain level)
+int cgt_multi_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* U0, int64_t ld_u0, const double* B, int64_t ld_b, int nPre,
+                   double alpha, int kc);
+int cgt_multi_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uc, int64_t ld_uc, const double* B, int64_t ld_b, int nPost,
+                 double alpha, double* dst, int64_t ld_dst, int kc);
+int cgt_multi_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int level, bool down, bool has_x0, int64_t ncols, int64_t* rd, int64_t* wr);
 int cgt_op_launch_bytes(const CgtDev& g, bool sweeps, int64_t* rd, int64_t* wr);
 
 // ---------------------------------------------------------------------------------------------

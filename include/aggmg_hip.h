@@ -174,6 +174,17 @@ int aggmg_synchronize(aggmg_ctx* ctx);
  * (aggmg_hier_multi_info says which).  Every result is bit for bit the same with the option on or off.  Read at every
  * call.  aggmg_patch_multi_launches counts the launches of the K-column sweep kernel. */
 #define AGGMG_OPT_PATCH_MULTI 11
+/* AGGMG_OPT_CHAIN_MULTI (default 0; environment AGGMG_CHAIN_MULTI=1 makes the default 1): the K-column cycle
+ * (aggmg_vcycle_multi_dev, and aggmg_pcg_multi_dev / aggmg_multigrid_multi_dev through it) also takes fused CG chain
+ * levels (AGGMG_LEVEL_FUSED_CHAIN) in column groups: each half of such a level is one launch of cgt_multi_kernel, which
+ * reads a row's operator and transfer words, its class and its index once for up to 8 columns.  A chain level
+ * qualifies when it smooths with point Jacobi on blocks of 1, 2 or 4 rows (CG p = 1, 2, 4), nPre and nPost each fit
+ * one launch (aggmg_chain_multi_tile_plan: max_sweeps) and both launches have a tile; chain levels with other block
+ * sizes or with element Schwarz / Gauss-Seidel sweeps and all other levels keep the hierarchy column by column
+ * (aggmg_hier_multi_info says which).  Chain levels mix with block-Jacobi levels and, under AGGMG_OPT_PATCH_MULTI, with
+ * patch levels.  Every result is bit for bit the same with the option on or off.  Read at every call.
+ * aggmg_chain_multi_launches counts the launches of the K-column chain kernel. */
+#define AGGMG_OPT_CHAIN_MULTI 12
 int aggmg_set_option(aggmg_ctx* ctx, int option, int value);
 /* Launches of the element-thread kernel (AGGMG_OPT_ELEMENT_THREADS) on this context so far. */
 int aggmg_element_thread_launches(aggmg_ctx* ctx, int64_t* count);
@@ -184,6 +195,19 @@ int aggmg_replay_launches(aggmg_ctx* ctx, int64_t* count);
 /* Launches of the K-column multiplicative patch sweep kernel (aggmg_smooth_multi_dev, and the patch levels of the
  * K-column cycle under AGGMG_OPT_PATCH_MULTI) on this context so far. */
 int aggmg_patch_multi_launches(aggmg_ctx* ctx, int64_t* count);
+/* Launches of the K-column chain kernel (the chain levels of the K-column cycle under AGGMG_OPT_CHAIN_MULTI) on this
+ * context so far. */
+int aggmg_chain_multi_launches(aggmg_ctx* ctx, int64_t* count);
+/* The tiles of a K-column chain launch (cgt_multi_kernel; needs no context): a launch of nsweeps point-Jacobi sweeps on
+ * a group of kb = 1, 2, 4 or 8 columns of a chain level with m = 1, 2 or 4 rows per block holds tile_blocks = 256 / m
+ * blocks per workgroup.  restrict_kind: 0 the launch ends with the sweeps (an ascent), 1 residual and restriction to a
+ * chain level, 2 residual and restriction to agglomerates of rho blocks.  It keeps halo_left / halo_right blocks on its
+ * sides -- nsweeps each, one more each for a residual, one more on the left for a chain restriction, on the right for an
+ * agglomerating one -- and owns `owned`, a multiple of rho for an agglomerating restriction (0: no such launch -- another
+ * m or kb, nsweeps outside 0 .. 8, halos that fill the tile).  max_sweeps: the most sweeps the K-column cycle puts into
+ * one launch; a half-cycle of more keeps the hierarchy column by column. */
+int aggmg_chain_multi_tile_plan(int m, int nsweeps, int restrict_kind, int rho, int kb, int* tile_blocks, int* owned,
+                                int* halo_left, int* halo_right, int* max_sweeps);
 /* Raw device memory owned by the context's device (plumbing for harnesses without torch, and the storage of the
  * Julia shim's DeviceVector).  aggmg_dev_alloc returns ZEROED memory: a fresh vector is the zero initial guess of
  * ldiv! (src/solvers.jl:66,87). */

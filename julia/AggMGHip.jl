@@ -315,6 +315,15 @@ function patch_multi_launches(ctx::Context)
     check(ctx.h, ccall((:aggmg_patch_multi_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
     return r[]
 end
+# AGGMG_OPT_CHAIN_MULTI (default 0; environment AGGMG_CHAIN_MULTI=1 makes the default 1): the K-column cycle also takes
+# fused CG chain levels (point Jacobi, p = 1, 2, 4) in column groups -- the same bits, each level's operator words read
+# once per group.  chain_multi_launches(ctx): how many launches the K-column chain kernel has served.
+const OPT_CHAIN_MULTI = 12
+function chain_multi_launches(ctx::Context)
+    r = Ref{Int64}(0)
+    check(ctx.h, ccall((:aggmg_chain_multi_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
+    return r[]
+end
 function set_option!(ctx::Context, option::Integer, value::Integer)
     check(ctx.h, ccall((:aggmg_set_option, LIB), Cint, (Handle, Cint, Cint), ctx.h, option, value))
     return ctx
