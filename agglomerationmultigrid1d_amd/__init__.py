@@ -10,7 +10,7 @@ from .api import (AbstractSmoother, AdditiveSchwarzSmoother, BlockDiagonal, Bloc
                   DeviceOperator,
                   DeviceMatrix, DeviceVector, DirectSolver, ElementPatchGaussSeidel, ElementPatchSchwarz, HybridSchwarzSmoother, JacobiSmoother, MeshHierarchy,
                   apply_smoother, cg_smoother, default_context, dg_smoother, element_patch_lists,
-                  dot, fgmres, iterative_smoother_solve, ldiv, multigrid, multigrid_dev, multigrid_v_cycle, norm2, pcg,
+                  dot, fgmres, fgmres_multi, iterative_smoother_solve, ldiv, multigrid, multigrid_dev, multigrid_v_cycle, norm2, pcg,
                   prolong_add, residual, restrict, smooth, smoother_launch_bytes, smoother_solve_dev,
                   chebyshev_weights)
 

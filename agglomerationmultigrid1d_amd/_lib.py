@@ -220,6 +220,10 @@ SYMBOLS = {
     "aggmg_multi_dot_dev": (c_int, [_P, _P, c_int64, c_int64, c_int64, _P, _PD]),
     "aggmg_multi_axpy_norm_dev": (c_int, [_P, _P, c_int64, c_int64, c_int64, _PD, _P, _PD]),
     "aggmg_fgmres_dev": (c_int, [_P, _P, _P, _P, c_int, c_int, c_double, c_int, c_int, c_double, _PD, POINTER(c_int)]),
+    "aggmg_multi_dot_cols_dev": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, c_int64, _PD]),
+    "aggmg_multi_axpy_norm_cols_dev": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int64, c_int64, _PD, _P, c_int64, _PD]),
+    "aggmg_fgmres_multi_dev": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int, c_int, c_double, c_int, c_int, c_double, _PD,
+                                       POINTER(c_int), POINTER(c_int64)]),
     "aggmg_residual_multi_dev": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P]),
     "aggmg_dot_cols_dev": (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, _PD]),
     "aggmg_norm2_cols_dev": (c_int, [_P, _P, c_int64, c_int64, c_int64, _PD]),

@@ -213,6 +213,38 @@ class Context:
                                                       ctypes.byref(out) if norm else None))
         return out.value if norm else None
 
+    def multi_dot_cols(self, V, W, n, nvec, ncols, bstride=None, cstride=None, ldw=None):
+        """V_i[:, c] . W[:, c] for nvec basis vectors of each of ncols independent bases, all in one launch sequence (C
+        ABI aggmg_multi_dot_cols_dev; EXTENSION: the orthogonalisation of fgmres_multi).  V a device buffer with basis
+        vector i of column c at offset i * bstride + c * cstride (defaults: cstride = n, bstride = n * ncols), W column
+        c at offset c * ldw (default n).  -> array (ncols, nvec); entry (c, i) is bit for bit multi_dot's entry i on
+        column c alone"""
+        n, nvec, ncols = int(n), int(nvec), int(ncols)
+        cstride = n if cstride is None else int(cstride)
+        bstride = cstride * ncols if bstride is None else int(bstride)
+        ldw = n if ldw is None else int(ldw)
+        out = np.zeros((max(1, ncols), max(1, nvec)))
+        self.check(self.lib.aggmg_multi_dot_cols_dev(self.handle, _ptr(V), n, nvec, ncols, bstride, cstride, _ptr(W), ldw,
+                                                     _pd(out)))
+        return out[:max(0, ncols), :max(0, nvec)]
+
+    def multi_axpy_norm_cols(self, V, coef, W, n, nvec, ncols, bstride=None, cstride=None, ldw=None, norm=True):
+        """W[:, c] += V_c @ coef[c] in place for ncols independent bases, one fused multiply-add per basis vector in
+        ascending order (C ABI aggmg_multi_axpy_norm_cols_dev; EXTENSION: the orthogonalisation of fgmres_multi); the
+        layout is multi_dot_cols', coef an (ncols, nvec) array.  -> array of the ncols norms of the stored columns, each
+        summed by the pass that stores it (bit for bit multi_axpy_norm on column c alone); None with norm=False"""
+        n, nvec, ncols = int(n), int(nvec), int(ncols)
+        cstride = n if cstride is None else int(cstride)
+        bstride = cstride * ncols if bstride is None else int(bstride)
+        ldw = n if ldw is None else int(ldw)
+        c = np.ascontiguousarray(_f64(coef))
+        if nvec >= 1 and ncols >= 1 and c.shape != (ncols, nvec):
+            raise DimensionMismatch("multi_axpy_norm_cols: coef must have shape (ncols, nvec)")
+        out = np.zeros(max(1, ncols))
+        self.check(self.lib.aggmg_multi_axpy_norm_cols_dev(self.handle, _ptr(V), n, nvec, ncols, bstride, cstride, _pd(c),
+                                                           _ptr(W), ldw, _pd(out) if norm else None))
+        return out[:max(0, ncols)] if norm else None
+
     def profile_enable(self, on=True):
         """True / 1: HIP events around every launch; 2: only the fine-level fused-down launch;
         False / 0: off"""
@@ -1230,6 +1262,22 @@ class MeshHierarchy:
                                           ctypes.byref(work)))
         return its[:K].copy(), [hist[j, :its[j]].tolist() for j in range(K)], work.value
 
+    def fgmres_multi_dev(self, B, X, ncols=None, ld=None, restart=30, maxiter=200, tol=1e-10, nPre=3, nPost=3,
+                         alpha=2.0 / 3.0):
+        """fgmres on K right-hand sides in lockstep, resident on the device (C ABI aggmg_fgmres_multi_dev; EXTENSION): B,
+        X (initial guesses in, results out) DeviceMatrix / column-major device buffers.  Column j is bit for bit
+        aggmg_fgmres_dev on column j.  -> (iters[K], res: K lists, work_cols)"""
+        N = self._ops[0].shape[0]
+        _, K, ld = _cols_shape("fgmres_multi_dev", B, N, ncols, ld)
+        hist = np.zeros((max(1, K), max(1, int(maxiter))))
+        its = np.zeros(max(1, K), dtype=np.int32)
+        work = ctypes.c_int64(0)
+        c = self.ctx
+        c.check(c.lib.aggmg_fgmres_multi_dev(c.handle, self.handle, _ptr(B), _ptr(X), K, ld, int(restart), int(maxiter),
+                                             float(tol), int(nPre), int(nPost), float(alpha), _pd(hist),
+                                             its.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(work)))
+        return its[:K].copy(), [hist[j, :its[j]].tolist() for j in range(K)], work.value
+
     def multigrid_multi_dev(self, X0, B, X, maxiter, tol, ncols=None, ld=None, check_every=1, nPre=3, nPost=3, alpha=2.0 / 3.0,
                             U_exact=None):
         """multigrid on K right-hand sides, resident on the device (C ABI aggmg_multigrid_multi_dev; EXTENSION): X0, B, X
@@ -1794,11 +1842,11 @@ def fgmres(H, b, x0=None, restart=30, maxiter=200, tol=1e-10, nPre=3, nPost=3, a
     (None: zeros) is not modified.  restart: iterations before the basis is dropped and the method starts again from the
     current residual, 1 .. 64; the work space is (2 restart + 2) vectors on the device.  Small values can stagnate where
     the default converges (restart 1 and 2 do on V(2,1) of the agglomerated DG hierarchy).  One
-    right-hand side only."""
+    right-hand side per call: fgmres_multi takes N x K matrices and runs the K recurrences in lockstep."""
     if isinstance(b, DeviceMatrix) or isinstance(x0, DeviceMatrix) or \
             (not isinstance(b, DeviceVector) and np.ndim(b) != 1):
-        raise ArgumentError("fgmres: b must be one vector; K right-hand sides are out of scope of fgmres (pcg and "
-                            "multigrid take N x K matrices)")
+        raise ArgumentError("fgmres: b must be one vector; K right-hand sides are out of scope of fgmres: use "
+                            "fgmres_multi (pcg and multigrid take N x K matrices themselves)")
     c = H.ctx
     N = H._ops[0].shape[0]
     on_device = isinstance(b, DeviceVector)
@@ -1823,6 +1871,27 @@ def fgmres(H, b, x0=None, restart=30, maxiter=200, tol=1e-10, nPre=3, nPost=3, a
     c.check(c.lib.aggmg_fgmres_dev(c.handle, H.handle, db.ptr, dx.ptr, int(restart), int(maxiter), float(tol), int(nPre),
                                    int(nPost), float(alpha), _pd(hist), ctypes.byref(it)))
     return (dx if on_device else dx.download()), it.value, hist[:it.value].tolist()
+
+
+def fgmres_multi(H, B, X0=None, restart=30, maxiter=200, tol=1e-10, nPre=3, nPost=3, alpha=2.0 / 3.0):
+    """fgmres on K right-hand sides (EXTENSION): K recurrences in lockstep, one K-column cycle, one K-column operator
+    product, one orthogonalisation launch sequence and one read-back per iteration (C ABI aggmg_fgmres_multi_dev; DESIGN.md
+    24).  B, X0 (N, K) host arrays in either memory order, or DeviceMatrix; X0 None: zero guesses; X0 is not modified.
+    -> (X, iters[K], res: K lists): column j's X, count and history are bit for bit those of fgmres on column j with the
+    same arguments -- each column stops by its own ||b_j|| and then costs no further work.  Valid for every cycle, as
+    fgmres.  The work space is (2 restart + 2) N x K matrices on the device."""
+    (dB, dX0), on_device = _device_matrices("fgmres_multi", H, [B, X0])
+    if dB is None:
+        raise ArgumentError("fgmres_multi: B is needed")
+    c = H.ctx
+    if dX0 is not None and not on_device:
+        dX = dX0                             # (the uploaded copy of the caller's array)
+    else:
+        dX = DeviceMatrix(c, dB.n, dB.k)     # (aggmg_dev_alloc zeroes: the zero guesses)
+        if dX0 is not None:
+            _copy_dev(c, dX.ptr.value, dX0.ptr.value, dB.n * dB.k)
+    its, res, _ = H.fgmres_multi_dev(dB, dX, dB.k, dB.n, restart, maxiter, tol, nPre, nPost, alpha)
+    return (dX if on_device else dX.download()), its, res
 
 
 def iterative_smoother_solve(A, smoother, x0, b, maxiter=1000, tol=1e-6, alpha=1.0, exact=True, check_every=1):

@@ -15,6 +15,7 @@
 #include "pair_elem_kernels.hpp"
 #include "krylov_kernels.hpp"
 #include "host_gmres.hpp"
+#include "host_gmres_cols.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // context
@@ -5145,6 +5146,285 @@ extern "C" int aggmg_multigrid_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const do
   for (int s = 0; s < act.n; ++s) CHECK(keep(s));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (work_cols) *work_cols = work;
+  return AGGMG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Flexible GMRES on K right-hand sides in lockstep (EXTENSION): K recurrences of aggmg_fgmres_dev, one HostGmres per
+// column, the cycle and the operator product on N x kact matrices, the orthogonalisation of all active columns in one
+// launch sequence (krylov_kernels.hpp: the *_cols kernels), one read-back per iteration.
+// ---------------------------------------------------------------------------------------------
+// device scalars per column of capacity: 65 dots and the norm behind them (packed per pass: dot (c, i) of a pass over
+// nvec vectors and na slots at [c * nvec + i], the norms at [na * nvec + c]), 65 coefficients from the host, beta
+constexpr int64_t kKrycDots = kKryMaxVec + 1, kKrycCoef = kKryMaxVec, kKrycScalars = kKrycDots + kKrycCoef + 1;
+
+static int kryc_scalars(aggmg_ctx* ctx, int64_t K) {
+  CHECK(cols_scalars(ctx, K));
+  CHECK(kry_scalars(ctx));
+  if (ctx->kryc_cap >= K) return AGGMG_OK;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->kryc_cap = 0;
+  CHECK(ctx->kryc_part.alloc(ctx, K * kKrycDots * kDotBlocks));
+  CHECK(ctx->kryc_sc.alloc(ctx, K * kKrycScalars, true));
+  CHECK(ctx->kryc_map.alloc(ctx, K));
+  ctx->kryc_cap = K;
+  return AGGMG_OK;
+}
+static double* kryc_coef(aggmg_ctx* ctx) { return ctx->kryc_sc + ctx->kryc_cap * kKrycDots; }
+static double* kryc_beta(aggmg_ctx* ctx) { return kryc_coef(ctx) + ctx->kryc_cap * kKrycCoef; }
+
+template <int G>
+static void launch_multi_dot_cols(aggmg_ctx* ctx, unsigned kc, int64_t n, const double* V, int64_t bs, int64_t cs, const double* W,
+                                  int64_t ldw, int64_t pcol, double* part) {
+  hipLaunchKernelGGL(multi_dot_cols_partial_kernel<G>, dim3(kDotBlocks, kc), dim3(kThreads), 0, ctx->stream, n, V, bs, cs, W, ldw,
+                     pcol, part);
+}
+template <int G>
+static void launch_multi_axpy_cols(aggmg_ctx* ctx, unsigned kc, int64_t n, const double* V, int64_t bs, int64_t cs,
+                                   const double* coef, int64_t cld, double scale, double* W, int64_t ldw, const int* wcol,
+                                   double* part) {
+  if (part)
+    hipLaunchKernelGGL((multi_axpy_cols_kernel<G, true>), dim3(kDotBlocks, kc), dim3(kThreads), 0, ctx->stream, n, V, bs, cs, coef,
+                       cld, scale, W, ldw, wcol, part);
+  else
+    hipLaunchKernelGGL((multi_axpy_cols_kernel<G, false>), dim3(kDotBlocks, kc), dim3(kThreads), 0, ctx->stream, n, V, bs, cs, coef,
+                       cld, scale, W, ldw, wcol, part);
+}
+
+// out[c * nvec + i] = V_i[:, c] . W[:, c], c < na <= kryc_cap, i < nvec <= kKryMaxVec (out on the device): per group of 8
+// vectors one pass over W for all slots, then one workgroup per dot; everything stays on the stream
+static int dev_multi_dot_cols(aggmg_ctx* ctx, int64_t n, int64_t nvec, int64_t na, const double* V, int64_t bs, int64_t cs,
+                              const double* W, int64_t ldw, double* out) {
+  for (int64_t i0 = 0; i0 < nvec; i0 += kKrylovGroup) {
+    const int g = (int)std::min<int64_t>(kKrylovGroup, nvec - i0);
+    for_col_chunks(na, [&](int64_t c0, unsigned kc) {
+#define KRY_CALL(G) \
+  launch_multi_dot_cols<G>(ctx, kc, n, V + i0 * bs + c0 * cs, bs, cs, W + c0 * ldw, ldw, nvec, ctx->kryc_part + (c0 * nvec + i0) * kDotBlocks)
+      KRY_GROUP_SWITCH(g, KRY_CALL)
+#undef KRY_CALL
+    });
+  }
+  hipLaunchKernelGGL(dot_cols_final_kernel, dim3((unsigned)(na * nvec)), dim3(kThreads), 0, ctx->stream, kDotBlocks,
+                     (const double*)ctx->kryc_part, out, 0);
+  HIPCHK(hipGetLastError());
+  return AGGMG_OK;
+}
+
+// W[:, d(c)] += V_c (scale coef_c), coef_c = coef + c * cld on the device, d(c) = wcol ? wcol[c] : c, in groups of 8
+// (ascending); norm_out (device, na entries, or null) receives the norms of the stored columns, summed by the pass of
+// the last group
+static int dev_multi_axpy_cols(aggmg_ctx* ctx, int64_t n, int64_t nvec, int64_t na, const double* V, int64_t bs, int64_t cs,
+                               const double* coef, int64_t cld, double scale, double* W, int64_t ldw, const int* wcol,
+                               double* norm_out) {
+  double* part = ctx->kryc_part + ctx->kryc_cap * kKryMaxVec * kDotBlocks;
+  for (int64_t i0 = 0; i0 < nvec; i0 += kKrylovGroup) {
+    const int g = (int)std::min<int64_t>(kKrylovGroup, nvec - i0);
+    const bool last = norm_out && i0 + g == nvec;
+    for_col_chunks(na, [&](int64_t c0, unsigned kc) {
+#define KRY_CALL(G)                                                                                                      \
+  launch_multi_axpy_cols<G>(ctx, kc, n, V + i0 * bs + c0 * cs, bs, cs, coef + c0 * cld + i0, cld, scale, wcol ? W : W + c0 * ldw, \
+                            ldw, wcol ? wcol + c0 : nullptr, last ? part + c0 * kDotBlocks : nullptr)
+      KRY_GROUP_SWITCH(g, KRY_CALL)
+#undef KRY_CALL
+    });
+  }
+  if (norm_out)
+    hipLaunchKernelGGL(dot_cols_final_kernel, dim3((unsigned)na), dim3(kThreads), 0, ctx->stream, kDotBlocks, (const double*)part,
+                       norm_out, 1);
+  HIPCHK(hipGetLastError());
+  return AGGMG_OK;
+}
+
+static int kry_cols_args(aggmg_ctx* ctx, const char* who, const double* V, int64_t n, int64_t nvec, int64_t ncols, int64_t bstride,
+                         int64_t cstride, const double* W, int64_t ldw, const void* host) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  const std::string w(who);
+  if (!V || !W || !host) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": NULL argument");
+  if (n < 0 || nvec < 1 || nvec > kKryMaxVec)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": needs n >= 0 and 1 <= nvec <= " + std::to_string(kKryMaxVec));
+  if (ncols < 1 || ncols > (1 << 20)) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": needs 1 <= ncols <= 2^20");
+  if (bstride < n || cstride < n || ldw < n)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": the basis stride, the column stride and ldw must be >= n");
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_multi_dot_cols_dev(aggmg_ctx* ctx, const double* V, int64_t n, int64_t nvec, int64_t ncols, int64_t bstride,
+                                        int64_t cstride, const double* W, int64_t ldw, double* out_host) {
+  CHECK(kry_cols_args(ctx, "aggmg_multi_dot_cols_dev", V, n, nvec, ncols, bstride, cstride, W, ldw, out_host));
+  HIPCHK(hipSetDevice(ctx->device));
+  CHECK(kryc_scalars(ctx, ncols));
+  CHECK(dev_multi_dot_cols(ctx, n, nvec, ncols, V, bstride, cstride, W, ldw, ctx->kryc_sc));
+  return read_scalars(ctx, ctx->kryc_sc, ncols * nvec, out_host);
+}
+
+extern "C" int aggmg_multi_axpy_norm_cols_dev(aggmg_ctx* ctx, const double* V, int64_t n, int64_t nvec, int64_t ncols,
+                                              int64_t bstride, int64_t cstride, const double* coef_host, double* W_inout,
+                                              int64_t ldw, double* norm_out_host) {
+  CHECK(kry_cols_args(ctx, "aggmg_multi_axpy_norm_cols_dev", V, n, nvec, ncols, bstride, cstride, W_inout, ldw, coef_host));
+  if (ranges_overlap(V, (nvec - 1) * bstride + (ncols - 1) * cstride + n, W_inout, (ncols - 1) * ldw + n))
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_multi_axpy_norm_cols_dev: W must not overlap V");
+  HIPCHK(hipSetDevice(ctx->device));
+  CHECK(kryc_scalars(ctx, ncols));
+  double* coef = kryc_coef(ctx);   // packed as the host array: nvec per column
+  HIPCHK(hipMemcpyAsync(coef, coef_host, (size_t)(ncols * nvec) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  double* norms = norm_out_host ? ctx->kryc_sc.get() : nullptr;
+  CHECK(dev_multi_axpy_cols(ctx, n, nvec, ncols, V, bstride, cstride, coef, nvec, 1.0, W_inout, ldw, nullptr, norms));
+  if (norm_out_host) return read_scalars(ctx, norms, ncols, norm_out_host);
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // (coef_host has been read when this returns)
+  return AGGMG_OK;
+}
+
+// K recurrences of aggmg_fgmres_dev in lockstep.  Work space (ctx->kry_work): V[j][slot][N], Z[j][slot][N], W[slot][N]
+// with ncols slots per basis index, so that V_j and Z_j of the active slots are contiguous N x kact matrices with
+// leading dimension N.  All active columns share the position j in the restart cycle and the iteration counter: a
+// column that stops leaves, and the others go on exactly as they would alone.
+extern "C" int aggmg_fgmres_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* B, double* X, int64_t ncols, int64_t ld,
+                                      int restart, int maxiter, double tol, int nPre, int nPost, double alpha, double* res_hist,
+                                      int* n_iters, int64_t* work_cols) {
+  CHECK(multi_solver_args(ctx, "aggmg_fgmres_multi_dev", h, B, X, ncols, ld, maxiter, nPre, nPost));
+  if (!res_hist || !n_iters) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_fgmres_multi_dev: NULL argument");
+  if (restart < 1 || restart > AGGMG_FGMRES_MAX_RESTART)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_fgmres_multi_dev: restart must be 1 .. " + std::to_string(AGGMG_FGMRES_MAX_RESTART));
+  aggmg_op* A = h->lv[0].A;
+  const int64_t N = A->m, K = ncols;
+  const int64_t span = (K - 1) * ld + N;
+  if (ranges_overlap(X, span, B, span)) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_fgmres_multi_dev: X must not overlap B");
+  CHECK(schedule_check(ctx, h, nPre, nPost));
+  HIPCHK(hipSetDevice(ctx->device));
+  for (int64_t j = 0; j < K; ++j) n_iters[j] = 0;
+  if (work_cols) *work_cols = 0;
+  if (maxiter == 0 || N == 0) return AGGMG_OK;
+  CHECK(kryc_scalars(ctx, K));
+  const int64_t bs = N * K;   // from basis vector j of a slot to its vector j + 1
+  const int64_t need = (2 * (int64_t)restart + 2) * bs;
+  if (ctx->kry_work.size() != need || !ctx->kry_work) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    (void)ctx->kry_work.reset(ctx);
+    if (int st = ctx->kry_work.alloc(ctx, need))
+      return fail(ctx, st, "aggmg_fgmres_multi_dev: no device memory for the work space of " + std::to_string(need * 8) +
+                               " bytes (restart " + std::to_string(restart) + ", ncols " + std::to_string(K) + ", " +
+                               std::to_string(2 * restart + 2) + " matrices of " + std::to_string(N) + " x " + std::to_string(K) +
+                               "): " + ctx->err);
+  }
+  double* V = ctx->kry_work;
+  double* Z = V + ((int64_t)restart + 1) * bs;
+  double* W = Z + (int64_t)restart * bs;
+  double* sc = ctx->kryc_sc;
+  double* coefd = kryc_coef(ctx);
+  double* betad = kryc_beta(ctx);
+  const size_t colb = (size_t)N * sizeof(double);
+  const unsigned grid = (unsigned)((N + kThreads - 1) / kThreads);
+  auto divide = [&](int64_t na, const double* s, double* Vj) {   // Vj[:, c] = W[:, c] / s[c]
+    for_col_chunks(na, [&](int64_t c0, unsigned kc) {
+      hipLaunchKernelGGL(div_scalar_cols_kernel, dim3(grid, kc), dim3(kThreads), 0, ctx->stream, N, (const double*)(W + c0 * N), N,
+                         s + c0, Vj + c0 * N, N);
+    });
+  };
+  std::vector<double> nb((size_t)K), beta((size_t)K), got((size_t)(K * kKrycDots));
+  std::vector<double> yfin((size_t)(K * kKrycCoef)), ycyc((size_t)(K * kKrycCoef));
+  std::vector<char> fin((size_t)K), upd((size_t)K);
+  std::vector<HostGmres> ls((size_t)K);   // by column: a move carries none
+  double col[AGGMG_FGMRES_MAX_RESTART + 2];
+  CHECK(dev_dot_cols(ctx, N, K, B, ld, B, ld, cols_sc(ctx, kColNormB), 1));
+  CHECK(read_scalars(ctx, cols_sc(ctx, kColNormB), K, nb.data()));
+  GmresSlots slots((int)K);
+  int it = 0;
+  while (slots.active() > 0 && it < maxiter) {
+    int na = slots.active();
+    // every cycle starts from r = b - A x: the K-column residual on every run of slots whose columns are neighbours
+    for (int s = 0; s < na;) {
+      int e = s + 1;
+      while (e < na && slots.column(e) == slots.column(e - 1) + 1) ++e;
+      const int64_t c = slots.column(s);
+      CHECK(residual_multi(ctx, A, X + c * ld, ld, B + c * ld, ld, e - s, W + (int64_t)s * N, N));
+      s = e;
+    }
+    CHECK(dev_dot_cols(ctx, N, na, W, N, W, N, betad, 1));
+    CHECK(read_scalars(ctx, betad, na, beta.data()));
+    bool any = false;
+    for (int s = 0; s < na; ++s) {   // (at entry: x untouched, n_iters = 0)
+      const double b = beta[(size_t)s];
+      fin[(size_t)s] = b == 0.0 || b < tol * nb[(size_t)slots.column(s)] || !std::isfinite(b);
+      any = any || fin[(size_t)s];
+    }
+    if (any) {
+      CHECK(slots.finish(fin, [&](int dst, int src) {
+        HIPCHK(hipMemcpyAsync(W + (int64_t)dst * N, W + (int64_t)src * N, colb, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(betad + dst, betad + src, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        beta[(size_t)dst] = beta[(size_t)src];
+        return (int)AGGMG_OK;
+      }));
+      na = slots.active();
+      if (na == 0) break;
+    }
+    divide(na, betad, V);   // v_0 = r / beta
+    HIPCHK(hipGetLastError());
+    for (int s = 0; s < na; ++s) ls[(size_t)slots.column(s)].start(beta[(size_t)s]);
+    const int len = std::min(restart, maxiter - it);
+    for (int j = 0; j < len; ++j) {
+      na = slots.active();
+      const int64_t nvec = j + 1;
+      double* Zj = Z + (int64_t)j * bs;
+      CHECK(aggmg_vcycle_multi_dev(ctx, h, nullptr, V + (int64_t)j * bs, na, N, nPre, nPost, alpha, Zj));   // Z_j = M^-1 V_j
+      slots.count_cycle();
+      CHECK(residual_multi(ctx, A, Zj, N, nullptr, 0, na, W, N));                                           // W = -A Z_j
+      double* norms = sc + (int64_t)na * nvec;
+      CHECK(dev_multi_dot_cols(ctx, N, nvec, na, V, bs, N, W, N, sc));                                      // h_c = V_c' w_c
+      CHECK(dev_multi_axpy_cols(ctx, N, nvec, na, V, bs, N, sc, nvec, -1.0, W, N, nullptr, norms));         // w_c -= V_c h_c; ||w_c||
+      CHECK(read_scalars(ctx, sc, (int64_t)na * (nvec + 1), got.data()));
+      ++it;
+      any = false;
+      for (int s = 0; s < na; ++s) {
+        const int c = slots.column(s);
+        for (int i = 0; i <= j; ++i) col[i] = got[(size_t)(s * nvec + i)];
+        col[j + 1] = got[(size_t)(na * nvec + s)];
+        const double res = ls[(size_t)c].push(col);
+        res_hist[(int64_t)c * maxiter + it - 1] = res;
+        n_iters[c] = it;
+        if (!std::isfinite(res)) {   // (x keeps the value of the last finished cycle)
+          fin[(size_t)s] = 1;
+          upd[(size_t)s] = 0;
+        } else {                     // converged, or the Krylov space is exhausted (no division by 0)
+          fin[(size_t)s] = upd[(size_t)s] = res < tol * nb[(size_t)c] || col[j + 1] == 0.0;
+        }
+        any = any || fin[(size_t)s];
+      }
+      if (any) {
+        for (int s = 0; s < na; ++s) {   // a finished column is final: x += Z y (for -A: -=) at once
+          if (!fin[(size_t)s] || !upd[(size_t)s]) continue;
+          const int64_t c = slots.column(s);
+          double* y = yfin.data() + c * kKrycCoef;
+          ls[(size_t)c].solve(y);
+          HIPCHK(hipMemcpyAsync(coefd + c * kKrycCoef, y, (size_t)nvec * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+          CHECK(dev_multi_axpy(ctx, N, nvec, Z + (int64_t)s * N, bs, coefd + c * kKrycCoef, -1.0, X + c * ld, nullptr));
+        }
+        CHECK(slots.finish(fin, [&](int dst, int src) {   // V_0..j, Z_0..j, W and ||w|| of the last slot
+          for (int64_t i = 0; i <= j; ++i) {
+            HIPCHK(hipMemcpyAsync(V + i * bs + (int64_t)dst * N, V + i * bs + (int64_t)src * N, colb, hipMemcpyDeviceToDevice, ctx->stream));
+            HIPCHK(hipMemcpyAsync(Z + i * bs + (int64_t)dst * N, Z + i * bs + (int64_t)src * N, colb, hipMemcpyDeviceToDevice, ctx->stream));
+          }
+          HIPCHK(hipMemcpyAsync(W + (int64_t)dst * N, W + (int64_t)src * N, colb, hipMemcpyDeviceToDevice, ctx->stream));
+          HIPCHK(hipMemcpyAsync(norms + dst, norms + src, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+          return (int)AGGMG_OK;
+        }));
+        if (slots.active() == 0) break;
+      }
+      if (j + 1 < len) {
+        divide(slots.active(), norms, V + (int64_t)(j + 1) * bs);
+        HIPCHK(hipGetLastError());
+      }
+    }
+    na = slots.active();
+    if (na == 0) break;
+    // the restart cycle is over for the columns still active: x_c += Z_c y_c, all in one launch sequence
+    for (int s = 0; s < na; ++s) ls[(size_t)slots.column(s)].solve(ycyc.data() + (int64_t)s * kKrycCoef);
+    HIPCHK(hipMemcpyAsync(coefd, ycyc.data(), (size_t)(na * kKrycCoef) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->kryc_map, slots.map(), (size_t)na * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    CHECK(dev_multi_axpy_cols(ctx, N, len, na, Z, bs, N, coefd, kKrycCoef, -1.0, X, ld, ctx->kryc_map, nullptr));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // (y and the map are read before they change)
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (work_cols) *work_cols = slots.work_cols();
   return AGGMG_OK;
 }
 

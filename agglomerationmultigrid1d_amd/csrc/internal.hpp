@@ -100,6 +100,13 @@ struct aggmg_ctx {
   // and one norm, the device scalars, and the solver's (2 restart + 2) N work space -- kept between calls of the same
   // size, exchanged when another size is asked for, freed with the context
   DevArray<double> kry_part, kry_sc, kry_work;
+  // its K-column forms (aggmg_fgmres_multi_dev, aggmg_multi_dot_cols_dev, aggmg_multi_axpy_norm_cols_dev): for
+  // kryc_cap columns the partial sums of 65 dots and one norm, the scalars and coefficients, and the slot -> column
+  // map; lazy, grown for more columns, freed with the context.  The solver's work space is kry_work,
+  // (2 restart + 2) N ncols doubles, under the same rule as the single-vector solver's.
+  DevArray<double> kryc_part, kryc_sc;
+  DevArray<int> kryc_map;
+  int64_t kryc_cap = 0;
   // owned-range reductions of the partitioned conjugate-gradient loop (aggmg_owned_dot_dev, aggmg_pcg_xr_owned_dev):
   // kOwnedBlocks partial sums per range, then the scalar; lazy, freed with the context
   DevArray<double> own_part;

@@ -879,6 +879,48 @@ int aggmg_multi_axpy_norm_dev(aggmg_ctx* ctx, const double* V, int64_t n, int64_
 #define AGGMG_FGMRES_MAX_RESTART 64
 int aggmg_fgmres_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* b, double* x_inout, int restart, int maxiter, double tol,
                      int nPre, int nPost, double alpha, double* res_hist, int* n_iters);
+/* The same two passes over ncols independent bases at once (what aggmg_fgmres_multi_dev runs per iteration).  Basis
+ * vector i of column c is V + i * bstride + c * cstride (basis index outer, column inner; bstride, cstride >= n), its
+ * vector is W + c * ldw (ldw >= n); 1 <= nvec <= AGGMG_FGMRES_MAX_RESTART + 1, ncols >= 1.  Both synchronous.
+ * aggmg_multi_dot_cols_dev: out_host[c * nvec + i] = V_i[:, c] . W[:, c], one pass over W per group of 8 vectors for all
+ * columns, one launch that finishes all ncols * nvec sums; entry (c, i) is bit for bit aggmg_multi_dot_dev's entry i on
+ * column c alone, hence aggmg_dot_dev's.
+ * aggmg_multi_axpy_norm_cols_dev: W[r, c] <- fma(coef_host[c * nvec + nvec-1], V_{nvec-1}[r, c], ... fma(coef_host[c * nvec],
+ * V_0[r, c], W[r, c])) for r < n (ascending i, in place; rows >= n and other columns are not touched); norm_out_host
+ * (ncols entries, may be NULL) receives ||W[:, c]||_2 of the stored columns: the bits aggmg_multi_axpy_norm_dev stores
+ * and returns on column c alone.
+ * AGGMG_ERR_ARGUMENT: NULL, n < 0, nvec outside 1 .. 65, ncols < 1, a stride or ldw < n, W overlapping V. */
+int aggmg_multi_dot_cols_dev(aggmg_ctx* ctx, const double* V, int64_t n, int64_t nvec, int64_t ncols, int64_t bstride,
+                             int64_t cstride, const double* W, int64_t ldw, double* out_host);
+int aggmg_multi_axpy_norm_cols_dev(aggmg_ctx* ctx, const double* V, int64_t n, int64_t nvec, int64_t ncols, int64_t bstride,
+                                   int64_t cstride, const double* coef_host, double* W_inout, int64_t ldw,
+                                   double* norm_out_host);
+/* aggmg_fgmres_dev on K right-hand sides: K recurrences in lockstep, each with its own Hessenberg matrix and rotations
+ * on the host.  B, X_inout: device, column-major, leading dimension ld >= N; X holds the initial guesses and the
+ * results.  Per iteration j of a restart cycle, on the kact columns still active: Z_j = M^-1 V_j by one K-column cycle
+ * from zero guesses (aggmg_vcycle_multi_dev), W = -A Z_j by the K-column residual, the dots and the update + norms of all
+ * columns in one launch sequence (aggmg_multi_dot_cols_dev's / aggmg_multi_axpy_norm_cols_dev's passes), ONE read-back of
+ * all columns' h_0..j and ||w||, v_{j+1} = w / ||w|| for all columns in one launch.  Column j's iterate, n_iters[j] and
+ * res_hist[j * maxiter + i] are bit for bit aggmg_fgmres_dev's on column j with the same arguments: the column stops when
+ * res < tol ||b_j|| (its own ||b_j||), at maxiter iterations (the last restart cycle is cut, as there), when ||w|| == 0
+ * (nothing is divided by it) or when a history entry is not finite (x_j then keeps the value of its last finished
+ * restart cycle); ||r_j|| == 0 or < tol ||b_j|| at the start of a restart cycle stops it -- at entry: n_iters[j] = 0 and
+ * x_j untouched.  All active columns share the position in the restart cycle, and a column's iteration counter is the
+ * common one until it leaves.  A column that has stopped is final: its x_j += Z y is applied at once, it leaves the
+ * active set, the last active column's state takes its place, and it costs no further work; *work_cols (may be NULL)
+ * returns the column-V-cycles actually run (= the sum of n_iters).  res_hist: host, ncols * maxiter entries; n_iters:
+ * host, ncols entries.  Hierarchies the K-column cycle or residual does not cover (aggmg_hier_multi_info: fused = 0;
+ * CG chain operators) run their column-by-column forms under the same contract.
+ * Work space: (2 restart + 2) N ncols doubles on the context -- V[j][column slot][N], Z[j][slot][N], W[slot][N] -- kept
+ * between calls of the same size, released when another size is asked for (by this solver or by aggmg_fgmres_dev, which
+ * shares it) and at aggmg_destroy; per-column scalars and partial sums (540 kB per column) grow with the largest ncols
+ * seen.  When the work space cannot be allocated: AGGMG_ERR_HIP, the message names the bytes, restart and ncols.
+ * AGGMG_ERR_ARGUMENT, before anything is enqueued: NULL, ncols < 1, ld < N, restart outside
+ * 1 .. AGGMG_FGMRES_MAX_RESTART, maxiter < 0, negative sweep counts, X overlapping B, a hierarchy created with
+ * AGGMG_COARSE_EXTERNAL. */
+int aggmg_fgmres_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* B, double* X_inout, int64_t ncols, int64_t ld,
+                           int restart, int maxiter, double tol, int nPre, int nPost, double alpha, double* res_hist,
+                           int* n_iters, int64_t* work_cols);
 /* ---- K right-hand sides through the outer loops (EXTENSION: the reference's solvers take vectors,
  * src/solvers.jl:116-139).  All matrices: device, column-major, leading dimension ld >= N (>= n). ---- */
 /* out_host[j] = X[:, j] . Y[:, j] / ||X[:, j]||_2, j < ncols, each in one pass over the matrices: bit for bit

@@ -801,7 +801,7 @@ end
 # one and returns a wrong answer without an error on any other.  res[i]: the residual norm of the least-squares problem
 # after iteration i.  b, x0 DeviceVectors -> x a DeviceVector, host vectors -> a host vector; x0 = nothing: zeros; x0 is
 # not modified.  restart 1 .. 64: the work space is (2 restart + 2) device vectors; small values can stagnate where the
-# default converges (DESIGN.md 18).  One right-hand side only: K columns are out of scope.
+# default converges (DESIGN.md 18).  One right-hand side per call: fgmres_multi takes N x K matrices.
 function fgmres(Hd::DeviceHierarchy, b::Union{AbstractVector,DeviceVector};
         x0::Union{Nothing,AbstractVector,DeviceVector} = nothing, restart::Integer = 30, maxiter::Integer = 200,
         tol::AbstractFloat = 1e-10, nPre::Integer = 3, nPost::Integer = 3, alpha::AbstractFloat = 2.0 / 3.0)
@@ -814,6 +814,28 @@ function fgmres(Hd::DeviceHierarchy, b::Union{AbstractVector,DeviceVector};
         (Handle, Handle, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Float64, Cint, Cint, Float64, Ptr{Float64}, Ref{Cint}),
         Hd.ctx.h, Hd.h, db.p, x.p, restart, maxiter, Float64(tol), nPre, nPost, Float64(alpha), res, it))
     return (on_device ? x : download(x)), Int(it[]), res[1:it[]]
+end
+
+# fgmres_multi(H, B; X0, restart, maxiter, tol) -> X, iters::Vector{Int}, res (one Vector per column): fgmres on K
+# right-hand sides, K recurrences in lockstep with one K-column cycle, one K-column operator product, one
+# orthogonalisation launch sequence and one read-back per iteration (aggmg_fgmres_multi_dev; DESIGN.md 24).  Column j's
+# X, count and history are bit for bit fgmres on column j; a column that has met its own tolerance costs no further
+# work.  B, X0 DeviceMatrix -> X a DeviceMatrix, host matrices -> a host matrix; X0 = nothing: zero guesses; X0 is not
+# modified.  The work space is (2 restart + 2) N x K device matrices.
+function fgmres_multi(Hd::DeviceHierarchy, B::Union{AbstractMatrix,DeviceMatrix};
+        X0::Union{Nothing,AbstractMatrix,DeviceMatrix} = nothing, restart::Integer = 30, maxiter::Integer = 200,
+        tol::AbstractFloat = 1e-10, nPre::Integer = 3, nPost::Integer = 3, alpha::AbstractFloat = 2.0 / 3.0)
+    on_device = B isa DeviceMatrix
+    dB = on_device ? B : DeviceMatrix(Hd.ctx, B)
+    K = dB.k
+    X = X0 === nothing ? DeviceMatrix(Hd.ctx, dB.n, K) :                   # (fresh memory is zeroed)
+        DeviceMatrix(Hd.ctx, X0 isa DeviceMatrix ? download(X0) : X0)     # (a copy: X0 stays as it is)
+    res = zeros(max(maxiter, 1), K); its = zeros(Cint, K); work = Ref{Int64}(0)
+    GC.@preserve dB X res its check(Hd.ctx.h, ccall((:aggmg_fgmres_multi_dev, LIB), Cint,
+        (Handle, Handle, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Cint, Float64, Cint, Cint, Float64, Ptr{Float64},
+         Ptr{Cint}, Ref{Int64}),
+        Hd.ctx.h, Hd.h, dB.p, X.p, K, dB.n, restart, maxiter, Float64(tol), nPre, nPost, Float64(alpha), res, its, work))
+    return (on_device ? X : download(X)), Int.(its), [res[1:its[j], j] for j in 1:K]
 end
 
 # iterative_smoother_solve(A, smoother, x0, b; maxiter = 1000, tol = 1e-6, alpha = 1.0) -> x, iter, res, err
