@@ -26,6 +26,7 @@ OPT_PAIR_ELEMENT_THREADS = 9
 OPT_REPLAY_PRESMOOTH = 10
 OPT_PATCH_MULTI = 11
 OPT_CHAIN_MULTI = 12
+OPT_ELEMENT_RECORDS_LDS = 13
 PROFILE_NTAGS = 256
 KIND_FUSED_DOWN, KIND_FUSED_UP, KIND_SMOOTH, KIND_RESIDUAL, KIND_RESTRICT, KIND_PROLONG, \
     KIND_JACOBI, KIND_BLOCK_APPLY, KIND_COARSE, KIND_FUSED_MID = range(10)
@@ -98,6 +99,9 @@ SYMBOLS = {
     "aggmg_element_thread_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_pair_element_thread_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_replay_launches": (c_int, [_P, POINTER(c_int64)]),
+    "aggmg_element_record_lds_launches": (c_int, [_P, POINTER(c_int64)]),
+    "aggmg_element_record_lds_cap": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
+    "aggmg_element_record_pack": (c_int, [c_int, _P, _P, _P, _P, _P, _P, c_int, _P, POINTER(c_int)]),
     "aggmg_patch_multi_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_chain_multi_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_chain_multi_tile_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),

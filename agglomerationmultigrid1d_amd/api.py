@@ -107,6 +107,20 @@ class Context:
         self.check(self.lib.aggmg_replay_launches(self.handle, ctypes.byref(n)))
         return int(n.value)
 
+    def element_record_lds_launches(self):
+        """launches of the element-thread kernels with the class records in LDS on this context so far (C ABI
+        aggmg_element_record_lds_launches, AGGMG_OPT_ELEMENT_RECORDS_LDS)"""
+        n = ctypes.c_int64(0)
+        self.check(self.lib.aggmg_element_record_lds_launches(self.handle, ctypes.byref(n)))
+        return int(n.value)
+
+    def element_record_lds_cap(self):
+        """(cap on classes in force, largest cap the option takes) of AGGMG_OPT_ELEMENT_RECORDS_LDS (C ABI
+        aggmg_element_record_lds_cap)"""
+        c, m = ctypes.c_int(0), ctypes.c_int(0)
+        self.check(self.lib.aggmg_element_record_lds_cap(self.handle, ctypes.byref(c), ctypes.byref(m)))
+        return int(c.value), int(m.value)
+
     def patch_multi_launches(self):
         """launches of the K-column multiplicative patch sweep kernel on this context so far (C ABI
         aggmg_patch_multi_launches; ElementPatchGaussSeidel.sweeps_multi_dev, AGGMG_OPT_PATCH_MULTI)"""

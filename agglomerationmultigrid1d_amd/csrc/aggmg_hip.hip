@@ -182,6 +182,11 @@ extern "C" int aggmg_set_option(aggmg_ctx* ctx, int option, int value) {
     case AGGMG_OPT_REPLAY_PRESMOOTH:
       ctx->replay_presmooth = value != 0;
       return AGGMG_OK;
+    case AGGMG_OPT_ELEMENT_RECORDS_LDS:
+      if (value < 0 || value > kElemRecMaxClasses)
+        return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_set_option: AGGMG_OPT_ELEMENT_RECORDS_LDS takes 0 .. " + std::to_string(kElemRecMaxClasses));
+      ctx->elem_rec_cap = value;
+      return AGGMG_OK;
     case AGGMG_OPT_PATCH_MULTI:
       ctx->patch_multi = value != 0;
       return AGGMG_OK;
@@ -584,6 +589,7 @@ static void xfer_out(FusedArgs& a, const TransferBtd& t) {
 // of their own (SweepWeights, kernels.hpp)
 struct FusedLaunch : FusedArgs {
   SweepWeights wts;
+  ElemRecTab rec = {nullptr, 0};   // the level's packed class records (DictDev::rec), set with the dictionary; or null
 };
 
 // What the element-thread kernel (elem_kernels.hpp) asks of a launch's arguments, on a level with compressed couplings
@@ -593,6 +599,12 @@ static bool elem_thread_args(const aggmg_ctx* ctx, const FusedArgs& a, bool chk,
   return ctx->elem_threads && a.lv.cls && a.lv.bsym && !a.gs && !chk && a.nsweeps >= 1 && sel_mode == 0 && !a.r_out &&
          !a.par_in && !a.par_out && !a.ld_out && (!a.lf_in || a.mc_in == 2) && (!a.lf_out || a.mc_out == 2) &&
          (!a.do_residual || a.lf_out);
+}
+// ... and of those launches the ones that keep the class records in LDS (AGGMG_OPT_ELEMENT_RECORDS_LDS; btd_elem_rec_kernel,
+// btd_elem_rec_replay_up_kernel): the level has its packed records, no more classes than the option allows, and a
+// residual comes from the lossless symmetric form (the record holds no full rows)
+static bool elem_record_args(const aggmg_ctx* ctx, const FusedLaunch& a) {
+  return a.rec.rec && a.rec.nclasses >= 1 && a.rec.nclasses <= ctx->elem_rec_cap && (!a.do_residual || (a.lv.dup && a.lv.corr));
 }
 
 template <int M, bool CMP>
@@ -659,6 +671,20 @@ static int launch_btd_t(aggmg_ctx* ctx, FusedLaunch a, int halo, const TileSel& 
       if (a.par_in || a.par_out || a.ld_out || (a.lf_in && a.mc_in != 2) || (a.lf_out && a.mc_out != 2))
         return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: dictionary launch with a transfer the variant does not index by class");
       if constexpr (M == 4) {
+        if (elem && elem_record_args(ctx, a)) {
+          auto go_rec = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(kElemThreads), elem_rec_lds_bytes<M>(a.rec.nclasses), ctx->stream,
+                               static_cast<const FusedArgs&>(a), a.wts, a.rec);
+          };
+          if (a.do_residual)
+            go_rec(btd_elem_rec_kernel<M, true>);
+          else
+            go_rec(btd_elem_rec_kernel<M, false>);
+          HIPCHK(hipGetLastError());
+          ++ctx->elem_launches;
+          ++ctx->elem_rec_launches;
+          return AGGMG_OK;
+        }
         if (elem) {
           auto go_elem = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(kElemThreads), elem_lds_bytes<M>(), ctx->stream,
@@ -793,7 +819,7 @@ static void fused_descent(FusedArgs& a, const aggmg_hier* h, const Level& l, dou
 // The level's operator dictionary in place of its full arrays (after fused_ascent / fused_descent): the default-mode
 // block-Jacobi launches of a cycle -- no checkpoint, no (L'D) restriction -- on a level that has one.  The variant reads
 // the same bits from the dictionary (btd_fused_kernel<..., DICT = true>).
-static void fused_dictionary(FusedArgs& a, const Level& l) {
+static void fused_dictionary(FusedLaunch& a, const Level& l) {
   const DictDev* d = l.dict.get();
   if (!d || a.gs || a.chk_part || a.ld_out || a.par_in || a.par_out || !a.lv.bsym) return;
   if ((a.lf_in && a.mc_in != 2) || (a.lf_out && a.mc_out != 2)) return;
@@ -805,6 +831,7 @@ static void fused_dictionary(FusedArgs& a, const Level& l) {
   a.lv.scol = d->scol;
   a.lv.dblk = d->dblk;
   a.lv.cls = d->cls;
+  if (d->rec) a.rec = ElemRecTab{d->rec, d->nclasses};
   // (lf_in / lf_out also say that there is a prolongation / a restriction: never null then)
   if (a.lf_in) (d->lf_unit ? a.lf1_in : a.lf_in) = d->lf;
   if (a.lf_out) (d->lf_unit ? a.lf1_out : a.lf_out) = d->lf;
@@ -2636,6 +2663,27 @@ extern "C" int aggmg_pair_element_thread_launches(aggmg_ctx* ctx, int64_t* count
   return AGGMG_OK;
 }
 
+extern "C" int aggmg_element_record_lds_launches(aggmg_ctx* ctx, int64_t* count) {
+  if (!ctx || !count) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_element_record_lds_launches: NULL argument");
+  *count = ctx->elem_rec_launches;
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_element_record_lds_cap(aggmg_ctx* ctx, int* cap, int* max_cap) {
+  if (!ctx || !cap) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_element_record_lds_cap: NULL argument");
+  *cap = ctx->elem_rec_cap;
+  if (max_cap) *max_cap = kElemRecMaxClasses;
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_element_record_pack(int nclasses, const double* bsym, const double* qrow, const double* qmir, const double* dup,
+                                         const uint32_t* corr, const double* lf, int lf_unit, double* rec, int* words) {
+  if (words) *words = kElemRecWords;
+  if (nclasses < 0 || (nclasses > 0 && (!bsym || !qrow || !qmir || !lf || !rec || !dup != !corr))) return AGGMG_ERR_ARGUMENT;
+  elem_record_pack(nclasses, bsym, qrow, qmir, dup, corr, lf, lf_unit != 0, rec);
+  return AGGMG_OK;
+}
+
 extern "C" int aggmg_replay_launches(aggmg_ctx* ctx, int64_t* count) {
   if (!ctx || !count) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_replay_launches: NULL argument");
   *count = ctx->replay_launches;
@@ -2846,10 +2894,16 @@ static int btd_replay_up(aggmg_ctx* ctx, aggmg_hier* h, const double* x0, const 
   a.tile_skip = sub.skip;
   if (sub.ntiles == 0) return AGGMG_OK;
   ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, 0);
-  hipLaunchKernelGGL(btd_elem_replay_up_kernel<4>, dim3((unsigned)sub.ntiles), dim3(kElemThreads), elem_lds_bytes<4>(), ctx->stream,
-                     static_cast<const FusedArgs&>(a), a.wts, nPre);
+  const bool rec = elem_record_args(ctx, a);
+  if (rec)
+    hipLaunchKernelGGL(btd_elem_rec_replay_up_kernel<4>, dim3((unsigned)sub.ntiles), dim3(kElemThreads),
+                       elem_rec_lds_bytes<4>(a.rec.nclasses), ctx->stream, static_cast<const FusedArgs&>(a), a.wts, nPre, a.rec);
+  else
+    hipLaunchKernelGGL(btd_elem_replay_up_kernel<4>, dim3((unsigned)sub.ntiles), dim3(kElemThreads), elem_lds_bytes<4>(), ctx->stream,
+                       static_cast<const FusedArgs&>(a), a.wts, nPre);
   HIPCHK(hipGetLastError());
   ++ctx->elem_launches;
+  if (rec) ++ctx->elem_rec_launches;
   ++ctx->replay_launches;
   return AGGMG_OK;
 }

@@ -13,6 +13,7 @@
 #pragma once
 #include <type_traits>
 
+#include "host_plan.hpp"
 #include "kernels.hpp"
 
 namespace aggmg {
@@ -466,6 +467,390 @@ __global__ __launch_bounds__(kElemThreads) void btd_elem_replay_up_kernel(FusedA
 #endif
     }
   }
+}
+
+// ---- the class records in LDS (AGGMG_OPT_ELEMENT_RECORDS_LDS) ----------------------------------------------------------
+// The kernels above fetch the element's class record through the vector memory path in two further round trips -- the
+// packed inverse, q_{e-1}, q_e and the rows of L once cls has landed, the residual's words after the sweeps -- although a
+// level has a handful of classes and nearly every lane of a wave asks for the same few hundred bytes.  The kernels below
+// copy the level's table of records into LDS at entry, with loads issued ahead of cls, b and u_in, and read every record
+// word from LDS where it is used (lanes of one class read one address, which LDS broadcasts).  After the entry phase they
+// issue no global load but the escape path's.  pcol = B^{-1} q_{e-1}, the same for every element of a class, comes with
+// the record: formed at set-up by elem_sym_row_apply's chain (host_plan.hpp, elem_record_pack), so the 16 FMAs per element
+// and the q_{e-1} registers go.  Everything else is the expression of the kernels above: the SAME BITS.
+//
+// The record's layout (kElemRecWords and the offsets kElemRec*) and its host repack: host_plan.hpp, elem_record_pack.
+// The escape words (dblk, scol) stay in global memory behind the unlikely branch.
+struct ElemRecTab {
+  const double* rec;   // [nclasses][kElemRecWords]
+  int nclasses;        // 1 .. kElemRecMaxClasses
+};
+template <int M>
+constexpr size_t elem_rec_lds_bytes(int nclasses) {
+  return elem_lds_bytes<M>() + (size_t)nclasses * kElemRecWords * sizeof(double);
+}
+
+// the table's loads, 16 bytes each, strided over the workgroup, as many rounds as the table has words for (a lane past
+// the table in its last round reads its last word) ...
+constexpr int kElemRecStage = (kElemRecMaxClasses * (kElemRecWords / 2) + kElemThreads - 1) / kElemThreads;
+__device__ __forceinline__ void elem_rec_fetch(const ElemRecTab& t, int x, elem_v2d (&v)[kElemRecStage]) {
+  const int n = t.nclasses * (kElemRecWords / 2);
+#pragma unroll
+  for (int k = 0; k < kElemRecStage; ++k) {
+    const int i = x + k * kElemThreads;
+    // (a round wholly past the table is not issued: n is the launch's, the branch uniform)
+    if (k == 0 || k * kElemThreads < n) v[k] = reinterpret_cast<const elem_v2d*>(t.rec)[i < n ? i : n - 1];
+  }
+}
+// ... and their stores, issued once the loads behind them (cls, b, u_in) are under way
+__device__ __forceinline__ void elem_rec_store(double* tab, const ElemRecTab& t, int x, const elem_v2d (&v)[kElemRecStage]) {
+  const int n = t.nclasses * (kElemRecWords / 2);
+#pragma unroll
+  for (int k = 0; k < kElemRecStage; ++k) {
+    const int i = x + k * kElemThreads;
+    if (i < n) reinterpret_cast<elem_v2d*>(tab)[i] = v[k];
+  }
+}
+
+// Keeps the uses of a loaded value behind this point.  (The compiler moves register arithmetic on a loaded value over
+// the table's barrier, and the wait for the streaming loads with it: the barrier would then wait for HBM.)
+template <class V>
+__device__ __forceinline__ void elem_rec_pin(V& v) {
+  asm volatile("" : "+v"(v));
+}
+template <int M>
+__device__ __forceinline__ void elem_rec_pin_all(unsigned& ce, double (&bb)[M], double (&uu)[M], double& ucx, double& ucy) {
+  elem_rec_pin(ce);
+#pragma unroll
+  for (int j = 0; j < M; ++j) elem_rec_pin(bb[j]);
+#pragma unroll
+  for (int j = 0; j < M; ++j) elem_rec_pin(uu[j]);
+  elem_rec_pin(ucx);
+  elem_rec_pin(ucy);
+}
+
+// what a sweep reads of the record: q_e, pcol and column r_sup of B^{-1} -- four words of the packed triangle
+template <int M>
+struct ElemRecStencil {
+  double q[M], pc[M], br[M];
+  __device__ __forceinline__ void load(const double* rec, int r_sup) {
+#pragma unroll
+    for (int j = 0; j < M; j += 2) elem_ld2(rec + kElemRecQrow + j, q[j], q[j + 1]);
+#pragma unroll
+    for (int j = 0; j < M; j += 2) elem_ld2(rec + kElemRecPcol + j, pc[j], pc[j + 1]);
+#pragma unroll
+    for (int i = 0; i < M; ++i) br[i] = rec[kElemRecBsym + (i < r_sup ? elem_tri<M>(i, r_sup) : elem_tri<M>(r_sup, i))];
+  }
+};
+// g = B^{-1} b from the record's packed triangle
+template <int M>
+__device__ __forceinline__ void elem_rec_g(const double* rec, const double (&bb)[M], double (&g)[M]) {
+  constexpr int T = M * (M + 1) / 2;
+  double tri[T];
+#pragma unroll
+  for (int k = 0; k < T; k += 2) elem_ld2(rec + kElemRecBsym + k, tri[k], tri[k + 1]);
+#pragma unroll
+  for (int i = 0; i < M; ++i) g[i] = elem_sym_row_apply<M>(tri, i, bb);
+}
+// one block-Jacobi sweep cur -> nxt and its barrier: u + w (g - pcol u-[c_sub] - B^{-1}[:, r_sup] (q . u+) - u), plus the
+// prolongation's terms where ADD says so (the replaying ascent's last pre-sweep)
+template <int M, bool ADD>
+__device__ __forceinline__ void elem_rec_sweep(const ElemRecStencil<M>& st, double*& cur, double*& nxt, int x, int c_sub,
+                                               double w, bool valid, const double (&g)[M], double (&uu)[M],
+                                               const double* luc) {
+  constexpr int S = kElemThreads + 2;
+  const double um = cur[c_sub * S + x - 1];
+  double up[M];
+#pragma unroll
+  for (int j = 0; j < M; ++j) up[j] = cur[j * S + x + 1];
+  double dlo, dhi;
+  elem_group_dot4(st.q, up, dlo, dhi);
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    double acc = __fma_rn(-st.pc[i], um, g[i]);
+    acc = __fma_rn(-st.br[i], i < 2 ? dlo : dhi, acc);
+    double un = __fma_rn(w, __dadd_rn(acc, -uu[i]), uu[i]);
+    if constexpr (ADD) un = __dadd_rn(un, luc[i]);
+    if (!valid) un = 0.0;
+    uu[i] = un;
+    nxt[i * S + x] = un;
+  }
+  __syncthreads();
+  double* t = cur;
+  cur = nxt;
+  nxt = t;
+}
+__device__ __forceinline__ void elem_rec_st_iterate(double* op, const double (&uu)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; j += 2) {
+    elem_v2d v;
+    v.x = uu[j];
+    v.y = uu[j + 1];
+#if AGGMG_NT & 2
+    __builtin_nontemporal_store(v, reinterpret_cast<elem_v2d*>(op + j));
+#else
+    *reinterpret_cast<elem_v2d*>(op + j) = v;
+#endif
+  }
+}
+
+// btd_elem_dict_kernel with the class table in LDS.  RES: the launch forms and restricts the explicit residual, from the
+// lossless symmetric form (btd_elem_dict_kernel<M, true>'s launches: the descent, the launch between two cycles);
+// otherwise it ends with the iterate (the storing ascent).  What the launcher guarantees beyond btd_elem_dict_kernel's
+// conditions: t.rec is the level's table, 1 <= t.nclasses <= kElemRecMaxClasses, every cls word is below t.nclasses, the
+// launch's LDS is elem_rec_lds_bytes<M>(t.nclasses), RES == (a.do_residual != 0), and a residual launch has dup / corr.
+template <int M, bool RES>
+__global__ __launch_bounds__(kElemThreads) void btd_elem_rec_kernel(FusedArgs a, SweepWeights wts, ElemRecTab t) {
+  static_assert(M == 4, "the element-thread kernel's block size");
+  constexpr int TE = kElemThreads;
+  constexpr int S = TE + 2;            // words of one component in a buffer
+  constexpr int T = M * (M + 1) / 2;
+  extern __shared__ double lds[];
+  double* cur = lds + 1;               // (j, x) at cur[j * S + x]
+  double* nxt = lds + M * S + 1;
+  double* const tab = lds + 2 * M * S; // the class table, behind the two buffers (16-byte aligned: 2 M S is even)
+
+  const int x = threadIdx.x;
+  const int64_t ne = a.lv.ne;
+  const int64_t e0 = fused_tile(a) * a.owned - a.halo_left;   // element at x = 0
+  const int own0 = a.halo_left, own1 = a.halo_left + a.owned;
+  const int64_t rem = ne - 1 - e0;
+  if (rem < 0) return;   // a tile wholly past the level: before any barrier
+  const int xlo = e0 < 0 ? (int)-e0 : 0, xhi = rem < TE - 1 ? (int)rem : TE - 1;
+  const bool valid = x >= xlo && x <= xhi;
+  const bool own = valid && x >= own0 && x < own1;
+  const unsigned xc = (unsigned)(x < xlo ? xlo : x > xhi ? xhi : x);
+
+  // ---- loads: the table first, then cls, b, u_in, the coarse pair -- the only global loads of the launch (but the
+  // escapes'); the table is stored and its barrier passed while the others are in flight ---------------------------------
+  elem_v2d tv[kElemRecStage];
+  elem_rec_fetch(t, x, tv);
+  const bool pro = a.lf_in != nullptr;
+  unsigned ce = (a.lv.cls + e0)[xc];
+  double bb[M], uu[M];
+  {
+    const double* const bp = a.b + e0 * M + xc * M;
+    const double* const up = (a.u_in ? a.u_in : a.b) + e0 * M + xc * M;   // (no first iterate: b's line again, dropped)
+#pragma unroll
+    for (int j = 0; j < M; j += 2) elem_ld2(bp + j, bb[j], bb[j + 1]);
+#pragma unroll
+    for (int j = 0; j < M; j += 2) elem_ld2(up + j, uu[j], uu[j + 1]);
+  }
+  double ucx = 0.0, ucy = 0.0;
+  if (pro) {
+    const int64_t J = ne <= 0x7fffffff ? (int64_t)((unsigned)(e0 + xc) / (unsigned)a.rho_in) : (e0 + xc) / a.rho_in;
+    elem_ld2(a.uc + J * 2, ucx, ucy);
+  }
+  elem_rec_store(tab, t, x, tv);
+  if (x < 4 * M) {   // the zero elements at the ends of both buffers
+    const int j = x & (M - 1), w = x / M;
+    (w & 2 ? nxt : cur)[j * S + (w & 1 ? TE : -1)] = 0.0;
+  }
+  __syncthreads();
+  elem_rec_pin_all<M>(ce, bb, uu, ucx, ucy);
+  if (!a.u_in) {
+#pragma unroll
+    for (int j = 0; j < M; ++j) uu[j] = 0.0;
+  }
+
+  const double* const rec = tab + ce * kElemRecWords;
+  if (pro) {   // u += L uc: the second product rounded, the first fused into the sum
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      double lx, ly;
+      elem_ld2(rec + kElemRecLf + 2 * j, lx, ly);
+      uu[j] = __dadd_rn(uu[j], __fma_rn(lx, ucx, __dmul_rn(ly, ucy)));
+    }
+  }
+  if (!valid) {
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      uu[j] = 0.0;
+      bb[j] = 0.0;
+    }
+  }
+  double g[M];
+  elem_rec_g<M>(rec, bb, g);
+#pragma unroll
+  for (int i = 0; i < M; ++i) cur[i * S + x] = uu[i];
+  const int c_sub = a.lv.c_sub, r_sup = a.lv.r_sup;
+  ElemRecStencil<M> st;
+  st.load(rec, r_sup);   // held over the sweeps: re-reading per sweep measured 0.030 ms per cycle slower (r32)
+  __syncthreads();
+
+  for (int sw = 0; sw < a.nsweeps; ++sw)
+    elem_rec_sweep<M, false>(st, cur, nxt, x, c_sub, wts.w[(unsigned)sw], valid, g, uu, nullptr);
+
+  if (a.u_out && own) elem_rec_st_iterate(a.u_out + e0 * M + (unsigned)(x * M), uu);
+  if constexpr (RES) {
+    // ---- explicit residual r = b - A u of the element's rows (btd_elem_dict_kernel<M, true>'s), the record's words
+    // from LDS ---------------------------------------------------------------------------------------------------------
+    double D[M][M], sc[M];
+    {
+      double du[T];
+#pragma unroll
+      for (int k = 0; k < T; k += 2) elem_ld2(rec + kElemRecDup + k, du[k], du[k + 1]);
+      const uint4 w4 = *reinterpret_cast<const uint4*>(rec + kElemRecCorr);
+      const uint32_t w[M] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+      for (int j = 0; j < M; j += 2) elem_ld2(rec + kElemRecQmir + j, sc[j], sc[j + 1]);
+      bool esc = false;
+#pragma unroll
+      for (int i = 0; i < M; ++i) {
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+          if (j >= i) {
+            D[i][j] = du[elem_tri<M>(i, j)];
+          } else {
+            const int d = (int)(int8_t)(w[i] >> (8 * j));
+            D[i][j] = sym_residual_decode(du[elem_tri<M>(j, i)], d);
+            esc |= d == kSymResidualEscape;
+          }
+        }
+        const int dc = (int)(int8_t)(w[i] >> 24);
+        sc[i] = sym_residual_decode(sc[i], dc);
+        esc |= dc == kSymResidualEscape;
+      }
+      if (__builtin_expect(own && esc, 0)) {
+#pragma unroll
+        for (int i = 0; i < M; ++i) {
+#pragma unroll
+          for (int j = 0; j < i; ++j)
+            if ((int)(int8_t)(w[i] >> (8 * j)) == kSymResidualEscape) D[i][j] = a.lv.dblk[((int64_t)ce * M + i) * M + j];
+          if ((int)(int8_t)(w[i] >> 24) == kSymResidualEscape) sc[i] = a.lv.scol[(int64_t)ce * M + i];
+        }
+      }
+    }
+    double rr[M];
+    {
+      const double um = cur[c_sub * S + x - 1];
+      double up[M];
+#pragma unroll
+      for (int j = 0; j < M; ++j) up[j] = cur[j * S + x + 1];
+      double dlo, dhi;
+      elem_group_dot4(st.q, up, dlo, dhi);
+#pragma unroll
+      for (int i = 0; i < M; ++i) {
+        double s = __fma_rn(sc[i], um, 0.0);
+#pragma unroll
+        for (int j = 0; j < M; ++j) s = __fma_rn(D[i][j], uu[j], s);   // (a valid element's uu is its words of cur)
+        if (i == r_sup) s = __dadd_rn(s, i < 2 ? dlo : dhi);
+        rr[i] = own ? __dadd_rn(bb[i], -s) : 0.0;
+      }
+    }
+    // ---- restriction onto two coarse modes, through the (now free) iterate buffers, ascending fine row ----------------
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      double lx, ly;
+      elem_ld2(rec + kElemRecLf + 2 * i, lx, ly);
+      nxt[i * S + x] = own ? __dmul_rn(lx, rr[i]) : 0.0;
+      cur[i * S + x] = own ? __dmul_rn(ly, rr[i]) : 0.0;
+    }
+    __syncthreads();
+    const int rho = a.rho_out;
+    const int ncoarse = a.owned / rho;   // owned coarse elements of this tile
+    const int64_t J0 = fused_tile(a) * ncoarse;
+    for (int k2 = x; k2 < ncoarse * 2; k2 += TE) {
+      const int Jl = k2 >> 1, c = k2 & 1;
+      const int64_t J = J0 + Jl;
+      if (J >= a.nec_out) continue;
+      const double* pr = (c ? cur : nxt) + a.halo_left + Jl * rho;
+      double acc = 0.0;
+      for (int k = 0; k < rho; ++k) {
+#pragma unroll
+        for (int j = 0; j < M; ++j) acc = __dadd_rn(acc, pr[j * S + k]);
+      }
+      a.rc_out[J * 2 + c] = acc;
+    }
+  }
+}
+
+// btd_elem_replay_up_kernel with the class table in LDS: the same conditions, and btd_elem_rec_kernel's on the table.
+template <int M>
+__global__ __launch_bounds__(kElemThreads) void btd_elem_rec_replay_up_kernel(FusedArgs a, SweepWeights wts, int npre, ElemRecTab t) {
+  static_assert(M == 4, "the element-thread kernel's block size");
+  constexpr int TE = kElemThreads;
+  constexpr int S = TE + 2;            // words of one component in a buffer
+  extern __shared__ double lds[];
+  double* cur = lds + 1;               // (j, x) at cur[j * S + x]
+  double* nxt = lds + M * S + 1;
+  double* const tab = lds + 2 * M * S;
+
+  const int x = threadIdx.x;
+  const int64_t ne = a.lv.ne;
+  const int64_t e0 = fused_tile(a) * a.owned - a.halo_left;   // element at x = 0
+  const int own0 = a.halo_left, own1 = a.halo_left + a.owned;
+  const int64_t rem = ne - 1 - e0;
+  if (rem < 0) return;   // a tile wholly past the level: before any barrier
+  const int xlo = e0 < 0 ? (int)-e0 : 0, xhi = rem < TE - 1 ? (int)rem : TE - 1;
+  const bool valid = x >= xlo && x <= xhi;
+  const bool own = valid && x >= own0 && x < own1;
+  const unsigned xc = (unsigned)(x < xlo ? xlo : x > xhi ? xhi : x);
+
+  // ---- loads, straight-line: the table, then cls, b, u_in, the coarse pair ------------------------------------------------
+  elem_v2d tv[kElemRecStage];
+  elem_rec_fetch(t, x, tv);
+  unsigned ce = (a.lv.cls + e0)[xc];
+  double bb[M], uu[M];
+  {
+    const double* const bp = a.b + e0 * M + xc * M;
+    const double* const up = (a.u_in ? a.u_in : a.b) + e0 * M + xc * M;   // (no first iterate: b's line again, dropped)
+#pragma unroll
+    for (int j = 0; j < M; j += 2) elem_ld2(bp + j, bb[j], bb[j + 1]);
+#pragma unroll
+    for (int j = 0; j < M; j += 2) elem_ld2(up + j, uu[j], uu[j + 1]);
+  }
+  double ucx, ucy;
+  {
+    const int64_t J = ne <= 0x7fffffff ? (int64_t)((unsigned)(e0 + xc) / (unsigned)a.rho_in) : (e0 + xc) / a.rho_in;
+    elem_ld2(a.uc + J * 2, ucx, ucy);
+  }
+  elem_rec_store(tab, t, x, tv);
+  if (x < 4 * M) {   // the zero elements at the ends of both buffers
+    const int j = x & (M - 1), w = x / M;
+    (w & 2 ? nxt : cur)[j * S + (w & 1 ? TE : -1)] = 0.0;
+  }
+  __syncthreads();
+  elem_rec_pin_all<M>(ce, bb, uu, ucx, ucy);
+  if (!a.u_in) {
+#pragma unroll
+    for (int j = 0; j < M; ++j) uu[j] = 0.0;
+  }
+
+  const double* const rec = tab + ce * kElemRecWords;
+  // L uc of the element's rows: the second product rounded, the first fused into the sum
+  double luc[M];
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    double lx, ly;
+    elem_ld2(rec + kElemRecLf + 2 * j, lx, ly);
+    luc[j] = __fma_rn(lx, ucx, __dmul_rn(ly, ucy));
+  }
+  if (!valid) {
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      uu[j] = 0.0;
+      bb[j] = 0.0;
+    }
+  }
+  double g[M];
+  elem_rec_g<M>(rec, bb, g);
+#pragma unroll
+  for (int i = 0; i < M; ++i) cur[i * S + x] = uu[i];
+  const int c_sub = a.lv.c_sub, r_sup = a.lv.r_sup;
+  ElemRecStencil<M> st;
+  st.load(rec, r_sup);   // held over the sweeps: re-reading per sweep measured 0.030 ms per cycle slower (r32)
+  __syncthreads();
+
+  // (the sweep placed three times, as in btd_elem_replay_up_kernel: the sweeps that add nothing carry no select for it)
+  for (int sw = 0; sw < npre - 1; ++sw)
+    elem_rec_sweep<M, false>(st, cur, nxt, x, c_sub, wts.w[(unsigned)sw], valid, g, uu, nullptr);
+  elem_rec_sweep<M, true>(st, cur, nxt, x, c_sub, wts.w[(unsigned)(npre - 1)], valid, g, uu, luc);
+  for (int sw = npre; sw < a.nsweeps; ++sw)
+    elem_rec_sweep<M, false>(st, cur, nxt, x, c_sub, wts.w[(unsigned)sw], valid, g, uu, nullptr);
+
+  if (own) elem_rec_st_iterate(a.u_out + e0 * M + (unsigned)(x * M), uu);
 }
 
 }  // namespace aggmg

@@ -4,8 +4,10 @@
 // section 5: sanitizers on the CPU build only); the .hip files use exactly these functions.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 namespace aggmg {
@@ -547,6 +549,57 @@ inline bool dist_halo_ok(int nl, const int64_t* W, const int* ratio, const int* 
     if (v < 0) return false;
   }
   return true;
+}
+
+// ---- the class records of the element-thread kernels (elem_kernels.hpp, AGGMG_OPT_ELEMENT_RECORDS_LDS) ---------------
+// One record per class of a level with blocks of 4 rows, 16-byte groups: every operator word the kernels read for an
+// element, repacked on the host from the dictionary's arrays (DictDev) --
+//   [0]  the packed inverse (bsym), 10 words                 [10] pcol = B^{-1} q_{e-1}
+//   [14] q_e (qrow)            [18] q_{e-1} (qmir)           [22] the upper triangle of D_e (dup), 10 words
+//   [32] the four corr words   [34] lx0 ly0 .. lx3 ly3       (rows of L; a unit first column is stored as the 1.0 it
+//                                                            stands for)
+constexpr int kElemRecWords = 42;
+constexpr int kElemRecBsym = 0, kElemRecPcol = 10, kElemRecQrow = 14, kElemRecQmir = 18, kElemRecDup = 22, kElemRecCorr = 32,
+              kElemRecLf = 34;
+static_assert(kElemRecWords % 2 == 0 && kElemRecPcol % 2 == 0 && kElemRecQrow % 2 == 0 && kElemRecQmir % 2 == 0 &&
+                  kElemRecDup % 2 == 0 && kElemRecCorr % 2 == 0 && kElemRecLf % 2 == 0,
+              "the groups of a record are read 16 bytes at a time");
+// Most classes of a level these kernels take (a level with more keeps the kernels above).  A launch's LDS follows the
+// level's class count: elem_lds_bytes<4>() = 16512 bytes of iterate buffers and 336 per class.  The registers allow 6
+// workgroups per CU where they are fewest (80 VGPRs in the launch that forms the residual: 6 waves per SIMD; 87 in the
+// replaying ascent: 5), and 6 workgroups share 163840 bytes of LDS: 27306 each, so (27306 - 16512) / 336 = 32 classes is
+// the largest table that costs no workgroup -- 6 x (16512 + 32 x 336) = 163584 (profiles/r32_elem_records_lds.md).
+#ifndef AGGMG_ELEM_REC_MAX_CLASSES
+#define AGGMG_ELEM_REC_MAX_CLASSES 32
+#endif
+constexpr int kElemRecMaxClasses = AGGMG_ELEM_REC_MAX_CLASSES;
+// rec [nclasses][kElemRecWords] from bsym [nclasses][10], qrow / qmir [nclasses][4], dup [nclasses][10] and corr
+// [nclasses][4] (both null on a level without the symmetric residual form: zeros), lf [nclasses][4] (lf_unit: the second
+// entries of the rows of L) or [nclasses][4][2] (the rows).  pcol is the kernels' chain (elem_sym_row_apply): row i of
+// the symmetric inverse times q_{e-1}, fma(tri[.], qm[j], acc) with j ascending from 0.0 -- std::fma rounds once, as
+// the device's fma does, so the words are the ones the kernels formed per element.
+inline void elem_record_pack(int nclasses, const double* bsym, const double* qrow, const double* qmir, const double* dup,
+                             const uint32_t* corr, const double* lf, bool lf_unit, double* rec) {
+  constexpr int M = 4, T = 10;
+  auto tri = [](int i, int j) { return i * M - (i * (i - 1)) / 2 + (j - i); };   // (i <= j) as elem_tri<4>
+  for (int c = 0; c < nclasses; ++c) {
+    double* r = rec + (size_t)c * kElemRecWords;
+    for (int k = 0; k < kElemRecWords; ++k) r[k] = 0.0;
+    for (int k = 0; k < T; ++k) r[kElemRecBsym + k] = bsym[c * T + k];
+    for (int i = 0; i < M; ++i) {
+      double acc = 0.0;
+      for (int j = 0; j < M; ++j) acc = std::fma(bsym[c * T + (i < j ? tri(i, j) : tri(j, i))], qmir[c * M + j], acc);
+      r[kElemRecPcol + i] = acc;
+      r[kElemRecQrow + i] = qrow[c * M + i];
+      r[kElemRecQmir + i] = qmir[c * M + i];
+      r[kElemRecLf + 2 * i] = lf_unit ? 1.0 : lf[(c * M + i) * 2];
+      r[kElemRecLf + 2 * i + 1] = lf_unit ? lf[c * M + i] : lf[(c * M + i) * 2 + 1];
+    }
+    if (dup && corr) {
+      for (int k = 0; k < T; ++k) r[kElemRecDup + k] = dup[c * T + k];
+      std::memcpy(r + kElemRecCorr, corr + c * M, M * sizeof(uint32_t));
+    }
+  }
 }
 
 }  // namespace aggmg

@@ -75,6 +75,10 @@ struct aggmg_ctx {
   int64_t elem_launches = 0;   // launches of the element-thread kernel so far (aggmg_element_thread_launches)
   bool pair_elem_threads = [] { const char* e = std::getenv("AGGMG_PAIR_ELEM_THREADS"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_PAIR_ELEMENT_THREADS
   int64_t pair_elem_launches = 0;   // launches of the element-thread pair kernels so far (aggmg_pair_element_thread_launches)
+  // AGGMG_OPT_ELEMENT_RECORDS_LDS: most classes of a level whose element-thread launches keep the class records in LDS
+  // (0: off; at most kElemRecMaxClasses, host_plan.hpp)
+  int elem_rec_cap = [] { const char* e = std::getenv("AGGMG_ELEM_RECORDS_LDS"); return (e && e[0] == '0') ? 0 : kElemRecMaxClasses; }();
+  int64_t elem_rec_launches = 0;   // launches of those kernels so far (aggmg_element_record_lds_launches)
   bool replay_presmooth = [] { const char* e = std::getenv("AGGMG_REPLAY_PRESMOOTH"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_REPLAY_PRESMOOTH
   int64_t replay_launches = 0;   // replayed cycles so far (aggmg_replay_launches)
   bool patch_multi = [] { const char* e = std::getenv("AGGMG_PATCH_MULTI"); return e && e[0] == '1'; }();  // AGGMG_OPT_PATCH_MULTI (default 0)
@@ -272,6 +276,10 @@ struct DictDev {
   DevArray<uint32_t> corr;
   DevArray<double> lf;       // [nclasses][m] second entries (the transfer has lf1), else [nclasses][m][2] rows of L
   bool lf_unit = false;      // lf holds the lf1 form
+  // blocks of 4 rows: the same words once more, one record of kElemRecWords per class (host_plan.hpp, elem_record_pack:
+  // what the element-thread launches copy into LDS under AGGMG_OPT_ELEMENT_RECORDS_LDS); only for a level of at most
+  // kElemRecMaxClasses classes, else null
+  DevArray<double> rec;
 };
 
 // operator dictionary of a level the two-level launches take (PairLevel::cls in pair_kernels.hpp; the same search as

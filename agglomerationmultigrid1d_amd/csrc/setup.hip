@@ -632,6 +632,31 @@ int setup_op_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, s
   F.add(b.dblk, &d->dblk, m * m);
   F.add(t.lf1 ? t.lf1 : t.lf, &d->lf, m * (t.lf1 ? 1 : 2));
   CHECK(dict_build(ctx, F, &d->cls, &d->nclasses));
+  if (m == 4 && d->nclasses > 0 && d->nclasses <= kElemRecMaxClasses) {
+    // the record of every class once more in the layout the element-thread kernels copy into LDS (host_plan.hpp,
+    // elem_record_pack), pcol = B^{-1} q_{e-1} with it: a few KB, repacked on the host
+    const int nc = d->nclasses, nl = d->lf_unit ? m : 2 * m;
+    std::vector<double> hb((size_t)T * nc), hq((size_t)m * nc), hm((size_t)m * nc), hd(b.dup ? (size_t)T * nc : 0), hl((size_t)nl * nc);
+    std::vector<uint32_t> hc(b.dup ? (size_t)m * nc : 0);
+    std::vector<double> rec((size_t)nc * kElemRecWords);
+    auto down = [&](auto& v, const auto* src) {
+      return hipMemcpyAsync(v.data(), src, v.size() * sizeof(v[0]), hipMemcpyDeviceToHost, ctx->stream);
+    };
+    HIPCHK(down(hb, d->bsym.get()));
+    HIPCHK(down(hq, d->qrow.get()));
+    HIPCHK(down(hm, d->qmir.get()));
+    if (b.dup) {
+      HIPCHK(down(hd, d->dup.get()));
+      HIPCHK(down(hc, d->corr.get()));
+    }
+    HIPCHK(down(hl, d->lf.get()));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    elem_record_pack(nc, hb.data(), hq.data(), hm.data(), b.dup ? hd.data() : nullptr, b.dup ? hc.data() : nullptr, hl.data(),
+                     d->lf_unit, rec.data());
+    CHECK(d->rec.alloc(ctx, (int64_t)rec.size()));
+    HIPCHK(hipMemcpyAsync(d->rec, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // (the host vector is done with)
+  }
   if (d->nclasses > 0) *out = std::move(d);
   return AGGMG_OK;
 }

@@ -185,7 +185,35 @@ int aggmg_synchronize(aggmg_ctx* ctx);
  * patch levels.  Every result is bit for bit the same with the option on or off.  Read at every call.
  * aggmg_chain_multi_launches counts the launches of the K-column chain kernel. */
 #define AGGMG_OPT_CHAIN_MULTI 12
+/* AGGMG_OPT_ELEMENT_RECORDS_LDS (default 32; environment AGGMG_ELEM_RECORDS_LDS=0 makes the default 0): the
+ * element-thread launches (AGGMG_OPT_ELEMENT_THREADS: descent, ascent, the launch between two cycles, the replaying
+ * ascent) on a level with at most `value` classes copy the level's table of class records -- one packed record of 336
+ * bytes per class: the packed inverse, B^{-1} q_{e-1} formed once at set-up, both coupling rows, the residual's
+ * symmetric form, the rows of the transfer -- into LDS at entry, with loads issued ahead of the streaming ones, and read
+ * every operator word from LDS where it is used; after the entry phase they issue no global load but the escapes of the
+ * symmetric residual form (btd_elem_rec_kernel, btd_elem_rec_replay_up_kernel; profiles/r32_elem_records_lds.md).
+ * Every result is bit for bit the same.  value: 0 switches it off; 1 .. 32 is the cap on classes -- 32 is the largest
+ * table that leaves the six workgroups per CU the kernels' registers allow (6 x (16512 + 32 x 336) <= 160 KiB); other
+ * values are an error.  Read at every launch.  Levels with more classes, levels whose residual does not have the
+ * symmetric form (AGGMG_OPT_SYMMETRIC_RESIDUAL 0) and every launch the element-thread kernels do not take keep their
+ * kernels either way.  aggmg_element_record_lds_launches counts the launches served (each also counts in
+ * aggmg_element_thread_launches); aggmg_element_record_lds_cap returns the cap in force. */
+#define AGGMG_OPT_ELEMENT_RECORDS_LDS 13
 int aggmg_set_option(aggmg_ctx* ctx, int option, int value);
+/* Launches of the element-thread kernels with the class records in LDS (AGGMG_OPT_ELEMENT_RECORDS_LDS) on this context
+ * so far. */
+int aggmg_element_record_lds_launches(aggmg_ctx* ctx, int64_t* count);
+/* The cap on classes in force (AGGMG_OPT_ELEMENT_RECORDS_LDS; 0: off) and, where max_cap is not NULL, the largest value
+ * the option takes. */
+int aggmg_element_record_lds_cap(aggmg_ctx* ctx, int* cap, int* max_cap);
+/* A test and diagnostic hook, not part of what a solver calls: the host repack behind those records (needs no context,
+ * no device), exposed so that the record's layout and its precomputed words can be checked without a GPU: rec [nclasses][*words] from the dictionary's
+ * arrays of a level with blocks of 4 rows -- bsym [nclasses][10], qrow and qmir [nclasses][4], dup [nclasses][10] and
+ * corr [nclasses][4] (both NULL: zeros), lf [nclasses][4] second entries (lf_unit != 0) or [nclasses][4][2] rows.  Word
+ * offsets in a record: bsym 0, pcol 10, qrow 14, qmir 18, dup 22, corr 32 (four 32-bit words), rows of L 34.  *words
+ * (may be NULL) receives the record's length in doubles, also when nclasses == 0. */
+int aggmg_element_record_pack(int nclasses, const double* bsym, const double* qrow, const double* qmir, const double* dup,
+                              const uint32_t* corr, const double* lf, int lf_unit, double* rec, int* words);
 /* Launches of the element-thread kernel (AGGMG_OPT_ELEMENT_THREADS) on this context so far. */
 int aggmg_element_thread_launches(aggmg_ctx* ctx, int64_t* count);
 /* Launches of the element-thread two-level kernels (AGGMG_OPT_PAIR_ELEMENT_THREADS) on this context so far. */

@@ -324,6 +324,22 @@ function chain_multi_launches(ctx::Context)
     check(ctx.h, ccall((:aggmg_chain_multi_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
     return r[]
 end
+# AGGMG_OPT_ELEMENT_RECORDS_LDS (default 32; environment AGGMG_ELEM_RECORDS_LDS=0 makes the default 0): the element-thread
+# launches on a level with at most that many classes keep the class records in LDS -- the same bits; 0 switches it off.
+# element_record_lds_launches(ctx): how many launches those kernels have served.
+const OPT_ELEMENT_RECORDS_LDS = 13
+function element_record_lds_launches(ctx::Context)
+    r = Ref{Int64}(0)
+    check(ctx.h, ccall((:aggmg_element_record_lds_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
+    return r[]
+end
+# (cap on classes in force, largest cap the option takes)
+function element_record_lds_cap(ctx::Context)
+    c = Ref{Cint}(0)
+    m = Ref{Cint}(0)
+    check(ctx.h, ccall((:aggmg_element_record_lds_cap, LIB), Cint, (Handle, Ref{Cint}, Ref{Cint}), ctx.h, c, m))
+    return (Int(c[]), Int(m[]))
+end
 function set_option!(ctx::Context, option::Integer, value::Integer)
     check(ctx.h, ccall((:aggmg_set_option, LIB), Cint, (Handle, Cint, Cint), ctx.h, option, value))
     return ctx
