@@ -485,16 +485,10 @@ static int launch_csr(aggmg_ctx* ctx, const CsrDev& A, const double* x, const do
   if (nblk >= ((int64_t)1 << 31)) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "grid too large");
   dim3 grid((unsigned)nblk), block(kThreads);
   CsrView v = A.view();
-  switch (lpr) {
-#define CASE(L)                                                                             \
-  case L:                                                                                   \
-    hipLaunchKernelGGL((csr_row_kernel<L, MODE>), grid, block, 0, ctx->stream, v, x, b, dg, alpha, y); \
-    break;
-    CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
-#undef CASE
-    default:
-      return fail(ctx, AGGMG_ERR_UNSUPPORTED, "bad lanes-per-row");
-  }
+  if (!with_block_size<csr_lanes_form, 64>(lpr, [&](auto l) {
+        hipLaunchKernelGGL((csr_row_kernel<decltype(l)::value, MODE>), grid, block, 0, ctx->stream, v, x, b, dg, alpha, y);
+      }))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "bad lanes-per-row");
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
@@ -654,16 +648,16 @@ static int launch_btd_t(aggmg_ctx* ctx, FusedLaunch a, int halo, const TileSel& 
   // residual rows' operator entries are parked in between a checkpoint and the later residuals of the launch)
   const size_t lds = (size_t)2 * (T::TE + 2) * M * sizeof(double) +
                      (chk ? ((size_t)2 * (T::NT / 64) + (CMP ? (size_t)T::NT * T::NS * (M + 1) : 0)) * sizeof(double) : 0);
-  constexpr bool kGrp = (CMP && (M == 2 || M == 4 || M == 8)) || (!CMP && (M == 2 || M == 4));
+  constexpr bool kGrp = btd_sym_form(M, CMP);
   const bool sym = kGrp && a.lv.bsym;
   // the lossless symmetric form of the residual's entries: block-Jacobi launches that form the explicit residual
-  constexpr bool kSres = kGrp && CMP && M <= 4;
+  constexpr bool kSres = btd_sres_form(M, CMP);
   const bool sres = kSres && a.lv.dup && !a.gs && !chk && a.do_residual && (a.r_out || a.lf_out);
   // instantiations per (M, CMP): symmetric packing x (block-Jacobi / red-black GS / block-Jacobi with checkpoint)
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, static_cast<const FusedArgs&>(a), a.wts);
   };
-  if constexpr (kGrp && CMP && M <= 4) {
+  if constexpr (kSres) {
     // the operator dictionary (fused_dictionary put its arrays in place of the full ones): block-Jacobi launches
     if (sym && a.lv.cls) {
       if (a.gs || chk) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: dictionary launch of a Gauss-Seidel / checkpoint variant");
@@ -736,28 +730,10 @@ static int btd_max_halo() {
   return (BtdTile<M, CMP>::TE - 8) / 2;
 }
 
-// The (M, CMP) the fused kernel is instantiated for, the one list of them: f(BtdTile<M, CMP>()) for the form that
-// serves b; false when there is none.
+// f(BtdTile<M, CMP>()) for the form of btd_form (forms.hpp) that serves b; false when there is none.
 template <class F>
 static bool btd_with_tile(const BtdDev& b, F&& f) {
-#define CASE(MM)                        \
-  case MM:                              \
-    if (b.cmp) f(BtdTile<MM, true>());  \
-    else f(BtdTile<MM, false>());       \
-    return true;
-#define CASE_C(MM)           \
-  case MM:                   \
-    f(BtdTile<MM, true>());  \
-    return true;
-  switch (b.m) {
-    case 1:
-      f(BtdTile<1, false>());
-      return true;
-      CASE(2) CASE(3) CASE(4) CASE(5) CASE_C(6) CASE_C(7) CASE_C(8) CASE_C(9)
-  }
-#undef CASE
-#undef CASE_C
-  return false;
+  return with_form<btd_form>(b.m, b.cmp, [&](auto t) { f(BtdTile<decltype(t)::kM, decltype(t)::kCmp>()); });
 }
 
 static int launch_btd(aggmg_ctx* ctx, const BtdDev& b, const FusedLaunch& a, int halo, const TileSel& sel = TileSel(),
@@ -916,136 +892,96 @@ static int btd_smooth(aggmg_ctx* ctx, const BtdDev& b, const double* u_in, const
 // ---------------------------------------------------------------------------------------------
 static_assert(kPatchMaxSweeps == kSweepWeights, "a patch launch takes as many sweeps as its weights array holds");
 
-// The (M, couplings) patch_sweep_kernel is instantiated for: every element-block form set-up produces (compressed
-// couplings 2 .. 9, dense ones 1 .. 5) up to 8 rows per element.  None of them needs scratch.
-static bool patch_instantiated(int m, bool cmp) { return cmp ? (m >= 2 && m <= 8) : (m >= 1 && m <= 5); }
+// (the forms the patch kernels are instantiated for: patch_form, forms.hpp.  None of them needs scratch: DESIGN.md section 19)
 
-// cls: the classes of the smoother's dictionary -- a's operator arrays are the dictionary's then (patch_smooth) -- or null
-template <int M, bool CMP>
-static int launch_patch_t(aggmg_ctx* ctx, PatchArgs a, const SweepWeights& wts, bool hybrid, const uint16_t* cls) {
-  constexpr int NS = PatchSlabs<M>::NS;
-  static_assert(NS == patch_slabs(M), "the planner sizes the tile the kernel is instantiated for");
-  const PatchTilePlan plan = patch_tile_plan(M, a.nsweeps);   // host_plan.hpp
-  if (plan.owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: patch sweep launch without a tile");
-  a.owned = plan.owned;
-  a.halo = plan.halo;
-  const int64_t ntiles = patch_tiles(a.ne, plan.owned);
-  if (ntiles == 0) return AGGMG_OK;
-  if (cls) {
-    if (hybrid)
-      hipLaunchKernelGGL((patch_sweep_dict_kernel<M, CMP, NS, true>), dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, a, wts, cls);
-    else
-      hipLaunchKernelGGL((patch_sweep_dict_kernel<M, CMP, NS, false>), dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, a, wts, cls);
-  } else if (hybrid)
-    hipLaunchKernelGGL((patch_sweep_kernel<M, CMP, NS, true>), dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, a, wts);
-  else
-    hipLaunchKernelGGL((patch_sweep_kernel<M, CMP, NS, false>), dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, a, wts);
-  HIPCHK(hipGetLastError());
-  return AGGMG_OK;
-}
-
-static int launch_patch(aggmg_ctx* ctx, const PatchDev& P, const PatchArgs& a, const SweepWeights& wts, const uint16_t* cls) {
-  const bool cmp = P.btd->cmp;
-#define CASE(MM)                                                             \
-  case MM:                                                                   \
-    return cmp ? launch_patch_t<MM, true>(ctx, a, wts, P.hybrid, cls) : launch_patch_t<MM, false>(ctx, a, wts, P.hybrid, cls);
-#define CASE_C(MM) \
-  case MM:         \
-    if (cmp) return launch_patch_t<MM, true>(ctx, a, wts, P.hybrid, cls); \
-    break;
-  switch (P.m) {
-    case 1:
-      if (!cmp) return launch_patch_t<1, false>(ctx, a, wts, P.hybrid, cls);
-      break;
-      CASE(2) CASE(3) CASE(4) CASE(5) CASE_C(6) CASE_C(7) CASE_C(8)
+// The arguments of s sweeps from src into dst.  A smoother with an operator dictionary gets its arrays in place of the full
+// ones -- the same bits, read by the element's class -- and launches the dictionary kernels (patch_cls).
+static PatchArgs patch_args(const PatchDev& P, const double* src, const double* rhs, double* dst, int s) {
+  const BtdDev& b = *P.btd;
+  PatchArgs a{b.dblk, b.scol, b.qrow, b.sub, b.sup, P.zrows, P.ne, b.c_sub, b.r_sup, src, rhs, dst, s, 0, 0};
+  if (const PatchDictDev* d = P.dict.get()) {
+    a.dblk = d->dblk;
+    a.scol = d->scol;
+    a.qrow = d->qrow;
+    a.sub = d->sub;
+    a.sup = d->sup;
+    a.zrows = d->zrows;
   }
-#undef CASE
-#undef CASE_C
-  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: block size not instantiated for the patch sweep kernel");
+  return a;
 }
+static const uint16_t* patch_cls(const PatchDev& P) { return P.dict ? P.dict->cls.get() : nullptr; }
 
-// the multiplicative two-colour sweeps (aggmg_patch_gs_setup): patch_gs_kernel in the tile of patch_gs_tile_plan
-template <int M, bool CMP>
-static int launch_patch_gs_t(aggmg_ctx* ctx, PatchArgs a, const SweepWeights& wts, bool reverse, const uint16_t* cls) {
-  constexpr int NS = PatchSlabs<M>::NS;
-  static_assert(NS == patch_slabs(M), "the planner sizes the tile the kernel is instantiated for");
-  const PatchTilePlan plan = patch_gs_tile_plan(M, a.nsweeps);   // host_plan.hpp
-  if (plan.owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: multiplicative patch sweep launch without a tile");
-  a.owned = plan.owned;
-  a.halo = plan.halo;
-  const int64_t ntiles = patch_tiles(a.ne, plan.owned);
-  if (ntiles == 0) return AGGMG_OK;
-  const PatchGsArgs g{a, reverse ? 1 : 0};
-  if (cls)
-    hipLaunchKernelGGL((patch_gs_dict_kernel<M, CMP, NS>), dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, g, wts, cls);
-  else
-    hipLaunchKernelGGL((patch_gs_kernel<M, CMP, NS>), dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, g, wts);
-  HIPCHK(hipGetLastError());
-  return AGGMG_OK;
-}
-
-static int launch_patch_gs(aggmg_ctx* ctx, const PatchDev& P, const PatchArgs& a, const SweepWeights& wts, bool reverse,
-                           const uint16_t* cls) {
-  const bool cmp = P.btd->cmp;
-#define CASE(MM)                                                             \
-  case MM:                                                                   \
-    return cmp ? launch_patch_gs_t<MM, true>(ctx, a, wts, reverse, cls) : launch_patch_gs_t<MM, false>(ctx, a, wts, reverse, cls);
-#define CASE_C(MM) \
-  case MM:         \
-    if (cmp) return launch_patch_gs_t<MM, true>(ctx, a, wts, reverse, cls); \
-    break;
-  switch (P.m) {
-    case 1:
-      if (!cmp) return launch_patch_gs_t<1, false>(ctx, a, wts, reverse, cls);
-      break;
-      CASE(2) CASE(3) CASE(4) CASE(5) CASE_C(6) CASE_C(7) CASE_C(8)
-  }
-#undef CASE
-#undef CASE_C
-  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: block size not instantiated for the multiplicative patch sweep kernel");
-}
-
-// the one-launch ascent of a multiplicative patch level (patch_gs_up_kernel): prolongation and nsweeps <= patch_gs_max_sweeps
-// reverse sweeps on the tiles sel chooses (fused_tile_subset with the sweep launch's owned size), the same tile plan
-template <int M, bool CMP>
-static int launch_patch_gs_up_t(aggmg_ctx* ctx, PatchGsUpArgs u, const SweepWeights& wts, const TileSel& sel, const uint16_t* cls) {
-  constexpr int NS = PatchSlabs<M>::NS;
-  PatchArgs& a = u.g.p;
-  const PatchTilePlan plan = patch_gs_tile_plan(M, a.nsweeps);   // host_plan.hpp
-  if (plan.owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: multiplicative patch ascent launch without a tile");
+// What every patch launch does before and around its kernel: the planner's tile (host_plan.hpp) into a, the tiles sel
+// chooses of a's elements (fused_tile_subset; default: all), and go(Form<M, CMP>, tiles, lds bytes) for the smoother's
+// form among those of Pred (forms.hpp).  go launches `what`'s kernel on its own argument struct, which holds a.
+template <auto Pred, class Go>
+static int launch_patch_tiles(aggmg_ctx* ctx, const PatchDev& P, PatchArgs& a, const PatchTilePlan& plan, const TileSel& sel,
+                              const char* what, Go&& go) {
+  if (!P.btd || !Pred(P.m, P.btd->cmp))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, std::string("internal: block size not instantiated for the ") + what + " kernel");
+  if (plan.owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, std::string("internal: ") + what + " launch without a tile");
   a.owned = plan.owned;
   a.halo = plan.halo;
   const TileSubset sub = fused_tile_subset(a.ne, plan.owned, sel.mode == 3 ? 0 : sel.mode, sel.head, sel.tail);
-  u.tile_split = sub.split;
-  u.tile_skip = sub.skip;
   if (sub.ntiles == 0) return AGGMG_OK;
-  if (cls)
-    hipLaunchKernelGGL((patch_gs_up_dict_kernel<M, CMP, NS>), dim3((unsigned)sub.ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, u, wts, cls);
-  else
-    hipLaunchKernelGGL((patch_gs_up_kernel<M, CMP, NS>), dim3((unsigned)sub.ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, u, wts);
+  with_form<Pred>(P.m, P.btd->cmp, [&](auto f) {
+    static_assert(PatchSlabs<decltype(f)::kM>::NS == patch_slabs(decltype(f)::kM), "the planner sizes the tile the kernel is instantiated for");
+    go(f, sub, plan.lds_bytes);
+  });
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
 
-static int launch_patch_gs_up(aggmg_ctx* ctx, const PatchDev& P, const PatchGsUpArgs& u, const SweepWeights& wts, const TileSel& sel,
-                              const uint16_t* cls) {
-  const bool cmp = P.btd->cmp;
-#define CASE(MM)                                                             \
-  case MM:                                                                   \
-    return cmp ? launch_patch_gs_up_t<MM, true>(ctx, u, wts, sel, cls) : launch_patch_gs_up_t<MM, false>(ctx, u, wts, sel, cls);
-#define CASE_C(MM) \
-  case MM:         \
-    if (cmp) return launch_patch_gs_up_t<MM, true>(ctx, u, wts, sel, cls); \
-    break;
-  switch (P.m) {
-    case 1:
-      if (!cmp) return launch_patch_gs_up_t<1, false>(ctx, u, wts, sel, cls);
-      break;
-      CASE(2) CASE(3) CASE(4) CASE(5) CASE_C(6) CASE_C(7) CASE_C(8)
-  }
-#undef CASE
-#undef CASE_C
-  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: block size not instantiated for the multiplicative patch ascent kernel");
+static int launch_patch(aggmg_ctx* ctx, const PatchDev& P, PatchArgs a, const SweepWeights& wts) {
+  const uint16_t* cls = patch_cls(P);
+  return launch_patch_tiles<patch_form>(ctx, P, a, patch_tile_plan(P.m, a.nsweeps), TileSel(), "patch sweep", [&](auto f, const TileSubset& t, size_t lds) {
+    using F = decltype(f);
+    constexpr int NS = PatchSlabs<F::kM>::NS;
+    const dim3 grid((unsigned)t.ntiles), block(kThreads);
+    if (cls) {
+      if (P.hybrid)
+        hipLaunchKernelGGL((patch_sweep_dict_kernel<F::kM, F::kCmp, NS, true>), grid, block, lds, ctx->stream, a, wts, cls);
+      else
+        hipLaunchKernelGGL((patch_sweep_dict_kernel<F::kM, F::kCmp, NS, false>), grid, block, lds, ctx->stream, a, wts, cls);
+    } else if (P.hybrid)
+      hipLaunchKernelGGL((patch_sweep_kernel<F::kM, F::kCmp, NS, true>), grid, block, lds, ctx->stream, a, wts);
+    else
+      hipLaunchKernelGGL((patch_sweep_kernel<F::kM, F::kCmp, NS, false>), grid, block, lds, ctx->stream, a, wts);
+  });
+}
+
+// the multiplicative two-colour sweeps (aggmg_patch_gs_setup): patch_gs_kernel in the tile of patch_gs_tile_plan
+static int launch_patch_gs(aggmg_ctx* ctx, const PatchDev& P, const PatchArgs& a, const SweepWeights& wts, bool reverse) {
+  const uint16_t* cls = patch_cls(P);
+  PatchGsArgs g{a, reverse ? 1 : 0};
+  return launch_patch_tiles<patch_form>(ctx, P, g.p, patch_gs_tile_plan(P.m, a.nsweeps), TileSel(), "multiplicative patch sweep",
+                                        [&](auto f, const TileSubset& t, size_t lds) {
+    using F = decltype(f);
+    constexpr int NS = PatchSlabs<F::kM>::NS;
+    const dim3 grid((unsigned)t.ntiles), block(kThreads);
+    if (cls)
+      hipLaunchKernelGGL((patch_gs_dict_kernel<F::kM, F::kCmp, NS>), grid, block, lds, ctx->stream, g, wts, cls);
+    else
+      hipLaunchKernelGGL((patch_gs_kernel<F::kM, F::kCmp, NS>), grid, block, lds, ctx->stream, g, wts);
+  });
+}
+
+// the one-launch ascent of a multiplicative patch level (patch_gs_up_kernel): prolongation and nsweeps <= patch_gs_max_sweeps
+// reverse sweeps on the tiles sel chooses, the same tile plan
+static int launch_patch_gs_up(aggmg_ctx* ctx, const PatchDev& P, PatchGsUpArgs u, const SweepWeights& wts, const TileSel& sel) {
+  const uint16_t* cls = patch_cls(P);
+  return launch_patch_tiles<patch_form>(ctx, P, u.g.p, patch_gs_tile_plan(P.m, u.g.p.nsweeps), sel, "multiplicative patch ascent",
+                                        [&](auto f, const TileSubset& t, size_t lds) {
+    using F = decltype(f);
+    constexpr int NS = PatchSlabs<F::kM>::NS;
+    const dim3 grid((unsigned)t.ntiles), block(kThreads);
+    u.tile_split = t.split;
+    u.tile_skip = t.skip;
+    if (cls)
+      hipLaunchKernelGGL((patch_gs_up_dict_kernel<F::kM, F::kCmp, NS>), grid, block, lds, ctx->stream, u, wts, cls);
+    else
+      hipLaunchKernelGGL((patch_gs_up_kernel<F::kM, F::kCmp, NS>), grid, block, lds, ctx->stream, u, wts);
+  });
 }
 
 // nsweeps sweeps from u_in (may be nullptr = zero) into u_out (!= u_in), in launches of up to patch_max_sweeps
@@ -1069,29 +1005,17 @@ static int patch_smooth(aggmg_ctx* ctx, const PatchDev& P, const double* u_in, c
     CHECK(scratch_lease(ctx, kScratchPing, N, "patch_smooth", &t0));
     if (nchunks > 2) CHECK(scratch_lease(ctx, kScratchPong, N, "patch_smooth", &t1));
   }
-  const BtdDev& b = *P.btd;
   const double* src = u_in;
   for (int c = 0; c < nchunks; ++c) {
     const int s = patch_chunk_sweeps(nsweeps, smax, c);
     double* dst = (c == nchunks - 1) ? u_out : (((nchunks - 1 - c) % 2 == 1) ? t0.get() : t1.get());
-    PatchArgs a{b.dblk, b.scol, b.qrow, b.sub, b.sup, P.zrows, P.ne, b.c_sub, b.r_sup, src, rhs, dst, s, 0, 0};
-    // the smoother's operator dictionary in place of the full arrays: the same bits, read by the element's class
-    const PatchDictDev* d = P.dict.get();
-    if (d) {
-      a.dblk = d->dblk;
-      a.scol = d->scol;
-      a.qrow = d->qrow;
-      a.sub = d->sub;
-      a.sup = d->sup;
-      a.zrows = d->zrows;
-    }
+    const PatchArgs a = patch_args(P, src, rhs, dst, s);
     {
       ProfScope ps(ctx, AGGMG_KIND_SMOOTH, level);
-      const uint16_t* cls = d ? d->cls.get() : nullptr;
       if (P.multiplicative)
-        CHECK(launch_patch_gs(ctx, P, a, alpha.from(c * smax).launch(s), reverse, cls));
+        CHECK(launch_patch_gs(ctx, P, a, alpha.from(c * smax).launch(s), reverse));
       else
-        CHECK(launch_patch(ctx, P, a, alpha.from(c * smax).launch(s), cls));
+        CHECK(launch_patch(ctx, P, a, alpha.from(c * smax).launch(s)));
     }
     src = dst;
   }
@@ -1099,49 +1023,26 @@ static int patch_smooth(aggmg_ctx* ctx, const PatchDev& P, const double* u_in, c
 }
 
 // ---- the multiplicative sweeps on K columns (patch_multi_kernels.hpp) ---------------------------------
-// the element-block forms patch_gs_multi_kernel is instantiated for: those of the K-column transfer kernel (launch_multi)
-static bool patch_multi_form_ok(const PatchDev& P) {
-  return P.multiplicative && P.btd && (P.btd->cmp ? (P.m == 2 || P.m == 4) : P.m == 2);
-}
-// the smallest instantiated column group that holds kc columns
-static int patch_multi_group(int kc) { return kc <= 1 ? 1 : (kc <= 2 ? 2 : (kc <= 4 ? 4 : 8)); }
+// the levels patch_gs_multi_kernel serves: multiplicative sweeps on a K-column form (multi_form, forms.hpp)
+static bool patch_multi_form_ok(const PatchDev& P) { return P.multiplicative && P.btd && multi_form(P.m, P.btd->cmp); }
 
-template <int M, bool CMP>
-static int launch_patch_gs_multi_t(aggmg_ctx* ctx, PatchGsMultiArgs m, const SweepWeights& wts, const uint16_t* cls) {
-  PatchArgs& a = m.g.p;
-  const int kb = patch_multi_group(m.kc);
-  const PatchTilePlan plan = patch_gs_multi_tile_plan(M, a.nsweeps, kb);   // host_plan.hpp
-  if (plan.owned <= 0 || m.kc < 1 || m.kc > kb)
-    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column multiplicative patch sweep launch without a tile");
-  a.owned = plan.owned;
-  a.halo = plan.halo;
-  const int64_t ntiles = patch_tiles(a.ne, plan.owned);
-  if (ntiles == 0) return AGGMG_OK;
-  auto go = [&](auto plain, auto dict) {
-    if (cls)
-      hipLaunchKernelGGL(dict, dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, m, wts, cls);
-    else
-      hipLaunchKernelGGL(plain, dim3((unsigned)ntiles), dim3(kThreads), plan.lds_bytes, ctx->stream, m, wts, cls);
-  };
-  switch (kb) {
-    case 1: go(patch_gs_multi_kernel<M, CMP, 1, false>, patch_gs_multi_kernel<M, CMP, 1, true>); break;
-    case 2: go(patch_gs_multi_kernel<M, CMP, 2, false>, patch_gs_multi_kernel<M, CMP, 2, true>); break;
-    case 4: go(patch_gs_multi_kernel<M, CMP, 4, false>, patch_gs_multi_kernel<M, CMP, 4, true>); break;
-    default: go(patch_gs_multi_kernel<M, CMP, 8, false>, patch_gs_multi_kernel<M, CMP, 8, true>); break;
-  }
-  HIPCHK(hipGetLastError());
-  ++ctx->patch_multi_launches;
-  return AGGMG_OK;
-}
-
-static int launch_patch_gs_multi(aggmg_ctx* ctx, const PatchDev& P, const PatchGsMultiArgs& m, const SweepWeights& wts,
-                                 const uint16_t* cls) {
-  if (patch_multi_form_ok(P)) {
-    if (P.btd->cmp && P.m == 4) return launch_patch_gs_multi_t<4, true>(ctx, m, wts, cls);
-    if (P.btd->cmp && P.m == 2) return launch_patch_gs_multi_t<2, true>(ctx, m, wts, cls);
-    if (!P.btd->cmp && P.m == 2) return launch_patch_gs_multi_t<2, false>(ctx, m, wts, cls);
-  }
-  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: block size not instantiated for the K-column multiplicative patch sweep kernel");
+static int launch_patch_gs_multi(aggmg_ctx* ctx, const PatchDev& P, PatchGsMultiArgs m, const SweepWeights& wts) {
+  if (!P.multiplicative) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column patch sweep launch on an additive smoother");
+  const uint16_t* cls = patch_cls(P);
+  const int kb = col_group(m.kc);
+  const PatchTilePlan plan = (m.kc >= 1 && m.kc <= kb) ? patch_gs_multi_tile_plan(P.m, m.g.p.nsweeps, kb) : PatchTilePlan();
+  return launch_patch_tiles<multi_form>(ctx, P, m.g.p, plan, TileSel(), "K-column multiplicative patch sweep",
+                                        [&](auto f, const TileSubset& t, size_t lds) {
+    using F = decltype(f);
+    with_col_group(m.kc, [&](auto g) {
+      constexpr int KB = decltype(g)::value;
+      if (cls)
+        hipLaunchKernelGGL((patch_gs_multi_kernel<F::kM, F::kCmp, KB, true>), dim3((unsigned)t.ntiles), dim3(kThreads), lds, ctx->stream, m, wts, cls);
+      else
+        hipLaunchKernelGGL((patch_gs_multi_kernel<F::kM, F::kCmp, KB, false>), dim3((unsigned)t.ntiles), dim3(kThreads), lds, ctx->stream, m, wts, cls);
+    });
+    ++ctx->patch_multi_launches;
+  });
 }
 
 // One column-major vector of a K-column run: column 0 and the doubles between two columns.
@@ -1164,7 +1065,6 @@ static int patch_smooth_multi(aggmg_ctx* ctx, const PatchDev& P, const double* U
     other.p = t0.get();
     other.ld = N;
   }
-  const BtdDev& b = *P.btd;
   const double* src = U0;
   int64_t ld_src = ld_u0;
   for (int c = 0; c < nchunks; ++c) {
@@ -1172,25 +1072,15 @@ static int patch_smooth_multi(aggmg_ctx* ctx, const PatchDev& P, const double* U
     const ColsPtr dst = ((nchunks - 1 - c) % 2 == 0) ? U : other;
     PatchGsMultiArgs m;
     std::memset(&m, 0, sizeof(m));
-    m.g.p = PatchArgs{b.dblk, b.scol, b.qrow, b.sub, b.sup, P.zrows, P.ne, b.c_sub, b.r_sup, src, B, dst.p, s, 0, 0};
+    m.g.p = patch_args(P, src, B, dst.p, s);
     m.g.reverse = reverse ? 1 : 0;
     m.ld_uin = ld_src;
     m.ld_b = ld_b;
     m.ld_uout = dst.ld;
     m.kc = kc;
-    // the smoother's operator dictionary in place of the full arrays, as patch_smooth takes it
-    const PatchDictDev* d = P.dict.get();
-    if (d) {
-      m.g.p.dblk = d->dblk;
-      m.g.p.scol = d->scol;
-      m.g.p.qrow = d->qrow;
-      m.g.p.sub = d->sub;
-      m.g.p.sup = d->sup;
-      m.g.p.zrows = d->zrows;
-    }
     {
       ProfScope ps(ctx, AGGMG_KIND_SMOOTH, level);
-      CHECK(launch_patch_gs_multi(ctx, P, m, alpha.from(c * smax).launch(s), d ? d->cls.get() : nullptr));
+      CHECK(launch_patch_gs_multi(ctx, P, m, alpha.from(c * smax).launch(s)));
     }
     src = dst.p;
     ld_src = dst.ld;
@@ -1277,7 +1167,7 @@ extern "C" int aggmg_patch_schwarz_setup(aggmg_ctx* ctx, aggmg_op* A, int64_t m,
     aggmg_smoother* elem = nullptr;
     const int st = aggmg_blockjacobi_setup(ctx, A, m, ne, lists.data(), 0, 0, &elem);
     if (st != AGGMG_OK && st != AGGMG_ERR_SINGULAR) return st;   // (a singular element block: the patches may still be regular)
-    if (elem && elem->btd && patch_instantiated((int)m, elem->btd->cmp) && patch_max_sweeps((int)m) >= 1) eb = elem->btd;
+    if (elem && elem->btd && patch_form((int)m, elem->btd->cmp) && patch_max_sweeps((int)m) >= 1) eb = elem->btd;
     if (elem) CHECK(aggmg_smoother_free(ctx, elem));
   }
   if (!eb) {   // the generic route on the lists, as everywhere: the same results to round-off
@@ -1313,7 +1203,7 @@ extern "C" int aggmg_patch_gs_setup(aggmg_ctx* ctx, aggmg_op* A, int64_t m, int6
   if (elem) CHECK(aggmg_smoother_free(ctx, elem));
   if (!eb)
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_patch_gs_setup: the operator is not block tridiagonal in the element blocking");
-  if (!patch_instantiated((int)m, eb->cmp))
+  if (!patch_form((int)m, eb->cmp))
     return fail(ctx, AGGMG_ERR_UNSUPPORTED,
                 "aggmg_patch_gs_setup: the sweep kernel is not instantiated for " + std::to_string(m) + " rows per element with " +
                     (eb->cmp ? "compressed" : "dense") + " couplings");
@@ -2047,14 +1937,10 @@ static int cr_chunks(aggmg_ctx* ctx, CrDev& cr, bool backward, const double* d_o
 // f(std::integral_constant<int, M>) -> status, for the factorisation's block size
 template <class F>
 static int cr_with_m(aggmg_ctx* ctx, const CrDev& cr, F&& f) {
-  switch (cr.m) {
-#define CASE(MM) \
-  case MM:       \
-    return f(std::integral_constant<int, MM>());
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-#undef CASE
-  }
-  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "cyclic reduction block size not instantiated");
+  int rc = AGGMG_OK;
+  if (!with_block_size<cr_form>(cr.m, [&](auto m) { rc = f(m); }))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "cyclic reduction block size not instantiated");
+  return rc;
 }
 
 // phase 0: chunk forward, 1: boundary system, 2: chunk backward; pstride: block stride of partR / partL
@@ -2979,26 +2865,16 @@ static bool patch_split_ok(const aggmg_hier* h, int nPost) {
 static int patch_up_split(aggmg_ctx* ctx, aggmg_hier* h, const double* rhs, int nPost, double alpha, double* dst, const TileSel& sel) {
   Level& l = h->lv[0];
   const PatchDev& P = *l.S->patch;
-  const BtdDev& b = *P.btd;
   PatchGsUpArgs u{};
-  u.g.p = PatchArgs{b.dblk, b.scol, b.qrow, b.sub, b.sup, P.zrows, P.ne, b.c_sub, b.r_sup, l.u[0], rhs, dst, nPost, 0, 0};
+  u.g.p = patch_args(P, l.u[0], rhs, dst, nPost);
   u.g.reverse = 1;   // post-smoothing: the colours in reverse order
-  const PatchDictDev* d = P.dict.get();
-  if (d) {   // the smoother's operator dictionary in place of the full arrays, as patch_smooth takes it
-    u.g.p.dblk = d->dblk;
-    u.g.p.scol = d->scol;
-    u.g.p.qrow = d->qrow;
-    u.g.p.sub = d->sub;
-    u.g.p.sup = d->sup;
-    u.g.p.zrows = d->zrows;
-  }
   u.uc = coarse_result(h, 0);
   u.lf = l.tb->lf;
   u.lf1 = l.tb->lf1;
   u.mc = l.tb->mc;
   u.rho = l.tb->rho;
   ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, 0);
-  return launch_patch_gs_up(ctx, P, u, l.damp_post(alpha).from(0).launch(nPost), sel, d ? d->cls.get() : nullptr);
+  return launch_patch_gs_up(ctx, P, u, l.damp_post(alpha).from(0).launch(nPost), sel);
 }
 
 // Generic levels: generic_sweeps between the generic launches.  The descent sweeps in place in l.u[0] (point Jacobi:
@@ -3150,7 +3026,7 @@ extern "C" int aggmg_vcycle_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0,
 #define AGGMG_MULTI_NT 256
 #endif
 constexpr int kMultiKB = AGGMG_MULTI_KB, kMultiNT = AGGMG_MULTI_NT;
-static_assert(kMultiKB == 1 || kMultiKB == 2 || kMultiKB == 4 || kMultiKB == 8, "column groups of 1, 2, 4 or 8");
+static_assert(is_col_group(kMultiKB), "column groups of 1, 2, 4 or 8");
 
 // A multiplicative patch level in column groups (AGGMG_OPT_PATCH_MULTI): the K-column sweeps (patch_gs_multi_kernel) and,
 // around them, the zero-sweep launches of the K-column transfer kernel on the smoother's element-block form -- where the
@@ -3182,13 +3058,13 @@ static bool multi_patch_level_ok(const aggmg_hier* h, int k, int nPre, int nPost
   return (nPre == 0 && nPost == 0) || smax >= 1;
 }
 
-// A fused chain level in column groups (AGGMG_OPT_CHAIN_MULTI): point-Jacobi sweeps on blocks of 1, 2 or 4 rows, each half
+// A fused chain level in column groups (AGGMG_OPT_CHAIN_MULTI): point-Jacobi sweeps on a block size of chain_dict_form, each half
 // one launch of cgt_multi_kernel with a tile (the planner its launcher runs; a group of kMultiKB columns: the tile does not
 // depend on the group).
 static bool multi_chain_level_ok(const aggmg_hier* h, int k, int nPre, int nPost) {
   const Level& l = h->lv[k];
   const CgtDev& g = *l.S->cgt;
-  if (g.sw != 0 || !(g.m == 1 || g.m == 2 || g.m == 4) || !l.tc || l.tc->type == kTrNone) return false;
+  if (g.sw != 0 || !chain_dict_form(g.m) || !l.tc || l.tc->type == kTrNone) return false;
   const int smax = chain_multi_max_sweeps(g.m);
   if (nPre > smax || nPost > smax) return false;
   TileQuery down, up;
@@ -3209,7 +3085,7 @@ static bool multi_level_ok(const aggmg_hier* h, int k, int nPre, int nPost, bool
   if (level_path(h, k) != LevelPath::FusedBtd || l.S->gs) return false;
   const BtdDev& b = *l.S->btd;
   const TransferBtd& t = *l.tb;
-  if (b.cmp ? !(b.m == 2 || b.m == 4) : b.m != 2) return false;
+  if (!multi_form(b.m, b.cmp)) return false;
   if (t.mc != 2 || t.rho <= 0 || b.ne != (int64_t)t.rho * t.nec) return false;
   if (t.ld && h->restriction == AGGMG_RESTRICT_PRECONDITIONED) return false;
   // the single-column cycle's launches at this level are single fused launches (no chunked sweeps) ...
@@ -3236,35 +3112,29 @@ template <int M, bool CMP, bool SYM>
 static int launch_multi_t(aggmg_ctx* ctx, MultiArgs m, const SweepWeights& wts, int halo) {
   constexpr int TE = kMultiNT / M;
   const int align = m.a.lf_out ? m.a.rho_out : 1;
-  const int owned = multi_tile_owned(TE, halo, align);   // host_plan.hpp, as multi_level_ok
+  const int owned = multi_tile_owned(TE, halo, align);   // host_plan.hpp, the planner multi_level_ok asks
   if (owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column tile too small for the requested halo");
   m.a.owned = owned;
   m.a.halo_left = halo;
   const int64_t ntiles = (m.a.lv.ne + owned - 1) / owned;
   if (ntiles == 0) return AGGMG_OK;
-  auto go = [&](auto kern, int kb) {
-    const size_t lds = (size_t)2 * kb * (TE + 2) * M * sizeof(double);
-    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(kMultiNT), lds, ctx->stream, m, wts);
-  };
-  // the smallest instantiated group that holds the columns
-  if (m.kc <= 1)
-    go(btd_multi_kernel<M, CMP, SYM, 1, kMultiNT>, 1);
-  else if (m.kc <= 2 || kMultiKB == 2)
-    go(btd_multi_kernel<M, CMP, SYM, 2, kMultiNT>, 2);
-  else if (m.kc <= 4 || kMultiKB == 4)
-    go(btd_multi_kernel<M, CMP, SYM, 4, kMultiNT>, 4);
-  else
-    go(btd_multi_kernel<M, CMP, SYM, 8, kMultiNT>, 8);
+  with_col_group(m.kc, kMultiKB, [&](auto g) {   // (never a group above the cycle's)
+    constexpr int KB = decltype(g)::value;
+    const size_t lds = (size_t)2 * KB * (TE + 2) * M * sizeof(double);
+    hipLaunchKernelGGL((btd_multi_kernel<M, CMP, SYM, KB, kMultiNT>), dim3((unsigned)ntiles), dim3(kMultiNT), lds, ctx->stream, m, wts);
+  });
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
 
 static int launch_multi(aggmg_ctx* ctx, const BtdDev& b, const MultiArgs& m, const SweepWeights& wts, int halo) {
-  const bool sym = b.bsym != nullptr;
-  if (b.cmp && b.m == 4) return sym ? launch_multi_t<4, true, true>(ctx, m, wts, halo) : launch_multi_t<4, true, false>(ctx, m, wts, halo);
-  if (b.cmp && b.m == 2) return sym ? launch_multi_t<2, true, true>(ctx, m, wts, halo) : launch_multi_t<2, true, false>(ctx, m, wts, halo);
-  if (!b.cmp && b.m == 2) return sym ? launch_multi_t<2, false, true>(ctx, m, wts, halo) : launch_multi_t<2, false, false>(ctx, m, wts, halo);
-  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: block size not instantiated for the K-column kernel");
+  int rc = AGGMG_OK;
+  if (!with_form<multi_form>(b.m, b.cmp, [&](auto f) {
+        using F = decltype(f);
+        rc = b.bsym ? launch_multi_t<F::kM, F::kCmp, true>(ctx, m, wts, halo) : launch_multi_t<F::kM, F::kCmp, false>(ctx, m, wts, halo);
+      }))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: block size not instantiated for the K-column kernel");
+  return rc;
 }
 
 // per-level K-column vectors for groups of `cols` columns; a call with no more columns than before allocates nothing
@@ -3999,7 +3869,7 @@ static void btd_launch_bytes(const BtdDev& b, bool sweeps, bool u_in, bool resid
                              const TransferBtd* tout, bool preconditioned, int64_t* rd, int64_t* wr, int64_t ncols = 1) {
   const int64_t m = b.m, ne = b.ne, N = ne * m, D = sizeof(double), K = ncols;
   const bool need_g = sweeps || (tout && preconditioned);
-  const bool grp = (b.cmp && (m == 2 || m == 4 || m == 8)) || (!b.cmp && (m == 2 || m == 4));
+  const bool grp = btd_sym_form(b.m, b.cmp);
   const bool sym = grp && b.bsym;
   int64_t r = K * N * D, w = 0;                                             // b
   if (u_in) r += K * N * D;
@@ -4888,11 +4758,11 @@ extern "C" int aggmg_fgmres_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* b, 
 }
 
 // ---- K-column residual -------------------------------------------------------------------------
-// the operators btd_residual_multi_kernel covers: what the K-column cycle covers (multi_level_ok), level by level
+// the operators btd_residual_multi_kernel covers: the K-column forms (multi_form, forms.hpp) with a tile
 static bool res_multi_ok(const aggmg_op* A) {
   if (A->cgt || !A->btd) return false;
   const BtdDev& b = *A->btd;
-  if (b.cmp ? !(b.m == 2 || b.m == 4) : b.m != 2) return false;
+  if (!multi_form(b.m, b.cmp)) return false;
   TileQuery q;
   q.launch = kTileMulti;
   q.te = kMultiNT / b.m;
@@ -4903,23 +4773,15 @@ static bool res_multi_ok(const aggmg_op* A) {
 template <int M, bool CMP>
 static int launch_res_multi_t(aggmg_ctx* ctx, ResMultiArgs m) {
   constexpr int TE = kMultiNT / M;
-  m.owned = multi_tile_owned(TE, 1, 1);   // host_plan.hpp, as res_multi_ok
+  m.owned = multi_tile_owned(TE, 1, 1);   // host_plan.hpp, the planner res_multi_ok asks
   if (m.owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column residual tile too small");
   const int64_t ntiles = (m.lv.ne + m.owned - 1) / m.owned;
   if (ntiles == 0) return AGGMG_OK;
-  auto go = [&](auto kern, int kb) {
-    const size_t lds = (size_t)kb * (TE + 2) * M * sizeof(double);
-    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(kMultiNT), lds, ctx->stream, m);
-  };
-  // the smallest instantiated group that holds the columns
-  if (m.kc <= 1)
-    go(btd_residual_multi_kernel<M, CMP, 1, kMultiNT>, 1);
-  else if (m.kc <= 2 || kMultiKB == 2)
-    go(btd_residual_multi_kernel<M, CMP, 2, kMultiNT>, 2);
-  else if (m.kc <= 4 || kMultiKB == 4)
-    go(btd_residual_multi_kernel<M, CMP, 4, kMultiNT>, 4);
-  else
-    go(btd_residual_multi_kernel<M, CMP, 8, kMultiNT>, 8);
+  with_col_group(m.kc, kMultiKB, [&](auto g) {   // (never a group above the cycle's)
+    constexpr int KB = decltype(g)::value;
+    const size_t lds = (size_t)KB * (TE + 2) * M * sizeof(double);
+    hipLaunchKernelGGL((btd_residual_multi_kernel<M, CMP, KB, kMultiNT>), dim3((unsigned)ntiles), dim3(kMultiNT), lds, ctx->stream, m);
+  });
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
@@ -4950,9 +4812,9 @@ static int residual_multi(aggmg_ctx* ctx, aggmg_op* A, const double* X, int64_t 
     m.ld_r = ldr;
     m.kc = (int)std::min<int64_t>(group, ncols - c0);
     ProfScope ps(ctx, AGGMG_KIND_RESIDUAL, 0);
-    if (b.cmp && b.m == 4) CHECK((launch_res_multi_t<4, true>(ctx, m)));
-    else if (b.cmp) CHECK((launch_res_multi_t<2, true>(ctx, m)));
-    else CHECK((launch_res_multi_t<2, false>(ctx, m)));
+    int rc = AGGMG_OK;   // (res_multi_ok: the form is one of multi_form)
+    with_form<multi_form>(b.m, b.cmp, [&](auto f) { rc = launch_res_multi_t<decltype(f)::kM, decltype(f)::kCmp>(ctx, m); });
+    CHECK(rc);
   }
   return AGGMG_OK;
 }

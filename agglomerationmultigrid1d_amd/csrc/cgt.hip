@@ -46,17 +46,9 @@ struct CgtTile {
 
 template <int SW>
 static int cgt_tile_blocks_t(int m) {
-  switch (m) {
-    case 1: return CgtTile<1, SW>::TE;
-    case 2: return CgtTile<2, SW>::TE;
-    case 3: return CgtTile<3, SW>::TE;
-    case 4: return CgtTile<4, SW>::TE;
-    case 5: return CgtTile<5, SW>::TE;
-    case 6: return CgtTile<6, SW>::TE;
-    case 7: return CgtTile<7, SW>::TE;
-    case 8: return CgtTile<8, SW>::TE;
-  }
-  return 0;
+  int te = 0;   // (no form of chain_form, forms.hpp: no tile)
+  with_block_size<chain_form>(m, [&](auto n) { te = CgtTile<decltype(n)::value, SW>::TE; });
+  return te;
 }
 int cgt_tile_blocks(int m) { return cgt_tile_blocks_t<0>(m); }
 
@@ -88,8 +80,7 @@ static int cgt_multi_launch_t(aggmg_ctx* ctx, CgtMultiArgs m, const SweepWeights
   const int kc_all = m.kc;
   for (int c0 = 0; c0 < kc_all; c0 += cgt_multi_kb_ceiling<M>()) {
     const int kc = std::min(kc_all - c0, cgt_multi_kb_ceiling<M>());
-    const int kb = kc <= 1 ? 1 : (kc <= 2 ? 2 : (kc <= 4 ? 4 : 8));   // the smallest instantiated group that holds the columns
-    const ChainMultiPlan p = chain_multi_tile_plan(M, a.nsweeps, kind, rho, kb, a.cls != nullptr, NT);   // host_plan.hpp, as multi_level_ok
+    const ChainMultiPlan p = chain_multi_tile_plan(M, a.nsweeps, kind, rho, col_group(kc), a.cls != nullptr, NT);   // host_plan.hpp, the planner multi_chain_level_ok asks
     if (p.owned <= 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column chain tile too small for the requested halo");
     CgtMultiArgs q = m;
     q.kc = kc;
@@ -103,14 +94,13 @@ static int cgt_multi_launch_t(aggmg_ctx* ctx, CgtMultiArgs m, const SweepWeights
     const int64_t ntiles = (a.lv.ne + p.owned - 1) / p.owned;
     if (ntiles == 0) return AGGMG_OK;
     if (ntiles >= ((int64_t)1 << 31)) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "grid too large");
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(NT), p.lds_bytes, ctx->stream, q, wts); };
-    const bool dict = a.cls != nullptr;
-    switch (kb) {
-      case 1: dict ? go(cgt_multi_kernel<M, 1, NT, true>) : go(cgt_multi_kernel<M, 1, NT, false>); break;
-      case 2: dict ? go(cgt_multi_kernel<M, 2, NT, true>) : go(cgt_multi_kernel<M, 2, NT, false>); break;
-      case 4: dict ? go(cgt_multi_kernel<M, 4, NT, true>) : go(cgt_multi_kernel<M, 4, NT, false>); break;
-      default: dict ? go(cgt_multi_kernel<M, 8, NT, true>) : go(cgt_multi_kernel<M, 8, NT, false>); break;
-    }
+    with_col_group(kc, [&](auto g) {
+      constexpr int KB = decltype(g)::value;
+      if (a.cls)
+        hipLaunchKernelGGL((cgt_multi_kernel<M, KB, NT, true>), dim3((unsigned)ntiles), dim3(NT), p.lds_bytes, ctx->stream, q, wts);
+      else
+        hipLaunchKernelGGL((cgt_multi_kernel<M, KB, NT, false>), dim3((unsigned)ntiles), dim3(NT), p.lds_bytes, ctx->stream, q, wts);
+    });
     HIPCHK(hipGetLastError());
     ++ctx->chain_multi_launches;
   }
@@ -119,12 +109,10 @@ static int cgt_multi_launch_t(aggmg_ctx* ctx, CgtMultiArgs m, const SweepWeights
 
 static int cgt_multi_launch(aggmg_ctx* ctx, const CgtDev& g, const CgtMultiArgs& m, const SweepWeights& wts) {
   if (g.sw != 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column chain launch on element-block sweeps");
-  switch (g.m) {
-    case 1: return cgt_multi_launch_t<1>(ctx, m, wts);
-    case 2: return cgt_multi_launch_t<2>(ctx, m, wts);
-    case 4: return cgt_multi_launch_t<4>(ctx, m, wts);
-  }
-  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: chain block size not instantiated for the K-column kernel");
+  int rc = AGGMG_OK;
+  if (!with_block_size<chain_dict_form>(g.m, [&](auto n) { rc = cgt_multi_launch_t<decltype(n)::value>(ctx, m, wts); }))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: chain block size not instantiated for the K-column kernel");
+  return rc;
 }
 
 template <int M, int K>
@@ -172,9 +160,9 @@ static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, const SweepWeights& wts, int
   if (a.chk_stride < 1) a.chk_stride = 1 << 30;
   size_t lds = (size_t)(sw ? 3 : 2) * (T::TE + 2) * M * sizeof(double) + (a.chk_part ? (size_t)2 * (T::NT / 64) * sizeof(double) : 0);
   // the operator dictionary (cgt_dictionary put its arrays in place of the full ones): point-Jacobi launches without
-  // checkpoints on blocks of 1, 2 or 4 rows; the tile's classes go to LDS behind the iterate buffers
+  // checkpoints on a block size of chain_dict_form; the tile's classes go to LDS behind the iterate buffers
   if (a.cls) {
-    if constexpr (K == 0 && (M == 1 || M == 2 || M == 4)) {
+    if constexpr (K == 0 && chain_dict_form(M)) {
       if (a.chk_part) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: dictionary launch of a checkpoint variant");
       lds += (size_t)(T::TE + 2) * sizeof(uint16_t);
       hipLaunchKernelGGL((cgt_fused_kernel<M, T::NS, T::NT, 0, false, true>), dim3((unsigned)ntiles), dim3(T::NT), lds, ctx->stream, a, wts);
@@ -205,14 +193,10 @@ static int cgt_launch_tt(aggmg_ctx* ctx, CgtArgs a, const SweepWeights& wts, int
 }
 
 static int cgt_launch(aggmg_ctx* ctx, const CgtDev& g, const CgtArgs& a, const SweepWeights& wts, CgtChk* chk_io = nullptr) {
-  switch (g.m) {
-#define CASE(MM) \
-  case MM:       \
-    return cgt_launch_t<MM>(ctx, a, wts, g.sw, chk_io);
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-#undef CASE
-  }
-  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "chain block size not instantiated");
+  int rc = AGGMG_OK;
+  if (!with_block_size<chain_form>(g.m, [&](auto n) { rc = cgt_launch_t<decltype(n)::value>(ctx, a, wts, g.sw, chk_io); }))
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "chain block size not instantiated");
+  return rc;
 }
 
 static CgtArgs cgt_args(const CgtDev& g) {

@@ -10,6 +10,8 @@
 #include <cstring>
 #include <vector>
 
+#include "forms.hpp"
+
 namespace aggmg {
 
 constexpr int kCrTailRows = 4096;  // scalar rows (blocks * m) the single-workgroup tail takes
@@ -379,15 +381,14 @@ inline int patch_gs_max_sweeps(int m, int threads = 256) {
 
 // ---- the same sweeps on K columns at once (patch_gs_multi_kernel, patch_multi_kernels.hpp) -----------------------------
 // One slab: a workgroup of `threads` threads holds threads / m elements, for the block sizes the K-column transfer kernel
-// covers (m = 2, 4), and kb = 1, 2, 4 or 8 columns of them.  Reach, halo and the most sweeps per launch follow the
+// covers (multi_block_size, forms.hpp), and a column group kb of them.  Reach, halo and the most sweeps per launch follow the
 // single-column rules above (neither depends on kb).  LDS: per column an iterate plane, updated in place, and a residual
 // plane, each padded by one element a side -- 2 kb (te + 2) m doubles, 33 KiB at kb = 8: four workgroups per compute unit.
-inline int patch_gs_multi_tile_elems(int m, int threads = 256) { return (m == 2 || m == 4) ? threads / m : 0; }
-inline bool patch_gs_multi_group(int kb) { return kb == 1 || kb == 2 || kb == 4 || kb == 8; }
+inline int patch_gs_multi_tile_elems(int m, int threads = 256) { return multi_block_size(m) ? threads / m : 0; }
 inline PatchTilePlan patch_gs_multi_tile_plan(int m, int sweeps, int kb, int threads = 256) {
   PatchTilePlan p;
   p.te = patch_gs_multi_tile_elems(m, threads);
-  if (p.te <= 0 || !patch_gs_multi_group(kb) || sweeps < 1 || sweeps > kPatchMaxSweeps) return p;
+  if (p.te <= 0 || !is_col_group(kb) || sweeps < 1 || sweeps > kPatchMaxSweeps) return p;
   p.halo = patch_gs_halo(sweeps);
   p.owned = patch_gs_owned(p.te, sweeps);
   p.lds_bytes = (size_t)2 * kb * (p.te + 2) * m * sizeof(double);
@@ -402,8 +403,8 @@ inline int patch_gs_multi_max_sweeps(int m, int threads = 256) {
 }
 
 // ---- the chain kernel on K columns at once (cgt_multi_kernel, cgt_multi_kernels.hpp) -------------------------------------
-// One slab: a workgroup of `threads` threads holds threads / m blocks, for m = 1, 2, 4 (lane groups of m) and kb = 1, 2, 4
-// or 8 columns of them.  The halos are the single-column launch's (cgt_launch_tt): a block per sweep and side, one more a
+// One slab: a workgroup of `threads` threads holds threads / m blocks, for the sizes of chain_dict_form (forms.hpp; lane groups
+// of m) and a column group kb of them.  The halos are the single-column launch's (cgt_launch_tt): a block per sweep and side, one more a
 // side for a residual, one more on the left for a chain restriction, on the right for an agglomerating one, whose ratio the
 // owned blocks are a multiple of.  The most sweeps per launch follow the single-column rule.  LDS: kb iterate planes per
 // ping-pong buffer, each padded by one block a side, and (dictionary variant) the tile's classes behind them.
@@ -414,13 +415,12 @@ struct ChainMultiPlan {
   int owned = 0;                     // 0: no tile
   size_t lds_bytes = 0;
 };
-inline int chain_multi_tile_blocks(int m, int threads = 256) { return (m == 1 || m == 2 || m == 4) ? threads / m : 0; }
-inline bool chain_multi_group(int kb) { return kb == 1 || kb == 2 || kb == 4 || kb == 8; }
+inline int chain_multi_tile_blocks(int m, int threads = 256) { return chain_dict_form(m) ? threads / m : 0; }
 inline ChainMultiPlan chain_multi_tile_plan(int m, int nsweeps, int restrict_kind, int rho, int kb, bool dict = false,
                                             int threads = 256) {
   ChainMultiPlan p;
   p.te = chain_multi_tile_blocks(m, threads);
-  if (p.te <= 0 || !chain_multi_group(kb) || nsweeps < 0 || nsweeps > kPatchMaxSweeps || rho < 1) return p;
+  if (p.te <= 0 || !is_col_group(kb) || nsweeps < 0 || nsweeps > kPatchMaxSweeps || rho < 1) return p;
   if (restrict_kind < kChainNoRestrict || restrict_kind > kChainToAgg) return p;
   p.halo_left = nsweeps + (restrict_kind != kChainNoRestrict ? 1 : 0) + (restrict_kind == kChainToChain ? 1 : 0);
   p.halo_right = nsweeps + (restrict_kind != kChainNoRestrict ? 1 : 0) + (restrict_kind == kChainToAgg ? 1 : 0);

@@ -294,27 +294,21 @@ int setup_invert_blocks(aggmg_ctx* ctx, int64_t nb, int m, const double* blocks_
   const unsigned long long none = (unsigned long long)nb;
   HIPCHK(hipMemcpyAsync(sing, &none, sizeof(none), hipMemcpyHostToDevice, ctx->stream));
   DevArray<double> work;
-  switch (m) {
-#define CASE(MM)                                                                              \
-  case MM:                                                                                    \
-    LAUNCH((block_invert_kernel<MM>), nb, nb, blocks_dev, colmajor, inv_dev, sing.get());     \
-    break;
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-#undef CASE
-    default:
-      CHECK(work.alloc(ctx, nb * ((int64_t)m * m + 2 * m)));
-      LAUNCH(block_invert_any_kernel, nb, nb, m, blocks_dev, colmajor, work.get(), inv_dev, sing.get());
+  const bool sized = with_block_size<invert_form>(m, [&](auto n) {
+    if (nb > 0)
+      hipLaunchKernelGGL((block_invert_kernel<decltype(n)::value>), dim3(grid_for(nb)), dim3(kSetupThreads), 0, ctx->stream, nb, blocks_dev,
+                         colmajor, inv_dev, sing.get());
+  });
+  HIPCHK(hipGetLastError());
+  if (!sized) {   // (no form of invert_form, forms.hpp: the kernel for any size)
+    CHECK(work.alloc(ctx, nb * ((int64_t)m * m + 2 * m)));
+    LAUNCH(block_invert_any_kernel, nb, nb, m, blocks_dev, colmajor, work.get(), inv_dev, sing.get());
   }
   unsigned long long got = none;
   HIPCHK(hipMemcpyAsync(&got, sing, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   *first_singular = got >= none ? -1 : (int64_t)got;
   return AGGMG_OK;
-}
-
-static bool btd_supported(int m, bool cmp) {
-  if (cmp) return m >= 2 && m <= 9;
-  return m >= 1 && m <= 5;
 }
 
 // dg_smoother(mesh, A, :blockJac) / cg_smoother(..., :addSchwarz | :hybridSchwarz) on the device: index lists
@@ -363,9 +357,9 @@ int setup_block_smoother(aggmg_ctx* ctx, aggmg_smoother* sm, const int64_t* bloc
       const unsigned submask = (unsigned)g[2], supmask = (unsigned)g[3];
       bool cmp = m >= 2 && __builtin_popcount(submask) <= 1 && __builtin_popcount(supmask) <= 1;
       int c_sub = submask ? __builtin_ctz(submask) : 0, r_sup = supmask ? __builtin_ctz(supmask) : 0;
-      if (cmp && !btd_supported(m, true)) cmp = false;
+      if (cmp && !btd_form(m, true)) cmp = false;
       if (!cmp) c_sub = r_sup = 0;
-      if (cmp || btd_supported(m, false)) {
+      if (cmp || btd_form(m, false)) {
         b->cmp = cmp;
         b->c_sub = c_sub;
         b->r_sup = r_sup;
@@ -374,8 +368,7 @@ int setup_block_smoother(aggmg_ctx* ctx, aggmg_smoother* sm, const int64_t* bloc
         HIPCHK(hipMemcpyAsync(b->binv, sm->binv, (size_t)N * m * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
         Flags asym;
         CHECK(asym.init(ctx, 1));
-        const bool grp = cmp ? (m == 2 || m == 4 || m == 8) : (m == 2 || m == 4);
-        const bool try_sym = grp && ctx->sym_packing && (!cmp || c_sub == r_sup);
+        const bool try_sym = btd_sym_form(m, cmp) && ctx->sym_packing && (!cmp || c_sub == r_sup);
         if (cmp) {
           CHECK(b->scol.alloc(ctx, N));
           CHECK(b->pcol.alloc(ctx, N));
@@ -611,8 +604,8 @@ int dict_build(aggmg_ctx* ctx, DictFields& F, DevArray<uint16_t>* cls, int* ncla
 int setup_op_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t, std::unique_ptr<DictDev>* out) {
   out->reset();
   const int m = b.m;
-  // the levels of btd_fused_kernel<M, CMP, ., SYM, ...> with M = 2, 4 whose transfer has two modes on equal agglomerates
-  if (!(b.cmp && b.bsym && (m == 2 || m == 4) && b.scol && b.dblk && b.qrow)) return AGGMG_OK;
+  // the levels of btd_fused_kernel<M, CMP, ., SYM, ...> on a form of btd_sres_form whose transfer has two modes on equal agglomerates
+  if (!(btd_sres_form(m, b.cmp) && b.bsym && b.scol && b.dblk && b.qrow)) return AGGMG_OK;
   if (!(t.rho > 0 && t.mc == 2 && t.lf) || b.ne < 1) return AGGMG_OK;
   const int T = m * (m + 1) / 2;
   auto d = std::make_unique<DictDev>();
@@ -721,8 +714,8 @@ int setup_pair_dictionary(aggmg_ctx* ctx, const BtdDev& b, const TransferBtd& t,
 int setup_cgt_dictionary(aggmg_ctx* ctx, const CgtDev& g, const TransferCgt& t, std::unique_ptr<CgtDictDev>* out) {
   out->reset();
   const int m = g.m;
-  // the levels of cgt_fused_kernel<M, ., ., 0, false, DICT = true>: blocks of 1, 2 or 4 rows, point-Jacobi sweeps
-  if (!((m == 1 || m == 2 || m == 4) && g.sw == 0 && g.dblk && g.subrow && g.supcol) || g.ne < 1) return AGGMG_OK;
+  // the levels of cgt_fused_kernel<M, ., ., 0, false, DICT = true>: a block size of chain_dict_form, point-Jacobi sweeps
+  if (!(chain_dict_form(m) && g.sw == 0 && g.dblk && g.subrow && g.supcol) || g.ne < 1) return AGGMG_OK;
   if (!((t.type == kTrChain && t.l) || (t.type == kTrAgg && t.l && t.lp && t.rho >= 1)) || t.mc < 1) return AGGMG_OK;
   auto d = std::make_unique<CgtDictDev>();
   // the record of block e (the trailing identity-padded one is a block like any other): its rows of dblk (m*m), subrow
@@ -1033,14 +1026,9 @@ static int cr_factor_blocks(aggmg_ctx* ctx, CrDev* cr, DevArray<double> a, DevAr
   DevArray<double> condt;
   CHECK(condt.alloc(ctx, 1, true));
   int st = AGGMG_OK;
-  switch (m) {
-#define CASE(MM) \
-  case MM:       \
-    st = cr_levels_t<MM>(ctx, cr, std::move(a), std::move(b), std::move(c), n, condt, bad.d); \
-    break;
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-#undef CASE
-  }
+  with_block_size<cr_form>(m, [&](auto mm) {
+    st = cr_levels_t<decltype(mm)::value>(ctx, cr, std::move(a), std::move(b), std::move(c), n, condt, bad.d);
+  });
   if (st == AGGMG_ERR_UNSUPPORTED) {  // too many levels
     cr_discard(cr);
     return AGGMG_OK;

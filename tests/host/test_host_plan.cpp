@@ -539,6 +539,33 @@ static void test_chunk_route() {
     }
 }
 
+// forms.hpp: the dispatchers call f exactly once, with the run-time form, for every form of the predicate and never else
+static void test_form_dispatch() {
+  for (int m = -1; m <= kMaxBlock + 2; ++m) {
+    for (int cmp = 0; cmp <= 1; ++cmp) {
+      int calls = 0, gm = 0, gc = -1;
+      const bool hit = with_form<patch_form>(m, cmp != 0, [&](auto f) {
+        ++calls;
+        gm = decltype(f)::kM;
+        gc = decltype(f)::kCmp ? 1 : 0;
+      });
+      EXPECT(hit == patch_form(m, cmp != 0) && calls == (hit ? 1 : 0) && (!hit || (gm == m && gc == cmp)));
+    }
+    int calls = 0, gm = 0;
+    const bool hit = with_block_size<chain_dict_form>(m, [&](auto n) {
+      ++calls;
+      gm = decltype(n)::value;
+    });
+    EXPECT(hit == chain_dict_form(m) && calls == (hit ? 1 : 0) && (!hit || gm == m));
+  }
+  for (int ceiling : {1, 2, 4, 8})
+    for (int kc = 1; kc <= ceiling; ++kc) {
+      int kb = 0;
+      with_col_group(kc, ceiling, [&](auto g) { kb = decltype(g)::value; });
+      EXPECT(kb == col_group(kc, ceiling) && kb >= kc && kb <= ceiling && is_col_group(kb) && (kb == 1 || kb / 2 < kc));
+    }
+}
+
 int main() {
   test_cr_plans();
   test_cr_buffers();
@@ -551,6 +578,7 @@ int main() {
   test_chk_reserve();
   test_lane_ranges();
   test_chunk_route();
+  test_form_dispatch();
   if (failures) {
     std::fprintf(stderr, "%d check(s) failed\n", failures);
     return 1;

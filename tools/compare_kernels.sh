@@ -38,7 +38,8 @@ for line in open(f"{d}/isa.raw"):
         seen[m.group(1)] = k + 1
         cur = f"{m.group(1)}#{k}"
         syms[cur] = []
-    elif cur and line.strip():
+    elif cur and line.strip() and line.strip() != "..." and not line.startswith("Disassembly of section"):
+        # (the disassembler's own lines between two code objects are not the last kernel's instructions)
         syms[cur].append(re.sub(r"// [0-9A-Fa-f]+:", "//", line.strip()))
 with open(f"{d}/isa.txt", "w") as f:
     for k in sorted(syms):
@@ -52,7 +53,9 @@ for b in blocks:
     if m:
         k = seen.get(m.group(1), 0)
         seen[m.group(1)] = k + 1
-        kern[f"{m.group(1)}#{k}"] = re.sub(r"amdhsa\.target:.*|amdhsa\.version:.*(\n\s+- \d+)*|\.\.\.|---|Displaying notes.*|\s+Owner.*|\s+AMDGPU.*|\s+AMDGPU Metadata.*", "", b).rstrip()
+        # (without the note's own header and trailer, which land in the first / last kernel's block of a code object)
+        b = re.sub(r"amdhsa\.kernels:|amdhsa\.target:.*|amdhsa\.version:.*(\n\s+- \d+)*|\.\.\.|---|Displaying notes.*|\s+Owner.*|\s+AMDGPU.*|\s+AMDGPU Metadata.*", "", b)
+        kern[f"{m.group(1)}#{k}"] = "\n".join(l for l in b.splitlines() if l.strip())
 with open(f"{d}/meta.txt", "w") as f:
     for k in sorted(kern):
         f.write(f"== {k}\n{kern[k]}\n")

@@ -1,7 +1,10 @@
 """Launches per kind and level (the library's HIP-event profiler, aggmg_profile_collect) of the entry points that drive
 cycles: on the benchmark's DG hierarchy and a CG-chain hierarchy (every level fused), and on small hierarchies that reach
 the rest of the cycle driver -- generic CSR sweeps, block sweeps on overlapping and on scrambled lists, the band kernel,
-block Gauss-Seidel, chunked block-tridiagonal sweeps between generic transfers, agglomerates of different sizes.  Two
+block Gauss-Seidel, chunked block-tridiagonal sweeps between generic transfers, agglomerates of different sizes,
+element-patch levels (hybrid, additive and multiplicative).  Every hierarchy also runs a cycle on K = 11 columns with the
+opt-in column-group paths on (AGGMG_OPT_PATCH_MULTI, AGGMG_OPT_CHAIN_MULTI: groups of 8 and 3 columns where the levels
+qualify, column by column elsewhere) and the K-column residual of its fine operator.  Two
 builds of the library that print the same table launch the same sequence, and with --dump the vectors they computed can
 be compared byte for byte -- what a host-side refactor has to show (AGGMG_HIP_LIB picks the build).
 
@@ -66,6 +69,33 @@ def cases(tag, H, b_host, multi):
         table(f"{tag} multigrid_v_cycle K=4", ctx, lambda: (None, mg.multigrid_v_cycle(H, np.zeros_like(B), B)))
 
 
+def multi_cases(tag, H, b_host, K=11):
+    """the K-column entry points with the opt-in column-group paths on"""
+    ctx = H.ctx
+    N = len(b_host)
+    B = np.stack([b_host * (j + 1) for j in range(K)], axis=1)
+    X0 = np.stack([np.cos(np.arange(N) * (0.37 + 0.05 * j)) for j in range(K)], axis=1)
+    for opt in (_lib.OPT_PATCH_MULTI, _lib.OPT_CHAIN_MULTI):
+        ctx.set_option(opt, 1)
+    try:
+        fused, group = H.multi_info(K)
+        table(f"{tag} vcycle K={K}", ctx, lambda: (f"fused={int(fused)} group={group}", mg.multigrid_v_cycle(H, X0, B)))
+
+        def residual():
+            dX, dB, dR = (mg.DeviceMatrix(ctx, N, K) for _ in range(3))
+            dX.upload(np.asfortranarray(X0))
+            dB.upload(np.asfortranarray(B))
+            H._ops[0].residual_multi_dev(dX, dB, dR)
+            R = dR.download()
+            for v in (dX, dB, dR):
+                v.free()
+            return None, R
+        table(f"{tag} residual_multi K={K}", ctx, residual)
+    finally:
+        for opt in (_lib.OPT_PATCH_MULTI, _lib.OPT_CHAIN_MULTI):
+            ctx.set_option(opt, 0)
+
+
 # ---- small hierarchies off the all-fused path: name -> (build(ctx, n) -> (H, b), level kinds, main sweep counts) ----
 def _cg(smoother):
     def build(ctx, n):
@@ -87,18 +117,23 @@ def _cg(smoother):
 def _dg(smoother):
     def build(ctx, n):
         U = UniformDgAggHierarchy(n, p=3, pAgg=1, ratios=(4, 2, 2))
-        if smoother in ("blockJac", "blockGS"):
+        if smoother in ("blockJac", "blockGS", "patchSchwarz0", "patchGS0"):
             return build_device_hierarchy(U, ctx, smoother=smoother), U.rhs()
         ops = [mg.DeviceOperator(U.stiffness_csc(k), _lib.OP_STIFFNESS, ctx) for k in range(U.nlevels)]
         if smoother == "jac":   # banded operators under point Jacobi: the band kernel, residual out of the sweeps' launch
             sms = [mg.JacobiSmoother(op, ctx, detect=False) for op in ops[:-1]]
+        elif smoother == "patchAdd0":   # additive element patches on the fine level, block Jacobi below
+            inds = [U.descriptor(k).mBlockInds for k in range(U.nlevels - 1)]
+            sms = [mg.ElementPatchSchwarz(ops[0], inds[0].shape[0], inds[0].shape[1], hybrid=False, ctx=ctx)]
+            sms += [mg.BlockJacobi(ops[k], inds[k], ctx) for k in range(1, U.nlevels - 1)]
         else:                   # the elements' blocks in a scrambled order: a partition of the rows, the one-pass block sweep
             sms = []
             for k in range(U.nlevels - 1):
                 inds = U.descriptor(k).mBlockInds
                 sms.append(mg.BlockJacobi(ops[k], np.ascontiguousarray(inds[:, np.random.default_rng(k).permutation(inds.shape[1])]), ctx))
         Ls = [mg.DeviceOperator(U.interpolation_csc(k), _lib.OP_TRANSFER, ctx) for k in range(U.nlevels - 1)]
-        return mg.MeshHierarchy(None, ops, sms, Ls, ctx=ctx), U.rhs()
+        meshes = [U.descriptor(k) for k in range(U.nlevels)] if smoother == "patchAdd0" else None   # (as build_device_hierarchy)
+        return mg.MeshHierarchy(meshes, ops, sms, Ls, ctx=ctx), U.rhs()
     return build
 
 
@@ -117,6 +152,10 @@ SMALL = {
     "dg_gs": (_dg("blockGS"), BTD, (3, 3)),
     "dg_s12": (_dg("blockJac"), BTD, (12, 12)),   # more sweeps than a fused launch takes: chunks + generic transfers
     "ragged": (_ragged, BTD, (3, 3)),
+    "patch_hyb": (_dg("patchSchwarz0"), BTD, (3, 3)),
+    "patch_add": (_dg("patchAdd0"), BTD, (3, 3)),
+    "patch_gs": (_dg("patchGS0"), BTD, (3, 3)),
+    "patch_gs12": (_dg("patchGS0"), BTD, (12, 12)),   # more sweeps than a patch launch takes: chunks
 }
 
 
@@ -177,17 +216,20 @@ def main():
     H = build_device_hierarchy(U, ctx)
     print("dg levels:", H.level_kinds())
     cases("dg", H, U.rhs(), True)
+    multi_cases("dg", H, U.rhs())
     H.free()
     U = UniformCgDgHierarchy(args.cg_elems, ps=(4, 2, 1))
     H = build_device_cg_hierarchy(U, ctx)
     print("cg levels:", H.level_kinds())
     cases("cg", H, U.rhs(), False)
+    multi_cases("cg", H, U.rhs())
     H.free()
     for tag, (build, kinds, sweeps) in SMALL.items():
         H, b = build(ctx, args.small_elems)
         print(f"{tag} levels:", H.level_kinds())
         assert H.level_kinds() == kinds, (tag, H.level_kinds(), kinds)
         small_cases(tag, H, b, sweeps)
+        multi_cases(tag, H, b)
         H.free()
 
 
