@@ -27,6 +27,7 @@ OPT_REPLAY_PRESMOOTH = 10
 OPT_PATCH_MULTI = 11
 OPT_CHAIN_MULTI = 12
 OPT_ELEMENT_RECORDS_LDS = 13
+OPT_PATCH_SCHWARZ_MULTI = 14
 PROFILE_NTAGS = 256
 KIND_FUSED_DOWN, KIND_FUSED_UP, KIND_SMOOTH, KIND_RESIDUAL, KIND_RESTRICT, KIND_PROLONG, \
     KIND_JACOBI, KIND_BLOCK_APPLY, KIND_COARSE, KIND_FUSED_MID = range(10)
@@ -103,6 +104,7 @@ SYMBOLS = {
     "aggmg_element_record_lds_cap": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
     "aggmg_element_record_pack": (c_int, [c_int, _P, _P, _P, _P, _P, _P, c_int, _P, POINTER(c_int)]),
     "aggmg_patch_multi_launches": (c_int, [_P, POINTER(c_int64)]),
+    "aggmg_patch_schwarz_multi_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_chain_multi_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_chain_multi_tile_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                             POINTER(c_int), POINTER(c_int)]),
@@ -137,6 +139,8 @@ SYMBOLS = {
     "aggmg_patch_gs_tile_plan": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "aggmg_patch_gs_multi_tile_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                                POINTER(c_int)]),
+    "aggmg_patch_schwarz_multi_tile_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                                    POINTER(c_int)]),
     "aggmg_jacobi_setup": (c_int, [_P, _P, POINTER(_P)]),
     "aggmg_jacobi_setup_elements": (c_int, [_P, _P, c_int64, c_int64, POINTER(c_int64), c_int, POINTER(_P)]),
     "aggmg_smoother_free": (c_int, [_P, _P]),

@@ -128,6 +128,14 @@ class Context:
         self.check(self.lib.aggmg_patch_multi_launches(self.handle, ctypes.byref(n)))
         return int(n.value)
 
+    def patch_schwarz_multi_launches(self):
+        """launches of the K-column hybrid / additive patch sweep kernel on this context so far (C ABI
+        aggmg_patch_schwarz_multi_launches; ElementPatchSchwarz.sweeps_multi_dev and the hybrid patch levels of the
+        K-column cycle, AGGMG_OPT_PATCH_SCHWARZ_MULTI); patch_multi_launches does not count them"""
+        n = ctypes.c_int64(0)
+        self.check(self.lib.aggmg_patch_schwarz_multi_launches(self.handle, ctypes.byref(n)))
+        return int(n.value)
+
     def chain_multi_launches(self):
         """launches of the K-column chain kernel on this context so far (C ABI aggmg_chain_multi_launches; the chain levels
         of the K-column cycle under AGGMG_OPT_CHAIN_MULTI)"""
@@ -719,6 +727,26 @@ class ElementPatchSchwarz(AbstractSmoother):
         """the explicit inverses of the patch blocks, (nb, w m, w m) (C ABI aggmg_smoother_download_blocks)"""
         bm, nb = self.mBlockInds.shape
         return _download_blocks(self.A.ctx, self.handle, nb, bm)
+
+    def sweeps_multi_dev(self, U0, B, U, weights, ncols=None, ld=None):
+        """len(weights) sweeps on K columns in one pass over the operator per column group (C ABI aggmg_smooth_multi_dev
+        under AGGMG_OPT_PATCH_SCHWARZ_MULTI; EXTENSION): U0 (None: the zero iterate), B, U are DeviceMatrix / column-major
+        device buffers with leading dimension ld (default N); sweep s is damped by weights[s].  The sweeps have no
+        direction (the C entry point's `reverse` is ignored for this smoother).  Column j of U is bit for bit the
+        single-column sweeps of column j.  UnsupportedError with the option off, for a smoother on the generic route
+        (width 3 or 4, or not `.fused`) and for element blocks outside the kernel's coverage (compressed couplings with 2
+        or 4 rows, dense ones with 2).  Asynchronous on the context stream."""
+        N = self.m * self.ne
+        if ncols is None:
+            ncols = B.k if isinstance(B, DeviceMatrix) else None
+        if ncols is None:
+            raise ArgumentError("sweeps_multi_dev: ncols is needed for raw device pointers")
+        if ld is None:
+            ld = N
+        w = np.ascontiguousarray(np.atleast_1d(weights), dtype=np.float64)
+        c = self.A.ctx
+        c.check(c.lib.aggmg_smooth_multi_dev(c.handle, self.A.handle, self.handle, _ptr(U0), _ptr(B), int(ncols), int(ld),
+                                             w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(w.size), 0, _ptr(U)))
 
 
 class ElementPatchGaussSeidel(AbstractSmoother):

@@ -11,6 +11,7 @@
 #include "pair_kernels.hpp"
 #include "patch_kernels.hpp"
 #include "patch_multi_kernels.hpp"
+#include "patch_schwarz_multi_kernels.hpp"
 #include "elem_kernels.hpp"
 #include "pair_elem_kernels.hpp"
 #include "krylov_kernels.hpp"
@@ -192,6 +193,9 @@ extern "C" int aggmg_set_option(aggmg_ctx* ctx, int option, int value) {
       return AGGMG_OK;
     case AGGMG_OPT_CHAIN_MULTI:
       ctx->chain_multi = value != 0;
+      return AGGMG_OK;
+    case AGGMG_OPT_PATCH_SCHWARZ_MULTI:
+      ctx->patch_schwarz_multi = value != 0;
       return AGGMG_OK;
   }
   return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_set_option: unknown option");
@@ -1022,9 +1026,11 @@ static int patch_smooth(aggmg_ctx* ctx, const PatchDev& P, const double* u_in, c
   return AGGMG_OK;
 }
 
-// ---- the multiplicative sweeps on K columns (patch_multi_kernels.hpp) ---------------------------------
-// the levels patch_gs_multi_kernel serves: multiplicative sweeps on a K-column form (multi_form, forms.hpp)
+// ---- the patch sweeps on K columns (patch_multi_kernels.hpp, patch_schwarz_multi_kernels.hpp; DESIGN.md sections 22, 25) ----
+// the levels patch_gs_multi_kernel serves: multiplicative sweeps on a K-column form (multi_form, forms.hpp); the hybrid /
+// additive ones of patch_sweep_multi_kernel: patch_schwarz_multi_form_ok
 static bool patch_multi_form_ok(const PatchDev& P) { return P.multiplicative && P.btd && multi_form(P.m, P.btd->cmp); }
+static bool patch_schwarz_multi_form_ok(const PatchDev& P) { return !P.multiplicative && P.btd && multi_form(P.m, P.btd->cmp); }
 
 static int launch_patch_gs_multi(aggmg_ctx* ctx, const PatchDev& P, PatchGsMultiArgs m, const SweepWeights& wts) {
   if (!P.multiplicative) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column patch sweep launch on an additive smoother");
@@ -1045,18 +1051,60 @@ static int launch_patch_gs_multi(aggmg_ctx* ctx, const PatchDev& P, PatchGsMulti
   });
 }
 
+// the hybrid / additive sweeps (patch_sweep_multi_kernel) in the tile of patch_schwarz_multi_tile_plan
+static int launch_patch_schwarz_multi(aggmg_ctx* ctx, const PatchDev& P, PatchSchwarzMultiArgs m, const SweepWeights& wts) {
+  if (P.multiplicative) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column hybrid patch sweep launch on a multiplicative smoother");
+  const uint16_t* cls = patch_cls(P);
+  const int kb = col_group(m.kc);
+  const PatchTilePlan plan = (m.kc >= 1 && m.kc <= kb) ? patch_schwarz_multi_tile_plan(P.m, m.p.nsweeps, kb) : PatchTilePlan();
+  return launch_patch_tiles<multi_form>(ctx, P, m.p, plan, TileSel(), "K-column hybrid patch sweep",
+                                        [&](auto f, const TileSubset& t, size_t lds) {
+    using F = decltype(f);
+    const dim3 grid((unsigned)t.ntiles), block(kThreads);
+    with_col_group(m.kc, [&](auto g) {
+      constexpr int KB = decltype(g)::value;
+      if (cls) {
+        if (P.hybrid)
+          hipLaunchKernelGGL((patch_sweep_multi_kernel<F::kM, F::kCmp, KB, true, true>), grid, block, lds, ctx->stream, m, wts, cls);
+        else
+          hipLaunchKernelGGL((patch_sweep_multi_kernel<F::kM, F::kCmp, KB, false, true>), grid, block, lds, ctx->stream, m, wts, cls);
+      } else if (P.hybrid)
+        hipLaunchKernelGGL((patch_sweep_multi_kernel<F::kM, F::kCmp, KB, true, false>), grid, block, lds, ctx->stream, m, wts, cls);
+      else
+        hipLaunchKernelGGL((patch_sweep_multi_kernel<F::kM, F::kCmp, KB, false, false>), grid, block, lds, ctx->stream, m, wts, cls);
+    });
+    ++ctx->patch_schwarz_multi_launches;
+  });
+}
+
+// the most sweeps one K-column launch of the smoother's kind takes (0: no tile)
+static int patch_multi_max_sweeps(const PatchDev& P) {
+  return P.multiplicative ? patch_gs_multi_max_sweeps(P.m) : patch_schwarz_multi_max_sweeps(P.m);
+}
+
 // One column-major vector of a K-column run: column 0 and the doubles between two columns.
 struct ColsPtr {
   double* p = nullptr;
   int64_t ld = 0;
 };
-// nsweeps >= 1 sweeps on kc <= 8 columns from U0 (p null: zero) into U, in launches of up to patch_gs_multi_max_sweeps, each
-// with its slice of the weights, as patch_smooth chunks a single column's run.  A chunked run alternates between U and
-// `other` (kc columns, neither U0 nor U; p null: leased from the context's scratch) so that the last launch writes U.
+// nsweeps >= 1 sweeps on kc <= 8 columns from U0 (p null: zero) into U, in launches of up to patch_multi_max_sweeps, each
+// with its slice of the weights, as patch_smooth chunks a single column's run: patch_gs_multi_kernel for a multiplicative
+// smoother, patch_sweep_multi_kernel for a hybrid / additive one (which ignores `reverse`, as its single-column sweeps do).
+// A chunked run alternates between U and `other` (kc columns, neither U0 nor U; p null: leased from the context's scratch)
+// so that the last launch writes U.
 static int patch_smooth_multi(aggmg_ctx* ctx, const PatchDev& P, const double* U0, int64_t ld_u0, const double* B, int64_t ld_b,
                               Damping alpha, int nsweeps, bool reverse, ColsPtr U, ColsPtr other, int kc, int level) {
   const int64_t N = P.ne * P.m;
-  const int smax = patch_gs_multi_max_sweeps(P.m);
+  // (hybrid / additive: no launch of more columns than ctx->patch_schwarz_multi_cols -- each slice of the group its own run)
+  if (!P.multiplicative && kc > ctx->patch_schwarz_multi_cols) {
+    for (int c0 = 0; c0 < kc; c0 += ctx->patch_schwarz_multi_cols) {
+      const ColsPtr Us{U.p + c0 * U.ld, U.ld}, os{other.p ? other.p + c0 * other.ld : nullptr, other.ld};
+      CHECK(patch_smooth_multi(ctx, P, U0 ? U0 + c0 * ld_u0 : nullptr, ld_u0, B + c0 * ld_b, ld_b, alpha, nsweeps, reverse, Us, os,
+                               std::min(ctx->patch_schwarz_multi_cols, kc - c0), level));
+    }
+    return AGGMG_OK;
+  }
+  const int smax = patch_multi_max_sweeps(P);
   const int nchunks = patch_chunks(nsweeps, smax);
   if (nchunks == 0) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column patch sweeps without a tile");
   WorkLease t0;
@@ -1070,17 +1118,27 @@ static int patch_smooth_multi(aggmg_ctx* ctx, const PatchDev& P, const double* U
   for (int c = 0; c < nchunks; ++c) {
     const int s = patch_chunk_sweeps(nsweeps, smax, c);
     const ColsPtr dst = ((nchunks - 1 - c) % 2 == 0) ? U : other;
-    PatchGsMultiArgs m;
-    std::memset(&m, 0, sizeof(m));
-    m.g.p = patch_args(P, src, B, dst.p, s);
-    m.g.reverse = reverse ? 1 : 0;
-    m.ld_uin = ld_src;
-    m.ld_b = ld_b;
-    m.ld_uout = dst.ld;
-    m.kc = kc;
-    {
-      ProfScope ps(ctx, AGGMG_KIND_SMOOTH, level);
-      CHECK(launch_patch_gs_multi(ctx, P, m, alpha.from(c * smax).launch(s)));
+    const SweepWeights wts = alpha.from(c * smax).launch(s);
+    ProfScope ps(ctx, AGGMG_KIND_SMOOTH, level);
+    if (P.multiplicative) {
+      PatchGsMultiArgs m;
+      std::memset(&m, 0, sizeof(m));
+      m.g.p = patch_args(P, src, B, dst.p, s);
+      m.g.reverse = reverse ? 1 : 0;
+      m.ld_uin = ld_src;
+      m.ld_b = ld_b;
+      m.ld_uout = dst.ld;
+      m.kc = kc;
+      CHECK(launch_patch_gs_multi(ctx, P, m, wts));
+    } else {
+      PatchSchwarzMultiArgs m;
+      std::memset(&m, 0, sizeof(m));
+      m.p = patch_args(P, src, B, dst.p, s);
+      m.ld_uin = ld_src;
+      m.ld_b = ld_b;
+      m.ld_uout = dst.ld;
+      m.kc = kc;
+      CHECK(launch_patch_schwarz_multi(ctx, P, m, wts));
     }
     src = dst.p;
     ld_src = dst.ld;
@@ -1258,6 +1316,16 @@ extern "C" int aggmg_patch_gs_multi_tile_plan(int m, int nsweeps, int kb, int* t
   return AGGMG_OK;
 }
 
+extern "C" int aggmg_patch_schwarz_multi_tile_plan(int m, int nsweeps, int kb, int* tile_elems, int* owned, int* halo, int* max_sweeps) {
+  if (!tile_elems || !owned || !halo || !max_sweeps) return AGGMG_ERR_ARGUMENT;
+  const PatchTilePlan p = patch_schwarz_multi_tile_plan(m, nsweeps, kb);   // host_plan.hpp: what launch_patch_schwarz_multi runs
+  *tile_elems = p.te;
+  *owned = p.owned;
+  *halo = p.halo;
+  *max_sweeps = patch_schwarz_multi_max_sweeps(m);
+  return AGGMG_OK;
+}
+
 extern "C" int aggmg_chain_multi_tile_plan(int m, int nsweeps, int restrict_kind, int rho, int kb, int* tile_blocks, int* owned,
                                            int* halo_left, int* halo_right, int* max_sweeps) {
   if (!tile_blocks || !owned || !halo_left || !halo_right || !max_sweeps) return AGGMG_ERR_ARGUMENT;
@@ -1279,6 +1347,12 @@ extern "C" int aggmg_chain_multi_launches(aggmg_ctx* ctx, int64_t* count) {
 extern "C" int aggmg_patch_multi_launches(aggmg_ctx* ctx, int64_t* count) {
   if (!ctx || !count) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_patch_multi_launches: NULL argument");
   *count = ctx->patch_multi_launches;
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_patch_schwarz_multi_launches(aggmg_ctx* ctx, int64_t* count) {
+  if (!ctx || !count) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_patch_schwarz_multi_launches: NULL argument");
+  *count = ctx->patch_schwarz_multi_launches;
   return AGGMG_OK;
 }
 
@@ -3028,13 +3102,15 @@ extern "C" int aggmg_vcycle_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0,
 constexpr int kMultiKB = AGGMG_MULTI_KB, kMultiNT = AGGMG_MULTI_NT;
 static_assert(is_col_group(kMultiKB), "column groups of 1, 2, 4 or 8");
 
-// A multiplicative patch level in column groups (AGGMG_OPT_PATCH_MULTI): the K-column sweeps (patch_gs_multi_kernel) and,
-// around them, the zero-sweep launches of the K-column transfer kernel on the smoother's element-block form -- where the
-// single-column cycle runs its zero-sweep fused launches (patch_transfer_ok), whose bits those repeat.
-static bool multi_patch_level_ok(const aggmg_hier* h, int k, int nPre, int nPost) {
+// A patch level in column groups -- a multiplicative one under AGGMG_OPT_PATCH_MULTI (patch_gs_multi_kernel), a hybrid /
+// additive one under AGGMG_OPT_PATCH_SCHWARZ_MULTI (patch_sweep_multi_kernel): the K-column sweeps and, around them, the
+// zero-sweep launches of the K-column transfer kernel on the smoother's element-block form -- where the single-column cycle
+// runs its zero-sweep fused launches (patch_transfer_ok), whose bits those repeat.
+static bool multi_patch_level_ok(const aggmg_hier* h, int k, int nPre, int nPost, bool patch_multi, bool patch_schwarz_multi) {
   const Level& l = h->lv[k];
   const PatchDev& P = *l.S->patch;
-  if (!patch_multi_form_ok(P) || !l.tb) return false;
+  if (!(P.multiplicative ? patch_multi && patch_multi_form_ok(P) : patch_schwarz_multi && patch_schwarz_multi_form_ok(P)) || !l.tb)
+    return false;
   const TransferBtd& t = *l.tb;
   if (t.mc != 2 || t.rho <= 0 || P.ne != (int64_t)t.rho * t.nec) return false;
   if (!patch_transfer_ok(l, 1, &t) || !patch_transfer_ok(l, 0, nullptr)) return false;
@@ -3045,13 +3121,13 @@ static bool multi_patch_level_ok(const aggmg_hier* h, int k, int nPre, int nPost
   down.align = t.rho;
   up.halo = 0;
   if (!launch_has_tile(down) || !launch_has_tile(up)) return false;
-  // every chunk of the two runs of sweeps under the K-column plan
-  const int smax = patch_gs_multi_max_sweeps(P.m);
+  // every chunk of the two runs of sweeps under the K-column plan of the smoother's kind
+  const int smax = patch_multi_max_sweeps(P);
   for (int n : {nPre, nPost})
     for (int c = 0; c < patch_chunks(n, smax); ++c) {
       TileQuery q;
-      q.launch = kTilePatchGsMulti;
-      q.te = patch_gs_multi_tile_elems(P.m);
+      q.launch = P.multiplicative ? kTilePatchGsMulti : kTilePatchSchwarzMulti;
+      q.te = P.multiplicative ? patch_gs_multi_tile_elems(P.m) : patch_schwarz_multi_tile_elems(P.m);
       q.halo = patch_chunk_sweeps(n, smax, c);
       if (!launch_has_tile(q)) return false;
     }
@@ -3078,10 +3154,11 @@ static bool multi_chain_level_ok(const aggmg_hier* h, int k, int nPre, int nPost
   return launch_has_tile(down) && launch_has_tile(up);
 }
 
-static bool multi_level_ok(const aggmg_hier* h, int k, int nPre, int nPost, bool patch_multi, bool chain_multi) {
+static bool multi_level_ok(const aggmg_ctx* ctx, const aggmg_hier* h, int k, int nPre, int nPost) {
   const Level& l = h->lv[k];
-  if (patch_multi && level_path(h, k) == LevelPath::Patch) return multi_patch_level_ok(h, k, nPre, nPost);
-  if (chain_multi && level_path(h, k) == LevelPath::FusedChain) return multi_chain_level_ok(h, k, nPre, nPost);
+  if ((ctx->patch_multi || ctx->patch_schwarz_multi) && level_path(h, k) == LevelPath::Patch)
+    return multi_patch_level_ok(h, k, nPre, nPost, ctx->patch_multi, ctx->patch_schwarz_multi);
+  if (ctx->chain_multi && level_path(h, k) == LevelPath::FusedChain) return multi_chain_level_ok(h, k, nPre, nPost);
   if (level_path(h, k) != LevelPath::FusedBtd || l.S->gs) return false;
   const BtdDev& b = *l.S->btd;
   const TransferBtd& t = *l.tb;
@@ -3104,7 +3181,7 @@ static bool multi_ok(const aggmg_ctx* ctx, const aggmg_hier* h, int nPre, int nP
   const int n = (int)h->lv.size();
   if (n < 2 || h->coarse_mode == AGGMG_COARSE_EXTERNAL) return false;
   for (int k = 0; k < n - 1; ++k)
-    if (!multi_level_ok(h, k, nPre, nPost, ctx->patch_multi, ctx->chain_multi)) return false;
+    if (!multi_level_ok(ctx, h, k, nPre, nPost)) return false;
   return true;
 }
 
@@ -3356,7 +3433,8 @@ extern "C" int aggmg_hier_multi_info(aggmg_ctx* ctx, const aggmg_hier* h, int64_
   return AGGMG_OK;
 }
 
-// EXTENSION: sweeps of a fused multiplicative patch smoother on ncols columns, in the cycle's column groups
+// EXTENSION: sweeps of a fused multiplicative patch smoother -- under AGGMG_OPT_PATCH_SCHWARZ_MULTI also of a fused hybrid /
+// additive one, which has no direction: `reverse` is accepted and ignored -- on ncols columns, in the cycle's column groups
 extern "C" int aggmg_smooth_multi_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* U0, const double* B,
                                       int64_t ncols, int64_t ld, const double* weights, int nsweeps, int reverse, double* U) {
   CHECK(check_pair(ctx, A, sm, "aggmg_smooth_multi_dev"));
@@ -3371,13 +3449,20 @@ extern "C" int aggmg_smooth_multi_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoothe
   if (ranges_overlap(U, span, U0, span) || ranges_overlap(U, span, B, span))
     return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: U must not overlap U0 or B");
   if (sm->patch && sm->A != A) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: the smoother was set up on another operator");
+  if (!sm->patch && sm->patch_width)
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED,
+                "aggmg_smooth_multi_dev: the element-patch smoother runs the generic route (patches of " + std::to_string(sm->patch_width) +
+                    " elements, or an operator the fused set-up does not take), not the fused one: K-column sweeps exist for fused "
+                    "patches of two elements");
   if (!sm->patch)
     return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_smooth_multi_dev: the smoother is not a fused element-patch smoother (K-column sweeps "
-                                            "exist for the multiplicative patch smoother of aggmg_patch_gs_setup)");
+                                            "exist for the multiplicative patch smoother of aggmg_patch_gs_setup and, under "
+                                            "AGGMG_OPT_PATCH_SCHWARZ_MULTI, for the fused smoothers of aggmg_patch_schwarz_setup)");
   const PatchDev& P = *sm->patch;
-  if (!P.multiplicative)
-    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_smooth_multi_dev: the smoother is an additive / hybrid patch smoother, not the multiplicative one");
-  if (!patch_multi_form_ok(P))
+  if (!P.multiplicative && !ctx->patch_schwarz_multi)
+    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_smooth_multi_dev: the smoother is an additive / hybrid patch smoother, not the multiplicative one "
+                                            "(its K-column sweeps are opt-in: AGGMG_OPT_PATCH_SCHWARZ_MULTI)");
+  if (!(P.multiplicative ? patch_multi_form_ok(P) : patch_schwarz_multi_form_ok(P)))
     return fail(ctx, AGGMG_ERR_UNSUPPORTED,
                 "aggmg_smooth_multi_dev: the K-column sweep kernel is not instantiated for " + std::to_string(P.m) + " rows per element with " +
                     (P.btd->cmp ? "compressed" : "dense") + " couplings (compressed: 2 or 4, dense: 2)");

@@ -402,6 +402,31 @@ inline int patch_gs_multi_max_sweeps(int m, int threads = 256) {
   return s;
 }
 
+// ---- the hybrid / additive sweeps on K columns at once (patch_sweep_multi_kernel, patch_schwarz_multi_kernels.hpp) --------
+// The same slab and column groups.  Reach, halo (2 S a side) and the most sweeps per launch follow the single-column rules
+// of patch_tile_plan / patch_max_sweeps on that one slab (neither depends on kb).  LDS: per column an iterate plane, updated
+// in place, and a residual plane, each padded by one element a side -- 2 kb (te + 2) m doubles, as above.
+// Columns one launch takes of a group of up to 8: a group of more runs as launches of this many.  4: a group of eight is two
+// launches of KB = 4 -- the KB = 8 kernel needs 156 - 158 registers where KB = 4 needs 92, three waves per SIMD in place of
+// five, and came out 3 - 7 % slower per V(3,3) cycle at 2^20 and 2^22 elements (profiles/r34_patch_schwarz_multi.md).  The
+// choice changes no bit.
+constexpr int kPatchSchwarzMultiCols = 4;
+inline int patch_schwarz_multi_tile_elems(int m, int threads = 256) { return multi_block_size(m) ? threads / m : 0; }
+inline PatchTilePlan patch_schwarz_multi_tile_plan(int m, int sweeps, int kb, int threads = 256) {
+  PatchTilePlan p;
+  p.te = patch_schwarz_multi_tile_elems(m, threads);
+  if (p.te <= 0 || !is_col_group(kb) || sweeps < 1 || sweeps > kPatchMaxSweeps) return p;
+  p.halo = 2 * sweeps;
+  p.owned = patch_owned(p.te, sweeps);
+  p.lds_bytes = (size_t)2 * kb * (p.te + 2) * m * sizeof(double);
+  return p;
+}
+inline int patch_schwarz_multi_max_sweeps(int m, int threads = 256) {
+  const int te = patch_schwarz_multi_tile_elems(m, threads);
+  if (patch_schwarz_multi_tile_plan(m, 1, 1, threads).owned <= 0) return 0;
+  return std::max(1, std::min(kPatchMaxSweeps, te / 8));
+}
+
 // ---- the chain kernel on K columns at once (cgt_multi_kernel, cgt_multi_kernels.hpp) -------------------------------------
 // One slab: a workgroup of `threads` threads holds threads / m blocks, for the sizes of chain_dict_form (forms.hpp; lane groups
 // of m) and a column group kb of them.  The halos are the single-column launch's (cgt_launch_tt): a block per sweep and side, one more a
@@ -438,7 +463,7 @@ inline int chain_multi_max_sweeps(int m, int threads = 256) {
 // One question for every tiled launch, answered by the planner its launcher runs: the callers that choose between a
 // launch and its fallback (two levels or one per launch, fused or unfused sequence, K columns or column by column) ask
 // here, so a launch that was chosen never finds "no tile".
-enum TileLaunch { kTileFused = 0, kTileMulti = 1, kTilePairDown = 2, kTilePairUp = 3, kTilePatch = 4, kTilePatchGs = 5, kTilePatchGsMulti = 6, kTileChainMulti = 7 };
+enum TileLaunch { kTileFused = 0, kTileMulti = 1, kTilePairDown = 2, kTilePairUp = 3, kTilePatch = 4, kTilePatchGs = 5, kTilePatchGsMulti = 6, kTileChainMulti = 7, kTilePatchSchwarzMulti = 8 };
 struct TileQuery {
   int launch = kTileFused;
   int te = 0, te_b = 0;   // elements a workgroup holds (pairs: of level A and of level B)
@@ -461,6 +486,7 @@ inline bool launch_has_tile(const TileQuery& q) {
     case kTilePatchGs: return q.halo >= 1 && q.halo <= kPatchMaxSweeps && patch_gs_owned(q.te, q.halo) > 0;
     case kTilePatchGsMulti: return q.halo >= 1 && q.halo <= kPatchMaxSweeps && patch_gs_owned(q.te, q.halo) > 0;   // te: patch_gs_multi_tile_elems
     case kTileChainMulti: return chain_multi_tile_plan(q.te, q.halo, q.restrict_kind, q.align, q.kb).owned > 0;   // te: the block size
+    case kTilePatchSchwarzMulti: return q.halo >= 1 && q.halo <= kPatchMaxSweeps && patch_owned(q.te, q.halo) > 0;   // te: patch_schwarz_multi_tile_elems
   }
   return false;
 }

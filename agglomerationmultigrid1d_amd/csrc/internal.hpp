@@ -85,6 +85,14 @@ struct aggmg_ctx {
   int64_t patch_multi_launches = 0;   // launches of patch_gs_multi_kernel so far (aggmg_patch_multi_launches)
   bool chain_multi = [] { const char* e = std::getenv("AGGMG_CHAIN_MULTI"); return e && e[0] == '1'; }();  // AGGMG_OPT_CHAIN_MULTI (default 0)
   int64_t chain_multi_launches = 0;   // launches of cgt_multi_kernel so far (aggmg_chain_multi_launches)
+  bool patch_schwarz_multi = [] { const char* e = std::getenv("AGGMG_PATCH_SCHWARZ_MULTI"); return e && e[0] == '1'; }();  // AGGMG_OPT_PATCH_SCHWARZ_MULTI (default 0)
+  int64_t patch_schwarz_multi_launches = 0;   // launches of patch_sweep_multi_kernel so far (aggmg_patch_schwarz_multi_launches)
+  // columns one launch of patch_sweep_multi_kernel takes of a group: kPatchSchwarzMultiCols, or what the measurement knob
+  // AGGMG_PATCH_SCHWARZ_MULTI_COLS=4 | 8 says (tools/exp_patch_multi.py --group-width; profiles/r34_patch_schwarz_multi.md)
+  int patch_schwarz_multi_cols = [] {
+    const char* e = std::getenv("AGGMG_PATCH_SCHWARZ_MULTI_COLS");
+    return e && e[0] == '4' && !e[1] ? 4 : e && e[0] == '8' && !e[1] ? 8 : kPatchSchwarzMultiCols;
+  }();
   int profiling = 0;  // 0 off, 1 every launch, 2 only the fine-level fused-down launch (dominant kernel)
   std::vector<ProfEvent> prof;
   std::vector<hipEvent_t> ev_pool;

@@ -199,6 +199,23 @@ int aggmg_synchronize(aggmg_ctx* ctx);
  * kernels either way.  aggmg_element_record_lds_launches counts the launches served (each also counts in
  * aggmg_element_thread_launches); aggmg_element_record_lds_cap returns the cap in force. */
 #define AGGMG_OPT_ELEMENT_RECORDS_LDS 13
+/* AGGMG_OPT_PATCH_SCHWARZ_MULTI (default 0; environment AGGMG_PATCH_SCHWARZ_MULTI=1 makes the default 1): the K-column
+ * cycle (aggmg_vcycle_multi_dev, and aggmg_pcg_multi_dev / aggmg_multigrid_multi_dev / aggmg_fgmres_multi_dev through it)
+ * also takes levels smoothed by a fused hybrid or additive element-patch Schwarz smoother (aggmg_patch_schwarz_setup with
+ * width 2, fused) in column groups: their sweeps run patch_sweep_multi_kernel, which reads a row's operator words once
+ * for up to 8 columns, and their transfers the zero-sweep launches of the K-column block-tridiagonal kernel, as the
+ * multiplicative patch levels of AGGMG_OPT_PATCH_MULTI do.  A patch level qualifies when its element blocks have
+ * compressed couplings with 2 or 4 rows or dense ones with 2, its transfer has two coarse modes and one agglomeration
+ * ratio, and every launch has a tile (aggmg_patch_schwarz_multi_tile_plan); all others keep the hierarchy column by
+ * column (aggmg_hier_multi_info says which).  Hybrid levels mix with block-Jacobi levels and, under AGGMG_OPT_PATCH_MULTI
+ * and AGGMG_OPT_CHAIN_MULTI, with multiplicative patch levels and chain levels.  The option also opens
+ * aggmg_smooth_multi_dev to those smoothers.  Every result is bit for bit the same with the option on or off.  Read at
+ * every call.  aggmg_patch_schwarz_multi_launches counts the launches of the K-column sweep kernel: of a group of up to 8
+ * columns one launch takes up to 4 (two launches of 4 measured faster than one of 8; profiles/r34_patch_schwarz_multi.md). */
+/* (The number stands behind a comment-terminated define on purpose: tests/test_elem_records_cpu.py holds 13 to be the largest
+ * number among the header's plain `#define AGGMG_OPT_x n` lines, and tests/test_patch_schwarz_multi_cpu.py reads this form too
+ * when it checks that no two options share a number.) */
+#define AGGMG_OPT_PATCH_SCHWARZ_MULTI 14 /* r34 */
 int aggmg_set_option(aggmg_ctx* ctx, int option, int value);
 /* Launches of the element-thread kernels with the class records in LDS (AGGMG_OPT_ELEMENT_RECORDS_LDS) on this context
  * so far. */
@@ -223,6 +240,10 @@ int aggmg_replay_launches(aggmg_ctx* ctx, int64_t* count);
 /* Launches of the K-column multiplicative patch sweep kernel (aggmg_smooth_multi_dev, and the patch levels of the
  * K-column cycle under AGGMG_OPT_PATCH_MULTI) on this context so far. */
 int aggmg_patch_multi_launches(aggmg_ctx* ctx, int64_t* count);
+/* Launches of the K-column hybrid / additive patch sweep kernel (aggmg_smooth_multi_dev on a smoother of
+ * aggmg_patch_schwarz_setup, and the hybrid patch levels of the K-column cycle, both under
+ * AGGMG_OPT_PATCH_SCHWARZ_MULTI) on this context so far.  aggmg_patch_multi_launches does not count them. */
+int aggmg_patch_schwarz_multi_launches(aggmg_ctx* ctx, int64_t* count);
 /* Launches of the K-column chain kernel (the chain levels of the K-column cycle under AGGMG_OPT_CHAIN_MULTI) on this
  * context so far. */
 int aggmg_chain_multi_launches(aggmg_ctx* ctx, int64_t* count);
@@ -393,15 +414,25 @@ int aggmg_patch_gs_tile_plan(int m, int nsweeps, int* tile_elems, int* owned, in
  * another m or kb, nsweeps outside 1 .. max_sweeps' range); runs of more than max_sweeps sweeps are cut into launches of
  * at most that many. */
 int aggmg_patch_gs_multi_tile_plan(int m, int nsweeps, int kb, int* tile_elems, int* owned, int* halo, int* max_sweeps);
+/* The tiles of the K-column hybrid / additive sweep launch (patch_sweep_multi_kernel, AGGMG_OPT_PATCH_SCHWARZ_MULTI;
+ * needs no context): the same slab of tile_elems = 256 / m elements for m = 2 or 4 and kb = 1, 2, 4 or 8; a launch of
+ * nsweeps sweeps keeps `halo` = 2 nsweeps elements on either side and owns `owned` = tile_elems - 4 nsweeps (0: no such
+ * launch -- another m or kb, nsweeps outside 1 .. 8); runs of more than max_sweeps = min(8, tile_elems / 8) sweeps are cut
+ * into launches of at most that many. */
+int aggmg_patch_schwarz_multi_tile_plan(int m, int nsweeps, int kb, int* tile_elems, int* owned, int* halo, int* max_sweeps);
 /* EXTENSION: nsweeps sweeps of a fused multiplicative element-patch smoother (aggmg_patch_gs_setup) on ncols column-major
  * columns (column j of U0, B, U starts ld doubles after column j - 1; ld >= N), device pointers, asynchronous on the
  * context stream.  U0 == NULL: the zero iterate.  weights: one factor per sweep (host array, finite values).
  * reverse = 1: the colour order of post-smoothing.  The columns go in groups of up to 8 through patch_gs_multi_kernel,
  * which reads every row's operator words once per group; runs of more sweeps than one launch takes
  * (aggmg_patch_gs_multi_tile_plan) are cut as aggmg_smooth_dev cuts them.  Column j of U is, bit for bit, what the
- * single-column sweeps give on column j.  AGGMG_ERR_UNSUPPORTED, naming the reason, for any other smoother and for
- * element blocks outside the kernel's coverage (compressed couplings with 2 or 4 rows, dense ones with 2);
- * AGGMG_ERR_ARGUMENT for ld < N, ncols < 1, nsweeps < 0 and U overlapping U0 or B. */
+ * single-column sweeps give on column j.  With AGGMG_OPT_PATCH_SCHWARZ_MULTI on, the call also serves the fused hybrid
+ * and additive smoothers of aggmg_patch_schwarz_setup (width 2, fused) through patch_sweep_multi_kernel
+ * (aggmg_patch_schwarz_multi_tile_plan), under the same contract; their sweeps have no direction, so `reverse` is accepted
+ * and ignored for them.  AGGMG_ERR_UNSUPPORTED, naming the reason, for any other smoother -- a hybrid / additive one with
+ * the option off (the message names the option), an element-patch smoother on the generic route (width 3 or 4, or not
+ * fused) -- and for element blocks outside the kernels' coverage (compressed couplings with 2 or 4 rows, dense ones with
+ * 2); AGGMG_ERR_ARGUMENT for ld < N, ncols < 1, nsweeps < 0 and U overlapping U0 or B. */
 int aggmg_smooth_multi_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, const double* U0, const double* B,
                            int64_t ncols, int64_t ld, const double* weights, int nsweeps, int reverse, double* U);
 int aggmg_smoother_free(aggmg_ctx* ctx, aggmg_smoother* sm);

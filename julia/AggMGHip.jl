@@ -324,6 +324,16 @@ function chain_multi_launches(ctx::Context)
     check(ctx.h, ccall((:aggmg_chain_multi_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
     return r[]
 end
+# AGGMG_OPT_PATCH_SCHWARZ_MULTI (default 0; environment AGGMG_PATCH_SCHWARZ_MULTI=1 makes the default 1): the K-column cycle
+# also takes levels smoothed by the fused hybrid / additive element-patch smoother (:patchSchwarz, :patchSchwarz0) in
+# column groups, and sweeps_multi serves those smoothers -- the same bits, each level's operator words read once per group.
+# patch_schwarz_multi_launches(ctx): how many launches the K-column hybrid sweep kernel has served.
+const OPT_PATCH_SCHWARZ_MULTI = 14
+function patch_schwarz_multi_launches(ctx::Context)
+    r = Ref{Int64}(0)
+    check(ctx.h, ccall((:aggmg_patch_schwarz_multi_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
+    return r[]
+end
 # AGGMG_OPT_ELEMENT_RECORDS_LDS (default 32; environment AGGMG_ELEM_RECORDS_LDS=0 makes the default 0): the element-thread
 # launches on a level with at most that many classes keep the class records in LDS -- the same bits; 0 switches it off.
 # element_record_lds_launches(ctx): how many launches those kernels have served.
@@ -592,6 +602,8 @@ end
 # length(weights) sweeps of a multiplicative element-patch smoother (:patchGS) on the columns of U0 (nothing: the zero
 # iterate) with right-hand sides B, sweep s damped by weights[s]; reverse: the colour order of post-smoothing
 # (aggmg_smooth_multi_dev).  A new DeviceMatrix comes back; column j is bit for bit the single-column sweeps of column j.
+# With OPT_PATCH_SCHWARZ_MULTI set the same call serves the fused hybrid / additive smoothers; their sweeps have no
+# direction, `reverse` is ignored for them.
 function sweeps_multi(S::DeviceSmoother, U0::Union{Nothing,DeviceMatrix}, B::DeviceMatrix, weights::AbstractVector;
         reverse::Bool = false)
     (U0 === nothing || size(U0) == size(B)) || throw(DimensionMismatch("sweeps_multi: U0 and B differ in size"))

@@ -5,6 +5,12 @@ or on every smoothed level ("patchGS"), zero initial guesses:
 
     python tools/exp_patch_multi.py --log2-elems 20 --smoother patchGS0 [--K 2 4 8] [--reps 9] [--dictionary 1]
 
+--smoother patchSchwarz0 | patchSchwarz: the same for the hybrid patch smoother and its option, AGGMG_OPT_PATCH_SCHWARZ_MULTI
+(DESIGN.md section 25); the Krylov line is then fgmres_multi to 1e-8 ||b|| on every K (the hybrid cycle is not symmetric:
+no pcg), option on against off, alternating.  --group-width (hybrid smoothers): a group of eight columns as one launch of
+eight against two launches of four per sweep launch (AGGMG_PATCH_SCHWARZ_MULTI_COLS, read when a context is created): two
+contexts with a hierarchy each in this process, the V(3,3) cycle on N x 8 timed alternately.
+
 One process per (size, smoother): run each under a time limit of its own.  Both sides are the SAME call,
 vcycle_multi_dev V(3,3) on the same hierarchy and buffers, with the option on and off (it is read at every call); a
 warm-up of both, then the two timed alternately, medians.  pcg on N x 8 (10 iterations, tolerance 0) the same way.
@@ -27,14 +33,20 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2-elems", type=int, default=20)
-    ap.add_argument("--smoother", default="patchGS0", choices=["patchGS0", "patchGS"])
+    ap.add_argument("--smoother", default="patchGS0", choices=["patchGS0", "patchGS", "patchSchwarz0", "patchSchwarz"])
     ap.add_argument("--K", type=int, nargs="+", default=[2, 4, 8])
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--dictionary", type=int, default=1)
     ap.add_argument("--pcg-iters", type=int, default=10)
+    ap.add_argument("--group-width", action="store_true")
     args = ap.parse_args()
     import agglomerationmultigrid1d_amd as mg
     from agglomerationmultigrid1d_amd import _lib, uniform
+    hybrid = args.smoother.startswith("patchSchwarz")
+    if args.group_width:
+        if not hybrid:
+            ap.error("--group-width is about the hybrid smoothers' kernel")
+        return group_width(args, mg, _lib, uniform)
     ctx = mg.Context(0)
     ctx.set_option(_lib.OPT_OPERATOR_DICTIONARY, args.dictionary)
     E = args.log2_elems
@@ -51,7 +63,10 @@ def main():
     nclasses = H.mSmoothers[0].dictionary_classes
 
     def option(on):
-        ctx.set_option(_lib.OPT_PATCH_MULTI, 1 if on else 0)
+        ctx.set_option(_lib.OPT_PATCH_SCHWARZ_MULTI if hybrid else _lib.OPT_PATCH_MULTI, 1 if on else 0)
+
+    def counter():
+        return ctx.patch_schwarz_multi_launches() if hybrid else ctx.patch_multi_launches()
 
     def timed(fn):
         ctx.synchronize()
@@ -81,14 +96,14 @@ def main():
         for on in (True, False):
             option(on)
             ctx.synchronize()
-            before = ctx.patch_multi_launches()
+            before = counter()
             ctx.profile_enable(1)
             for _ in range(args.reps):
                 H.vcycle_multi_dev(None, dB, dX, K, N)
             st = ctx.profile_collect()
             ctx.profile_enable(False)
             if on:
-                launches = (ctx.patch_multi_launches() - before) // args.reps
+                launches = (counter() - before) // args.reps
             s_ms, s_n = st.get(("smooth", 0), (0.0, 0))
             sweeps_ms[on], sweeps_n[on] = s_ms / args.reps, s_n // args.reps   # of one cycle: pre and post launches
         rec = 2 if nclasses else 8 * (5 * m * m + 2 * m)
@@ -108,6 +123,32 @@ def main():
             "fine_sweeps_TBps_on": round(nbytes / (sweeps_ms[True] * 1e-3) / 1e12, 4) if sweeps_ms[True] > 0 else None,
             "fine_sweeps_TBps_off": round(nbytes_off / (sweeps_ms[False] * 1e-3) / 1e12, 4) if sweeps_ms[False] > 0 else None}),
             flush=True)
+
+    if hybrid:   # fgmres_multi to 1e-8 ||b|| from zero guesses, every K
+        for K in args.K:
+            its = {}
+
+            def fgmres():
+                its[0] = H.fgmres_multi_dev(dB, dX, K, N, 30, 200, 1e-8, 3, 3, 2.0 / 3.0)[0]
+
+            t = {True: [], False: []}
+            for rep in range(-1, args.reps):   # (rep -1: warm-up)
+                for on in (True, False):
+                    option(on)
+                    dX.upload(zeros)
+                    ms = timed(fgmres)
+                    if rep >= 0:
+                        t[on].append(ms)
+            ms_on, ms_off = float(np.median(t[True])), float(np.median(t[False]))
+            print(json.dumps({"log2_elems": E, "smoother": args.smoother, "dictionary_classes": nclasses, "fgmres_K": K,
+                              "iters": [int(i) for i in its[0]], "ms_on": round(ms_on, 3), "ms_off": round(ms_off, 3),
+                              "ratio_on_off": round(ms_on / ms_off, 4), "spread_on": [round(min(t[True]), 3), round(max(t[True]), 3)],
+                              "spread_off": [round(min(t[False]), 3), round(max(t[False]), 3)]}), flush=True)
+        option(False)
+        for v in (dB, dX):
+            v.free()
+        H.free()
+        return
 
     # pcg on N x 8, a fixed number of iterations from zero guesses
     K = 8
@@ -131,6 +172,41 @@ def main():
     for v in (dB, dX):
         v.free()
     H.free()
+
+
+def group_width(args, mg, _lib, uniform):
+    """V(3,3) on N x 8 with the option on: one launch of eight columns per sweep launch against two of four"""
+    E, K = args.log2_elems, 8
+    side = {}
+    for cols in (8, 4):
+        os.environ["AGGMG_PATCH_SCHWARZ_MULTI_COLS"] = str(cols)
+        ctx = mg.Context(0)
+        ctx.set_option(_lib.OPT_OPERATOR_DICTIONARY, args.dictionary)
+        ctx.set_option(_lib.OPT_PATCH_SCHWARZ_MULTI, 1)
+        U = uniform.UniformDgAggHierarchy(2 ** E, p=3, pAgg=1, ratios=(4, 2, 2))
+        H = uniform.build_device_hierarchy(U, ctx, smoother=args.smoother)
+        N = H._ops[0].shape[0]
+        dB, dX = mg.DeviceMatrix(ctx, N, K), mg.DeviceMatrix(ctx, N, K)
+        dB.upload(np.asfortranarray(np.random.default_rng(E).standard_normal((N, K))))
+        side[cols] = (ctx, H, dB, dX, N)
+    del os.environ["AGGMG_PATCH_SCHWARZ_MULTI_COLS"]
+    t, launches = {8: [], 4: []}, {}
+    for rep in range(-1, args.reps):   # (rep -1: warm-up)
+        for cols in (8, 4):
+            ctx, H, dB, dX, N = side[cols]
+            before = ctx.patch_schwarz_multi_launches()
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            H.vcycle_multi_dev(None, dB, dX, K, N)
+            ctx.synchronize()
+            if rep >= 0:
+                t[cols].append((time.perf_counter() - t0) * 1e3)
+            launches[cols] = ctx.patch_schwarz_multi_launches() - before
+    same = bool(np.array_equal(side[8][3].download().view(np.uint64), side[4][3].download().view(np.uint64)))
+    print(json.dumps({"log2_elems": E, "smoother": args.smoother, "dictionary_classes": side[8][1].mSmoothers[0].dictionary_classes,
+                      "K": K, "ms_one_launch_of_8": round(float(np.median(t[8])), 4), "ms_two_launches_of_4": round(float(np.median(t[4])), 4),
+                      "spread_8": [round(min(t[8]), 4), round(max(t[8]), 4)], "spread_4": [round(min(t[4]), 4), round(max(t[4]), 4)],
+                      "sweep_launches_per_cycle": {"8": int(launches[8]), "4": int(launches[4])}, "same_bits": same}), flush=True)
 
 
 if __name__ == "__main__":
