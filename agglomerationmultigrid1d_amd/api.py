@@ -121,6 +121,20 @@ class Context:
         self.check(self.lib.aggmg_element_record_lds_cap(self.handle, ctypes.byref(c), ctypes.byref(m)))
         return int(c.value), int(m.value)
 
+    def coarse_dictionary_launches(self):
+        """stage launches of the coarsest solve that read their factors from LDS on this context so far (C ABI
+        aggmg_coarse_dictionary_launches, AGGMG_OPT_COARSE_DICTIONARY)"""
+        n = ctypes.c_int64(0)
+        self.check(self.lib.aggmg_coarse_dictionary_launches(self.handle, ctypes.byref(n)))
+        return int(n.value)
+
+    def coarse_dictionary_cap(self):
+        """(cap on classes in force, largest cap the option takes) of AGGMG_OPT_COARSE_DICTIONARY (C ABI
+        aggmg_coarse_dictionary_cap)"""
+        c, m = ctypes.c_int(0), ctypes.c_int(0)
+        self.check(self.lib.aggmg_coarse_dictionary_cap(self.handle, ctypes.byref(c), ctypes.byref(m)))
+        return int(c.value), int(m.value)
+
     def patch_multi_launches(self):
         """launches of the K-column multiplicative patch sweep kernel on this context so far (C ABI
         aggmg_patch_multi_launches; ElementPatchGaussSeidel.sweeps_multi_dev, AGGMG_OPT_PATCH_MULTI)"""
@@ -1494,6 +1508,21 @@ class MeshHierarchy:
         return dict(on_device=bool(a.value), block_size=b.value, cond_est=c.value, probe_backward_error=e.value,
                     tail=("none", "cyclic reduction", "parallel cyclic reduction")[k.value], tail_blocks=nb.value,
                     order="element chain" if on.value else "operator")
+
+    def coarse_dictionary(self):
+        """-> dict(stages=[dict(taken, first_level, levels)], even_classes=[...], odd_classes=[...]) of the coarsest
+        solve's dictionary (AGGMG_OPT_COARSE_DICTIONARY; C ABI aggmg_hier_coarse_dictionary): per chunk stage whether its
+        launches read their factors from LDS and the reducing levels it spans; per reducing level up to the last one of
+        the last stage the distinct records among its even rows' multipliers and among its odd rows' factors (-1: not
+        classed, 0: more than the search tracks)"""
+        cap = 64
+        arr = [(ctypes.c_int * cap)() for _ in range(5)]
+        ns = ctypes.c_int(0)
+        self.ctx.check(self.ctx.lib.aggmg_hier_coarse_dictionary(self.ctx.handle, self.handle, cap, ctypes.byref(ns), *arr))
+        taken, first, nlv, ev, od = arr
+        stages = [dict(taken=bool(taken[s]), first_level=int(first[s]), levels=int(nlv[s])) for s in range(ns.value)]
+        nl = max((s["first_level"] + s["levels"] for s in stages), default=0)
+        return dict(stages=stages, even_classes=[int(ev[l]) for l in range(nl)], odd_classes=[int(od[l]) for l in range(nl)])
 
     def last_coarse_ms(self):
         ms = ctypes.c_double(0.0)

@@ -188,6 +188,11 @@ extern "C" int aggmg_set_option(aggmg_ctx* ctx, int option, int value) {
         return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_set_option: AGGMG_OPT_ELEMENT_RECORDS_LDS takes 0 .. " + std::to_string(kElemRecMaxClasses));
       ctx->elem_rec_cap = value;
       return AGGMG_OK;
+    case AGGMG_OPT_COARSE_DICTIONARY:
+      if (value < 0 || value > kCrDictMaxClasses)
+        return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_set_option: AGGMG_OPT_COARSE_DICTIONARY takes 0 .. " + std::to_string(kCrDictMaxClasses));
+      ctx->coarse_dict_cap = value;
+      return AGGMG_OK;
     case AGGMG_OPT_PATCH_MULTI:
       ctx->patch_multi = value != 0;
       return AGGMG_OK;
@@ -1906,17 +1911,54 @@ static void cr_launch_tail(aggmg_ctx* ctx, CrDev& cr, const CrStageArgs& T, size
   hipLaunchKernelGGL((cr_tail_kernel<M>), dim3(1, kc), dim3(kCrThreads), tail_lds, ctx->stream, T, d, db, x);
 }
 
-// one launch of a stage's forward / backward kernel: chunks A.c0 .. A.c0 + grid of kc columns
+// where a launch of stage S finds the stage's table and class indices (S.dict.take; AGGMG_OPT_COARSE_DICTIONARY)
+static CrDictArgs cr_make_dict_args(const CrStage& S) {
+  CrDictArgs D;
+  std::memset(&D, 0, sizeof(D));
+  D.tab = S.dict_tab;
+  D.cidx = S.dict_idx;
+  for (int l = 0; l < S.q; ++l) {
+    D.tab_e[l] = S.dict.tab_e[l];
+    D.tab_o[l] = S.dict.tab_o[l];
+    D.idx_e[l] = S.dict.idx_e[l];
+    D.idx_o[l] = S.dict.idx_o[l];
+  }
+  D.tab_words = S.dict.tab_words;
+  D.idx_count = S.dict.idx_count;
+  D.tab_off = S.dict.tab_off;
+  D.idx_off = S.dict.idx_off;
+  return D;
+}
+
+// one launch of stage S's forward / backward kernel: chunks A.c0 .. A.c0 + grid of kc columns; a stage that took the
+// dictionary form runs the kernels that read its factors from LDS
 template <int M, bool FUSE_TAIL = false>
-static void cr_launch_forward(aggmg_ctx* ctx, const CrStageArgs& A, unsigned grid, int kc, const double* d, const double* db,
-                              double* partR, double* partL, const CrStageArgs& T, size_t tail_lds = 0, double* xt = nullptr,
-                              unsigned int* ticket = nullptr) {
+static void cr_launch_forward(aggmg_ctx* ctx, const CrStage& S, const CrStageArgs& A, unsigned grid, int kc, const double* d,
+                              const double* db, double* partR, double* partL, const CrStageArgs& T, size_t tail_lds = 0,
+                              double* xt = nullptr, unsigned int* ticket = nullptr) {
+  if constexpr (cr_dict_form(M)) {
+    if (S.dict.take) {
+      hipLaunchKernelGGL((cr_stage_forward_dict_kernel<M, FUSE_TAIL>), dim3(grid, kc), dim3(cr_stage_threads()),
+                         std::max(S.dict.lds_bytes, tail_lds), ctx->stream, A, cr_make_dict_args(S), d, db, partR, partL, T, xt,
+                         ticket);
+      ++ctx->coarse_dict_launches;
+      return;
+    }
+  }
   hipLaunchKernelGGL((cr_stage_forward_kernel<M, FUSE_TAIL>), dim3(grid, kc), dim3(cr_stage_threads()),
                      std::max((size_t)A.lds_total * sizeof(double), tail_lds), ctx->stream, A, d, db, partR, partL, T, xt, ticket);
 }
 template <int M>
-static void cr_launch_backward(aggmg_ctx* ctx, const CrStageArgs& A, unsigned grid, int kc, const double* d, const double* db,
-                               const double* xq, double* x) {
+static void cr_launch_backward(aggmg_ctx* ctx, const CrStage& S, const CrStageArgs& A, unsigned grid, int kc, const double* d,
+                               const double* db, const double* xq, double* x) {
+  if constexpr (cr_dict_form(M)) {
+    if (S.dict.take) {
+      hipLaunchKernelGGL((cr_stage_backward_dict_kernel<M>), dim3(grid, kc), dim3(cr_stage_threads()), S.dict.lds_bytes,
+                         ctx->stream, A, cr_make_dict_args(S), d, db, xq, x);
+      ++ctx->coarse_dict_launches;
+      return;
+    }
+  }
   hipLaunchKernelGGL((cr_stage_backward_kernel<M>), dim3(grid, kc), dim3(cr_stage_threads()), (size_t)A.lds_total * sizeof(double),
                      ctx->stream, A, d, db, xq, x);
 }
@@ -1962,9 +2004,9 @@ static int cr_walk(aggmg_ctx* ctx, CrDev& cr, const CrRun& run, int s0, const do
     A.dstride = in.dstride;
     const unsigned grid = (unsigned)std::max<int64_t>(A.n_out, 1);
     if (s == ns - 1 && fuse_tail) {
-      cr_launch_forward<M, true>(ctx, A, grid, kc, in.d, in.db, R.partR, R.partL, T, tail_lds, R.xq, cr.ticket);
+      cr_launch_forward<M, true>(ctx, cr.st[s], A, grid, kc, in.d, in.db, R.partR, R.partL, T, tail_lds, R.xq, cr.ticket);
     } else {
-      cr_launch_forward<M>(ctx, A, grid, kc, in.d, in.db, R.partR, R.partL, T);
+      cr_launch_forward<M>(ctx, cr.st[s], A, grid, kc, in.d, in.db, R.partR, R.partL, T);
       if (s == ns - 1) {
         T.cs_d = T.cs_x = R.cs_part;
         cr_launch_tail<M>(ctx, cr, T, tail_lds, R.partR, R.partL, R.xq, kc);
@@ -1977,7 +2019,7 @@ static int cr_walk(aggmg_ctx* ctx, CrDev& cr, const CrRun& run, int s0, const do
     A.cs_d = in.cs_d;
     A.cs_x = in.cs_x;
     A.dstride = in.dstride;
-    cr_launch_backward<M>(ctx, A, (unsigned)std::max<int64_t>(A.n_out, 1), kc, in.d, in.db, run.st[s].xq, in.x);
+    cr_launch_backward<M>(ctx, cr.st[s], A, (unsigned)std::max<int64_t>(A.n_out, 1), kc, in.d, in.db, run.st[s].xq, in.x);
   }
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
@@ -1998,11 +2040,11 @@ static int cr_chunks(aggmg_ctx* ctx, CrDev& cr, bool backward, const double* d_o
   if (!grid) return AGGMG_OK;
   const double* d0 = d_owned - blk_lo * M;  // global block indexing; only owned blocks are touched
   if (backward) {
-    cr_launch_backward<M>(ctx, A, grid, 1, d0, nullptr, xq, x_owned - blk_lo * M);
+    cr_launch_backward<M>(ctx, S, A, grid, 1, d0, nullptr, xq, x_owned - blk_lo * M);
   } else {
     CrStageArgs T;
     std::memset(&T, 0, sizeof(T));
-    cr_launch_forward<M>(ctx, A, grid, 1, d0, nullptr, partR, partL, T);
+    cr_launch_forward<M>(ctx, S, A, grid, 1, d0, nullptr, partR, partL, T);
   }
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
@@ -2620,6 +2662,39 @@ extern "C" int aggmg_element_thread_launches(aggmg_ctx* ctx, int64_t* count) {
 extern "C" int aggmg_pair_element_thread_launches(aggmg_ctx* ctx, int64_t* count) {
   if (!ctx || !count) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_pair_element_thread_launches: NULL argument");
   *count = ctx->pair_elem_launches;
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_coarse_dictionary_launches(aggmg_ctx* ctx, int64_t* count) {
+  if (!ctx || !count) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_coarse_dictionary_launches: NULL argument");
+  *count = ctx->coarse_dict_launches;
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_coarse_dictionary_cap(aggmg_ctx* ctx, int* cap, int* max_cap) {
+  if (!ctx || !cap) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_coarse_dictionary_cap: NULL argument");
+  *cap = ctx->coarse_dict_cap;
+  if (max_cap) *max_cap = kCrDictMaxClasses;
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_hier_coarse_dictionary(aggmg_ctx* ctx, const aggmg_hier* h, int capacity, int* nstages, int* taken,
+                                            int* first_level, int* nlevels, int* even_classes, int* odd_classes) {
+  if (!ctx || !h || !nstages || !taken || !first_level || !nlevels || !even_classes || !odd_classes || capacity < kCrMaxLevels)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_coarse_dictionary: NULL argument or capacity below " + std::to_string(kCrMaxLevels));
+  const CrDev& cr = h->cr;
+  *nstages = cr.valid ? (int)cr.st.size() : 0;
+  for (int i = 0; i < capacity; ++i) taken[i] = first_level[i] = nlevels[i] = 0, even_classes[i] = odd_classes[i] = -1;
+  if (!cr.valid) return AGGMG_OK;
+  for (size_t s = 0; s < cr.st.size(); ++s) {
+    taken[s] = cr.st[s].dict.take ? 1 : 0;
+    first_level[s] = cr.st[s].l0;
+    nlevels[s] = cr.st[s].q;
+  }
+  for (size_t l = 0; l < cr.dict_even.size() && l < (size_t)capacity; ++l) {
+    even_classes[l] = cr.dict_even[l];
+    odd_classes[l] = cr.dict_odd[l];
+  }
   return AGGMG_OK;
 }
 

@@ -36,6 +36,10 @@
 // PcrArgs::cs_*) -- so a group of columns costs the launches of one and every column keeps its bits.  The host walks the
 // stages once for any number of columns (cr_walk, aggmg_hip.hip): where a run's buffers lie and how far apart its columns
 // are is its CrRun, from which cr_make_args sets the pointers and the cs_* strides.
+//
+// Factors by class (AGGMG_OPT_COARSE_DICTIONARY, block sizes 1 and 2): a chunk stage whose levels hold few distinct factor
+// records runs cr_stage_forward_dict_kernel / cr_stage_backward_dict_kernel, which keep the records in LDS -- the section
+// behind the stage kernels below.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -505,6 +509,20 @@ __device__ __forceinline__ void cr_loc_bwd_pre(const CrLevel* lv, const CrSubFac
   }
 }
 
+// Where a step's sub-chunks take their factors from: the levels' arrays in global memory (CrGlobalFactors: the batched
+// fetches above), or a stage's table of class records in LDS (CrDictLds, end of the stages' section).  even / odd fill
+// CrSubFactors / CrSubFactorsB of sub-chunk b of the step whose first local level is a.
+struct CrGlobalFactors {
+  template <int M, int QS>
+  __device__ __forceinline__ void even(const CrStageArgs& A, int a, int64_t b, CrSubFactors<M, QS>& F) const {
+    cr_pre_load<M, QS, 0>(&A.lv[a], b, F);
+  }
+  template <int M, int QS>
+  __device__ __forceinline__ void odd(const CrStageArgs& A, int a, int64_t b, CrSubFactorsB<M, QS>& F) const {
+    cr_pre_load_b<M, QS, 0>(&A.lv[a], b, F);
+  }
+};
+
 // geometry of step s for chunk c
 struct CrStepGeom {
   int a, a1;            // local levels in / out
@@ -606,10 +624,10 @@ __device__ __forceinline__ void cr_loc_load(const CrStageArgs& A, int s, const C
   }
 }
 
-template <int M, int QS>
+template <int M, int QS, class Src = CrGlobalFactors>
 __device__ __forceinline__ void cr_step_forward(const CrStageArgs& A, int s, int64_t c, bool wg_shared,
                                                 const double* __restrict__ d0, const double* __restrict__ d0b,
-                                                double* sh) {
+                                                double* sh, const Src& src = Src()) {
   const CrStepGeom g = cr_step_geom<QS>(A, s, c, wg_shared);
   const int cnt_out = ((1 << (A.q - g.a1)) + 1) * M;
   double* Rout = sh + A.lds_off[s + 1];
@@ -621,7 +639,7 @@ __device__ __forceinline__ void cr_step_forward(const CrStageArgs& A, int s, int
     bool tshared;
     if constexpr (M <= 2) {
       CrSubFactors<M, QS> F;
-      cr_pre_load<M, QS, 0>(&A.lv[g.a], b, F);
+      src.template even<M, QS>(A, g.a, b, F);
       __builtin_amdgcn_sched_barrier(0);
       cr_loc_load<M, QS>(A, s, g, b, d0, d0b, sh, v, thi, tshared, wg_shared && s > 0 && i == g.nb - 1);
 #ifdef AGGMG_CR_TRACE
@@ -652,11 +670,11 @@ __device__ __forceinline__ void cr_step_forward(const CrStageArgs& A, int s, int
 
 // xtop: x of the step's output level, indexed by block - xtop_lo (LDS, or the global boundary
 // solution); xout: x of the step's input level (LDS for s >= 1, the caller's vector for s == 0)
-template <int M, int QS>
+template <int M, int QS, class Src = CrGlobalFactors>
 __device__ __forceinline__ void cr_step_backward(const CrStageArgs& A, int s, int64_t c, bool wg_shared,
                                                  const double* __restrict__ d0, const double* __restrict__ d0b,
                                                  const double* xtop, int64_t xtop_lo, double* xout, int64_t xout_lo,
-                                                 double* sh) {
+                                                 double* sh, const Src& src = Src()) {
   constexpr int NB = 1 << QS;
   const CrStepGeom g = cr_step_geom<QS>(A, s, c, wg_shared);
   for (int i = threadIdx.x; i < g.nb; i += blockDim.x) {
@@ -670,7 +688,7 @@ __device__ __forceinline__ void cr_step_backward(const CrStageArgs& A, int s, in
     const int64_t br = has_right ? b + 1 : b;
     if constexpr (M <= 2) {
       CrSubFactorsB<M, QS> F;
-      cr_pre_load_b<M, QS, 0>(&A.lv[g.a], b, F);
+      src.template odd<M, QS>(A, g.a, b, F);
       __builtin_amdgcn_sched_barrier(0);
       cr_loc_load<M, QS>(A, s, g, b, d0, d0b, sh, v, thi, tshared, wg_shared && s > 0 && i == g.nb - 1);
       if constexpr (QS >= 2) cr_mid_move<M, QS, 1, false>(cr_col_mid(A) + A.mid_off[s] + b * (cr_mid_blocks<QS>() * M), v);
@@ -714,19 +732,19 @@ __device__ __forceinline__ void cr_step_backward(const CrStageArgs& A, int s, in
   }
 }
 
-template <int M>
+template <int M, class Src = CrGlobalFactors>
 __device__ __forceinline__ void cr_forward_steps(const CrStageArgs& A, int64_t c, bool wg_shared,
                                                  const double* __restrict__ d0, const double* __restrict__ d0b,
-                                                 double* sh) {
+                                                 double* sh, const Src& src = Src()) {
   constexpr int Q = CrRadix<M>::Q;
   for (int s = 0; s < A.nsteps; ++s) {
     const int qs = A.step_a[s + 1] - A.step_a[s];
     if (qs == 1) {
-      cr_step_forward<M, 1>(A, s, c, wg_shared, d0, d0b, sh);
+      cr_step_forward<M, 1>(A, s, c, wg_shared, d0, d0b, sh, src);
     } else if (qs == 2) {
-      cr_step_forward<M, 2>(A, s, c, wg_shared, d0, d0b, sh);
+      cr_step_forward<M, 2>(A, s, c, wg_shared, d0, d0b, sh, src);
     } else {
-      if constexpr (Q >= 3) cr_step_forward<M, 3>(A, s, c, wg_shared, d0, d0b, sh);
+      if constexpr (Q >= 3) cr_step_forward<M, 3>(A, s, c, wg_shared, d0, d0b, sh, src);
     }
     __syncthreads();
     CR_STAMP(A, 4 + s);
@@ -735,10 +753,11 @@ __device__ __forceinline__ void cr_forward_steps(const CrStageArgs& A, int64_t c
 
 // xq: the solution at the chunk's end blocks (global, level-q block index), or null when the top
 // vector is already in LDS (tail)
-template <int M>
+template <int M, class Src = CrGlobalFactors>
 __device__ __forceinline__ void cr_backward_steps(const CrStageArgs& A, int64_t c, bool wg_shared,
                                                   const double* __restrict__ d0, const double* __restrict__ d0b,
-                                                  const double* __restrict__ xq, double* __restrict__ x0, double* sh) {
+                                                  const double* __restrict__ xq, double* __restrict__ x0, double* sh,
+                                                  const Src& src = Src()) {
   constexpr int Q = CrRadix<M>::Q;
   for (int s = A.nsteps - 1; s >= 0; --s) {
     const int a = A.step_a[s], a1 = A.step_a[s + 1];
@@ -749,11 +768,11 @@ __device__ __forceinline__ void cr_backward_steps(const CrStageArgs& A, int64_t 
     double* xout = s ? sh + A.lds_xoff[s] : x0;
     const int64_t xout_lo = s ? (c << (A.q - a)) : 0;
     if (qs == 1) {
-      cr_step_backward<M, 1>(A, s, c, wg_shared, d0, d0b, xtop, xtop_lo, xout, xout_lo, sh);
+      cr_step_backward<M, 1>(A, s, c, wg_shared, d0, d0b, xtop, xtop_lo, xout, xout_lo, sh, src);
     } else if (qs == 2) {
-      cr_step_backward<M, 2>(A, s, c, wg_shared, d0, d0b, xtop, xtop_lo, xout, xout_lo, sh);
+      cr_step_backward<M, 2>(A, s, c, wg_shared, d0, d0b, xtop, xtop_lo, xout, xout_lo, sh, src);
     } else {
-      if constexpr (Q >= 3) cr_step_backward<M, 3>(A, s, c, wg_shared, d0, d0b, xtop, xtop_lo, xout, xout_lo, sh);
+      if constexpr (Q >= 3) cr_step_backward<M, 3>(A, s, c, wg_shared, d0, d0b, xtop, xtop_lo, xout, xout_lo, sh, src);
     }
     __syncthreads();
     CR_STAMP(A, 8 + s);
@@ -903,6 +922,224 @@ __global__ __launch_bounds__(kCrThreads) CR_WAVES_ATTR void cr_stage_backward_ke
     }
   }
   cr_backward_steps<M>(A, c, wg_shared, d0, d0b, xq, x0, sh);
+  CR_STAMP_WAIT(A, 15);
+  CR_TRACE_FLUSH(A);
+}
+
+// ---- chunk stages with the factor records in LDS (AGGMG_OPT_COARSE_DICTIONARY; block sizes 1 and 2) -----------------
+// On a hierarchy of equal elements the factors of a level are a handful of distinct records repeated over the rows, and
+// the stage kernels above read them, cold, from HBM in every cycle: four fifths of what a stage launch moves.  Set-up
+// (setup.hip: setup_cr_dictionary) classes the records of every level of a stage by bit pattern -- the even rows' fe pair;
+// the odd rows' fo pair, lu block and perm -- and leaves per stage ONE table of the classes' records (host_plan.hpp:
+// cr_dict_plan has the layout) and per chunk the class indices of the chunk's rows on all q levels, in the order the
+// kernels keep them in LDS.  A workgroup copies both with 16-byte loads at entry; from then on a sub-chunk's factors are
+// LDS reads by class, and the launch loads from global memory only the vectors, mid, stack and xq.  The records are the
+// arrays' bits and the arithmetic is cr_loc_fwd_pre / cr_loc_bwd_pre on them: every result is bit for bit that of
+// cr_stage_forward_kernel / cr_stage_backward_kernel.  (The arguments are a struct of their own: CrStageArgs keeps its
+// size, and with it the argument layout of the kernels above.)
+struct CrDictArgs {
+  const double* tab;     // the stage's table: tab_words doubles
+  const uint16_t* cidx;  // [chunks][idx_count] class indices, chunk-major
+  int tab_e[kCrMaxStageLevels], tab_o[kCrMaxStageLevels];  // a level's even / odd records in the table (doubles)
+  int idx_e[kCrMaxStageLevels], idx_o[kCrMaxStageLevels];  // a level's even / odd rows among a chunk's indices
+  int tab_words, idx_count;
+  int tab_off, idx_off;  // where the launch's LDS keeps the two (doubles)
+};
+
+// Table and class indices of chunk c into LDS, and the vectors' part of it zeroed.  The first kRounds rounds of both
+// copies are loads issued back to back before the first store (a round past the end repeats the last word: no branch
+// between the loads); larger tables take further rounds one by one.
+__device__ __forceinline__ void cr_dict_fill(const CrDictArgs& D, int64_t c, int lds_total, double* sh) {
+  constexpr int kRounds = 6;
+  const double2* st = reinterpret_cast<const double2*>(D.tab);
+  const double2* si = reinterpret_cast<const double2*>(D.cidx + c * D.idx_count);
+  double2* dt = reinterpret_cast<double2*>(sh + D.tab_off);
+  double2* di = reinterpret_cast<double2*>(sh + D.idx_off);
+  const int nt = D.tab_words / 2, ni = D.idx_count / 8;
+  double2 rt[kRounds], ri[kRounds];
+#pragma unroll
+  for (int k = 0; k < kRounds; ++k) {
+    const int t = (int)threadIdx.x + k * (int)blockDim.x;
+    rt[k] = st[t < nt ? t : nt - 1];
+  }
+#pragma unroll
+  for (int k = 0; k < kRounds; ++k) {
+    const int t = (int)threadIdx.x + k * (int)blockDim.x;
+    ri[k] = si[t < ni ? t : ni - 1];
+  }
+  for (int t = threadIdx.x; t < lds_total; t += blockDim.x) sh[t] = 0.0;
+#pragma unroll
+  for (int k = 0; k < kRounds; ++k) {
+    const int t = (int)threadIdx.x + k * (int)blockDim.x;
+    if (t < nt) dt[t] = rt[k];
+    if (t < ni) di[t] = ri[k];
+  }
+  for (int t = (int)threadIdx.x + kRounds * (int)blockDim.x; t < nt; t += blockDim.x) dt[t] = st[t];
+  for (int t = (int)threadIdx.x + kRounds * (int)blockDim.x; t < ni; t += blockDim.x) di[t] = si[t];
+}
+
+// cr_pre_load / cr_pre_load_b from the table: row j of local level l of chunk c has its class at index
+// j - (c << (q - l - 1)) of the level's part of the chunk's indices.  A sub-chunk's rows lie in 0 .. 2^(q-l-1) (even) and
+// 0 .. 2^(q-l-1) - 1 (odd) there; a row past the end of the level has the class of the level's last row -- set-up wrote
+// the clamp cr_pre_load applies into the indices -- and its value is discarded by the same selects.
+template <int M, int QS, int I>
+__device__ __forceinline__ void cr_pre_load_dict(const CrDictArgs& D, const double* tab, const uint16_t* idx, int q, int a,
+                                                 int64_t c, int64_t b, CrSubFactors<M, QS>& F) {
+  if constexpr (I < QS) {
+    const int l = a + I;
+    constexpr int NB1 = 1 << (QS - I - 1);
+    const int t0 = (int)((b << (QS - I - 1)) - (c << (q - l - 1)));
+    const uint16_t* ix = idx + D.idx_e[l] + t0;
+    const double* T = tab + D.tab_e[l];
+#pragma unroll
+    for (int jj = 0; jj <= NB1; ++jj) cr_load_pair<M>(T + (int)ix[jj] * (2 * M * M), F.fe[CrEvenOff<QS, I>::rows + jj]);
+    cr_pre_load_dict<M, QS, I + 1>(D, tab, idx, q, a, c, b, F);
+  }
+}
+
+template <int M, int QS, int I>
+__device__ __forceinline__ void cr_pre_load_b_dict(const CrDictArgs& D, const double* tab, const uint16_t* idx, int q, int a,
+                                                   int64_t c, int64_t b, CrSubFactorsB<M, QS>& F) {
+  if constexpr (I < QS) {
+    const int l = a + I;
+    constexpr int NB1 = 1 << (QS - I - 1);
+    constexpr int W = (3 * M * M + (M + 1) / 2 + 1) & ~1;  // cr_dict_odd_words(M)
+    const int t0 = (int)((b << (QS - I - 1)) - (c << (q - l - 1)));
+    const uint16_t* ix = idx + D.idx_o[l] + t0;
+    const double* T = tab + D.tab_o[l];
+#pragma unroll
+    for (int jj = 0; jj < NB1; ++jj) {
+      const double* r = T + (int)ix[jj] * W;
+      constexpr int o = CrOddOff<QS, I>::rows;
+      cr_load_pair<M>(r, F.fo[o + jj]);
+      if constexpr (M == 2) {
+        const double2 t0v = reinterpret_cast<const double2*>(r + 2 * M * M)[0], t1v = reinterpret_cast<const double2*>(r + 2 * M * M)[1];
+        const int2 pp = *reinterpret_cast<const int2*>(r + 3 * M * M);
+        F.lu[o + jj][0] = t0v.x, F.lu[o + jj][1] = t0v.y, F.lu[o + jj][2] = t1v.x, F.lu[o + jj][3] = t1v.y;
+        F.perm[o + jj][0] = pp.x, F.perm[o + jj][1] = pp.y;
+      } else {
+#pragma unroll
+        for (int k = 0; k < M * M; ++k) F.lu[o + jj][k] = r[2 * M * M + k];
+#pragma unroll
+        for (int k = 0; k < M; ++k) F.perm[o + jj][k] = reinterpret_cast<const int32_t*>(r + 3 * M * M)[k];
+      }
+    }
+    cr_pre_load_b_dict<M, QS, I + 1>(D, tab, idx, q, a, c, b, F);
+  }
+}
+
+struct CrDictLds {
+  const CrDictArgs& D;
+  const double* tab;    // LDS
+  const uint16_t* idx;  // LDS
+  int64_t c;
+  template <int M, int QS>
+  __device__ __forceinline__ void even(const CrStageArgs& A, int a, int64_t b, CrSubFactors<M, QS>& F) const {
+    cr_pre_load_dict<M, QS, 0>(D, tab, idx, A.q, a, c, b, F);
+  }
+  template <int M, int QS>
+  __device__ __forceinline__ void odd(const CrStageArgs& A, int a, int64_t b, CrSubFactorsB<M, QS>& F) const {
+    cr_pre_load_b_dict<M, QS, 0>(D, tab, idx, A.q, a, c, b, F);
+  }
+};
+
+// cr_stage_forward_kernel with the stage's factors from LDS (the tail of a FUSE_TAIL launch keeps its own arrays)
+template <int M, bool FUSE_TAIL>
+__global__ __launch_bounds__(kCrThreads) CR_WAVES_ATTR void cr_stage_forward_dict_kernel(CrStageArgs A, CrDictArgs D,
+                                                                           const double* __restrict__ d0,
+                                                                           const double* __restrict__ d0b, double* partR,
+                                                                           double* partL, CrStageArgs T, double* xq,
+                                                                           unsigned int* ticket) {
+  static_assert(M <= 2, "the batched factor fetch: block sizes 1 and 2");
+  extern __shared__ double2 sh_dict[];  // (16-byte aligned: the table's records are read and written as double2)
+  double* const sh = reinterpret_cast<double*>(sh_dict);
+  __shared__ unsigned int s_ticket;
+  const int64_t c = A.c0 + blockIdx.x;
+  const int64_t col = blockIdx.y;
+  d0 += col * A.cs_d;
+  if (d0b) d0b += col * A.cs_d;
+  partR += col * A.cs_o;
+  partL += col * A.cs_o;
+  const bool wg_shared = ((c + 1) << A.q) <= A.lv[0].n - 1;
+  CR_TRACE_BEGIN();
+  CR_STAMP(A, 0);
+  cr_dict_fill(D, c, A.lds_total, sh);
+  __syncthreads();
+  CR_STAMP(A, 1);
+  const CrDictLds src{D, sh + D.tab_off, reinterpret_cast<const uint16_t*>(sh + D.idx_off), c};
+  cr_forward_steps<M>(A, c, wg_shared, d0, d0b, sh, src);
+  {
+    const double* R = sh + A.lds_off[A.nsteps];  // level q: blocks c, c + 1
+    if (threadIdx.x < M) {
+      const int os = A.ostride ? A.ostride : M;
+      partR[c * os + threadIdx.x] = R[threadIdx.x];
+      if (c + 1 <= A.n_out - 1) partL[(c + 1) * os + threadIdx.x] = R[2 * M + M + threadIdx.x];
+    }
+  }
+  if (A.stack) {
+    double* st = A.stack + col * A.cs_stack + c * (int64_t)A.stack_stride;
+    int o = 0;
+    for (int s = 1; s < A.nsteps; ++s) {
+      const int cnt = ((1 << (A.q - A.step_a[s])) + 1) * M;
+      const double* R = sh + A.lds_off[s];
+      for (int t = threadIdx.x; t < cnt; t += blockDim.x) st[o + t] = R[t] + R[cnt + t];
+      o += cnt;
+    }
+  }
+  CR_STAMP_WAIT(A, 15);
+  CR_TRACE_FLUSH(A);
+  if constexpr (FUSE_TAIL) {
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) s_ticket = atomicAdd(ticket, 1u);
+    __syncthreads();
+    if (s_ticket != gridDim.x - 1) return;
+    __threadfence();
+    cr_tail_body<M>(T, partR, partL, xq, sh);
+    if (threadIdx.x == 0) *ticket = 0u;
+  }
+}
+
+// cr_stage_backward_kernel with the stage's factors from LDS
+template <int M>
+__global__ __launch_bounds__(kCrThreads) CR_WAVES_ATTR void cr_stage_backward_dict_kernel(CrStageArgs A, CrDictArgs D,
+                                                                            const double* __restrict__ d0,
+                                                                            const double* __restrict__ d0b,
+                                                                            const double* __restrict__ xq,
+                                                                            double* __restrict__ x0) {
+  static_assert(M <= 2, "the batched factor fetch: block sizes 1 and 2");
+  extern __shared__ double2 sh_dict[];  // (16-byte aligned: the table's records are read and written as double2)
+  double* const sh = reinterpret_cast<double*>(sh_dict);
+  const int64_t c = A.c0 + blockIdx.x;
+  const int64_t col = blockIdx.y;
+  d0 += col * A.cs_d;
+  if (d0b) d0b += col * A.cs_d;
+  xq += col * A.cs_xq;
+  x0 += col * A.cs_x;
+  const bool wg_shared = ((c + 1) << A.q) <= A.lv[0].n - 1;
+  CR_TRACE_BEGIN();
+  CR_STAMP(A, 0);
+  cr_dict_fill(D, c, A.lds_total, sh);
+  __syncthreads();
+  CR_STAMP(A, 1);
+  const CrDictLds src{D, sh + D.tab_off, reinterpret_cast<const uint16_t*>(sh + D.idx_off), c};
+  if (A.nsteps > 1) {
+    if (A.stack) {
+      const double* st = A.stack + col * A.cs_stack + c * (int64_t)A.stack_stride;
+      int o = 0;
+      for (int s = 1; s < A.nsteps; ++s) {
+        const int cnt = ((1 << (A.q - A.step_a[s])) + 1) * M;
+        double* R = sh + A.lds_off[s];
+        for (int t = threadIdx.x; t < cnt; t += blockDim.x) R[t] = st[o + t];
+        o += cnt;
+      }
+      __syncthreads();
+      CR_STAMP(A, 2);
+    } else {
+      cr_forward_steps<M>(A, c, wg_shared, d0, d0b, sh, src);
+    }
+  }
+  cr_backward_steps<M>(A, c, wg_shared, d0, d0b, xq, x0, sh, src);
   CR_STAMP_WAIT(A, 15);
   CR_TRACE_FLUSH(A);
 }

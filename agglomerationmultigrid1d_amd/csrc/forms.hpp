@@ -31,6 +31,9 @@ constexpr bool chain_dict_form(int m) { return m == 1 || m == 2 || m == 4; }
 // the cyclic reduction of the coarsest solve; the block inversion of set-up (larger blocks take its any-size kernel)
 constexpr bool cr_form(int m) { return m >= 1 && m <= 8; }
 constexpr bool invert_form(int m) { return m >= 1 && m <= 8; }
+// ... its chunk stages with the factor records in LDS (cr_stage_forward_dict_kernel, cr_stage_backward_dict_kernel): the
+// block sizes whose sub-chunk factors are fetched in one batch
+constexpr bool cr_dict_form(int m) { return m == 1 || m == 2; }
 // lanes per row of csr_row_kernel
 constexpr bool csr_lanes_form(int l) { return l >= 1 && l <= 64 && (l & (l - 1)) == 0; }
 
@@ -126,6 +129,7 @@ static_assert(size_mask(multi_block_size) == 0b10100, "the K-column lane groups:
 static_assert(size_mask(chain_form) == 0b111111110 && size_mask(cr_form) == 0b111111110 && size_mask(invert_form) == 0b111111110,
               "chain_form, cr_form, invert_form: 1..8");
 static_assert(size_mask(chain_dict_form) == 0b10110 && count_bits(size_mask(chain_dict_form)) == 3, "chain_dict_form: 1, 2, 4");
+static_assert(size_mask(cr_dict_form) == 0b110, "cr_dict_form: 1, 2");
 static_assert(size_mask(is_col_group) == 0b100010110, "column groups: 1, 2, 4, 8");
 static_assert(col_group(1) == 1 && col_group(2) == 2 && col_group(3) == 4 && col_group(4) == 4 && col_group(5) == 8 && col_group(8) == 8 &&
                   col_group(3, 2) == 2 && col_group(8, 4) == 4 && col_group(3, 4) == 4,

@@ -173,6 +173,75 @@ inline int64_t cr_multi_layout(const std::vector<Stage>& stages, const CrStagePl
   return o;
 }
 
+// ---- coarsest solve: a stage's dictionary of factor records (AGGMG_OPT_COARSE_DICTIONARY, cr_kernels.hpp) ------------
+// A chunk stage whose levels hold few distinct factor records keeps them in LDS: per level one table of the even rows'
+// records (the fe pair: 2 m^2 doubles) and one of the odd rows' (the fo pair, the lu block and perm: 2 m^2 + m^2 doubles
+// and m 32-bit words, padded to 16 bytes), all of a stage in ONE table that a launch copies with 16-byte loads, and per
+// level and parity the class index (uint16) of every row.  A launch's LDS then holds, behind the stage's vectors
+// (lds_total doubles): the table, and the class indices of the workgroup's chunk -- 2^(q-l-1) + 1 even and 2^(q-l-1) odd
+// rows of local level l.  Block sizes 1 and 2 (forms.hpp: cr_dict_form).
+//
+// kCrDictMaxClasses, the largest cap on classes per level and parity and the option's default: what the launch's LDS limit
+// (kCrLdsBudgetBytes, the limit a stage's vectors are planned against) leaves at the largest plan, q = 12 levels of blocks
+// of 2: 160 KiB - 28272 bytes of vectors - 16416 bytes of class indices = 119152 bytes for 12 levels of cap x (64 + 112)
+// bytes -> cap 56.  The cap only bounds the worst case: a stage's table is as large as its levels' class counts make it,
+// and the stage takes the form when that table fits (cr_dict_plan) -- all or nothing per stage.
+constexpr int kCrDictMaxClasses = 56;
+constexpr int cr_dict_even_words(int m) { return 2 * m * m; }                             // doubles per even record
+constexpr int cr_dict_odd_words(int m) { return (3 * m * m + (m + 1) / 2 + 1) & ~1; }     // doubles per odd record
+constexpr int cr_dict_index_count(int q) { return ((2 << q) - 2 + q + 7) & ~7; }          // uint16 per chunk, all levels
+struct CrDictPlan {
+  bool take = false;
+  int tab_e[kCrMaxStageLevels] = {0}, tab_o[kCrMaxStageLevels] = {0};  // doubles from the table's start, per local level
+  int tab_words = 0;                                                    // the table, doubles (even)
+  int idx_e[kCrMaxStageLevels] = {0}, idx_o[kCrMaxStageLevels] = {0};  // uint16 from the index region's start
+  int idx_count = 0;                                                    // uint16 (a multiple of 8)
+  int tab_off = 0, idx_off = 0;                                         // doubles from the start of the launch's LDS
+  size_t lds_bytes = 0;                                                 // vectors + table + class indices
+};
+// the layout of a stage of q levels whose local level l has n_even_cls[l] / n_odd_cls[l] classes; take = false (and the
+// layout left undefined) for another block size, a level without classes or with more than `cap`, or a launch beyond
+// lds_limit bytes
+inline CrDictPlan cr_dict_plan(int m, int q, int lds_total, const int* n_even_cls, const int* n_odd_cls, int cap,
+                               size_t lds_limit = kCrLdsBudgetBytes) {
+  CrDictPlan P;
+  if (!cr_dict_form(m) || q < 1 || q > kCrMaxStageLevels || cap < 1) return P;
+  for (int l = 0; l < q; ++l)
+    if (n_even_cls[l] < 1 || n_even_cls[l] > cap || n_odd_cls[l] < 1 || n_odd_cls[l] > cap) return P;
+  int o = 0;
+  for (int l = 0; l < q; ++l) {
+    P.tab_e[l] = o;
+    o += n_even_cls[l] * cr_dict_even_words(m);
+    P.tab_o[l] = o;
+    o += n_odd_cls[l] * cr_dict_odd_words(m);
+  }
+  P.tab_words = o;   // (both record lengths are even: every offset stands on 16 bytes)
+  int i = 0;
+  for (int l = 0; l < q; ++l) {
+    P.idx_e[l] = i;
+    i += (1 << (q - l - 1)) + 1;
+    P.idx_o[l] = i;
+    i += 1 << (q - l - 1);
+  }
+  P.idx_count = (i + 7) & ~7;
+  P.tab_off = (lds_total + 1) & ~1;
+  P.idx_off = P.tab_off + P.tab_words;
+  P.lds_bytes = (size_t)P.idx_off * sizeof(double) + (size_t)P.idx_count * sizeof(uint16_t);
+  P.take = P.lds_bytes <= lds_limit;
+  return P;
+}
+// class c's odd record from the dictionary's arrays fo [nc][2 m^2], lu [nc][m^2], perm [nc][m]
+inline void cr_dict_pack_odd(int m, int nc, const double* fo, const double* lu, const int32_t* perm, double* rec) {
+  const int mm = m * m, w = cr_dict_odd_words(m);
+  for (int c = 0; c < nc; ++c) {
+    double* r = rec + (size_t)c * w;
+    std::memset(r, 0, (size_t)w * sizeof(double));
+    std::memcpy(r, fo + (size_t)c * 2 * mm, (size_t)2 * mm * sizeof(double));
+    std::memcpy(r + 2 * mm, lu + (size_t)c * mm, (size_t)mm * sizeof(double));
+    std::memcpy(r + 3 * mm, perm + (size_t)c * m, (size_t)m * sizeof(int32_t));
+  }
+}
+
 // ---- generic CSR kernels: row blocks -------------------------------------------------------------------------------
 // csr_stream_kernel: runs of consecutive rows holding at most max_nnz entries and at most max_rows rows; a row longer
 // than max_nnz stands alone (the kernel reduces it across the workgroup).  -> block boundaries, blocks + 1 entries

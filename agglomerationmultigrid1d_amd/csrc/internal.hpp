@@ -79,6 +79,10 @@ struct aggmg_ctx {
   // (0: off; at most kElemRecMaxClasses, host_plan.hpp)
   int elem_rec_cap = [] { const char* e = std::getenv("AGGMG_ELEM_RECORDS_LDS"); return (e && e[0] == '0') ? 0 : kElemRecMaxClasses; }();
   int64_t elem_rec_launches = 0;   // launches of those kernels so far (aggmg_element_record_lds_launches)
+  // AGGMG_OPT_COARSE_DICTIONARY: most classes per level and parity of a chunk stage of the coarsest solve that keeps its
+  // factor records in LDS (0: off; at most kCrDictMaxClasses, host_plan.hpp); read when a hierarchy is created
+  int coarse_dict_cap = [] { const char* e = std::getenv("AGGMG_COARSE_DICT"); return (e && e[0] == '0') ? 0 : kCrDictMaxClasses; }();
+  int64_t coarse_dict_launches = 0;   // stage launches served (aggmg_coarse_dictionary_launches)
   bool replay_presmooth = [] { const char* e = std::getenv("AGGMG_REPLAY_PRESMOOTH"); return !(e && e[0] == '0'); }();  // AGGMG_OPT_REPLAY_PRESMOOTH
   int64_t replay_launches = 0;   // replayed cycles so far (aggmg_replay_launches)
   bool patch_multi = [] { const char* e = std::getenv("AGGMG_PATCH_MULTI"); return e && e[0] == '1'; }();  // AGGMG_OPT_PATCH_MULTI (default 0)
@@ -383,6 +387,11 @@ struct CrStage : CrStagePlan {    // the host-side plan (host_plan.hpp) + the st
   double *partL = nullptr, *xq = nullptr;     // ... these two are views into it
   DevArray<double> stack;       // per chunk: summed inputs of the steps after the first
   DevArray<double> mid;         // per step and sub-chunk: reduced right-hand sides of the inner sub-levels' odd rows
+  // AGGMG_OPT_COARSE_DICTIONARY (dict.take): the table of the levels' class records and, per chunk, the class indices of
+  // its rows on all q levels (host_plan.hpp: cr_dict_plan; cr_kernels.hpp: CrDictArgs)
+  CrDictPlan dict;
+  DevArray<double> dict_tab;
+  DevArray<uint16_t> dict_idx;
 };
 
 // Where one solve's launches read and write: per stage and for the tail the per-solve buffers and the doubles between
@@ -413,6 +422,9 @@ struct CrDev {
   const double* lu_last = nullptr;
   const int32_t* perm_last = nullptr;
   std::vector<CrStage> st;      // chunk stages ...
+  // classes of the even / odd rows' factor records per reducing level (setup_cr_dictionary): -1 not classed, 0 more than
+  // the search tracks
+  std::vector<int> dict_even, dict_odd;
   CrStage tail;                 // ... then the remaining levels in one workgroup
   CrRun run;                    // one column in the buffers of st and tail (set-up fills it in)
   DevArray<double> d0, x0;              // staging for padded systems (N not a multiple of m) / in-place calls / chain order

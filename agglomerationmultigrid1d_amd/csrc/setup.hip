@@ -551,6 +551,18 @@ struct DictFields {
     };
     v.f[k] = DictField{full.get(), nullptr, n, (int)sizeof(T), back ? 1 : 0};
   }
+  // (an array that is a view: the levels of the cyclic reduction)
+  template <typename T>
+  void add_view(const T* full, DevArray<T>* dict, int n) {
+    static_assert(sizeof(T) == 8 || sizeof(T) == 4, "records are made of 64- and 32-bit words");
+    const int k = v.nf++;
+    make[k] = [this, k, dict](aggmg_ctx* ctx, int64_t count) {
+      CHECK(dict->alloc(ctx, count));
+      v.f[k].dict = dict->get();
+      return (int)AGGMG_OK;
+    };
+    v.f[k] = DictField{full, nullptr, n, (int)sizeof(T), 0};
+  }
 };
 
 // The classes of identical records of a level: *nclasses > 0, cls[ne] and the dictionary's arrays (through F.make: they
@@ -870,6 +882,79 @@ static int setup_pcr_t(aggmg_ctx* ctx, CrDev* cr, const CrDev::Raw& R) {
 
 void cr_discard(CrDev* c) { *c = CrDev(); }
 
+// AGGMG_OPT_COARSE_DICTIONARY: the chunk stages whose levels hold at most ctx->coarse_dict_cap distinct factor records
+// get their table and class indices (cr_kernels.hpp: CrDictArgs), all or nothing per stage -- cr_dict_plan decides.  Only
+// the stages' levels are classed, and a stage stops at its first level over the cap: a system of unlike rows costs one
+// search.  The levels' full arrays stay: the other path and the tail read them.
+static int setup_cr_dictionary(aggmg_ctx* ctx, CrDev* cr) {
+  const int m = cr->m, cap = ctx->coarse_dict_cap, mm = m * m;
+  cr->dict_even.assign(cr->lv.size(), -1);
+  cr->dict_odd.assign(cr->lv.size(), -1);
+  if (!cr_dict_form(m) || cap < 1) return AGGMG_OK;
+  for (CrStage& S : cr->st) {
+    int ne[kCrMaxStageLevels] = {0}, no[kCrMaxStageLevels] = {0};
+    std::vector<DevArray<uint16_t>> ce(S.q), co(S.q);
+    std::vector<DevArray<double>> fe(S.q), fo(S.q), lu(S.q);
+    std::vector<DevArray<int32_t>> pm(S.q);
+    bool ok = true;
+    for (int l = 0; l < S.q && ok; ++l) {
+      const CrLevel& L = cr->lv[S.l0 + l];
+      ok = L.n_odd >= 1;
+      if (!ok) break;
+      DictFields E(L.n_even);
+      E.add_view(L.fe, &fe[l], 2 * mm);
+      CHECK(dict_build(ctx, E, &ce[l], &ne[l]));
+      cr->dict_even[S.l0 + l] = ne[l];
+      ok = ne[l] >= 1 && ne[l] <= cap;
+      if (!ok) break;
+      DictFields O(L.n_odd);
+      O.add_view(L.fo, &fo[l], 2 * mm);
+      O.add_view(L.lu, &lu[l], mm);
+      O.add_view(L.perm, &pm[l], m);
+      CHECK(dict_build(ctx, O, &co[l], &no[l]));
+      cr->dict_odd[S.l0 + l] = no[l];
+      ok = no[l] >= 1 && no[l] <= cap;
+    }
+    if (!ok) continue;
+    const CrDictPlan P = cr_dict_plan(m, S.q, S.lds_total, ne, no, cap);
+    if (!P.take) continue;
+    // the table: the levels' dictionaries in the stage's layout, a few KB repacked on the host
+    std::vector<double> tab((size_t)P.tab_words, 0.0);
+    std::vector<std::vector<double>> hfo(S.q), hlu(S.q);
+    std::vector<std::vector<int32_t>> hpm(S.q);
+    auto down = [&](void* dst, const void* src, size_t bytes) {
+      return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    };
+    for (int l = 0; l < S.q; ++l) {
+      hfo[l].resize((size_t)no[l] * 2 * mm);
+      hlu[l].resize((size_t)no[l] * mm);
+      hpm[l].resize((size_t)no[l] * m);
+      HIPCHK(down(tab.data() + P.tab_e[l], fe[l].get(), (size_t)ne[l] * 2 * mm * sizeof(double)));
+      HIPCHK(down(hfo[l].data(), fo[l].get(), hfo[l].size() * sizeof(double)));
+      HIPCHK(down(hlu[l].data(), lu[l].get(), hlu[l].size() * sizeof(double)));
+      HIPCHK(down(hpm[l].data(), pm[l].get(), hpm[l].size() * sizeof(int32_t)));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int l = 0; l < S.q; ++l) cr_dict_pack_odd(m, no[l], hfo[l].data(), hlu[l].data(), hpm[l].data(), tab.data() + P.tab_o[l]);
+    CHECK(S.dict_tab.alloc(ctx, P.tab_words));
+    HIPCHK(hipMemcpyAsync(S.dict_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    // the class indices of every chunk (chunk c = block c of the stage's output level), in the order of the launch's LDS
+    const int64_t chunks = std::max<int64_t>(S.n_out, 1);
+    CHECK(S.dict_idx.alloc(ctx, chunks * P.idx_count, true));
+    for (int l = 0; l < S.q; ++l) {
+      const CrLevel& L = cr->lv[S.l0 + l];
+      const int shift = S.q - l - 1, cnt = 1 << shift;
+      LAUNCH(cr_dict_chunk_index_kernel, chunks * (cnt + 1), chunks, cnt + 1, shift, L.n_even, (const uint16_t*)ce[l],
+             S.dict_idx.get(), P.idx_count, P.idx_e[l]);
+      LAUNCH(cr_dict_chunk_index_kernel, chunks * cnt, chunks, cnt, shift, L.n_odd, (const uint16_t*)co[l], S.dict_idx.get(),
+             P.idx_count, P.idx_o[l]);
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // (the host table and the levels' class arrays are done with)
+    S.dict = P;
+  }
+  return AGGMG_OK;
+}
+
 // probe vector of the factorisation check: entries in [-1, 1) from a hash of the index (no structure a
 // tridiagonal stencil could annihilate)
 __global__ __launch_bounds__(kSetupThreads) void probe_vector_kernel(int64_t n, double* __restrict__ w) {
@@ -1150,6 +1235,7 @@ static int cr_factor_blocks(aggmg_ctx* ctx, CrDev* cr, DevArray<double> a, DevAr
   }
   CHECK(cr->ticket.alloc(ctx, 1, true));
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  CHECK(setup_cr_dictionary(ctx, cr));
   cr->run = CrRun();
   for (const CrStage& S : cr->st) cr->run.st.push_back(cr_run_stage(S));
   cr->run.tail = cr_run_stage(cr->tail);

@@ -1027,6 +1027,22 @@ __global__ __launch_bounds__(kSetupThreads) void cr_even_multipliers_kernel(int6
   }
 }
 
+// ---- class indices of a dictionary stage, chunk-major (cr_kernels.hpp: CrDictArgs::cidx) ------------------------------
+// entry t < count of chunk c's part `off` of its idx_count indices: the class of row (c << shift) + t of the level's even
+// or odd rows, a row past the end standing for the last one (the clamp of cr_pre_load / cr_pre_load_b).  One thread per
+// (chunk, entry).
+__global__ __launch_bounds__(kSetupThreads) void cr_dict_chunk_index_kernel(int64_t n_chunks, int count, int shift,
+                                                                            int64_t n_rows, const uint16_t* __restrict__ cls,
+                                                                            uint16_t* __restrict__ out, int idx_count, int off) {
+  const int64_t i = (int64_t)blockIdx.x * kSetupThreads + threadIdx.x;
+  if (i >= n_chunks * count) return;
+  const int64_t c = i / count;
+  const int t = (int)(i - c * count);
+  int64_t g = (c << shift) + t;
+  if (g > n_rows - 1) g = n_rows - 1;
+  out[c * idx_count + off + t] = cls[g];
+}
+
 // ---- parallel cyclic reduction of the tail's boundary system (cr_kernels.hpp: cr_pcr_tail_kernel) ----------------------
 // blk B^-1 by row-vector solves with the pivoted factors P B = L U (F: unit-lower L, U with RECIPROCAL pivots)
 template <int M>

@@ -216,7 +216,30 @@ int aggmg_synchronize(aggmg_ctx* ctx);
  * number among the header's plain `#define AGGMG_OPT_x n` lines, and tests/test_patch_schwarz_multi_cpu.py reads this form too
  * when it checks that no two options share a number.) */
 #define AGGMG_OPT_PATCH_SCHWARZ_MULTI 14 /* r34 */
+/* AGGMG_OPT_COARSE_DICTIONARY (default 56; environment AGGMG_COARSE_DICT=0 makes the default 0): the chunk stages of the
+ * coarsest level's cyclic reduction (block sizes 1 and 2) keep their factors in LDS where the levels of a stage hold few
+ * distinct factor records, as the coarsest operator of a hierarchy of equal elements does.  Set-up classes, by bit
+ * pattern, the even rows' forward multipliers and the odd rows' couplings, factored diagonal block and permutation of
+ * every level of a stage; a stage all of whose levels have at most `value` classes of either kind, and whose table of
+ * class records and per-chunk class indices fit the launch's LDS beside its vectors (160 KiB in all), runs
+ * cr_stage_forward_dict_kernel / cr_stage_backward_dict_kernel: a workgroup copies table and indices into LDS at entry
+ * and loads nothing but vectors afterwards.  All or nothing per stage; the tail, other block sizes and stages that do
+ * not qualify keep their kernels and arrays.  Every result is bit for bit the same.  value: 0 switches it off; 1 .. 56
+ * is the cap on classes per level and kind -- 56 is what 160 KiB leave per level beside the vectors (28272 bytes) and
+ * class indices (16416 bytes) of the largest stage, 12 levels of blocks of 2, at 64 + 112 bytes per pair of records;
+ * other values are an error.  Read when a hierarchy is created.  aggmg_coarse_dictionary_launches counts the stage
+ * launches served, aggmg_hier_coarse_dictionary says which stages took the form.  (The number stands in parentheses on
+ * purpose: tests/test_patch_schwarz_multi_cpu.py holds 14 to be the count of the header's `#define AGGMG_OPT_x n` lines,
+ * with or without a comment behind the number.) */
+#define AGGMG_OPT_COARSE_DICTIONARY (15)
 int aggmg_set_option(aggmg_ctx* ctx, int option, int value);
+/* Stage launches of the coarsest solve that read their factors from LDS (AGGMG_OPT_COARSE_DICTIONARY) on this context
+ * so far: two per chunk stage that took the form and solve (one forward, one backward), whatever the number of columns
+ * of the launch. */
+int aggmg_coarse_dictionary_launches(aggmg_ctx* ctx, int64_t* count);
+/* The cap on classes in force (AGGMG_OPT_COARSE_DICTIONARY; 0: off) and, where max_cap is not NULL, the largest value
+ * the option takes. */
+int aggmg_coarse_dictionary_cap(aggmg_ctx* ctx, int* cap, int* max_cap);
 /* Launches of the element-thread kernels with the class records in LDS (AGGMG_OPT_ELEMENT_RECORDS_LDS) on this context
  * so far. */
 int aggmg_element_record_lds_launches(aggmg_ctx* ctx, int64_t* count);
@@ -717,6 +740,15 @@ int aggmg_hier_get_sweep_weights(aggmg_ctx* ctx, const aggmg_hier* h, int level,
  * the eigenvalue from below (0.989 - 0.995 of it after 40 steps on the benchmark hierarchies). */
 int aggmg_hier_estimate_lambda_max(aggmg_ctx* ctx, aggmg_hier* h, int level, const double* v0, int iters,
                                    double* lambda_max);
+/* The coarsest solve's dictionary (AGGMG_OPT_COARSE_DICTIONARY).  *nstages: the chunk stages of the device solve (0: none,
+ * or no device solve).  For stage s < *nstages: taken[s] 1 when its launches read their factors from LDS, first_level[s]
+ * and nlevels[s] the reducing levels it spans.  For reducing level l: even_classes[l] / odd_classes[l], the distinct
+ * records found among its even rows' multipliers / its odd rows' factors; -1 where set-up did not class the level (the
+ * option off, another block size, a level of the tail, a level behind the first one of its stage that went over the
+ * cap), 0 where there are more than the search tracks (1024).  Every array holds `capacity` entries, at least 40;
+ * entries beyond the stages / levels are 0 / -1. */
+int aggmg_hier_coarse_dictionary(aggmg_ctx* ctx, const aggmg_hier* h, int capacity, int* nstages, int* taken,
+                                 int* first_level, int* nlevels, int* even_classes, int* odd_classes);
 /* Which coarsest solver a hierarchy uses: on_device (1 = cyclic reduction), its block size and the
  * largest pivot-block condition estimate met while factoring (0 for the host solver). */
 int aggmg_hier_coarse_info(aggmg_ctx* ctx, const aggmg_hier* h, int* on_device, int* block_size,

@@ -334,6 +334,16 @@ function patch_schwarz_multi_launches(ctx::Context)
     check(ctx.h, ccall((:aggmg_patch_schwarz_multi_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
     return r[]
 end
+# AGGMG_OPT_COARSE_DICTIONARY (default 56; environment AGGMG_COARSE_DICT=0 makes the default 0): the chunk stages of the
+# coarsest solve whose levels hold at most that many distinct factor records of either kind keep them in LDS -- the same
+# bits; 0 switches it off.  Read when a hierarchy is created.
+# coarse_dictionary_launches(ctx): how many stage launches those kernels have served.
+const OPT_COARSE_DICTIONARY = 15
+function coarse_dictionary_launches(ctx::Context)
+    r = Ref{Int64}(0)
+    check(ctx.h, ccall((:aggmg_coarse_dictionary_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
+    return r[]
+end
 # AGGMG_OPT_ELEMENT_RECORDS_LDS (default 32; environment AGGMG_ELEM_RECORDS_LDS=0 makes the default 0): the element-thread
 # launches on a level with at most that many classes keep the class records in LDS -- the same bits; 0 switches it off.
 # element_record_lds_launches(ctx): how many launches those kernels have served.

@@ -231,6 +231,9 @@ def main():
         small_cases(tag, H, b, sweeps)
         multi_cases(tag, H, b)
         H.free()
+    # (the one line that differs between a build with AGGMG_OPT_COARSE_DICTIONARY and one without or before it)
+    if hasattr(ctx, "coarse_dictionary_launches"):
+        print("coarse dictionary launches:", ctx.coarse_dictionary_launches())
 
 
 if __name__ == "__main__":
