@@ -1087,26 +1087,30 @@ static int patch_multi_max_sweeps(const PatchDev& P) {
   return P.multiplicative ? patch_gs_multi_max_sweeps(P.m) : patch_schwarz_multi_max_sweeps(P.m);
 }
 
-// One column-major vector of a K-column run: column 0 and the doubles between two columns.
-struct ColsPtr {
-  double* p = nullptr;
-  int64_t ld = 0;
-};
-// nsweeps >= 1 sweeps on kc <= 8 columns from U0 (p null: zero) into U, in launches of up to patch_multi_max_sweeps, each
+// a zeroed argument block of a K-column sweep kernel with the tail the two kinds share: the column strides, the columns
+template <class Args>
+static Args patch_multi_args(ColsIn src, ColsIn B, ColsOut dst, int kc) {
+  Args m;
+  std::memset(&m, 0, sizeof(m));
+  m.ld_uin = src.ld;
+  m.ld_b = B.ld;
+  m.ld_uout = dst.ld;
+  m.kc = kc;
+  return m;
+}
+// nsweeps >= 1 sweeps on kc <= 8 columns from U0 (null: zero) into U, in launches of up to patch_multi_max_sweeps, each
 // with its slice of the weights, as patch_smooth chunks a single column's run: patch_gs_multi_kernel for a multiplicative
 // smoother, patch_sweep_multi_kernel for a hybrid / additive one (which ignores `reverse`, as its single-column sweeps do).
-// A chunked run alternates between U and `other` (kc columns, neither U0 nor U; p null: leased from the context's scratch)
+// A chunked run alternates between U and `other` (kc columns, neither U0 nor U; null: leased from the context's scratch)
 // so that the last launch writes U.
-static int patch_smooth_multi(aggmg_ctx* ctx, const PatchDev& P, const double* U0, int64_t ld_u0, const double* B, int64_t ld_b,
-                              Damping alpha, int nsweeps, bool reverse, ColsPtr U, ColsPtr other, int kc, int level) {
+static int patch_smooth_multi(aggmg_ctx* ctx, const PatchDev& P, ColsIn U0, ColsIn B, Damping alpha, int nsweeps, bool reverse,
+                              ColsOut U, ColsOut other, int kc, int level) {
   const int64_t N = P.ne * P.m;
   // (hybrid / additive: no launch of more columns than ctx->patch_schwarz_multi_cols -- each slice of the group its own run)
   if (!P.multiplicative && kc > ctx->patch_schwarz_multi_cols) {
-    for (int c0 = 0; c0 < kc; c0 += ctx->patch_schwarz_multi_cols) {
-      const ColsPtr Us{U.p + c0 * U.ld, U.ld}, os{other.p ? other.p + c0 * other.ld : nullptr, other.ld};
-      CHECK(patch_smooth_multi(ctx, P, U0 ? U0 + c0 * ld_u0 : nullptr, ld_u0, B + c0 * ld_b, ld_b, alpha, nsweeps, reverse, Us, os,
+    for (int c0 = 0; c0 < kc; c0 += ctx->patch_schwarz_multi_cols)
+      CHECK(patch_smooth_multi(ctx, P, U0.at(c0), B.at(c0), alpha, nsweeps, reverse, U.at(c0), other.at(c0),
                                std::min(ctx->patch_schwarz_multi_cols, kc - c0), level));
-    }
     return AGGMG_OK;
   }
   const int smax = patch_multi_max_sweeps(P);
@@ -1115,38 +1119,25 @@ static int patch_smooth_multi(aggmg_ctx* ctx, const PatchDev& P, const double* U
   WorkLease t0;
   if (nchunks > 1 && !other.p) {
     CHECK(scratch_lease(ctx, kScratchPing, N * kc, "patch_smooth_multi", &t0));
-    other.p = t0.get();
-    other.ld = N;
+    other = ColsOut(t0.get(), N);
   }
-  const double* src = U0;
-  int64_t ld_src = ld_u0;
+  ColsIn src = U0;
   for (int c = 0; c < nchunks; ++c) {
     const int s = patch_chunk_sweeps(nsweeps, smax, c);
-    const ColsPtr dst = ((nchunks - 1 - c) % 2 == 0) ? U : other;
+    const ColsOut dst = ((nchunks - 1 - c) % 2 == 0) ? U : other;
     const SweepWeights wts = alpha.from(c * smax).launch(s);
     ProfScope ps(ctx, AGGMG_KIND_SMOOTH, level);
     if (P.multiplicative) {
-      PatchGsMultiArgs m;
-      std::memset(&m, 0, sizeof(m));
-      m.g.p = patch_args(P, src, B, dst.p, s);
+      PatchGsMultiArgs m = patch_multi_args<PatchGsMultiArgs>(src, B, dst, kc);
+      m.g.p = patch_args(P, src.p, B.p, dst.p, s);
       m.g.reverse = reverse ? 1 : 0;
-      m.ld_uin = ld_src;
-      m.ld_b = ld_b;
-      m.ld_uout = dst.ld;
-      m.kc = kc;
       CHECK(launch_patch_gs_multi(ctx, P, m, wts));
     } else {
-      PatchSchwarzMultiArgs m;
-      std::memset(&m, 0, sizeof(m));
-      m.p = patch_args(P, src, B, dst.p, s);
-      m.ld_uin = ld_src;
-      m.ld_b = ld_b;
-      m.ld_uout = dst.ld;
-      m.kc = kc;
+      PatchSchwarzMultiArgs m = patch_multi_args<PatchSchwarzMultiArgs>(src, B, dst, kc);
+      m.p = patch_args(P, src.p, B.p, dst.p, s);
       CHECK(launch_patch_schwarz_multi(ctx, P, m, wts));
     }
-    src = dst.p;
-    ld_src = dst.ld;
+    src = dst;
   }
   return AGGMG_OK;
 }
@@ -2447,9 +2438,9 @@ static int coarse_solve(aggmg_ctx* ctx, aggmg_hier* h, const double* rhs_dev, do
 // the coarsest solve of a column group (at most kMultiKB columns): one launch sequence on the device factorisation;
 // column by column on the host banded LU, under AGGMG_CR_FUSE_TAIL=1 (its ticket counts the chunks of one solve) and for
 // a group of one -- the same bits either way
-static int coarse_solve_multi(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int64_t ldb, double* X, int64_t ldx, int kc) {
-  if (h->cr.valid && kc > 1 && !cr_fuse_tail()) return cr_solve(ctx, h, B, ldb, X, ldx, kc);
-  for (int j = 0; j < kc; ++j) CHECK(coarse_solve(ctx, h, B + j * ldb, X + j * ldx));
+static int coarse_solve_multi(aggmg_ctx* ctx, aggmg_hier* h, ColsIn B, ColsOut X, int kc) {
+  if (h->cr.valid && kc > 1 && !cr_fuse_tail()) return cr_solve(ctx, h, B.p, B.ld, X.p, X.ld, kc);
+  for (int j = 0; j < kc; ++j) CHECK(coarse_solve(ctx, h, B.at(j).p, X.at(j).p));
   return AGGMG_OK;
 }
 
@@ -3162,12 +3153,11 @@ extern "C" int aggmg_vcycle_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* x0,
 
 // ---- K right-hand sides in one pass over the operators (EXTENSION: the reference's multigrid_v_cycle / ldiv! take
 // vectors, src/solvers.jl:19,63,84) ------------------------------------------------------------------------------
-// The columns go in groups of at most kMultiKB; every non-coarsest level runs ONE btd_multi_kernel launch per group
-// on the way down and one on the way up (no two-level launches here), and the coarsest solve one launch sequence per
-// group (cr_solve).  A hierarchy with a level outside the kernel's coverage runs the single-column cycle on every
-// column instead (a one-level hierarchy, whose cycle is the coarsest solve alone, still in groups): the same bits either
-// way (multi_kernels.hpp), aggmg_hier_multi_info says which.  Under AGGMG_OPT_PATCH_MULTI a multiplicative element-patch
-// level runs in groups too: the K-column sweeps (patch_multi_kernels.hpp) between zero-sweep btd_multi_kernel launches.
+// The columns go in groups of at most kMultiKB; every non-coarsest level runs the two halves of its kernel family per
+// group (block-tridiagonal levels always, patch and chain levels by option; no two-level launches
+// here), and the coarsest solve one launch sequence per group (cr_solve).  A hierarchy with a level no family accepts runs
+// the single-column cycle on every column instead (a one-level hierarchy, whose cycle is the coarsest solve alone, still
+// in groups): the same bits either way (multi_kernels.hpp), aggmg_hier_multi_info says which.
 #ifndef AGGMG_MULTI_KB
 #define AGGMG_MULTI_KB 8
 #endif
@@ -3181,10 +3171,10 @@ static_assert(is_col_group(kMultiKB), "column groups of 1, 2, 4 or 8");
 // additive one under AGGMG_OPT_PATCH_SCHWARZ_MULTI (patch_sweep_multi_kernel): the K-column sweeps and, around them, the
 // zero-sweep launches of the K-column transfer kernel on the smoother's element-block form -- where the single-column cycle
 // runs its zero-sweep fused launches (patch_transfer_ok), whose bits those repeat.
-static bool multi_patch_level_ok(const aggmg_hier* h, int k, int nPre, int nPost, bool patch_multi, bool patch_schwarz_multi) {
+static bool multi_patch_level_ok(const aggmg_ctx* ctx, const aggmg_hier* h, int k, int nPre, int nPost) {
   const Level& l = h->lv[k];
   const PatchDev& P = *l.S->patch;
-  if (!(P.multiplicative ? patch_multi && patch_multi_form_ok(P) : patch_schwarz_multi && patch_schwarz_multi_form_ok(P)) || !l.tb)
+  if (!(P.multiplicative ? ctx->patch_multi && patch_multi_form_ok(P) : ctx->patch_schwarz_multi && patch_schwarz_multi_form_ok(P)) || !l.tb)
     return false;
   const TransferBtd& t = *l.tb;
   if (t.mc != 2 || t.rho <= 0 || P.ne != (int64_t)t.rho * t.nec) return false;
@@ -3212,10 +3202,10 @@ static bool multi_patch_level_ok(const aggmg_hier* h, int k, int nPre, int nPost
 // A fused chain level in column groups (AGGMG_OPT_CHAIN_MULTI): point-Jacobi sweeps on a block size of chain_dict_form, each half
 // one launch of cgt_multi_kernel with a tile (the planner its launcher runs; a group of kMultiKB columns: the tile does not
 // depend on the group).
-static bool multi_chain_level_ok(const aggmg_hier* h, int k, int nPre, int nPost) {
+static bool multi_chain_level_ok(const aggmg_ctx* ctx, const aggmg_hier* h, int k, int nPre, int nPost) {
   const Level& l = h->lv[k];
   const CgtDev& g = *l.S->cgt;
-  if (g.sw != 0 || !chain_dict_form(g.m) || !l.tc || l.tc->type == kTrNone) return false;
+  if (!ctx->chain_multi || g.sw != 0 || !chain_dict_form(g.m) || !l.tc || l.tc->type == kTrNone) return false;
   const int smax = chain_multi_max_sweeps(g.m);
   if (nPre > smax || nPost > smax) return false;
   TileQuery down, up;
@@ -3229,15 +3219,13 @@ static bool multi_chain_level_ok(const aggmg_hier* h, int k, int nPre, int nPost
   return launch_has_tile(down) && launch_has_tile(up);
 }
 
-static bool multi_level_ok(const aggmg_ctx* ctx, const aggmg_hier* h, int k, int nPre, int nPost) {
+// A fused block-tridiagonal level in column groups (always on): block-Jacobi sweeps on a K-column form, each half one
+// launch of btd_multi_kernel where the single-column cycle runs one fused launch.
+static bool multi_btd_level_ok(const aggmg_ctx*, const aggmg_hier* h, int k, int nPre, int nPost) {
   const Level& l = h->lv[k];
-  if ((ctx->patch_multi || ctx->patch_schwarz_multi) && level_path(h, k) == LevelPath::Patch)
-    return multi_patch_level_ok(h, k, nPre, nPost, ctx->patch_multi, ctx->patch_schwarz_multi);
-  if (ctx->chain_multi && level_path(h, k) == LevelPath::FusedChain) return multi_chain_level_ok(h, k, nPre, nPost);
-  if (level_path(h, k) != LevelPath::FusedBtd || l.S->gs) return false;
   const BtdDev& b = *l.S->btd;
   const TransferBtd& t = *l.tb;
-  if (!multi_form(b.m, b.cmp)) return false;
+  if (l.S->gs || !multi_form(b.m, b.cmp)) return false;
   if (t.mc != 2 || t.rho <= 0 || b.ne != (int64_t)t.rho * t.nec) return false;
   if (t.ld && h->restriction == AGGMG_RESTRICT_PRECONDITIONED) return false;
   // the single-column cycle's launches at this level are single fused launches (no chunked sweeps) ...
@@ -3250,6 +3238,16 @@ static bool multi_level_ok(const aggmg_ctx* ctx, const aggmg_hier* h, int k, int
   down.align = t.rho;
   up.halo = nPost;
   return launch_has_tile(down) && launch_has_tile(up);
+}
+
+// the family that runs level k in column groups, if one does: the switch of vcycle_multi_group
+static bool multi_level_ok(const aggmg_ctx* ctx, const aggmg_hier* h, int k, int nPre, int nPost) {
+  switch (level_path(h, k)) {
+    case LevelPath::FusedChain: return multi_chain_level_ok(ctx, h, k, nPre, nPost);
+    case LevelPath::FusedBtd: return multi_btd_level_ok(ctx, h, k, nPre, nPost);
+    case LevelPath::Patch: return multi_patch_level_ok(ctx, h, k, nPre, nPost);
+    default: return false;   // (the generic kernels; the coarsest level)
+  }
 }
 
 static bool multi_ok(const aggmg_ctx* ctx, const aggmg_hier* h, int nPre, int nPost) {
@@ -3289,148 +3287,124 @@ static int launch_multi(aggmg_ctx* ctx, const BtdDev& b, const MultiArgs& m, con
   return rc;
 }
 
-// per-level K-column vectors for groups of `cols` columns; a call with no more columns than before allocates nothing
+// per-level K-column vectors for groups of `cols` columns (LevelCols: which a level has), multi_ld(h, k) doubles per
+// column; a call with no more columns than before allocates nothing
 static int multi_workspace(aggmg_ctx* ctx, aggmg_hier* h, int64_t cols) {
   if (h->multi_cols >= cols && !h->mu.empty()) return AGGMG_OK;
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  for (auto& m : h->mu)
-    for (auto& p : m) CHECK(p.reset(ctx));
+  for (LevelCols& m : h->mu)
+    for (DevArray<double>* p : {&m.u, &m.up, &m.rhs, &m.aux}) CHECK(p->reset(ctx));
   h->multi_cols = 0;
   const int n = (int)h->lv.size();
   h->mu.resize(n);
   for (int k = 0; k < n; ++k) {
-    const bool coarsest = k == n - 1;
-    for (int s = 0; s < 4; ++s) {
-      if (s == 1 && (k == 0 || coarsest)) continue;   // the ascent's output: the caller's X at level 0, none at the coarsest
-      if (s == 2 && k == 0) continue;                 // level 0's right-hand side is the caller's B
-      if (s == 3 && level_path(h, k) != LevelPath::Patch) continue;   // a patch level's prolonged iterate / second sweep vector
-      // a chain level's vectors (and those a chain level keeps in block order): Nalloc doubles per column, the padding rows
-      // of the trailing block included, and zero-filled like the level's own (aggmg_hier_create) -- the kernels rely on
-      // zeros in the padding rows
-      const bool chain = level_path(h, k) == LevelPath::FusedChain || h->lv[k].native_io;
-      CHECK(h->mu[k][s].alloc(ctx, (chain ? h->lv[k].Nalloc : h->lv[k].N) * cols, chain));
-    }
+    LevelCols& m = h->mu[k];
+    // a chain level's vectors (and those a chain level keeps in block order) are zero-filled like the level's own
+    // (aggmg_hier_create): the kernels rely on zeros in the padding rows of the trailing block
+    const bool chain = level_path(h, k) == LevelPath::FusedChain || h->lv[k].native_io;
+    auto vec = [&](DevArray<double>& v) { return v.alloc(ctx, multi_ld(h, k) * cols, chain); };
+    CHECK(vec(m.u));
+    if (k > 0 && k < n - 1) CHECK(vec(m.up));
+    if (k > 0) CHECK(vec(m.rhs));
+    if (level_path(h, k) == LevelPath::Patch) CHECK(vec(m.aux));
   }
   h->multi_cols = cols;
   return AGGMG_OK;
 }
 
-// A multiplicative patch level of the K-column cycle (multi_patch_level_ok), the launches of patch_down / patch_up for kc
-// columns each.  Descent: the pre sweeps from U0 (null: zero; none at nPre == 0) into mu[k][0], then the zero-sweep K-column
-// launch on the smoother's element blocks -- explicit residual and its restriction into the next level's right-hand
-// sides (always the explicit residual, as patch_down).
-static int multi_patch_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* U0, const double* B, int64_t ld_b, int nPre,
-                            double alpha, int kc) {
-  Level& l = h->lv[k];
-  Level& c = h->lv[k + 1];
-  const PatchDev& P = *l.S->patch;
-  const int64_t ld_u0 = k == 0 ? ld_b : l.N;   // (level 0: the caller's X0 and B share a leading dimension)
-  if (nPre > 0)
-    CHECK(patch_smooth_multi(ctx, P, U0, ld_u0, B, ld_b, l.damp_pre(alpha), nPre, false, ColsPtr{h->mu[k][0].get(), l.N},
-                             ColsPtr{h->mu[k][3].get(), l.N}, kc, k));
+// The argument block of a btd_multi_kernel launch: the fused launch's own (after fused_ascent / fused_descent), kc columns
+// and the column strides of its vectors (a null view: the launch has no such vector).
+static MultiArgs multi_args(const FusedLaunch& f, int kc, ColsIn uin, ColsIn rhs, ColsOut uout, ColsIn uc, ColsOut rc) {
   MultiArgs m;
   std::memset(&m, 0, sizeof(m));
-  // (no sweep: the launch also copies the iterate the ascent starts from)
-  const FusedLaunch f = nPre > 0 ? fused_sweeps(*P.btd, h->mu[k][0], B, nullptr, 0.0, 0) : fused_sweeps(*P.btd, U0, B, h->mu[k][0], 0.0, 0);
   m.a = f;
-  fused_descent(m.a, h, l, h->mu[k + 1][2]);
-  m.a.ld_out = nullptr;   // the explicit residual's restriction, as patch_down
-  m.a.lf_out = l.tb->lf;
-  m.kc = kc;
-  m.ld_uin = nPre > 0 ? l.N : ld_u0;
-  m.ld_b = ld_b;
-  m.ld_uout = l.N;
-  m.ld_rc = c.N;
-  ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
-  return launch_multi(ctx, *P.btd, m, f.wts, 1);
-}
-// Ascent: the zero-sweep K-column prolong-add of mu[k][0] into the scratch vector mu[k][3], then the reverse sweeps into
-// dst (mu[k][0], read for the last time by the prolongation, is the second vector of a chunked run); no sweep: the
-// prolonged iterate goes to dst at once.
-static int multi_patch_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uc, const double* B, int64_t ld_b, int nPost,
-                          double alpha, ColsPtr dst, int kc) {
-  Level& l = h->lv[k];
-  Level& c = h->lv[k + 1];
-  const PatchDev& P = *l.S->patch;
-  const ColsPtr mid = nPost > 0 ? ColsPtr{h->mu[k][3].get(), l.N} : dst;
-  {
-    MultiArgs m;
-    std::memset(&m, 0, sizeof(m));
-    const FusedLaunch f = fused_sweeps(*P.btd, h->mu[k][0], B, mid.p, 0.0, 0);
-    m.a = f;
-    fused_ascent(m.a, l, uc);
-    m.kc = kc;
-    m.ld_uin = l.N;
-    m.ld_b = ld_b;
-    m.ld_uout = mid.ld;
-    m.ld_uc = c.N;
-    ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
-    CHECK(launch_multi(ctx, *P.btd, m, f.wts, 0));
-  }
-  if (nPost == 0) return AGGMG_OK;
-  return patch_smooth_multi(ctx, P, mid.p, mid.ld, B, ld_b, l.damp_post(alpha), nPost, true, dst, ColsPtr{h->mu[k][0].get(), l.N}, kc, k);
+  multi_strides(m, kc, uin, rhs, uout, uc, rc);
+  return m;
 }
 
-// columns [c0, c0 + kc) of a K-column cycle whose every non-coarsest level multi_level_ok accepts
-static int vcycle_multi_group(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, const double* B, int64_t ld, int nPre,
-                              int nPost, double alpha, double* X, int kc) {
+// ---- the halves of a level of the K-column cycle, kc columns each: one pair per family, one argument list (cgt.hip has
+// the chain family's, cgt_multi_down / cgt_multi_up) ------------------------------------------------------------------------
+// A block-tridiagonal level (multi_btd_level_ok).  Descent: nPre sweeps from uin (null: zero) into the level's u, the
+// explicit residual and its restriction into the next level's right-hand sides, one launch.
+static int btd_multi_down(aggmg_ctx* ctx, aggmg_hier* h, int k, ColsIn uin, ColsIn rhs, int nPre, double alpha, int kc) {
+  Level& l = h->lv[k];
+  const ColsOut u = multi_vec(h, k, &LevelCols::u), rc = multi_vec(h, k + 1, &LevelCols::rhs);
+  FusedLaunch f = fused_sweeps(*l.S->btd, uin.p, rhs.p, u.p, l.damp_pre(alpha), nPre);
+  fused_descent(f, h, l, rc.p);   // (lf: multi_btd_level_ok refuses the levels that would take (L'D))
+  ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
+  return launch_multi(ctx, *l.S->btd, multi_args(f, kc, uin, rhs, u, ColsIn(), rc), f.wts, nPre + 1);
+}
+// Ascent: prolong-add of the coarse result onto the level's u, nPost sweeps, into dst, one launch.
+static int btd_multi_up(aggmg_ctx* ctx, aggmg_hier* h, int k, ColsIn rhs, int nPost, double alpha, ColsOut dst, int kc) {
+  Level& l = h->lv[k];
+  const ColsIn u = multi_vec(h, k, &LevelCols::u), uc = multi_coarse_result(h, k);
+  FusedLaunch f = fused_sweeps(*l.S->btd, u.p, rhs.p, dst.p, l.damp_post(alpha), nPost);
+  fused_ascent(f, l, uc.p);
+  ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
+  return launch_multi(ctx, *l.S->btd, multi_args(f, kc, u, rhs, dst, uc, ColsOut()), f.wts, nPost);
+}
+
+// A patch level (multi_patch_level_ok), the launches of patch_down / patch_up for kc columns each.  Descent: the pre sweeps
+// from uin (null: zero; none at nPre == 0) into the level's u, then the zero-sweep K-column launch on the smoother's element
+// blocks -- explicit residual and its restriction into the next level's right-hand sides (always the explicit residual, as
+// patch_down).
+static int multi_patch_down(aggmg_ctx* ctx, aggmg_hier* h, int k, ColsIn uin, ColsIn rhs, int nPre, double alpha, int kc) {
+  Level& l = h->lv[k];
+  const PatchDev& P = *l.S->patch;
+  const ColsOut u = multi_vec(h, k, &LevelCols::u), rc = multi_vec(h, k + 1, &LevelCols::rhs);
+  if (nPre > 0) CHECK(patch_smooth_multi(ctx, P, uin, rhs, l.damp_pre(alpha), nPre, false, u, multi_vec(h, k, &LevelCols::aux), kc, k));
+  // (no sweep: the launch also copies the iterate the ascent starts from)
+  const ColsIn src = nPre > 0 ? ColsIn(u) : uin;
+  FusedLaunch f = fused_sweeps(*P.btd, src.p, rhs.p, nPre > 0 ? nullptr : u.p, 0.0, 0);
+  fused_descent(f, h, l, rc.p);
+  f.ld_out = nullptr;   // the explicit residual's restriction, as patch_down
+  f.lf_out = l.tb->lf;
+  ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
+  return launch_multi(ctx, *P.btd, multi_args(f, kc, src, rhs, u, ColsIn(), rc), f.wts, 1);
+}
+// Ascent: the zero-sweep K-column prolong-add of the level's u into its aux, then the reverse sweeps into dst (u, read for
+// the last time by the prolongation, is the second vector of a chunked run); no sweep: the prolonged iterate goes to dst
+// at once.
+static int multi_patch_up(aggmg_ctx* ctx, aggmg_hier* h, int k, ColsIn rhs, int nPost, double alpha, ColsOut dst, int kc) {
+  Level& l = h->lv[k];
+  const PatchDev& P = *l.S->patch;
+  const ColsOut u = multi_vec(h, k, &LevelCols::u), mid = nPost > 0 ? multi_vec(h, k, &LevelCols::aux) : dst;
+  const ColsIn uc = multi_coarse_result(h, k);
+  {
+    FusedLaunch f = fused_sweeps(*P.btd, u.p, rhs.p, mid.p, 0.0, 0);
+    fused_ascent(f, l, uc.p);
+    ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
+    CHECK(launch_multi(ctx, *P.btd, multi_args(f, kc, u, rhs, mid, uc, ColsOut()), f.wts, 0));
+  }
+  if (nPost == 0) return AGGMG_OK;
+  return patch_smooth_multi(ctx, P, mid, rhs, l.damp_post(alpha), nPost, true, dst, u, kc, k);
+}
+
+// kc columns of a K-column cycle whose every non-coarsest level multi_level_ok accepts: X0 (null: zero guesses), B and X
+// are the group's columns of the caller's matrices
+static int vcycle_multi_group(aggmg_ctx* ctx, aggmg_hier* h, ColsIn X0, ColsIn B, int nPre, int nPost, double alpha, ColsOut X,
+                              int kc) {
   const int n = (int)h->lv.size();
   for (int k = 0; k < n - 1; ++k) {   // descent (src/solvers.jl:28-37)
-    Level& l = h->lv[k];
-    Level& c = h->lv[k + 1];
-    if (level_path(h, k) == LevelPath::Patch) {
-      CHECK(multi_patch_down(ctx, h, k, k == 0 ? X0 : nullptr, k == 0 ? B : h->mu[k][2], k == 0 ? ld : l.N, nPre, alpha, kc));
-      continue;
+    const ColsIn uin = multi_uin(k, X0), rhs = multi_rhs(h, k, B);
+    switch (level_path(h, k)) {
+      case LevelPath::FusedChain: CHECK(cgt_multi_down(ctx, h, k, uin, rhs, nPre, alpha, kc)); break;
+      case LevelPath::FusedBtd: CHECK(btd_multi_down(ctx, h, k, uin, rhs, nPre, alpha, kc)); break;
+      case LevelPath::Patch: CHECK(multi_patch_down(ctx, h, k, uin, rhs, nPre, alpha, kc)); break;
+      default: return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column cycle on a level no K-column family runs");
     }
-    if (level_path(h, k) == LevelPath::FusedChain) {
-      CHECK(cgt_multi_down(ctx, h, k, k == 0 ? X0 : nullptr, ld, k == 0 ? B : h->mu[k][2], k == 0 ? ld : l.Nalloc, nPre, alpha, kc));
-      continue;
-    }
-    MultiArgs m;
-    std::memset(&m, 0, sizeof(m));
-    // u[k] = zeros for k > 1 (:29-31)
-    const FusedLaunch f = fused_sweeps(*l.S->btd, k == 0 ? X0 : nullptr, k == 0 ? B : h->mu[k][2], h->mu[k][0], l.damp_pre(alpha), nPre);
-    m.a = f;
-    fused_descent(m.a, h, l, h->mu[k + 1][2]);   // (lf: multi_level_ok refuses the levels that would take (L'D))
-    m.kc = kc;
-    m.ld_uin = ld;
-    m.ld_b = k == 0 ? ld : l.N;
-    m.ld_uout = l.N;
-    m.ld_rc = c.N;
-    ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
-    CHECK(launch_multi(ctx, *l.S->btd, m, f.wts, nPre + 1));
   }
-  {  // coarsest solve (:39): one launch sequence for the group
-    const int64_t Nc = h->lv[n - 1].N;
-    CHECK(coarse_solve_multi(ctx, h, h->mu[n - 1][2], Nc, h->mu[n - 1][0], Nc, kc));
-  }
+  // coarsest solve (:39): one launch sequence for the group
+  CHECK(coarse_solve_multi(ctx, h, multi_vec(h, n - 1, &LevelCols::rhs), multi_vec(h, n - 1, &LevelCols::u), kc));
   for (int k = n - 2; k >= 0; --k) {   // ascent (:41-47)
-    Level& l = h->lv[k];
-    Level& c = h->lv[k + 1];
-    if (level_path(h, k) == LevelPath::Patch) {
-      const double* uc = (k + 1 == n - 1) ? h->mu[k + 1][0] : h->mu[k + 1][1];
-      CHECK(multi_patch_up(ctx, h, k, uc, k == 0 ? B : h->mu[k][2], k == 0 ? ld : l.N, nPost, alpha,
-                           ColsPtr{k == 0 ? X : h->mu[k][1].get(), k == 0 ? ld : l.N}, kc));
-      continue;
+    const ColsIn rhs = multi_rhs(h, k, B);
+    const ColsOut dst = multi_dst(h, k, X);
+    switch (level_path(h, k)) {
+      case LevelPath::FusedChain: CHECK(cgt_multi_up(ctx, h, k, rhs, nPost, alpha, dst, kc)); break;
+      case LevelPath::FusedBtd: CHECK(btd_multi_up(ctx, h, k, rhs, nPost, alpha, dst, kc)); break;
+      case LevelPath::Patch: CHECK(multi_patch_up(ctx, h, k, rhs, nPost, alpha, dst, kc)); break;
+      default: return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column cycle on a level no K-column family runs");
     }
-    if (level_path(h, k) == LevelPath::FusedChain) {
-      const double* uc = (k + 1 == n - 1) ? h->mu[k + 1][0] : h->mu[k + 1][1];
-      CHECK(cgt_multi_up(ctx, h, k, uc, c.Nalloc, k == 0 ? B : h->mu[k][2], k == 0 ? ld : l.Nalloc, nPost, alpha,
-                         k == 0 ? X : h->mu[k][1].get(), k == 0 ? ld : l.Nalloc, kc));
-      continue;
-    }
-    MultiArgs m;
-    std::memset(&m, 0, sizeof(m));
-    const FusedLaunch f = fused_sweeps(*l.S->btd, h->mu[k][0], k == 0 ? B : h->mu[k][2], k == 0 ? X : h->mu[k][1], l.damp_post(alpha), nPost);
-    m.a = f;
-    fused_ascent(m.a, l, (k + 1 == n - 1) ? h->mu[k + 1][0] : h->mu[k + 1][1]);
-    m.kc = kc;
-    m.ld_uin = l.N;
-    m.ld_b = k == 0 ? ld : l.N;
-    m.ld_uout = k == 0 ? ld : l.N;
-    m.ld_uc = c.N;
-    ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
-    CHECK(launch_multi(ctx, *l.S->btd, m, f.wts, nPost));
   }
   return AGGMG_OK;
 }
@@ -3440,12 +3414,28 @@ static bool ranges_overlap(const double* a, int64_t na, const double* b, int64_t
   return a < b + nb && b < a + na;
 }
 
+// The argument checks every K-column entry point makes once its pointers are known to be there, in the order they fire:
+// the column count; the entry point's own complaint (`own`: null when it has none); the stride; the output against the
+// inputs it must not overlap (`overlap`: the complaint; a null input overlaps nothing); the externally solved coarsest
+// level (h: null for an entry point without a hierarchy).
+static int multi_entry_check(aggmg_ctx* ctx, const char* who, int64_t N, int64_t ncols, int64_t ld, const char* own, ColsOut out,
+                             std::initializer_list<ColsIn> in, const char* overlap, const aggmg_hier* h) {
+  auto bad = [&](const std::string& what) { return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": " + what); };
+  if (ncols < 1) return bad("ncols must be >= 1");
+  if (own) return bad(own);
+  if (ld < N) return bad("ld must be >= N (" + std::to_string(N) + ")");
+  const int64_t span = (ncols - 1) * ld + N;   // doubles from the first column's start to the last one's end
+  for (const ColsIn& v : in)
+    if (ranges_overlap(out.p, span, v.p, span)) return bad(overlap);
+  if (h && h->coarse_mode == AGGMG_COARSE_EXTERNAL) return bad("hierarchy was created with AGGMG_COARSE_EXTERNAL");
+  return AGGMG_OK;
+}
+
 // the coarsest-level system for ncols column-major columns, in the cycle's groups
-static int coarse_solve_cols(aggmg_ctx* ctx, aggmg_hier* h, const double* B, int64_t ncols, int64_t ld, double* X) {
+static int coarse_solve_cols(aggmg_ctx* ctx, aggmg_hier* h, ColsIn B, int64_t ncols, ColsOut X) {
   const int64_t group = std::min<int64_t>(ncols, kMultiKB);
   h->last_coarse_ms = 0.0;
-  for (int64_t c0 = 0; c0 < ncols; c0 += group)
-    CHECK(coarse_solve_multi(ctx, h, B + c0 * ld, ld, X + c0 * ld, ld, (int)std::min<int64_t>(group, ncols - c0)));
+  for (int64_t c0 = 0; c0 < ncols; c0 += group) CHECK(coarse_solve_multi(ctx, h, B.at(c0), X.at(c0), (int)std::min<int64_t>(group, ncols - c0)));
   return AGGMG_OK;
 }
 
@@ -3454,45 +3444,31 @@ extern "C" int aggmg_hier_coarse_solve_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, 
                                                  double* X) {
   if (!ctx) return AGGMG_ERR_ARGUMENT;
   if (!h || !B || !X) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_coarse_solve_multi_dev: NULL argument");
-  if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_coarse_solve_multi_dev: ncols must be >= 1");
-  const int64_t N = h->lv.back().N;
-  if (ld < N)
-    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_coarse_solve_multi_dev: ld must be >= N (" + std::to_string(N) + ")");
-  const int64_t span = (ncols - 1) * ld + N;
-  if (ranges_overlap(X, span, B, span))
-    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_coarse_solve_multi_dev: X must not overlap B");
-  if (h->coarse_mode == AGGMG_COARSE_EXTERNAL)
-    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_coarse_solve_multi_dev: hierarchy was created with AGGMG_COARSE_EXTERNAL");
-  return coarse_solve_cols(ctx, h, B, ncols, ld, X);
+  const ColsIn Bc(B, ld);
+  const ColsOut Xc(X, ld);
+  CHECK(multi_entry_check(ctx, "aggmg_hier_coarse_solve_multi_dev", h->lv.back().N, ncols, ld, nullptr, Xc, {Bc}, "X must not overlap B", h));
+  return coarse_solve_cols(ctx, h, Bc, ncols, Xc);
 }
 
 extern "C" int aggmg_vcycle_multi_dev(aggmg_ctx* ctx, aggmg_hier* h, const double* X0, const double* B, int64_t ncols,
                                       int64_t ld, int nPre, int nPost, double alpha, double* X) {
   if (!ctx) return AGGMG_ERR_ARGUMENT;
   if (!h || !B || !X) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: NULL argument");
-  if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: ncols must be >= 1");
-  if (nPre < 0 || nPost < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: negative sweep count");
-  const int64_t N = h->lv[0].N;
-  if (ld < N) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: ld must be >= N (" + std::to_string(N) + ")");
-  const int64_t span = (ncols - 1) * ld + N;   // doubles from the first column's start to the last one's end
-  if (ranges_overlap(X, span, X0, span) || ranges_overlap(X, span, B, span))
-    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: X must not overlap X0 or B");
-  if (h->coarse_mode == AGGMG_COARSE_EXTERNAL)
-    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_vcycle_multi_dev: hierarchy was created with AGGMG_COARSE_EXTERNAL");
-  if (h->lv.size() == 1) return coarse_solve_cols(ctx, h, B, ncols, ld, X);   // the cycle is the coarsest solve (:39)
+  const ColsIn X0c(X0, ld), Bc(B, ld);
+  const ColsOut Xc(X, ld);
+  CHECK(multi_entry_check(ctx, "aggmg_vcycle_multi_dev", h->lv[0].N, ncols, ld, (nPre < 0 || nPost < 0) ? "negative sweep count" : nullptr,
+                          Xc, {X0c, Bc}, "X must not overlap X0 or B", h));
+  if (h->lv.size() == 1) return coarse_solve_cols(ctx, h, Bc, ncols, Xc);   // the cycle is the coarsest solve (:39)
   if (!multi_ok(ctx, h, nPre, nPost)) {   // column by column: the single-column cycle on every column slice
-    for (int64_t j = 0; j < ncols; ++j)
-      CHECK(aggmg_vcycle_dev(ctx, h, X0 ? X0 + j * ld : nullptr, B + j * ld, nPre, nPost, alpha, X + j * ld));
+    for (int64_t j = 0; j < ncols; ++j) CHECK(aggmg_vcycle_dev(ctx, h, X0c.at(j).p, Bc.at(j).p, nPre, nPost, alpha, Xc.at(j).p));
     return AGGMG_OK;
   }
   CHECK(schedule_check(ctx, h, nPre, nPost));
   const int64_t group = std::min<int64_t>(ncols, kMultiKB);
   CHECK(multi_workspace(ctx, h, group));
   h->last_coarse_ms = 0.0;
-  for (int64_t c0 = 0; c0 < ncols; c0 += group) {
-    const int kc = (int)std::min<int64_t>(group, ncols - c0);
-    CHECK(vcycle_multi_group(ctx, h, X0 ? X0 + c0 * ld : nullptr, B + c0 * ld, ld, nPre, nPost, alpha, X + c0 * ld, kc));
-  }
+  for (int64_t c0 = 0; c0 < ncols; c0 += group)
+    CHECK(vcycle_multi_group(ctx, h, X0c.at(c0), Bc.at(c0), nPre, nPost, alpha, Xc.at(c0), (int)std::min<int64_t>(group, ncols - c0)));
   return AGGMG_OK;
 }
 
@@ -3514,15 +3490,13 @@ extern "C" int aggmg_smooth_multi_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoothe
                                       int64_t ncols, int64_t ld, const double* weights, int nsweeps, int reverse, double* U) {
   CHECK(check_pair(ctx, A, sm, "aggmg_smooth_multi_dev"));
   if (!B || !U) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: NULL argument");
-  if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: ncols must be >= 1");
-  if (nsweeps < 0 || (nsweeps > 0 && !weights)) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: negative sweep count or no weights");
-  for (int s = 0; s < nsweeps; ++s)
-    if (!std::isfinite(weights[s])) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: weight is not finite");
+  const char* own = (nsweeps < 0 || (nsweeps > 0 && !weights)) ? "negative sweep count or no weights" : nullptr;
+  for (int s = 0; !own && s < nsweeps; ++s)
+    if (!std::isfinite(weights[s])) own = "weight is not finite";
   const int64_t N = A->m;
-  if (ld < N) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: ld must be >= N (" + std::to_string(N) + ")");
-  const int64_t span = (ncols - 1) * ld + N;
-  if (ranges_overlap(U, span, U0, span) || ranges_overlap(U, span, B, span))
-    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: U must not overlap U0 or B");
+  const ColsIn U0c(U0, ld), Bc(B, ld);
+  const ColsOut Uc(U, ld);
+  CHECK(multi_entry_check(ctx, "aggmg_smooth_multi_dev", N, ncols, ld, own, Uc, {U0c, Bc}, "U must not overlap U0 or B", nullptr));
   if (sm->patch && sm->A != A) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_smooth_multi_dev: the smoother was set up on another operator");
   if (!sm->patch && sm->patch_width)
     return fail(ctx, AGGMG_ERR_UNSUPPORTED,
@@ -3550,11 +3524,9 @@ extern "C" int aggmg_smooth_multi_dev(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoothe
     return AGGMG_OK;
   }
   const int64_t group = std::min<int64_t>(ncols, kMultiKB);
-  for (int64_t c0 = 0; c0 < ncols; c0 += group) {
-    const int kc = (int)std::min<int64_t>(group, ncols - c0);
-    CHECK(patch_smooth_multi(ctx, P, U0 ? U0 + c0 * ld : nullptr, ld, B + c0 * ld, ld, Damping(0.0, weights), nsweeps, reverse != 0,
-                             ColsPtr{U + c0 * ld, ld}, ColsPtr{}, kc, 0));
-  }
+  for (int64_t c0 = 0; c0 < ncols; c0 += group)
+    CHECK(patch_smooth_multi(ctx, P, U0c.at(c0), Bc.at(c0), Damping(0.0, weights), nsweeps, reverse != 0, Uc.at(c0), ColsOut(),
+                             (int)std::min<int64_t>(group, ncols - c0), 0));
   return AGGMG_OK;
 }
 
@@ -4105,14 +4077,16 @@ extern "C" int aggmg_hier_multi_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h
   if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_multi_launch_bytes: ncols must be >= 1");
   const Level& l = h->lv[level];
   const bool down = kind == AGGMG_KIND_FUSED_DOWN;
-  if (level_path(h, level) == LevelPath::FusedChain)   // (a launch of cgt_multi_kernel, AGGMG_OPT_CHAIN_MULTI)
-    return cgt_multi_launch_bytes(ctx, h, level, down, has_x0 != 0, ncols, read_bytes, write_bytes);
-  if (level_path(h, level) != LevelPath::FusedBtd)
-    return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_hier_multi_launch_bytes: the level has no fused block-tridiagonal launch");
-  const bool pre = l.tb->ld && h->restriction == AGGMG_RESTRICT_PRECONDITIONED;
-  btd_launch_bytes(*l.S->btd, true, !down || has_x0, down, false, down ? nullptr : l.tb.get(), down ? l.tb.get() : nullptr, pre,
-                   read_bytes, write_bytes, ncols);
-  return AGGMG_OK;
+  switch (level_path(h, level)) {   // the families of vcycle_multi_group
+    case LevelPath::FusedChain:     // (a launch of cgt_multi_kernel, AGGMG_OPT_CHAIN_MULTI)
+      return cgt_multi_launch_bytes(ctx, h, level, down, has_x0 != 0, ncols, read_bytes, write_bytes);
+    case LevelPath::FusedBtd:
+      btd_launch_bytes(*l.S->btd, true, !down || has_x0, down, false, down ? nullptr : l.tb.get(), down ? l.tb.get() : nullptr,
+                       restrict_with_ld(h, l), read_bytes, write_bytes, ncols);
+      return AGGMG_OK;
+    default: break;   // (a patch level: several launches a half -- its sweep launch: aggmg_smoother_launch_bytes)
+  }
+  return fail(ctx, AGGMG_ERR_UNSUPPORTED, "aggmg_hier_multi_launch_bytes: the level has no fused block-tridiagonal launch");
 }
 
 extern "C" int aggmg_smoother_launch_bytes(aggmg_ctx* ctx, aggmg_op* A, aggmg_smoother* sm, int what, int64_t* read_bytes,
@@ -5043,17 +5017,12 @@ struct ActiveCols {
 static int multi_solver_args(aggmg_ctx* ctx, const char* who, aggmg_hier* h, const double* B, const double* X, int64_t ncols,
                              int64_t ld, int maxiter, int nPre, int nPost) {
   if (!ctx) return AGGMG_ERR_ARGUMENT;
-  const std::string w(who);
-  if (!h || !B || !X) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": NULL argument");
-  if (ncols < 1) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": ncols must be >= 1");
-  if (ncols > (1 << 20)) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": more than 2^20 columns");
-  if (nPre < 0 || nPost < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": negative sweep count");
-  if (maxiter < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": negative maxiter");
-  const int64_t N = h->lv[0].N;
-  if (ld < N) return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": ld must be >= N (" + std::to_string(N) + ")");
-  if (h->coarse_mode == AGGMG_COARSE_EXTERNAL)
-    return fail(ctx, AGGMG_ERR_ARGUMENT, w + ": hierarchy was created with AGGMG_COARSE_EXTERNAL");
-  return AGGMG_OK;
+  if (!h || !B || !X) return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": NULL argument");
+  const char* own = ncols > (1 << 20)          ? "more than 2^20 columns"
+                    : (nPre < 0 || nPost < 0) ? "negative sweep count"
+                    : maxiter < 0             ? "negative maxiter"
+                                              : nullptr;
+  return multi_entry_check(ctx, who, h->lv[0].N, ncols, ld, own, ColsOut(), {}, nullptr, h);   // (X holds the guesses: no overlap rule)
 }
 
 // K conjugate-gradient recurrences in lockstep (aggmg_pcg_dev per column): per-column scalars on the device, the

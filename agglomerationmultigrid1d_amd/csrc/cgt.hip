@@ -433,65 +433,48 @@ int cgt_mid(aggmg_ctx* ctx, aggmg_hier* h, const double* cur, double* alt, const
 }
 
 // ---- K columns per launch: the halves of a chain level of the K-column cycle (the launcher: above, beside cgt_launch) ----
-// descending half of kc columns on a fused chain level: nPre sweeps from U0 (level 0 only: the caller's X0, or null --
-// zero), residual, restriction into the next level's right-hand sides; the pre-smoothed iterates go to mu[k][0] in block
-// order.  The ext flags are cgt_down's.
-int cgt_multi_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* U0, int64_t ld_u0, const double* B, int64_t ld_b, int nPre,
-                   double alpha, int kc) {
-  Level& l = h->lv[k];
-  Level& c = h->lv[k + 1];
-  const CgtDev& g = *l.S->cgt;
+// what the two halves share: nsweeps sweeps from uin into uout with right-hand sides rhs, kc columns, the coarse result
+// uc to prolong from or the restricted residuals rc to write (a null view: none)
+static CgtMultiArgs cgt_multi_args(const CgtDev& g, int nsweeps, int kc, ColsIn uin, ColsIn rhs, ColsOut uout, ColsIn uc, ColsOut rc) {
   CgtMultiArgs m;
   std::memset(&m, 0, sizeof(m));
   m.a = cgt_args(g);
-  CgtArgs& a = m.a;
-  a.nsweeps = nPre;
-  a.u_in = U0;
-  a.b = B;
-  a.ext = (U0 ? kExtUin : 0) | ((k == 0 || !l.native_io) ? kExtB : 0);
-  a.u_out = h->mu[k][0];
-  a.do_residual = 1;
-  a.tout = cgt_xfer(*l.tc, c.native_io);
-  a.rc_out = h->mu[k + 1][2];
-  cgt_dictionary(a, g, l.cdict.get());
-  m.kc = kc;
-  m.ld_uin = ld_u0;
-  m.ld_b = ld_b;
-  m.ld_uout = l.Nalloc;
-  m.ld_rc = c.Nalloc;
-  const SweepWeights wts = l.damp_pre(alpha).launch(nPre);
-  ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
-  return cgt_multi_launch(ctx, g, m, wts);
+  m.a.nsweeps = nsweeps;
+  m.a.u_in = uin.p;
+  m.a.b = rhs.p;
+  m.a.u_out = uout.p;
+  m.a.uc = uc.p;
+  m.a.rc_out = rc.p;
+  multi_strides(m, kc, uin, rhs, uout, uc, rc);
+  return m;
 }
 
-// ascending half: prolongation-add of uc onto the pre-smoothed iterates (mu[k][0], block order), nPost sweeps, into dst --
-// the caller's numbering at level 0 and on a level whose vectors are not kept in block order, as cgt_up
-int cgt_multi_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uc, int64_t ld_uc, const double* B, int64_t ld_b, int nPost,
-                 double alpha, double* dst, int64_t ld_dst, int kc) {
+// descending half of kc columns on a fused chain level: nPre sweeps from uin (level 0 only: the caller's X0; null --
+// zero), residual, restriction into the next level's right-hand sides; the pre-smoothed iterates go to the level's u in
+// block order.  The ext flags are cgt_down's.
+int cgt_multi_down(aggmg_ctx* ctx, aggmg_hier* h, int k, ColsIn uin, ColsIn rhs, int nPre, double alpha, int kc) {
   Level& l = h->lv[k];
-  Level& c = h->lv[k + 1];
   const CgtDev& g = *l.S->cgt;
-  CgtMultiArgs m;
-  std::memset(&m, 0, sizeof(m));
-  m.a = cgt_args(g);
-  CgtArgs& a = m.a;
-  a.nsweeps = nPost;
-  a.u_in = h->mu[k][0];
-  a.b = B;
-  const bool ext = (k == 0) || !l.native_io;
-  a.ext = (ext ? kExtB : 0) | (ext ? kExtUout : 0);
-  a.u_out = dst;
-  a.tin = cgt_xfer(*l.tc, c.native_io);
-  a.uc = uc;
-  cgt_dictionary(a, g, l.cdict.get());
-  m.kc = kc;
-  m.ld_uin = l.Nalloc;
-  m.ld_b = ld_b;
-  m.ld_uout = ld_dst;
-  m.ld_uc = ld_uc;
-  const SweepWeights wts = l.damp_post(alpha).launch(nPost);
+  CgtMultiArgs m = cgt_multi_args(g, nPre, kc, uin, rhs, multi_vec(h, k, &LevelCols::u), ColsIn(), multi_vec(h, k + 1, &LevelCols::rhs));
+  m.a.ext = (uin.p ? kExtUin : 0) | ((k == 0 || !l.native_io) ? kExtB : 0);
+  m.a.do_residual = 1;
+  m.a.tout = cgt_xfer(*l.tc, h->lv[k + 1].native_io);
+  cgt_dictionary(m.a, g, l.cdict.get());
+  ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
+  return cgt_multi_launch(ctx, g, m, l.damp_pre(alpha).launch(nPre));
+}
+
+// ascending half: prolongation-add of the coarse result onto the pre-smoothed iterates (the level's u, block order), nPost
+// sweeps, into dst -- the caller's numbering at level 0 and on a level whose vectors are not kept in block order, as cgt_up
+int cgt_multi_up(aggmg_ctx* ctx, aggmg_hier* h, int k, ColsIn rhs, int nPost, double alpha, ColsOut dst, int kc) {
+  Level& l = h->lv[k];
+  const CgtDev& g = *l.S->cgt;
+  CgtMultiArgs m = cgt_multi_args(g, nPost, kc, multi_vec(h, k, &LevelCols::u), rhs, dst, multi_coarse_result(h, k), ColsOut());
+  m.a.ext = ((k == 0) || !l.native_io) ? (kExtB | kExtUout) : 0;
+  m.a.tin = cgt_xfer(*l.tc, h->lv[k + 1].native_io);
+  cgt_dictionary(m.a, g, l.cdict.get());
   ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
-  return cgt_multi_launch(ctx, g, m, wts);
+  return cgt_multi_launch(ctx, g, m, l.damp_post(alpha).launch(nPost));
 }
 
 // ---- compulsory bytes: what the arrays of a launch hold, each read or written once -------------

@@ -7,7 +7,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -453,6 +452,28 @@ struct CrDev {
   std::vector<Raw> raw;
 };
 
+// One column-major matrix of a K-column run: column 0 and the doubles between two columns -- the one way the K-column
+// code passes a pointer with its stride.  at(c0): the columns from c0 on (of a null view: a null view).
+template <class T>
+struct Cols {
+  T* p = nullptr;
+  int64_t ld = 0;
+  Cols(T* p_ = nullptr, int64_t ld_ = 0) : p(p_), ld(ld_) {}
+  template <class U, class = std::enable_if_t<std::is_same<const U, T>::value>>
+  Cols(Cols<U> o) : p(o.p), ld(o.ld) {}   // what is written may be read
+  Cols at(int64_t c0) const { return p ? Cols(p + c0 * ld, ld) : Cols(); }
+};
+using ColsIn = Cols<const double>;
+using ColsOut = Cols<double>;
+
+// The vectors level k of a K-column cycle keeps in h->mu[k] (multi_workspace allocates the ones the level has)
+struct LevelCols {
+  DevArray<double> u;     // the pre-smoothed iterate; on the coarsest level the solution
+  DevArray<double> up;    // the post-smoothed iterate, levels 1 .. n-2 (level 0 writes the caller's X)
+  DevArray<double> rhs;   // the right-hand side, levels >= 1 (level 0 reads the caller's B)
+  DevArray<double> aux;   // patch levels: the prolonged iterate in front of the post sweeps; second vector of a chunked run
+};
+
 struct aggmg_hier {
   std::vector<Level> lv;
   int coarse_mode = 0;
@@ -460,12 +481,9 @@ struct aggmg_hier {
   CrDev cr;
   DevArray<double> cyc[2];  // iterate ping-pong for multi-cycle calls (lazy)
   DevArray<double> io[3];   // x0, b, x_out of the host-pointer entry aggmg_vcycle (lazy)
-  // K-column cycles (aggmg_vcycle_multi_dev, lazy, grown to the largest column group asked for): per level, multi_cols
-  // columns of the pre-smoothed iterate (mu[k][0]), the post-smoothed one (mu[k][1], levels 1 .. n-2) and the right-hand
-  // side (mu[k][2], levels >= 1); the coarsest level's solution goes to mu[n-1][0]; a multiplicative patch level
-  // (AGGMG_OPT_PATCH_MULTI) has one more, mu[k][3]: the prolonged iterate in front of its post sweeps, and the second
-  // vector of a chunked run of sweeps
-  std::vector<std::array<DevArray<double>, 4>> mu;
+  // K-column cycles (aggmg_vcycle_multi_dev; multi_workspace: lazy, grown to the largest column group asked for): per
+  // level, multi_cols columns of each vector the level has, multi_ld(h, k) doubles apart
+  std::vector<LevelCols> mu;
   int64_t multi_cols = 0;
   // the coarsest solve of a column group in one launch sequence (cr_run_cols; lazy, grown like mu): per column of the
   // group what a CrStage holds for one (partR / partL / xq, stack, mid of every stage, the tail's mid) in ONE zeroed
@@ -520,6 +538,35 @@ inline LevelPath level_path(const aggmg_hier* h, int k) {
   if (l.S && l.S->patch && l.S->A == l.A) return LevelPath::Patch;
   if (l.S && l.S->btd && l.S->A == l.A) return l.tb ? LevelPath::FusedBtd : LevelPath::BtdTransfer;
   return LevelPath::Generic;
+}
+
+// ---- the vectors of the K-column cycle (aggmg_vcycle_multi_dev) ------------------------------
+// The column stride of level k's vectors in h->mu[k]: multi_workspace sizes them with it, every half-cycle reads and
+// writes them with it, the level above included (its restricted residuals, the result it prolongs from).  It is Nalloc.
+// aggmg_hier_create sets Nalloc = N on every level and raises it -- to the block-ordered length, the padding rows of the
+// trailing block included -- only where the level's smoother has a chain form on the level's own operator: never on the
+// coarsest level, which has no smoother.  The set-ups build a chain form only for a smoother with neither a
+// block-tridiagonal nor a patch form, so level_path sends such a level to FusedChain or to Generic, and multi_ok accepts it
+// as FusedChain alone.  On an accepted hierarchy, then, Nalloc == N on every block-tridiagonal, patch and coarsest level
+// (their kernels address N rows per column) and Nalloc is the block-ordered length on every chain level (whose kernels
+// address that many, and want the padding rows zero).
+inline int64_t multi_ld(const aggmg_hier* h, int k) { return h->lv[k].Nalloc; }
+inline ColsOut multi_vec(const aggmg_hier* h, int k, DevArray<double> LevelCols::*v) {
+  return ColsOut((h->mu[k].*v).get(), multi_ld(h, k));
+}
+// the tail MultiArgs and CgtMultiArgs share: the columns of the launch, the column strides of its vectors (null view: none)
+template <class Args>
+inline void multi_strides(Args& m, int kc, ColsIn uin, ColsIn rhs, ColsOut uout, ColsIn uc, ColsOut rc) {
+  m.kc = kc;
+  m.ld_uin = uin.ld, m.ld_b = rhs.ld, m.ld_uout = uout.ld, m.ld_uc = uc.ld, m.ld_rc = rc.ld;
+}
+// Which vectors level k of a cycle on the caller's X0 (null: zero guesses), B and X uses: the K-column counterparts of
+// rhs, uin, dst and coarse_result of the single-column driver -- the one place that knows level 0 and the coarsest apart
+inline ColsIn multi_rhs(const aggmg_hier* h, int k, ColsIn B) { return k == 0 ? B : ColsIn(multi_vec(h, k, &LevelCols::rhs)); }
+inline ColsIn multi_uin(int k, ColsIn X0) { return k == 0 ? X0 : ColsIn(); }   // u[k] = zeros for k > 1 (src/solvers.jl:29-31)
+inline ColsOut multi_dst(const aggmg_hier* h, int k, ColsOut X) { return k == 0 ? X : multi_vec(h, k, &LevelCols::up); }
+inline ColsIn multi_coarse_result(const aggmg_hier* h, int k) {   // what level k prolongs from
+  return multi_vec(h, k + 1, k + 1 == (int)h->lv.size() - 1 ? &LevelCols::u : &LevelCols::up);
 }
 
 // A slot of the context's shared vectors for `who` (a string literal), held until *lease goes out of scope.  A slot that
@@ -607,11 +654,9 @@ int cgt_mid(aggmg_ctx* ctx, aggmg_hier* h, const double* cur, double* alt, const
 // compulsory bytes (every array of the launch once) of a chain level's fused launches / of a stand-alone sweep or residual launch
 int cgt_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int level, bool down, bool up, bool has_x0, int64_t* rd, int64_t* wr);
 // K columns per launch (AGGMG_OPT_CHAIN_MULTI): the halves of a fused chain level of the K-column cycle, on the vectors of
-// multi_workspace (h->mu; leading dimension Nalloc on a chain level)
-int cgt_multi_down(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* U0, int64_t ld_u0, const double* B, int64_t ld_b, int nPre,
-                   double alpha, int kc);
-int cgt_multi_up(aggmg_ctx* ctx, aggmg_hier* h, int k, const double* uc, int64_t ld_uc, const double* B, int64_t ld_b, int nPost,
-                 double alpha, double* dst, int64_t ld_dst, int kc);
+// multi_workspace (h->mu); the argument list of every family's K-column halves
+int cgt_multi_down(aggmg_ctx* ctx, aggmg_hier* h, int k, ColsIn uin, ColsIn rhs, int nPre, double alpha, int kc);
+int cgt_multi_up(aggmg_ctx* ctx, aggmg_hier* h, int k, ColsIn rhs, int nPost, double alpha, ColsOut dst, int kc);
 int cgt_multi_launch_bytes(aggmg_ctx* ctx, const aggmg_hier* h, int level, bool down, bool has_x0, int64_t ncols, int64_t* rd, int64_t* wr);
 int cgt_op_launch_bytes(const CgtDev& g, bool sweeps, int64_t* rd, int64_t* wr);
 
