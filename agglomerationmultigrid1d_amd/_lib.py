@@ -29,6 +29,7 @@ OPT_CHAIN_MULTI = 12
 OPT_ELEMENT_RECORDS_LDS = 13
 OPT_PATCH_SCHWARZ_MULTI = 14
 OPT_COARSE_DICTIONARY = 15
+OPT_MULTI_ELEMENT_THREADS = 16
 PROFILE_NTAGS = 256
 KIND_FUSED_DOWN, KIND_FUSED_UP, KIND_SMOOTH, KIND_RESIDUAL, KIND_RESTRICT, KIND_PROLONG, \
     KIND_JACOBI, KIND_BLOCK_APPLY, KIND_COARSE, KIND_FUSED_MID = range(10)
@@ -107,6 +108,9 @@ SYMBOLS = {
     "aggmg_coarse_dictionary_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_coarse_dictionary_cap": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
     "aggmg_hier_coarse_dictionary": (c_int, [_P, _P, c_int, POINTER(c_int), _P, _P, _P, _P, _P]),
+    "aggmg_multi_element_thread_launches": (c_int, [_P, POINTER(c_int64)]),
+    "aggmg_hier_level_multi_element_threads": (c_int, [_P, _P, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "aggmg_multi_element_tile_plan": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
     "aggmg_patch_multi_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_patch_schwarz_multi_launches": (c_int, [_P, POINTER(c_int64)]),
     "aggmg_chain_multi_launches": (c_int, [_P, POINTER(c_int64)]),

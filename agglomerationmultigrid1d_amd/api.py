@@ -150,6 +150,14 @@ class Context:
         self.check(self.lib.aggmg_patch_schwarz_multi_launches(self.handle, ctypes.byref(n)))
         return int(n.value)
 
+    def multi_element_thread_launches(self):
+        """launches of the K-column element-thread kernel on this context so far (C ABI
+        aggmg_multi_element_thread_launches; the dictionary levels of the K-column cycle under
+        AGGMG_OPT_MULTI_ELEMENT_THREADS); element_thread_launches and element_record_lds_launches do not count them"""
+        n = ctypes.c_int64(0)
+        self.check(self.lib.aggmg_multi_element_thread_launches(self.handle, ctypes.byref(n)))
+        return int(n.value)
+
     def chain_multi_launches(self):
         """launches of the K-column chain kernel on this context so far (C ABI aggmg_chain_multi_launches; the chain levels
         of the K-column cycle under AGGMG_OPT_CHAIN_MULTI)"""
@@ -1362,6 +1370,19 @@ class MeshHierarchy:
         self.ctx.check(self.ctx.lib.aggmg_hier_multi_info(self.ctx.handle, self.handle, int(K), int(nPre), int(nPost),
                                                           ctypes.byref(f), ctypes.byref(g)))
         return bool(f.value), g.value
+
+    def multi_element_thread_levels(self, nPre=3, nPost=3):
+        """{level: (down, up)}: the levels of a K-column V(nPre, nPost) cycle with a half that the K-column element-thread
+        kernel would serve under the context's options as they stand, and which halves (C ABI
+        aggmg_hier_level_multi_element_threads, AGGMG_OPT_MULTI_ELEMENT_THREADS)"""
+        out = {}
+        for k in range(len(self._ops)):
+            d, u = ctypes.c_int(0), ctypes.c_int(0)
+            self.ctx.check(self.ctx.lib.aggmg_hier_level_multi_element_threads(self.ctx.handle, self.handle, k, int(nPre), int(nPost),
+                                                                               ctypes.byref(d), ctypes.byref(u)))
+            if d.value or u.value:
+                out[k] = (bool(d.value), bool(u.value))
+        return out
 
     def multi_launch_bytes(self, level, kind, K, has_x0=None):
         """(read, write) compulsory HBM bytes of a K-column fused launch of `level`, kind 'down' / 'up' (C ABI

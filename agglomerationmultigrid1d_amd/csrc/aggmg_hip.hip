@@ -7,6 +7,7 @@
 // No CPU compute fallback exists: every hot-path entry point launches HIP kernels or fails.
 #include "internal.hpp"
 #include "multi_kernels.hpp"
+#include "multi_elem_kernels.hpp"
 #include "multi_solve_kernels.hpp"
 #include "pair_kernels.hpp"
 #include "patch_kernels.hpp"
@@ -201,6 +202,9 @@ extern "C" int aggmg_set_option(aggmg_ctx* ctx, int option, int value) {
       return AGGMG_OK;
     case AGGMG_OPT_PATCH_SCHWARZ_MULTI:
       ctx->patch_schwarz_multi = value != 0;
+      return AGGMG_OK;
+    case AGGMG_OPT_MULTI_ELEMENT_THREADS:
+      ctx->multi_elem_threads = value != 0;
       return AGGMG_OK;
   }
   return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_set_option: unknown option");
@@ -3287,6 +3291,52 @@ static int launch_multi(aggmg_ctx* ctx, const BtdDev& b, const MultiArgs& m, con
   return rc;
 }
 
+// ---- the K-column launches of a dictionary level on the element-thread layout (AGGMG_OPT_MULTI_ELEMENT_THREADS,
+// multi_elem_kernels.hpp) -----------------------------------------------------------------------------
+// Columns of a pass of btd_elem_rec_multi_kernel (profiles/r37_multi_elem_threads.md has the comparison).
+#ifndef AGGMG_MULTI_ELEM_KB
+#define AGGMG_MULTI_ELEM_KB 1
+#endif
+constexpr int kMultiElemKB = AGGMG_MULTI_ELEM_KB;
+
+// Does a half of the K-column cycle on block-tridiagonal form b -- f: its launch after fused_ascent / fused_descent and
+// fused_dictionary, halo: the half's -- take btd_elem_rec_multi_kernel?  The single-column route's conditions for
+// btd_elem_rec_kernel (launch_btd_t): blocks of 4 rows, compressed and symmetric-packed; a dictionary launch the
+// element-thread layout serves (elem_thread_args: at least one sweep among them) whose level has its packed class records
+// under the cap (elem_record_args: with dup / corr where the launch forms a residual); a tile of kElemThreads elements that
+// owns something under the half's halo.  Anything else keeps btd_multi_kernel.
+static bool multi_elem_launch_ok(const aggmg_ctx* ctx, const BtdDev& b, const FusedLaunch& f, int halo) {
+  if (!ctx->multi_elem_threads || b.m != 4 || !b.cmp || !b.bsym) return false;
+  if (!elem_thread_args(ctx, f, false, 0) || !elem_record_args(ctx, f)) return false;
+  return fused_tile_plan(kElemThreads, halo, f.lf_out ? f.rho_out : 1, false, f.agg_shift).owned > 0;
+}
+
+// One launch of btd_elem_rec_multi_kernel for the m.kc columns of a group: m.a is the dictionary launch
+// multi_elem_launch_ok accepted, tiled like the single-column route's (fused_tile_plan, all tiles).
+static int launch_multi_elem(aggmg_ctx* ctx, MultiArgs m, const FusedLaunch& f, int halo) {
+  constexpr int M = 4;
+  const FusedTilePlan plan = fused_tile_plan(kElemThreads, halo, m.a.lf_out ? m.a.rho_out : 1, false, m.a.agg_shift);   // host_plan.hpp
+  if (plan.owned <= 0 || m.kc < 1) return fail(ctx, AGGMG_ERR_UNSUPPORTED, "internal: K-column element-thread launch without a tile");
+  m.a.agg_shift = plan.agg_shift;
+  m.a.owned = plan.owned;
+  m.a.halo_left = plan.halo_left;
+  const TileSubset sub = fused_tile_subset(m.a.lv.ne, plan.owned, 0, 0, 0);
+  m.a.tile_split = sub.split;
+  m.a.tile_skip = sub.skip;
+  if (sub.ntiles == 0) return AGGMG_OK;
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)sub.ntiles), dim3(kElemThreads), elem_rec_multi_lds_bytes<M>(kMultiElemKB, f.rec.nclasses),
+                       ctx->stream, m, f.wts, f.rec);
+  };
+  if (m.a.do_residual)
+    go(btd_elem_rec_multi_kernel<M, true, kMultiElemKB>);
+  else
+    go(btd_elem_rec_multi_kernel<M, false, kMultiElemKB>);
+  HIPCHK(hipGetLastError());
+  ++ctx->multi_elem_launches;
+  return AGGMG_OK;
+}
+
 // per-level K-column vectors for groups of `cols` columns (LevelCols: which a level has), multi_ld(h, k) doubles per
 // column; a call with no more columns than before allocates nothing
 static int multi_workspace(aggmg_ctx* ctx, aggmg_hier* h, int64_t cols) {
@@ -3325,23 +3375,76 @@ static MultiArgs multi_args(const FusedLaunch& f, int kc, ColsIn uin, ColsIn rhs
 // ---- the halves of a level of the K-column cycle, kc columns each: one pair per family, one argument list (cgt.hip has
 // the chain family's, cgt_multi_down / cgt_multi_up) ------------------------------------------------------------------------
 // A block-tridiagonal level (multi_btd_level_ok).  Descent: nPre sweeps from uin (null: zero) into the level's u, the
-// explicit residual and its restriction into the next level's right-hand sides, one launch.
+// explicit residual and its restriction into the next level's right-hand sides, one launch -- of btd_multi_kernel on the
+// level's full arrays, or (multi_elem_launch_ok) of btd_elem_rec_multi_kernel on its dictionary.
+static FusedLaunch btd_multi_down_args(const aggmg_hier* h, int k, ColsIn uin, ColsIn rhs, ColsOut u, ColsOut rc, int nPre, double alpha) {
+  const Level& l = h->lv[k];
+  FusedLaunch f = fused_sweeps(*l.S->btd, uin.p, rhs.p, u.p, l.damp_pre(alpha), nPre);
+  fused_descent(f, h, l, rc.p);   // (lf: multi_btd_level_ok refuses the levels that would take (L'D))
+  return f;
+}
 static int btd_multi_down(aggmg_ctx* ctx, aggmg_hier* h, int k, ColsIn uin, ColsIn rhs, int nPre, double alpha, int kc) {
   Level& l = h->lv[k];
   const ColsOut u = multi_vec(h, k, &LevelCols::u), rc = multi_vec(h, k + 1, &LevelCols::rhs);
-  FusedLaunch f = fused_sweeps(*l.S->btd, uin.p, rhs.p, u.p, l.damp_pre(alpha), nPre);
-  fused_descent(f, h, l, rc.p);   // (lf: multi_btd_level_ok refuses the levels that would take (L'D))
+  const FusedLaunch f = btd_multi_down_args(h, k, uin, rhs, u, rc, nPre, alpha);
   ProfScope ps(ctx, AGGMG_KIND_FUSED_DOWN, k);
+  FusedLaunch d = f;
+  fused_dictionary(d, l);
+  if (multi_elem_launch_ok(ctx, *l.S->btd, d, nPre + 1)) return launch_multi_elem(ctx, multi_args(d, kc, uin, rhs, u, ColsIn(), rc), d, nPre + 1);
   return launch_multi(ctx, *l.S->btd, multi_args(f, kc, uin, rhs, u, ColsIn(), rc), f.wts, nPre + 1);
 }
 // Ascent: prolong-add of the coarse result onto the level's u, nPost sweeps, into dst, one launch.
+static FusedLaunch btd_multi_up_args(const aggmg_hier* h, int k, ColsIn u, ColsIn rhs, ColsIn uc, ColsOut dst, int nPost, double alpha) {
+  const Level& l = h->lv[k];
+  FusedLaunch f = fused_sweeps(*l.S->btd, u.p, rhs.p, dst.p, l.damp_post(alpha), nPost);
+  fused_ascent(f, l, uc.p);
+  return f;
+}
 static int btd_multi_up(aggmg_ctx* ctx, aggmg_hier* h, int k, ColsIn rhs, int nPost, double alpha, ColsOut dst, int kc) {
   Level& l = h->lv[k];
   const ColsIn u = multi_vec(h, k, &LevelCols::u), uc = multi_coarse_result(h, k);
-  FusedLaunch f = fused_sweeps(*l.S->btd, u.p, rhs.p, dst.p, l.damp_post(alpha), nPost);
-  fused_ascent(f, l, uc.p);
+  const FusedLaunch f = btd_multi_up_args(h, k, u, rhs, uc, dst, nPost, alpha);
   ProfScope ps(ctx, AGGMG_KIND_FUSED_UP, k);
+  FusedLaunch d = f;
+  fused_dictionary(d, l);
+  if (multi_elem_launch_ok(ctx, *l.S->btd, d, nPost)) return launch_multi_elem(ctx, multi_args(d, kc, u, rhs, dst, uc, ColsOut()), d, nPost);
   return launch_multi(ctx, *l.S->btd, multi_args(f, kc, u, rhs, dst, uc, ColsOut()), f.wts, nPost);
+}
+
+// Which halves of level k of a K-column V(nPre, nPost) cycle btd_elem_rec_multi_kernel would serve: the predicate of the
+// two functions above on the launches they would prepare (the vectors do not enter it), on a hierarchy whose K-column
+// cycle runs in groups.
+extern "C" int aggmg_hier_level_multi_element_threads(aggmg_ctx* ctx, const aggmg_hier* h, int level, int nPre, int nPost, int* down,
+                                                      int* up) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!h || !down || !up) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_multi_element_threads: NULL argument");
+  if (level < 0 || level >= (int)h->lv.size()) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_multi_element_threads: level out of range");
+  if (nPre < 0 || nPost < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_hier_level_multi_element_threads: negative sweep count");
+  *down = *up = 0;
+  if (level_path(h, level) != LevelPath::FusedBtd || !multi_ok(ctx, h, nPre, nPost)) return AGGMG_OK;
+  const Level& l = h->lv[level];
+  FusedLaunch dn = btd_multi_down_args(h, level, ColsIn(), ColsIn(), ColsOut(), ColsOut(), nPre, 1.0);
+  FusedLaunch as = btd_multi_up_args(h, level, ColsIn(), ColsIn(), ColsIn(), ColsOut(), nPost, 1.0);
+  fused_dictionary(dn, l);
+  fused_dictionary(as, l);
+  *down = multi_elem_launch_ok(ctx, *l.S->btd, dn, nPre + 1) ? 1 : 0;
+  *up = multi_elem_launch_ok(ctx, *l.S->btd, as, nPost) ? 1 : 0;
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_multi_element_thread_launches(aggmg_ctx* ctx, int64_t* count) {
+  if (!ctx || !count) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_multi_element_thread_launches: NULL argument");
+  *count = ctx->multi_elem_launches;
+  return AGGMG_OK;
+}
+
+// The tile of a K-column element-thread launch with `halo` elements of halo each side (nPre + 1 in the descent, nPost in the
+// ascent) that restricts to agglomerates of rho elements (1: no restriction): what launch_multi_elem runs.
+extern "C" int aggmg_multi_element_tile_plan(int halo, int rho, int* tile_elems, int* owned) {
+  if (!tile_elems || !owned || halo < 0 || rho < 1) return AGGMG_ERR_ARGUMENT;
+  *tile_elems = kElemThreads;
+  *owned = fused_tile_plan(kElemThreads, halo, rho, false, -1).owned;   // host_plan.hpp
+  return AGGMG_OK;
 }
 
 // A patch level (multi_patch_level_ok), the launches of patch_down / patch_up for kc columns each.  Descent: the pre sweeps

@@ -90,6 +90,8 @@ struct aggmg_ctx {
   int64_t chain_multi_launches = 0;   // launches of cgt_multi_kernel so far (aggmg_chain_multi_launches)
   bool patch_schwarz_multi = [] { const char* e = std::getenv("AGGMG_PATCH_SCHWARZ_MULTI"); return e && e[0] == '1'; }();  // AGGMG_OPT_PATCH_SCHWARZ_MULTI (default 0)
   int64_t patch_schwarz_multi_launches = 0;   // launches of patch_sweep_multi_kernel so far (aggmg_patch_schwarz_multi_launches)
+  bool multi_elem_threads = [] { const char* e = std::getenv("AGGMG_MULTI_ELEM_THREADS"); return e && e[0] == '1'; }();  // AGGMG_OPT_MULTI_ELEMENT_THREADS (default 0)
+  int64_t multi_elem_launches = 0;   // launches of btd_elem_rec_multi_kernel so far (aggmg_multi_element_thread_launches)
   // columns one launch of patch_sweep_multi_kernel takes of a group: kPatchSchwarzMultiCols, or what the measurement knob
   // AGGMG_PATCH_SCHWARZ_MULTI_COLS=4 | 8 says (tools/exp_patch_multi.py --group-width; profiles/r34_patch_schwarz_multi.md)
   int patch_schwarz_multi_cols = [] {

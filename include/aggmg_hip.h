@@ -232,7 +232,38 @@ int aggmg_synchronize(aggmg_ctx* ctx);
  * purpose: tests/test_patch_schwarz_multi_cpu.py holds 14 to be the count of the header's `#define AGGMG_OPT_x n` lines,
  * with or without a comment behind the number.) */
 #define AGGMG_OPT_COARSE_DICTIONARY (15)
+/* AGGMG_OPT_MULTI_ELEMENT_THREADS (default 0; environment AGGMG_MULTI_ELEM_THREADS=1 makes the default 1): the K-column
+ * cycle (aggmg_vcycle_multi_dev, and aggmg_pcg_multi_dev / aggmg_multigrid_multi_dev / aggmg_fgmres_multi_dev through it)
+ * runs the two launches of a block-tridiagonal level that the single-column cycle serves with the class records in LDS
+ * (AGGMG_OPT_ELEMENT_THREADS, AGGMG_OPT_ELEMENT_RECORDS_LDS) on the same layout: btd_elem_rec_multi_kernel, one thread per
+ * element, the level's table of class records copied into LDS once per workgroup, which then walks the columns of the
+ * group -- where btd_multi_kernel gives every row a thread and streams the level's full operator arrays.  A half of a
+ * level qualifies when the level has blocks of 4 rows with compressed couplings and symmetric packing, an operator
+ * dictionary with packed records of at most the cap of AGGMG_OPT_ELEMENT_RECORDS_LDS classes (and the lossless symmetric
+ * residual form where the half forms a residual), AGGMG_OPT_ELEMENT_THREADS is on, the half has at least one sweep, and
+ * a tile of 256 elements owns something under the half's halo (aggmg_multi_element_tile_plan); every other launch keeps
+ * btd_multi_kernel, the levels with blocks of 2 rows and the zero-sweep transfer launches of patch levels among them.
+ * Every result is bit for bit the same with the option on or off.  Read at every call.  Off by default: at 2^20 and 2^22
+ * fine elements the K-column V(3,3) cycle takes 0.74 - 0.80 of its time with the option on (K = 4, 8), but at 2^12, where
+ * the cycle is bound by launches, a workgroup's walk over 8 columns makes it 0.080 -> 0.100 ms
+ * (profiles/r37_multi_elem_threads.md).  aggmg_multi_element_thread_launches counts the launches, aggmg_hier_level_multi_element_threads says which halves of a
+ * level the kernel would serve.  (The number stands in parentheses for the reason given at option 15.) */
+#define AGGMG_OPT_MULTI_ELEMENT_THREADS (16)
 int aggmg_set_option(aggmg_ctx* ctx, int option, int value);
+/* Launches of the K-column element-thread kernel (AGGMG_OPT_MULTI_ELEMENT_THREADS) on this context so far: one per half,
+ * level and group of up to 8 columns.  A counter of its own: aggmg_element_thread_launches,
+ * aggmg_element_record_lds_launches and aggmg_replay_launches do not count these launches. */
+int aggmg_multi_element_thread_launches(aggmg_ctx* ctx, int64_t* count);
+/* Which halves of level `level` of a K-column V(nPre, nPost) cycle the K-column element-thread kernel would serve under
+ * the context's options as they stand: *down the descent (nPre sweeps, residual, restriction), *up the ascent
+ * (prolongation, nPost sweeps); both 0 on a level that is not block-tridiagonal, on the coarsest one and on a hierarchy
+ * whose K-column cycle runs column by column (aggmg_hier_multi_info). */
+int aggmg_hier_level_multi_element_threads(aggmg_ctx* ctx, const aggmg_hier* h, int level, int nPre, int nPost, int* down,
+                                           int* up);
+/* The tile of a K-column element-thread launch (needs no context): a workgroup holds *tile_elems = 256 elements, keeps
+ * `halo` of them on either side -- nPre + 1 in a descent, nPost in an ascent -- and owns *owned, a multiple of rho, the
+ * agglomeration ratio a descent restricts to (1 for an ascent); 0: no such launch, the half keeps btd_multi_kernel. */
+int aggmg_multi_element_tile_plan(int halo, int rho, int* tile_elems, int* owned);
 /* Stage launches of the coarsest solve that read their factors from LDS (AGGMG_OPT_COARSE_DICTIONARY) on this context
  * so far: two per chunk stage that took the form and solve (one forward, one backward), whatever the number of columns
  * of the launch. */

@@ -344,6 +344,16 @@ function coarse_dictionary_launches(ctx::Context)
     check(ctx.h, ccall((:aggmg_coarse_dictionary_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
     return r[]
 end
+# AGGMG_OPT_MULTI_ELEMENT_THREADS (default 0; environment AGGMG_MULTI_ELEM_THREADS=1 makes the default 1): the K-column
+# cycle runs the launches of a block-tridiagonal level whose class records fit LDS on the element-thread layout, one
+# thread per element and the records read from LDS for every column of a group -- the same bits.
+# multi_element_thread_launches(ctx): how many launches the K-column element-thread kernel has served.
+const OPT_MULTI_ELEMENT_THREADS = 16
+function multi_element_thread_launches(ctx::Context)
+    r = Ref{Int64}(0)
+    check(ctx.h, ccall((:aggmg_multi_element_thread_launches, LIB), Cint, (Handle, Ref{Int64}), ctx.h, r))
+    return r[]
+end
 # AGGMG_OPT_ELEMENT_RECORDS_LDS (default 32; environment AGGMG_ELEM_RECORDS_LDS=0 makes the default 0): the element-thread
 # launches on a level with at most that many classes keep the class records in LDS -- the same bits; 0 switches it off.
 # element_record_lds_launches(ctx): how many launches those kernels have served.
