@@ -251,6 +251,10 @@ SYMBOLS = {
     "aggmg_pcg_xr_owned_dev": (c_int, [_P, c_int64, _P, _P, _P, _P, c_double, c_int, POINTER(c_int64), POINTER(c_int64),
                                        POINTER(c_double)]),
     "aggmg_pcg_p_dev": (c_int, [_P, c_int64, _P, _P, c_double]),
+    "aggmg_owned_multi_dot_dev": (c_int, [_P, _P, c_int64, c_int64, _P, c_int, POINTER(c_int64), POINTER(c_int64), _PD]),
+    "aggmg_owned_multi_axpy_norm_dev": (c_int, [_P, c_int64, _P, c_int64, c_int64, _PD, _P, c_int, POINTER(c_int64),
+                                                POINTER(c_int64), _PD]),
+    "aggmg_div_scalar_dev": (c_int, [_P, c_int64, _P, c_double, _P]),
     "aggmg_residual_multi_launch_bytes": (c_int, [_P, _P, c_int64, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "aggmg_profile_enable": (c_int, [_P, c_int]),
     "aggmg_profile_collect": (c_int, [_P, _PD, POINTER(c_int64)]),

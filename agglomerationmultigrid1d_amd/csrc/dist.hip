@@ -973,3 +973,153 @@ extern "C" int aggmg_pcg_p_dev(aggmg_ctx* ctx, int64_t n, double* p, const doubl
   HIPCHK(hipGetLastError());
   return AGGMG_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// flexible GMRES around the partitioned cycle (distributed.fgmres): the fused passes of its orthogonalisation over the
+// owned ranges, and the scaling by a host scalar (dist_solve_kernels.hpp).  Their partial sums and scalars live in a
+// buffer of their own (own_multi_part), so that nothing the conjugate-gradient entry points read moves.
+// ---------------------------------------------------------------------------------------------
+constexpr int64_t kOwnedMaxVec = AGGMG_FGMRES_MAX_RESTART + 1;
+constexpr int64_t kOwnedPartStride = (int64_t)kOwnedBlocks * kOwnedMaxRanges;   // partial sums of one dot
+constexpr int64_t kOwnedMultiScalars = kOwnedMaxVec * kOwnedPartStride;         // behind them: 65 dots, then the sum of squares
+
+static int owned_multi_buffers(aggmg_ctx* ctx) {
+  if (!ctx->own_multi_part) CHECK(ctx->own_multi_part.alloc(ctx, kOwnedMultiScalars + kOwnedMaxVec + 1));
+  return AGGMG_OK;
+}
+
+static bool owned_overlap(const double* a, int64_t na, const double* b, int64_t nb) { return a < b + nb && b < a + na; }
+
+// the basis vectors can be read 16 bytes at a time on w's pair grid: V shares w's alignment and so does every V + g * ld
+static bool owned_basis_aligned(const double* w, const double* V, int64_t nvec, int64_t ld) {
+  return owned_same_alignment(w, V) && (nvec == 1 || ld % 2 == 0);
+}
+
+#define OWNED_GROUP_SWITCH(g, CALL) \
+  switch (g) {                      \
+    case 1: CALL(1); break;         \
+    case 2: CALL(2); break;         \
+    case 3: CALL(3); break;         \
+    case 4: CALL(4); break;         \
+    case 5: CALL(5); break;         \
+    case 6: CALL(6); break;         \
+    case 7: CALL(7); break;         \
+    default: CALL(8); break;        \
+  }
+
+template <int G>
+static void launch_owned_multi_dot(aggmg_ctx* ctx, const OwnedRanges& R, bool vec, const double* w, const double* V, int64_t ld,
+                                   double* part) {
+  const dim3 grid(kOwnedBlocks, (unsigned)R.n);
+  if (vec)
+    hipLaunchKernelGGL((owned_multi_dot_partial_kernel<G, true>), grid, dim3(kThreads), 0, ctx->stream, R, owned_parity(w), w, V, ld,
+                       part, kOwnedPartStride);
+  else
+    hipLaunchKernelGGL((owned_multi_dot_partial_kernel<G, false>), grid, dim3(kThreads), 0, ctx->stream, R, owned_parity(w), w, V, ld,
+                       part, kOwnedPartStride);
+}
+
+template <int G>
+static void launch_owned_multi_axpy(aggmg_ctx* ctx, int64_t n, const OwnedRanges& R, bool vec, double* w, const double* V, int64_t ld,
+                                    const OwnedCoefs& c, double* part) {
+  const dim3 grid(kOwnedBlocks), block(kThreads);
+  const int par = owned_parity(w);
+  if (vec && part)
+    hipLaunchKernelGGL((owned_multi_axpy_kernel<G, true, true>), grid, block, 0, ctx->stream, n, par, w, V, ld, c, R, part);
+  else if (vec)
+    hipLaunchKernelGGL((owned_multi_axpy_kernel<G, true, false>), grid, block, 0, ctx->stream, n, par, w, V, ld, c, R, part);
+  else if (part)
+    hipLaunchKernelGGL((owned_multi_axpy_kernel<G, false, true>), grid, block, 0, ctx->stream, n, par, w, V, ld, c, R, part);
+  else
+    hipLaunchKernelGGL((owned_multi_axpy_kernel<G, false, false>), grid, block, 0, ctx->stream, n, par, w, V, ld, c, R, part);
+}
+
+static int owned_multi_args(aggmg_ctx* ctx, const char* who, const double* V, int64_t nvec, const double* w, const void* host) {
+  if (!V || !w || !host) return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": NULL argument");
+  if (nvec < 1 || nvec > kOwnedMaxVec)
+    return fail(ctx, AGGMG_ERR_ARGUMENT, std::string(who) + ": needs 1 <= nvec <= " + std::to_string(kOwnedMaxVec));
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_owned_multi_dot_dev(aggmg_ctx* ctx, const double* V, int64_t nvec, int64_t ld, const double* w, int nranges,
+                                         const int64_t* lo, const int64_t* hi, double* out_host) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  CHECK(owned_multi_args(ctx, "aggmg_owned_multi_dot_dev", V, nvec, w, out_host));
+  HIPCHK(hipSetDevice(ctx->device));
+  OwnedRanges R;
+  CHECK(owned_ranges(ctx, "aggmg_owned_multi_dot_dev", nranges, lo, hi, -1, &R));
+  // (the call takes no vector length: the rows it reads end at the largest hi)
+  int64_t n = 0;
+  for (int g = 0; g < nranges; ++g) n = std::max(n, hi[g]);
+  if (ld < n) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_owned_multi_dot_dev: ld must reach the end of the last range");
+  if (owned_overlap(V, (nvec - 1) * ld + n, w, n))
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_owned_multi_dot_dev: w must not overlap V");
+  if (nranges == 0) {
+    for (int64_t i = 0; i < nvec; ++i) out_host[i] = 0.0;
+    return AGGMG_OK;
+  }
+  CHECK(owned_multi_buffers(ctx));
+  double* part = ctx->own_multi_part;
+  double* sc = part + kOwnedMultiScalars;
+  const bool vec = owned_basis_aligned(w, V, nvec, ld);
+  for (int64_t i0 = 0; i0 < nvec; i0 += kOwnedGroup) {
+    const int g = (int)std::min<int64_t>(kOwnedGroup, nvec - i0);
+#define OWNED_CALL(G) launch_owned_multi_dot<G>(ctx, R, vec, w, V + i0 * ld, ld, part + i0 * kOwnedPartStride)
+    OWNED_GROUP_SWITCH(g, OWNED_CALL)
+#undef OWNED_CALL
+  }
+  hipLaunchKernelGGL(owned_multi_final_kernel, dim3((unsigned)nvec), dim3(kThreads), 0, ctx->stream, kOwnedBlocks * nranges,
+                     (const double*)part, kOwnedPartStride, sc);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out_host, sc, (size_t)nvec * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_owned_multi_axpy_norm_dev(aggmg_ctx* ctx, int64_t n, const double* V, int64_t nvec, int64_t ld,
+                                               const double* coef_host, double* w_inout, int nranges, const int64_t* lo,
+                                               const int64_t* hi, double* sumsq_out_host) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  CHECK(owned_multi_args(ctx, "aggmg_owned_multi_axpy_norm_dev", V, nvec, w_inout, coef_host));
+  if (n < 0 || ld < n) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_owned_multi_axpy_norm_dev: needs 0 <= n <= ld");
+  if (owned_overlap(V, (nvec - 1) * ld + n, w_inout, n))
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_owned_multi_axpy_norm_dev: w must not overlap V");
+  HIPCHK(hipSetDevice(ctx->device));
+  OwnedRanges R;
+  CHECK(owned_ranges(ctx, "aggmg_owned_multi_axpy_norm_dev", nranges, lo, hi, n, &R));
+  CHECK(owned_multi_buffers(ctx));
+  double* part = ctx->own_multi_part;          // (the update's kOwnedBlocks sums take the first dot's place)
+  double* sc = part + kOwnedMultiScalars + kOwnedMaxVec;
+  const bool vec = owned_basis_aligned(w_inout, V, nvec, ld);
+  for (int64_t i0 = 0; i0 < nvec; i0 += kOwnedGroup) {
+    const int g = (int)std::min<int64_t>(kOwnedGroup, nvec - i0);
+    OwnedCoefs c;
+    for (int k = 0; k < kOwnedGroup; ++k) c.c[k] = k < g ? coef_host[i0 + k] : 0.0;
+    double* p = (sumsq_out_host && i0 + g == nvec) ? part : nullptr;   // the pass that stores the final values sums them
+#define OWNED_CALL(G) launch_owned_multi_axpy<G>(ctx, n, R, vec, w_inout, V + i0 * ld, ld, c, p)
+    OWNED_GROUP_SWITCH(g, OWNED_CALL)
+#undef OWNED_CALL
+  }
+  HIPCHK(hipGetLastError());
+  if (!sumsq_out_host) return AGGMG_OK;        // (the coefficients travelled by value: nothing of the caller's is read later)
+  hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, kOwnedBlocks, (const double*)part, sc, 0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(sumsq_out_host, sc, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return AGGMG_OK;
+}
+
+extern "C" int aggmg_div_scalar_dev(aggmg_ctx* ctx, int64_t n, const double* w, double s, double* v) {
+  if (!ctx) return AGGMG_ERR_ARGUMENT;
+  if (!w || !v || n < 0) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_div_scalar_dev: bad argument");
+  if (s == 0.0 || !std::isfinite(s)) return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_div_scalar_dev: the divisor must be finite and not 0");
+  if (w != v && owned_overlap(w, n, v, n))
+    return fail(ctx, AGGMG_ERR_ARGUMENT, "aggmg_div_scalar_dev: v must be w itself or not overlap it");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (owned_same_alignment(w, v))
+    hipLaunchKernelGGL(owned_div_kernel<true>, dim3(kOwnedBlocks), dim3(kThreads), 0, ctx->stream, n, owned_parity(w), w, s, v);
+  else
+    hipLaunchKernelGGL(owned_div_kernel<false>, dim3(kOwnedBlocks), dim3(kThreads), 0, ctx->stream, n, owned_parity(w), w, s, v);
+  HIPCHK(hipGetLastError());
+  return AGGMG_OK;
+}

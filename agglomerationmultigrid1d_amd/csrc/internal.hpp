@@ -127,6 +127,10 @@ struct aggmg_ctx {
   // owned-range reductions of the partitioned conjugate-gradient loop (aggmg_owned_dot_dev, aggmg_pcg_xr_owned_dev):
   // kOwnedBlocks partial sums per range, then the scalar; lazy, freed with the context
   DevArray<double> own_part;
+  // the same for the partitioned flexible GMRES loop (aggmg_owned_multi_dot_dev, aggmg_owned_multi_axpy_norm_dev): the
+  // partial sums of up to 65 dots (kOwnedBlocks per range each), 65 dots and one sum of squares; a buffer of its own, so
+  // that own_part stays as the conjugate-gradient entry points read it; lazy (2.1 MB), freed with the context
+  DevArray<double> own_multi_part;
   // host <-> device staging of the host-pointer entry points (aggmg_vcycle): per worker thread a stream and two
   // pinned chunks (HostStager in aggmg_hip.hip); allocated on first use
   struct StageLane {

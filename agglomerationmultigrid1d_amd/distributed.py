@@ -303,6 +303,14 @@ class CgRankLayout:
 # ------------------------------------------------------------------------------------------
 # communicator (torch.distributed; device tensors for nccl, host staging for gloo)
 # ------------------------------------------------------------------------------------------
+def _rank_order_sum(rows):
+    """rows[r]: rank r's vector -> rows[0] + rows[1] + ... added in that order, entry by entry"""
+    acc = np.array(rows[0], dtype=np.float64)
+    for r in range(1, len(rows)):
+        acc = acc + rows[r]
+    return acc
+
+
 class Comm:
     def __init__(self, world, rank, staged=False):
         import torch
@@ -346,6 +354,22 @@ class Comm:
         o = self.torch.empty(self.world, dtype=self.torch.float64, device=t.device)
         self.dist.all_gather_into_tensor(o, t)
         return float(np.sum(np.asarray(o.cpu().tolist())))
+
+    def sum_vec(self, values):
+        """elementwise sum over ranks of a short float64 vector -> NumPy vector: ONE all-gather, then the ranks' vectors
+        added in rank order by an explicit loop (_rank_order_sum), so that every rank holds the same bits whatever way
+        np.sum would block the additions.  (sum() keeps its np.sum: up to 7 ranks that is this very chain, on 8 NumPy adds
+        the eight terms as a tree.)"""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        if self.world == 1:
+            return v.copy()
+        on_dev = (not self.staged) and self.dist.get_backend() == "nccl"
+        t = self.torch.from_numpy(v.copy())
+        if on_dev:
+            t = t.cuda()
+        o = self.torch.empty(self.world * v.size, dtype=self.torch.float64, device=t.device)
+        self.dist.all_gather_into_tensor(o, t)
+        return _rank_order_sum(o.cpu().numpy().reshape(self.world, v.size))
 
     def min_int(self, value, device=None):
         """minimum over ranks of a small integer (agreement on a route before the first collective)"""
@@ -434,6 +458,10 @@ class ThreadComm(Comm):
 
     def sum(self, value):
         return float(np.sum(np.asarray(self._exchange(float(value)))))
+
+    def sum_vec(self, values):
+        v = np.array(values, dtype=np.float64).reshape(-1)
+        return _rank_order_sum(np.stack(self._exchange(v)))
 
     def host_all_gather(self, s):
         return np.concatenate(self._exchange(np.array(s, copy=True)))
@@ -943,6 +971,52 @@ class HipEngine:
     def assign(self, dst, src):
         self.copy_segments([(dst, src)])
 
+    # ---- flexible GMRES around the partitioned cycle (fgmres): the basis block and the passes over it, library stream ----
+    def new_basis(self, nvec, n):
+        """nvec zeroed local vectors of n rows as the rows of one (nvec, ld) tensor; ld even, so that every vector sits at
+        the block's own offset from a 16-byte boundary (the one engine.new's vectors have) and the fused passes read all
+        of them 16 bytes at a time"""
+        return self.torch.zeros((int(nvec), int(n) + (int(n) & 1)), dtype=self.torch.float64, device=self.dev)
+
+    def _basis(self, V, nvec, w, who):
+        if V.dim() != 2 or V.stride(1) != 1 or not (1 <= nvec <= V.shape[0]) or V.shape[1] < w.numel():
+            raise ValueError(f"{who}: V holds its vectors as rows of at least len(w) entries, nvec of them")
+        return int(V.stride(0)) if V.shape[0] > 1 else int(V.shape[1])
+
+    def owned_multi_dot(self, ranges, V, nvec, w):
+        """-> NumPy vector: entry i the sum over the local rows in `ranges` of V[i] w, i < nvec, one pass over w per group
+        of 8 vectors and one read-back (aggmg_owned_multi_dot_dev); entry i has the bits of owned_dot(ranges, w, V[i])"""
+        c = self.ctx
+        ld = self._basis(V, nvec, w, "owned_multi_dot")
+        k, lo, hi = self._ranges(ranges, w.numel())
+        out = np.zeros(int(nvec))
+        c.check(c.lib.aggmg_owned_multi_dot_dev(c.handle, _p(V), int(nvec), ld, _p(w), k, lo, hi,
+                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return out
+
+    def owned_multi_axpy_norm(self, ranges, V, nvec, coef, w, sumsq=True):
+        """w += sum_i coef[i] V[i] on the whole local vector (an fma chain, ascending i); sumsq: -> the sum over `ranges`
+        of the squares of the stored values, from the pass that stores them (aggmg_owned_multi_axpy_norm_dev); else the
+        call only enqueues and returns None"""
+        c = self.ctx
+        ld = self._basis(V, nvec, w, "owned_multi_axpy_norm")
+        k, lo, hi = self._ranges(ranges, w.numel())
+        cf = np.ascontiguousarray(coef, dtype=np.float64)
+        if cf.shape != (int(nvec),):
+            raise ValueError("owned_multi_axpy_norm: one coefficient per vector")
+        out = ctypes.c_double(0.0)
+        c.check(c.lib.aggmg_owned_multi_axpy_norm_dev(c.handle, w.numel(), _p(V), int(nvec), ld,
+                                                      cf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _p(w), k, lo, hi,
+                                                      ctypes.byref(out) if sumsq else None))
+        return out.value if sumsq else None
+
+    def div_scalar(self, w, s, v):
+        """v = w / s on the local vectors (aggmg_div_scalar_dev): a division, s a host scalar"""
+        c = self.ctx
+        if w.numel() != v.numel():
+            raise ValueError("div_scalar: vectors of one length")
+        c.check(c.lib.aggmg_div_scalar_dev(c.handle, w.numel(), _p(w), float(s), _p(v)))
+
     def down(self, x0, b, nPre, alpha):
         self.H.vcycle_down_dev(x0, b, nPre, alpha)
 
@@ -1162,6 +1236,157 @@ def pcg(dv, b, x0=None, maxiter=50, tol=1e-10, nPre=3, nPost=3, alpha=2.0 / 3.0)
         rz_new = c.sum(e.owned_dot(own, r, z))
         e.pcg_p(p, z, rz_new / rz)
         rz = rz_new
+    sync()
+    return x, len(res), res
+
+
+FGMRES_MAX_RESTART = 64      # == AGGMG_FGMRES_MAX_RESTART (include/aggmg_hip.h)
+
+
+class HostGmres:
+    """The small dense part of one restart cycle of GMRES on the host: csrc/host_gmres.hpp restated line for line (the
+    partitioned loop below is Python, so its least-squares object is too).  Columns of the Hessenberg matrix arrive one
+    at a time and are kept in triangular form by Givens rotations; after column j, |g_{j+1}| is the residual norm of
+    min_y || beta e_1 - Hbar_j y ||_2, and y comes from one back-substitution when the cycle ends."""
+
+    kMaxRestart = FGMRES_MAX_RESTART
+
+    def __init__(self):
+        m = self.kMaxRestart
+        self.k = 0
+        self.r = [[0.0] * (m + 1) for _ in range(m)]       # r[column][row]: the rotated columns
+        self.c = [0.0] * m
+        self.s = [0.0] * m
+        self.g = [0.0] * (m + 1)
+
+    def start(self, beta):
+        """a new cycle: g = beta e_1, no columns"""
+        self.k = 0
+        self.g[0] = float(beta)
+
+    def size(self):
+        return self.k
+
+    def push(self, h):
+        """column j = size(): h[0 .. j] the projections, h[j + 1] the sub-diagonal entry -> |g_{j+1}|"""
+        j = self.k
+        r = self.r[j]
+        for i in range(j + 2):
+            r[i] = float(h[i])
+        for i in range(j):                                 # the rotations of the earlier columns
+            a, b = r[i], r[i + 1]
+            r[i] = self.c[i] * a + self.s[i] * b
+            r[i + 1] = self.c[i] * b - self.s[i] * a
+        a, b = r[j], r[j + 1]
+        d = float(np.hypot(a, b))                          # (the C library's hypot, as std::hypot: math.hypot is another)
+        if d == 0.0:      # a zero column below the rotations: nothing to rotate (the back-substitution will divide by 0)
+            self.c[j], self.s[j] = 1.0, 0.0
+        else:
+            self.c[j], self.s[j] = a / d, b / d
+        r[j] = d
+        r[j + 1] = 0.0
+        self.g[j + 1] = -self.s[j] * self.g[j]
+        self.g[j] = self.c[j] * self.g[j]
+        self.k = j + 1
+        return abs(self.g[self.k])
+
+    def solve(self):
+        """-> y[0 .. size() - 1] = argmin || beta e_1 - Hbar y ||: back-substitution on the triangular factor"""
+        k = self.k
+        y = [0.0] * k
+        for i in range(k - 1, -1, -1):
+            t = self.g[i]
+            for l in range(i + 1, k):
+                t -= self.r[l][i] * y[l]
+            with np.errstate(divide="ignore", invalid="ignore"):       # (IEEE division as in C++: inf / nan, no exception)
+                y[i] = float(np.float64(t) / np.float64(self.r[i][i]))
+        return y
+
+
+def fgmres(dv, b, x0=None, restart=30, maxiter=200, tol=1e-10, nPre=3, nPost=3, alpha=2.0 / 3.0):
+    """Right-preconditioned flexible GMRES(restart) on an element-partitioned hierarchy, preconditioned by one partitioned
+    V-cycle from a zero guess.  EXTENSION: the recurrence of the single-GPU fgmres (C ABI aggmg_fgmres_dev), operation for
+    operation, with every global scalar the rank-ordered sum (comm.sum_vec) of the ranks' owned terms: all ranks hold the
+    same bits and take the same branch.  The Krylov loop for partitioned cycles that are NOT symmetric -- hybrid
+    element-patch levels, nPre != nPost, sweep-weight schedules whose post half is not the pre half reversed -- where pcg
+    returns a wrong answer or refuses.
+
+    Per restart cycle: x's ghosts are exchanged, r = b - A x (owned rows exact), beta = sqrt(sum of the owned r.r); the
+    loop ends there when beta == 0, beta < tol ||b|| or beta is not finite (at entry: 0 iterations, x untouched);
+    v_0 = r / beta.  Per iteration j: v_j's ghosts are exchanged (the cycle reads its right-hand side on the whole local
+    domain), z_j = M^-1 v_j, z_j's ghosts are exchanged, w = -A z_j (the Arnoldi relation is kept for -A, as on one GPU,
+    and the correction is x -= Z y), h = sum_vec(V[:j+1]' w over the owned rows) in one fused pass, w -= V h with the
+    owned sum of squares from the same pass, h_{j+1,j} = sqrt of its rank sum, the column goes through the Givens
+    rotations on the host (HostGmres), res[it] = |g_{j+1}|, v_{j+1} = w / h_{j+1,j}.  It stops when res < tol ||b||, at
+    maxiter (the last restart cycle is cut), when h_{j+1,j} == 0 (nothing is divided), or at an entry that is not finite
+    (x then keeps the value of the last finished restart cycle).
+
+    dv: DistributedVCycle or NativeDistributedVCycle.  b, x0: local vectors (owned + ghosts); b valid on the whole local
+    domain; x0 (None: zeros; its ghosts may be anything) is not modified.  -> (x local vector whose owned part is the
+    iterate, iterations, res list); maxiter <= 0 returns a copy of the start vector, 0 and [].  Cost per iteration beside
+    the cycle's own three exchanges: TWO interface exchanges (v_j, z_j) and TWO scalar all-gathers (h; ||w||^2), plus one
+    exchange and one all-gather per restart cycle.  Work space: 2 restart + 2 local vectors per rank (V: restart + 1, Z:
+    restart, w) beside x and a zero vector.  ValueError, on every rank alike and before any collective: restart outside
+    1 .. 64, sweep counts above the layout's halo widths.  No N x K form and no `err` history."""
+    e, L, c = dv.e, dv.L, dv.c
+    restart = int(restart)
+    if not 1 <= restart <= FGMRES_MAX_RESTART:
+        raise ValueError(f"fgmres: restart must be 1 .. {FGMRES_MAX_RESTART}")
+    if nPre > L.nPre or nPost > L.nPost:
+        raise ValueError("halo widths were sized for fewer sweeps")
+    own = L.owned_ranges(0)
+    n = L.local_dofs(0)
+    on_gpu = hasattr(e, "torch") and e.torch.cuda.is_available()
+    sync = e.torch.cuda.synchronize if on_gpu else (lambda: None)
+    sync()                         # (x0 / b may have been filled on torch's stream just now)
+    x = e.new(n)
+    if maxiter <= 0:
+        sync()
+        if x0 is not None:
+            e.assign(x, x0)
+            sync()
+        return x, 0, []
+    w, zero = e.new(n), e.new(n)
+    Vb, Zb = e.new_basis(restart + 1, n), e.new_basis(restart, n)
+    V = [Vb[j][:n] for j in range(restart + 1)]          # the basis vectors as local vectors (a row may be one longer)
+    Z = [Zb[j][:n] for j in range(restart)]
+    sync()                         # torch zero-filled the new vectors on ITS stream; the library may run on its own
+    if x0 is not None:
+        e.assign(x, x0)
+    nb = float(np.sqrt(c.sum_vec([e.owned_dot(own, b, b)])[0]))
+    ls = HostGmres()
+    res, done = [], False
+    while not done and len(res) < maxiter:
+        dv.exchange_ghosts(x)
+        e.residual(x, b, w)                                # every cycle starts from r = b - A x
+        beta = float(np.sqrt(c.sum_vec([e.owned_dot(own, w, w)])[0]))
+        if beta == 0.0 or beta < tol * nb or not np.isfinite(beta):
+            break                                          # (at entry: x untouched, 0 iterations)
+        e.div_scalar(w, beta, V[0])                        # v_0 = r / beta
+        ls.start(beta)
+        length = min(restart, int(maxiter) - len(res))
+        finite = True
+        for j in range(length):
+            dv.exchange_ghosts(V[j])
+            dv.vcycle(zero, V[j], Z[j], nPre, nPost, alpha, x0_ghosts_valid=True)      # z_j = M^-1 v_j
+            dv.exchange_ghosts(Z[j])
+            e.neg_apply(Z[j], w)                                                       # w = -A z_j
+            h = c.sum_vec(e.owned_multi_dot(own, Vb, j + 1, w))                        # h = V' w
+            hn = float(np.sqrt(c.sum_vec([e.owned_multi_axpy_norm(own, Vb, j + 1, -h, w)])[0]))     # w -= V h; ||w||
+            r = float(ls.push(list(h) + [hn]))
+            res.append(r)
+            if not np.isfinite(r):
+                finite, done = False, True
+                break
+            if r < tol * nb or hn == 0.0:                  # converged, or the Krylov space is exhausted (no division by 0)
+                done = True
+                break
+            if j + 1 < length:
+                e.div_scalar(w, hn, V[j + 1])
+        if not finite:
+            break                                          # (x keeps the value of the last finished cycle)
+        y = ls.solve()
+        e.owned_multi_axpy_norm(own, Zb, ls.size(), -np.asarray(y), x, sumsq=False)    # x += Z y (for -A: -=)
     sync()
     return x, len(res), res
 

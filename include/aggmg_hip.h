@@ -1083,6 +1083,31 @@ int aggmg_pcg_xr_owned_dev(aggmg_ctx* ctx, int64_t n, double* x, double* r, cons
                            int nranges, const int64_t* lo, const int64_t* hi, double* rr_out);
 /* p = z + beta p on n rows.  Asynchronous. */
 int aggmg_pcg_p_dev(aggmg_ctx* ctx, int64_t n, double* p, const double* z, double beta);
+/* ---- flexible GMRES around the element-partitioned cycle (EXTENSION: aggmg_fgmres_dev's recurrence with every global
+ * scalar a rank-ordered sum of the ranks' owned terms -- the Krylov loop for partitioned cycles that are not symmetric:
+ * hybrid element-patch levels, nPre != nPost).  The passes of its orthogonalisation over a device basis V (vector i at
+ * V + i * ld, 1 <= nvec <= AGGMG_FGMRES_MAX_RESTART + 1) and a local device vector w, with the owned rows given as for
+ * aggmg_owned_dot_dev.  Fixed slices, strides and summation trees, no atomics: the same bits from run to run, and the
+ * same bits whether or not the basis vectors share w's offset from a 16-byte boundary (an odd ld walks the same pairs
+ * with 8-byte accesses).  AGGMG_ERR_ARGUMENT, before anything is enqueued: NULL, nvec outside 1 .. 65, ld smaller than
+ * the rows read, more than 4 ranges, a bad range or overlapping ranges, w overlapping V. ---- */
+/* out_host[i] = sum over the ranges of V_i[r] w[r], i < nvec: one pass over w per group of 8 vectors, one launch that
+ * finishes all sums, one read-back; synchronous.  Entry i is bit for bit aggmg_owned_dot_dev(w, V_i) on the same ranges
+ * (w first: its address fixes the pair grid).  As there, the call takes no vector length: every range must lie inside w
+ * and every V_i; ld must reach the end of the last range. */
+int aggmg_owned_multi_dot_dev(aggmg_ctx* ctx, const double* V, int64_t nvec, int64_t ld, const double* w, int nranges,
+                              const int64_t* lo, const int64_t* hi, double* out_host);
+/* w[r] <- fma(c[nvec-1], V_{nvec-1}[r], ... fma(c[0], V_0[r], w[r])) on all n local rows (ascending i, in place, groups
+ * of 8, one pass over w per group; rows >= n are not touched; ld >= n): the values aggmg_multi_axpy_norm_dev stores.
+ * *sumsq_out_host (may be NULL) receives the sum over the ranges of the squares of the stored values, formed by the
+ * pass that stores them -- NOT its root: the caller adds the ranks' sums first.  Synchronous with it; without it the
+ * call only enqueues (coef_host has been read when it returns). */
+int aggmg_owned_multi_axpy_norm_dev(aggmg_ctx* ctx, int64_t n, const double* V, int64_t nvec, int64_t ld, const double* coef_host,
+                                    double* w_inout, int nranges, const int64_t* lo, const int64_t* hi, double* sumsq_out_host);
+/* v[r] = w[r] / s on n rows: a division, not a multiplication by the reciprocal (v_{j+1} = w / h_{j+1,j} as
+ * aggmg_fgmres_dev forms it); s arrives by value because the global norm is on the host after the sum over the ranks.
+ * v may be w itself.  Asynchronous.  AGGMG_ERR_ARGUMENT: NULL, n < 0, s == 0 or not finite, v overlapping w partly. */
+int aggmg_div_scalar_dev(aggmg_ctx* ctx, int64_t n, const double* w, double s, double* v);
 /* aggmg_multigrid_dev on K right-hand sides: check_every K-column cycles, then the K-column residual and the column
  * norms, column j stopping when ||b_j - A x_j|| < tol ||b_j||.  Column j of X and n_cycles[j] / n_checks[j] are
  * bit for bit aggmg_multigrid_dev's on column j; res_hist[j * n_checks_max + i] (and err_hist, ||x_j - U_exact[:, j]||,
