@@ -1406,6 +1406,33 @@ def _replicated_coarse_hierarchy(Ac, ctx, world):
             ctx.set_option(_lib.OPT_COARSE_CHUNK_LOG2, 12)
 
 
+def gathered_coarse_hierarchy(sub, diag, sup, ctx, comm):
+    """The replicated one-level hierarchy of the GLOBAL coarsest operator from every rank's OWNED block rows: sub, diag,
+    sup (owned blocks, m, m) -- the blocks (k, k - 1), (k, k), (k, k + 1) of this rank's owned coarsest elements, the
+    same number on every rank -- are stacked, all-gathered through `comm`, concatenated in rank order and uploaded
+    (block_tridiag_to_csc, DeviceOperator, _replicated_coarse_hierarchy).  The first / last owned block row of a rank
+    couples to a ghost column that exists locally unless the rank sits at the domain boundary, where the block is zero
+    anyway.  The tail of build_local_uniform and build_local_cg."""
+    import torch
+    from . import _lib
+    from .api import DeviceOperator
+    from .uniform import block_tridiag_to_csc, _csc
+    sub, diag, sup = (np.ascontiguousarray(x, dtype=np.float64) for x in (sub, diag, sup))
+    no, mc = diag.shape[0], diag.shape[1]
+    mine = torch.from_numpy(np.stack([sub, diag, sup]).reshape(-1))
+    dev = torch.device("cuda", ctx.device) if (comm.world > 1 and not comm.staged and
+                                                comm.dist.get_backend() == "nccl") else None
+    if dev is not None:
+        mine = mine.to(dev)
+    allb = torch.empty(mine.numel() * comm.world, dtype=torch.float64, device=mine.device)
+    comm.all_gather(allb, mine)
+    allb = allb.cpu().numpy().reshape(comm.world, 3, no, mc, mc)
+    gsub, gdiag, gsup = (np.concatenate([allb[r, i] for r in range(comm.world)]) for i in range(3))
+    colptr, rowval, nzval, N = block_tridiag_to_csc(gsub, gdiag, gsup)
+    Ac = DeviceOperator(_csc(colptr, rowval, nzval, (N, N)), _lib.OP_STIFFNESS, ctx)
+    return _replicated_coarse_hierarchy(Ac, ctx, comm.world)
+
+
 def build_local_uniform(n, p, pAgg, ratios, layout, ctx, comm, smoother="blockJac"):
     """Local operators of this rank for the uniform model problem, uploaded through the CSC
     boundary, plus the global coarsest operator assembled from every rank's owned block rows.
@@ -1415,11 +1442,10 @@ def build_local_uniform(n, p, pAgg, ratios, layout, ctx, comm, smoother="blockJa
     in rows of the outermost ghost element, inside the consumed margin).  The layout must have been sized for the
     smoother list (RankLayout(..., smoothers=smoother_kinds(smoother, len(ratios)))): ValueError otherwise.
     -> (HipEngine, U_local)"""
-    import torch
     from . import _lib
     from .api import (BlockGaussSeidel, BlockJacobi, DeviceOperator, ElementPatchGaussSeidel, ElementPatchSchwarz,
                       MeshHierarchy)
-    from .uniform import UniformDgAggHierarchy, block_tridiag_to_csc, _csc
+    from .uniform import UniformDgAggHierarchy
     kinds = smoother_kinds(smoother, len(layout.ratios))
     if smoother not in ("blockJac", "blockGS"):
         need = halo_widths(layout.ratios, layout.nPre, layout.nPost, smoothers=kinds)
@@ -1451,22 +1477,7 @@ def build_local_uniform(n, p, pAgg, ratios, layout, ctx, comm, smoother="blockJa
     nc = nl - 1
     gl, _ = layout.ghosts(nc)
     no = layout.own[nc][1] - layout.own[nc][0]
-    mc = layout.m[nc]
-    sub, diag, sup = (np.ascontiguousarray(x[gl:gl + no]) for x in U.levels[nc]['A'])
-    # the first / last owned block row of a rank couples to a ghost column that exists locally
-    # unless the rank sits at the domain boundary, where the block is zero anyway
-    mine = torch.from_numpy(np.stack([sub, diag, sup]).reshape(-1))
-    dev = torch.device("cuda", ctx.device) if (comm.world > 1 and not comm.staged and
-                                                comm.dist.get_backend() == "nccl") else None
-    if dev is not None:
-        mine = mine.to(dev)
-    allb = torch.empty(mine.numel() * comm.world, dtype=torch.float64, device=mine.device)
-    comm.all_gather(allb, mine)
-    allb = allb.cpu().numpy().reshape(comm.world, 3, no, mc, mc)
-    gsub, gdiag, gsup = (np.concatenate([allb[r, i] for r in range(comm.world)]) for i in range(3))
-    colptr, rowval, nzval, N = block_tridiag_to_csc(gsub, gdiag, gsup)
-    Ac = DeviceOperator(_csc(colptr, rowval, nzval, (N, N)), _lib.OP_STIFFNESS, ctx)
-    Hc = _replicated_coarse_hierarchy(Ac, ctx, comm.world)
+    Hc = gathered_coarse_hierarchy(*(x[gl:gl + no] for x in U.levels[nc]['A']), ctx, comm)
     return HipEngine(H, Hc, ctx), U
 
 
@@ -1476,11 +1487,10 @@ def build_local_cg(n, ps, layout, ctx, comm, smoother=None):
     (DG p=0) operator assembled from every rank's owned rows.  smoother: cg_smoother's kinds 'jac' (default: the
     layout's), 'addSchwarz', 'hybridSchwarz' (src/smoother.jl:88-139) or the 'blockGS' extension -- the layout must
     have been sized for it (CgRankLayout(..., smoother=)).  -> (HipEngine, U_local)"""
-    import torch
     from . import _lib
     from .api import (AdditiveSchwarzSmoother, BlockGaussSeidel, DeviceOperator, HybridSchwarzSmoother, JacobiSmoother,
                       MeshHierarchy)
-    from .uniform import UniformCgDgHierarchy, block_tridiag_to_csc, _csc
+    from .uniform import UniformCgDgHierarchy
     smoother = smoother or getattr(layout, "smoother", "jac")
     if CgRankLayout.SWEEP_REACH[smoother] > CgRankLayout.SWEEP_REACH[getattr(layout, "smoother", "jac")]:
         raise ValueError(f"the layout's ghost layers were sized for {layout.smoother!r} sweeps, not {smoother!r}")
@@ -1499,19 +1509,7 @@ def build_local_cg(n, ps, layout, ctx, comm, smoother=None):
     nc = nl - 1
     gl, _ = layout.ghosts(nc)
     no = layout.own[nc][1] - layout.own[nc][0]
-    sub, diag, sup = (np.ascontiguousarray(x[gl:gl + no]) for x in U.dg0.levels[0]['A'])
-    mine = torch.from_numpy(np.stack([sub, diag, sup]).reshape(-1))
-    dev = torch.device("cuda", ctx.device) if (comm.world > 1 and not comm.staged and
-                                                comm.dist.get_backend() == "nccl") else None
-    if dev is not None:
-        mine = mine.to(dev)
-    allb = torch.empty(mine.numel() * comm.world, dtype=torch.float64, device=mine.device)
-    comm.all_gather(allb, mine)
-    allb = allb.cpu().numpy().reshape(comm.world, 3, no, 1, 1)
-    gsub, gdiag, gsup = (np.concatenate([allb[r, i] for r in range(comm.world)]) for i in range(3))
-    colptr, rowval, nzval, N = block_tridiag_to_csc(gsub, gdiag, gsup)
-    Ac = DeviceOperator(_csc(colptr, rowval, nzval, (N, N)), _lib.OP_STIFFNESS, ctx)
-    Hc = _replicated_coarse_hierarchy(Ac, ctx, comm.world)
+    Hc = gathered_coarse_hierarchy(*(x[gl:gl + no] for x in U.dg0.levels[0]['A']), ctx, comm)
     return HipEngine(H, Hc, ctx), U
 
 

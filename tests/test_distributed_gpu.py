@@ -1,7 +1,9 @@
 """N > 1 path with the real HIP engine: two ranks sharing the one GPU of the test box, `gloo`
 process group with host-staged collectives (RCCL needs one device per rank, so the nccl backend
 itself can only run on the multi-GPU node).  Owned results must equal the single-GPU V-cycle of
-the same library to the last bits and the oracle within tolerance."""
+the same library to the last bits.  No test here calls the oracle, and every operator comes from the
+uniform generator, whose interior elements all carry the same record: the partitioned cycle against
+the oracle, on meshes with unequal elements, is tests/test_gpu_distributed_nonuniform.py."""
 import os
 import sys
 
